@@ -3,7 +3,7 @@
 BASELINE.json (config C2: B = 4096 live-point draws against one pixel, NH3 (1,1)+(2,2), 1024
 channels each, 2 velocity components, get_irdc_priors).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (prior transform -> model spectra -> chi^2) over one batch of
 B unit-cube rows against one map pixel.  The pixels are those of BASELINE config C3 (a synthetic
@@ -13,19 +13,33 @@ it in HBM and walks it, one pixel per step.  Per-GPU work is fixed (weak scaling
 data-path collective: the ranks only meet in the barrier / max-time reduction around a timed block
 and in the end-of-run gather of per-pixel records (RCCL through the engine's C ABI, no torch).
 
+The headline (`value`, `ms_per_step`) is one run of W warm-up steps and then exactly K timed steps in `--exp-mode`
+(the table mode by default), between barrier + device synchronisation; `ms_per_step` = the slowest rank's time / K.
+Every timed step has unit-cube rows of its own in HBM; a run of more than CHUNK_STEPS steps gets fresh rows between
+chunks of that many steps, outside the clock.  `--dump-outputs DIR` writes what the last timed step returned to its
+caller: `lnL.npy` (B log-likelihoods) and `theta.npy` (the B x ndim physical parameters the pass wrote over its
+unit-cube rows), float64, per rank r > 0 as `lnL_rank<r>.npy` / `theta_rank<r>.npy`.  All inputs are seeded, so the
+same arguments give the same inputs in every run.  A plain run does nothing else.
+
+`--full` adds everything else the benchmark measures (below): the other numerical mode, the repeated timed blocks,
+the one-lane kernel times and roofline, the spectra-out mode, the C4 block, config 5 as specified and the CPU baseline.
+Its figures (`modes`, `roofline`, `configs`, the speed-ups) come from the repeated blocks as they always have; only the top-level `value` / `ms_per_step` are the headline's K-step run.
+
 Every input of a timed block (the unit-cube rows of all its steps, the stripe, the prior tables) is
-resident in HBM before the clock starts.  A timed block is the K-step sequence of `--steps`, repeated back to
+resident in HBM before the clock starts.  A timed block of `--full` is the K-step sequence of `--steps` (at most
+MAX_BLOCK_STEPS steps), repeated back to
 back `repeats_per_block` times (chosen so that a block lasts >= 20 ms whatever K is: K = 20 steps alone are
 0.6 ms, of which the fill and drain of the launch pipeline are 12 %; every repeat works on unit-cube rows of its own)
 between barrier + device synchronisation on both sides; its time is the maximum over ranks and `ms_per_step` =
-block time / (K x repeats).  `--blocks` blocks are timed; `value` is the median block (whole-job evaluations /
-block time), `spread` holds min / max; `k_steps_alone` is the same for blocks of exactly K steps.
+block time / (K x repeats).  `--blocks` blocks are timed; `modes.<mode>.value` is the median block (whole-job
+evaluations / block time), `min` / `max` its spread; `k_steps_alone` is the same for blocks of exactly K steps;
+`modes.<mode>.steps_run` is the headline's run of exactly K timed steps (in the headline's mode).
 Both numerical modes are timed in the same run (`modes`); `value`, `ms_per_step`, `dtype` and `roofline` are the
 TABLE mode's -- the reference's own arithmetic (core/fastexp.c:234-283: float-narrowed argument, f64 product of three
 table entries; models/hyperfine.pyx:93-96: tau summed in f64) --, the fast mode (f32 exponentials, <= 1e-6 on Tb) is
 the `fast_*` keys of `roofline` and `modes.fast`.  `roofline`: algorithmic bytes per launch / the average duration of
 the likelihood kernel, measured live with HIP events on a one-lane runner (launches do not overlap there, so
-the interval is what `rocprofv3 --kernel-trace --stats -- python bench.py --streams 1` reports for
+the interval is what `rocprofv3 --kernel-trace --stats -- python bench.py --full --streams 1` reports for
 the kernel: profiles/r05/); the pipelined rate of the timed blocks is given beside it.
 
 Rank 0 prints ONE JSON line (DESIGN.md "Measurement" explains every field).
@@ -61,7 +75,8 @@ WORKLOADS = {
 }
 PROFILE_DIRS = [ROOT / 'profiles' / 'r05', ROOT / 'profiles' / 'r04', ROOT / 'profiles' / 'r03', ROOT / 'profiles' / 'r02']
 MIN_BLOCK_S = 0.025            # length a timed block is sized for from a lone K-step probe (>= 20 ms in effect)
-MAX_BLOCK_STEPS = 4096
+MAX_BLOCK_STEPS = 4096         # (also the K of --full's repeated blocks when --steps is larger)
+CHUNK_STEPS = 8192             # timed steps of the headline whose unit-cube rows are resident at once (~0.44 MB each at C2)
 # (table mode: launches of two and more units per wave slot -- the engine's coalesced steps -- run as lnl_kernel_queue)
 LNL_KERNEL_NAME = {'fast': 'void lnl_kernel<2, false, false, 2>', 'table': 'void lnl_kernel_queue<false, 2>'}
 OTHER_MODE = {'table': 'fast', 'fast': 'table'}
@@ -325,6 +340,7 @@ class Measure:
         if batch:
             self.B = batch
         self.ndim = 6 * self.ncomp
+        self.k_block = min(args.steps, MAX_BLOCK_STEPS)     # K of the repeated blocks (--full)
         self.per_row = args.pixels_per_step == 'B'
         if self.per_row and side * side // world < self.B:
             raise SystemExit('--pixels-per-step B needs a stripe of at least B pixels')
@@ -405,7 +421,7 @@ class Measure:
         args, comm = self.args, self.comm
         step = step or self.step
         out = []
-        n_timed = args.steps * repeats
+        n_timed = self.k_block * repeats
         for _ in range(n_blocks):
             self.reset_inputs(args.warmup + n_timed)
             for k in range(args.warmup):
@@ -424,13 +440,55 @@ class Measure:
         mine = np.array(out)
         return comm.allreduce(mine, 'max'), comm.allreduce(mine, 'min')
 
+    def steps_run(self, handle):
+        """The headline measurement: --warmup steps, then exactly --steps timed steps, in chunks of at most CHUNK_STEPS
+        steps whose unit-cube rows are resident before the clock starts (a later chunk gets fresh rows in the buffer
+        slots of the first, outside the clock).  {value, ms_per_step, seconds, chunks, rank_ms_per_step, last}: `last`
+        is the buffer slot of the last timed step, whose lnL and theta stay in the buffers."""
+        args, comm = self.args, self.comm
+        n_chunk = min(args.steps, CHUNK_STEPS)
+        self.alloc_inputs(args.warmup + n_chunk)
+        seconds, done, chunks = 0.0, 0, 0
+        while done < args.steps:
+            n = min(n_chunk, args.steps - done)
+            self.reset_inputs(args.warmup + n)
+            if chunks == 0:
+                for k in range(args.warmup):
+                    self.step(handle, k)
+            self.sync(handle)
+            comm.barrier()
+            t0 = time.perf_counter()
+            for k in range(args.warmup, args.warmup + n):
+                self.step(handle, k)
+            self.sync(handle)
+            seconds += time.perf_counter() - t0
+            comm.barrier()
+            done += n
+            chunks += 1
+        slowest = float(comm.allreduce(np.array([seconds]), 'max')[0])
+        fastest = float(comm.allreduce(np.array([seconds]), 'min')[0])
+        out = {'value': args.steps * self.B * self.world / slowest, 'ms_per_step': slowest / args.steps * 1e3,
+               'seconds': slowest, 'chunks': chunks, 'last': args.warmup + n - 1}
+        if self.world > 1:
+            out['rank_ms_per_step'] = {'slowest': slowest / args.steps * 1e3, 'fastest': fastest / args.steps * 1e3}
+        return out
+
+    def last_step_outputs(self, slot):
+        """(lnL [B], theta [B, ndim]) of the step in buffer slot `slot`: what the entry point returned to its caller."""
+        _ffi, lib, buf, B = self._ffi, self.lib, self.buf, self.B
+        lnL = np.empty(B)
+        theta = np.empty((B, self.ndim))
+        _ffi.check(lib.nfa_memcpy_d2h(lnL.ctypes.data_as(C.c_void_p), C.c_void_p(buf['lnL'].value + slot * B * 8), B * 8))
+        _ffi.check(lib.nfa_memcpy_d2h(theta.ctypes.data_as(C.c_void_p), C.c_void_p(buf['U'].value + slot * self.step_bytes),
+                                      self.step_bytes))
+        return lnL, theta
+
     def repeats_for(self, handle, step=None):
         """How often the K-step sequence is repeated inside a timed block so that the block lasts MIN_BLOCK_S: from
         two probe blocks of K steps (the slowest rank's time, so that every rank repeats alike)."""
-        args = self.args
         t, _ = self.timed_blocks(handle, 2, 1, step)
         r = int(np.ceil(MIN_BLOCK_S / float(t.min())))       # (a lone K-step block pays fill and drain: the repeated block runs faster per step, hence the margin in MIN_BLOCK_S)
-        return max(1, min(r, MAX_BLOCK_STEPS // args.steps if args.steps <= MAX_BLOCK_STEPS else 1))
+        return max(1, min(r, MAX_BLOCK_STEPS // self.k_block))
 
     def one_lane_kernel_times(self, spl=1, launch=None):
         """(lnl_kernel us, set-up kernel us, launches) on a one-lane runner: launches do not overlap, a
@@ -475,15 +533,15 @@ class Measure:
         _ffi = self._ffi
         per_mode = {}
         # buffers for the longest block any mode will run: sized from a probe in the fastest mode of the run
-        self.alloc_inputs(args.warmup + args.steps)
+        self.alloc_inputs(args.warmup + self.k_block)
         na.set_exp_mode('fast' if 'fast' in modes else modes[0])
         r_cap = self.repeats_for(self.rh) + 1
-        self.alloc_inputs(args.warmup + max(args.steps * r_cap, min(60, args.warmup + args.steps)))
+        self.alloc_inputs(args.warmup + max(self.k_block * r_cap, min(60, args.warmup + self.k_block)))
         for mode in modes:
             na.set_exp_mode(mode)
             n_blocks = n_blocks_head if mode == head_mode else n_blocks_other
             repeats = min(r_cap, self.repeats_for(self.rh))
-            steps_block = args.steps * repeats
+            steps_block = self.k_block * repeats
             evals_per_block = steps_block * B * world
             t, t_fastest = self.timed_blocks(self.rh, n_blocks, repeats)
             med = float(np.median(t))
@@ -498,8 +556,8 @@ class Measure:
             if extras and mode == head_mode and repeats > 1:
                 # blocks of exactly K steps, nothing repeated: what the fill and drain of the launch pipeline cost a short block
                 tk, _ = self.timed_blocks(self.rh, max(3, n_blocks // 3), 1)
-                entry['k_steps_alone'] = {'value': args.steps * B * world / float(np.median(tk)),
-                                          'ms_per_step': float(np.median(tk)) / args.steps * 1e3, 'block_ms': float(np.median(tk)) * 1e3}
+                entry['k_steps_alone'] = {'value': self.k_block * B * world / float(np.median(tk)),
+                                          'ms_per_step': float(np.median(tk)) / self.k_block * 1e3, 'block_ms': float(np.median(tk)) * 1e3}
             if extras and mode == head_mode and self.steps_per_launch > 1 and not args.skip_single_step:
                 # the same blocks with every step launched on its own
                 _ffi.set_option('coalesce', 1)
@@ -546,8 +604,8 @@ class Measure:
                                                         C.c_void_p(buf['lnL'].value + k * B * 8)))
         na.set_exp_mode(mode)
         repeats = self.repeats_for(self.rh, step)
-        repeats = max(1, min(repeats, (buf['cap'] - args.warmup) // args.steps))
-        steps_block = args.steps * repeats
+        repeats = max(1, min(repeats, (buf['cap'] - args.warmup) // self.k_block))
+        steps_block = self.k_block * repeats
         t, _ = self.timed_blocks(self.rh, n_blocks, repeats, step)
         med = float(np.median(t))
         bytes_eval = self.bytes_eval + chan_tot * 8
@@ -596,7 +654,12 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--blocks', type=int, default=121, help='timed blocks of --steps steps (value = the median block)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: the other mode, repeated blocks, one-lane kernel times and '
+                         'roofline, spectra-out, the C4 block, config 5 and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='write lnL.npy and theta.npy of the last timed step (float64) into DIR')
+    ap.add_argument('--blocks', type=int, default=121, help='--full: repeated blocks of --steps steps (modes.<mode>.value = the median block)')
     ap.add_argument('--workload', default='C2', choices=sorted(WORKLOADS) + ['C5', 'C5r4'],
                     help='C2 (default) is the headline metric; C5 = nested sampling of a 32x32 cube (not a "step" bench)')
     ap.add_argument('--side', type=int, default=128, help='pixels per side of the synthetic cube (C3: 128)')
@@ -605,13 +668,13 @@ def main():
                     help="1: the B rows of a step share one pixel (C2, the metric); B: every row has its own pixel "
                          "(one evaluation per pixel: the shape whose data really stream from HBM)")
     ap.add_argument('--exp-mode', default=os.environ.get('NFA_EXP_MODE', REFERENCE_PRECISION_MODE), choices=list(MODES),
-                    help='the mode `value` is quoted in (both are timed)')
+                    help='the mode `value` is quoted in (with --full, both are timed)')
     ap.add_argument('--modes', default='all', choices=['all', 'one'], help='time both numerical modes or only --exp-mode')
     ap.add_argument('--spectra-out', default='auto', choices=['auto', 'on', 'off', 'only'],
-                    help='also time the spectra-out mode (nfa_runner_predict_batch_dev; auto: with the default C2 run on one GPU); '
+                    help='--full: also time the spectra-out mode (nfa_runner_predict_batch_dev; auto: with the default C2 run on one GPU); '
                          'only: nothing else (profiler runs)')
     ap.add_argument('--configs', default='auto', choices=['auto', 'on', 'off'],
-                    help='also time a short C4 block in both modes (auto: with the default C2 run on one GPU)')
+                    help='--full: also time a short C4 block in both modes (auto: with the default C2 run on one GPU)')
     ap.add_argument('--wpb', type=int, default=0, help='engine A/B knob: waves per workgroup (0 = default)')
     ap.add_argument('--wpb-table', type=int, default=0, help='engine A/B knob: waves per workgroup in table mode (0 = chosen per spectra set)')
     ap.add_argument('--lnl-cap', type=int, default=-1, help='engine A/B knob: likelihood workgroups per CU (0 = no cap)')
@@ -633,10 +696,16 @@ def main():
     ap.add_argument('--setup-sub', type=int, default=0, help='engine A/B knob: 1 = one group of items per set-up workgroup in the table mode (default: two)')
     ap.add_argument('--setup-threads', type=int, default=0, help='engine A/B knob: threads per set-up workgroup (0 = default)')
     ap.add_argument('--ablate', type=int, default=0, help='timing experiment with the -DNFA_ABLATE build (INVALID results)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave out the CPU baseline')
     ap.add_argument('--skip-single-step', action='store_true',
                     help='do not also time the launch of a single step (profiler runs: one launch shape per kernel name)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.dump_outputs and (args.workload in ('C5', 'C5r4') or args.spectra_out == 'only'):
+        ap.error('--dump-outputs writes the outputs of the likelihood steps: not with --workload C5 / C5r4 or --spectra-out only')
+    if not args.full and 'on' in (args.spectra_out, args.configs):
+        ap.error('--spectra-out on and --configs on are measurements of --full')
 
     if args.workload == 'C5':
         return bench_c5(args)
@@ -690,7 +759,7 @@ def main():
     n_other = max(3, args.blocks // 2)
     spectra = None
     if args.spectra_out == 'only':
-        M.alloc_inputs(args.warmup + max(args.steps * 8, 60))
+        M.alloc_inputs(args.warmup + max(M.k_block * 8, 60))
         spectra = M.run_spectra_out(na, args.exp_mode, args.blocks)
         if rank == 0:
             print(json.dumps({'metric': 'spectra-out evals/sec (predict_batch), 1024-ch 2-comp NH3(1,1)+(2,2)', **spectra}), flush=True)
@@ -698,44 +767,60 @@ def main():
         comm.barrier()
         comm.close()
         return
-    per_mode = M.run_modes(na, modes, args.exp_mode, args.blocks, n_other)
-
-    # results of the last step, for the end-of-run gather and a sanity check
-    buf, step_bytes, lon, lat, n_pix = M.buf, M.step_bytes, M.lon, M.lat, M.n_pix
-    lnL = np.empty(B)
-    n_steps = args.warmup + args.steps
-    _ffi.check(lib.nfa_memcpy_d2h(lnL.ctypes.data_as(C.c_void_p),
-                                  C.c_void_p(buf['lnL'].value + (n_steps - 1) * B * 8), B * 8))
+    # ---- the headline: --warmup steps, then exactly --steps timed steps in --exp-mode
+    na.set_exp_mode(args.exp_mode)
+    run = M.steps_run(M.rh)
+    lon, lat, n_pix = M.lon, M.lat, M.n_pix
+    lnL, theta = M.last_step_outputs(run['last'])
+    if args.dump_outputs:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        tag = f'_rank{rank}' if rank else ''
+        np.save(out_dir / f'lnL{tag}.npy', lnL)
+        np.save(out_dir / f'theta{tag}.npy', theta)
     if not np.isfinite(lnL).all() and not args.ablate:
         raise SystemExit('non-finite log-likelihood in the benchmark batch')
-    # ... and the timed steps were fed what they are said to be fed: theta of the last step of the first and of the
-    # last repeat of the last block is the prior transform of the unit-cube rows (a step that found rows an earlier pass
-    # had already turned into theta would do different, cheaper work)
+    # ... and the timed steps were fed what they are said to be fed: theta of the first and of the last timed step (of
+    # the last chunk) is the prior transform of the unit-cube rows (a step that found rows an earlier pass had already
+    # turned into theta would do different, cheaper work)
     want = M.U_host.copy()
     M.ut.transform_batch(want, ncomp)
-    theta = np.empty((B, ndim))
-    last_repeats = per_mode[modes[-1]]['repeats_per_block']
-    for k in sorted({n_steps - 1, args.warmup + args.steps * last_repeats - 1}):
-        _ffi.check(lib.nfa_memcpy_d2h(theta.ctypes.data_as(C.c_void_p), C.c_void_p(buf['U'].value + k * step_bytes), step_bytes))
-        if not np.allclose(theta, want, rtol=1e-9, atol=1e-9) and not args.ablate:
+    for k in sorted({args.warmup, run['last']}):
+        got = theta if k == run['last'] else M.last_step_outputs(k)[1]
+        if not np.allclose(got, want, rtol=1e-9, atol=1e-9) and not args.ablate:
             raise SystemExit(f'theta of timed step {k} is not the prior transform of its unit-cube rows: stale inputs')
     # end-of-run gather of fixed-size per-pixel records: here (i_lon, i_lat, rank, best lnL
-    # of the last pixel walked, evaluations made per block by this rank)
-    k_last = (n_steps - 1) % n_pix
+    # of the last pixel walked, evaluations made in the timed steps by this rank)
+    k_last = run['last'] % n_pix
     rec = np.array([[lon[k_last], lat[k_last], rank, float(lnL.max()), float(args.steps * B)]])
     allrec = nfcomm.gather_pixel_records(rec, comm)
     assert allrec.shape == (world, 5) and (allrec[:, 0] % world == allrec[:, 2]).all()
 
+    # ---- --full: everything else the benchmark measures
+    per_mode, configs = {}, {}
+    if args.full:
+        # the repeated blocks of every mode, as figures of their own (everything below is derived from them); the
+        # headline's run of exactly --steps steps rides along in its mode's entry as `steps_run`
+        per_mode = M.run_modes(na, modes, args.exp_mode, args.blocks, n_other)
+        per_mode[args.exp_mode]['steps_run'] = {k: run[k] for k in ('value', 'ms_per_step', 'seconds', 'chunks')}
+        # theta of the last step of the first and of the last repeat of the last block: fresh rows there as well
+        buf, step_bytes = M.buf, M.step_bytes
+        th = np.empty((B, ndim))
+        last_repeats = per_mode[modes[-1]]['repeats_per_block']
+        for k in sorted({args.warmup + M.k_block - 1, args.warmup + M.k_block * last_repeats - 1}):
+            _ffi.check(lib.nfa_memcpy_d2h(th.ctypes.data_as(C.c_void_p), C.c_void_p(buf['U'].value + k * step_bytes), step_bytes))
+            if not np.allclose(th, want, rtol=1e-9, atol=1e-9) and not args.ablate:
+                raise SystemExit(f'theta of timed step {k} is not the prior transform of its unit-cube rows: stale inputs')
+
     # the spectra-out mode (the HBM-bound form of the path) on the same stripe, in the fast mode (the form whose store
     # counts: in the table mode the same rows are arithmetic for twice as long)
-    if args.spectra_out == 'on' or (args.spectra_out == 'auto' and default_run):
+    if args.full and (args.spectra_out == 'on' or (args.spectra_out == 'auto' and default_run)):
         spectra = M.run_spectra_out(na, 'fast', max(5, args.blocks // 8))
     spec0, ut, U_host = M.spec0, M.ut, M.U_host
     M.close()
     # BASELINE config 4 (three transitions x 2048 channels x 3 components: the LDS hyperfine-table stress), a short block
     # in both modes on a small cube of its own
-    configs = {}
-    if args.configs == 'on' or (args.configs == 'auto' and default_run):
+    if args.full and (args.configs == 'on' or (args.configs == 'auto' and default_run)):
         M4 = Measure(args, na, lib, comm, rank, world, 'C4', 32)
         pm4 = M4.run_modes(na, list(MODES), None, 0, max(5, args.blocks // 6), extras=False)
         configs['C4'] = {
@@ -760,9 +845,9 @@ def main():
         # HIP reports the UUID as 16 ASCII hex digits on this stack: show those; raw bytes otherwise
         uuids.append(raw.decode('ascii') if all(32 < b < 127 for b in raw) else raw.hex())
 
-    if rank == 0:
+    value, cpu = run['value'], None
+    if rank == 0 and args.full:
         head = per_mode[args.exp_mode]
-        value = head['value']
         step_s = head['ms_per_step'] * 1e-3
         # (key order: what reads this line keeps the first twenty scalars of `roofline` -- the headline mode's figures
         # first, then the other mode's as other_*)
@@ -817,7 +902,7 @@ def main():
             if us:
                 roof['rocprof_avg_launch_us'] = us
                 roof['rocprof_frac'] = bytes_eval * B * steps_per_launch / (us * 1e-6) / 1e9 / HBM_PEAK_GBS
-                roof['rocprof'] = (f'{rel(f)} (rocprofv3 --kernel-trace --stats -- python bench.py --streams 1 --modes one '
+                roof['rocprof'] = (f'{rel(f)} (rocprofv3 --kernel-trace --stats -- python bench.py --full --streams 1 --modes one '
                                    f'--exp-mode {args.exp_mode} --no-cpu-baseline --skip-single-step --spectra-out off --configs off)')
         # the like-for-like number: the same workload in the reference's own arithmetic (f64 table product, f64 tau).
         # Flat keys beside the block: what reads this line keeps scalars of `roofline` and drops nested objects.
@@ -877,7 +962,6 @@ def main():
                         'SQ_ACTIVE_INST_VALU and instructions per evaluation (separate --pmc passes); with --pixels-per-step 1 '
                         'the pixel stays in L2 (traffic << algorithmic bytes), see DESIGN.md.  `reference_precision` (and the flat '
                         'reference_precision_* keys): the same workload and timing in the table mode, the reference\'s own f64 arithmetic')
-        cpu = None
         if args.gpus == 1 and not args.no_cpu_baseline and not per_row:
             cpu = cpu_baseline(spec0, ut.lower(), ncomp, U_host)
             # the port beside the real reference.  The reference cannot travel; its rate at this shape
@@ -891,6 +975,7 @@ def main():
                 cpu['reference_equivalent'] = cpu['value'] / ratio
                 cpu['ratio_source'] = f'{f.relative_to(ROOT)}: port {pv["port_evals_per_s_one_core"]:.0f} evals/s against the ' \
                                       f'reference\'s {pv["reference_evals_per_s_one_core"]:.0f} on one core of the same CPU'
+    if rank == 0:
         name = C.create_string_buffer(128)
         lib.nfa_device_name(name, 128)
         metric = 'loglikelihood evals/sec, 1024-ch 2-comp NH3(1,1)+(2,2); HBM GB/s vs peak'
@@ -898,7 +983,7 @@ def main():
             metric += ' [one evaluation per pixel]'
         line = {
             'metric': metric, 'value': value, 'unit': 'evals/s', 'n_gpus': args.gpus, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': head['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak',
+            'warmup': args.warmup, 'ms_per_step': run['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak',
             'vs_baseline': None, 'dtype': DTYPES[args.exp_mode], 'data': 'synthetic',
             'config': {
                 'workload': f'{args.workload}: B={B} live-point draws per step per GPU against one pixel, '
@@ -907,7 +992,8 @@ def main():
                             f'{args.side}x{args.side}, one pixel per '
                             + ('ROW (one evaluation per pixel)' if per_row else 'step'),
                 'exp_mode': args.exp_mode, 'stream_lanes': M.lanes_used, 'steps_per_launch': steps_per_launch, 'pixels_per_gpu': int(n_pix),
-                'repeats_per_block': head['repeats_per_block'], 'block_ms': head['block_ms'],
+                'timed_ms': run['seconds'] * 1e3, 'chunks': run['chunks'],
+                **({'repeats_per_block': head['repeats_per_block'], 'block_ms': head['block_ms']} if args.full else {}),
                 **({'reference_precision_mode': REFERENCE_PRECISION_MODE, 'reference_precision_value': per_mode[REFERENCE_PRECISION_MODE]['value'],
                     'reference_precision_ms_per_step': per_mode[REFERENCE_PRECISION_MODE]['ms_per_step']}
                    if REFERENCE_PRECISION_MODE in per_mode else {}),
@@ -921,18 +1007,19 @@ def main():
                                'solo': 'RCCL (nfa_comm_*) when N > 1'}[comm_kind],
                 'device': name.value.decode(),
             },
-            'spread': {'blocks': head['blocks'], 'statistic': 'median block', 'min': head['min'], 'max': head['max'],
-                       **({'rank_ms_per_step': head['rank_ms_per_step']} if 'rank_ms_per_step' in head else {})},
-            'modes': per_mode, 'roofline': roof, 'cpu_baseline': cpu,
+            'spread': {'statistic': 'one run of --steps timed steps (the slowest rank)',
+                       **({'rank_ms_per_step': run['rank_ms_per_step']} if 'rank_ms_per_step' in run else {})},
         }
+        if args.full:
+            line.update({'modes': per_mode, 'roofline': roof, 'cpu_baseline': cpu})
         if configs:
             line['configs'] = configs
         if spectra:
             line['spectra_out'] = spectra
         if cpu:
-            line['speedup_vs_cpu_all_cores'] = value / cpu['value']
+            line['speedup_vs_cpu_all_cores'] = head['value'] / cpu['value']
             if 'reference_equivalent' in cpu:       # against what the reference itself would deliver on these cores
-                line['speedup_vs_reference_all_cores'] = value / cpu['reference_equivalent']
+                line['speedup_vs_reference_all_cores'] = head['value'] / cpu['reference_equivalent']
                 if REFERENCE_PRECISION_MODE in per_mode:
                     line['reference_precision_speedup_vs_reference_all_cores'] = per_mode[REFERENCE_PRECISION_MODE]['value'] / cpu['reference_equivalent']
         print(json.dumps(line), flush=True)

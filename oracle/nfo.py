@@ -160,8 +160,7 @@ def ref_fastexp_lib(fast_math=False):
     """The reference's own fastexp.c compiled as-is (oracle/_ref); None if absent."""
     path = HERE / '_ref' / ('libfastexp_ref_fm.so' if fast_math else 'libfastexp_ref.so')
     if not path.exists():
-        if Path('/root/reference/nestfit/core/fastexp.c').exists():
-            build()
+        build()                  # (oracle/Makefile builds _ref only where the reference's source is readable)
         if not path.exists():
             return None
     r = C.CDLL(str(path))

@@ -11,17 +11,17 @@ out=gpurun_out/r02; mkdir -p $out
 ONE="--streams 1 --modes one --no-cpu-baseline --skip-single-step --blocks 3 --steps 60 --warmup 12"     # one lane; 72 steps = 18 launches of four steps: one launch shape
 case "$1" in
 bench)
-  python bench.py > $out/bench_default.json 2> $out/bench_default.err || exit 1
-  python bench.py --pixels-per-step B --no-cpu-baseline > $out/bench_pixel_per_row.json 2>> $out/bench_default.err || exit 1
-  python bench.py --workload C4 --no-cpu-baseline --side 32 > $out/bench_C4.json 2>> $out/bench_default.err || exit 1
-  python bench.py --workload C1 --no-cpu-baseline --side 32 > $out/bench_C1.json 2>> $out/bench_default.err || exit 1
-  python bench.py --batch 16384 --steps 50 --no-cpu-baseline --modes one > $out/bench_B16384.json 2>> $out/bench_default.err || exit 1
+  python bench.py --full > $out/bench_default.json 2> $out/bench_default.err || exit 1
+  python bench.py --full --pixels-per-step B --no-cpu-baseline > $out/bench_pixel_per_row.json 2>> $out/bench_default.err || exit 1
+  python bench.py --full --workload C4 --no-cpu-baseline --side 32 > $out/bench_C4.json 2>> $out/bench_default.err || exit 1
+  python bench.py --full --workload C1 --no-cpu-baseline --side 32 > $out/bench_C1.json 2>> $out/bench_default.err || exit 1
+  python bench.py --full --batch 16384 --steps 50 --no-cpu-baseline --modes one > $out/bench_B16384.json 2>> $out/bench_default.err || exit 1
   python bench.py --workload C5 > $out/bench_C5.json 2>> $out/bench_default.err || exit 1
   ;;
 rocprof)
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/onelane -- python bench.py $ONE > $out/bench_onelane.json 2> $out/onelane.err || exit 2
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/onelane -- python bench.py --full $ONE > $out/bench_onelane.json 2> $out/onelane.err || exit 2
   cp $out/onelane/*/*kernel_stats.csv $out/onelane_kernel_stats.csv
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/default -- python bench.py --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/default.err || exit 2
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/default -- python bench.py --full --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/default.err || exit 2
   cp $out/default/*/*kernel_stats.csv $out/default_kernel_stats.csv
   ;;
 pmc)
@@ -31,7 +31,7 @@ pmc)
            "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_LDS_BANK_CONFLICT" \
            "SQ_INSTS_BRANCH SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_ANY"; do
     i=$((i+1))
-    timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/pmc_$i -- python bench.py $ONE > $out/pmc_$i.log 2>&1 || echo "pmc pass $i failed"
+    timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/pmc_$i -- python bench.py --full $ONE > $out/pmc_$i.log 2>&1 || echo "pmc pass $i failed"
   done
   python profiles/pmc_to_json.py "lnl_kernel<2, false" 16384 $out/pmc_lnl_fast.json $out/pmc_*/*/*counter_collection.csv > $out/pmc_lnl_fast.txt
   python profiles/pmc_to_json.py "setup_kernel" 16384 $out/pmc_setup.json $out/pmc_*/*/*counter_collection.csv > $out/pmc_setup.txt
@@ -42,7 +42,7 @@ pmc_table)
   for p in "SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU_CVT"; do
     i=$((i+1))
-    timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/pmct_$i -- python bench.py $ONE --exp-mode table > $out/pmct_$i.log 2>&1 || echo "pmc_table pass $i failed"
+    timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/pmct_$i -- python bench.py --full $ONE --exp-mode table > $out/pmct_$i.log 2>&1 || echo "pmc_table pass $i failed"
   done
   python profiles/pmc_to_json.py "lnl_kernel<0, false" 16384 $out/pmc_lnl_table.json $out/pmct_*/*/*counter_collection.csv > $out/pmc_lnl_table.txt
   ;;

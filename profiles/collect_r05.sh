@@ -14,19 +14,19 @@ out=gpurun_out/r05; mkdir -p $out
 ONE="--streams 1 --modes one --no-cpu-baseline --skip-single-step --spectra-out off --configs off --blocks 3 --steps 64 --warmup 16"     # one lane; blocks of 64 steps = launches of eight steps: one launch shape
 case "$1" in
 bench)
-  python3 bench.py --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err || exit 1
-  python3 bench.py --pixels-per-step B --no-cpu-baseline --configs off --spectra-out off > $out/bench_pixel_per_row.json 2>> $out/bench_default.err || exit 1
-  python3 bench.py --workload C4 --no-cpu-baseline --side 32 > $out/bench_C4.json 2>> $out/bench_default.err || exit 1
-  python3 bench.py --workload C1 --no-cpu-baseline --side 32 > $out/bench_C1.json 2>> $out/bench_default.err || exit 1
-  python3 bench.py --batch 16384 --steps 50 --no-cpu-baseline --modes one --configs off --spectra-out off > $out/bench_B16384.json 2>> $out/bench_default.err || exit 1
+  python3 bench.py --full --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err || exit 1
+  python3 bench.py --full --pixels-per-step B --no-cpu-baseline --configs off --spectra-out off > $out/bench_pixel_per_row.json 2>> $out/bench_default.err || exit 1
+  python3 bench.py --full --workload C4 --no-cpu-baseline --side 32 > $out/bench_C4.json 2>> $out/bench_default.err || exit 1
+  python3 bench.py --full --workload C1 --no-cpu-baseline --side 32 > $out/bench_C1.json 2>> $out/bench_default.err || exit 1
+  python3 bench.py --full --batch 16384 --steps 50 --no-cpu-baseline --modes one --configs off --spectra-out off > $out/bench_B16384.json 2>> $out/bench_default.err || exit 1
   ;;
 rocprof)
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/onelane_table -- python3 bench.py $ONE --exp-mode table > $out/bench_onelane_table.json 2> $out/onelane_table.err || exit 2
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/onelane_table -- python3 bench.py --full $ONE --exp-mode table > $out/bench_onelane_table.json 2> $out/onelane_table.err || exit 2
   cp $out/onelane_table/*/*kernel_stats.csv $out/onelane_kernel_stats_table.csv
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/onelane -- python3 bench.py $ONE --exp-mode fast > $out/bench_onelane.json 2> $out/onelane.err || exit 2
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/onelane -- python3 bench.py --full $ONE --exp-mode fast > $out/bench_onelane.json 2> $out/onelane.err || exit 2
   cp $out/onelane/*/*kernel_stats.csv $out/onelane_kernel_stats.csv
   for m in table fast; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/fourlane_$m -- python3 bench.py --steps 20 --warmup 5 --blocks 15 --modes one --exp-mode $m --no-cpu-baseline --skip-single-step --spectra-out off --configs off > $out/bench_fourlane_$m.json 2> $out/fourlane_$m.err || exit 2
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/fourlane_$m -- python3 bench.py --full --steps 20 --warmup 5 --blocks 15 --modes one --exp-mode $m --no-cpu-baseline --skip-single-step --spectra-out off --configs off > $out/bench_fourlane_$m.json 2> $out/fourlane_$m.err || exit 2
     cp $out/fourlane_$m/*/*kernel_stats.csv $out/fourlane_${m}_kernel_stats.csv
     python3 profiles/fourlane_summary.py $out/fourlane_$m/*/*kernel_trace.csv $out/bench_fourlane_$m.json > $out/fourlane_${m}_summary.txt
     rm -rf $out/fourlane_$m
@@ -44,7 +44,7 @@ pmc|pmc_fast)
            "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32 SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
            "SQ_INSTS_BRANCH SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_VMEM"; do
     i=$((i+1))
-    timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/pmc_${tag}_$i -- python3 bench.py $ONE --exp-mode $mode > $out/pmc_${tag}_$i.log 2>&1 || echo "pmc pass $i failed"
+    timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/pmc_${tag}_$i -- python3 bench.py --full $ONE --exp-mode $mode > $out/pmc_${tag}_$i.log 2>&1 || echo "pmc pass $i failed"
   done
   python3 profiles/pmc_to_json.py "$kern" 32768 $out/pmc_lnl_$tag.json $out/pmc_${tag}_*/*/*counter_collection.csv > $out/pmc_lnl_$tag.txt
   [ "$1" = pmc ] && python3 profiles/pmc_to_json.py "setup_kernel" 32768 $out/pmc_setup.json $out/pmc_${tag}_*/*/*counter_collection.csv > $out/pmc_setup.txt

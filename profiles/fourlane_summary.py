@@ -35,5 +35,5 @@ n = len(lnl)
 print(f'launches of {spl} coalesced steps (lnl_kernel, {spl * B} evaluations each): {n}')
 print(f'sum of their durations: {tot} ns = {tot / max(n, 1) / 1e3:.1f} us per launch = {tot / max(n * spl, 1) / 1e3:.2f} us per step (launches overlap on the stream lanes: each is stretched by its neighbours)')
 print(f'time during which at least one of them ran (union of the intervals): {union} ns = {union / max(n * spl, 1) / 1e3:.2f} us per step')
-print(f'bench line of the same run (under the tracer): {m["ms_per_step"] * 1e3:.2f} us per step over blocks of {m["repeats_per_block"]} x {line["steps"]} steps, {line["value"] / 1e6:.1f} M evaluations/s')
+print(f'bench line of the same run (under the tracer): {m["ms_per_step"] * 1e3:.2f} us per step over blocks of {m["repeats_per_block"]} x {line["steps"]} steps, {m["value"] / 1e6:.1f} M evaluations/s')
 print(f'one-lane launch of the same shape (roofline.avg_launch_us of that line, HIP events): {line["roofline"].get("avg_launch_us")} us = {line["roofline"].get("avg_launch_us", 0) / spl:.2f} us per step')

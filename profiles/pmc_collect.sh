@@ -1,14 +1,15 @@
 #!/bin/bash
-# usage: pmc_collect.sh <outdir-tag> <bench args...>   (run on the GPU box, from the repo root)
+# usage: pmc_collect.sh <outdir-tag> <bench args...>   (run on the GPU box, from the repo root; output under ${PROFILE_OUT:-profile_out})
 # Collects SQ counters in separate passes (8 SQ slots per pass) with rocprofv3 --pmc.
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+out=${PROFILE_OUT:-profile_out}
+mkdir -p $out
 i=0
 for p in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM" \
          "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_ANY" \
          "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_LDS_BANK_CONFLICT" \
          "SQ_INSTS_BRANCH SQ_INSTS_LDS_ATOMIC SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_VMEM SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d gpurun_out/pmc_${tag}_$i -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-profile-events "$@" > gpurun_out/pmc_${tag}_$i.log 2>&1 || echo "pmc pass $i failed"
+  timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/pmc_${tag}_$i -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-profile-events "$@" > $out/pmc_${tag}_$i.log 2>&1 || echo "pmc pass $i failed"
 done

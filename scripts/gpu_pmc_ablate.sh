@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mode=$1; shift
 out=gpurun_out/${NFA_ROUND:-r05}/pmc_ablate; mkdir -p $out
 for a in "$@"; do
-  NFA_ENGINE_LIB=$PWD/nestfit_amd/lib/libnestfit_amd_test.so timeout -k 10 200 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_INSTS_BRANCH --output-format csv -d $out/a$a -- python bench.py --steps 8 --warmup 2 --blocks 2 --no-cpu-baseline --streams 1 --modes one --exp-mode $mode --skip-single-step --spectra-out off --configs off --ablate $a > $out/a$a.log 2>&1 || echo "ablate $a failed"
+  NFA_ENGINE_LIB=$PWD/nestfit_amd/lib/libnestfit_amd_test.so timeout -k 10 200 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_INSTS_BRANCH --output-format csv -d $out/a$a -- python bench.py --full --steps 8 --warmup 2 --blocks 2 --no-cpu-baseline --streams 1 --modes one --exp-mode $mode --skip-single-step --spectra-out off --configs off --ablate $a > $out/a$a.log 2>&1 || echo "ablate $a failed"
 done
 python - "$@" <<'P'
 import csv, glob, os, sys, collections

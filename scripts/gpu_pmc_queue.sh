@@ -8,7 +8,7 @@ for k in "$@"; do
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_ANY" \
            "SQ_INSTS_BRANCH SQ_INSTS_LDS_ATOMIC SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_VMEM SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_CVT GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/k${k}_$i -- python bench.py --steps 10 --warmup 2 --blocks 3 --no-cpu-baseline --streams 1 --modes one --exp-mode table --skip-single-step --spectra-out off --configs off --lnl-queue $k > $out/k${k}_$i.log 2>&1 || echo "pmc pass $i of queue $k failed"
+    timeout -k 10 200 rocprofv3 --pmc $p --output-format csv -d $out/k${k}_$i -- python bench.py --full --steps 10 --warmup 2 --blocks 3 --no-cpu-baseline --streams 1 --modes one --exp-mode table --skip-single-step --spectra-out off --configs off --lnl-queue $k > $out/k${k}_$i.log 2>&1 || echo "pmc pass $i of queue $k failed"
   done
 done
 python - "$@" <<'P'

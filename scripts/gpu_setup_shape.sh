@@ -8,7 +8,7 @@ for r in 1 2; do
   for lib in libnestfit_amd ab_w4; do
     for shape in "0 0" "32 256" "64 512" "32 512" "16 256"; do
       set -- $shape
-      NFA_ENGINE_LIB=nestfit_amd/lib/$lib.so python bench.py $B --setup-ti $1 --setup-threads $2 > $out/${lib}_$1_$2_$r.json 2>>$out/err.log || { tail -3 $out/err.log; exit 1; }
+      NFA_ENGINE_LIB=nestfit_amd/lib/$lib.so python bench.py --full $B --setup-ti $1 --setup-threads $2 > $out/${lib}_$1_$2_$r.json 2>>$out/err.log || { tail -3 $out/err.log; exit 1; }
     done
   done
 done
@@ -19,6 +19,6 @@ for lib in ('libnestfit_amd','ab_w4'):
         v=[];su=[]
         for f in sorted(glob.glob(f'gpurun_out/r05/setup_shape/{lib}_{shape}_*.json')):
             d=json.loads(open(f).read().strip().splitlines()[-1]); m=d['modes'][sys.argv[1]]
-            v.append(d['value']/1e6); su.append(m.get('setup_kernel_us',0))
+            v.append(m['value']/1e6); su.append(m.get('setup_kernel_us',0))
         print(f'{sys.argv[1]} {lib:16s} ti_threads {shape:8s} value {st.median(v):7.2f} M   setup kernel {st.median(su):6.1f} us')
 P

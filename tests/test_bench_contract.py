@@ -1,12 +1,14 @@
-"""bench.py as the driver runs it (short): ONE JSON line with the contract's keys, the two modes, the
-roofline and -- with two ranks sharing the one GPU (`NFA_BENCH_SAME_GPU`, the rehearsal of `--gpus N`) --
-the whole-job value of two stripes."""
+"""bench.py as the driver runs it (short): ONE JSON line with the contract's keys -- the plain run the headline
+alone and the outputs of its last step, `--full` the two modes, the roofline and the other measurements -- and, with
+two ranks sharing the one GPU (`NFA_BENCH_SAME_GPU`, the rehearsal of `--gpus N`), the whole-job value of two
+stripes."""
 import json
 import os
 import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,8 +25,65 @@ def _run(args, env=None):
     return json.loads(lines[0])
 
 
+def _oracle_lnl(nfo, k, side):
+    """lnL of the bench's unit-cube rows (rank 0) against pixel k of the C2 stripe of a side x side cube, by the CPU
+    oracle: the pixel's truth and noise as bench.make_stripe draws them, its clean spectra from the oracle."""
+    import bench
+    import nestfit_amd as na
+    from nestfit_amd.cube import shard_pixels
+    from nestfit_amd.synth import freq_axis
+    trans, n_chan, vhalf, ncomp, _, B = bench.WORKLOADS['C2']
+    lon, lat = shard_pixels((side, side), 0, 1)
+    k %= lon.size
+    truth = bench.stripe_truths('C2', side, lon[k:k + 1], lat[k:k + 1])[0]
+    noise = np.random.default_rng(5 + int(lon[k]) * side + int(lat[k])).normal(0, 0.2, len(trans) * n_chan)
+    spectra = []
+    for s, t in enumerate(trans):
+        x = freq_axis(t, n_chan, vhalf)
+        clean = nfo.AmmoniaSpectrum(x, np.zeros(n_chan), 0.2, t)
+        nfo.amm_predict(clean, truth)
+        spectra.append(nfo.AmmoniaSpectrum(x, clean.get_spec() + noise[s * n_chan:(s + 1) * n_chan], 0.2, t))
+    run = nfo.AmmoniaRunner(spectra, nfo.PriorSet(na.get_irdc_priors(size=500, vsys=0.0).lower()), ncomp=ncomp)
+    return run.loglikelihood_batch(np.random.default_rng(7).uniform(size=(B, 6 * ncomp)))
+
+
+def test_plain_line_is_the_headline_and_its_outputs(tmp_path, nfo):
+    plain = ['--steps', '6', '--warmup', '2', '--side', '16']
+    d = _run(plain + ['--dump-outputs', str(tmp_path / 'a')])
+    for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                'vs_baseline', 'dtype', 'data', 'config', 'spread'):
+        assert key in d, key
+    assert d['n_gpus'] == 1 and d['steps'] == 6 and d['warmup'] == 2 and d['unit'] == 'evals/s'
+    assert d['higher_is_better'] is True and d['dtype'].startswith('f64 (reference FastExp') and d['config']['exp_mode'] == 'table'
+    # value = evaluations of the 6 timed steps / their time, in one chunk
+    assert d['value'] == pytest.approx(4096 / (d['ms_per_step'] * 1e-3), rel=1e-6)
+    assert d['config']['chunks'] == 1 and d['config']['timed_ms'] > 0
+    # nothing of --full
+    for key in ('modes', 'roofline', 'cpu_baseline', 'spectra_out', 'configs'):
+        assert key not in d, key
+    # what the last timed step returned: B log-likelihoods and the B x 12 physical parameters, float64
+    lnL, theta = np.load(tmp_path / 'a' / 'lnL.npy'), np.load(tmp_path / 'a' / 'theta.npy')
+    assert lnL.dtype == theta.dtype == np.float64 and lnL.shape == (4096,) and theta.shape == (4096, 12)
+    assert np.isfinite(lnL).all()
+    # ... of the LAST timed step: pixel (warmup + steps - 1) % n_pix of the stripe, against the oracle (an earlier step
+    # walked another pixel, whose lnL differs by far more)
+    np.testing.assert_allclose(lnL, _oracle_lnl(nfo, 2 + 6 - 1, 16), rtol=1e-6)
+    # the same arguments feed the same inputs: a second run returns the same outputs
+    _run(plain + ['--dump-outputs', str(tmp_path / 'b')])
+    np.testing.assert_array_equal(np.load(tmp_path / 'b' / 'theta.npy'), theta)
+    np.testing.assert_allclose(np.load(tmp_path / 'b' / 'lnL.npy'), lnL, rtol=1e-12, atol=0)
+
+
+def test_steps_beyond_one_chunk_are_all_timed():
+    """More timed steps than have unit-cube rows resident at once (bench.CHUNK_STEPS): every one of them is timed."""
+    d = _run(['--steps', '8200', '--warmup', '2', '--side', '16'])
+    assert d['steps'] == 8200 and d['config']['chunks'] == 2
+    assert d['value'] == pytest.approx(8200 * 4096 / (d['config']['timed_ms'] * 1e-3), rel=1e-6)
+    assert d['ms_per_step'] == pytest.approx(d['config']['timed_ms'] / 8200, rel=1e-6)
+
+
 def test_default_line_has_the_contract_keys():
-    d = _run(SHORT)
+    d = _run(SHORT + ['--full'])
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
                 'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline', 'modes', 'spread'):
         assert key in d, key
@@ -32,14 +91,19 @@ def test_default_line_has_the_contract_keys():
     assert d['higher_is_better'] is True and d['scaling'] == 'weak' and d['vs_baseline'] is None and d['data'] == 'synthetic'
     assert 'workload' in d['config'] and 'model' not in d['config']
     # the headline is the table mode: the reference's own arithmetic (fastexp.c:234-283, hyperfine.pyx:93-96)
-    assert set(d['modes']) == {'table', 'fast'} and d['modes']['table']['value'] == d['value'] and d['dtype'].startswith('f64 (reference FastExp')
+    assert set(d['modes']) == {'table', 'fast'} and d['modes']['table']['steps_run']['value'] == d['value'] and d['dtype'].startswith('f64 (reference FastExp')
+    assert d['modes']['table']['steps_run']['ms_per_step'] == d['ms_per_step']
+    # every other figure of the line is the repeated blocks': the median block inside its own spread
+    for m in ('table', 'fast'):
+        e = d['modes'][m]
+        assert e['min'] <= e['value'] <= e['max'] and e['value'] == pytest.approx(4096 / (e['ms_per_step'] * 1e-3), rel=1e-6)
     r = d['roofline']
     for key in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic'):
         assert key in r, key
     assert r['frac'] == pytest.approx(r['achieved'] / r['peak']) and 0 < r['frac'] < 1
     # value = evaluations of the timed block / its time
     assert d['value'] == pytest.approx(4096 / (d['ms_per_step'] * 1e-3), rel=1e-6)
-    assert d['modes']['fast']['value'] > d['value']
+    assert d['modes']['fast']['value'] > d['modes']['table']['value']
     # ... its figures lead `roofline`, the fast mode's follow as fast_* inside the first twenty keys (what reads the line
     # keeps that many scalars)
     keys = list(r)
@@ -48,7 +112,8 @@ def test_default_line_has_the_contract_keys():
         assert key in keys[:20], (key, keys[:24])
     assert r['fast_value'] == d['modes']['fast']['value'] and 0 < r['frac'] < r['fast_frac'] < 1
     rp = r['reference_precision']
-    assert rp['mode'] == 'table' and rp['dtype'].startswith('f64') and rp['value'] == d['value']
+    assert rp['mode'] == 'table' and rp['dtype'].startswith('f64') and rp['value'] == d['modes']['table']['value']
+    assert r['pipeline']['us_per_step'] == pytest.approx(d['modes']['table']['ms_per_step'] * 1e3)
     assert r['reference_precision_value'] == rp['value'] and r['reference_precision_frac'] == pytest.approx(r['frac'])
     assert d['config']['reference_precision_value'] == rp['value']
     # the spectra-out mode and the short C4 block of the default command

@@ -1,13 +1,14 @@
 """Sibling models on the same kernels: N2H+ (nestfit/models/diazenylium.pyx)
 and Gaussian (nestfit/models/gaussian.pyx).
 
-CPU part: line data against the reference text, oracle sanity against closed forms.
+CPU part: line data against the reference text (its literals recorded in tests/golden/reference_literals.json),
+oracle sanity against closed forms.
 GPU part: engine against the oracle through the C ABI, all three numerical modes.
 There are no reference outputs for these two models among the survey's known answers, so the
 oracle is pinned for them only through the shared pieces (FastExp, iemtex, windows) and the
 literal line data: "parity unpinned beyond the restatement" (DESIGN.md section 2).
 """
-import re
+import json
 from pathlib import Path
 
 import numpy as np
@@ -15,7 +16,7 @@ import pytest
 
 CKMS = 299792.458
 N2HP_NU = {1: 93173.7637e6, 2: 186344.8420e6, 3: 279511.8325e6}
-REF = Path('/root/reference/nestfit/models/diazenylium.pyx')
+LITERALS = Path(__file__).resolve().parent / 'golden' / 'reference_literals.json'
 
 
 def n2hp_axis(trans, n, vhalf=20.0):
@@ -23,27 +24,16 @@ def n2hp_axis(trans, n, vhalf=20.0):
     return N2HP_NU[trans] * (1.0 - v / CKMS)
 
 
-def _floats(txt):
-    txt = re.sub(r'#.*', '', txt)
-    return [float(v) for v in re.findall(r'[-+]?\d+\.?\d*(?:[eE][-+]?\d+)?', txt)]
-
-
-def _block(text, start, end=']'):
-    a = text.index(start) + len(start)
-    return text[a:text.index(end, a)]
-
-
 # ---------------------------------------------------------------------------- CPU
-@pytest.mark.skipif(not REF.exists(), reason='reference tree not present')
 def test_n2hp_line_data_matches_reference_text(nfo):
-    text = REF.read_text()
+    ref = json.loads(LITERALS.read_text())['n2hp']
     lib = nfo.lib()
-    nhf = [int(v) for v in _floats(_block(text, 'NHF = ['))]
+    nhf = ref['NHF']
     assert nhf == [lib.nfo_n2hp_nhf(t) for t in (1, 2, 3)] == [15, 40, 45]
-    assert _floats(_block(text, 'NU = [')) == [lib.nfo_n2hp_nu(t) for t in (1, 2, 3)]
+    assert ref['NU'] == [lib.nfo_n2hp_nu(t) for t in (1, 2, 3)]
     for t in (1, 2, 3):
-        v = _floats(_block(text, f'VOFF[{t-1}][:NHF[{t-1}]] = ['))
-        w = _floats(_block(text, f'TAU_WTS[{t-1}][:NHF[{t-1}]] = ['))
+        v = ref['VOFF'][t - 1]
+        w = ref['TAU_WTS'][t - 1]
         assert len(v) == len(w) == nhf[t - 1]
         assert v == [lib.nfo_n2hp_voff(t, i) for i in range(len(v))]
         assert w == [lib.nfo_n2hp_tau_wt(t, i) for i in range(len(w))]
