@@ -77,7 +77,7 @@ int nfa_get_exp_mode(void);
  *                   multiple of 64; pixels given or not) that follow each other are held and launched together,
  *                   at most this many (1 = every call its own launches).  Results are bitwise the same; anything
  *                   that looks at them or changes the way launches are made (nfa_runner_synchronize,
- *                   nfa_device_synchronize, the host-pointer calls, a mode change, the sampler) launches what is
+ *                   nfa_device_synchronize, the host-pointer calls, a mode change, nfa_set_option, the sampler) launches what is
  *                   held first.  Read at every call;
  *   "prior_stage"   1 / 0: the set-up kernel stages the prior tables in LDS (default) or reads them from global
  *                   memory; taken over by priors created afterwards (A/B knob: no measurable difference in the

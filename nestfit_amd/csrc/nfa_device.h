@@ -152,6 +152,7 @@ __device__ __forceinline__ int group_of(const BatchGroup &g, long b) {
 }
 
 #define LNL_PARTS 4      // row parts of a unit: the fixed shape of its chi^2 sum
+#define NFA_TRACE_WAVES 8192   // waves the queue kernel's trace buffer holds (test library, nfa_test_queue_trace)
 struct LnlGeom {
     int nhf_max;       // lines per component slot in the LDS line table
     int wave_doubles;  // LDS doubles per wave
@@ -1309,8 +1310,9 @@ lnl_kernel_queue(SpecDev S, BatchGroup grp, const double *__restrict__ D, double
         lnl_body<0, WRITE_SPEC, false, NCOMP, true>(*(const SpecDev *)&A->S, nullptr, A->D, A->part, A->spec_out, A->B, *(const LnlGeom *)&A->G,
                                                     A->g_tabs, smem, sm, n_shared, blockIdx.x, (const BatchGroup *)&A->grp, (long)u_item);
 #ifdef NFA_TEST_HOOKS
-        if (G.trace && lane_q == 0 && n_rec < 8) {
-            unsigned long long *t = G.trace + ((size_t)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 8 + n_rec) * 4;
+        const unsigned t_wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        if (G.trace && lane_q == 0 && n_rec < 8 && t_wave < NFA_TRACE_WAVES) {      // (waves beyond the buffer: not recorded)
+            unsigned long long *t = G.trace + ((size_t)t_wave * 8 + n_rec) * 4;
             t[0] = t_start; t[1] = wall_clock64(); t[2] = u_item; t[3] = unit;
         }
         n_rec += 1;

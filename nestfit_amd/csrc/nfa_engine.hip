@@ -301,6 +301,8 @@ int nfa_set_exp_mode(int mode) {
 int nfa_get_exp_mode(void) { return g_eng.exp_mode; }
 
 int nfa_set_option(const char *key, int value) {
+    // what is held was accepted under the old options (enqueue_dev: B % setup_ti; launch_setup reads it at the flush)
+    { int rc = flush_all_runners(); if (rc) return rc; }
     if (key && !strcmp(key, "lnl_cap") && value >= 0 && value <= 8) { g_eng.lnl_cap = value; return NFA_OK; }
     if (key && !strcmp(key, "lnl_queue_wg") && value >= 0 && value <= 2) { g_eng.lnl_queue_wg = value; return NFA_OK; }
     if (key && !strcmp(key, "lnl_queue") && (value == 0 || value == 1)) { g_eng.lnl_queue = value; return NFA_OK; }
@@ -758,7 +760,9 @@ static int reserve_lane(nfa_runner *r, int slot, int64_t B) {
     HIP_TRY(hipMalloc(&r->d_part[slot], sizeof(double) * cap * n_spec));
     if (!r->d_queue[slot]) {
         HIP_TRY(hipMalloc(&r->d_queue[slot], sizeof(unsigned) * NFA_QUEUE_WORDS));
-        HIP_TRY(hipMemset(r->d_queue[slot], 0, sizeof(unsigned) * NFA_QUEUE_WORDS));
+        // on the lane itself: the lanes are non-blocking streams, so a null-stream memset is not ordered before the lane's
+        // first queue launch, which could then start from whatever the fresh allocation held
+        HIP_TRY(hipMemsetAsync(r->d_queue[slot], 0, sizeof(unsigned) * NFA_QUEUE_WORDS, r->lanes[slot]));
     }
     r->cap_D[slot] = cap;
     return NFA_OK;

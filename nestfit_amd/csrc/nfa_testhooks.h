@@ -206,7 +206,6 @@ int nfa_test_callback_latency(nfa_loglike_callback_fn callback, void *runner, in
 //  wave of a launch records {start, end, item * nspec + spectrum, position in the order} of up to 8 units, in ticks of
 //  10 ns (s_memrealtime); the buffer holds the last launch
 // ---------------------------------------------------------------------------
-#define NFA_TRACE_WAVES 8192
 int nfa_test_queue_trace(int on) {
     int rc0 = engine_init(); if (rc0) return rc0;
     if (on && !g_eng.d_trace) {

@@ -3,42 +3,14 @@ the engine's coalescing of batches that arrive back to back: every batch must co
 -pointer call gives it, whatever company it travelled in -- groups of four, a rest, shapes that change mid-stream,
 batches that cannot be coalesced, a mode switch between two batches, cube runners with pixel arrays and single
 -pixel runners without."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
+from device_buffers import DeviceArrays as _DeviceArrays
 from nestfit_amd.synth import freq_axis
 
 pytestmark = pytest.mark.gpu
-
-
-class _DeviceArrays:
-    def __init__(self, lib, check):
-        self.lib, self.check, self.ptrs = lib, check, []
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        p = C.c_void_p()
-        self.check(self.lib.nfa_malloc(C.byref(p), a.nbytes))
-        self.check(self.lib.nfa_memcpy_h2d(p, a.ctypes.data_as(C.c_void_p), a.nbytes))
-        self.ptrs.append(p)
-        return p
-
-    def empty(self, nbytes):
-        p = C.c_void_p()
-        self.check(self.lib.nfa_malloc(C.byref(p), nbytes))
-        self.ptrs.append(p)
-        return p
-
-    def download(self, p, like):
-        out = np.empty_like(like)
-        self.check(self.lib.nfa_memcpy_d2h(out.ctypes.data_as(C.c_void_p), p, out.nbytes))
-        return out
-
-    def free(self):
-        for p in self.ptrs:
-            self.lib.nfa_free(p)
 
 
 def _run_on_device(_ffi, handle, batches, sync_after=()):
