@@ -194,6 +194,8 @@ struct nfa_specset {
 struct nfa_priors {
     PriorProg prog{};
     PriorProg *d_prog = nullptr;       // device copy handed to the kernels
+    PriorProg *d_prog_global = nullptr;    // the same program with n_stage = 0 (its tables read from global memory: the same
+                                           // values) for a set-up launch whose staged layout does not fit; d_prog if nothing is staged
     std::vector<double *> d_arrays;
 };
 
@@ -652,6 +654,11 @@ static int priors_fill(nfa_priors *p, const nfa_prior_desc *priors, int n_prior,
     }
     HIP_TRY(hipMalloc(&p->d_prog, sizeof(PriorProg)));
     HIP_TRY(hipMemcpy(p->d_prog, &p->prog, sizeof(PriorProg), hipMemcpyHostToDevice));
+    if (g.n_stage == 0) { p->d_prog_global = p->d_prog; return NFA_OK; }
+    PriorProg flat = g;
+    flat.n_stage = 0; flat.stage_doubles = 0; flat.stage_image = nullptr;
+    HIP_TRY(hipMalloc(&p->d_prog_global, sizeof(PriorProg)));
+    HIP_TRY(hipMemcpy(p->d_prog_global, &flat, sizeof(PriorProg), hipMemcpyHostToDevice));
     return NFA_OK;
 }
 
@@ -669,6 +676,7 @@ int nfa_priors_create(nfa_priors **out, const nfa_prior_desc *priors, int n_prio
 
 int nfa_priors_destroy(nfa_priors *p) {
     if (!p) return NFA_OK;
+    if (p->d_prog_global != p->d_prog) (void)hipFree(p->d_prog_global);
     (void)hipFree(p->d_prog);
     for (double *d : p->d_arrays) (void)hipFree(d);
     delete p;
@@ -827,12 +835,26 @@ static int reserve_lane(nfa_runner *r, int slot, int64_t B) {
     return NFA_OK;
 }
 
-// LDS of the set-up stage: exponential tables, theta + partition records + the prior program and its tables
+// LDS of the set-up stage: exponential tables, theta + partition records + the prior program and `stage_doubles` of its tables
 static bool setup_uses_tables(const nfa_runner *r, int mode) { return mode == 0 && r->ss->dev.model == NFA_MODEL_AMMONIA; }
-static size_t setup_lds_bytes(const nfa_runner *r, int mode, bool has_prior, int nsub = 1) {
+static size_t setup_lds_layout(const nfa_runner *r, int mode, int nsub, int stage_doubles) {
     const size_t work = (size_t)nsub * ((size_t)64 * r->ndim + (size_t)SETUP_TI * r->ncomp * QREC) + sizeof(PriorProg) / sizeof(double) + 1
-                        + (has_prior ? (size_t)r->pr->prog.stage_doubles : 0);
+                        + (size_t)stage_doubles;
     return sizeof(double) * ((setup_uses_tables(r, mode) ? (SM_END_TABLE - SM_EXP2) : NFA_EXP2_N) + work);
+}
+// Whether a launch stages the prior tables the priors were created with.  Whether they fit is only known here: in the
+// table mode, 500-point irdc tables (10 of them staged) and 8 or more components need more than 160 KiB.  Such a launch
+// takes the copy of the program that reads the tables from global memory (nfa_priors::d_prog_global): the same values, so
+// the same bits, as priors created under option prior_stage 0.
+static bool setup_staged(const nfa_runner *r, int mode, bool has_prior, int nsub) {
+    return has_prior && r->pr->prog.n_stage > 0 && setup_lds_layout(r, mode, nsub, r->pr->prog.stage_doubles) <= 160 * 1024;
+}
+static size_t setup_lds_bytes(const nfa_runner *r, int mode, bool has_prior, int nsub = 1) {
+    return setup_lds_layout(r, mode, nsub, setup_staged(r, mode, has_prior, nsub) ? r->pr->prog.stage_doubles : 0);
+}
+static const PriorProg *setup_prog(const nfa_runner *r, int mode, bool has_prior, int nsub = 1) {
+    if (!has_prior) return nullptr;
+    return (const PriorProg *)(setup_staged(r, mode, has_prior, nsub) ? r->pr->d_prog : r->pr->d_prog_global);
 }
 
 static int launch_setup(nfa_runner *r, double *d_U, int64_t B, bool has_prior, int slot, int mode) {
@@ -840,7 +862,6 @@ static int launch_setup(nfa_runner *r, double *d_U, int64_t B, bool has_prior, i
     hipStream_t st = r->lanes[slot];
     int rc = reserve_lane(r, slot, B); if (rc) return rc;
     if (has_prior && !r->pr) return fail(NFA_ERR_STATE, "runner has no priors (predict-only)");
-    const PriorProg *prog = has_prior ? (const PriorProg *)r->pr->d_prog : nullptr;
     // items per workgroup and waves per workgroup (options setup_ti, setup_threads: A/B knobs)
     const int ti = g_eng.setup_ti > 0 ? g_eng.setup_ti : SETUP_TI;
     const bool tables = setup_uses_tables(r, mode);
@@ -853,17 +874,18 @@ static int launch_setup(nfa_runner *r, double *d_U, int64_t B, bool has_prior, i
     // and two rounds of them for 32768 items; 133 KB for two: one round): 48.4 -> see profiles/r05/ab_table_linestep.txt.
     // Every batch of a group must hold whole workgroups; a launch of ONE batch may have any size (the last workgroup's
     // second group then has fewer items, or none: the sampler's batches).  Small launches keep one group per workgroup:
-    // they are latency, not rounds.
+    // they are latency, not rounds.  Two groups only with the prior tables staged (as the priors were created).
     int nsub = 1;
     const bool whole = r->cur_group.n <= 1 || (B % (2 * ti) == 0 && r->cur_group.each % (2 * ti) == 0);
     if (tables && g_eng.setup_threads == 0 && g_eng.setup_sub != 1 && ti == SETUP_TI && whole && B > (int64_t)ti * g_eng.n_cu
-        && setup_lds_bytes(r, mode, has_prior, 2) <= 160 * 1024) {
+        && setup_lds_layout(r, mode, 2, has_prior ? r->pr->prog.stage_doubles : 0) <= 160 * 1024) {
         nsub = 2;
         threads = 1024;
     }
     const unsigned blocks = (unsigned)((B + (int64_t)ti * nsub - 1) / ((int64_t)ti * nsub));
     const size_t lds = setup_lds_bytes(r, mode, has_prior, nsub);
     if (lds > 160 * 1024) return fail(NFA_ERR_ARG, "too many parameters for the set-up kernel");
+    const PriorProg *prog = setup_prog(r, mode, has_prior, nsub);
     auto kern = nsub == 2 ? setup_kernel<0, false, 2> : tables ? setup_kernel<0, false> : mode == 2 ? setup_kernel<1, true> : setup_kernel<1, false>;
     { int rc2 = ensure_dynamic_lds((const void *)kern, lds); if (rc2) return rc2; }
     (void)d_U;                                               // the batches' arrays travel in r->cur_group
@@ -1228,7 +1250,7 @@ template <int MODE, int NCOMP>
 static void launch_point_t(nfa_runner *r, const SpecDev &S, const PointIn &in, const LnlGeom &G, size_t lds) {
     auto kern = point_kernel<MODE, NCOMP>;
     (void)ensure_dynamic_lds((const void *)kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)in.n), dim3(POINT_THREADS), lds, r->lanes[0], (const PriorProg *)r->pr->d_prog, S, in,
+    hipLaunchKernelGGL(kern, dim3((unsigned)in.n), dim3(POINT_THREADS), lds, r->lanes[0], setup_prog(r, 1, true), S, in,
                        r->d_pix, r->d_U, r->d_D[0], r->d_part[0], r->d_point, r->d_point_done, G,
                        (const double *)g_eng.d_tabs);
 }

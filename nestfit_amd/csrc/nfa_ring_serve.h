@@ -171,7 +171,7 @@ template <int MODE, int NCOMP>
 static int launch_ring_serve_t(nfa_runner *r, const SpecDev &S, const RingServeArgs &A, const LnlGeom &G, size_t lds, int n_wg) {
     auto kern = ring_serve_kernel<MODE, NCOMP>;
     { int rc = ensure_dynamic_lds((const void *)kern, lds); if (rc) return rc; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(POINT_THREADS), lds, r->lanes[0], (const PriorProg *)r->pr->d_prog, S, A,
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(POINT_THREADS), lds, r->lanes[0], setup_prog(r, 1, true), S, A,
                        r->d_pix, r->d_U, r->d_D[0], r->d_part[0], G, (const double *)g_eng.d_tabs);
     HIP_TRY(hipGetLastError());
     return NFA_OK;

@@ -28,6 +28,7 @@ def _prior_sets(na):
     d_sep = na.Distribution(3 * u + 0.7, stats.beta(1.5, 3.5).pdf(u))
     d_s = na.Distribution(2 * u + 0.067, stats.beta(1.5, 5).pdf(u))
     d_t = na.Distribution(23 * u + 7, stats.beta(3, 6.7).pdf(u))
+    d_vw = na.Distribution(80 * u - 40, stats.beta(5, 5).pdf(u))
     rest = [na.DuplicatePrior(d_t, 1, 2), na.Prior(d_t, 3), na.ConstantPrior(0.25, 5)]
     return {
         'ordered': [na.OrderedPrior(d_v, 0), na.Prior(d_s, 4)] + rest,
@@ -38,11 +39,33 @@ def _prior_sets(na):
         'rplace_wide': [na.ResolvedPlacementPrior(na.Prior(d_v, 0), na.Prior(d_s, 4), scale=6.0)] + rest,
         'irdc': list(na.get_irdc_priors(size=500).priors),
         'synth': list(na.get_synth_priors(size=500).priors),
+        # up to ten components (MAXCOMP): the minimum separations of the sets above overflow the 8 km/s axis in most
+        # draws at high counts (Degenerate), so these place them on +-40 km/s, with sigma <= 1 km/s for the irdc shape
+        'rplace_wide_axis': [na.ResolvedPlacementPrior(na.Prior(d_vw, 0), na.Prior(d_s, 4), scale=1.2)] + rest,
+        'irdc_wide_axis': irdc_wide_axis(na, size=500),
     }
 
 
+def irdc_wide_axis(na, size=500, vhalf=40.0, sigm_hi=1.0):
+    """get_irdc_priors' five priors and table size on a velocity axis of +-vhalf km/s and sigma in [0.067, sigm_hi]:
+    its draws are never degenerate up to ten components while 9 * 1.2 * FWHM * sigm_hi < 2 * vhalf."""
+    from scipy import stats
+    u = np.linspace(0, 1, size)
+    d_voff = na.Distribution(2 * vhalf * u - vhalf, stats.beta(5.0, 5.0).pdf(u))
+    d_sigm = na.Distribution((sigm_hi - 0.067) * u + 0.067, stats.beta(1.5, 5.0).pdf(u))
+    return [na.ResolvedPlacementPrior(na.Prior(d_voff, 0), na.Prior(d_sigm, 4), scale=1.2),
+            na.Prior(na.Distribution(23.00 * u + 7.00, stats.beta(3.0, 6.7).pdf(u)), 1),
+            na.Prior(na.Distribution(9.26 * u + 2.80, stats.beta(1.0, 2.5).pdf(u)), 2),
+            na.Prior(na.Distribution(4.00 * u + 12.50, stats.beta(10.0, 8.5).pdf(u)), 3),
+            na.ConstantPrior(0, 5)]
+
+
 def _ncomps(name):
-    return (1, 2) if name in ('censep', 'rcensep', 'synth') else (1, 2, 3, 4)       # n <= 2: core.pyx:316-318, 364-366
+    if name in ('censep', 'rcensep', 'synth'):
+        return (1, 2)                                # n <= 2: core.pyx:316-318, 364-366
+    if name in ('rplace', 'rplace_wide', 'irdc'):
+        return (1, 2, 3, 4)                          # beyond: mostly Degenerate on their 8 km/s axis (the *_wide_axis sets)
+    return tuple(range(1, 11))                       # up to MAXCOMP
 
 
 def test_oracle_prior_transforms_against_closed_forms(nfo):
