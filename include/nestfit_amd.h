@@ -170,8 +170,24 @@ int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, c
                                      const double *chan_noise);
 int nfa_specset_destroy(nfa_specset *ss);
 int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data);
-/* null_lnZ[n_pix][n_spec] = -sum(data^2)/(2 noise^2)   (core.pyx:517-520) */
+/* null_lnZ[n_pix][n_spec] = -sum(data^2)/(2 noise^2)   (core.pyx:517-520); with a baseline, the baseline-only model:
+ * -chi2_min(p = 0) / (2 sigma_ref^2) (nfa_specset_set_baseline) */
 int nfa_specset_null_lnz(const nfa_specset *ss, double *out);
+/* A polynomial baseline of degree <= order per (pixel, spectrum), profiled out of the likelihood in closed form (no sampler
+ * dimension).  With weights w_c (1 for a scalar noise, (sigma_ref / sigma_c)^2 for a channel noise, 0 where masked),
+ * residual r = d - p(theta) and V_K the polynomials of degree <= K in the channel index of the spectrum:
+ *     chi2_min,s = min_{b in V_K} sum_c w_c (r_c - b_c)^2,    lnL = -sum_s chi2_min,s / (2 sigma_ref,s^2)
+ * That is the marginal likelihood under a flat prior on the baseline's coefficients up to a factor that depends only on the
+ * pixel, its weights and K -- the same for nfa_specset_null_lnz, which then returns the baseline-only model, and for every
+ * ncomp: differences of lnZ are Bayes factors of baseline-marginalised models.  A spectrum with n <= K unmasked channels
+ * gets degree n - 1 (its chi2_min is 0).
+ * order = -1 removes the baseline (the set's former results bit for bit), 0..NFA_BASELINE_MAX sets it; anything else
+ * returns NFA_ERR_ARG.  Batches held for coalescing are launched first (as by nfa_set_option) and the device is
+ * synchronised: call it between batches, not while one of this set's runners is in flight.  nfa_specset_set_data keeps
+ * the order.  Spectra out are unchanged: the model without the baseline.  Single points of such a set go through the
+ * batch kernels, and nfa_ring_serve_device refuses its runners (NFA_ERR_ARG; nfa_ring_serve serves them). */
+#define NFA_BASELINE_MAX 3
+int nfa_specset_set_baseline(nfa_specset *ss, int order);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

@@ -9,6 +9,49 @@ from . import _ffi
 from .core import Runner, _as_inplace_matrix, _as_inplace_vector
 
 MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_GAUSSIAN = 0, 1, 2
+BASELINE_MAX = 3          # NFA_BASELINE_MAX
+
+
+def check_baseline_order(order):
+    """`baseline_order` of a runner: None (or -1) for no baseline, else an integer 0..BASELINE_MAX; ValueError otherwise."""
+    if order is None:
+        return None
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)):
+        raise ValueError(f'baseline_order must be None or an integer in -1..{BASELINE_MAX}, not {order!r}')
+    order = int(order)
+    if not -1 <= order <= BASELINE_MAX:
+        raise ValueError(f'baseline_order must be None or an integer in -1..{BASELINE_MAX}, not {order}')
+    return None if order == -1 else order
+
+
+def baseline_fit(resid, weight, order):
+    """Best-fit baselines of residual spectra resid[..., N] under channel weights weight[..., N] (0: masked, whose residual
+    is ignored; the scale of the weights does not matter): the polynomial of degree <= `order` in the channel index that
+    minimises sum w (r - b)^2, evaluated at every channel -- the likelihood's baseline, on the host with numpy.
+    Legendre basis of u = (2j - (N - 1)) / (N - 1); with n <= order weighted channels the degree is n - 1, with none 0."""
+    resid = np.asarray(resid, dtype=np.float64)
+    n = resid.shape[-1]
+    weight = np.broadcast_to(np.asarray(weight, dtype=np.float64), resid.shape)
+    u = (2.0 * np.arange(n) - (n - 1)) / (n - 1) if n > 1 else np.zeros(n)
+    flat_r, flat_w = resid.reshape(-1, n), weight.reshape(-1, n)
+    out = np.zeros_like(flat_r)
+    for i, (r, w) in enumerate(zip(flat_r, flat_w)):
+        live = w > 0
+        k = min(int(order), int(live.sum()) - 1)
+        if k < 0:
+            continue
+        V = np.polynomial.legendre.legvander(u, k)
+        sw = np.sqrt(w[live])
+        coef = np.linalg.lstsq(V[live] * sw[:, None], r[live] * sw, rcond=None)[0]
+        out[i] = V @ coef
+    return out.reshape(resid.shape)
+
+
+def channel_weights(noise, size):
+    """Relative channel weights 1 / sigma_c^2 of one spectrum (a scalar noise: ones; inf: 0)."""
+    if np.ndim(noise) == 0:
+        return np.ones(size)
+    return 1.0 / np.asarray(noise, dtype=np.float64) ** 2
 
 
 class _SpecSet:
@@ -46,6 +89,14 @@ class _SpecSet:
             _ffi.dptr(data), _ffi.dptr(noise)))
         self.handle = h
         self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
+        self.baseline_order = None
+
+    def set_baseline(self, order):
+        """A polynomial baseline of degree <= `order` per (pixel, spectrum) profiled out of the likelihood, or none
+        (None / -1): nfa_specset_set_baseline.  null_lnZ() then is the baseline-only model's."""
+        order = check_baseline_order(order)
+        _ffi.check(_ffi.load().nfa_specset_set_baseline(self.handle, -1 if order is None else order))
+        self.baseline_order = order
 
     def null_lnZ(self):
         out = np.empty((self.n_pix, self.n_spec))
@@ -157,8 +208,13 @@ class EngineRunner(Runner):
     MODEL = MODEL_AMMONIA
     N_MODEL = 6
 
-    def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None):
+    def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None):
+        """baseline_order: None, or 0..3 for a polynomial baseline of that degree per spectrum, profiled out of the
+        likelihood in closed form (nfa_specset_set_baseline).  null_lnZ is then the baseline-only model's, from
+        the runner's own spectra set (the spectra keep the reference's spectrum-alone value), and lnZ - null_lnZ is a Bayes
+        factor of baseline-marginalised models."""
         assert ncomp > 0
+        baseline_order = check_baseline_order(baseline_order)
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -179,6 +235,27 @@ class EngineRunner(Runner):
         self._ss = _SpecSet([s.xarr for s in spectra], [s.trans_id for s in spectra], data, noise,
                             model=self.MODEL, rest_freqs=rest_freqs)
         self._run = _RunnerHandle(self._ss, utrans, self.ncomp, cold, lte)
+        self.baseline_order = baseline_order
+        if baseline_order is not None:
+            self._ss.set_baseline(baseline_order)
+            self.null_lnZ = float(self._ss.null_lnZ().sum())
+
+    def _model_spectra(self):
+        return list(self.spectra)
+
+    def fit_baseline(self, params):
+        """Best-fit baseline of every spectrum for physical `params` (after `predict`, which this calls): one array of
+        n_chan_tot values, the spectra concatenated.  numpy on the host (`baseline_fit`): for residual plots, not the hot
+        path.  ValueError without a baseline."""
+        if self.baseline_order is None:
+            raise ValueError('this runner has no baseline (baseline_order=None)')
+        self.predict(params)
+        out = []
+        for s in self._model_spectra():
+            w = channel_weights(s.noise, s.size)
+            resid = np.where(w > 0, s.data - s.get_spec(), 0.0)
+            out.append(baseline_fit(resid, w, self.baseline_order))
+        return np.concatenate(out)
 
     def set_exp_mode(self, mode):
         """Numerical mode of this runner alone (None: the process default again): runners of different

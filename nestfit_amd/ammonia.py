@@ -5,7 +5,7 @@ behaviour; all arithmetic runs in the HIP engine through the C ABI.
 import numpy as np
 
 from ._model import (MODEL_AMMONIA, EngineRunner, EngineSpectrumMixin, _pix_ptr, _RunnerHandle,  # noqa: F401
-                     _SpecSet, par_names)
+                     _SpecSet, check_baseline_order, par_names)
 from .core import HyperfineSpectrum
 
 N_LEVELS = 9
@@ -55,15 +55,17 @@ class AmmoniaRunner(EngineRunner):
     MODEL = MODEL_AMMONIA
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False):
+    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None):
         assert ncomp > 0
+        baseline_order = check_baseline_order(baseline_order)
         self.spectra = list(spectra)
         self.cold = bool(cold)
         self.lte = bool(lte)
-        self._setup(self.spectra, utrans, ncomp, self.cold, self.lte)
+        self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, baseline_order=baseline_order)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
+        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         spectra = np.array([AmmoniaSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

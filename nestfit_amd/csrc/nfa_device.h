@@ -92,7 +92,43 @@ struct SpecDev {
     // [0, 1] per channel, 0 where sigma_c = inf masks the channel (whose `data` are then 0); wdata = chan_w * data.
     // [n_pix][chan_tot] both, like `data`.  chi^2 becomes sum w (d - p)^2 and -chi^2 / (2 sigma_ref^2) the likelihood.
     const double *chan_w, *wdata;
+    // Spectra sets with a polynomial baseline per spectrum (nfa_specset_set_baseline; null and -1 without one), which are
+    // always weighted (a scalar noise: chan_w == 1): [n_pix][n_spec][NFA_BL_REC] records of bl_setup_kernel (below).
+    const double *bl;
+    int     bl_order;
 };
+
+// Baseline record of a (pixel, spectrum), DESIGN 4.5: [0, 4) m_k(d) = sum_j w_j P_k(u_j) d_j, the Legendre moments of the
+// data; [4, 14) L^-1 packed by rows (L00, L10, L11, L20, ...), G = L L^T the Gram matrix G_kl = sum_j w_j P_k(u_j) P_l(u_j)
+// of the basis P_0..P_order.  A direction the Cholesky factorisation drops (pivot <= 1e-12 G_kk) and the orders above
+// bl_order have zero rows and columns, so that ||L^-1 e||^2 is the weighted least-squares fit of e over the rest.
+#define NFA_BL_REC 16
+#define NFA_BL_NB  4            // moments every baseline form accumulates: P_0..P_3, whatever the order
+
+// P_1..P_3 of u = (2 j - (N - 1)) / (N - 1), ui = 1 / (N - 1) (0 for N = 1: u = 0); P_0 = 1
+__device__ __forceinline__ void bl_basis(int j, int N, double ui, double &p1, double &p2, double &p3) {
+    const double u = (double)(2 * j - (N - 1)) * ui;
+    p1 = u;
+    p2 = __builtin_fma(1.5 * u, u, -0.5);                   // (3 u^2 - 1) / 2
+    p3 = u * __builtin_fma(2.5 * u, u, -1.5);               // (5 u^3 - 3 u) / 2
+}
+
+// ||L^-1 e||^2, e = m(d) - m(p), of the record R: the chi^2 the best baseline takes away (rows in order)
+__device__ __forceinline__ double bl_quad(const double *R, const double *mp) {
+    double e[NFA_BL_NB];
+#pragma unroll
+    for (int k = 0; k < NFA_BL_NB; ++k) e[k] = R[k] - mp[k];
+    double q = 0.0;
+    int o = NFA_BL_NB;
+#pragma unroll
+    for (int i = 0; i < NFA_BL_NB; ++i) {
+        double y = 0.0;
+#pragma unroll
+        for (int k = 0; k <= i; ++k) y = __builtin_fma(R[o++], e[k], y);
+        q = __builtin_fma(y, y, q);
+    }
+    return q;
+}
 
 // derived-parameter record of one item (doubles), written by setup_kernel (nfa_setup.h):
 //   [c*4 + 0] tex  [c*4 + 1] sigm/CKMS  [c*4 + 2] voff/CKMS  [c*4 + 3] 1/tex
@@ -762,7 +798,9 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // exponential tables (n_shared doubles at the start of smem), the line tables follow them.
 // WEIGHTED: the spectra set has a noise per channel (SpecDev.chan_w); chi^2 = sum w d^2 + sum p (w p - 2 w d), whose
 // operations with w == 1.0 are exactly those of the unweighted form (multiplying by 1.0 changes no bits).
-template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false>
+// BASELINE (weighted sets only): a polynomial baseline per spectrum is profiled out, chi^2_min = that chi^2 minus
+// ||L^-1 (m(d) - m(p))||^2 (SpecDev.bl); the moments m_k(p) = sum w P_k(u) p are summed like chi^2 itself.
+template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -818,7 +856,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     LineRec *w_line = (LineRec *)(smem + n_shared + (size_t)ulocal * G.wave_doubles);
     int2 *w_win = (int2 *)(w_line + (NCOMP > 0 ? NCOMP : S.ncomp) * G.nhf_max);   // the windows [lo, hi) follow the table
     // split > 1: the parts' per-lane sums meet here, [unit of the workgroup][part][lane]
-    double *w_part = smem + n_shared + (size_t)upw * G.wave_doubles + (size_t)ulocal * (LNL_PARTS * 64);
+    // (BASELINE: the parts' moment sums follow, [unit][1 + k][part][lane])
+    double *w_part = smem + n_shared + (size_t)upw * G.wave_doubles + (size_t)ulocal * (LNL_PARTS * 64 * (BASELINE ? 1 + NFA_BL_NB : 1));
     if (unit >= units) {
         if (split > 1) { __syncthreads(); __syncthreads(); }         // the two barriers of the waves at work
         return;
@@ -951,9 +990,18 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     constexpr bool SPEC_DEFER = WRITE_SPEC && MODE == 2;
     double pend_v = 0.0;                                           // spectra out: the row whose store is still to be issued
     int pend_j = -1;
+    // BASELINE: the moments m_k(p) of the lane's channels, per part (bl_acc) and over the parts in part order (bl_tot)
+    static_assert(!BASELINE || (WEIGHTED && !DYN), "the baseline form is a weighted batch form");
+    constexpr int NBL = BASELINE ? NFA_BL_NB : 1;
+    double bl_acc[NBL], bl_tot[NBL];
+#pragma unroll
+    for (int k = 0; k < NBL; ++k) bl_tot[k] = 0.0;
+    const double bl_ui = BASELINE && N > 1 ? 1.0 / (double)(N - 1) : 0.0;
     for (int hp = 0; hp < parts_per_wave; ++hp) {
     const int h = rpart * parts_per_wave + hp;                 // part h = rows h, h + LNL_PARTS, h + 2 LNL_PARTS, ...
     acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < NBL; ++k) bl_acc[k] = 0.0;
     for (int row = h; row < n_rows; row += LNL_PARTS) {
         const int r0 = row << 6;
         const int j = r0 + lane;
@@ -1217,19 +1265,48 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
             else if (WRITE_SPEC) { if (valid) __builtin_nontemporal_store(pred, so + j); }
             // lanes beyond N: pred = 0
             if (any) acc = __builtin_fma(pred, __builtin_fma(-2.0, dj, WEIGHTED ? wj * pred : pred), acc);
+            if (BASELINE && any) {                                 // (lanes beyond N and masked channels: w p = 0)
+                const double wp = wj * pred;
+                double p1, p2, p3;
+                bl_basis(j, N, bl_ui, p1, p2, p3);
+                bl_acc[0] += wp;
+                bl_acc[1 % NBL] = __builtin_fma(wp, p1, bl_acc[1 % NBL]);
+                bl_acc[2 % NBL] = __builtin_fma(wp, p2, bl_acc[2 % NBL]);
+                bl_acc[3 % NBL] = __builtin_fma(wp, p3, bl_acc[3 % NBL]);
+            }
         }
     }
-    if (split == 1) tot += acc; else w_part[h * 64 + lane] = acc;
+    if (split == 1) {
+        tot += acc;
+#pragma unroll
+        for (int k = 0; k < NBL && BASELINE; ++k) bl_tot[k] += bl_acc[k];
+    } else {
+        w_part[h * 64 + lane] = acc;
+#pragma unroll
+        for (int k = 0; k < NBL && BASELINE; ++k) w_part[((1 + k) * LNL_PARTS + h) * 64 + lane] = bl_acc[k];
+    }
     }
     if (SPEC_DEFER && pend_j >= 0) __builtin_nontemporal_store(pend_v, so + pend_j);
     if (split > 1) {
         __syncthreads();
         if (rpart != 0) return;
         for (int h = 0; h < LNL_PARTS; ++h) tot += w_part[h * 64 + lane];
+#pragma unroll
+        for (int k = 0; k < NBL && BASELINE; ++k)
+            for (int h = 0; h < LNL_PARTS; ++h) bl_tot[k] += w_part[((1 + k) * LNL_PARTS + h) * 64 + lane];
     }
     tot = wave_sum(tot);
+    double bl_q = 0.0;                                             // BASELINE: what the best baseline takes away
+    if (BASELINE) {
+#pragma unroll
+        for (int k = 0; k < NBL; ++k) bl_tot[k] = wave_sum(bl_tot[k]);
+        bl_q = bl_quad(S.bl + (p_ix * nspec + s) * NFA_BL_REC, bl_tot);
+    }
     // sum of squared deviations of the unit; lnl_sum_kernel scales and adds
-    if (lane == 0 && part) part[unit] = S.totsq[p_ix * nspec + s] + tot;
+    if (lane == 0 && part) {
+        if (BASELINE) part[unit] = (S.totsq[p_ix * nspec + s] + tot) - bl_q;
+        else part[unit] = S.totsq[p_ix * nspec + s] + tot;
+    }
 }
 
 // WIDE (fast mode only): the spectra set holds a transition with more than 26 lines (N2H+)
@@ -1269,6 +1346,19 @@ lnl_kernel_wt(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *_
     const double *sm = smem;
     if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
     lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+}
+
+// lnl_kernel of a spectra set with a baseline (SpecDev.bl; always weighted): every mode, WIDE and spectra out, one
+// instance for all orders (the four moments are always formed; the record's rows above the order are zero)
+template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_bl(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+              double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP, false, true, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one
@@ -1500,3 +1590,103 @@ __device__ __forceinline__ void null_lnz_body(const SpecDev &S, long n_pix, doub
 }
 __global__ void null_lnz_kernel(SpecDev S, long n_pix, double *__restrict__ out) { null_lnz_body<false>(S, n_pix, out); }
 __global__ void null_lnz_w_kernel(SpecDev S, long n_pix, double *__restrict__ out) { null_lnz_body<true>(S, n_pix, out); }
+
+// Baseline records (SpecDev.bl, NFA_BL_REC) of pixels [pix0, pix0 + n_pix): one wave per (pixel, spectrum).  m_k(d) =
+// sum_j wdata_j P_k(u_j) always; with form_basis also the Gram matrix G_kl = sum_j w_j P_k P_l of P_0..P_order, its
+// Cholesky factor L (a pivot <= 1e-12 G_kk drops that direction: a spectrum with n <= order unmasked channels gets order
+// n - 1, one with none adds nothing) and L^-1 -- nfa_specset_set_data keeps the basis and forms the moments again.
+__global__ void bl_setup_kernel(SpecDev S, long pix0, long n_pix, double *__restrict__ bl, int form_basis) {
+    const int lane = threadIdx.x & 63;
+    const long w = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (w >= n_pix * S.n_spec) return;
+    const long p = pix0 + w / S.n_spec;
+    const int s = (int)(w - (p - pix0) * S.n_spec);
+    const int N = S.size[s];
+    const double ui = N > 1 ? 1.0 / (double)(N - 1) : 0.0;
+    const double *wd = S.wdata + p * S.chan_tot + S.off[s], *wc = S.chan_w + p * S.chan_tot + S.off[s];
+    double m[NFA_BL_NB], g[NFA_BL_NB][NFA_BL_NB];
+#pragma unroll
+    for (int k = 0; k < NFA_BL_NB; ++k) {
+        m[k] = 0.0;
+#pragma unroll
+        for (int l = 0; l < NFA_BL_NB; ++l) g[k][l] = 0.0;
+    }
+    for (int j = lane; j < N; j += 64) {
+        double P[NFA_BL_NB];
+        P[0] = 1.0;
+        bl_basis(j, N, ui, P[1], P[2], P[3]);
+        const double x = wd[j];
+#pragma unroll
+        for (int k = 0; k < NFA_BL_NB; ++k) m[k] = __builtin_fma(x, P[k], m[k]);
+        if (form_basis) {
+            const double wj = wc[j];
+#pragma unroll
+            for (int k = 0; k < NFA_BL_NB; ++k)
+#pragma unroll
+                for (int l = 0; l <= k; ++l) g[k][l] = __builtin_fma(wj * P[k], P[l], g[k][l]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NFA_BL_NB; ++k) m[k] = wave_sum(m[k]);
+    double *R = bl + (p * S.n_spec + s) * NFA_BL_REC;
+    if (form_basis) {
+#pragma unroll
+        for (int k = 0; k < NFA_BL_NB; ++k)
+#pragma unroll
+            for (int l = 0; l <= k; ++l) g[k][l] = wave_sum(g[k][l]);
+    }
+    if (lane != 0) return;
+#pragma unroll
+    for (int k = 0; k < NFA_BL_NB; ++k) R[k] = m[k];
+    if (!form_basis) return;
+    // G = L L^T over the kept directions of P_0..P_order (L's other rows and columns: 0)
+    const int K = S.bl_order;
+    double L[NFA_BL_NB][NFA_BL_NB], M[NFA_BL_NB][NFA_BL_NB];
+    bool keep[NFA_BL_NB];
+#pragma unroll
+    for (int i = 0; i < NFA_BL_NB; ++i) {
+#pragma unroll
+        for (int k = 0; k < NFA_BL_NB; ++k) { L[i][k] = 0.0; M[i][k] = 0.0; }
+        keep[i] = false;
+        if (i > K) continue;
+#pragma unroll
+        for (int k = 0; k < i; ++k) {
+            if (!keep[k]) continue;
+            double v = g[i][k];
+            for (int l = 0; l < k; ++l) v -= L[i][l] * L[k][l];
+            L[i][k] = v / L[k][k];
+        }
+        double d = g[i][i];
+        for (int l = 0; l < i; ++l) d -= L[i][l] * L[i][l];
+        keep[i] = d > 1e-12 * g[i][i];
+        if (keep[i]) L[i][i] = sqrt(d);
+        else for (int k = 0; k < i; ++k) L[i][k] = 0.0;
+    }
+    // M = L^-1 by forward substitution (a dropped direction: its row and column stay 0)
+#pragma unroll
+    for (int i = 0; i < NFA_BL_NB; ++i) {
+        if (!keep[i]) continue;
+        M[i][i] = 1.0 / L[i][i];
+        for (int k = 0; k < i; ++k) {
+            double v = 0.0;
+            for (int l = k; l < i; ++l) v += L[i][l] * M[l][k];
+            M[i][k] = -v * M[i][i];
+        }
+    }
+    int o = NFA_BL_NB;
+#pragma unroll
+    for (int i = 0; i < NFA_BL_NB; ++i)
+#pragma unroll
+        for (int k = 0; k <= i; ++k) R[o++] = M[i][k];
+}
+
+// null_lnZ of a set with a baseline: -(totsq - ||L^-1 m(d)||^2) / (2 sigma_ref^2), the likelihood's own value at p = 0
+// (lnl_body: tot = 0 and m(p) = 0 there).  One lane per (pixel, spectrum).
+__global__ void null_lnz_bl_kernel(SpecDev S, long n_pix, double *__restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix * S.n_spec) return;
+    const double zero[NFA_BL_NB] = {0.0, 0.0, 0.0, 0.0};
+    const double chi2 = (S.totsq[i] + 0.0) - bl_quad(S.bl + i * NFA_BL_REC, zero);
+    const double noise = S.noise[i];
+    out[i] = -chi2 / (2 * (noise * noise));
+}

@@ -189,6 +189,8 @@ struct nfa_specset {
     double *d_xarr = nullptr, *d_t0 = nullptr, *d_tbg = nullptr, *d_data = nullptr, *d_noise = nullptr;
     double *d_t0tbg = nullptr, *d_rowsq = nullptr, *d_totsq = nullptr;
     double *d_w = nullptr, *d_wdata = nullptr;     // a noise per channel: SpecDev.chan_w, .wdata (null otherwise)
+    double *d_bl = nullptr;                         // a baseline: SpecDev.bl (nfa_specset_set_baseline)
+    bool    bl_w1 = false;                          // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
 };
 
 struct nfa_priors {
@@ -382,6 +384,16 @@ static int launch_chan_weight(nfa_specset *ss, int64_t pix0, int64_t n, bool for
     return NFA_OK;
 }
 
+// baseline records of pixels [pix0, pix0 + n) (form_basis: the Gram matrix and L^-1 too, not only m(d))
+static int launch_bl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_basis) {
+    const int64_t waves = n * ss->dev.n_spec;
+    hipLaunchKernelGGL(bl_setup_kernel, dim3((unsigned)((waves * 64 + 255) / 256)), dim3(256), 0, 0, ss->dev,
+                       (long)pix0, (long)n, ss->d_bl, (int)form_basis);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return NFA_OK;
+}
+
 static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *sizes, const int32_t *trans_ids,
                         const double *rest_freqs, const double *const *xarr, int64_t n_pix, const double *data,
                         const double *noise, const double *chan_noise) {
@@ -450,6 +462,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     HIP_TRY(hipGetLastError());
     d.xarr = ss->d_xarr; d.t0 = ss->d_t0; d.tbg = ss->d_tbg; d.data = ss->d_data; d.noise = ss->d_noise;
     d.t0tbg = ss->d_t0tbg; d.rowsq = ss->d_rowsq; d.totsq = ss->d_totsq;
+    d.bl = nullptr; d.bl_order = -1;                                    // no baseline (nfa_specset_set_baseline)
     if (chan_noise) {
         HIP_TRY(hipMalloc(&ss->d_w, sizeof(double) * tot * n_pix));
         HIP_TRY(hipMalloc(&ss->d_wdata, sizeof(double) * tot * n_pix));
@@ -522,7 +535,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     if (!ss) return NFA_OK;
     (void)hipFree(ss->d_xarr); (void)hipFree(ss->d_t0); (void)hipFree(ss->d_tbg); (void)hipFree(ss->d_data); (void)hipFree(ss->d_noise);
     (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq);
-    (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata);
+    (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl);
     delete ss;
     return NFA_OK;
 }
@@ -533,7 +546,47 @@ int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data) {
     HIP_TRY(hipMemcpy(ss->d_data + pix * ss->dev.chan_tot, data, sizeof(double) * ss->dev.chan_tot,
                       hipMemcpyHostToDevice));
     if (ss->dev.chan_w) { rc = launch_chan_weight(ss, pix, 1, false); if (rc) return rc; }      // the mask stays
-    return launch_rowsq(ss, pix, 1);
+    rc = launch_rowsq(ss, pix, 1); if (rc) return rc;
+    return ss->dev.bl ? launch_bl_setup(ss, pix, 1, false) : NFA_OK;                             // the basis stays
+}
+
+int nfa_specset_set_baseline(nfa_specset *ss, int order) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
+    int rc = engine_init(); if (rc) return rc;
+    // held batches were accepted for the old likelihood, launches in flight read the buffers changed here, and a runner's
+    // captured single-point graph holds the old SpecDev
+    rc = flush_all_runners(); if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    {
+        std::lock_guard<std::mutex> lk(g_runners_m);
+        for (nfa_runner *r : g_runners)
+            if (r->ss == ss) { RUNNER_LOCK(r); if (r->g1) { (void)hipGraphExecDestroy(r->g1); r->g1 = nullptr; } }
+    }
+    SpecDev &d = ss->dev;
+    if (order < 0) {
+        if (ss->bl_w1) {                  // back to the scalar set, whose totsq the w == 1 form left as they were
+            (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata);
+            ss->d_w = ss->d_wdata = nullptr; d.chan_w = d.wdata = nullptr;
+            ss->bl_w1 = false;
+        }
+        (void)hipFree(ss->d_bl);
+        ss->d_bl = nullptr; d.bl = nullptr; d.bl_order = -1;
+        return NFA_OK;
+    }
+    const size_t n = (size_t)(ss->n_pix * d.chan_tot);
+    if (!d.chan_w) {                      // a scalar noise runs as the weighted form with w == 1: its bits
+        HIP_TRY(hipMalloc(&ss->d_w, sizeof(double) * n));
+        HIP_TRY(hipMalloc(&ss->d_wdata, sizeof(double) * n));
+        ss->bl_w1 = true;
+        std::vector<double> one(n, 1.0);
+        HIP_TRY(hipMemcpy(ss->d_w, one.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
+        rc = launch_chan_weight(ss, 0, ss->n_pix, false); if (rc) return rc;
+    }
+    if (!ss->d_bl) HIP_TRY(hipMalloc(&ss->d_bl, sizeof(double) * NFA_BL_REC * ss->n_pix * d.n_spec));
+    d.bl = ss->d_bl; d.bl_order = order;
+    return launch_bl_setup(ss, 0, ss->n_pix, true);
 }
 
 int nfa_specset_null_lnz(const nfa_specset *ss, double *out) {
@@ -541,8 +594,11 @@ int nfa_specset_null_lnz(const nfa_specset *ss, double *out) {
     const int64_t n = ss->n_pix * ss->dev.n_spec;
     double *d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(double) * n));
-    hipLaunchKernelGGL(ss->dev.chan_w ? null_lnz_w_kernel : null_lnz_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0,
-                       ss->dev, (long)ss->n_pix, d_out);
+    if (ss->dev.bl)                                           // the baseline-only model
+        hipLaunchKernelGGL(null_lnz_bl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
+    else
+        hipLaunchKernelGGL(ss->dev.chan_w ? null_lnz_w_kernel : null_lnz_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0,
+                           ss->dev, (long)ss->n_pix, d_out);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost);
     (void)hipFree(d_out);                                     // on every path
@@ -990,8 +1046,11 @@ static int launch_lnl_t(nfa_runner *r, const int *d_pix, int slot, double *d_lnL
 #endif
     const int64_t n_units = B * S.n_spec, wg_resident = (int64_t)g_eng.n_cu * (g_eng.lnl_queue_wg > 0 ? g_eng.lnl_queue_wg : table_wg_per_cu(r, waves));
     const bool weighted = S.chan_w != nullptr;                  // (lnl_kernel_wt: not the queue form)
+    const bool baseline = S.bl != nullptr;                      // (lnl_kernel_bl, always weighted: neither)
     if (MODE == 0 && !WIDE && !weighted && r->d_queue[slot] && lnl_uses_queue(r, S, B, 0)) G.queue = r->d_queue[slot];
-    size_t lds = sizeof(double) * ((size_t)n_shared + ((size_t)G.wave_doubles + (split > 1 ? LNL_PARTS * 64 : 0)) * (waves / split))
+    // split > 1: the parts' sums of the units of a workgroup (a baseline: and of the moments of each unit)
+    const size_t part_doubles = split > 1 ? (size_t)LNL_PARTS * 64 * (baseline ? 1 + NFA_BL_NB : 1) : 0;
+    size_t lds = sizeof(double) * ((size_t)n_shared + ((size_t)G.wave_doubles + part_doubles) * (waves / split))
                + (G.queue ? 16 : 0);
     if (MODE == 0) lds = std::max(lds, sizeof(double) * (size_t)(n_shared + SM_TABLE_TAIL));
     if (lds > 160 * 1024) return fail(NFA_ERR_ARG, "ncomp too large for the LDS line table");
@@ -1001,6 +1060,7 @@ static int launch_lnl_t(nfa_runner *r, const int *d_pix, int slot, double *d_lnL
     if constexpr (MODE == 0 && WS) kern = lnl_kernel_w8<MODE, WS, WIDE, NCOMP>;
     if constexpr (MODE == 0 && !WIDE) { if (G.queue) kern = lnl_kernel_queue<WS, NCOMP>; }
     if (weighted) kern = lnl_kernel_wt<MODE, WS, WIDE, NCOMP>;
+    if (baseline) kern = lnl_kernel_bl<MODE, WS, WIDE, NCOMP>;
     { int rc2 = ensure_dynamic_lds((const void *)kern, lds); if (rc2) return rc2; }
     const int64_t units = B * S.n_spec;
     const int64_t upw = waves / split;
@@ -1266,7 +1326,7 @@ static void launch_point_n(nfa_runner *r, const SpecDev &S, const PointIn &in, c
 
 static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, double *lnL, int64_t B) {
     const int ndim = r->ndim;
-    // (weighted spectra sets: the batch kernels, lnl_kernel_wt)
+    // (weighted spectra sets, baseline sets among them: the batch kernels, lnl_kernel_wt / lnl_kernel_bl)
     if (!g_eng.point || r->profiling || ndim > NFA_POINT_MAXDIM || lnl_wide(r) || r->ss->dev.chan_w || B > NFA_POINT_MAXB) return 0;
     const int mode = r->exp_mode >= 0 ? r->exp_mode : g_eng.exp_mode;
     const SpecDev S = runner_specdev(r);

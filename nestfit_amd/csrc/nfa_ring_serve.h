@@ -199,7 +199,8 @@ int nfa_ring_serve_device(nfa_ring *ring, nfa_runner *run, int lifetime_ms, int 
     if (run->ndim != h->ndim) return fail(NFA_ERR_ARG, "ring and runner disagree on ndim");
     if (h->max_points != 1) return fail(NFA_ERR_ARG, "the resident kernel serves one point per slot: use nfa_ring_serve for this ring");
     if (run->ndim > NFA_POINT_MAXDIM || lnl_wide(run)) return fail(NFA_ERR_ARG, "this runner's points go through the batch kernels: use nfa_ring_serve");
-    // (the resident kernel has no weighted form: it would compute the unweighted sum)
+    // (the resident kernel has no weighted form: it would compute the unweighted sum; nor a baseline form)
+    if (run->ss->dev.bl) return fail(NFA_ERR_ARG, "the resident kernel has no form for a baseline: use nfa_ring_serve");
     if (run->ss->dev.chan_w) return fail(NFA_ERR_ARG, "the resident kernel has no form for a noise per channel: use nfa_ring_serve");
     if (lifetime_ms <= 0) lifetime_ms = 20;
     if (lifetime_ms > 1000) lifetime_ms = 1000;

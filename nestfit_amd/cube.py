@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order
 from .core import _as_inplace_matrix
 
 
@@ -42,14 +42,21 @@ class CubeRunner:
     noise : array [n_pix, n_spec], K; or [n_pix, sum(len(x) for x in xarrs)], a noise per channel
         (inf masks a channel, whose data are then ignored: see `core.Spectrum`)
     utrans : PriorTransformer
+    baseline_order : None, or 0..3: a polynomial baseline of that degree per (pixel, spectrum), profiled out of the
+        likelihood in closed form; null_lnZ is then the baseline-only model's
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
-                 model=0, rest_freqs=None):
+                 model=0, rest_freqs=None, baseline_order=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz])."""
         assert ncomp > 0
+        baseline_order = check_baseline_order(baseline_order)
         self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs)
         self._run = _RunnerHandle(self._ss, utrans, ncomp, cold, lte)
+        self.baseline_order = baseline_order
+        if baseline_order is not None:
+            self._ss.set_baseline(baseline_order)
+        self._data, self._noise = data, noise                # (fit_baseline)
         self.utrans = utrans
         self.ncomp = int(ncomp)
         self.n_model = {0: 6, 1: 4, 2: 3}[int(model)]
@@ -102,6 +109,25 @@ class CubeRunner:
             self._run.handle, pix.ctypes.data_as(_ffi._ip), _ffi.dptr(theta), B,
             _ffi.dptr(spec) if want_spectra else None, _ffi.dptr(lnl)))
         return spec, lnl
+
+    def fit_baseline(self, pix, theta):
+        """Best-fit baselines [B, n_chan_tot] of physical parameter rows theta[B, ndim] against pixels pix[B]: the
+        polynomials the likelihood profiles out, fitted with numpy to data - predict_batch (for residual plots, not the
+        hot path).  ValueError without a baseline."""
+        if self.baseline_order is None:
+            raise ValueError('this runner has no baseline (baseline_order=None)')
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        spec, _ = self.predict_batch(pix, theta)
+        data = np.asarray(self._data, dtype=np.float64)[pix]
+        noise = np.asarray(self._noise, dtype=np.float64)[pix]
+        off = self._ss.offsets
+        out = np.empty_like(spec)
+        for k in range(self.n_spec):
+            sl = slice(off[k], off[k + 1])
+            w = 1.0 / noise[:, sl] ** 2 if self._ss.per_channel else np.ones_like(spec[:, sl])
+            resid = np.where(w > 0, data[:, sl] - spec[:, sl], 0.0)
+            out[:, sl] = baseline_fit(resid, w, self.baseline_order)
+        return out
 
     def peak_and_integrated(self, pix, theta):
         """max_spec and sum_spec of every spectrum for parameter rows (core.pyx:532-539 as

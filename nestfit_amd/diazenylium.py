@@ -5,7 +5,7 @@ nestfit/models/hyperfine.pyx:52-118).  Parameters per component: voff, tex, ltau
 """
 import numpy as np
 
-from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, par_names
+from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_baseline_order, par_names
 from .core import HyperfineSpectrum
 
 N_LEVELS = 3
@@ -46,13 +46,15 @@ class DiazenyliumRunner(EngineRunner):
     MODEL = MODEL_DIAZENYLIUM
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None):
         assert ncomp > 0
+        baseline_order = check_baseline_order(baseline_order)
         self.spectra = list(spectra)
-        self._setup(self.spectra, utrans, ncomp)
+        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
+        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         spectra = np.array([DiazenyliumSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

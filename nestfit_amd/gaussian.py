@@ -7,7 +7,7 @@ radiative-transfer pass.
 import numpy as np
 
 from . import core
-from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, par_names
+from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_baseline_order, par_names
 
 N_PARAMS = 3
 
@@ -33,17 +33,22 @@ class GaussianRunner(EngineRunner):
     MODEL = MODEL_GAUSSIAN
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectrum, utrans, ncomp=1):
+    def __init__(self, spectrum, utrans, ncomp=1, baseline_order=None):
         assert ncomp > 0
+        baseline_order = check_baseline_order(baseline_order)
         self.spectrum = spectrum
-        self._setup([spectrum], utrans, ncomp, rest_freqs=[float(spectrum.rest_freq)])
+        self._setup([spectrum], utrans, ncomp, rest_freqs=[float(spectrum.rest_freq)], baseline_order=baseline_order)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
+        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         return cls(Spectrum(*spec_data), utrans, **kwargs)
 
     def get_spectrum(self):
         return np.array(self.spectrum)
+
+    def _model_spectra(self):
+        return [self.spectrum]
 
     def predict(self, params):
         params = self._check_params(params)

@@ -420,6 +420,10 @@ class HdfStore:
         self.hdf.attrs.update({name: get(fitter) for name, get in FITTER_ATTRS})
         # the built-in sampler's named setting (sampler.PRECISION: margins of its bound's free rejections), where the results are
         self.hdf.attrs['sampler_precision'] = str(getattr(fitter, 'mn_kwargs', {}).get('precision') or 'default')
+        # the polynomial baseline profiled out of the likelihood (runner_kwargs['baseline_order']), -1 for none;
+        # a store without the attribute was fitted without one
+        order = (getattr(fitter, 'runner_kwargs', None) or {}).get('baseline_order')
+        self.hdf.attrs['baseline_order'] = -1 if order is None else int(order)
         quantum = getattr(fitter, 'nlive_quantum', 1)
         if quantum != 1:                 # a deviation from main.py:445-447 is written down where the results are
             self.hdf.attrs['nlive_quantum'] = int(quantum)
