@@ -17,6 +17,7 @@
 #include <mutex>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/nestfit_amd.h"
@@ -48,7 +49,7 @@ struct Engine {
     int    exp_mode = 2;             // "fast": see include/nestfit_amd.h, nfa_set_exp_mode
     int    wpb = 1;                  // waves per workgroup of the likelihood kernel (fast / poly mode): one -- a workgroup
                                      // retires, and its slot is refilled, wave by wave (4: -1.5 %, 8: -9 %, profiles/r02/sweep_lanes.txt)
-    int    wpb_table = 0;            // the same in table mode; 0 = chosen per spectra set (launch_lnl_t)
+    int    wpb_table = 0;            // the same in table mode; 0 = chosen per spectra set (table_waves)
     int    lnl_split = 0;            // waves per (item, spectrum) unit of the likelihood kernel: 1, 2, 4, or
                                      // 0 = by launch size (resolve_split).  The chi^2 of a unit is a sum of LNL_PARTS
                                      // row blocks in a fixed order whatever the split, so every evaluation is bitwise
@@ -89,6 +90,7 @@ struct Engine {
     double t0_xmin = 0, t0_xmax = 0, t0_inv_dx = 0;
 };
 static Engine g_eng;
+static const size_t LDS_PER_CU = 160 * 1024;      // LDS of a compute unit (gfx950), the most one workgroup can ask for
 struct nfa_runner;
 static int flush_pending(nfa_runner *r);
 static int flush_all_runners();
@@ -253,6 +255,8 @@ struct nfa_runner {
     std::recursive_mutex mu;
 };
 #define RUNNER_LOCK(r) std::lock_guard<std::recursive_mutex> runner_lock_((r)->mu)
+// numerical mode of a runner's launches: its own, or the process default at call time
+static int runner_mode(const nfa_runner *r) { return r->exp_mode >= 0 ? r->exp_mode : g_eng.exp_mode; }
 
 extern "C" {
 
@@ -818,7 +822,7 @@ int nfa_runner_set_exp_mode(nfa_runner *r, int mode) {
     r->exp_mode = mode;
     return NFA_OK;
 }
-int nfa_runner_get_exp_mode(const nfa_runner *r) { return !r ? -1 : r->exp_mode >= 0 ? r->exp_mode : g_eng.exp_mode; }
+int nfa_runner_get_exp_mode(const nfa_runner *r) { return !r ? -1 : runner_mode(r); }
 
 static int runner_reserve(nfa_runner *r, int64_t B, bool spec) {
     if (B > r->cap_B) {
@@ -848,8 +852,6 @@ static SpecDev runner_specdev(const nfa_runner *r) {
     return S;
 }
 
-// Set-up stage of a batch on stream lane `slot`: [unit cube -> theta in place] -> partition sums ->
-// derived records r->d_D[slot], one launch (setup_kernel, nfa_setup.h)
 // A kernel that wants more than 64 KB of dynamic LDS has to be told so -- once per kernel and size, not on every
 // launch (the attribute call is a trip into the runtime: 1-2 us of the ~10 the host spends on enqueueing a step).
 static int ensure_dynamic_lds(const void *kernel, size_t lds) {
@@ -891,29 +893,32 @@ static int reserve_lane(nfa_runner *r, int slot, int64_t B) {
     return NFA_OK;
 }
 
-// LDS of the set-up stage: exponential tables, theta + partition records + the prior program and `stage_doubles` of its tables
+// LDS of the set-up stage: exponential tables (`tables`: FastExp's product tables too, setup_uses_tables), theta +
+// partition records + the prior program and `stage_doubles` of its tables
 static bool setup_uses_tables(const nfa_runner *r, int mode) { return mode == 0 && r->ss->dev.model == NFA_MODEL_AMMONIA; }
-static size_t setup_lds_layout(const nfa_runner *r, int mode, int nsub, int stage_doubles) {
+static size_t setup_lds_layout(const nfa_runner *r, bool tables, int nsub, int stage_doubles) {
     const size_t work = (size_t)nsub * ((size_t)64 * r->ndim + (size_t)SETUP_TI * r->ncomp * QREC) + sizeof(PriorProg) / sizeof(double) + 1
                         + (size_t)stage_doubles;
-    return sizeof(double) * ((setup_uses_tables(r, mode) ? (SM_END_TABLE - SM_EXP2) : NFA_EXP2_N) + work);
+    return sizeof(double) * ((tables ? (SM_END_TABLE - SM_EXP2) : NFA_EXP2_N) + work);
 }
 // Whether a launch stages the prior tables the priors were created with.  Whether they fit is only known here: in the
 // table mode, 500-point irdc tables (10 of them staged) and 8 or more components need more than 160 KiB.  Such a launch
 // takes the copy of the program that reads the tables from global memory (nfa_priors::d_prog_global): the same values, so
 // the same bits, as priors created under option prior_stage 0.
-static bool setup_staged(const nfa_runner *r, int mode, bool has_prior, int nsub) {
-    return has_prior && r->pr->prog.n_stage > 0 && setup_lds_layout(r, mode, nsub, r->pr->prog.stage_doubles) <= 160 * 1024;
+static bool setup_staged(const nfa_runner *r, bool tables, bool has_prior, int nsub) {
+    return has_prior && r->pr->prog.n_stage > 0 && setup_lds_layout(r, tables, nsub, r->pr->prog.stage_doubles) <= LDS_PER_CU;
 }
-static size_t setup_lds_bytes(const nfa_runner *r, int mode, bool has_prior, int nsub = 1) {
-    return setup_lds_layout(r, mode, nsub, setup_staged(r, mode, has_prior, nsub) ? r->pr->prog.stage_doubles : 0);
+static size_t setup_lds_bytes(const nfa_runner *r, bool tables, bool has_prior, int nsub = 1) {
+    return setup_lds_layout(r, tables, nsub, setup_staged(r, tables, has_prior, nsub) ? r->pr->prog.stage_doubles : 0);
 }
-static const PriorProg *setup_prog(const nfa_runner *r, int mode, bool has_prior, int nsub = 1) {
+static const PriorProg *setup_prog(const nfa_runner *r, bool tables, bool has_prior, int nsub = 1) {
     if (!has_prior) return nullptr;
-    return (const PriorProg *)(setup_staged(r, mode, has_prior, nsub) ? r->pr->d_prog : r->pr->d_prog_global);
+    return (const PriorProg *)(setup_staged(r, tables, has_prior, nsub) ? r->pr->d_prog : r->pr->d_prog_global);
 }
 
-static int launch_setup(nfa_runner *r, double *d_U, int64_t B, bool has_prior, int slot, int mode) {
+// Set-up stage of a batch (the arrays travel in r->cur_group) on stream lane `slot`: [unit cube -> theta in place] ->
+// partition sums -> derived records r->d_D[slot], one launch (setup_kernel, nfa_setup.h)
+static int launch_setup(nfa_runner *r, int64_t B, bool has_prior, int slot, int mode) {
     const SpecDev S = runner_specdev(r);
     hipStream_t st = r->lanes[slot];
     int rc = reserve_lane(r, slot, B); if (rc) return rc;
@@ -934,17 +939,16 @@ static int launch_setup(nfa_runner *r, double *d_U, int64_t B, bool has_prior, i
     int nsub = 1;
     const bool whole = r->cur_group.n <= 1 || (B % (2 * ti) == 0 && r->cur_group.each % (2 * ti) == 0);
     if (tables && g_eng.setup_threads == 0 && g_eng.setup_sub != 1 && ti == SETUP_TI && whole && B > (int64_t)ti * g_eng.n_cu
-        && setup_lds_layout(r, mode, 2, has_prior ? r->pr->prog.stage_doubles : 0) <= 160 * 1024) {
+        && setup_lds_layout(r, tables, 2, has_prior ? r->pr->prog.stage_doubles : 0) <= LDS_PER_CU) {
         nsub = 2;
         threads = 1024;
     }
     const unsigned blocks = (unsigned)((B + (int64_t)ti * nsub - 1) / ((int64_t)ti * nsub));
-    const size_t lds = setup_lds_bytes(r, mode, has_prior, nsub);
-    if (lds > 160 * 1024) return fail(NFA_ERR_ARG, "too many parameters for the set-up kernel");
-    const PriorProg *prog = setup_prog(r, mode, has_prior, nsub);
+    const size_t lds = setup_lds_bytes(r, tables, has_prior, nsub);
+    if (lds > LDS_PER_CU) return fail(NFA_ERR_ARG, "too many parameters for the set-up kernel");
+    const PriorProg *prog = setup_prog(r, tables, has_prior, nsub);
     auto kern = nsub == 2 ? setup_kernel<0, false, 2> : tables ? setup_kernel<0, false> : mode == 2 ? setup_kernel<1, true> : setup_kernel<1, false>;
     { int rc2 = ensure_dynamic_lds((const void *)kern, lds); if (rc2) return rc2; }
-    (void)d_U;                                               // the batches' arrays travel in r->cur_group
     if (r->ev_cur)      // profiling: the events ride on the dispatch itself -- its own start and stop, as a tracer sees them
         hipExtLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, st, r->ev_cur[0], r->ev_cur[1], 0, prog, S, r->cur_group, r->d_D[slot], (long)B,
                               has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, ti);
@@ -977,14 +981,17 @@ static int table_waves(const nfa_runner *r) {
     int best = -1, best_blocks = 0, waves = 16;
     for (int w = 4; w <= 16; w += 2) {
         const size_t need = sizeof(double) * ((size_t)n_shared + (size_t)wave_doubles * w);
-        const int blocks = (int)((160 * 1024) / need);
+        const int blocks = (int)(LDS_PER_CU / need);
         const int resident = std::min(32, blocks * w);
         if (resident > best || (resident == best && blocks > best_blocks)) { best = resident; best_blocks = blocks; waves = w; }
     }
     return waves;
 }
 
-// waves per unit of a launch of B items (runner option lnl_split; 0 = by the size of the launch)
+// waves per unit of a launch of B items (runner option lnl_split; 0 = by the size of the launch).  A launch with fewer
+// units than a few per wave slot is latency bound: its waves are placed once and every SIMD waits for its own longest;
+// splitting the rows of a unit over 2 or 4 waves gives the hardware shorter waves to place as slots free up (a single
+// point: 2 units -> 8 waves).
 static int resolve_split(const nfa_runner *r, const SpecDev &S, int64_t B) {
     int split = r->lnl_split;
     if (split == 0) {
@@ -998,87 +1005,132 @@ static int resolve_split(const nfa_runner *r, const SpecDev &S, int64_t B) {
     return split;
 }
 
-// table mode, one wave per unit, at least two units per wave slot of the device: as many workgroups as are resident at
-// once, the units drawn from the launch's queue (lnl_kernel_queue)
 // workgroups of `waves` waves of the table mode that a CU holds at once (LDS: the tables, the waves' line tables, the queue's words)
 static int table_wg_per_cu(const nfa_runner *r, int waves) {
     const size_t need = sizeof(double) * ((size_t)(SM_END_TABLE - SM_EXP2) + (size_t)lnl_wave_doubles(r) * waves) + 16;
-    return std::max(1, std::min((int)((160 * 1024) / need), 32 / waves));
-}
-static bool lnl_uses_queue(const nfa_runner *r, const SpecDev &S, int64_t B, int mode) {
-    if (mode != 0 || g_eng.lnl_queue == 0 || lnl_wide(r)) return false;
-    if (resolve_split(r, S, B) != 1) return false;
-    // (short units -- config 1's 256 channels are four rows -- finish before the draw has paid: 348 M evaluations/s one
-    // unit per wave against 335 M through the queue; from eight rows per spectrum on)
-    for (int k = 0; k < S.n_spec; ++k) if (S.size[k] < 512) return false;
-    const int waves = table_waves(r);
-    return B * S.n_spec >= 2 * ((int64_t)g_eng.n_cu * table_wg_per_cu(r, waves)) * waves;     // two units per resident wave and more
+    return std::max(1, std::min((int)(LDS_PER_CU / need), 32 / waves));
 }
 
-template <int MODE, bool WS, bool WIDE, int NCOMP>
-static int launch_lnl_t(nfa_runner *r, const int *d_pix, int slot, double *d_lnL,
-                        double *d_spec, int64_t B) {
-    const SpecDev S = runner_specdev(r);
-    LnlGeom G;
-    G.ablate = g_eng.ablate;
+// What of LnlGeom the runner and the size of the launch (B items) decide.  The queue and the test library's trace stay
+// null and the timing switches off: plan_lnl sets them for a batch launch, the fused kernels have none.
+static LnlGeom lnl_geom(const nfa_runner *r, int64_t B) {
+    const SpecDev &S = r->ss->dev;
+    LnlGeom G = {};
     G.nhf_max = r->ss->nhf_max;
     G.inv_nspec = S.n_spec == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)S.n_spec) + 1u;
     G.inv_nhf = G.nhf_max == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)G.nhf_max) + 1u;
-    if (B * S.n_spec * 8 >= (1LL << 28)) return fail(NFA_ERR_ARG, "batch too large for one launch");
-    // Waves per unit.  A launch with fewer units than a few per wave slot is latency bound: its waves are
-    // placed once and every SIMD waits for its own longest; splitting the rows of a unit over 2 or 4 waves
-    // gives the hardware shorter waves to place as slots free up (a single point: 2 units -> 8 waves).
-    const int split = resolve_split(r, S, B);
-    G.split = split;
+    G.split = resolve_split(r, S, B);
     G.wave_doubles = lnl_wave_doubles(r);
-    const int n_shared = (MODE == 0) ? (SM_END_TABLE - SM_EXP2) : 0;
-    // waves per workgroup.  Table mode stages 51 KB of product tables per workgroup, so the
-    // workgroup is made as fat as keeps the most waves resident per CU (ties: more workgroups,
-    // so that one stages while another computes).
-    int waves = std::max(1, std::min(r->wpb, 16));
-    waves = std::max(waves, split);
-    waves -= waves % split;
-    if (MODE == 0 && split > 1) waves = std::max(8, split);
-    if (MODE == 0 && split == 1) waves = table_waves(r);
-    G.queue = nullptr;
+    return G;
+}
+
+// ---- the likelihood launch of a batch: which kernel form, how many waves, how much LDS, how many workgroups -----------
+enum LnlForm { LNL_PLAIN, LNL_W8, LNL_QUEUE, LNL_WEIGHTED, LNL_BASELINE };     // lnl_kernel, _w8, _queue, _wt, _bl
+struct LnlPlan { LnlForm form; bool wide; LnlGeom G; int waves; size_t lds; int64_t blocks; };   // waves per workgroup, its dynamic LDS in bytes, workgroups
+
+// Plans the launch for B items of spectra set S in `mode` on stream lane `slot` (the source of the table in DESIGN 4.2).
+// Arithmetic only, no call into the runtime and no allocation: it runs per launch, inside the ~10 us the host spends on
+// enqueueing a step.
+static int plan_lnl(const nfa_runner *r, const SpecDev &S, int64_t B, int mode, bool write_spec, int slot, LnlPlan *out) {
+    const int64_t units = B * S.n_spec;
+    if (units * 8 >= (1LL << 28)) return fail(NFA_ERR_ARG, "batch too large for one launch");
+    const bool table = mode == 0;
+    // table mode: more than 26 lines in a transition (N2H+ 2-1, 3-2): 64-bit line masks, a mask per component;
+    // fast mode: more lines than any NH3 transition (or 2^22 channels): fp64 running sum of tau
+    const bool wide = lnl_wide(r);
+    LnlGeom G = lnl_geom(r, B);
+    G.ablate = g_eng.ablate;
 #ifdef NFA_TEST_HOOKS
     G.trace = g_eng.d_trace;
 #endif
-    const int64_t n_units = B * S.n_spec, wg_resident = (int64_t)g_eng.n_cu * (g_eng.lnl_queue_wg > 0 ? g_eng.lnl_queue_wg : table_wg_per_cu(r, waves));
-    const bool weighted = S.chan_w != nullptr;                  // (lnl_kernel_wt: not the queue form)
-    const bool baseline = S.bl != nullptr;                      // (lnl_kernel_bl, always weighted: neither)
-    if (MODE == 0 && !WIDE && !weighted && r->d_queue[slot] && lnl_uses_queue(r, S, B, 0)) G.queue = r->d_queue[slot];
-    // split > 1: the parts' sums of the units of a workgroup (a baseline: and of the moments of each unit)
-    const size_t part_doubles = split > 1 ? (size_t)LNL_PARTS * 64 * (baseline ? 1 + NFA_BL_NB : 1) : 0;
-    size_t lds = sizeof(double) * ((size_t)n_shared + ((size_t)G.wave_doubles + part_doubles) * (waves / split))
-               + (G.queue ? 16 : 0);
-    if (MODE == 0) lds = std::max(lds, sizeof(double) * (size_t)(n_shared + SM_TABLE_TAIL));
-    if (lds > 160 * 1024) return fail(NFA_ERR_ARG, "ncomp too large for the LDS line table");
-    if (MODE != 0 && r->lnl_cap > 0 && waves * r->lnl_cap < 32)      // residency cap: see Engine::lnl_cap
-        lds = std::max(lds, (size_t)((160 * 1024) / r->lnl_cap) & ~(size_t)15);
-    void (*kern)(SpecDev, BatchGroup, const double *, double *, double *, long, LnlGeom, const double *) = lnl_kernel<MODE, WS, WIDE, NCOMP>;
-    if constexpr (MODE == 0 && WS) kern = lnl_kernel_w8<MODE, WS, WIDE, NCOMP>;
-    if constexpr (MODE == 0 && !WIDE) { if (G.queue) kern = lnl_kernel_queue<WS, NCOMP>; }
-    if (weighted) kern = lnl_kernel_wt<MODE, WS, WIDE, NCOMP>;
-    if (baseline) kern = lnl_kernel_bl<MODE, WS, WIDE, NCOMP>;
-    { int rc2 = ensure_dynamic_lds((const void *)kern, lds); if (rc2) return rc2; }
-    const int64_t units = B * S.n_spec;
-    const int64_t upw = waves / split;
-    const int64_t blocks = G.queue ? wg_resident : (units + upw - 1) / upw;
+    const int split = G.split;
+    // Waves per workgroup: option wpb, made a multiple of the split.  Table mode stages 51 KB of product tables per
+    // workgroup, so the workgroup is made as fat as keeps the most waves resident per CU (table_waves); its split launches take eight.
+    int waves = std::max(1, std::min(r->wpb, 16));
+    waves = std::max(waves, split);
+    waves -= waves % split;
+    if (table) waves = split > 1 ? std::max(8, split) : table_waves(r);
+    const int upw = waves / split;                               // units per workgroup
+    // What the queue form asks of the launch's size: units of eight rows and more (short units -- config 1's 256 channels
+    // are four rows -- finish before the draw has paid: 348 M evaluations/s one unit per wave against 335 M through the
+    // queue), and two units and more per wave of the workgroups that are resident at once.
+    bool long_units = true;
+    for (int k = 0; k < S.n_spec; ++k) if (S.size[k] < 512) long_units = false;
+    const int wg_per_cu = table_wg_per_cu(r, waves);
+    const bool fills_twice = units >= 2 * ((int64_t)g_eng.n_cu * wg_per_cu) * waves;
+    // The form: the first line that applies.
+    LnlForm form = LNL_PLAIN;
+    if (S.bl) form = LNL_BASELINE;                   // every mode, wide, spectra out; such a set is weighted too
+    else if (S.chan_w) form = LNL_WEIGHTED;          // every mode, wide, spectra out: no queue or w8 form of its own (the
+                                                     // units give the same bits whatever the form, so none is instantiated)
+    else if (table && !wide && split == 1            // the queue kernel is table mode, narrow, one wave per unit ...
+             && g_eng.lnl_queue != 0                 // ... unless switched off (option lnl_queue) ...
+             && long_units && fills_twice            // ... pays for launches like these only ...
+             && r->d_queue[slot])                    // ... and needs the lane's counters (reserve_lane)
+        form = LNL_QUEUE;
+    else if (table && write_spec) form = LNL_W8;     // table mode with spectra out asks for 66 registers left alone
+    const bool queue = form == LNL_QUEUE;
+    if (queue) G.queue = r->d_queue[slot];
+    // LDS: [table mode: the product tables][per unit of the workgroup: the line table; split > 1: the parts' sums
+    // (a baseline: and those of the moments of the unit)][queue: the workgroup's queue word and count]
+    const int n_shared = table ? (SM_END_TABLE - SM_EXP2) : 0;
+    const size_t part_doubles = split > 1 ? (size_t)LNL_PARTS * 64 * (form == LNL_BASELINE ? 1 + NFA_BL_NB : 1) : 0;
+    size_t lds = sizeof(double) * ((size_t)n_shared + ((size_t)G.wave_doubles + part_doubles) * upw) + (queue ? 16 : 0);
+    if (table) lds = std::max(lds, sizeof(double) * (size_t)(n_shared + SM_TABLE_TAIL));
+    if (lds > LDS_PER_CU) return fail(NFA_ERR_ARG, "ncomp too large for the LDS line table");
+    if (!table && r->lnl_cap > 0 && waves * r->lnl_cap < 32)         // residency cap: see Engine::lnl_cap
+        lds = std::max(lds, (LDS_PER_CU / r->lnl_cap) & ~(size_t)15);
+    // the queue form: as many workgroups as are resident at once (option lnl_queue_wg: A/B); else one per upw units
+    const int64_t blocks = queue ? (int64_t)g_eng.n_cu * (g_eng.lnl_queue_wg > 0 ? g_eng.lnl_queue_wg : wg_per_cu) : (units + upw - 1) / upw;
     if (blocks > 0x7fffffffLL) return fail(NFA_ERR_ARG, "batch too large for one launch");
+    *out = LnlPlan{form, wide, G, waves, lds, blocks};
+    return NFA_OK;
+}
+
+// The kernel of a plan.  Naming an instance compiles it, so this names the instances a plan can ask for and no others:
+// lnl_kernel, _wt and _bl for all 32 (mode, spectra out, wide, NCOMP), lnl_kernel_w8 for the table mode with spectra out,
+// lnl_kernel_queue for the table mode's narrow sets.  NCOMP 1..3: the component loop unrolled; 0: the general form.
+typedef void (*LnlKernel)(SpecDev, BatchGroup, const double *, double *, double *, long, LnlGeom, const double *);
+template <int I>     // I: bit 4 fast mode, bit 3 spectra out, bit 2 wide, bits 0-1 NCOMP
+static LnlKernel lnl_kernel_inst(LnlForm form) {
+    constexpr int MODE = (I & 16) ? 2 : 0, NCOMP = I & 3;
+    constexpr bool WS = (I & 8) != 0, WIDE = (I & 4) != 0;
+    if (form == LNL_BASELINE) return lnl_kernel_bl<MODE, WS, WIDE, NCOMP>;
+    if (form == LNL_WEIGHTED) return lnl_kernel_wt<MODE, WS, WIDE, NCOMP>;
+    if constexpr (MODE == 0 && !WIDE) if (form == LNL_QUEUE) return lnl_kernel_queue<WS, NCOMP>;
+    if constexpr (MODE == 0 && WS) if (form == LNL_W8) return lnl_kernel_w8<MODE, WS, WIDE, NCOMP>;
+    return form == LNL_PLAIN ? lnl_kernel<MODE, WS, WIDE, NCOMP> : nullptr;      // (null: not a form of this instance)
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_at(int i, LnlForm form, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_inst<(int)I>...};
+    return inst[i](form);
+}
+static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, LnlForm form) {
+    const int i = (mode == 0 ? 0 : 16) | (write_spec ? 8 : 0) | (wide ? 4 : 0) | (ncomp >= 1 && ncomp <= 3 ? ncomp : 0);
+    return lnl_kernel_at(i, form, std::make_index_sequence<32>());
+}
+
+// Likelihood stage of the batch in r->cur_group on stream lane `slot`: chi^2 parts of the units (and spectra out), then
+// -- want_lnl, and nobody else sums the parts -- lnL of the items (lnl_sum_kernel)
+static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, int64_t B, int mode) {
+    const SpecDev S = runner_specdev(r);
+    LnlPlan P;
+    int rc = plan_lnl(r, S, B, mode, d_spec != nullptr, slot, &P); if (rc) return rc;
+    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form);
+    if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
+    rc = ensure_dynamic_lds((const void *)kern, P.lds); if (rc) return rc;
     hipStream_t st = r->lanes[slot];
-    (void)d_pix;
+    double *part = want_lnl ? r->d_part[slot] : nullptr;
     if (r->ev_cur) {
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * waves), lds, st, r->ev_cur[2], r->ev_cur[3], 0, S, r->cur_group,
-                              (const double *)r->d_D[slot], d_lnL ? r->d_part[slot] : nullptr, d_spec, (long)B, G,
-                              (const double *)g_eng.d_tabs);
+        hipExtLaunchKernelGGL(kern, dim3((unsigned)P.blocks), dim3(64 * P.waves), P.lds, st, r->ev_cur[2], r->ev_cur[3], 0, S, r->cur_group,
+                              (const double *)r->d_D[slot], part, d_spec, (long)B, P.G, (const double *)g_eng.d_tabs);
         r->ev_cur = nullptr;
     } else
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * waves), lds, st, S, r->cur_group,
-                           (const double *)r->d_D[slot], d_lnL ? r->d_part[slot] : nullptr, d_spec, (long)B, G,
-                           (const double *)g_eng.d_tabs);
+        hipLaunchKernelGGL(kern, dim3((unsigned)P.blocks), dim3(64 * P.waves), P.lds, st, S, r->cur_group,
+                           (const double *)r->d_D[slot], part, d_spec, (long)B, P.G, (const double *)g_eng.d_tabs);
     HIP_TRY(hipGetLastError());
-    if (d_lnL && !r->part_only) {
+    if (want_lnl && !r->part_only) {
         hipLaunchKernelGGL(lnl_sum_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st,
                            (const double *)r->d_part[slot], S.noise, r->cur_group, (long)B, S.n_spec);
         HIP_TRY(hipGetLastError());
@@ -1086,51 +1138,10 @@ static int launch_lnl_t(nfa_runner *r, const int *d_pix, int slot, double *d_lnL
     return NFA_OK;
 }
 
-// component count: 1..3 are compiled with the component loop unrolled, anything else takes the general form
-template <int MODE, bool WS, bool WIDE>
-static int launch_lnl_n(nfa_runner *r, const int *d_pix, int slot, double *d_lnL, double *d_spec, int64_t B) {
-    switch (r->ncomp) {
-    case 1: return launch_lnl_t<MODE, WS, WIDE, 1>(r, d_pix, slot, d_lnL, d_spec, B);
-    case 2: return launch_lnl_t<MODE, WS, WIDE, 2>(r, d_pix, slot, d_lnL, d_spec, B);
-    case 3: return launch_lnl_t<MODE, WS, WIDE, 3>(r, d_pix, slot, d_lnL, d_spec, B);
-    default: return launch_lnl_t<MODE, WS, WIDE, 0>(r, d_pix, slot, d_lnL, d_spec, B);
-    }
-}
-
-static int launch_lnl(nfa_runner *r, const int *d_pix, int slot, double *d_lnL, double *d_spec, int64_t B,
-                      int mode) {
-    switch (mode) {
-    case 0:
-        if (lnl_wide(r))                // more than 26 lines in a transition (N2H+ 2-1, 3-2): 64-bit line masks, a mask per component
-            return d_spec ? launch_lnl_n<0, true, true>(r, d_pix, slot, d_lnL, d_spec, B)
-                          : launch_lnl_n<0, false, true>(r, d_pix, slot, d_lnL, d_spec, B);
-        return d_spec ? launch_lnl_n<0, true, false>(r, d_pix, slot, d_lnL, d_spec, B)
-                      : launch_lnl_n<0, false, false>(r, d_pix, slot, d_lnL, d_spec, B);
-    default:
-        if (lnl_wide(r))                // more lines than any NH3 transition (or 2^22 channels): fp64 running sum of tau
-            return d_spec ? launch_lnl_n<2, true, true>(r, d_pix, slot, d_lnL, d_spec, B)
-                          : launch_lnl_n<2, false, true>(r, d_pix, slot, d_lnL, d_spec, B);
-        return d_spec ? launch_lnl_n<2, true, false>(r, d_pix, slot, d_lnL, d_spec, B)
-                      : launch_lnl_n<2, false, false>(r, d_pix, slot, d_lnL, d_spec, B);
-    }
-}
-
-// One batch on the next stream lane: set-up kernel, then likelihood kernel.  `lane_out`
-// receives the lane (stream) the batch was enqueued on.
-static int run_group(nfa_runner *r, const BatchGroup &grp, double *d_spec, bool has_prior, int force_lane, int *lane_out);
-
-static int run_batch(nfa_runner *r, const int *d_pix, double *d_U, double *d_lnL, double *d_spec,
-                     int64_t B, bool has_prior, int force_lane, int *lane_out) {
-    BatchGroup g = {};
-    g.pix[0] = d_pix; g.U[0] = d_U; g.lnL[0] = d_lnL; g.each = (long)B; g.n = 1;
-    return run_group(r, g, d_spec, has_prior, force_lane, lane_out);
-}
-
-// The batches of `grp` (one, or several of the same shape coalesced) as one set of launches on the next lane.
-static int run_group(nfa_runner *r, const BatchGroup &grp, double *d_spec, bool has_prior, int force_lane, int *lane_out) {
+// The batches of `grp` (one, or several of the same shape coalesced) as one set of launches on the next stream lane
+// (force_lane >= 0: on that one): set-up kernel, then likelihood kernel.
+static int run_group(nfa_runner *r, const BatchGroup &grp, double *d_spec, bool has_prior, int force_lane) {
     const int64_t B = (int64_t)grp.each * grp.n;
-    const int *d_pix = grp.pix[0];
-    double *d_U = grp.U[0], *d_lnL = grp.lnL[0];
     int rc0 = engine_init(); if (rc0) return rc0;            // binds the calling thread to the device
     if (!g_eng.have_t0) return fail(NFA_ERR_STATE, "nfa_set_iemtex_table has not been called");
     // Lanes a sequence of batches rotates over.  Four overlap the draining tail of one batch with the next;
@@ -1150,30 +1161,28 @@ static int run_group(nfa_runner *r, const BatchGroup &grp, double *d_spec, bool 
         n_use = std::min(n_use, r->n_lanes);
     }
     const int slot = force_lane >= 0 ? force_lane : (int)(r->n_calls % (uint64_t)n_use);
-    hipStream_t st = r->lanes[slot];
-    hipEvent_t *e = nullptr;
     if (r->profiling) {
         if (r->ev_used + 4 > r->ev.size()) {
             for (int k = 0; k < 4; ++k) { hipEvent_t x; HIP_TRY(hipEventCreate(&x)); r->ev.push_back(x); }
         }
-        e = &r->ev[r->ev_used];
+        r->ev_cur = &r->ev[r->ev_used];                       // (launch_lnl takes the last pair and clears it)
         r->ev_used += 4;
-        r->ev_cur = e;
     }
-    const int mode = r->exp_mode >= 0 ? r->exp_mode : g_eng.exp_mode;      // read once per batch
+    const int mode = runner_mode(r);                          // read once per batch
     r->cur_group = grp;
-    int rc = launch_setup(r, d_U, B, has_prior, slot, mode);
+    int rc = launch_setup(r, B, has_prior, slot, mode);
     if (rc) return rc;
-    rc = launch_lnl(r, d_pix, slot, d_lnL, d_spec, B, mode);
+    rc = launch_lnl(r, slot, grp.lnL[0] != nullptr, d_spec, B, mode);
     if (rc) return rc;
-    if (r->ev_cur) {        // (a likelihood launcher that does not carry events: the pair goes behind it, an empty interval)
-        HIP_TRY(hipEventRecord(r->ev_cur[2], st)); HIP_TRY(hipEventRecord(r->ev_cur[3], st));
-        r->ev_cur = nullptr;
-    }
     r->n_calls++;
     r->lane_busy |= 1u << slot;
-    if (lane_out) *lane_out = slot;
     return NFA_OK;
+}
+static int run_batch(nfa_runner *r, const int *d_pix, double *d_U, double *d_lnL, double *d_spec,
+                     int64_t B, bool has_prior, int force_lane) {
+    BatchGroup g = {};
+    g.pix[0] = d_pix; g.U[0] = d_U; g.lnL[0] = d_lnL; g.each = (long)B; g.n = 1;
+    return run_group(r, g, d_spec, has_prior, force_lane);
 }
 
 // Coalescing of device-pointer batches.  nfa_runner_loglike_batch_dev returns before anything runs anyway; batches
@@ -1185,7 +1194,7 @@ static int flush_pending(nfa_runner *r) {
     if (r->pending.n == 0) return NFA_OK;
     const BatchGroup g = r->pending;
     r->pending.n = 0;
-    return run_group(r, g, g.spec[0], r->pending_prior, -1, nullptr);
+    return run_group(r, g, g.spec[0], r->pending_prior, -1);
 }
 static int flush_all_runners() {
     std::lock_guard<std::mutex> lk(g_runners_m);
@@ -1227,7 +1236,7 @@ static int enqueue_dev(nfa_runner *r, const int32_t *d_pix, double *d_U, double 
                     (int64_t)(p.n + 1) * units > NFA_GROUP_MAX * slots)) {
         int rc = flush_pending(r); if (rc) return rc;
     }
-    if (!fits) return run_batch(r, d_pix, d_U, d_lnL, d_spec, B, has_prior, -1, nullptr);
+    if (!fits) return run_batch(r, d_pix, d_U, d_lnL, d_spec, B, has_prior, -1);
     p.pix[p.n] = d_pix; p.U[p.n] = d_U; p.lnL[p.n] = d_lnL; p.spec[p.n] = d_spec; p.each = (long)B; p.n += 1;
     r->pending_prior = has_prior;
     if (p.n >= group || (int64_t)(p.n + 1) * units > NFA_GROUP_MAX * slots) return flush_pending(r);
@@ -1303,48 +1312,54 @@ int nfa_runner_synchronize(nfa_runner *r) {
 
 }  // extern "C"
 
+// ---- the fused kernels: point_kernel (nfa_setup.h) and ring_serve_kernel (nfa_ring_serve.h) --------------------------
+// Both run setup_body and lnl_body<MODE, false, false, NCOMP> (narrow, unweighted) in one workgroup of POINT_WAVES waves.
+// Why they cannot serve a runner's points (nullptr: they can; `split`: of a launch of one item), in the words
+// nfa_ring_serve_device fails with; few_points_kernel takes the batch path instead.
+static const char *fused_refusal(const nfa_runner *r, int split) {
+    if (r->ndim > NFA_POINT_MAXDIM || lnl_wide(r)) return "this runner's points go through the batch kernels: use nfa_ring_serve";
+    // (weighted sets, baseline sets among them: lnl_kernel_wt / lnl_kernel_bl.  The unweighted body would compute the unweighted sum.)
+    if (r->ss->dev.bl) return "the resident kernel has no form for a baseline: use nfa_ring_serve";
+    if (r->ss->dev.chan_w) return "the resident kernel has no form for a noise per channel: use nfa_ring_serve";
+    if (split > POINT_WAVES) return "spectra too short for the point kernel's split";
+    return nullptr;
+}
+// LDS of their stages in bytes.  `setup`: the set-up stage's layout with the prior tables it stages, behind the exponential
+// tables -- the kernel stages those itself (table mode: FastExp's product tables whatever the model), so the stage's
+// layout and program (setup_prog) are asked for without them; `tables`: the likelihood's; `units`: line tables and
+// split parts of the POINT_WAVES / split units of a pass.  How the pieces lie in LDS differs: see the two callers.
+struct FusedLds { size_t setup, tables, units; };
+static FusedLds fused_lds(const nfa_runner *r, int mode, const LnlGeom &G) {
+    const size_t n_tables = mode == 0 ? (SM_END_TABLE - SM_EXP2) : 0, n_staged = mode == 0 ? n_tables : NFA_EXP2_N;
+    return FusedLds{setup_lds_bytes(r, false, true) + sizeof(double) * (n_staged - NFA_EXP2_N), sizeof(double) * n_tables,
+                    sizeof(double) * (((size_t)G.wave_doubles + (G.split > 1 ? LNL_PARTS * 64 : 0)) * (POINT_WAVES / G.split))};
+}
+
 // One point, or the few a broker gathered, through the point kernel (nfa_setup.h); returns 1 when the call
 // was served, 0 when another path has to do it, a negative value on a device error.
 #define POINT_HOST_DOUBLES (NFA_POINT_MAXB * (2 * NFA_POINT_MAXDIM + 2) + 8)
-template <int MODE, int NCOMP>
-static void launch_point_t(nfa_runner *r, const SpecDev &S, const PointIn &in, const LnlGeom &G, size_t lds) {
-    auto kern = point_kernel<MODE, NCOMP>;
-    (void)ensure_dynamic_lds((const void *)kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)in.n), dim3(POINT_THREADS), lds, r->lanes[0], setup_prog(r, 1, true), S, in,
-                       r->d_pix, r->d_U, r->d_D[0], r->d_part[0], r->d_point, r->d_point_done, G,
-                       (const double *)g_eng.d_tabs);
-}
-template <int MODE>
-static void launch_point_n(nfa_runner *r, const SpecDev &S, const PointIn &in, const LnlGeom &G, size_t lds) {
-    switch (r->ncomp) {
-    case 1: return launch_point_t<MODE, 1>(r, S, in, G, lds);
-    case 2: return launch_point_t<MODE, 2>(r, S, in, G, lds);
-    case 3: return launch_point_t<MODE, 3>(r, S, in, G, lds);
-    default: return launch_point_t<MODE, 0>(r, S, in, G, lds);
+template <int MODE>    // the instance of a component count: 1..3 with the component loop unrolled, anything else the general form
+static decltype(&point_kernel<MODE, 0>) point_kernel_of(int ncomp) {
+    switch (ncomp) {
+    case 1: return point_kernel<MODE, 1>;
+    case 2: return point_kernel<MODE, 2>;
+    case 3: return point_kernel<MODE, 3>;
+    default: return point_kernel<MODE, 0>;
     }
 }
 
 static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, double *lnL, int64_t B) {
     const int ndim = r->ndim;
-    // (weighted spectra sets, baseline sets among them: the batch kernels, lnl_kernel_wt / lnl_kernel_bl)
-    if (!g_eng.point || r->profiling || ndim > NFA_POINT_MAXDIM || lnl_wide(r) || r->ss->dev.chan_w || B > NFA_POINT_MAXB) return 0;
-    const int mode = r->exp_mode >= 0 ? r->exp_mode : g_eng.exp_mode;
+    if (!g_eng.point || r->profiling || B > NFA_POINT_MAXB) return 0;
+    const LnlGeom G = lnl_geom(r, 1);
+    if (fused_refusal(r, G.split)) return 0;
+    const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
-    LnlGeom G;
-    G.ablate = 0;
-    G.nhf_max = r->ss->nhf_max;
-    G.inv_nspec = S.n_spec == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)S.n_spec) + 1u;
-    G.inv_nhf = G.nhf_max == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)G.nhf_max) + 1u;
-    G.split = resolve_split(r, S, 1);
-    if (G.split > POINT_WAVES) return 0;
-    G.wave_doubles = lnl_wave_doubles(r);
     const int upw = POINT_WAVES / G.split;                       // units per pass of the workgroup
-    const int n_shared = mode == 0 ? (SM_END_TABLE - SM_EXP2) : 0;
     // the set-up stage and the likelihood waves use the same LDS one after the other, behind the staged tables
-    const size_t n_staged = mode == 0 ? (SM_END_TABLE - SM_EXP2) : NFA_EXP2_N;
-    const size_t lds = std::max(setup_lds_bytes(r, 1, true) + sizeof(double) * (n_staged - NFA_EXP2_N),
-                                sizeof(double) * ((size_t)n_shared + ((size_t)G.wave_doubles + (G.split > 1 ? LNL_PARTS * 64 : 0)) * upw));
-    if (lds > 160 * 1024) return 0;
+    const FusedLds L = fused_lds(r, mode, G);
+    const size_t lds = std::max(L.setup, L.tables + L.units);
+    if (lds > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {
         bool ok = hipHostMalloc((void **)&r->h_point, sizeof(double) * POINT_HOST_DOUBLES, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess
@@ -1379,10 +1394,11 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     volatile unsigned long long *flag = (volatile unsigned long long *)(r->h_point + B * (ndim + 1));
     *flag = 0;                                                   // the slot holds other data when B changes
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    switch (mode) {
-    case 0: launch_point_n<0>(r, S, in, G, lds); break;
-    default: launch_point_n<2>(r, S, in, G, lds); break;
-    }
+    const auto kern = mode == 0 ? point_kernel_of<0>(r->ncomp) : point_kernel_of<2>(r->ncomp);
+    (void)ensure_dynamic_lds((const void *)kern, lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)in.n), dim3(POINT_THREADS), lds, r->lanes[0], setup_prog(r, false, true), S, in,
+                       r->d_pix, r->d_U, r->d_D[0], r->d_part[0], r->d_point, r->d_point_done, G,
+                       (const double *)g_eng.d_tabs);
     if (hipGetLastError() != hipSuccess) { fail(NFA_ERR_DEVICE, "point kernel launch failed"); return -1; }
     // the kernel's last store is the sequence number; the host reads it straight from the mapped buffer
     const auto t_start = std::chrono::steady_clock::now();
@@ -1414,7 +1430,7 @@ static int single_point_graph(nfa_runner *r, double *U, double *lnL) {
         profiled = profiled || (pre && (strstr(pre, "rocprof") || strstr(pre, "roctracer")));
         g_eng.graph = profiled ? 0 : 1;
     }
-    const int mode = r->exp_mode >= 0 ? r->exp_mode : g_eng.exp_mode;
+    const int mode = runner_mode(r);
     if (!g_eng.graph || r->profiling || mode == 0 || r->cap_B < 1 || r->cap_D[0] < 1 || r->n_single < 2) return 0;
     const int ndim = r->ndim;
     hipStream_t st = r->lanes[0];
@@ -1424,7 +1440,7 @@ static int single_point_graph(nfa_runner *r, double *U, double *lnL) {
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) return 0;
         bool ok = hipMemcpyAsync(r->d_U, r->h_pin, sizeof(double) * ndim, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && run_batch(r, nullptr, r->d_U, r->d_lnL, nullptr, 1, true, 0, nullptr) == NFA_OK;
+        ok = ok && run_batch(r, nullptr, r->d_U, r->d_lnL, nullptr, 1, true, 0) == NFA_OK;
         ok = ok && hipMemcpyAsync(r->h_pin, r->d_U, sizeof(double) * ndim, hipMemcpyDeviceToHost, st) == hipSuccess;
         ok = ok && hipMemcpyAsync(r->h_pin + ndim, r->d_lnL, sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
         const bool ended = hipStreamEndCapture(st, &graph) == hipSuccess && graph;
@@ -1505,7 +1521,7 @@ int nfa_runner_loglike_batch(nfa_runner *r, const int32_t *pix, double *U, doubl
         if (!vU) HIP_TRY(hipMemcpyAsync(r->d_U + b0 * ndim, U + b0 * ndim, sizeof(double) * nb * ndim, hipMemcpyHostToDevice, st));
         if (pix && !vP) HIP_TRY(hipMemcpyAsync(r->d_pix + b0, pix + b0, sizeof(int) * nb, hipMemcpyHostToDevice, st));
         rc = run_batch(r, pix ? (vP ? vP + b0 : r->d_pix + b0) : nullptr, vU ? vU + b0 * ndim : r->d_U + b0 * ndim,
-                       vL ? vL + b0 : r->d_lnL + b0, nullptr, nb, true, c, nullptr);
+                       vL ? vL + b0 : r->d_lnL + b0, nullptr, nb, true, c);
         if (rc) return rc;
     }
     for (int c = 0; c < n_chunks; ++c) {
@@ -1536,7 +1552,7 @@ int nfa_runner_predict_batch(nfa_runner *r, const int32_t *pix, const double *th
     HIP_TRY(hipMemcpyAsync(r->d_U, theta, sizeof(double) * B * r->ndim, hipMemcpyHostToDevice, st));
     if (pix) HIP_TRY(hipMemcpyAsync(r->d_pix, pix, sizeof(int) * B, hipMemcpyHostToDevice, st));
     rc = run_batch(r, pix ? r->d_pix : nullptr, r->d_U, vL ? vL : r->d_lnL, spectra_out ? (vS ? vS : r->d_spec) : nullptr, B,
-                   false, 0, nullptr);
+                   false, 0);
     if (rc) return rc;
     if (spectra_out && !vS)
         HIP_TRY(hipMemcpyAsync(spectra_out, r->d_spec, sizeof(double) * B * r->ss->dev.chan_tot,

@@ -167,22 +167,13 @@ __global__ void __launch_bounds__(POINT_THREADS) ring_serve_kernel(const PriorPr
     }
 }
 
-template <int MODE, int NCOMP>
-static int launch_ring_serve_t(nfa_runner *r, const SpecDev &S, const RingServeArgs &A, const LnlGeom &G, size_t lds, int n_wg) {
-    auto kern = ring_serve_kernel<MODE, NCOMP>;
-    { int rc = ensure_dynamic_lds((const void *)kern, lds); if (rc) return rc; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(POINT_THREADS), lds, r->lanes[0], setup_prog(r, 1, true), S, A,
-                       r->d_pix, r->d_U, r->d_D[0], r->d_part[0], G, (const double *)g_eng.d_tabs);
-    HIP_TRY(hipGetLastError());
-    return NFA_OK;
-}
-template <int MODE>
-static int launch_ring_serve_n(nfa_runner *r, const SpecDev &S, const RingServeArgs &A, const LnlGeom &G, size_t lds, int n_wg) {
-    switch (r->ncomp) {
-    case 1: return launch_ring_serve_t<MODE, 1>(r, S, A, G, lds, n_wg);
-    case 2: return launch_ring_serve_t<MODE, 2>(r, S, A, G, lds, n_wg);
-    case 3: return launch_ring_serve_t<MODE, 3>(r, S, A, G, lds, n_wg);
-    default: return launch_ring_serve_t<MODE, 0>(r, S, A, G, lds, n_wg);
+template <int MODE>    // the instance of a component count, as point_kernel_of
+static decltype(&ring_serve_kernel<MODE, 0>) ring_serve_kernel_of(int ncomp) {
+    switch (ncomp) {
+    case 1: return ring_serve_kernel<MODE, 1>;
+    case 2: return ring_serve_kernel<MODE, 2>;
+    case 3: return ring_serve_kernel<MODE, 3>;
+    default: return ring_serve_kernel<MODE, 0>;
     }
 }
 
@@ -198,35 +189,25 @@ int nfa_ring_serve_device(nfa_ring *ring, nfa_runner *run, int lifetime_ms, int 
     RingHeader *h = ring->hdr;
     if (run->ndim != h->ndim) return fail(NFA_ERR_ARG, "ring and runner disagree on ndim");
     if (h->max_points != 1) return fail(NFA_ERR_ARG, "the resident kernel serves one point per slot: use nfa_ring_serve for this ring");
-    if (run->ndim > NFA_POINT_MAXDIM || lnl_wide(run)) return fail(NFA_ERR_ARG, "this runner's points go through the batch kernels: use nfa_ring_serve");
-    // (the resident kernel has no weighted form: it would compute the unweighted sum; nor a baseline form)
-    if (run->ss->dev.bl) return fail(NFA_ERR_ARG, "the resident kernel has no form for a baseline: use nfa_ring_serve");
-    if (run->ss->dev.chan_w) return fail(NFA_ERR_ARG, "the resident kernel has no form for a noise per channel: use nfa_ring_serve");
+    const LnlGeom G = lnl_geom(run, 1);
+    if (const char *why = fused_refusal(run, G.split)) return fail(NFA_ERR_ARG, why);
     if (lifetime_ms <= 0) lifetime_ms = 20;
     if (lifetime_ms > 1000) lifetime_ms = 1000;
     RUNNER_LOCK(run);
     { int rc = sync_all_lanes(run); if (rc) return rc; }
-    const int mode = run->exp_mode >= 0 ? run->exp_mode : g_eng.exp_mode;
+    const int mode = runner_mode(run);
     const SpecDev S = runner_specdev(run);
-    LnlGeom G;
-    G.ablate = 0;
-    G.nhf_max = run->ss->nhf_max;
-    G.inv_nspec = S.n_spec == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)S.n_spec) + 1u;
-    G.inv_nhf = G.nhf_max == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)G.nhf_max) + 1u;
-    G.split = resolve_split(run, S, 1);
-    if (G.split > POINT_WAVES) return fail(NFA_ERR_ARG, "spectra too short for the point kernel's split");
-    G.wave_doubles = lnl_wave_doubles(run);
     const int upw = POINT_WAVES / G.split;
-    const int n_shared = mode == 0 ? (SM_END_TABLE - SM_EXP2) : 0;
-    const size_t n_staged = mode == 0 ? (SM_END_TABLE - SM_EXP2) : NFA_EXP2_N;
     // [exponential tables][theta, partition records][prior program + tables: staged once][line tables of the likelihood waves]
-    size_t lds = setup_lds_bytes(run, 1, true) + sizeof(double) * (n_staged - NFA_EXP2_N)
-                 + sizeof(double) * (((size_t)G.wave_doubles + (G.split > 1 ? LNL_PARTS * 64 : 0)) * upw);
-    if (mode == 0) lds = std::max(lds, sizeof(double) * (size_t)(n_shared + SM_TABLE_TAIL));
+    const FusedLds L = fused_lds(run, mode, G);
+    size_t lds = L.setup + L.units;
+    if (mode == 0) lds = std::max(lds, L.tables + sizeof(double) * SM_TABLE_TAIL);
     lds = (lds + 15) & ~(size_t)15;
     const int ctl_double = (int)(lds / sizeof(double));
     lds += 16;                                                   // the workgroup's control words
-    if (lds > 160 * 1024) return fail(NFA_ERR_ARG, "too many parameters for the resident kernel");
+    if (lds > LDS_PER_CU) return fail(NFA_ERR_ARG, "too many parameters for the resident kernel");
+    const auto kern = mode == 0 ? ring_serve_kernel_of<0>(run->ncomp) : ring_serve_kernel_of<2>(run->ncomp);
+    { int rc = ensure_dynamic_lds((const void *)kern, lds); if (rc) return rc; }
     const int n_wg = std::max(1, std::min(h->n_slots, 64));
     { int rc = runner_reserve(run, n_wg, false); if (rc) return rc; }
     { int rc = reserve_lane(run, 0, n_wg); if (rc) return rc; }
@@ -261,14 +242,11 @@ int nfa_ring_serve_device(nfa_ring *ring, nfa_runner *run, int lifetime_ms, int 
     hipStream_t st = run->lanes[0];
     for (;;) {
         if (h->stop.load(std::memory_order_acquire)) break;
-        int rc;
-        switch (mode) {
-        case 0: rc = launch_ring_serve_n<0>(run, S, A, G, lds, n_wg); break;
-        default: rc = launch_ring_serve_n<2>(run, S, A, G, lds, n_wg); break;
-        }
-        if (rc) { rc_out = rc; break; }
+        hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(POINT_THREADS), lds, st, setup_prog(run, false, true), S, A,
+                           run->d_pix, run->d_U, run->d_D[0], run->d_part[0], G, (const double *)g_eng.d_tabs);
+        hipError_t q = hipGetLastError();
+        if (q != hipSuccess) { rc_out = fail(NFA_ERR_DEVICE, std::string("launching the resident kernel: ") + hipGetErrorString(q)); break; }
         // while the instance lives: heartbeat, wake-ups for clients asleep on a finished slot
-        hipError_t q;
         while ((q = hipStreamQuery(st)) == hipErrorNotReady) {
             h->last_serve_us.store(ring_now_us(), std::memory_order_release);
             for (int k = 0; k < h->n_slots; ++k) {

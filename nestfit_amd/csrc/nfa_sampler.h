@@ -1937,7 +1937,7 @@ int nfa_sampler_begin(nfa_sampler *s, double tol, double efr, int64_t seed, int6
         const long tot = (long)P * N;
         hipLaunchKernelGGL(ns_init_live_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d, s->d_livepix);
         HIP_TRY(hipGetLastError());
-        int rc = run_batch(r, s->d_livepix, d.Tlive, d.Llive, nullptr, (int64_t)P * N, true, 0, nullptr);
+        int rc = run_batch(r, s->d_livepix, d.Tlive, d.Llive, nullptr, (int64_t)P * N, true, 0);
         if (rc) return rc;
         hipLaunchKernelGGL(ns_sanitize_kernel, dim3((unsigned)(((long)P * N + 255) / 256)), dim3(256), 0, st,
                            d.Llive, (long)P * N, log_zero);
@@ -2102,7 +2102,7 @@ int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active_ou
                 dh[h].part = nullptr;
                 if (n_rows > 0) {
                     r->part_only = true;                                   // (the update wave sums the parts of a row)
-                    int rc = run_batch(r, dh[h].candpix, dh[h].candT, dh[h].candL, nullptr, n_rows, true, h, nullptr);
+                    int rc = run_batch(r, dh[h].candpix, dh[h].candT, dh[h].candL, nullptr, n_rows, true, h);
                     r->part_only = false;
                     if (rc) return rc;
                     dh[h].part = r->d_part[h];                             // (after the batch: its buffers may have grown)
