@@ -413,7 +413,7 @@ int nfa_sampler_set_ellipsoids(nfa_sampler *s, int max_ellipsoids);
  * the bounding boxes of the live points in the unit cube's axes, in the ellipsoid's own frame and in n_frames fixed
  * rotations of it (-2: the default = 32 where the bound is sheared, none elsewhere; -1: none; 0..64).  margin: a face lies
  * beyond the extreme live point by margin * max(0.1 s, extreme - mean - 1.5 s), s the spread along its direction
- * (0: the default, 1.75).  MultiNest has no counterpart; `efr` keeps its meaning for the ellipsoid the proposals are drawn
+ * (0: the default, 2.5).  MultiNest has no counterpart; `efr` keeps its meaning for the ellipsoid the proposals are drawn
  * from (nestfit/core/core.pyx:727-732). */
 int nfa_sampler_set_boxes(nfa_sampler *s, int n_frames, double margin);
 /* A volume-preserving shear in front of a one-ellipsoid bound (between create and begin).  The live region of a faint
@@ -422,13 +422,13 @@ int nfa_sampler_set_boxes(nfa_sampler *s, int n_frames, double margin);
  * inside one velocity component, products of the earlier coordinates): an additive triangular map has a unit Jacobian, so
  * a point drawn uniformly in the w-ellipsoid and mapped back is uniform over its curved image in the unit cube.  Boxes, if
  * on, are fitted and tested in the w frame.  enlarge: the safety factor on the sheared ellipsoid's enclosing volume (>= 1;
- * 2.5 is the measured choice), 0 = off, < 0 = the default (engine option "sampler_shear_pct": 2.5 unless changed).  Applies
+ * 3 is the measured choice), 0 = off, < 0 = the default (engine option "sampler_shear_pct": 3 unless changed).  Applies
  * where all five free parameters of two or three components are sampled (10 or 15 dimensions); accepted and without effect
  * elsewhere.  MultiNest has no counterpart (its answer to curved regions is more ellipsoids: nestfit/core/core.pyx:727-760). */
 int nfa_sampler_set_shear(nfa_sampler *s, double enlarge);
 /* With the shear and the boxes on: every pair (i, j) of the sheared coordinates has the bounding ellipse of the live points'
  * projection onto (w_i, w_j) -- the covariance ellipse scaled to enclose them, its area times `enlarge` -- as one more free
- * veto: the region lies inside the cylinder over each of its projections.  enlarge >= 1 (1.75 is the measured choice), 0 = off,
+ * veto: the region lies inside the cylinder over each of its projections.  enlarge >= 1 (2 is the measured choice), 0 = off,
  * < 0 = the default (engine option "sampler_pairs_pct", hundredths).  Between create and begin. */
 int nfa_sampler_set_pairs(nfa_sampler *s, double enlarge);
 /* After a run: every pixel's table of posterior samples in one copy (what MultiNest leaves in its post files and mn_dump

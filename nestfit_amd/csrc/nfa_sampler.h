@@ -23,6 +23,8 @@
 // Only the unit-cube slots the likelihood depends on are sampled (free_mask).
 #pragma once
 
+#include "nfa_sampler_plan.h"   // the policy constants, the knobs and ns_plan: the run's form, decided once
+
 #define NS_MAXD      60          // 6 parameters x MAXCOMP
 #define NS_TAG_LIVE  (1ull << 62)
 #define NS_B_RADIUS  255ull
@@ -30,10 +32,6 @@
 #define NS_WALK_TARGET 0.5     // acceptance the walk scale is tuned to
 #define NS_W         64          // walkers per lane slice of the update wave
 #define NS_WMAX      256         // walkers per pixel at most
-// Walkers of a pixel with n live points: a cycle's walkers are harvested against a threshold that rises with every
-// replacement, so many more than a third of n mostly harvest each other's leftovers (of k walkers n ln(1 + k / n) pass);
-// 64 of them are a small batch once the pixels are few -- 128 from 384 live points, 256 from 768.
-__host__ __device__ inline int ns_walkers_for(int n) { return n >= 768 ? 256 : n >= 384 ? 128 : 64; }
 
 __host__ __device__ inline uint64_t ns_mix(uint64_t x) {             // splitmix64 finaliser
     x += 0x9E3779B97F4A7C15ull;
@@ -57,10 +55,6 @@ __host__ __device__ inline double ns_uniform_of(uint64_t stream, uint64_t b) {
 // Several bounding ellipsoids per pixel (MultiNest's `mmodal` bound in its simplest form): up to NS_ME of them where at
 // most NS_ME_MAXD dimensions are sampled.  A cluster of live points is cut in two across its principal axis at its
 // centre; the cut is kept when the two halves' ellipsoids together have less than NS_ME_GAIN of the parent's volume.
-#define NS_ME 4
-#ifndef NS_ME_MAXD
-#define NS_ME_MAXD 6
-#endif
 #define NS_ME_GAIN 0.7
 static_assert(NS_ME_MAXD <= 6, "ns_refit_kernel dispatches the cluster fits for up to six sampled dimensions");
 #define NS_B_ELL 253ull            // random-stream slots of a proposal: which ellipsoid, and the 1 / (number that hold it) test
@@ -72,27 +66,14 @@ static_assert(NS_ME_MAXD <= 6, "ns_refit_kernel dispatches the cluster fits for 
 // small where the marginal ends abruptly (a flat direction), large where it thins out (the projection of a round body).
 // scripts/proto_intersection.py measured what each family of bounds cuts off the true region and what it saves; the
 // numpy twin's _fit_boxes / _box_veto hold the same arithmetic.
-#define NS_FRAMES 32               // rotated frames a caller gets who asks for boxes without naming a number
-#define NS_FRAMES_MAX 64
-#define NS_MARGIN_C 2.5            // (round 4: 1.75, sampler.py precision='speed')
 #define NS_MARGIN_A 1.5
 #define NS_MARGIN_FLOOR 0.1
-#define NS_RATIO_MAX 32            // proposals drawn per round: at most this multiple of the evaluations aimed for
 #define NS_FRAME_SEED 0x5EEDF00Dull
 // A volume-preserving shear in front of the one-ellipsoid bound (the twin's _fit_shear): every sampled coordinate minus a
 // quadratic function of the earlier ones -- the curved tex / ntot ridges of faint pixels come out straight, and an
 // ellipsoid around straight things is small
 #define NS_SHEAR_RIDGE 1e-6        // on the Gram matrix's diagonal, times the live points
-#define NS_SHEAR_ENLARGE 3.0       // safety factor on the enclosing volume of the sheared ellipsoid (round 4: 2.5, sampler.py precision='speed')
 #define NS_SHEAR_PIVOT 1e-9        // a Cholesky pivot below this fraction of its diagonal entry: the monomial is dropped
-#define NS_SHEAR_MMAX 64           // monomials at most
-#define NS_REFIT_THREADS 512       // of the workgroup that fits a one-ellipsoid bound
-#define NS_PAIRS_ENLARGE 2.0       // safety factor on the area of a pair ellipse (round 4: 1.75, sampler.py precision='speed')
-#define NS_KP_START 256            // a pixel's share of proposals in its first rejection round
-#define NS_K_TARGET 16             // replacements per pixel and rejection round the per-pixel share of proposals aims at
-#define NS_WALK_LOWD 6             // up to this many sampled dimensions ...
-#define NS_WALK_FACTOR_LOWD 64     // ... the switch to walks waits for an acceptance below 1 / (64 n_steps)
-#define NS_WALK_FACTOR 2           // above: 1 / (2 n_steps)
 struct NsDev {
     int     P, N, D, K;                 // pixels, live points, SAMPLED dimensions, candidates per round (at least)
     int     DT;                         // length of a theta row (all unit-cube slots of the runner)
@@ -179,21 +160,6 @@ struct NsDev {
 };
 #define NS_TICK(slot) do { if (timing) { const long t_ = (long)wall_clock64(); S.dbg[slot] += t_ - t_last; t_last = t_; } } while (0)
 
-// The monomials of the shear (host; the twin's _shear_monomials): [1], then per coordinate j its own z_j, z_j^2 and
-// z_k z_j for the earlier coordinates k of the same velocity component (k % nc == j % nc).
-static void ns_shear_monomials(int D, int nc, std::vector<int> &mono, std::vector<int> &start) {
-    mono.assign({-1, -1});
-    start.clear();
-    for (int j = 0; j < D; ++j) {
-        start.push_back((int)mono.size() / 2);
-        mono.push_back(j); mono.push_back(-1);
-        mono.push_back(j); mono.push_back(j);
-        for (int k = 0; k < j; ++k)
-            if (k % nc == j % nc) { mono.push_back(k); mono.push_back(j); }
-    }
-    mono.resize((size_t)(start.back() + 1) * 2);      // the last coordinate is nobody's feature
-}
-
 // The fixed frames (host; the twin's _frames): entries 2 u - 1 from the counter-based stream, columns orthonormalised one
 // after the other (modified Gram-Schmidt).
 static void ns_make_frames(int D, int K, std::vector<double> &Q) {
@@ -210,9 +176,7 @@ static void ns_make_frames(int D, int K, std::vector<double> &Q) {
             }
             double n2 = 0.0;
             for (int a = 0; a < D; ++a) n2 += v[a] * v[a];
-            const double inv = 1.0 / sqrt(n2);
             for (int a = 0; a < D; ++a) q[a * D + b] = v[a] / sqrt(n2);
-            (void)inv;
         }
     }
 }
@@ -1053,8 +1017,6 @@ __device__ void ns_refit(const NsDev &S, int p, long n_iter, double *sA, double 
 }
 
 // ---- several ellipsoids ----------------------------------------------------------------------
-// One fit slot in LDS: [c: D][L: D*D, lower][cov: D*D, lower][r2, lnv, n, final]
-__host__ __device__ inline int ns_me_slot(int D) { return D + 2 * D * D + 4; }
 // Mean, covariance, Cholesky factor, largest Mahalanobis distance and ln volume (safety factor included) of the live
 // points whose label is k (and, with side >= 0, whose side bit is `side`); su = the pixel's live points in LDS.
 template <int DD>
@@ -1244,11 +1206,6 @@ __device__ void ns_refit_multi(const NsDev &S, int p, long n_iter, double *su, i
 // that can replace anything, the threshold never falls -- are handed to wave 0, in order.  (One wave walking 16 k flags
 // in chunks of 512, three dependent global loads per chunk, was ~0.6-1.1 ms per round of the boxes' runs.)
 // q indexes actlist
-#define NS_UPD_THREADS 256
-#define NS_UPD_SEG (4 * NS_UPD_THREADS)
-__host__ __device__ inline size_t ns_upd_lds(int N) {   // doubles: live lnL | survivors' lnL | their k, row, rank (ints) | counts | control
-    return (size_t)((N + 1) & ~1) + NS_UPD_SEG + (3 * NS_UPD_SEG) / 2 + 16 + 2;
-}
 __global__ void __launch_bounds__(NS_UPD_THREADS) NFA_UPD_ATTR ns_update_kernel(NsDev S, int n_act, int Kr, long round) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1687,66 +1644,198 @@ __global__ void __launch_bounds__(NS_FIN_THREADS) ns_finish_kernel(NsDev S, cons
 }
 
 // ---- host side -----------------------------------------------------------------------------
-#ifndef NS_KMAX
-#define NS_KMAX 65536           // most proposals one pixel gets in a round
-#endif
 #define NS_PARTS 4              // at most this many groups of pixels, each on its own stream lane
 struct nfa_sampler {
     nfa_runner *r = nullptr;
     NsDev d = {};
+    NsPlan plan = {};           // the run's form (ns_plan): nfa_sampler_create fills what sizes the buffers, nfa_sampler_begin the rest
+    NsKnobs set;                // what nfa_sampler_set_* asked for, and the process options the buffers were sized for
+    std::vector<void *> bufs;   // every device buffer of the sampler (ns_alloc), freed by nfa_sampler_destroy
     long b_target = 0;          // candidates per round the sampler aims for (all pixels together)
-    int *d_pixmap = nullptr, *d_actlist = nullptr, *d_livepix = nullptr, *d_fmap = nullptr;
-    int *d_nlive = nullptr, *d_updp = nullptr;
-    long *d_capp = nullptr;
-    double *d_frames = nullptr;
-    int set_frames = -2;        // nfa_sampler_set_boxes: -2 = the default (NS_FRAMES above NS_ME_MAXD sampled dimensions), -1 = no boxes
-    double set_margin = 0.0;    // ... 0 = the default
-    double set_pairs = -1.0;    // nfa_sampler_set_pairs: < 0 = the default, 0 = off, >= 1 = the safety factor on the ellipses' areas
-    double set_shear = -1.0;    // nfa_sampler_set_shear: < 0 = the default (engine option sampler_shear_pct), 0 = off, >= 1 = the safety factor
-    int *d_sh_mono = nullptr, *d_sh_start = nullptr;
+    int *d_livepix = nullptr;
     std::vector<int> fm;        // the sampled dimensions' slots
     size_t k_alloc = 0;         // proposal rows allocated per pixel
-    long ratio_max = NS_RATIO_MAX, kmax = NS_KMAX;   // options sampler_ratio_max / sampler_kmax as they stood at creation
     long raw_sum = 0, val_sum = 0;   // proposals drawn / evaluated since the last look at the active pixels
     std::vector<int> h_nlive;   // per-pixel live points (empty: d.N for everybody)
-    int max_ell = 0;            // nfa_sampler_set_ellipsoids (0: the default)
     std::vector<int> h_active, h_act;
     long rounds = 0;
     int  n_act = 0, check_every = 8;
-    size_t lds = 0, lds_refit = 0;
     bool ran = false;
     // host memory the device writes (mapped): per part, [rows of the round][sequence number of the round], 16 bytes each
     unsigned long long *h_pub = nullptr, *d_pub = nullptr;
     unsigned long long seq = 0;  // sequence number of the last proposing launch
 };
 
+// A device buffer of the sampler, recorded where it is allocated.  (The pointers the kernels only read are const in
+// NsDev; the host fills them through ns_mut.)
+template <class T> static hipError_t ns_alloc(nfa_sampler *s, T *&ptr, size_t count) {
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, sizeof(T) * count);
+    if (e != hipSuccess) return e;
+    s->bufs.push_back(p);
+    ptr = (T *)p;
+    return hipSuccess;
+}
+template <class T> static T *ns_mut(const T *p) { return const_cast<T *>(p); }
+
+// Device buffers that live as long as one call
+struct NsTemp {
+    std::vector<void *> bufs;
+    bool ok = true;
+    template <class T> T *get(size_t count) {
+        void *p = nullptr;
+        if (!ok || hipMalloc(&p, sizeof(T) * count) != hipSuccess) { ok = false; return nullptr; }
+        bufs.push_back(p);
+        return (T *)p;
+    }
+    ~NsTemp() { for (void *p : bufs) (void)hipFree(p); }
+};
+
+// The process options as knobs: the only place that reads them (sentinels and hundredths end here)
+static NsKnobs ns_engine_knobs() {
+    NsKnobs k;
+    if (g_eng.sampler_ellipsoids == 1) k.ellipsoids = 1;
+    if (g_eng.sampler_frames != -2) k.frames = g_eng.sampler_frames;
+    if (g_eng.sampler_margin_pct > 0) k.margin = 0.01 * g_eng.sampler_margin_pct;
+    if (g_eng.sampler_shear_pct >= 0) k.shear = 0.01 * g_eng.sampler_shear_pct;
+    if (g_eng.sampler_pairs_pct >= 0) k.pairs = 0.01 * g_eng.sampler_pairs_pct;
+    if (g_eng.sampler_walk_factor > 0) k.walk_factor = g_eng.sampler_walk_factor;
+    if (g_eng.sampler_ktarget >= 0) k.k_target = g_eng.sampler_ktarget;
+    if (g_eng.sampler_ratio_max > 0) k.ratio_max = g_eng.sampler_ratio_max;
+    if (g_eng.sampler_kmax > 0) k.kmax = g_eng.sampler_kmax;
+    k.walkers = g_eng.sampler_walkers;
+    k.refit_every = g_eng.sampler_refit_every;
+    return k;
+}
+static NsPlan ns_plan_of(const nfa_sampler *s) {
+    return ns_plan(s->d.D, s->d.DT, s->d.N, s->fm.data(), ns_merge(s->set, ns_engine_knobs()));
+}
+
+// NFA_NS_TIMING=1: what the kernels' stage clocks collected
+static void ns_timing_report(const NsDev &d) {
+    long h[64];
+    if (hipMemcpy(h, d.dbg, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
+        fprintf(stderr, "[ns timing, first listed pixel of part 0] update launches %ld: prologue %.1f us, loads %.1f us (%ld batches), counts+compaction %.1f us, "
+                "wave-0 pass %.1f us (%ld survivors, %ld replacements), tail %.1f us per launch\n", h[8], 0.01 * h[0] / h[8], 0.01 * h[1] / h[8], h[9],
+                0.01 * h[2] / h[8], 0.01 * h[3] / h[8], h[12], h[11], 0.01 * h[4] / h[8]);
+    if (hipMemcpy(h, d.dbg, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[14] > 0)
+        fprintf(stderr, "[ns timing, all update workgroups] %ld: mean %.1f us, longest %.1f us; walking ones %ld: mean %.1f us\n", h[14], 0.01 * h[13] / h[14],
+                0.01 * h[15], h[6], h[6] ? 0.01 * h[5] / h[6] : 0.0);
+    if (h[57]) fprintf(stderr, "[ns timing, refit workgroup 0] %ld refits: standardise %.1f, Gram %.1f, Cholesky %.1f, back substitution %.1f, w %.1f, covariance %.1f, "
+                       "its Cholesky + axis box %.1f, y %.1f, frames' boxes %.1f us\n", h[57], 0.01 * h[48] / h[57], 0.01 * h[49] / h[57], 0.01 * h[50] / h[57], 0.01 * h[51] / h[57],
+                       0.01 * h[52] / h[57], 0.01 * h[53] / h[57], 0.01 * h[54] / h[57], 0.01 * h[55] / h[57], 0.01 * h[56] / h[57]);
+    for (int b = 0; b < 16; ++b) if (h[16 + b]) fprintf(stderr, "    <= %5ld us: %9ld workgroups, %8.1f ms in all\n", 1l << b, h[16 + b], 1e-5 * h[32 + b]);
+}
+
+// The sampler's buffers, sized for n_pix pixels of nlive live points, cap_iter dead points and s->k_alloc proposals each
+static int ns_create_buffers(nfa_sampler *s, const int32_t *pix, size_t C) {
+    NsDev &d = s->d;
+    const size_t P = (size_t)d.P, N = (size_t)d.N, D = (size_t)d.D, DT = (size_t)d.DT, K = s->k_alloc, W = (size_t)d.w_stride;
+    bool ok = true;
+    auto A = [&](auto *&ptr, size_t count) { ok = ok && ns_alloc(s, ptr, count) == hipSuccess; };
+    A(d.pixmap, P); A(d.actlist, P); A(s->d_livepix, P * N);
+    A(d.fmap, D);
+    A(d.Ulive, P * N * D); A(d.Tlive, P * N * DT); A(d.Llive, P * N);
+    A(d.centre, P * NS_ME * D); A(d.axes, P * NS_ME * D * D);
+    A(d.elnv, P * NS_ME); A(d.nell, P);
+    A(d.n_iter, P); A(d.n_evals, P); A(d.cand_base, P); A(d.lnZ, P);
+    A(d.active, P); A(d.since_fit, P); A(d.use_cube, P); A(d.refit_due, P);
+    A(d.deadT, P * C * DT); A(d.deadL, P * C); A(d.deadlnw, P * C);
+    A(d.candU, P * K * D); A(d.candT, P * K * DT); A(d.candL, P * K);
+    A(d.candpix, P * K); A(d.valid, P * K); A(d.slot, P * K); A(d.count, NS_PARTS);
+    A(d.walk, P); A(d.wstep, P); A(d.wW, P); A(d.wscale, P);
+    A(d.wLthr, P); A(d.wacc_sum, P); A(d.wtot_sum, P);
+    A(d.wU, P * W * D); A(d.wT, P * W * DT); A(d.wL, P * W);
+    A(d.wnacc, P * W); A(d.lnvol, P);
+    A(d.ubox, P * D * 2); A(d.fbox, P * (NS_FRAMES_MAX + 1) * D * 2);
+    A(d.rj_scan, P); A(d.rj_acc, P); A(d.rj_raw, P); A(d.rj_val, P);
+    A(d.ln_pass, P);
+    A(d.frames, (size_t)NS_FRAMES_MAX * D * D);
+    A(d.sh_mono, NS_SHEAR_MMAX * 2); A(d.sh_start, D);
+    A(d.Kp, P); A(d.pair_tab, P * (D * (D - 1) / 2 + 1) * 5);
+    A(d.sh_mu, P * D); A(d.sh_sg, P * D); A(d.sh_beta, P * D * NS_SHEAR_MMAX);
+    if (getenv("NFA_NS_TIMING")) A(d.dbg, 64);
+    if (!ok) return fail(NFA_ERR_DEVICE, "out of device memory for the sampler state");
+    if (d.dbg) HIP_TRY(hipMemset(d.dbg, 0, sizeof(long) * 64));
+    std::vector<int> pm(P);
+    for (size_t p = 0; p < P; ++p) pm[p] = pix ? pix[p] : 0;
+    HIP_TRY(hipMemcpy(ns_mut(d.pixmap), pm.data(), sizeof(int) * P, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ns_mut(d.fmap), s->fm.data(), sizeof(int) * D, hipMemcpyHostToDevice));
+    return NFA_OK;
+}
+
+// The bounds of the first n_pix listed pixels of view dv that are due (direct: of all of them, before the first round)
+static void ns_launch_refit(const nfa_sampler *s, const NsDev &dv, int n_pix, int direct, hipStream_t st) {
+    hipLaunchKernelGGL(ns_refit_kernel, dim3((unsigned)n_pix), dim3(s->plan.refit_threads), s->plan.lds_refit, st, dv, n_pix, direct);
+}
+
+// Can a pixel be due for a refit in the round after `rounds` of them?  Rejection-mode pixels every refit_every-th
+// round, walking ones at a cycle's end -- and in a cycle's first round, where a pixel that has just turned to walks
+// brings along what it collected before
+static bool ns_refit_can_be_due(const NsDev &d, long rounds) {
+    return (rounds + 1) % d.refit_every == 0 || (d.method != 0 && ((rounds + 1) % d.n_steps == 0 || rounds % d.n_steps == 0));
+}
+
+// Candidates per pixel in the rounds until the next look at the active pixels: the round's batch stays near b_target
+// however few pixels are left.  With boxes most proposals are vetoed for free: so many more are drawn that a round
+// still evaluates ~b_target
+static int ns_chunk_kr(nfa_sampler *s) {
+    long ratio = 1;
+    if (s->d.boxes && s->raw_sum > 0)
+        ratio = std::min<long>(s->plan.ratio_max, std::max<long>(1, (s->raw_sum + s->val_sum / 2) / std::max<long>(s->val_sum, 1)));
+    s->raw_sum = s->val_sum = 0;
+    // (n_act * Kr rows <= ratio_max * b_target: what nfa_sampler_create allocated)
+    return (int)std::min<long>(s->plan.kmax, std::max<long>(s->d.K, (s->b_target * ratio) / s->n_act));
+}
+
+// Every part works on its own slices of the proposal / compact-row buffers and of the list of active pixels
+static void ns_part_views(const nfa_sampler *s, int n_parts, int Kr, int *n_pix_h, NsDev *dh) {
+    const NsDev &d = s->d;
+    long first = 0;
+    for (int h = 0; h < NS_PARTS; ++h) {
+        n_pix_h[h] = h < n_parts ? (s->n_act * (h + 1)) / n_parts - (s->n_act * h) / n_parts : 0;
+        dh[h] = d;
+        const long off = first * Kr;
+        dh[h].candU += off * d.D; dh[h].candT += off * d.DT; dh[h].candL += off;
+        dh[h].candpix += off; dh[h].valid += off; dh[h].slot += off;
+        dh[h].count += h; dh[h].actlist += first;
+        dh[h].host_rows = (int *)(s->d_pub + 2 * h); dh[h].host_seq = s->d_pub + 2 * h + 1;
+        first += n_pix_h[h];
+    }
+}
+
+// Kr proposals for each of the view's n_pix pixels; compile-time dimensions where they are common
+static void ns_launch_propose(const NsDev &dv, int n_pix, int Kr, hipStream_t st) {
+    const dim3 pg((unsigned)((Kr + 127) / 128), (unsigned)std::min(n_pix, 65535), (unsigned)((n_pix + 65534) / 65535));
+    switch (dv.D) {
+    case 5: hipLaunchKernelGGL(ns_propose_kernel<5>, pg, dim3(NS_PROPOSE_THREADS), 0, st, dv, n_pix, Kr); break;
+    case 10: hipLaunchKernelGGL(ns_propose_kernel_v128<10>, pg, dim3(NS_PROPOSE_THREADS), 0, st, dv, n_pix, Kr); break;
+    case 15: hipLaunchKernelGGL(ns_propose_kernel<15>, pg, dim3(NS_PROPOSE_THREADS), 0, st, dv, n_pix, Kr); break;
+    default: hipLaunchKernelGGL(ns_propose_kernel<0>, pg, dim3(NS_PROPOSE_THREADS), 0, st, dv, n_pix, Kr); break;
+    }
+}
+
+// The proposals of part h's round s->seq that lie inside the prior: the only ones worth a likelihood.  Their number is
+// the publishing launch's last store into the mapped buffer, behind it the round's sequence number
+static int ns_wait_rows(const nfa_sampler *s, int h, hipStream_t st, int *n_rows) {
+    volatile unsigned long long *pub = s->h_pub + 2 * h;
+    const auto t_start = std::chrono::steady_clock::now();
+    for (uint64_t spins = 0; __atomic_load_n(pub + 1, __ATOMIC_ACQUIRE) != s->seq; ++spins) {
+        if ((spins & 0x3fff) == 0x3fff && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) {
+            // nothing came back: a fault surfaces here, a very slow launch finishes
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+    }
+    *n_rows = (int)(unsigned)(pub[0] & 0xffffffffull);
+    return NFA_OK;
+}
+
 extern "C" {
 
 int nfa_sampler_destroy(nfa_sampler *s) {
     if (!s) return NFA_OK;
-    NsDev &d = s->d;
-    if (d.dbg) {
-        long h[64];
-        if (hipMemcpy(h, d.dbg, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
-            fprintf(stderr, "[ns timing, first listed pixel of part 0] update launches %ld: prologue %.1f us, loads %.1f us (%ld batches), counts+compaction %.1f us, "
-                    "wave-0 pass %.1f us (%ld survivors, %ld replacements), tail %.1f us per launch\n", h[8], 0.01 * h[0] / h[8], 0.01 * h[1] / h[8], h[9],
-                    0.01 * h[2] / h[8], 0.01 * h[3] / h[8], h[12], h[11], 0.01 * h[4] / h[8]);
-        if (hipMemcpy(h, d.dbg, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[14] > 0)
-            fprintf(stderr, "[ns timing, all update workgroups] %ld: mean %.1f us, longest %.1f us; walking ones %ld: mean %.1f us\n", h[14], 0.01 * h[13] / h[14],
-                    0.01 * h[15], h[6], h[6] ? 0.01 * h[5] / h[6] : 0.0);
-        if (h[57]) fprintf(stderr, "[ns timing, refit workgroup 0] %ld refits: standardise %.1f, Gram %.1f, Cholesky %.1f, back substitution %.1f, w %.1f, covariance %.1f, "
-                           "its Cholesky + axis box %.1f, y %.1f, frames' boxes %.1f us\n", h[57], 0.01 * h[48] / h[57], 0.01 * h[49] / h[57], 0.01 * h[50] / h[57], 0.01 * h[51] / h[57],
-                           0.01 * h[52] / h[57], 0.01 * h[53] / h[57], 0.01 * h[54] / h[57], 0.01 * h[55] / h[57], 0.01 * h[56] / h[57]);
-        for (int b = 0; b < 16; ++b) if (h[16 + b]) fprintf(stderr, "    <= %5ld us: %9ld workgroups, %8.1f ms in all\n", 1l << b, h[16 + b], 1e-5 * h[32 + b]);
-        (void)hipFree(d.dbg);
-    }
-    void *ptrs[] = {d.Ulive, d.Tlive, d.Llive, d.centre, d.axes, d.n_iter, d.n_evals, d.cand_base, d.lnZ, d.active, d.use_cube,
-                    d.since_fit, d.refit_due, d.deadT, d.deadL, d.deadlnw, d.candU, d.candT, d.candL, d.candpix, d.valid, d.slot, d.count,
-                    d.walk, d.wstep, d.wW, d.wscale, d.wLthr, d.wacc_sum, d.wtot_sum, d.wU, d.wT, d.wL, d.wnacc, d.lnvol, d.elnv, d.nell,
-                    s->d_pixmap, s->d_actlist, s->d_livepix, s->d_fmap, s->d_nlive, s->d_updp, s->d_capp,
-                    s->d_frames, d.ubox, d.fbox, d.rj_scan, d.rj_acc, d.rj_raw, d.rj_val, d.ln_pass,
-                    s->d_sh_mono, s->d_sh_start, d.sh_mu, d.sh_sg, d.sh_beta, d.Kp, d.pair_tab};
-    for (void *p : ptrs) (void)hipFree(p);
+    if (s->d.dbg) ns_timing_report(s->d);
+    for (void *p : s->bufs) (void)hipFree(p);
     if (s->h_pub) (void)hipHostFree(s->h_pub);
     delete s;
     return NFA_OK;
@@ -1767,60 +1856,27 @@ int nfa_sampler_create(nfa_sampler **out, nfa_runner *r, const int32_t *pix, int
     if (batch_target < 1 || batch_target > (1 << 26)) return fail(NFA_ERR_ARG, "batch_target out of range");
     if (r->ndim > NS_MAXD) return fail(NFA_ERR_ARG, "too many dimensions");
     int rc = check_pix(r, pix, n_pix); if (rc) return rc;
-    nfa_sampler *s = new nfa_sampler();
-    s->r = r;
-    NsDev &d = s->d;
     // sampled dimensions: the unit-cube slots the likelihood depends on (free_mask[ndim], NULL = all);
     // a constant or duplicated parameter's slot is integrated out exactly by not sampling it
     std::vector<int> fm;
     for (int j = 0; j < r->ndim; ++j) if (!free_mask || free_mask[j]) fm.push_back(j);
-    if (fm.empty()) { delete s; return fail(NFA_ERR_ARG, "no free dimension to sample"); }
-    d.P = (int)n_pix; d.N = nlive; d.D = (int)fm.size(); d.DT = r->ndim; d.K = n_cand; d.cap = (long)cap_iter;
-    const size_t P = (size_t)n_pix, N = (size_t)nlive, D = fm.size(), DT = (size_t)r->ndim, C = (size_t)cap_iter;
-    s->b_target = std::max<long>((long)n_pix * n_cand, (long)batch_target);
-    // rows of the candidate buffers: n_act * Kr <= max(b_target, n_act * K) <= b_target -- times NS_RATIO_MAX where boxes
-    // may veto proposals for free (one-ellipsoid bounds: more than NS_ME_MAXD sampled dimensions, or on request)
-    // (the two process options are read ONCE, here: the buffers are sized for them, and a value changed while the sampler
-    // lives must not outrun the buffers)
-    const size_t ratio_alloc = g_eng.sampler_ratio_max > 0 ? g_eng.sampler_ratio_max : NS_RATIO_MAX;
-    s->ratio_max = (long)ratio_alloc;
-    s->kmax = g_eng.sampler_kmax > 0 ? g_eng.sampler_kmax : NS_KMAX;
-    const size_t K = ((size_t)s->b_target * ratio_alloc + P - 1) / P;       // so that P * K >= ratio_max * b_target
-    s->k_alloc = K;
-    std::vector<int> pm(P);
-    for (size_t p = 0; p < P; ++p) pm[p] = pix ? pix[p] : 0;
-#define NS_ALLOC(ptr, type, count) \
-    if (hipMalloc((void **)&(ptr), sizeof(type) * (count)) != hipSuccess) { \
-        nfa_sampler_destroy(s); return fail(NFA_ERR_DEVICE, "out of device memory for the sampler state"); }
-    NS_ALLOC(s->d_pixmap, int, P); NS_ALLOC(s->d_actlist, int, P); NS_ALLOC(s->d_livepix, int, P * N);
-    NS_ALLOC(s->d_fmap, int, D);
-    NS_ALLOC(d.Ulive, double, P * N * D); NS_ALLOC(d.Tlive, double, P * N * DT); NS_ALLOC(d.Llive, double, P * N);
-    NS_ALLOC(d.centre, double, P * NS_ME * D); NS_ALLOC(d.axes, double, P * NS_ME * D * D);
-    NS_ALLOC(d.elnv, double, P * NS_ME); NS_ALLOC(d.nell, int, P);
-    NS_ALLOC(d.n_iter, long, P); NS_ALLOC(d.n_evals, long, P); NS_ALLOC(d.cand_base, long, P); NS_ALLOC(d.lnZ, double, P);
-    NS_ALLOC(d.active, int, P); NS_ALLOC(d.since_fit, int, P); NS_ALLOC(d.use_cube, int, P); NS_ALLOC(d.refit_due, int, P);
-    NS_ALLOC(d.deadT, double, P * C * DT); NS_ALLOC(d.deadL, double, P * C); NS_ALLOC(d.deadlnw, double, P * C);
-    NS_ALLOC(d.candU, double, P * K * D); NS_ALLOC(d.candT, double, P * K * DT); NS_ALLOC(d.candL, double, P * K);
-    NS_ALLOC(d.candpix, int, P * K); NS_ALLOC(d.valid, int, P * K); NS_ALLOC(d.slot, int, P * K); NS_ALLOC(d.count, int, NS_PARTS);
-    NS_ALLOC(d.walk, int, P); NS_ALLOC(d.wstep, int, P); NS_ALLOC(d.wW, int, P); NS_ALLOC(d.wscale, double, P);
-    NS_ALLOC(d.wLthr, double, P); NS_ALLOC(d.wacc_sum, long, P); NS_ALLOC(d.wtot_sum, long, P);
-    d.w_fixed = g_eng.sampler_walkers;
-    d.w_stride = d.w_fixed > 0 ? d.w_fixed : ns_walkers_for(N);      // (a pixel's own count can only be smaller than N)
-    NS_ALLOC(d.wU, double, P * d.w_stride * D); NS_ALLOC(d.wT, double, P * d.w_stride * DT); NS_ALLOC(d.wL, double, P * d.w_stride);
-    NS_ALLOC(d.wnacc, int, P * d.w_stride); NS_ALLOC(d.lnvol, double, P);
-    NS_ALLOC(d.ubox, double, P * D * 2); NS_ALLOC(d.fbox, double, P * (NS_FRAMES_MAX + 1) * D * 2);
-    NS_ALLOC(d.rj_scan, long, P); NS_ALLOC(d.rj_acc, long, P); NS_ALLOC(d.rj_raw, long, P); NS_ALLOC(d.rj_val, long, P);
-    NS_ALLOC(d.ln_pass, double, P);
-    NS_ALLOC(s->d_frames, double, (size_t)NS_FRAMES_MAX * D * D);
-    NS_ALLOC(s->d_sh_mono, int, NS_SHEAR_MMAX * 2); NS_ALLOC(s->d_sh_start, int, D);
-    NS_ALLOC(d.Kp, int, P); NS_ALLOC(d.pair_tab, double, P * (D * (D - 1) / 2 + 1) * 5);
-    NS_ALLOC(d.sh_mu, double, P * D); NS_ALLOC(d.sh_sg, double, P * D); NS_ALLOC(d.sh_beta, double, P * D * NS_SHEAR_MMAX);
+    if (fm.empty()) return fail(NFA_ERR_ARG, "no free dimension to sample");
+    nfa_sampler *s = new nfa_sampler();
+    s->r = r;
     s->fm = fm;
-    if (getenv("NFA_NS_TIMING")) { NS_ALLOC(d.dbg, long, 64); HIP_TRY(hipMemset(d.dbg, 0, sizeof(long) * 64)); }
-#undef NS_ALLOC
-    HIP_TRY(hipMemcpy(s->d_pixmap, pm.data(), sizeof(int) * P, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_fmap, fm.data(), sizeof(int) * D, hipMemcpyHostToDevice));
-    d.pixmap = s->d_pixmap; d.actlist = s->d_actlist; d.fmap = s->d_fmap;
+    NsDev &d = s->d;
+    d.P = (int)n_pix; d.N = nlive; d.D = (int)fm.size(); d.DT = r->ndim; d.K = n_cand; d.cap = (long)cap_iter;
+    s->b_target = std::max<long>((long)n_pix * n_cand, (long)batch_target);
+    // The three process options the buffers are sized for are read ONCE, here, and pinned: a value changed while the
+    // sampler lives must not outrun the buffers
+    s->plan = ns_plan_of(s);
+    s->set.ratio_max = s->plan.ratio_max; s->set.kmax = s->plan.kmax; s->set.walkers = s->plan.w_fixed;
+    d.w_fixed = s->plan.w_fixed; d.w_stride = s->plan.w_stride;
+    // rows of the candidate buffers: n_act * Kr <= max(b_target, n_act * K) <= b_target -- times ratio_max where boxes
+    // may veto proposals for free: P * k_alloc >= ratio_max * b_target
+    s->k_alloc = ((size_t)s->b_target * (size_t)s->plan.ratio_max + (size_t)n_pix - 1) / (size_t)n_pix;
+    rc = ns_create_buffers(s, pix, (size_t)cap_iter);
+    if (rc) { nfa_sampler_destroy(s); return rc; }
     *out = s;
     return NFA_OK;
 }
@@ -1841,27 +1897,29 @@ int nfa_sampler_set_pixel_nlive(nfa_sampler *s, const int32_t *nlive, const int6
         if (cap[p] < 1 || cap[p] > d.cap || upd[p] < 1) return fail(NFA_ERR_ARG, "a pixel's cap / upd is out of range");
         hn[p] = nlive[p]; hc[p] = (long)cap[p]; hu[p] = upd[p];
     }
-    if (!s->d_nlive) {
-        HIP_TRY(hipMalloc((void **)&s->d_nlive, sizeof(int) * P));
-        HIP_TRY(hipMalloc((void **)&s->d_updp, sizeof(int) * P));
-        HIP_TRY(hipMalloc((void **)&s->d_capp, sizeof(long) * P));
+    int *dn = ns_mut(d.nlive), *du = ns_mut(d.updp);
+    long *dc = ns_mut(d.capp);
+    if (!dn) {
+        HIP_TRY(ns_alloc(s, dn, P));
+        HIP_TRY(ns_alloc(s, du, P));
+        HIP_TRY(ns_alloc(s, dc, P));
     }
-    HIP_TRY(hipMemcpy(s->d_nlive, hn.data(), sizeof(int) * P, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_updp, hu.data(), sizeof(int) * P, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_capp, hc.data(), sizeof(long) * P, hipMemcpyHostToDevice));
-    d.nlive = s->d_nlive; d.updp = s->d_updp; d.capp = s->d_capp;
+    HIP_TRY(hipMemcpy(dn, hn.data(), sizeof(int) * P, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(du, hu.data(), sizeof(int) * P, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dc, hc.data(), sizeof(long) * P, hipMemcpyHostToDevice));
+    d.nlive = dn; d.updp = du; d.capp = dc;       // (only now: the kernels take a null pointer as "everybody the same")
     s->h_nlive = hn;
     return NFA_OK;
 }
 
 // Free rejections by boxes (one-ellipsoid bounds): n_frames rotated frames beside the unit cube's axes and the ellipsoid's
-// own (-2: the default -- none; -1: no boxes; 0..64; NS_FRAMES = 32 is the measured choice), margin = the
+// own (-2: the default -- NS_FRAMES = 32 where the bound is sheared, none elsewhere; -1: no boxes; 0..64), margin = the
 // factor c of a face's distance beyond the extreme live point (0: the default, NS_MARGIN_C).  Before nfa_sampler_begin.
 int nfa_sampler_set_boxes(nfa_sampler *s, int n_frames, double margin) {
     if (!s || n_frames < -2 || n_frames > NS_FRAMES_MAX || !(margin >= 0.0) || margin > 100.0) return fail(NFA_ERR_ARG, "boxes: frames -2 (default), -1 (none) .. 64; margin >= 0");
     if (s->ran) return fail(NFA_ERR_STATE, "call nfa_sampler_set_boxes before nfa_sampler_begin");
-    s->set_frames = n_frames;
-    s->set_margin = margin;
+    s->set.frames = n_frames != -2 ? n_frames : NS_UNSET;
+    s->set.margin = margin > 0.0 ? margin : NS_UNSET;
     return NFA_OK;
 }
 
@@ -1871,7 +1929,7 @@ int nfa_sampler_set_boxes(nfa_sampler *s, int n_frames, double margin) {
 int nfa_sampler_set_shear(nfa_sampler *s, double enlarge) {
     if (!s || (enlarge > 0.0 && enlarge < 1.0) || enlarge > 1e6 || enlarge != enlarge) return fail(NFA_ERR_ARG, "shear: 0 (off), < 0 (default) or a safety factor >= 1");
     if (s->ran) return fail(NFA_ERR_STATE, "call nfa_sampler_set_shear before nfa_sampler_begin");
-    s->set_shear = enlarge;
+    s->set.shear = enlarge >= 0.0 ? enlarge : NS_UNSET;
     return NFA_OK;
 }
 
@@ -1880,14 +1938,14 @@ int nfa_sampler_set_shear(nfa_sampler *s, double enlarge) {
 int nfa_sampler_set_pairs(nfa_sampler *s, double enlarge) {
     if (!s || (enlarge > 0.0 && enlarge < 1.0) || enlarge > 1e6 || enlarge != enlarge) return fail(NFA_ERR_ARG, "pairs: 0 (off), < 0 (default) or a safety factor >= 1");
     if (s->ran) return fail(NFA_ERR_STATE, "call nfa_sampler_set_pairs before nfa_sampler_begin");
-    s->set_pairs = enlarge;
+    s->set.pairs = enlarge >= 0.0 ? enlarge : NS_UNSET;
     return NFA_OK;
 }
 
 int nfa_sampler_set_ellipsoids(nfa_sampler *s, int max_ellipsoids) {
     if (!s || max_ellipsoids < 0 || max_ellipsoids > NS_ME) return fail(NFA_ERR_ARG, "ellipsoids per pixel: 0 (default) .. 4");
     if (s->ran) return fail(NFA_ERR_STATE, "call nfa_sampler_set_ellipsoids before nfa_sampler_begin");
-    s->max_ell = max_ellipsoids;
+    s->set.ellipsoids = max_ellipsoids > 0 ? max_ellipsoids : NS_UNSET;
     return NFA_OK;
 }
 
@@ -1908,6 +1966,17 @@ int nfa_sampler_begin(nfa_sampler *s, double tol, double efr, int64_t seed, int6
     { int rcf = sync_all_lanes(r); if (rcf) return rcf; }    // the lanes are the sampler's from here on
     NsDev &d = s->d;
     const int P = d.P, N = d.N, D = d.D;
+    hipStream_t st = r->lanes[0];
+    // the run's form, and its copy where the kernels read it
+    const NsPlan plan = ns_plan_of(s);
+    if (plan.error) return fail(NFA_ERR_STATE, plan.error);
+    s->plan = plan;
+    d.max_ell = plan.max_ell; d.stage_live = plan.stage_live; d.multi = plan.multi;
+    d.shear = plan.shear; d.sh_M = plan.sh_M;
+    if (plan.shear) d.ln_enlarge_shear = log(plan.shear_enlarge);
+    d.boxes = plan.boxes; d.n_frames = plan.n_frames; d.margin_c = plan.margin_c;
+    d.pairs = plan.pairs; d.pairs_enlarge = plan.pairs_enlarge;
+    d.walk_factor = plan.walk_factor; d.k_target = plan.k_target; d.refit_every = plan.refit_every;
     d.ln_enlarge = log(enlarge);
     d.method = method; d.n_steps = n_steps;
     d.tol = tol; d.maxiter = (long)maxiter; d.upd = upd; d.seed = (uint64_t)seed; d.log_zero = log_zero;
@@ -1915,24 +1984,15 @@ int nfa_sampler_begin(nfa_sampler *s, double tol, double efr, int64_t seed, int6
     d.ln_efr = log(efr);
     d.ln_vball = 0.5 * D * log(M_PI) - lgamma(0.5 * D + 1.0);
     s->check_every = check_every;
-    hipStream_t st = r->lanes[0];
-    HIP_TRY(hipMemsetAsync(d.n_iter, 0, sizeof(long) * P, st));
-    HIP_TRY(hipMemsetAsync(d.cand_base, 0, sizeof(long) * P, st));
-    HIP_TRY(hipMemsetAsync(d.since_fit, 0, sizeof(int) * P, st));
-    HIP_TRY(hipMemsetAsync(d.refit_due, 0, sizeof(int) * P, st));
-    HIP_TRY(hipMemsetAsync(d.walk, 0, sizeof(int) * P, st));
-    HIP_TRY(hipMemsetAsync(d.wstep, 0, sizeof(int) * P, st));
-    HIP_TRY(hipMemsetAsync(d.wacc_sum, 0, sizeof(long) * P, st));
-    HIP_TRY(hipMemsetAsync(d.wtot_sum, 0, sizeof(long) * P, st));
-    HIP_TRY(hipMemsetAsync(d.rj_scan, 0, sizeof(long) * P, st));
-    HIP_TRY(hipMemsetAsync(d.rj_acc, 0, sizeof(long) * P, st));
-    HIP_TRY(hipMemsetAsync(d.rj_raw, 0, sizeof(long) * P, st));
-    HIP_TRY(hipMemsetAsync(d.rj_val, 0, sizeof(long) * P, st));
-    HIP_TRY(hipMemsetAsync(d.ln_pass, 0, sizeof(double) * P, st));
-    // (a pixel starts with a small share and doubles it while its rounds accept little: started at the round's Kr, a run of
-    // two pixels drew 65 k proposals per pixel in its first round, where every second one is accepted, and halved from there)
+    s->raw_sum = s->val_sum = 0;
+    // zero: the per-pixel counters and flags
+    const struct { void *ptr; size_t elem; } zeroed[] = {
+        {d.n_iter, sizeof(long)}, {d.cand_base, sizeof(long)}, {d.since_fit, sizeof(int)}, {d.refit_due, sizeof(int)},
+        {d.walk, sizeof(int)}, {d.wstep, sizeof(int)}, {d.wacc_sum, sizeof(long)}, {d.wtot_sum, sizeof(long)},
+        {d.rj_scan, sizeof(long)}, {d.rj_acc, sizeof(long)}, {d.rj_raw, sizeof(long)}, {d.rj_val, sizeof(long)},
+        {d.ln_pass, sizeof(double)}};
+    for (const auto &z : zeroed) HIP_TRY(hipMemsetAsync(z.ptr, 0, z.elem * P, st));
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d.Kp, NS_KP_START, P, st));
-    d.k_target = g_eng.sampler_ktarget >= 0 ? g_eng.sampler_ktarget : NS_K_TARGET;
     {   // live points
         const long tot = (long)P * N;
         hipLaunchKernelGGL(ns_init_live_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d, s->d_livepix);
@@ -1943,6 +2003,7 @@ int nfa_sampler_begin(nfa_sampler *s, double tol, double efr, int64_t seed, int6
                            d.Llive, (long)P * N, log_zero);
         HIP_TRY(hipGetLastError());
     }
+    // upload: the counters' starting values, then the tables of the shear and of the boxes
     std::vector<long> h_evals((size_t)P, (long)N);
     for (size_t p = 0; p < s->h_nlive.size(); ++p) h_evals[p] = s->h_nlive[p];      // a pixel's own live points were its first evaluations
     std::vector<double> h_lnz((size_t)P, -INFINITY);
@@ -1950,74 +2011,31 @@ int nfa_sampler_begin(nfa_sampler *s, double tol, double efr, int64_t seed, int6
     HIP_TRY(hipMemcpyAsync(d.n_evals, h_evals.data(), sizeof(long) * P, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d.lnZ, h_lnz.data(), sizeof(double) * P, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d.active, s->h_active.data(), sizeof(int) * P, hipMemcpyHostToDevice, st));
-    s->lds = sizeof(double) * ns_upd_lds(N);                                // the update workgroup: the live log-likelihoods, a segment's survivors
-    s->lds_refit = sizeof(double) * (8 + (size_t)D * D + (size_t)((D + 1) & ~1));  // the refit workgroup: reductions, ...
-    d.stage_live = (size_t)N * D * sizeof(double) <= 96 * 1024 ? 1 : 0;
-    d.refit_every = g_eng.sampler_refit_every;
-    // When does a pixel give up rejection sampling for constrained walks?  Measured on config 5 (profiles/r03/
-    // sweep_walk_factor.txt): with ten sampled dimensions the walks win from an acceptance of ~1 in 2 n_steps down (the
-    // run takes 7.0-7.2 s for factors 1..4, 8.6 s at 32, 10.9 s at 64); with five they hardly ever do -- a rejection
-    // round is one large batch, a walk cycle n_steps small ones, and the run goes from 1.16 s (factor 2) to 0.84 s (64;
-    // rejection only: 0.79 s).  The walks stay as the way out of a bound that has become hopeless.
-    d.walk_factor = g_eng.sampler_walk_factor > 0 ? g_eng.sampler_walk_factor : (D <= NS_WALK_LOWD ? NS_WALK_FACTOR_LOWD : NS_WALK_FACTOR);
-    if (d.stage_live) s->lds_refit += sizeof(double) * (size_t)N * D;       // ... the live points ...
-    d.max_ell = s->max_ell > 0 ? s->max_ell : (g_eng.sampler_ellipsoids == 1 ? 1 : NS_ME);
-    d.multi = (d.stage_live && D <= NS_ME_MAXD && d.max_ell > 1) ? 1 : 0;
-    if (d.multi) s->lds_refit += sizeof(double) * (size_t)((NS_ME + 2) * ns_me_slot(D)) + sizeof(int) * (size_t)((N + 3) & ~3);   // ... fit slots, labels
-    {   // the shear: one-ellipsoid bounds of all five free parameters of two or three components
-        const double enl = s->set_shear >= 0.0 ? s->set_shear : g_eng.sampler_shear_pct >= 0 ? 0.01 * g_eng.sampler_shear_pct : NS_SHEAR_ENLARGE;
-        const int nc = D / 5;
-        bool shape = (D == 10 || D == 15) && d.DT == 6 * nc;
-        for (int j = 0; shape && j < D; ++j) shape = (s->fm[(size_t)j] % nc) == (j % nc);
-        d.shear = (enl >= 1.0 && shape && !d.multi && d.stage_live) ? 1 : 0;
-        d.sh_M = 0;
-        if (d.shear) {
-            std::vector<int> mono, start;
-            ns_shear_monomials(D, nc, mono, start);
-            d.sh_M = (int)mono.size() / 2;
-            if (d.sh_M > NS_SHEAR_MMAX) return fail(NFA_ERR_STATE, "shear: too many monomials");
-            HIP_TRY(hipMemcpyAsync(s->d_sh_mono, mono.data(), sizeof(int) * mono.size(), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(s->d_sh_start, start.data(), sizeof(int) * start.size(), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            d.ln_enlarge_shear = log(enl);
-            s->lds_refit += sizeof(double) * ((size_t)d.sh_M * d.sh_M + (size_t)D * d.sh_M + 2 * (size_t)D + 2);
-        }
-        d.sh_mono = s->d_sh_mono; d.sh_start = s->d_sh_start;
+    if (plan.shear) {
+        std::vector<int> mono, start;
+        ns_shear_monomials(D, D / 5, mono, start);
+        HIP_TRY(hipMemcpyAsync(ns_mut(d.sh_mono), mono.data(), sizeof(int) * mono.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ns_mut(d.sh_start), start.data(), sizeof(int) * start.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));                       // (the vectors go out of scope)
     }
-    {   // free rejections by boxes: one-ellipsoid bounds whose live points are staged in LDS
-        // (off unless asked for: on BASELINE config 5 the boxes save a quarter of the evaluations of the two-component runs
-        // and cost more than that in longer rounds -- DESIGN section 10; a bright pixel alone needs a third of the walks' evaluations)
-        // (by default: NS_FRAMES frames where the bound is sheared -- there the pair halves the evaluations of config 5's
-        // two-component runs in less time than the walks take -- and none elsewhere)
-        int nf = s->set_frames != -2 ? s->set_frames : g_eng.sampler_frames != -2 ? g_eng.sampler_frames : (d.shear ? NS_FRAMES : -1);
-        d.boxes = (!d.multi && d.stage_live && nf >= 0) ? 1 : 0;
-        d.n_frames = d.boxes ? nf : 0;
-        d.margin_c = s->set_margin > 0.0 ? s->set_margin : g_eng.sampler_margin_pct > 0 ? 0.01 * g_eng.sampler_margin_pct : NS_MARGIN_C;
-        if (d.boxes && d.n_frames > 0) {
-            std::vector<double> Q;
-            ns_make_frames(D, d.n_frames, Q);
-            HIP_TRY(hipMemcpyAsync(s->d_frames, Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));                   // (Q goes out of scope)
-        }
-        d.frames = s->d_frames;
-        s->raw_sum = s->val_sum = 0;
-        const double pe = s->set_pairs >= 0.0 ? s->set_pairs : g_eng.sampler_pairs_pct >= 0 ? 0.01 * g_eng.sampler_pairs_pct : NS_PAIRS_ENLARGE;
-        d.pairs = (d.shear && d.boxes && pe >= 1.0) ? 1 : 0;
-        d.pairs_enlarge = pe;
-        if (d.pairs && (size_t)(D * (D - 1) / 2) * 4 > (size_t)d.sh_M * d.sh_M) d.pairs = 0;      // (they are fitted in the shear's scratch)
+    if (plan.boxes && plan.n_frames > 0) {
+        std::vector<double> Q;
+        ns_make_frames(D, plan.n_frames, Q);
+        HIP_TRY(hipMemcpyAsync(ns_mut(d.frames), Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));                       // (Q goes out of scope)
     }
-    if (s->lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)ns_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
-    if (s->lds_refit > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)ns_refit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_refit));
-    hipLaunchKernelGGL(ns_refit_kernel, dim3((unsigned)P), dim3(d.multi ? 64 : NS_REFIT_THREADS), s->lds_refit, st, d, P, 1);   // first ellipsoids
+    if (plan.lds_update > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void *)ns_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_update));
+    if (plan.lds_refit > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void *)ns_refit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_refit));
+    ns_launch_refit(s, d, P, 1, st);                             // first ellipsoids
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     s->rounds = 0;
     s->n_act = maxiter > 0 ? P : 0;
     s->h_act.resize((size_t)P);
     for (int p = 0; p < P; ++p) s->h_act[p] = p;
-    if (s->n_act) HIP_TRY(hipMemcpy(s->d_actlist, s->h_act.data(), sizeof(int) * P, hipMemcpyHostToDevice));
+    if (s->n_act) HIP_TRY(hipMemcpy(ns_mut(d.actlist), s->h_act.data(), sizeof(int) * P, hipMemcpyHostToDevice));
     s->ran = true;
     return NFA_OK;
 }
@@ -2028,7 +2046,7 @@ int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active_ou
     RUNNER_LOCK(r);
     { int rcf = flush_pending(r); if (rcf) return rcf; }
     NsDev &d = s->d;
-    const int P = d.P, K = d.K, D = d.D;
+    const int P = d.P;
     // The active pixels are split in groups that run on different stream lanes: proposing and
     // updating one group (latency-bound, few waves) overlaps the likelihood batch of another.  A pixel's random stream and decisions do not depend on its company, so the
     // split changes nothing in the results.
@@ -2042,44 +2060,16 @@ int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active_ou
         HIP_TRY(hipMemcpy(d.count, zeros, sizeof(int) * NS_PARTS, hipMemcpyHostToDevice));   // the publishing launches leave them at zero
     }
     for (int64_t chunk = 0; s->n_act > 0 && (max_chunks <= 0 || chunk < max_chunks); ++chunk) {
-        // candidates per pixel: the round's batch stays near b_target however few pixels are left
         const int n_act = s->n_act;
-        // with boxes most proposals are vetoed for free: so many more are drawn that a round still evaluates ~b_target
-        long ratio = 1;
-        const long ratio_max = s->ratio_max;
-        if (d.boxes && s->raw_sum > 0) ratio = std::min<long>(ratio_max, std::max<long>(1, (s->raw_sum + s->val_sum / 2) / std::max<long>(s->val_sum, 1)));
-        s->raw_sum = s->val_sum = 0;
-        const long kmax = s->kmax;
-        const int Kr = (int)std::min<long>(kmax, std::max<long>(K, (s->b_target * ratio) / n_act));    // (n_act * Kr rows <= NS_RATIO_MAX * b_target: what nfa_sampler_create allocated)
+        const int Kr = ns_chunk_kr(s);
         int n_pix_h[NS_PARTS];
         NsDev dh[NS_PARTS];
-        {   // every part works on its own slices of the proposal / compact-row buffers
-            long first = 0;
-            for (int h = 0; h < NS_PARTS; ++h) {
-                n_pix_h[h] = h < n_half ? (n_act * (h + 1)) / n_half - (n_act * h) / n_half : 0;
-                dh[h] = d;
-                const long off = first * Kr;
-                dh[h].candU += off * D; dh[h].candT += off * d.DT; dh[h].candL += off;
-                dh[h].candpix += off; dh[h].valid += off; dh[h].slot += off;
-                dh[h].count += h; dh[h].actlist += first;
-                dh[h].host_rows = (int *)(s->d_pub + 2 * h); dh[h].host_seq = s->d_pub + 2 * h + 1;
-                first += n_pix_h[h];
-            }
-        }
+        ns_part_views(s, n_half, Kr, n_pix_h, dh);
         for (int c = 0; c < s->check_every; ++c) {
             for (int h = 0; h < NS_PARTS; ++h) {
                 if (n_pix_h[h] == 0) continue;
-                hipStream_t st = r->lanes[h];
-                const long B = (long)n_pix_h[h] * Kr;
-                (void)B;
-                const dim3 pg((unsigned)((Kr + 127) / 128), (unsigned)std::min(n_pix_h[h], 65535), (unsigned)((n_pix_h[h] + 65534) / 65535));
-                switch (D) {                                        // compile-time dimensions where they are common
-                case 5: hipLaunchKernelGGL(ns_propose_kernel<5>, pg, dim3(NS_PROPOSE_THREADS), 0, st, dh[h], n_pix_h[h], Kr); break;
-                case 10: hipLaunchKernelGGL(ns_propose_kernel_v128<10>, pg, dim3(NS_PROPOSE_THREADS), 0, st, dh[h], n_pix_h[h], Kr); break;
-                case 15: hipLaunchKernelGGL(ns_propose_kernel<15>, pg, dim3(NS_PROPOSE_THREADS), 0, st, dh[h], n_pix_h[h], Kr); break;
-                default: hipLaunchKernelGGL(ns_propose_kernel<0>, pg, dim3(NS_PROPOSE_THREADS), 0, st, dh[h], n_pix_h[h], Kr); break;
-                }
-                hipLaunchKernelGGL(ns_publish_kernel, dim3(1), dim3(1), 0, st, dh[h], s->seq + 1);
+                ns_launch_propose(dh[h], n_pix_h[h], Kr, r->lanes[h]);
+                hipLaunchKernelGGL(ns_publish_kernel, dim3(1), dim3(1), 0, r->lanes[h], dh[h], s->seq + 1);
                 HIP_TRY(hipGetLastError());
             }
             s->seq += 1;
@@ -2087,17 +2077,8 @@ int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active_ou
             for (int h = 0; h < NS_PARTS; ++h) {
                 if (n_pix_h[h] == 0) continue;
                 hipStream_t st = r->lanes[h];
-                // proposals inside the prior: the only ones worth a likelihood.  Their number is the launch's last store
-                // into the mapped buffer, behind it the round's sequence number
-                volatile unsigned long long *pub = s->h_pub + 2 * h;
-                const auto t_start = std::chrono::steady_clock::now();
-                for (uint64_t spins = 0; __atomic_load_n(pub + 1, __ATOMIC_ACQUIRE) != s->seq; ++spins) {
-                    if ((spins & 0x3fff) == 0x3fff && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) {
-                        // nothing came back: a fault surfaces here, a very slow launch finishes
-                        HIP_TRY(hipStreamSynchronize(st));
-                    }
-                }
-                const int n_rows = (int)(unsigned)(pub[0] & 0xffffffffull);
+                int n_rows = 0;
+                { int rc = ns_wait_rows(s, h, st, &n_rows); if (rc) return rc; }
                 s->val_sum += n_rows;
                 dh[h].part = nullptr;
                 if (n_rows > 0) {
@@ -2108,12 +2089,8 @@ int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active_ou
                     dh[h].part = r->d_part[h];                             // (after the batch: its buffers may have grown)
                     dh[h].noise = r->ss->dev.noise; dh[h].nspec = r->ss->dev.n_spec;
                 }
-                hipLaunchKernelGGL(ns_update_kernel, dim3((unsigned)n_pix_h[h]), dim3(NS_UPD_THREADS), s->lds, st, dh[h], n_pix_h[h], Kr, s->rounds);
-                // the refit wave of the pixels the update marked, in the rounds where a pixel can be due: rejection-mode
-                // pixels every refit_every-th round, walking ones at a cycle's end -- and in a cycle's first round, where a
-                // pixel that has just turned to walks brings along what it collected before
-                if ((s->rounds + 1) % d.refit_every == 0 || (d.method != 0 && ((s->rounds + 1) % d.n_steps == 0 || s->rounds % d.n_steps == 0)))
-                    hipLaunchKernelGGL(ns_refit_kernel, dim3((unsigned)n_pix_h[h]), dim3(dh[h].multi ? 64 : NS_REFIT_THREADS), s->lds_refit, st, dh[h], n_pix_h[h], 0);
+                hipLaunchKernelGGL(ns_update_kernel, dim3((unsigned)n_pix_h[h]), dim3(NS_UPD_THREADS), s->plan.lds_update, st, dh[h], n_pix_h[h], Kr, s->rounds);
+                if (ns_refit_can_be_due(d, s->rounds)) ns_launch_refit(s, dh[h], n_pix_h[h], 0, st);   // the refit wave of the pixels the update marked
                 HIP_TRY(hipGetLastError());
             }
             s->rounds += 1;
@@ -2122,7 +2099,7 @@ int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active_ou
         HIP_TRY(hipMemcpy(s->h_active.data(), d.active, sizeof(int) * P, hipMemcpyDeviceToHost));
         s->n_act = 0;
         for (int p = 0; p < P; ++p) if (s->h_active[p]) s->h_act[s->n_act++] = p;
-        if (s->n_act) HIP_TRY(hipMemcpy(s->d_actlist, s->h_act.data(), sizeof(int) * s->n_act, hipMemcpyHostToDevice));
+        if (s->n_act) HIP_TRY(hipMemcpy(ns_mut(d.actlist), s->h_act.data(), sizeof(int) * s->n_act, hipMemcpyHostToDevice));
     }
     for (int h = 0; h < n_half; ++h) HIP_TRY(hipStreamSynchronize(r->lanes[h]));
     if (n_active_out) *n_active_out = s->n_act;
@@ -2168,14 +2145,10 @@ int nfa_sampler_dead_packed(nfa_sampler *s, const int64_t *offsets, double *thet
         if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > d.cap) return fail(NFA_ERR_ARG, "bad offsets");
     const int64_t total = offsets[P];
     if (total == 0) return NFA_OK;
-    long *d_off = nullptr;
-    double *d_T = nullptr, *d_L = nullptr, *d_W = nullptr;
-    auto release = [&]() { (void)hipFree(d_off); (void)hipFree(d_T); (void)hipFree(d_L); (void)hipFree(d_W); };
-    if (hipMalloc((void **)&d_off, sizeof(long) * (P + 1)) != hipSuccess || hipMalloc((void **)&d_T, sizeof(double) * total * d.DT) != hipSuccess
-        || hipMalloc((void **)&d_L, sizeof(double) * total) != hipSuccess || hipMalloc((void **)&d_W, sizeof(double) * total) != hipSuccess) {
-        release();
-        return fail(NFA_ERR_DEVICE, "out of device memory for the packed dead points");
-    }
+    NsTemp tmp;
+    long *d_off = tmp.get<long>((size_t)P + 1);
+    double *d_T = tmp.get<double>((size_t)total * d.DT), *d_L = tmp.get<double>((size_t)total), *d_W = tmp.get<double>((size_t)total);
+    if (!tmp.ok) return fail(NFA_ERR_DEVICE, "out of device memory for the packed dead points");
     static_assert(sizeof(long) == sizeof(int64_t), "LP64");
     hipStream_t st = s->r->lanes[0];
     bool ok = hipMemcpyAsync(d_off, offsets, sizeof(long) * (P + 1), hipMemcpyHostToDevice, st) == hipSuccess;
@@ -2185,7 +2158,6 @@ int nfa_sampler_dead_packed(nfa_sampler *s, const int64_t *offsets, double *thet
     ok = ok && hipMemcpyAsync(lnL, d_L, sizeof(double) * total, hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = ok && hipMemcpyAsync(lnw, d_W, sizeof(double) * total, hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
-    release();
     return ok ? NFA_OK : fail(NFA_ERR_DEVICE, "copying the dead points failed");
 }
 
@@ -2201,16 +2173,12 @@ int nfa_sampler_posterior_packed(nfa_sampler *s, const int64_t *offsets, const d
         if (offsets[p + 1] - offsets[p] < nl || offsets[p + 1] - offsets[p] - nl > d.cap) return fail(NFA_ERR_ARG, "bad offsets");
     }
     const int64_t total = offsets[P];
-    long *d_off = nullptr;
-    double *d_lo = nullptr, *d_out = nullptr, *d_st = nullptr;
     const size_t n_st = (size_t)P * (6 + 4 * d.DT);
-    auto release = [&]() { (void)hipFree(d_off); (void)hipFree(d_lo); (void)hipFree(d_out); (void)hipFree(d_st); };
-    if (hipMalloc((void **)&d_off, sizeof(long) * (P + 1)) != hipSuccess || hipMalloc((void **)&d_lo, sizeof(double) * P) != hipSuccess
-        || hipMalloc((void **)&d_out, sizeof(double) * total * (d.DT + 2)) != hipSuccess
-        || (stats && hipMalloc((void **)&d_st, sizeof(double) * n_st) != hipSuccess)) {
-        release();
-        return fail(NFA_ERR_DEVICE, "out of device memory for the packed posterior tables");
-    }
+    NsTemp tmp;
+    long *d_off = tmp.get<long>((size_t)P + 1);
+    double *d_lo = tmp.get<double>((size_t)P), *d_out = tmp.get<double>((size_t)total * (d.DT + 2));
+    double *d_st = stats ? tmp.get<double>(n_st) : nullptr;
+    if (!tmp.ok) return fail(NFA_ERR_DEVICE, "out of device memory for the packed posterior tables");
     static_assert(sizeof(long) == sizeof(int64_t), "LP64");
     hipStream_t st = s->r->lanes[0];
     bool ok = hipMemcpyAsync(d_off, offsets, sizeof(long) * (P + 1), hipMemcpyHostToDevice, st) == hipSuccess;
@@ -2224,7 +2192,6 @@ int nfa_sampler_posterior_packed(nfa_sampler *s, const int64_t *offsets, const d
     }
     ok = ok && hipMemcpyAsync(out, d_out, sizeof(double) * total * (d.DT + 2), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
-    release();
     return ok ? NFA_OK : fail(NFA_ERR_DEVICE, "copying the posterior tables failed");
 }
 

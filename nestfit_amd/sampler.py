@@ -25,6 +25,7 @@ over), so evidences agree with a MultiNest run only within their sampling error.
 bit-for-bit is the likelihood it is fed (tests drive the same sampler with the CPU oracle).
 """
 import math
+import types
 
 import numpy as np
 
@@ -120,7 +121,6 @@ def _walkers_for(n):
     """Walkers of a pixel with n live points (ns_walkers_for): 64, 128 from 384 live points, 256 from 768."""
     return 256 if n >= 768 else 128 if n >= 384 else 64
 _WALK_TARGET = 0.5              # acceptance the walk scale is tuned to (NS_WALK_TARGET on the device)
-_WALK_LOWD, _WALK_FACTOR_LOWD, _WALK_FACTOR = 6, 64, 2      # NS_WALK_LOWD, NS_WALK_FACTOR_LOWD, NS_WALK_FACTOR
 
 
 def _ball_points(seed, p, a, D):
@@ -193,7 +193,7 @@ def _fit_ellipsoids(U, efr, ln_x, enlarge=1.0):
 
 
 # ---- several ellipsoids per pixel (ns_refit_multi / the rejection branch of ns_propose_kernel) ----------
-_NS_ME, _NS_ME_MAXD, _NS_ME_GAIN = 4, 6, 0.7        # NS_ME, NS_ME_MAXD, NS_ME_GAIN
+_NS_ME_GAIN = 0.7               # NS_ME_GAIN
 _B_ELL, _B_KEEP = _U64(253), _U64(254)
 
 
@@ -288,8 +288,7 @@ def _candidates_multi(seed, p, base, K, cs, As, lv, ne, lnvol):
 # spacing of the extreme order statistics would give (scripts/proto_intersection.py: the fraction of the true region a
 # bound cuts off, and the evaluations per iteration it saves).
 _FRAME_SEED = _U64(0x5EEDF00D)
-_NS_FRAMES, _NS_MARGIN_C, _NS_MARGIN_A, _NS_MARGIN_FLOOR = 32, 2.5, 1.5, 0.1      # NS_FRAMES, NS_MARGIN_C (round 4: 1.75 = precision='speed'), NS_MARGIN_A, NS_MARGIN_FLOOR
-_NS_RATIO_MAX = 32                                                             # NS_RATIO_MAX
+_NS_MARGIN_A, _NS_MARGIN_FLOOR = 1.5, 0.1      # NS_MARGIN_A, NS_MARGIN_FLOOR
 
 
 def _frames(D, K):
@@ -344,11 +343,8 @@ def _box_veto(cand, zz, ubox, fbox, frames):
 
 
 # ---- a volume-preserving shear in front of the one-ellipsoid bound (ns_shear_fit / ns_shear_inv on the device) --------
-_NS_KP_START = 256                                                              # NS_KP_START
-_NS_K_TARGET = 16                                                               # NS_K_TARGET
 _NS_SHEAR_RIDGE = 1e-6                                                          # NS_SHEAR_RIDGE
 _NS_SHEAR_PIVOT = 1e-9                                                          # NS_SHEAR_PIVOT
-_NS_SHEAR_ENLARGE = 3.0                                                         # NS_SHEAR_ENLARGE (round 4: 2.5 = precision='speed')
 
 
 def _shear_monomials(comp):
@@ -434,9 +430,6 @@ def _shear_inv(W, mu, sg, beta, mono, start):
             pj = int(start[j])
             Z[:, j] = W[:, j] + _shear_phi(Z, mono, pj) @ beta[j, :pj]
         return mu + sg * Z
-
-
-_NS_PAIRS_ENLARGE = 2.0                                                         # NS_PAIRS_ENLARGE (round 4: 1.75 = precision='speed')
 
 
 def _fit_pairs(W, enlarge):
@@ -594,6 +587,52 @@ def resolve_precision(precision, margin=None, pairs=None, method='auto', shear=N
             knobs.get('method', method) if method == 'auto' else method, knobs.get('shear') if shear is None else shear)
 
 
+# ---- the run's form, decided once: ns_plan of csrc/nfa_sampler_plan.h, the same chain under the same field names.  The
+# constants are the header's NS_* of the same names (tests/test_sampler_plan.py compares the two plans field by field)
+_NS_ME, _NS_ME_MAXD, _NS_STAGE_BYTES = 4, 6, 96 * 1024
+_NS_FRAMES, _NS_MARGIN_C = 32, 2.5                                  # (margin, round 4: 1.75 = precision='speed')
+_NS_SHEAR_ENLARGE, _NS_SHEAR_MMAX, _NS_PAIRS_ENLARGE = 3.0, 64, 2.0     # (round 4: 2.5 and 1.75 = precision='speed')
+_NS_RATIO_MAX, _NS_KMAX, _NS_KP_START, _NS_K_TARGET, _NS_REFIT_EVERY = 32, 65536, 256, 16, 4
+_NS_WALK_LOWD, _NS_WALK_FACTOR_LOWD, _NS_WALK_FACTOR = 6, 64, 2
+
+
+def _plan(nd, ndim, nlive, fmap, ellipsoids=None, frames=None, walkers=None, walk_factor=None, k_target=None,
+          refit_every=None, ratio_max=None, kmax=None, margin=None, shear=None, pairs=None):
+    """What bound a run gets: `nd` sampled dimensions of `ndim` slots (fmap[nd] = their slots), `nlive` = the largest
+    number of live points of a pixel, every knob None (unset) or a value.  In dependency order, like ns_plan."""
+    def pick(v, default):
+        return default if v is None else v
+    p = types.SimpleNamespace(error=None)
+    p.ratio_max, p.kmax = int(pick(ratio_max, _NS_RATIO_MAX)), int(pick(kmax, _NS_KMAX))
+    p.w_fixed = int(pick(walkers, 0))                           # (A/B knob; 0: by the live points)
+    p.w_stride = p.w_fixed if p.w_fixed > 0 else _walkers_for(nlive)
+    # to walks below an acceptance of 1 in walk_factor * n_steps: 2 from seven sampled dimensions on, 64 below -- there a
+    # rejection round, one large batch, beats a walk cycle of n_steps small ones down to very low acceptances
+    p.walk_factor = int(pick(walk_factor, _NS_WALK_FACTOR_LOWD if nd <= _NS_WALK_LOWD else _NS_WALK_FACTOR))
+    p.k_target, p.refit_every = int(pick(k_target, _NS_K_TARGET)), int(pick(refit_every, _NS_REFIT_EVERY))
+    p.stage_live = int(nlive * nd * 8 <= _NS_STAGE_BYTES)       # the device's refit holds the live points in LDS
+    p.max_ell = int(pick(ellipsoids, _NS_ME))
+    p.multi = int(bool(p.stage_live) and nd <= _NS_ME_MAXD and p.max_ell > 1)
+    # the shear: all five free parameters of two or three components, slot % ncomp = dimension % ncomp
+    p.shear_enlarge = float(pick(shear, _NS_SHEAR_ENLARGE))
+    nc = nd // 5
+    shape = nd in (10, 15) and ndim == 6 * nc and bool(np.all(np.asarray(fmap) % nc == np.arange(nd) % nc))
+    p.shear = int(p.shear_enlarge >= 1.0 and shape and not p.multi and bool(p.stage_live))
+    p.sh_M = int(_shear_monomials(np.arange(nd) % nc)[0].shape[0]) if p.shear else 0
+    if p.sh_M > _NS_SHEAR_MMAX:
+        p.error = 'shear: too many monomials'
+        return p
+    # boxes: one-ellipsoid bounds with staged live points; by default _NS_FRAMES frames where the bound is sheared, none elsewhere
+    nf = int(pick(frames, _NS_FRAMES if p.shear else -1))
+    p.boxes = int(not p.multi and bool(p.stage_live) and nf >= 0)
+    p.n_frames = nf if p.boxes else 0
+    p.margin_c = float(pick(margin, _NS_MARGIN_C))
+    # the pair ellipses: with the shear and the boxes (the device fits them in the shear's scratch, four doubles a pair)
+    p.pairs_enlarge = float(pick(pairs, _NS_PAIRS_ENLARGE))
+    p.pairs = int(bool(p.shear) and bool(p.boxes) and p.pairs_enlarge >= 1.0 and (nd * (nd - 1) // 2) * 4 <= p.sh_M * p.sh_M)
+    return p
+
+
 def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxiter=int(1e6),
                n_cand=None, upd_frac=0.1, log_zero=LOG_ZERO, chunk=1 << 18, cap_iter=None,
                check_every=32, batch_target=262144, enlarge=1.5, method='auto', n_steps=None, free_mask=None, walk_factor=None, ellipsoids=None, walkers=None,
@@ -692,32 +731,26 @@ def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxit
     since_fit = np.zeros(P, dtype=np.int64)
     updp = np.maximum(1, (upd_frac * nl).astype(np.int64))
     # the bound: several ellipsoids per pixel where few dimensions are sampled (and the live points fit in the device's
-    # LDS), one otherwise; [pixel][ellipsoid]
-    max_ell = _NS_ME if not ellipsoids else int(ellipsoids)      # `ellipsoids`: None / 0 = the default, 1 = one, up to 4
-    multi = nd <= _NS_ME_MAXD and nlive * nd * 8 <= 96 * 1024 and max_ell > 1
+    # LDS), one otherwise -- with a shear, boxes and pair ellipses where the shape allows (`_plan`; `ellipsoids`, `walkers`,
+    # `walk_factor`, `ratio_max`, `kmax`: None / 0 = the default); [pixel][ellipsoid]
+    pl = _plan(nd, ndim, nlive, fmap, ellipsoids=ellipsoids or None, frames=frames, walkers=walkers or None,
+               walk_factor=walk_factor or None, k_target=k_target, refit_every=refit_every, ratio_max=ratio_max or None,
+               kmax=kmax or None, margin=margin, shear=shear, pairs=pairs)
+    assert pl.error is None and (pl.shear_enlarge == 0.0 or pl.shear_enlarge >= 1.0)
+    max_ell, multi, shear_on, boxes, pairs_on = pl.max_ell, bool(pl.multi), bool(pl.shear), bool(pl.boxes), bool(pl.pairs)
+    n_frames, margin_c, pairs_enl = pl.n_frames, pl.margin_c, pl.pairs_enlarge
+    walk_factor, w_stride, k_target, refit_every = pl.walk_factor, pl.w_stride, pl.k_target, pl.refit_every
     centre, axes = np.zeros((P, _NS_ME, nd)), np.zeros((P, _NS_ME, nd, nd))
     elnv, nell = np.full((P, _NS_ME), -np.inf), np.ones(P, dtype=np.int64)
     use_cube, lnvol = np.empty(P, dtype=bool), np.empty(P)
-    # free rejections (one-ellipsoid bounds only): boxes in the unit cube's axes, the ellipsoid's frame and n_frames rotations
-    # (the device's shapes for the shear: all five free parameters of two or three components, slot % ncomp = dimension % ncomp;
-    # there it is on by default, with NS_FRAMES box frames, like the device's -- shear=0 / frames=-1 turn them off)
-    ncomp_s = max(1, nd // 5)
-    shear = _NS_SHEAR_ENLARGE if shear is None else shear
-    shear_on = (bool(shear) and (not multi) and nd in (10, 15) and ndim == 6 * ncomp_s and nlive * nd * 8 <= 96 * 1024
-                and bool(np.all(fmap % ncomp_s == np.arange(nd) % ncomp_s)))
-    n_frames = (_NS_FRAMES if shear_on else -1) if frames is None else int(frames)
-    boxes = (not multi) and n_frames >= 0 and nlive * nd * 8 <= 96 * 1024
-    margin_c = _NS_MARGIN_C if margin is None else float(margin)
-    Qf = _frames(nd, max(n_frames, 0)) if boxes else None
+    # free rejections (one-ellipsoid bounds only): boxes in the unit cube's axes, the ellipsoid's frame and n_frames
+    # rotations; the pair ellipses (`_fit_pairs`) with the shear and the boxes
+    Qf = _frames(nd, n_frames) if boxes else None
     ubox = np.zeros((P, nd, 2))
-    fbox = np.zeros((P, max(n_frames, 0) + 1, nd, 2))
-    # the pair ellipses (`_fit_pairs`): with the shear and the boxes, unless pairs=0; `pairs` = the safety factor on their areas
-    pairs_enl = _NS_PAIRS_ENLARGE if pairs is None else float(pairs)
-    pairs_on = shear_on and boxes and pairs_enl >= 1.0
+    fbox = np.zeros((P, n_frames + 1, nd, 2))
     pair_tab = np.zeros((P, nd * (nd - 1) // 2, 5)) if pairs_on else None
     if shear_on:
-        assert float(shear) >= 1.0
-        mono, mstart = _shear_monomials(fmap % ncomp_s)
+        mono, mstart = _shear_monomials(fmap % (nd // 5))
         sh_mu, sh_sg, sh_beta = np.zeros((P, nd)), np.ones((P, nd)), np.zeros((P, nd, mono.shape[0]))
 
     def refit(p, ln_x):
@@ -728,7 +761,7 @@ def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxit
             sh_mu[p], sh_sg[p], sh_beta[p] = _fit_shear(Ulive[p, :n], mono, mstart)
             Wl = _shear_fwd(Ulive[p, :n], sh_mu[p], sh_sg[p], sh_beta[p], mono, mstart)
             ln_jac = float(np.log(sh_sg[p]).sum())                  # ln |du / dw|: volumes in w units are smaller by this
-            c1, a1, _, v1 = _fit_ellipsoids(Wl[None], efr, np.array([ln_x - ln_jac]), float(shear))
+            c1, a1, _, v1 = _fit_ellipsoids(Wl[None], efr, np.array([ln_x - ln_jac]), pl.shear_enlarge)
             centre[p, 0], axes[p, 0], lnvol[p], nell[p] = c1[0], a1[0], v1[0] + ln_jac, 1
             use_cube[p], elnv[p, 0] = lnvol[p] >= 0.0, lnvol[p]
             if boxes:
@@ -750,11 +783,8 @@ def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxit
     Kr = K
     method = {'reject': 0, 'auto': 1, 'walk': 2}[method] if isinstance(method, str) else int(method)
     n_steps = int(n_steps) if n_steps else 10 * nd
-    # a pixel turns to walks when a rejection round accepts fewer than 1 in walk_factor * n_steps candidates (and back
-    # above eight times that): 2 from seven sampled dimensions on, 64 below -- there a rejection round, one large batch,
-    # beats a walk cycle of n_steps small ones down to very low acceptances (csrc/nfa_sampler.h: NS_WALK_FACTOR*,
-    # profiles/r03/sweep_walk_factor.txt).  The device takes the same default (engine option `sampler_walk_factor`).
-    walk_factor = int(walk_factor) if walk_factor else (_WALK_FACTOR_LOWD if nd <= _WALK_LOWD else _WALK_FACTOR)
+    # (a pixel turns to walks when a rejection round accepts fewer than 1 in walk_factor * n_steps candidates, and back
+    # above eight times that: profiles/r03/sweep_walk_factor.txt; the device's engine option `sampler_walk_factor`)
     # constrained random walks (ns_update_kernel's walk branch): state per pixel and per walker
     walk = np.zeros(P, dtype=bool)
     wstep = np.zeros(P, dtype=np.int64)
@@ -763,7 +793,6 @@ def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxit
     wLthr = np.zeros(P)
     wacc_sum = np.zeros(P, dtype=np.int64)
     wtot_sum = np.zeros(P, dtype=np.int64)
-    w_stride = int(walkers) if walkers else _walkers_for(nlive)     # walker slots per pixel (`walkers`: A/B knob, else by the live points)
     wU = np.zeros((P, w_stride, nd))
     wT = np.zeros((P, w_stride, ndim))
     wL = np.zeros((P, w_stride))
@@ -773,7 +802,6 @@ def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxit
     # ellipsoid: what the way back from the walks counts the bound's volume with)
     # a pixel's own share of a rejection round's proposals (ns_kp / NS_K_TARGET): halved after a round with more than twice
     # k_target replacements, doubled after one with fewer than half of it; 0 = the round's Kr
-    k_target = _NS_K_TARGET if k_target is None else int(k_target)
     Kp = np.full(P, _NS_KP_START, dtype=np.int64)                # (a small share first, doubled while little is accepted)
     rj_scan, rj_acc = np.zeros(P, dtype=np.int64), np.zeros(P, dtype=np.int64)
     rj_raw, rj_val = np.zeros(P, dtype=np.int64), np.zeros(P, dtype=np.int64)
@@ -800,9 +828,9 @@ def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxit
     while active.any():
         if rnd % check_every == 0:                              # the device compacts its pixel list here
             # with boxes most proposals are vetoed for free: draw so many more that a round still evaluates ~b_target
-            ratio = min(int(ratio_max) if ratio_max else _NS_RATIO_MAX, max(1, (raw_sum + val_sum // 2) // max(val_sum, 1))) if boxes and raw_sum else 1
+            ratio = min(pl.ratio_max, max(1, (raw_sum + val_sum // 2) // max(val_sum, 1))) if boxes and raw_sum else 1
             n_chunk = int(active.sum())                          # the pixels the device's list holds until the next look
-            Kr = int(min(kmax if kmax else 65536, max(K, (b_target * ratio) // n_chunk)))
+            Kr = int(min(pl.kmax, max(K, (b_target * ratio) // n_chunk)))
             raw_sum = val_sum = 0
         raw_sum += Kr * n_chunk
         idx = np.flatnonzero(active)
@@ -815,7 +843,7 @@ def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxit
             if walk[p]:
                 # one Metropolis step of every walker inside {L > threshold frozen at the cycle start}
                 step = int(wstep[p])
-                W = min(w_stride, int(walkers) if walkers else _walkers_for(nlive), Kr) if step == 0 else int(wW[p])
+                W = min(w_stride, pl.w_fixed or _walkers_for(nlive), Kr) if step == 0 else int(wW[p])
                 a = _U64(cand_base[p]) + np.arange(W, dtype=_U64)
                 if step == 0:
                     start = np.minimum(nlive - 1, (_uniform(seed, p, a, _B_START) * nlive).astype(np.int64))
