@@ -149,6 +149,7 @@ int nfa_specset_create(nfa_specset **out, int n_spec, const int64_t *sizes,
 #define NFA_MODEL_AMMONIA      0
 #define NFA_MODEL_DIAZENYLIUM  1
 #define NFA_MODEL_GAUSSIAN     2
+#define NFA_MODEL_HYPERFINE    3   /* nfa_specset_create_lines below; this function returns NFA_ERR_ARG for it */
 int nfa_specset_create_model(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
                              const int32_t *trans_ids, const double *rest_freqs,
                              const double *const *xarr, int64_t n_pix, const double *data,
@@ -168,6 +169,25 @@ int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, c
                                      const int32_t *trans_ids, const double *rest_freqs,
                                      const double *const *xarr, int64_t n_pix, const double *data,
                                      const double *chan_noise);
+/* model 3 = any species whose spectrum is a set of hyperfine lines sharing one excitation temperature: c_hf_predict
+ * (nestfit/models/hyperfine.pyx:52-118) on a line table of the caller's, with the parameters of N2H+ per component
+ * (voff, tex, ltau, sigm; parameter-major).  Spectrum s has n_lines[s] lines (1..50) at the rest frequency
+ * rest_freqs[s] (Hz); voff (km/s) and tau_wts hold the tables of the spectra one after the other, sum(n_lines) values
+ * each.  The optical depth of line i of a component is 10^ltau * tau_wts[i]: the weights are used as given, not
+ * normalised, and ltau is shared by the spectra of a pixel (like c_nnhp_predict), so relative optical depths between
+ * transitions are folded into the weights.  The order of a table's lines does not matter.
+ * Exactly one of noise[n_pix][n_spec] and chan_noise[n_pix][sum(sizes)] is non-NULL (the latter as for
+ * nfa_specset_create_channel_noise).  Returns NFA_ERR_ARG, with a message, for a line count outside 1..50, a rest
+ * frequency that is not finite and positive, an offset that is not finite or not below the speed of light, a weight
+ * that is not finite or is negative, and a table whose weights are all zero; every check of the other creators
+ * applies as well. */
+int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
+                             const double *rest_freqs, const double *voff, const double *tau_wts,
+                             const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                             const double *chan_noise);
+/* A shipped line table, as a template for nfa_specset_create_lines: model 0 (trans_id 1..9) or 1 (trans_id 1..3);
+ * voff and tau_wts take 50 doubles each (zero behind the *n lines), *nu the rest frequency in Hz.  Needs no device. */
+int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n);
 int nfa_specset_destroy(nfa_specset *ss);
 int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data);
 /* null_lnZ[n_pix][n_spec] = -sum(data^2)/(2 noise^2)   (core.pyx:517-520); with a baseline, the baseline-only model:

@@ -10,10 +10,19 @@ from .core import (ConstantPrior, CenSepPrior, Distribution, DuplicatePrior, Ord
 from .ammonia import AmmoniaRunner, AmmoniaSpectrum, amm_predict
 from .diazenylium import DiazenyliumRunner, DiazenyliumSpectrum, nnhp_predict
 from .gaussian import GaussianRunner, gauss_predict
-from . import ammonia, diazenylium, gaussian
+from . import ammonia, diazenylium, gaussian, hyperfine
+from .hyperfine import HyperfineRunner, LineTable
 
 # registry like nestfit/models/__init__.py:3-7
 MODELS = {m.NAME: m for m in (ammonia, diazenylium, gaussian)}
+
+
+def model_module(name):
+    """The model module of a store's `model_name`: one of MODELS (the reference's three), or `hyperfine`, the model
+    of caller-supplied line tables; None for an unknown name."""
+    return hyperfine if name == hyperfine.NAME else MODELS.get(name)
+
+
 from .prior_constructors import get_irdc_priors, get_synth_priors
 
 __all__ = [
@@ -22,5 +31,5 @@ __all__ = [
     'CenSepPrior', 'ResolvedCenSepPrior', 'ResolvedPlacementPrior', 'PriorTransformer',
     'AmmoniaSpectrum', 'AmmoniaRunner', 'amm_predict', 'get_irdc_priors', 'get_synth_priors',
     'DiazenyliumSpectrum', 'DiazenyliumRunner', 'nnhp_predict', 'GaussianRunner', 'gauss_predict',
-    'MODELS',
+    'MODELS', 'hyperfine', 'LineTable', 'HyperfineRunner', 'model_module',
 ]

@@ -8,7 +8,8 @@ import numpy as np
 from . import _ffi
 from .core import Runner, _as_inplace_matrix, _as_inplace_vector
 
-MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_GAUSSIAN = 0, 1, 2
+MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_GAUSSIAN, MODEL_HYPERFINE = 0, 1, 2, 3
+N_MODEL = {MODEL_AMMONIA: 6, MODEL_DIAZENYLIUM: 4, MODEL_GAUSSIAN: 3, MODEL_HYPERFINE: 4}      # parameters per component
 BASELINE_MAX = 3          # NFA_BASELINE_MAX
 
 
@@ -57,9 +58,20 @@ def channel_weights(noise, size):
 class _SpecSet:
     """Owner of a device-resident set of spectra (one pixel or a cube)."""
 
-    def __init__(self, xarrs, trans_ids, data, noise, model=MODEL_AMMONIA, rest_freqs=None):
+    def __init__(self, xarrs, trans_ids, data, noise, model=MODEL_AMMONIA, rest_freqs=None, lines=None):
         """xarrs: list of 1-D axes; data [n_pix, sum(sizes)]; noise [n_pix, n_spec], or [n_pix, sum(sizes)]
-        for a noise per channel (nfa_specset_create_channel_noise: inf masks a channel)."""
+        for a noise per channel (nfa_specset_create_channel_noise: inf masks a channel).  lines: the hyperfine
+        model's `LineTable` of every spectrum (nfa_specset_create_lines; `trans_ids` and `rest_freqs` are then unused)."""
+        self.model = int(model)
+        if (self.model == MODEL_HYPERFINE) != (lines is not None):
+            raise ValueError('the hyperfine model (3), and no other, takes `lines`: one LineTable per spectrum')
+        if lines is not None:
+            from .hyperfine import LineTable
+            lines = list(lines)
+            if len(lines) != len(xarrs) or not all(isinstance(t, LineTable) for t in lines):
+                raise ValueError('`lines` must hold one LineTable per spectrum')
+            trans_ids = [-1] * len(lines)
+        self.lines = lines
         lib = _ffi.engine()
         self.n_spec = len(xarrs)
         self.sizes = np.array([x.size for x in xarrs], dtype=np.int64)
@@ -78,15 +90,24 @@ class _SpecSet:
                        else np.full(self.n_pix, self.chan_tot)).astype(np.int64)
         xp = (_ffi._dp * self.n_spec)(*[_ffi.dptr(x) for x in self.xarrs])
         h = C.c_void_p()
-        self.model = int(model)
         self.rest_freqs = (None if rest_freqs is None
                            else np.ascontiguousarray(rest_freqs, dtype=np.float64))
-        create = lib.nfa_specset_create_channel_noise if self.per_channel else lib.nfa_specset_create_model
-        _ffi.check(create(
-            C.byref(h), self.model, self.n_spec, self.sizes.ctypes.data_as(_ffi._lp),
-            self.trans_ids.ctypes.data_as(_ffi._ip),
-            None if self.rest_freqs is None else _ffi.dptr(self.rest_freqs), xp, self.n_pix,
-            _ffi.dptr(data), _ffi.dptr(noise)))
+        sizes_p = self.sizes.ctypes.data_as(_ffi._lp)
+        if lines is not None:                       # the caller's tables: exactly one of the two noise arguments
+            n_lines = np.array([t.n for t in lines], dtype=np.int32)
+            self.rest_freqs = np.array([t.nu for t in lines], dtype=np.float64)
+            voff = np.ascontiguousarray(np.concatenate([t.voff for t in lines]), dtype=np.float64)
+            tau_wts = np.ascontiguousarray(np.concatenate([t.tau_wts for t in lines]), dtype=np.float64)
+            rc = lib.nfa_specset_create_lines(
+                C.byref(h), self.n_spec, sizes_p, n_lines.ctypes.data_as(_ffi._ip), _ffi.dptr(self.rest_freqs),
+                _ffi.dptr(voff), _ffi.dptr(tau_wts), xp, self.n_pix, _ffi.dptr(data),
+                None if self.per_channel else _ffi.dptr(noise), _ffi.dptr(noise) if self.per_channel else None)
+        else:
+            create = lib.nfa_specset_create_channel_noise if self.per_channel else lib.nfa_specset_create_model
+            rc = create(C.byref(h), self.model, self.n_spec, sizes_p, self.trans_ids.ctypes.data_as(_ffi._ip),
+                        None if self.rest_freqs is None else _ffi.dptr(self.rest_freqs), xp, self.n_pix,
+                        _ffi.dptr(data), _ffi.dptr(noise))
+        _ffi.check(rc)
         self.handle = h
         self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
         self.baseline_order = None
@@ -160,10 +181,11 @@ class EngineSpectrumMixin:
     one pixel, runner handles cached per (ncomp, cold, lte)."""
     MODEL = MODEL_AMMONIA
 
-    def _attach(self, trans_id, rest_freq=None):
+    def _attach(self, trans_id, rest_freq=None, lines=None):
         self._ss = _SpecSet([self.xarr], [trans_id], self.data.reshape(1, -1),
                             np.reshape(self.noise, (1, -1)), model=self.MODEL,
-                            rest_freqs=None if rest_freq is None else [rest_freq])
+                            rest_freqs=None if rest_freq is None else [rest_freq],
+                            lines=None if lines is None else [lines])
         self.null_lnZ = float(self._ss.null_lnZ()[0, 0])
         self._runners = {}
 
@@ -233,7 +255,8 @@ class EngineRunner(Runner):
         else:
             noise = np.array([[s.noise for s in spectra]])
         self._ss = _SpecSet([s.xarr for s in spectra], [s.trans_id for s in spectra], data, noise,
-                            model=self.MODEL, rest_freqs=rest_freqs)
+                            model=self.MODEL, rest_freqs=rest_freqs,
+                            lines=[s.lines for s in spectra] if self.MODEL == MODEL_HYPERFINE else None)
         self._run = _RunnerHandle(self._ss, utrans, self.ncomp, cold, lte)
         self.baseline_order = baseline_order
         if baseline_order is not None:

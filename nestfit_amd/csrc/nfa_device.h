@@ -56,21 +56,29 @@
 #define SM_END_TABLE  (SM_FEA + 1280)   // 8432 doubles
 #define SM_TABLE_TAIL 768               // doubles that must follow the staged tables in LDS (row 15 of A ends there)
 
-// Transition tables of every model in one index space: 0..8 NH3 (1,1)..(9,9), 9..11 N2H+
-// 1-0, 2-1, 3-2, 12 the Gaussian model's single "line" (offset 0, weight 1, rest frequency
-// from the spectrum).  SpecDev.trans holds index + 1.
+// Transition indices of every model in one index space: 0..8 NH3 (1,1)..(9,9), 9..11 N2H+ 1-0, 2-1, 3-2, 12 the
+// Gaussian model's single "line" (offset 0, weight 1, rest frequency from the spectrum), 13 a spectrum of the
+// hyperfine model, whose lines the caller supplies (nfa_specset_create_lines).  SpecDev.trans holds index + 1.
+// The index selects what belongs to a transition beyond its lines (c_nu and c_ea: ammonia only; the Gaussian
+// model's line centre, nf_line); the lines themselves are per spectrum, in device memory (SpecDev.lines).
 #define NFA_T_N2HP   NFA_N_LEVELS
 #define NFA_T_GAUSS  (NFA_N_LEVELS + NFA_N2HP_LEVELS)
-#define NFA_T_ALL    (NFA_T_GAUSS + 1)
-__constant__ int    c_nhf[NFA_T_ALL];
+#define NFA_T_LINES  (NFA_T_GAUSS + 1)
+#define NFA_T_ALL    (NFA_T_LINES + 1)
 __constant__ double c_nu[NFA_T_ALL];
 __constant__ double c_ea[NFA_N_LEVELS];
-__constant__ double c_voff[NFA_T_ALL][NFA_MAX_HF_N];
-__constant__ double c_hfreq[NFA_T_ALL][NFA_MAX_HF_N];       // (1 - voff / CKMS) * nu of every line
-__constant__ double c_tauw[NFA_T_ALL][NFA_MAX_HF_N];
-// position of line i of transition t when the lines are ordered by their velocity offset (stable): in that order
-// the lines whose windows touch a row of channels form ONE run of neighbours (fast mode's line table, lnl_body)
-__constant__ unsigned char c_rank[NFA_T_ALL][NFA_MAX_HF_N];
+
+// The lines of one spectrum as the kernels read them (nfa_engine.hip: line_row_fill; the shipped tables for ammonia,
+// N2H+ and the Gaussian model, the caller's for the hyperfine model): hf_freq = (1 - voff / CKMS) * nu of every line
+// (hyperfine.pyx:71), its weight, the number of lines, and the position of every line when the lines are ordered by
+// their velocity offset (stable): in that order the lines whose windows touch a row of channels form ONE run of
+// neighbours (fast mode's line table, lnl_body).
+struct LineRow {
+    double        hfreq[NFA_MAX_HF_N];
+    double        tauw[NFA_MAX_HF_N];
+    int           nhf;
+    unsigned char rank[NFA_MAX_HF_N];
+};
 
 struct SpecDev {
     int     n_spec, ncomp, cold, lte;
@@ -96,6 +104,7 @@ struct SpecDev {
     // always weighted (a scalar noise: chan_w == 1): [n_pix][n_spec][NFA_BL_REC] records of bl_setup_kernel (below).
     const double *bl;
     int     bl_order;
+    const LineRow *lines;                // [n_spec]: the lines of every spectrum, in device memory
 };
 
 // Baseline record of a (pixel, spectrum), DESIGN 4.5: [0, 4) m_k(d) = sum_j w_j P_k(u_j) d_j, the Legendre moments of the
@@ -400,16 +409,17 @@ __device__ __forceinline__ double nf_partition_level(int j, double trot, const d
     return (double)(2 * j + 1) * nf_fastexp<MODE>(nf_partition_arg(j, trot), sm);
 }
 
-// Line centre, width and channel window of hyperfine line i of transition t
+// Line centre, width and channel window of hyperfine line i of a spectrum of transition t whose row of
+// hf_freq is `hfreq` (LineRow.hfreq)
 // (reference: nestfit/models/hyperfine.pyx:70-91).  Plain double arithmetic,
 // no contraction: the floor() arguments must round like the reference's.
 struct LineConst { double nucen, idenom; int lo, hi; };
-__device__ __forceinline__ LineConst nf_line(int t, int i, double v_over_c, double s_over_c, double nu0,
+__device__ __forceinline__ LineConst nf_line(int t, const double *__restrict__ hfreq, int i, double v_over_c, double s_over_c, double nu0,
                                              double nu_min, double nu_chan, int N, double r_chan = 0.0) {
     LineConst r;
     // hf_freq = (1 - voff_i / CKMS) nu0 (hyperfine.pyx:71) is a constant of the line: the host forms it
-    // with the same two IEEE operations at start-up (c_hfreq); the Gaussian model's line has voff = 0
-    const double hf_freq   = t == NFA_T_GAUSS ? nu0 : c_hfreq[t][i];
+    // with the same two IEEE operations when the set is made (LineRow.hfreq); the Gaussian model's line has voff = 0
+    const double hf_freq   = t == NFA_T_GAUSS ? nu0 : hfreq[i];
     const double hf_width  = s_over_c * hf_freq;             // (sigm / CKMS) * hf_freq
     const double hf_offset = v_over_c * hf_freq;             // (voff / CKMS) * hf_freq
     // the Gaussian model forms its centre as rest_freq * (1 - voff / CKMS) (gaussian.pyx:33)
@@ -460,7 +470,7 @@ __device__ __forceinline__ const double *stage_exp_tables(double *smem, const do
 //  line records (hyperfine.pyx:68-91) of one (item, spectrum) unit, in the wave's LDS slice
 // ---------------------------------------------------------------------------
 // 32 bytes = two 16-byte broadcast reads.  The table of a component is kept in the order of the lines' velocity
-// offsets (c_rank), so that the lines whose windows touch a row of channels are ONE run of neighbours; the windows
+// offsets (LineRow.rank), so that the lines whose windows touch a row of channels are ONE run of neighbours; the windows
 // themselves, [lo, hi), lie behind the table as an array of their own (the row loop's hit masks).
 //   nucen   line centre (hyperfine.pyx:73)
 //   idenom  0.5 / width^2 (hyperfine.pyx:75)
@@ -866,7 +876,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     const long b = (long)bu;
     const int s = (int)(unit - bu * (unsigned)nspec);
     const int t = S.trans[s] - 1, N = S.size[s], off = S.off[s];
-    const int nhf = __builtin_amdgcn_readfirstlane(c_nhf[t]);
+    const LineRow *__restrict__ lrow = S.lines + s;
+    const int nhf = __builtin_amdgcn_readfirstlane(lrow->nhf);
     long p_ix = 0;
     double *so = WRITE_SPEC ? spec_out + b * S.chan_tot + off : nullptr;     // spectra out: the unit's model spectrum
     if (grp) {                                                    // batch kernels: the item's batch of the group has the pixels
@@ -887,7 +898,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
         double r_nucen = 0.0, r_idenom = 0.0, r_htau = 0.0;
         int r_lo = 0, r_len = 0, slot = p;
         if (i < nhf) {
-            const LineConst lc = nf_line(t, i, D[b * drec + c * 4 + 2], D[b * drec + c * 4 + 1], nu0, S.nu_min[s],
+            const LineConst lc = nf_line(t, lrow->hfreq, i, D[b * drec + c * 4 + 2], D[b * drec + c * 4 + 1], nu0, S.nu_min[s],
                                          S.nu_chan[s], N, S.r_chan[s]);
             int lo = lc.lo;
             const int hi = lc.hi;
@@ -904,10 +915,10 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
             if (!(fabs(lc.nucen) < INFINITY) || !(lc.idenom < INFINITY)) lo = hi;
             r_nucen = lc.nucen;
             r_idenom = lc.idenom;
-            r_htau = D[b * drec + 4 * ncomp + (c * nspec + s) * DREC_CS + DK_TMAIN] * c_tauw[t][i];
+            r_htau = D[b * drec + 4 * ncomp + (c * nspec + s) * DREC_CS + DK_TMAIN] * lrow->tauw[i];
             r_lo = lo;
             r_len = hi > lo ? hi - lo : 0;
-            slot = c * G.nhf_max + c_rank[t][i];                 // velocity order: the lines of a row are neighbours
+            slot = c * G.nhf_max + lrow->rank[i];                 // velocity order: the lines of a row are neighbours
         }
         LineRec rec;
         rec.nucen = r_nucen;

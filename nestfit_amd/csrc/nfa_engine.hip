@@ -103,6 +103,34 @@ static std::vector<nfa_runner *> g_runners;         // live runners: nfa_device_
 // library is loaded, and only if the user has not set it.
 __attribute__((constructor)) static void nfa_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
 
+// The line row of one spectrum as the kernels read it (LineRow, nfa_device.h), from a table of n lines: hf_freq of every
+// line with one rounding per operation (hyperfine.pyx:71) and the rank of every line when the lines are ordered by
+// velocity offset (stable).  The slots behind the last line hold hf_freq of a zero offset, weight 0 and their own index.
+static void line_row_fill(LineRow &row, int n, double nu, const double *voff, const double *tauw) {
+    row.nhf = n;
+    for (int i = 0; i < NFA_MAX_HF_N; ++i) {
+        volatile double q = (i < n ? voff[i] : 0.0) / NFA_CKMS;       // hyperfine.pyx:71, one rounding per operation
+        volatile double f = 1.0 - q;
+        row.hfreq[i] = f * nu;
+        row.tauw[i] = i < n ? tauw[i] : 0.0;
+        row.rank[i] = (unsigned char)i;
+    }
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return voff[a] > voff[b]; });
+    for (int k = 0; k < n; ++k) row.rank[order[k]] = (unsigned char)k;
+}
+// The shipped table of global transition index tg (NFA_T_*): the line count, the rest frequency, offsets and weights
+static int builtin_table(int tg, double *nu, const double **voff, const double **tauw) {
+    static const double gauss_voff[NFA_MAX_HF_N] = {0.0}, gauss_w[NFA_MAX_HF_N] = {1.0};
+    if (tg < NFA_T_N2HP) { *nu = nfa_nu[tg]; *voff = nfa_voff[tg]; *tauw = nfa_tau_wts[tg]; return nfa_nhf[tg]; }
+    if (tg < NFA_T_GAUSS) {
+        const int t = tg - NFA_T_N2HP;
+        *nu = nfa_n2hp_nu[t]; *voff = nfa_n2hp_voff[t]; *tauw = nfa_n2hp_tau_wts[t]; return nfa_n2hp_nhf[t];
+    }
+    *nu = 0.0; *voff = gauss_voff; *tauw = gauss_w; return 1;
+}
+
 static int engine_init_once();
 // HIP's current device is per host thread (default 0): every public entry point that allocates or
 // launches binds the calling thread to the engine's device first (broker threads, sampler threads
@@ -128,43 +156,13 @@ static int engine_init_once() {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, g_eng.device));
     g_eng.n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    {   // transition tables of all models in one index space (nfa_device.h)
-        static int h_nhf[NFA_T_ALL];
-        static double h_nu[NFA_T_ALL], h_voff[NFA_T_ALL][NFA_MAX_HF_N], h_tauw[NFA_T_ALL][NFA_MAX_HF_N];
-        memset(h_voff, 0, sizeof(h_voff)); memset(h_tauw, 0, sizeof(h_tauw));
-        for (int t = 0; t < NFA_N_LEVELS; ++t) {
-            h_nhf[t] = nfa_nhf[t]; h_nu[t] = nfa_nu[t];
-            memcpy(h_voff[t], nfa_voff[t], sizeof(h_voff[t])); memcpy(h_tauw[t], nfa_tau_wts[t], sizeof(h_tauw[t]));
-        }
-        for (int t = 0; t < NFA_N2HP_LEVELS; ++t) {
-            const int g = NFA_T_N2HP + t;
-            h_nhf[g] = nfa_n2hp_nhf[t]; h_nu[g] = nfa_n2hp_nu[t];
-            memcpy(h_voff[g], nfa_n2hp_voff[t], sizeof(h_voff[g])); memcpy(h_tauw[g], nfa_n2hp_tau_wts[t], sizeof(h_tauw[g]));
-        }
-        h_nhf[NFA_T_GAUSS] = 1; h_nu[NFA_T_GAUSS] = 0.0; h_tauw[NFA_T_GAUSS][0] = 1.0;
-        static double h_hfreq[NFA_T_ALL][NFA_MAX_HF_N];
-        for (int t = 0; t < NFA_T_ALL; ++t)
-            for (int i = 0; i < NFA_MAX_HF_N; ++i) {
-                volatile double q = h_voff[t][i] / NFA_CKMS;      // hyperfine.pyx:71, one rounding per operation
-                volatile double f = 1.0 - q;
-                h_hfreq[t][i] = f * h_nu[t];
-            }
-        // rank of every line when a transition's lines are ordered by velocity offset (stable; nfa_device.h: c_rank)
-        static unsigned char h_rank[NFA_T_ALL][NFA_MAX_HF_N];
-        for (int t = 0; t < NFA_T_ALL; ++t) {
-            std::vector<int> order(h_nhf[t]);
-            for (int i = 0; i < h_nhf[t]; ++i) order[i] = i;
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return h_voff[t][a] > h_voff[t][b]; });
-            for (int i = 0; i < NFA_MAX_HF_N; ++i) h_rank[t][i] = (unsigned char)i;
-            for (int k = 0; k < h_nhf[t]; ++k) h_rank[t][order[k]] = (unsigned char)k;
-        }
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_rank), h_rank, sizeof(h_rank)));
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_hfreq), h_hfreq, sizeof(h_hfreq)));
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_nhf), h_nhf, sizeof(h_nhf)));
+    {   // what belongs to a transition beyond its lines (nfa_device.h); the lines are per spectra set (specset_fill)
+        static double h_nu[NFA_T_ALL];
+        for (int t = 0; t < NFA_N_LEVELS; ++t) h_nu[t] = nfa_nu[t];
+        for (int t = 0; t < NFA_N2HP_LEVELS; ++t) h_nu[NFA_T_N2HP + t] = nfa_n2hp_nu[t];
+        h_nu[NFA_T_GAUSS] = 0.0; h_nu[NFA_T_LINES] = 0.0;
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_nu), h_nu, sizeof(h_nu)));
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_ea), nfa_ea, sizeof(nfa_ea)));
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_voff), h_voff, sizeof(h_voff)));
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_tauw), h_tauw, sizeof(h_tauw)));
     }
     std::vector<double> tabs(SM_END_TABLE, 0.0);
     // 2^(i/256)
@@ -192,6 +190,8 @@ struct nfa_specset {
     double *d_t0tbg = nullptr, *d_rowsq = nullptr, *d_totsq = nullptr;
     double *d_w = nullptr, *d_wdata = nullptr;     // a noise per channel: SpecDev.chan_w, .wdata (null otherwise)
     double *d_bl = nullptr;                         // a baseline: SpecDev.bl (nfa_specset_set_baseline)
+    LineRow *d_lines = nullptr;                     // the line rows of the spectra: SpecDev.lines
+    int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
     bool    bl_w1 = false;                          // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
 };
 
@@ -398,15 +398,20 @@ static int launch_bl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_b
     return NFA_OK;
 }
 
+// The caller's line tables of the hyperfine model (nfa_specset_create_lines): n_lines[n_spec], and the spectra's offsets
+// and weights concatenated
+struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; };
+
 static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *sizes, const int32_t *trans_ids,
                         const double *rest_freqs, const double *const *xarr, int64_t n_pix, const double *data,
-                        const double *noise, const double *chan_noise) {
+                        const double *noise, const double *chan_noise, const LineTables *lines) {
     SpecDev &d = ss->dev;
     d.n_spec = n_spec;
     d.model = model;
-    d.npar = model == NFA_MODEL_DIAZENYLIUM ? NFA_N2HP_PARAMS : model == NFA_MODEL_GAUSSIAN ? NFA_GAUSS_PARAMS
-                                                                                          : NFA_N_PARAMS;
-    int64_t tot = 0, rows = 0;
+    d.npar = model == NFA_MODEL_DIAZENYLIUM || model == NFA_MODEL_HYPERFINE ? NFA_N2HP_PARAMS
+           : model == NFA_MODEL_GAUSSIAN ? NFA_GAUSS_PARAMS : NFA_N_PARAMS;
+    std::vector<LineRow> h_lines((size_t)n_spec, LineRow{});          // the line rows of the spectra
+    int64_t tot = 0, rows = 0, line0 = 0;
     for (int s = 0; s < n_spec; ++s) {
         if (sizes[s] < 2 || sizes[s] > (1 << 24)) return fail(NFA_ERR_ARG, "spectrum size out of range");
         int tglob;                                                      // index into the device tables
@@ -422,10 +427,26 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
             tglob = NFA_T_N2HP + trans_ids[s] - 1;
             d.rest[s] = nfa_n2hp_nu[trans_ids[s] - 1];
             ss->nhf_max = std::max(ss->nhf_max, nfa_n2hp_nhf[trans_ids[s] - 1]);
-        } else {
+        } else if (model == NFA_MODEL_GAUSSIAN) {
             tglob = NFA_T_GAUSS;
             d.rest[s] = rest_freqs ? rest_freqs[s] : 0.0;               // core.pyx:510
             ss->nhf_max = std::max(ss->nhf_max, 1);
+        } else {
+            tglob = NFA_T_LINES;
+            d.rest[s] = rest_freqs[s];
+            ss->nhf_max = std::max(ss->nhf_max, (int)lines->n_lines[s]);
+        }
+        {
+            double nu; const double *voff, *tauw;
+            int n;
+            if (model == NFA_MODEL_HYPERFINE) {
+                n = lines->n_lines[s]; nu = rest_freqs[s]; voff = lines->voff + line0; tauw = lines->tau_wts + line0;
+                line0 += n;
+            } else {
+                n = builtin_table(tglob, &nu, &voff, &tauw);
+            }
+            ss->h_nhf[s] = n;
+            line_row_fill(h_lines[s], n, nu, voff, tauw);
         }
         const double nu_chan = xarr[s][1] - xarr[s][0];
         if (!(nu_chan > 0)) return fail(NFA_ERR_ARG, "frequency axis must be ascending");   // core.pyx:503-504
@@ -467,6 +488,9 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     d.xarr = ss->d_xarr; d.t0 = ss->d_t0; d.tbg = ss->d_tbg; d.data = ss->d_data; d.noise = ss->d_noise;
     d.t0tbg = ss->d_t0tbg; d.rowsq = ss->d_rowsq; d.totsq = ss->d_totsq;
     d.bl = nullptr; d.bl_order = -1;                                    // no baseline (nfa_specset_set_baseline)
+    HIP_TRY(hipMalloc(&ss->d_lines, sizeof(LineRow) * n_spec));
+    HIP_TRY(hipMemcpy(ss->d_lines, h_lines.data(), sizeof(LineRow) * n_spec, hipMemcpyHostToDevice));
+    d.lines = ss->d_lines;
     if (chan_noise) {
         HIP_TRY(hipMalloc(&ss->d_w, sizeof(double) * tot * n_pix));
         HIP_TRY(hipMalloc(&ss->d_wdata, sizeof(double) * tot * n_pix));
@@ -480,16 +504,18 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
 static int specset_create(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
                           const int32_t *trans_ids, const double *rest_freqs,
                           const double *const *xarr, int64_t n_pix, const double *data,
-                          const double *noise, const double *chan_noise) {
-    if (model < NFA_MODEL_AMMONIA || model > NFA_MODEL_GAUSSIAN) return fail(NFA_ERR_ARG, "unknown model");
-    if (model != NFA_MODEL_GAUSSIAN && !trans_ids) return fail(NFA_ERR_ARG, "null argument");
+                          const double *noise, const double *chan_noise, const LineTables *lines = nullptr) {
+    if (model == NFA_MODEL_HYPERFINE && !lines)
+        return fail(NFA_ERR_ARG, "the hyperfine model takes its line tables through nfa_specset_create_lines");
+    if (model < NFA_MODEL_AMMONIA || model > NFA_MODEL_HYPERFINE) return fail(NFA_ERR_ARG, "unknown model");
+    if (model != NFA_MODEL_GAUSSIAN && model != NFA_MODEL_HYPERFINE && !trans_ids) return fail(NFA_ERR_ARG, "null argument");
     if (model == NFA_MODEL_GAUSSIAN && n_spec != 1)                     // gaussian.pyx:57-89
         return fail(NFA_ERR_ARG, "the Gaussian model takes one spectrum");
     if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
     if (n_pix < 1) return fail(NFA_ERR_ARG, "n_pix must be >= 1");
     int rc = engine_init(); if (rc) return rc;
     nfa_specset *ss = new nfa_specset();
-    rc = specset_fill(ss, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, noise, chan_noise);
+    rc = specset_fill(ss, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, noise, chan_noise, lines);
     if (rc) { nfa_specset_destroy(ss); return rc; }          // frees whatever was allocated
     *out = ss;
     return NFA_OK;
@@ -504,10 +530,10 @@ int nfa_specset_create_model(nfa_specset **out, int model, int n_spec, const int
 }
 
 // sigma_ref of every (pixel, spectrum) -- the smallest finite sigma_c -- after the checks of the declaration
-int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
-                                     const int32_t *trans_ids, const double *rest_freqs,
-                                     const double *const *xarr, int64_t n_pix, const double *data,
-                                     const double *chan_noise) {
+static int specset_create_channel_noise(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
+                                        const int32_t *trans_ids, const double *rest_freqs,
+                                        const double *const *xarr, int64_t n_pix, const double *data,
+                                        const double *chan_noise, const LineTables *lines) {
     if (!out || !sizes || !xarr || !data || !chan_noise) return fail(NFA_ERR_ARG, "null argument");
     if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
     if (n_pix < 1) return fail(NFA_ERR_ARG, "n_pix must be >= 1");
@@ -532,14 +558,67 @@ int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, c
             ref[(size_t)(p * n_spec + s)] = lo;
         }
     }
-    return specset_create(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, ref.data(), chan_noise);
+    return specset_create(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, ref.data(), chan_noise, lines);
+}
+int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
+                                     const int32_t *trans_ids, const double *rest_freqs,
+                                     const double *const *xarr, int64_t n_pix, const double *data,
+                                     const double *chan_noise) {
+    return specset_create_channel_noise(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, chan_noise, nullptr);
+}
+
+int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
+                             const double *rest_freqs, const double *voff, const double *tau_wts,
+                             const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                             const double *chan_noise) {
+    if (!out || !sizes || !n_lines || !rest_freqs || !voff || !tau_wts || !xarr || !data)
+        return fail(NFA_ERR_ARG, "null argument");
+    if ((noise != nullptr) == (chan_noise != nullptr))
+        return fail(NFA_ERR_ARG, "exactly one of noise and chan_noise must be given");
+    if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
+    int64_t l0 = 0;
+    for (int s = 0; s < n_spec; ++s) {
+        const int n = n_lines[s];
+        const std::string at = " (spectrum " + std::to_string(s) + ")";
+        if (n < 1 || n > NFA_MAX_HF_N) return fail(NFA_ERR_ARG, "a line table must have 1..50 lines" + at);
+        if (!(std::isfinite(rest_freqs[s]) && rest_freqs[s] > 0))
+            return fail(NFA_ERR_ARG, "a rest frequency must be finite and positive" + at);
+        bool any = false;
+        for (int i = 0; i < n; ++i) {
+            const double v = voff[l0 + i], w = tau_wts[l0 + i];
+            if (!(std::isfinite(v) && std::fabs(v) < NFA_CKMS))
+                return fail(NFA_ERR_ARG, "a velocity offset must be finite and below the speed of light" + at);
+            if (!(std::isfinite(w) && w >= 0)) return fail(NFA_ERR_ARG, "a line weight must be finite and not negative" + at);
+            any = any || w > 0;
+        }
+        if (!any) return fail(NFA_ERR_ARG, "the weights of a line table are all zero" + at);
+        l0 += n;
+    }
+    const LineTables lt = {n_lines, voff, tau_wts};
+    if (chan_noise)
+        return specset_create_channel_noise(out, NFA_MODEL_HYPERFINE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data,
+                                            chan_noise, &lt);
+    return specset_create(out, NFA_MODEL_HYPERFINE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data, noise, nullptr, &lt);
+}
+
+int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n) {
+    if (!nu || !voff || !tau_wts || !n) return fail(NFA_ERR_ARG, "null argument");
+    int tg;
+    if (model == NFA_MODEL_AMMONIA && trans_id >= 1 && trans_id <= NFA_N_LEVELS) tg = trans_id - 1;
+    else if (model == NFA_MODEL_DIAZENYLIUM && trans_id >= 1 && trans_id <= NFA_N2HP_LEVELS) tg = NFA_T_N2HP + trans_id - 1;
+    else return fail(NFA_ERR_ARG, "no shipped line table for this model and trans_id (ammonia 1..9, N2H+ 1..3)");
+    const double *v, *w;
+    *n = builtin_table(tg, nu, &v, &w);
+    memcpy(voff, v, sizeof(double) * NFA_MAX_HF_N);
+    memcpy(tau_wts, w, sizeof(double) * NFA_MAX_HF_N);
+    return NFA_OK;
 }
 
 int nfa_specset_destroy(nfa_specset *ss) {
     if (!ss) return NFA_OK;
     (void)hipFree(ss->d_xarr); (void)hipFree(ss->d_t0); (void)hipFree(ss->d_tbg); (void)hipFree(ss->d_data); (void)hipFree(ss->d_noise);
     (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq);
-    (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl);
+    (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl); (void)hipFree(ss->d_lines);
     delete ss;
     return NFA_OK;
 }
@@ -777,7 +856,7 @@ int nfa_runner_create(nfa_runner **out, nfa_specset *ss, nfa_priors *priors, int
     if (!out || !ss) return fail(NFA_ERR_ARG, "null argument");
     if (ncomp < 1 || ncomp > MAXCOMP) return fail(NFA_ERR_ARG, "ncomp must be in 1..10");   // ammonia.pyx:401
     if (priors && priors->prog.n_param != ss->dev.npar)
-        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+, 3 Gaussian)");
+        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+ and hyperfine, 3 Gaussian)");
     int rc = engine_init(); if (rc) return rc;
     nfa_runner *r = new nfa_runner();
     r->ss = ss; r->pr = priors; r->ncomp = ncomp; r->cold = cold ? 1 : 0; r->lte = lte ? 1 : 0;

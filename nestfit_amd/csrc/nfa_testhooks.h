@@ -60,8 +60,8 @@ __global__ void test_partition_kernel(const double *trot, double *qpara, double 
 
 __global__ void test_windows_kernel(SpecDev S, int s, double voff, double sigm, int *lo, int *hi) {
     const int t = S.trans[s] - 1, i = threadIdx.x;
-    if (i >= c_nhf[t]) return;
-    const LineConst lc = nf_line(t, i, voff / NFA_CKMS, sigm / NFA_CKMS, S.rest[s], S.nu_min[s], S.nu_chan[s],
+    if (i >= S.lines[s].nhf) return;
+    const LineConst lc = nf_line(t, S.lines[s].hfreq, i, voff / NFA_CKMS, sigm / NFA_CKMS, S.rest[s], S.nu_min[s], S.nu_chan[s],
                                  S.size[s]);
     lo[i] = lc.lo; hi[i] = lc.hi;
 }
@@ -144,8 +144,7 @@ int nfa_test_partition(const double *trot, double *qpara, double *qorth, int64_t
 int nfa_test_windows(nfa_runner *r, int spec, double voff, double sigm, int32_t *lo, int32_t *hi) {
     if (!r || spec < 0 || spec >= r->ss->dev.n_spec) return fail(NFA_ERR_ARG, "bad spectrum index");
     int *dl = nullptr, *dh = nullptr;
-    const int tg = r->ss->dev.trans[spec] - 1;          // index into the combined tables
-    const int nhf = tg < NFA_T_N2HP ? nfa_nhf[tg] : tg < NFA_T_GAUSS ? nfa_n2hp_nhf[tg - NFA_T_N2HP] : 1;
+    const int nhf = r->ss->h_nhf[spec];
     HIP_TRY(hipMalloc(&dl, sizeof(int) * 64));
     HIP_TRY(hipMalloc(&dh, sizeof(int) * 64));
     hipLaunchKernelGGL(test_windows_kernel, dim3(1), dim3(64), 0, 0, r->ss->dev, spec, voff, sigm, dl, dh);

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order
+from ._model import N_MODEL, _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order
 from .core import _as_inplace_matrix
 
 
@@ -47,11 +47,12 @@ class CubeRunner:
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
-                 model=0, rest_freqs=None, baseline_order=None):
-        """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz])."""
+                 model=0, rest_freqs=None, baseline_order=None, lines=None):
+        """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
+        one `LineTable` per spectrum; `trans_ids` is not used)."""
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
-        self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs)
+        self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs, lines=lines)
         self._run = _RunnerHandle(self._ss, utrans, ncomp, cold, lte)
         self.baseline_order = baseline_order
         if baseline_order is not None:
@@ -59,7 +60,7 @@ class CubeRunner:
         self._data, self._noise = data, noise                # (fit_baseline)
         self.utrans = utrans
         self.ncomp = int(ncomp)
-        self.n_model = {0: 6, 1: 4, 2: 3}[int(model)]
+        self.n_model = N_MODEL[int(model)]
         self.n_params = self.ndim = self.n_model * self.ncomp
         self.n_pix = self._ss.n_pix
         self.n_spec = self._ss.n_spec

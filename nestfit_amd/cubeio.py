@@ -299,8 +299,14 @@ class DataCube:
     (descending) radio velocities in km/s, `dv` the channel width in km/s.  `cube` is a `SimpleCube` (or
     anything with its attributes); `noise_map` a number or a noise-map object."""
 
-    def __init__(self, cube, noise_map, trans_id=None):
+    def __init__(self, cube, noise_map, trans_id=None, lines=None):
+        """lines: the cube's `LineTable` (hyperfine model), the alternative to `trans_id`."""
+        if lines is not None:
+            from .hyperfine import LineTable
+            if trans_id is not None or not isinstance(lines, LineTable):
+                raise ValueError('a cube takes a trans_id or a LineTable (lines=), not both')
         self.trans_id = trans_id
+        self.lines = lines
         self.noise_map = noise_map if hasattr(noise_map, 'get_noise') else NoiseMapUniform(noise_map)
         self._header = dict(cube.header)
         kelvin, freq, velo = self._ingest(cube)
@@ -466,6 +472,8 @@ class CubeStack:
                                     for dc in self.cubes], axis=1)
         else:
             noise = np.stack([dc.noise_map.values_at(lon, lat) for dc in self.cubes], axis=1)
+        if model == 3:                                               # the hyperfine model: the cubes' line tables
+            runner_kwargs = dict(runner_kwargs, lines=[getattr(dc, 'lines', None) for dc in self.cubes])
         runner = CubeRunner([dc.xarr for dc in self.cubes], [dc.trans_id for dc in self.cubes], data, noise,
                             utrans, ncomp=ncomp, model=model, **runner_kwargs)
         return runner, lon, lat

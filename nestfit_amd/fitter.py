@@ -16,7 +16,7 @@ from . import sampler
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
-_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2}
+_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3}
 
 
 class _RunInfo:
@@ -230,6 +230,7 @@ class CubeFitter:
             store.insert_header(self.stack)
         store.insert_fitter_pars(self)
         store.insert_model_metadata(self.runner_cls)
+        store.insert_model_lines(self.stack)
         todo = range(store.nchunks) if rank is None else [0]
         written = {}
         for k in todo:

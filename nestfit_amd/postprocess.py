@@ -12,7 +12,7 @@ order (..., b, l).
 """
 import numpy as np
 
-_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2}
+_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3}
 N_PDF_BINS = 200                 # edges when `aggregate_run_pdfs` makes its own bins (main.py:905-917)
 PDF_FLOOR = 1e-32                # zero-probability bins before the logarithm (main.py:980)
 PREDICT_ROWS = 4096              # (pixel, component) rows per device batch
@@ -275,6 +275,23 @@ def quantize_conv_marginals(store):
 # ---------------------------------------------------------------------------------------------
 #  the two steps on the hot path: one model evaluation per (pixel, component)
 # ---------------------------------------------------------------------------------------------
+def check_model_lines(store, stack):
+    """The line tables of the stack's cubes (hyperfine model), after comparing them with the ones the store was fitted
+    with: ValueError where they differ -- map products of other lines than the fit's would be silently wrong."""
+    tables = [getattr(dc, 'lines', None) for dc in stack.cubes]
+    if any(t is None for t in tables):
+        raise ValueError('the store was fitted with the hyperfine model: every cube of the stack needs its LineTable (DataCube(..., lines=))')
+    stored = store.read_model_lines()
+    if len(stored) != len(tables) or any(a != b for a, b in zip(stored, tables)):
+        raise ValueError("the stack's line tables differ from the ones the store was fitted with (/model_lines)")
+    return tables
+
+
+def _spec_name(k, dc):
+    """Dataset name of cube k under model_spec: trans<ID> (main.py:1190), spec<k> for a cube with a `LineTable` (hyperfine model)."""
+    return f'spec{k}' if getattr(dc, 'lines', None) is not None else f'trans{dc.trans_id}'
+
+
 def _device_predictor(store, stack):
     """predict(lon[B], lat[B], theta[B, p], want_spectra) -> (spectra[B, chan_tot] or None, peak[B, t],
     integrated[B, t]) on the GPU: every pixel's data stay where the fit left them conceptually -- a predict
@@ -288,6 +305,8 @@ def _device_predictor(store, stack):
     extra = {}
     if model_id == 2:                                    # the Gaussian model has no transition table to take them from
         extra['rest_freqs'] = [float(dc.full_header.get('RESTFRQ', dc.full_header.get('RESTFREQ'))) for dc in stack.cubes]
+    if model_id == 3:                                    # the caller's line tables: the stack's, which must be the store's
+        extra['lines'] = check_model_lines(store, stack)
     runner = CubeRunner(xarrs, trans, np.zeros((1, chan_tot)), np.ones((1, len(xarrs))), None, ncomp=1,
                         model=model_id, **extra)
     runner.set_exp_mode('table')                         # map products in the reference's own arithmetic: a one-off, not a rate
@@ -367,8 +386,8 @@ def generate_predicted_profiles(store, stack, runner=None, predict_backend=None)
         spec, _, _ = predict(l[s], b[s], theta[s], True)
         for k, cube in enumerate(cubes):
             cube[m[s], :, b[s], l[s]] = spec[:, edges[k]:edges[k + 1]]
-    for cube, dc in zip(cubes, stack.cubes):
-        store.create_dataset(f'trans{dc.trans_id}', cube, group=f'{store.dpath}/model_spec')
+    for k, (cube, dc) in enumerate(zip(cubes, stack.cubes)):
+        store.create_dataset(_spec_name(k, dc), cube, group=f'{store.dpath}/model_spec')
 
 
 def create_fits_from_store(store, prefix='source'):
@@ -391,6 +410,8 @@ def create_fits_from_store(store, prefix='source'):
 def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, post_kernel=None,
                     evid_weight=True, predict_backend=None):
     """All steps in the reference's order (main.py:1240-1276)."""
+    if store.hdf.attrs.get('model_name') == 'hyperfine':     # before any product is written
+        check_model_lines(store, stack)
     aggregate_run_attributes(store)
     convolve_evidence(store, evid_kernel)
     aggregate_run_products(store)

@@ -275,6 +275,7 @@ TABLE_NAME = 'table'
 CHUNK_STEM = 'chunk'
 FILE_SUFFIXES = {'hdf5': '.hdf', 'npz': '.npz'}       # '.hdf' is the reference's (main.py:236)
 PRODUCTS_GROUP = '/products'
+MODEL_LINES_GROUP = '/model_lines'
 
 # root attribute of the table file  <-  attribute of the CubeFitter          (store_spec.rst:60-63)
 FITTER_ATTRS = (
@@ -308,7 +309,7 @@ class HdfStore:
     chunk_prefix = CHUNK_STEM
 
     def __init__(self, store_name, nchunks=1, file_format=None):
-        from . import MODELS
+        from . import model_module
         self.store_name = str(store_name)
         self.store_dir = Path(check_ext(self.store_name, ext=STORE_SUFFIX.lstrip('.')))
         self.store_dir.mkdir(parents=True, exist_ok=True)
@@ -322,7 +323,7 @@ class HdfStore:
         root = self.hdf.attrs
         root.setdefault('nchunks', nchunks)          # an existing store keeps its own number of chunks
         self.nchunks = root['nchunks']
-        self.model = MODELS.get(root.get('model_name'))
+        self.model = model_module(root.get('model_name'))
         # An HDF5 table keeps its links in the file (external links, resolved while reading it); the .npz twin has no
         # link objects, so there the links of a linked store are rebuilt on opening -- in memory only: opening a
         # store to read it never rewrites it.
@@ -432,6 +433,37 @@ class HdfStore:
         assert self.is_open
         module = inspect.getmodule(runner_cls)
         self.hdf.attrs.update({name: getattr(module, attr) for name, attr in MODEL_ATTRS})
+
+    def insert_model_lines(self, stack):
+        """The line table of every cube that has one (hyperfine model) under /model_lines/spec<k>: attributes `nu` and
+        `name`, datasets `voff` and `tau_wts`.  Nothing for the models whose tables ship with the engine."""
+        assert self.is_open
+        tables = [getattr(dc, 'lines', None) for dc in stack.cubes]
+        if all(t is None for t in tables):
+            return
+        if MODEL_LINES_GROUP in self.hdf:
+            del self.hdf[MODEL_LINES_GROUP]
+        for k, t in enumerate(tables):
+            if t is None:
+                raise ValueError('either every cube of a stack has a LineTable or none has')
+            group = self.hdf.require_group(f'{MODEL_LINES_GROUP}/spec{k}')
+            group.attrs.update(nu=float(t.nu), name='' if t.name is None else t.name)
+            group.create_dataset('voff', data=np.array(t.voff))
+            group.create_dataset('tau_wts', data=np.array(t.tau_wts))
+
+    def read_model_lines(self):
+        """The `LineTable`s the store was fitted with, in cube order ([] for a store without any)."""
+        from .hyperfine import LineTable
+        assert self.is_open
+        if MODEL_LINES_GROUP not in self.hdf:
+            return []
+        top = self.hdf[MODEL_LINES_GROUP]
+        out = []
+        for k in range(len(list(top))):
+            g = top[f'spec{k}']
+            out.append(LineTable(g.attrs['nu'], np.asarray(g['voff'][...]), np.asarray(g['tau_wts'][...]),
+                                 name=g.attrs.get('name') or None))
+        return out
 
     # ---- products -----------------------------------------------------------------------------
     def create_dataset(self, dset_name, data, group='', clobber=True):
