@@ -150,6 +150,7 @@ int nfa_specset_create(nfa_specset **out, int n_spec, const int64_t *sizes,
 #define NFA_MODEL_DIAZENYLIUM  1
 #define NFA_MODEL_GAUSSIAN     2
 #define NFA_MODEL_HYPERFINE    3   /* nfa_specset_create_lines below; this function returns NFA_ERR_ARG for it */
+#define NFA_MODEL_LTE          4   /* nfa_specset_create_lte below; this function returns NFA_ERR_ARG for it */
 int nfa_specset_create_model(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
                              const int32_t *trans_ids, const double *rest_freqs,
                              const double *const *xarr, int64_t n_pix, const double *data,
@@ -185,6 +186,28 @@ int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes
                              const double *rest_freqs, const double *voff, const double *tau_wts,
                              const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                              const double *chan_noise);
+/* model 4 = one species in LTE across several rotational transitions: column density, excitation temperature and a
+ * partition function give every transition its own optical depth.  Parameters per component, parameter-major: voff (km/s),
+ * tex (K), lncol = log10 of the total column density (cm^-2), sigm (km/s).  Spectrum s covers ONE transition, with any
+ * hyperfine structure inside it: n_lines, rest_freqs, voff and tau_wts as for nfa_specset_create_lines, but the weights
+ * of a transition sum to 1; e_up[n_spec] (K) and g_up[n_spec] are its upper level's energy and statistical weight,
+ * a_ul[n_spec] (1/s) its Einstein coefficient.  All spectra share the partition function Q, given at n_q (2..64)
+ * temperatures q_temp (K, strictly ascending) as q_val.  In cgs units, with T0 = h nu / k:
+ *     ln Q(T)  linear in ln T between the bracketing entries of the table; outside it the end segment's line is continued
+ *     N_u      = 10^lncol g_up exp(-e_up / tex) / Q(tex)
+ *     tau_main = N_u c^2 a_ul / (8 pi nu^2) expm1(T0 / tex) CKMS / (sigm nu sqrt(2 pi))
+ * tau_main is the transition's peak optical depth summed over its lines; line i gets tau_main * tau_wts[i], and the
+ * spectrum follows as for model 3 (c_hf_predict with tex).  A tex or sigm that is not an ordinary positive number gives
+ * NaN.  Returns NFA_ERR_ARG, with a message, for everything nfa_specset_create_lines refuses and for an e_up that is not
+ * finite or is negative, a g_up or a_ul that is not finite and positive, a transition whose weights do not sum to 1
+ * within 1e-6, n_q outside 2..64, temperatures that are not positive and strictly ascending, and a Q that is not finite
+ * and positive. */
+int nfa_specset_create_lte(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
+                           const double *rest_freqs, const double *voff, const double *tau_wts,
+                           const double *e_up, const double *g_up, const double *a_ul,
+                           int n_q, const double *q_temp, const double *q_val,
+                           const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                           const double *chan_noise);
 /* A shipped line table, as a template for nfa_specset_create_lines: model 0 (trans_id 1..9) or 1 (trans_id 1..3);
  * voff and tau_wts take 50 doubles each (zero behind the *n lines), *nu the rest frequency in Hz.  Needs no device. */
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n);

@@ -10,17 +10,18 @@ from .core import (ConstantPrior, CenSepPrior, Distribution, DuplicatePrior, Ord
 from .ammonia import AmmoniaRunner, AmmoniaSpectrum, amm_predict
 from .diazenylium import DiazenyliumRunner, DiazenyliumSpectrum, nnhp_predict
 from .gaussian import GaussianRunner, gauss_predict
-from . import ammonia, diazenylium, gaussian, hyperfine
+from . import ammonia, diazenylium, gaussian, hyperfine, lte
 from .hyperfine import HyperfineRunner, LineTable
+from .lte import LteLines, LteRunner, LteSpectrum, Molecule, lte_predict
 
 # registry like nestfit/models/__init__.py:3-7
 MODELS = {m.NAME: m for m in (ammonia, diazenylium, gaussian)}
 
 
 def model_module(name):
-    """The model module of a store's `model_name`: one of MODELS (the reference's three), or `hyperfine`, the model
-    of caller-supplied line tables; None for an unknown name."""
-    return hyperfine if name == hyperfine.NAME else MODELS.get(name)
+    """The model module of a store's `model_name`: one of MODELS (the reference's three), `hyperfine`, the model of
+    caller-supplied line tables, or `lte`, one species in LTE across several transitions; None for an unknown name."""
+    return {hyperfine.NAME: hyperfine, lte.NAME: lte}.get(name) or MODELS.get(name)
 
 
 from .prior_constructors import get_irdc_priors, get_synth_priors
@@ -32,4 +33,5 @@ __all__ = [
     'AmmoniaSpectrum', 'AmmoniaRunner', 'amm_predict', 'get_irdc_priors', 'get_synth_priors',
     'DiazenyliumSpectrum', 'DiazenyliumRunner', 'nnhp_predict', 'GaussianRunner', 'gauss_predict',
     'MODELS', 'hyperfine', 'LineTable', 'HyperfineRunner', 'model_module',
+    'lte', 'Molecule', 'LteLines', 'LteSpectrum', 'LteRunner', 'lte_predict',
 ]

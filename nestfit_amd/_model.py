@@ -8,8 +8,9 @@ import numpy as np
 from . import _ffi
 from .core import Runner, _as_inplace_matrix, _as_inplace_vector
 
-MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_GAUSSIAN, MODEL_HYPERFINE = 0, 1, 2, 3
-N_MODEL = {MODEL_AMMONIA: 6, MODEL_DIAZENYLIUM: 4, MODEL_GAUSSIAN: 3, MODEL_HYPERFINE: 4}      # parameters per component
+MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_GAUSSIAN, MODEL_HYPERFINE, MODEL_LTE = 0, 1, 2, 3, 4
+# parameters per component
+N_MODEL = {MODEL_AMMONIA: 6, MODEL_DIAZENYLIUM: 4, MODEL_GAUSSIAN: 3, MODEL_HYPERFINE: 4, MODEL_LTE: 4}
 BASELINE_MAX = 3          # NFA_BASELINE_MAX
 
 
@@ -61,16 +62,23 @@ class _SpecSet:
     def __init__(self, xarrs, trans_ids, data, noise, model=MODEL_AMMONIA, rest_freqs=None, lines=None):
         """xarrs: list of 1-D axes; data [n_pix, sum(sizes)]; noise [n_pix, n_spec], or [n_pix, sum(sizes)]
         for a noise per channel (nfa_specset_create_channel_noise: inf masks a channel).  lines: the hyperfine
-        model's `LineTable` of every spectrum (nfa_specset_create_lines; `trans_ids` and `rest_freqs` are then unused)."""
+        model's `LineTable` of every spectrum (nfa_specset_create_lines; `trans_ids` and `rest_freqs` are then unused), or
+        the LTE model's `LteLines` of every spectrum, all of one `Molecule` (nfa_specset_create_lte)."""
         self.model = int(model)
-        if (self.model == MODEL_HYPERFINE) != (lines is not None):
-            raise ValueError('the hyperfine model (3), and no other, takes `lines`: one LineTable per spectrum')
+        if (self.model in (MODEL_HYPERFINE, MODEL_LTE)) != (lines is not None):
+            raise ValueError('the hyperfine model (3) and the LTE model (4), and no other, take `lines`: one LineTable '
+                             '(LteLines) per spectrum')
+        molecule = None
         if lines is not None:
             from .hyperfine import LineTable
             lines = list(lines)
             if len(lines) != len(xarrs) or not all(isinstance(t, LineTable) for t in lines):
                 raise ValueError('`lines` must hold one LineTable per spectrum')
+            if self.model == MODEL_LTE:
+                from .lte import check_one_molecule
+                molecule = check_one_molecule(lines)
             trans_ids = [-1] * len(lines)
+        self.molecule = molecule
         self.lines = lines
         lib = _ffi.engine()
         self.n_spec = len(xarrs)
@@ -98,10 +106,18 @@ class _SpecSet:
             self.rest_freqs = np.array([t.nu for t in lines], dtype=np.float64)
             voff = np.ascontiguousarray(np.concatenate([t.voff for t in lines]), dtype=np.float64)
             tau_wts = np.ascontiguousarray(np.concatenate([t.tau_wts for t in lines]), dtype=np.float64)
-            rc = lib.nfa_specset_create_lines(
-                C.byref(h), self.n_spec, sizes_p, n_lines.ctypes.data_as(_ffi._ip), _ffi.dptr(self.rest_freqs),
-                _ffi.dptr(voff), _ffi.dptr(tau_wts), xp, self.n_pix, _ffi.dptr(data),
-                None if self.per_channel else _ffi.dptr(noise), _ffi.dptr(noise) if self.per_channel else None)
+            head = (C.byref(h), self.n_spec, sizes_p, n_lines.ctypes.data_as(_ffi._ip), _ffi.dptr(self.rest_freqs),
+                    _ffi.dptr(voff), _ffi.dptr(tau_wts))
+            tail = (xp, self.n_pix, _ffi.dptr(data),
+                    None if self.per_channel else _ffi.dptr(noise), _ffi.dptr(noise) if self.per_channel else None)
+            if molecule is not None:
+                e_up, g_up, a_ul = (np.array([getattr(t, k) for t in lines], dtype=np.float64)
+                                    for k in ('e_up', 'g_up', 'a_ul'))
+                q_temp, q_val = np.ascontiguousarray(molecule.q_temp), np.ascontiguousarray(molecule.q_val)
+                rc = lib.nfa_specset_create_lte(*head, _ffi.dptr(e_up), _ffi.dptr(g_up), _ffi.dptr(a_ul), molecule.n,
+                                                _ffi.dptr(q_temp), _ffi.dptr(q_val), *tail)
+            else:
+                rc = lib.nfa_specset_create_lines(*head, *tail)
         else:
             create = lib.nfa_specset_create_channel_noise if self.per_channel else lib.nfa_specset_create_model
             rc = create(C.byref(h), self.model, self.n_spec, sizes_p, self.trans_ids.ctypes.data_as(_ffi._ip),
@@ -256,7 +272,7 @@ class EngineRunner(Runner):
             noise = np.array([[s.noise for s in spectra]])
         self._ss = _SpecSet([s.xarr for s in spectra], [s.trans_id for s in spectra], data, noise,
                             model=self.MODEL, rest_freqs=rest_freqs,
-                            lines=[s.lines for s in spectra] if self.MODEL == MODEL_HYPERFINE else None)
+                            lines=[s.lines for s in spectra] if self.MODEL in (MODEL_HYPERFINE, MODEL_LTE) else None)
         self._run = _RunnerHandle(self._ss, utrans, self.ncomp, cold, lte)
         self.baseline_order = baseline_order
         if baseline_order is not None:

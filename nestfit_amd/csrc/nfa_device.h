@@ -58,7 +58,8 @@
 
 // Transition indices of every model in one index space: 0..8 NH3 (1,1)..(9,9), 9..11 N2H+ 1-0, 2-1, 3-2, 12 the
 // Gaussian model's single "line" (offset 0, weight 1, rest frequency from the spectrum), 13 a spectrum of the
-// hyperfine model, whose lines the caller supplies (nfa_specset_create_lines).  SpecDev.trans holds index + 1.
+// hyperfine model or of the LTE model, whose lines the caller supplies (nfa_specset_create_lines, _create_lte).
+// SpecDev.trans holds index + 1.
 // The index selects what belongs to a transition beyond its lines (c_nu and c_ea: ammonia only; the Gaussian
 // model's line centre, nf_line); the lines themselves are per spectrum, in device memory (SpecDev.lines).
 #define NFA_T_N2HP   NFA_N_LEVELS
@@ -80,9 +81,20 @@ struct LineRow {
     unsigned char rank[NFA_MAX_HF_N];
 };
 
+// What the LTE model (NFA_MODEL_LTE, nfa_specset_create_lte) needs beyond the lines, one record per spectra set in
+// device memory: the upper level and the Einstein coefficient of every spectrum's transition, and the species'
+// partition function as ln Q over ln T with the slope of every segment (slope[k]: entries k, k + 1).  Only the set-up
+// stage's derive_lte_lane reads it (nfa_setup.h).
+#define NFA_LTE_MAXQ 64
+struct LteRec {
+    double e_up[MAXSPEC], g_up[MAXSPEC], a_ul[MAXSPEC];      // K, statistical weight, 1/s
+    int    n_q, pad;
+    double ln_t[NFA_LTE_MAXQ], ln_q[NFA_LTE_MAXQ], slope[NFA_LTE_MAXQ];
+};
+
 struct SpecDev {
     int     n_spec, ncomp, cold, lte;
-    int     model, npar;                 // NFA_MODEL_*, parameters per component (6 / 4 / 3)
+    int     model, npar;                 // NFA_MODEL_*, parameters per component (6 / 4 / 3 / 4 / 4)
     double  rest[MAXSPEC];               // line rest frequency (tables, or Spectrum.rest_freq)
     int     size[MAXSPEC], trans[MAXSPEC], off[MAXSPEC];
     double  nu_min[MAXSPEC], nu_chan[MAXSPEC];
@@ -105,6 +117,7 @@ struct SpecDev {
     const double *bl;
     int     bl_order;
     const LineRow *lines;                // [n_spec]: the lines of every spectrum, in device memory
+    const LteRec  *lte_rec;              // the LTE model's transitions and partition function (null for models 0..3)
 };
 
 // Baseline record of a (pixel, spectrum), DESIGN 4.5: [0, 4) m_k(d) = sum_j w_j P_k(u_j) d_j, the Legendre moments of the

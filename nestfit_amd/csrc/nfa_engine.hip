@@ -191,6 +191,7 @@ struct nfa_specset {
     double *d_w = nullptr, *d_wdata = nullptr;     // a noise per channel: SpecDev.chan_w, .wdata (null otherwise)
     double *d_bl = nullptr;                         // a baseline: SpecDev.bl (nfa_specset_set_baseline)
     LineRow *d_lines = nullptr;                     // the line rows of the spectra: SpecDev.lines
+    LteRec  *d_lte = nullptr;                       // the LTE model's record: SpecDev.lte_rec (null for the other models)
     int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
     bool    bl_w1 = false;                          // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
 };
@@ -399,8 +400,8 @@ static int launch_bl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_b
 }
 
 // The caller's line tables of the hyperfine model (nfa_specset_create_lines): n_lines[n_spec], and the spectra's offsets
-// and weights concatenated
-struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; };
+// and weights concatenated; `lte`: the LTE model's record as well (nfa_specset_create_lte), null for the hyperfine model
+struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; const LteRec *lte; };
 
 static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *sizes, const int32_t *trans_ids,
                         const double *rest_freqs, const double *const *xarr, int64_t n_pix, const double *data,
@@ -408,7 +409,8 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     SpecDev &d = ss->dev;
     d.n_spec = n_spec;
     d.model = model;
-    d.npar = model == NFA_MODEL_DIAZENYLIUM || model == NFA_MODEL_HYPERFINE ? NFA_N2HP_PARAMS
+    const bool tabled = model == NFA_MODEL_HYPERFINE || model == NFA_MODEL_LTE;      // the caller's line tables
+    d.npar = model == NFA_MODEL_DIAZENYLIUM || tabled ? NFA_N2HP_PARAMS
            : model == NFA_MODEL_GAUSSIAN ? NFA_GAUSS_PARAMS : NFA_N_PARAMS;
     std::vector<LineRow> h_lines((size_t)n_spec, LineRow{});          // the line rows of the spectra
     int64_t tot = 0, rows = 0, line0 = 0;
@@ -439,7 +441,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
         {
             double nu; const double *voff, *tauw;
             int n;
-            if (model == NFA_MODEL_HYPERFINE) {
+            if (tabled) {
                 n = lines->n_lines[s]; nu = rest_freqs[s]; voff = lines->voff + line0; tauw = lines->tau_wts + line0;
                 line0 += n;
             } else {
@@ -491,6 +493,11 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     HIP_TRY(hipMalloc(&ss->d_lines, sizeof(LineRow) * n_spec));
     HIP_TRY(hipMemcpy(ss->d_lines, h_lines.data(), sizeof(LineRow) * n_spec, hipMemcpyHostToDevice));
     d.lines = ss->d_lines;
+    if (model == NFA_MODEL_LTE) {
+        HIP_TRY(hipMalloc(&ss->d_lte, sizeof(LteRec)));
+        HIP_TRY(hipMemcpy(ss->d_lte, lines->lte, sizeof(LteRec), hipMemcpyHostToDevice));
+        d.lte_rec = ss->d_lte;
+    }
     if (chan_noise) {
         HIP_TRY(hipMalloc(&ss->d_w, sizeof(double) * tot * n_pix));
         HIP_TRY(hipMalloc(&ss->d_wdata, sizeof(double) * tot * n_pix));
@@ -507,8 +514,11 @@ static int specset_create(nfa_specset **out, int model, int n_spec, const int64_
                           const double *noise, const double *chan_noise, const LineTables *lines = nullptr) {
     if (model == NFA_MODEL_HYPERFINE && !lines)
         return fail(NFA_ERR_ARG, "the hyperfine model takes its line tables through nfa_specset_create_lines");
-    if (model < NFA_MODEL_AMMONIA || model > NFA_MODEL_HYPERFINE) return fail(NFA_ERR_ARG, "unknown model");
-    if (model != NFA_MODEL_GAUSSIAN && model != NFA_MODEL_HYPERFINE && !trans_ids) return fail(NFA_ERR_ARG, "null argument");
+    if (model == NFA_MODEL_LTE && !(lines && lines->lte))
+        return fail(NFA_ERR_ARG, "unknown model to this creator: the LTE model takes its line tables and partition function "
+                                 "through nfa_specset_create_lte");
+    if (model < NFA_MODEL_AMMONIA || model > NFA_MODEL_LTE) return fail(NFA_ERR_ARG, "unknown model");
+    if (model != NFA_MODEL_GAUSSIAN && !lines && !trans_ids) return fail(NFA_ERR_ARG, "null argument");
     if (model == NFA_MODEL_GAUSSIAN && n_spec != 1)                     // gaussian.pyx:57-89
         return fail(NFA_ERR_ARG, "the Gaussian model takes one spectrum");
     if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
@@ -567,10 +577,10 @@ int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, c
     return specset_create_channel_noise(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, chan_noise, nullptr);
 }
 
-int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
+// the checks of nfa_specset_create_lines on its own arguments
+static int check_line_tables(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
                              const double *rest_freqs, const double *voff, const double *tau_wts,
-                             const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
-                             const double *chan_noise) {
+                             const double *const *xarr, const double *data, const double *noise, const double *chan_noise) {
     if (!out || !sizes || !n_lines || !rest_freqs || !voff || !tau_wts || !xarr || !data)
         return fail(NFA_ERR_ARG, "null argument");
     if ((noise != nullptr) == (chan_noise != nullptr))
@@ -594,11 +604,68 @@ int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes
         if (!any) return fail(NFA_ERR_ARG, "the weights of a line table are all zero" + at);
         l0 += n;
     }
-    const LineTables lt = {n_lines, voff, tau_wts};
+    return NFA_OK;
+}
+
+int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
+                             const double *rest_freqs, const double *voff, const double *tau_wts,
+                             const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                             const double *chan_noise) {
+    int rc = check_line_tables(out, n_spec, sizes, n_lines, rest_freqs, voff, tau_wts, xarr, data, noise, chan_noise);
+    if (rc) return rc;
+    const LineTables lt = {n_lines, voff, tau_wts, nullptr};
     if (chan_noise)
         return specset_create_channel_noise(out, NFA_MODEL_HYPERFINE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data,
                                             chan_noise, &lt);
     return specset_create(out, NFA_MODEL_HYPERFINE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data, noise, nullptr, &lt);
+}
+
+int nfa_specset_create_lte(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
+                           const double *rest_freqs, const double *voff, const double *tau_wts,
+                           const double *e_up, const double *g_up, const double *a_ul,
+                           int n_q, const double *q_temp, const double *q_val,
+                           const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                           const double *chan_noise) {
+    int rc = check_line_tables(out, n_spec, sizes, n_lines, rest_freqs, voff, tau_wts, xarr, data, noise, chan_noise);
+    if (rc) return rc;
+    if (!e_up || !g_up || !a_ul || !q_temp || !q_val) return fail(NFA_ERR_ARG, "null argument");
+    LteRec rec = {};
+    int64_t l0 = 0;
+    for (int s = 0; s < n_spec; ++s) {
+        const std::string at = " (spectrum " + std::to_string(s) + ")";
+        if (!(std::isfinite(e_up[s]) && e_up[s] >= 0))
+            return fail(NFA_ERR_ARG, "an upper-level energy must be finite and not negative (K)" + at);
+        if (!(std::isfinite(g_up[s]) && g_up[s] > 0))
+            return fail(NFA_ERR_ARG, "an upper-level weight must be finite and positive" + at);
+        if (!(std::isfinite(a_ul[s]) && a_ul[s] > 0))
+            return fail(NFA_ERR_ARG, "an Einstein coefficient must be finite and positive (1/s)" + at);
+        double sum = 0.0;
+        for (int i = 0; i < n_lines[s]; ++i) sum += tau_wts[l0 + i];
+        if (!(std::fabs(sum - 1.0) <= 1e-6))
+            return fail(NFA_ERR_ARG, "the weights of a transition must sum to 1 within 1e-6" + at);
+        l0 += n_lines[s];
+        rec.e_up[s] = e_up[s]; rec.g_up[s] = g_up[s]; rec.a_ul[s] = a_ul[s];
+    }
+    if (n_q < 2 || n_q > NFA_LTE_MAXQ) return fail(NFA_ERR_ARG, "a partition table must have 2..64 entries");
+    for (int k = 0; k < n_q; ++k) {
+        if (!(std::isfinite(q_temp[k]) && q_temp[k] > 0 && (k == 0 || q_temp[k] > q_temp[k - 1])))
+            return fail(NFA_ERR_ARG, "the temperatures of a partition table must be finite, positive and strictly ascending");
+        if (!(std::isfinite(q_val[k]) && q_val[k] > 0))
+            return fail(NFA_ERR_ARG, "a partition function value must be finite and positive");
+        rec.ln_t[k] = log(q_temp[k]);
+        rec.ln_q[k] = log(q_val[k]);
+    }
+    for (int k = 0; k + 1 < n_q; ++k) {
+        if (!(rec.ln_t[k + 1] > rec.ln_t[k]))
+            return fail(NFA_ERR_ARG, "the temperatures of a partition table must be finite, positive and strictly ascending");
+        rec.slope[k] = (rec.ln_q[k + 1] - rec.ln_q[k]) / (rec.ln_t[k + 1] - rec.ln_t[k]);
+    }
+    rec.n_q = n_q;
+    const LineTables lt = {n_lines, voff, tau_wts, &rec};
+    if (chan_noise)
+        return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data,
+                                            chan_noise, &lt);
+    return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data, noise, nullptr, &lt);
 }
 
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n) {
@@ -619,6 +686,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_xarr); (void)hipFree(ss->d_t0); (void)hipFree(ss->d_tbg); (void)hipFree(ss->d_data); (void)hipFree(ss->d_noise);
     (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq);
     (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl); (void)hipFree(ss->d_lines);
+    (void)hipFree(ss->d_lte);
     delete ss;
     return NFA_OK;
 }
@@ -856,7 +924,7 @@ int nfa_runner_create(nfa_runner **out, nfa_specset *ss, nfa_priors *priors, int
     if (!out || !ss) return fail(NFA_ERR_ARG, "null argument");
     if (ncomp < 1 || ncomp > MAXCOMP) return fail(NFA_ERR_ARG, "ncomp must be in 1..10");   // ammonia.pyx:401
     if (priors && priors->prog.n_param != ss->dev.npar)
-        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+ and hyperfine, 3 Gaussian)");
+        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+, hyperfine and LTE, 3 Gaussian)");
     int rc = engine_init(); if (rc) return rc;
     nfa_runner *r = new nfa_runner();
     r->ss = ss; r->pr = priors; r->ncomp = ncomp; r->cold = cold ? 1 : 0; r->lte = lte ? 1 : 0;

@@ -390,6 +390,29 @@ __device__ __forceinline__ void derive_lane(const SpecDev &S, const double *th, 
     write_y_model<FAST>(dk, S, s, tex, g_tabs);
 }
 
+//  LTE (NFA_MODEL_LTE): voff, tex, lncol, sigm -> tau_main of the spectrum's transition from the column density, the
+//  upper level and the partition function (LteRec):
+//      N_u = 10^lncol g exp(-E/tex) / Q(tex),   ln Q linear in ln T between the table's entries (end segments continued)
+//      tau_main = N_u c^2 A / (8 pi nu^2) expm1(T0/tex) CKMS / (sigm nu sqrt(2 pi)),   T0 = h nu / k
+//  fracterm and widthterm as derive_lane forms them.  The segment is found by a scan over the table (at most 62
+//  compares of one register against uniform loads: no bisection's dependent chain, no registers for its bounds);
+//  one log and two exp per lane: exp(-E/tex) / Q is one exponential of the summed exponents.  No model has a reference
+//  whose log10 round trip there would be to mirror: tau_main as it stands in every mode.  The record is derive_simple_lane's,
+//  which calls this for its amplitude: the parameters lie as the hyperfine model's, and one copy of the record's code
+//  serves both (a second one cost the table mode's two-group set-up kernel registers it does not have).
+__device__ __forceinline__ double derive_lte_lane(const SpecDev &S, int s, double tex, double lncol, double sigm) {
+    const LteRec &L = *S.lte_rec;
+    const double nu0 = S.rest[s];
+    const double ln_tex = log(tex);
+    int k = 0;
+    for (int i = 1; i < L.n_q - 1; ++i) k += ln_tex >= L.ln_t[i] ? 1 : 0;
+    const double ln_q = L.ln_q[k] + L.slope[k] * (ln_tex - L.ln_t[k]);
+    const double pop_upper = exp10(lncol) * L.g_up[s] * exp(-L.e_up[s] / tex - ln_q);
+    const double fracterm = (NFA_CCMS * NFA_CCMS) * L.a_ul[s] / (8 * M_PI * (nu0 * nu0));
+    const double widthterm = NFA_CKMS / (sigm * nu0 * sqrt(2 * M_PI));
+    return pop_upper * fracterm * expm1(NFA_H * nu0 / (NFA_KB * tex)) * widthterm;
+}
+
 //  The sibling models hand c_hf_predict its arguments directly.
 //  N2H+ (diazenylium.pyx:138-154): voff, tex, ltau, sigm -> tau_main = 10**ltau (hyperfine.pyx:63)
 //  Gaussian (gaussian.pyx:17-35): voff, sigm, peak -> one line of weight `peak`, no Tb pass
@@ -401,7 +424,9 @@ __device__ __forceinline__ void derive_simple_lane(const SpecDev &S, const doubl
     const double voff = TH(c);
     const double tex  = gauss ? 1.0 : TH(ncomp + c);
     const double sigm = gauss ? TH(ncomp + c) : TH(3 * ncomp + c);
-    const double amp  = gauss ? TH(2 * ncomp + c) : pow(10.0, TH(2 * ncomp + c));
+    const double amp  = gauss ? TH(2 * ncomp + c)
+                      : S.model == NFA_MODEL_LTE ? derive_lte_lane(S, s, tex, TH(2 * ncomp + c), sigm)
+                      : pow(10.0, TH(2 * ncomp + c));
     if (s == 0) {
         double *d = Db + c * 4;
         d[0] = tex;

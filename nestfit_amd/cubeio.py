@@ -300,7 +300,7 @@ class DataCube:
     anything with its attributes); `noise_map` a number or a noise-map object."""
 
     def __init__(self, cube, noise_map, trans_id=None, lines=None):
-        """lines: the cube's `LineTable` (hyperfine model), the alternative to `trans_id`."""
+        """lines: the cube's `LineTable` (hyperfine model) or `LteLines` (LTE model), the alternative to `trans_id`."""
         if lines is not None:
             from .hyperfine import LineTable
             if trans_id is not None or not isinstance(lines, LineTable):
@@ -472,7 +472,7 @@ class CubeStack:
                                     for dc in self.cubes], axis=1)
         else:
             noise = np.stack([dc.noise_map.values_at(lon, lat) for dc in self.cubes], axis=1)
-        if model == 3:                                               # the hyperfine model: the cubes' line tables
+        if model in (3, 4):                                          # the hyperfine and LTE models: the cubes' line tables
             runner_kwargs = dict(runner_kwargs, lines=[getattr(dc, 'lines', None) for dc in self.cubes])
         runner = CubeRunner([dc.xarr for dc in self.cubes], [dc.trans_id for dc in self.cubes], data, noise,
                             utrans, ncomp=ncomp, model=model, **runner_kwargs)

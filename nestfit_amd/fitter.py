@@ -16,7 +16,7 @@ from . import sampler
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
-_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3}
+_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4}
 
 
 class _RunInfo:

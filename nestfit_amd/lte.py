@@ -1,0 +1,273 @@
+"""One species in local thermodynamic equilibrium across several rotational transitions: column density, excitation
+temperature and a partition function give every transition its own optical depth, so that cubes of, say, the 1-0 and
+3-2 lines of one field are ONE fit per pixel with `N` and `T_ex` as parameters.  Parameters per component,
+parameter-major: voff (km/s), tex (K), lncol = log10 of the total column density (cm^-2), sigm (km/s).
+
+Every spectrum covers one transition, with any hyperfine structure inside it (an `LteLines`: a `LineTable` whose
+weights sum to 1, plus the upper level and the Einstein coefficient); the spectra of a runner share one `Molecule`,
+the partition function on a table of temperatures.  In cgs units, with T0 = h nu / k:
+
+    ln Q(T)  linear in ln T between the bracketing entries of the table; outside it the end segment's line continues
+    N_u      = 10**lncol * g_up * exp(-e_up / tex) / Q(tex)
+    tau_main = N_u * c^2 a_ul / (8 pi nu^2) * expm1(T0 / tex) * CKMS / (sigm * nu * sqrt(2 pi))
+
+`tau_main` is the transition's peak optical depth summed over its lines; line i gets tau_main * tau_wts[i], and the
+spectrum follows as for the hyperfine model (the reference's c_hf_predict, nestfit/models/hyperfine.pyx:52-118).
+
+No molecular data ship with this module: rest frequencies, level energies, Einstein coefficients and the partition
+function come from a catalogue of the user's.
+"""
+import numpy as np
+
+from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, par_names
+from .core import HyperfineSpectrum as _HyperfineBase
+from .hyperfine import CKMS, LineTable
+
+N_PARAMS = 4
+MAX_Q = 64                # NFA_LTE_MAXQ
+H_CGS = 6.62607015e-27    # csrc/nh3_data.h: NFA_H, NFA_KB, NFA_CCMS
+KB_CGS = 1.380649e-16
+CCMS = 29979245800.0
+WEIGHT_SUM_TOL = 1e-6
+
+
+class Molecule:
+    """The partition function of a species: `q_val` at the 2..64 strictly ascending temperatures `q_temp` (K), and a
+    name.  Immutable and compared by value; everything the engine would refuse raises ValueError here."""
+    __slots__ = ('_name', '_q_temp', '_q_val', '_ln_t', '_ln_q', '_slope')
+
+    def __init__(self, name, q_temp, q_val):
+        try:
+            q_temp = np.array(q_temp, dtype=np.float64)
+            q_val = np.array(q_val, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f'a partition table takes numbers: {e}') from None
+        if q_temp.ndim != 1 or q_val.ndim != 1 or q_temp.shape != q_val.shape:
+            raise ValueError(f'q_temp and q_val must be one-dimensional and of one length, not {q_temp.shape} and {q_val.shape}')
+        if not 2 <= q_temp.size <= MAX_Q:
+            raise ValueError(f'a partition table must have 2..{MAX_Q} entries, not {q_temp.size}')
+        if not (np.all(np.isfinite(q_temp)) and np.all(q_temp > 0) and np.all(np.diff(q_temp) > 0)):
+            raise ValueError('the temperatures of a partition table must be finite, positive and strictly ascending')
+        if not (np.all(np.isfinite(q_val)) and np.all(q_val > 0)):
+            raise ValueError('every partition function value must be finite and positive')
+        ln_t, ln_q = np.log(q_temp), np.log(q_val)
+        if not np.all(np.diff(ln_t) > 0):
+            raise ValueError('the temperatures of a partition table must be finite, positive and strictly ascending')
+        slope = np.diff(ln_q) / np.diff(ln_t)
+        for a in (q_temp, q_val, ln_t, ln_q, slope):
+            a.setflags(write=False)
+        for key, value in (('_name', str(name)), ('_q_temp', q_temp), ('_q_val', q_val), ('_ln_t', ln_t),
+                           ('_ln_q', ln_q), ('_slope', slope)):
+            object.__setattr__(self, key, value)
+
+    name = property(lambda self: self._name)
+    q_temp = property(lambda self: self._q_temp)
+    q_val = property(lambda self: self._q_val)
+    n = property(lambda self: int(self._q_temp.size))
+
+    def __setattr__(self, key, value):
+        raise AttributeError('a Molecule is immutable')
+
+    def __delattr__(self, key):
+        raise AttributeError('a Molecule is immutable')
+
+    def __eq__(self, other):
+        if not isinstance(other, Molecule):
+            return NotImplemented
+        return (self.name == other.name and np.array_equal(self.q_temp, other.q_temp)
+                and np.array_equal(self.q_val, other.q_val))
+
+    def __hash__(self):
+        return hash((self.name, self.q_temp.tobytes(), self.q_val.tobytes()))
+
+    def __repr__(self):
+        return f'Molecule({self.name!r}, Q at {self.n} temperatures {self.q_temp[0]:g}..{self.q_temp[-1]:g} K)'
+
+    def ln_partition(self, temp):
+        """ln Q(T): linear in ln T inside the segment that brackets T, the end segments continued outside the table."""
+        ln_temp = np.log(np.asarray(temp, dtype=np.float64))
+        k = np.clip(np.searchsorted(self._ln_t, ln_temp, side='right') - 1, 0, self.n - 2)
+        return self._ln_q[k] + self._slope[k] * (ln_temp - self._ln_t[k])
+
+    def partition(self, temp):
+        """Q(T), the log-log interpolation of the table."""
+        return np.exp(self.ln_partition(temp))
+
+    def transition(self, nu, e_up, g_up, a_ul, voff=(0.0,), tau_wts=(1.0,), name=None, normalise=False):
+        """One transition of this species as an `LteLines`: rest frequency `nu` (Hz), upper-level energy `e_up` (K)
+        and statistical weight `g_up`, Einstein coefficient `a_ul` (1/s), and its hyperfine lines."""
+        return LteLines(self, nu, e_up, g_up, a_ul, voff, tau_wts, name=name, normalise=normalise)
+
+
+class LteLines(LineTable):
+    """The lines of one rotational transition of a `Molecule`: a `LineTable` whose weights sum to 1 (within 1e-6; with
+    `normalise=True` they are divided by their sum), plus `e_up` (K), `g_up` and `a_ul` (1/s).  Immutable."""
+    __slots__ = ('_molecule', '_e_up', '_g_up', '_a_ul')
+
+    def __init__(self, molecule, nu, e_up, g_up, a_ul, voff=(0.0,), tau_wts=(1.0,), name=None, normalise=False):
+        if not isinstance(molecule, Molecule):
+            raise ValueError(f'`molecule` must be a Molecule, not {type(molecule).__name__}')
+        try:
+            e_up, g_up, a_ul = float(e_up), float(g_up), float(a_ul)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f'a transition takes numbers: {e}') from None
+        if not (np.isfinite(e_up) and e_up >= 0):
+            raise ValueError(f'the upper-level energy must be finite and not negative (K), not {e_up}')
+        if not (np.isfinite(g_up) and g_up > 0):
+            raise ValueError(f'the upper-level weight must be finite and positive, not {g_up}')
+        if not (np.isfinite(a_ul) and a_ul > 0):
+            raise ValueError(f'the Einstein coefficient must be finite and positive (1/s), not {a_ul}')
+        if normalise:
+            LineTable.__init__(self, nu, voff, tau_wts, name=name)       # its checks first: a sum that can divide
+            tau_wts = self.tau_wts / self.tau_wts.sum()
+        LineTable.__init__(self, nu, voff, tau_wts, name=name)
+        total = float(self.tau_wts.sum())
+        if not abs(total - 1.0) <= WEIGHT_SUM_TOL:
+            raise ValueError(f'the weights of a transition must sum to 1 within {WEIGHT_SUM_TOL:g} (normalise=True divides '
+                             f'them by their sum), not {total!r}')
+        for key, value in (('_molecule', molecule), ('_e_up', e_up), ('_g_up', g_up), ('_a_ul', a_ul)):
+            object.__setattr__(self, key, value)
+
+    molecule = property(lambda self: self._molecule)
+    e_up = property(lambda self: self._e_up)
+    g_up = property(lambda self: self._g_up)
+    a_ul = property(lambda self: self._a_ul)
+
+    def __setattr__(self, key, value):
+        raise AttributeError('an LteLines is immutable')
+
+    def __delattr__(self, key):
+        raise AttributeError('an LteLines is immutable')
+
+    def __eq__(self, other):
+        """The same numbers in the same order and the same molecule (the transition's name is a label)."""
+        if not isinstance(other, LineTable):
+            return NotImplemented
+        if not isinstance(other, LteLines):
+            return False
+        return (LineTable.__eq__(self, other) and self.e_up == other.e_up and self.g_up == other.g_up
+                and self.a_ul == other.a_ul and self.molecule == other.molecule)
+
+    def __ne__(self, other):
+        r = self.__eq__(other)
+        return r if r is NotImplemented else not r
+
+    def __hash__(self):
+        return hash((LineTable.__hash__(self), self.e_up, self.g_up, self.a_ul, hash(self.molecule)))
+
+    def __repr__(self):
+        return (f'LteLines({self.molecule.name!r}, nu={self.nu!r}, e_up={self.e_up!r}, g_up={self.g_up!r}, '
+                f'a_ul={self.a_ul!r}, {self.n} lines, name={self.name!r})')
+
+    def tau_main(self, tex, lncol, sigm):
+        """The transition's peak optical depth summed over its lines, for `tex` (K), `lncol` (log10 cm^-2) and `sigm`
+        (km/s); numpy, broadcasting."""
+        tex, lncol, sigm = (np.asarray(a, dtype=np.float64) for a in (tex, lncol, sigm))
+        nu = self.nu
+        t0 = H_CGS * nu / KB_CGS
+        pop_upper = 10.0 ** lncol * self.g_up * np.exp(-self.e_up / tex) / self.molecule.partition(tex)
+        fracterm = CCMS * CCMS * self.a_ul / (8 * np.pi * (nu * nu))
+        widthterm = CKMS / (sigm * nu * np.sqrt(2 * np.pi))
+        return pop_upper * fracterm * np.expm1(t0 / tex) * widthterm
+
+
+def check_one_molecule(lines):
+    """The `Molecule` the `LteLines` of a runner share; ValueError if one is no LteLines or they name different ones."""
+    lines = list(lines)
+    if not lines or not all(isinstance(t, LteLines) for t in lines):
+        raise ValueError('the LTE model takes one LteLines per spectrum (Molecule.transition)')
+    if any(t.molecule != lines[0].molecule for t in lines[1:]):
+        raise ValueError('the spectra of an LTE runner share one Molecule (one species, one partition function): '
+                         + ', '.join(sorted({t.molecule.name for t in lines})))
+    return lines[0].molecule
+
+
+class LteSpectrum(EngineSpectrumMixin, _HyperfineBase):
+    """A spectrum of one transition, `lines` (an `LteLines`).
+
+    Parameters
+    ----------
+    xarr : array, Hz, ascending
+    data : array, K
+    noise : number, K; or one value per channel (inf masks a channel)
+    lines : LteLines
+    """
+    MODEL = MODEL_LTE
+
+    def __init__(self, xarr, data, noise, lines):
+        if not isinstance(lines, LteLines):
+            raise ValueError(f'`lines` must be an LteLines, not {type(lines).__name__}')
+        _HyperfineBase.__init__(self, xarr, data, noise, rest_freq=lines.nu)
+        self.lines = lines
+        self._attach(-1, lines=lines)
+
+    @property
+    def tbg_arr(self):
+        return self._ss.tbg()
+
+
+def lte_predict(s, params):
+    """Model spectrum of `s` for parameter-major `params` (voff, tex, lncol, sigm of every component); result in
+    ``s.get_spec()`` / ``s.loglikelihood``."""
+    s._predict(params, N_PARAMS)
+
+
+class LteRunner(EngineRunner):
+    """Prior transform + model + log-likelihood of spectra with an `LteLines` each, all of one `Molecule`."""
+    MODEL = MODEL_LTE
+    N_MODEL = N_PARAMS
+
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None):
+        assert ncomp > 0
+        baseline_order = check_baseline_order(baseline_order)
+        self.spectra = list(spectra)
+        self.molecule = check_one_molecule([s.lines for s in self.spectra])
+        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order)
+
+    @classmethod
+    def from_data(cls, spec_data, utrans, **kwargs):
+        """spec_data: rows [xarr, data, noise, LteLines]."""
+        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
+        spec_data = list(spec_data)
+        check_one_molecule([row[3] for row in spec_data])
+        spectra = np.array([LteSpectrum(*args) for args in spec_data])
+        return cls(spectra, utrans, **kwargs)
+
+    def get_spectra(self):
+        return np.array(self.spectra)
+
+    def predict(self, params):
+        params = self._check_params(params)
+        for s in self.spectra:
+            lte_predict(s, params)
+
+
+# Aliases and metadata at module scope, shaped like hyperfine.py's
+N = N_PARAMS
+IX_VCEN = 0
+IX_SIGM = 3
+NAME = 'lte'
+model_predict = lte_predict
+ModelSpectrum = LteSpectrum
+ModelRunner = LteRunner
+
+PAR_NAMES = ['voff', 'tex', 'lncol', 'sigm']
+PAR_NAMES_SHORT = ['v', 'Tx', 'lN', 's']
+
+TEX_LABELS = [
+    r'$v_\mathrm{lsr}$',
+    r'$T_\mathrm{ex}$',
+    r'$\log(N)$',
+    r'$\sigma_\mathrm{v}$',
+]
+
+TEX_LABELS_WITH_UNITS = [
+    r'$v_\mathrm{lsr} \ [\mathrm{km\, s^{-1}}]$',
+    r'$T_\mathrm{ex} \ [\mathrm{K}]$',
+    r'$\log(N) \ [\mathrm{cm^{-2}}]$',
+    r'$\sigma_\mathrm{v} \ [\mathrm{km\, s^{-1}}]$',
+]
+
+
+def get_par_names(ncomp=None):
+    return par_names(PAR_NAMES_SHORT, ncomp)

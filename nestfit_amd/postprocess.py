@@ -12,7 +12,7 @@ order (..., b, l).
 """
 import numpy as np
 
-_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3}
+_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4}
 N_PDF_BINS = 200                 # edges when `aggregate_run_pdfs` makes its own bins (main.py:905-917)
 PDF_FLOOR = 1e-32                # zero-probability bins before the logarithm (main.py:980)
 PREDICT_ROWS = 4096              # (pixel, component) rows per device batch
@@ -276,8 +276,9 @@ def quantize_conv_marginals(store):
 #  the two steps on the hot path: one model evaluation per (pixel, component)
 # ---------------------------------------------------------------------------------------------
 def check_model_lines(store, stack):
-    """The line tables of the stack's cubes (hyperfine model), after comparing them with the ones the store was fitted
-    with: ValueError where they differ -- map products of other lines than the fit's would be silently wrong."""
+    """The line tables of the stack's cubes (hyperfine and LTE models), after comparing them with the ones the store was
+    fitted with: ValueError where they differ -- map products of other lines than the fit's would be silently wrong.  An
+    `LteLines` compares its transition (e_up, g_up, a_ul) and its molecule's partition table as well."""
     tables = [getattr(dc, 'lines', None) for dc in stack.cubes]
     if any(t is None for t in tables):
         raise ValueError('the store was fitted with the hyperfine model: every cube of the stack needs its LineTable (DataCube(..., lines=))')
@@ -305,7 +306,7 @@ def _device_predictor(store, stack):
     extra = {}
     if model_id == 2:                                    # the Gaussian model has no transition table to take them from
         extra['rest_freqs'] = [float(dc.full_header.get('RESTFRQ', dc.full_header.get('RESTFREQ'))) for dc in stack.cubes]
-    if model_id == 3:                                    # the caller's line tables: the stack's, which must be the store's
+    if model_id in (3, 4):                               # the caller's line tables: the stack's, which must be the store's
         extra['lines'] = check_model_lines(store, stack)
     runner = CubeRunner(xarrs, trans, np.zeros((1, chan_tot)), np.ones((1, len(xarrs))), None, ncomp=1,
                         model=model_id, **extra)
@@ -410,7 +411,7 @@ def create_fits_from_store(store, prefix='source'):
 def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, post_kernel=None,
                     evid_weight=True, predict_backend=None):
     """All steps in the reference's order (main.py:1240-1276)."""
-    if store.hdf.attrs.get('model_name') == 'hyperfine':     # before any product is written
+    if store.hdf.attrs.get('model_name') in ('hyperfine', 'lte'):     # before any product is written
         check_model_lines(store, stack)
     aggregate_run_attributes(store)
     convolve_evidence(store, evid_kernel)

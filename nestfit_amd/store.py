@@ -276,6 +276,7 @@ CHUNK_STEM = 'chunk'
 FILE_SUFFIXES = {'hdf5': '.hdf', 'npz': '.npz'}       # '.hdf' is the reference's (main.py:236)
 PRODUCTS_GROUP = '/products'
 MODEL_LINES_GROUP = '/model_lines'
+MODEL_PARTITION_GROUP = '/model_partition'
 
 # root attribute of the table file  <-  attribute of the CubeFitter          (store_spec.rst:60-63)
 FITTER_ATTRS = (
@@ -436,33 +437,56 @@ class HdfStore:
 
     def insert_model_lines(self, stack):
         """The line table of every cube that has one (hyperfine model) under /model_lines/spec<k>: attributes `nu` and
-        `name`, datasets `voff` and `tau_wts`.  Nothing for the models whose tables ship with the engine."""
+        `name`, datasets `voff` and `tau_wts`.  Nothing for the models whose tables ship with the engine.  The LTE model's
+        `LteLines` add the attributes `e_up`, `g_up` and `a_ul`, and their molecule's partition table goes under
+        /model_partition: datasets `temp` and `q`, attribute `name`."""
         assert self.is_open
         tables = [getattr(dc, 'lines', None) for dc in stack.cubes]
         if all(t is None for t in tables):
             return
-        if MODEL_LINES_GROUP in self.hdf:
-            del self.hdf[MODEL_LINES_GROUP]
+        for old in (MODEL_LINES_GROUP, MODEL_PARTITION_GROUP):
+            if old in self.hdf:
+                del self.hdf[old]
+        if any(t is None for t in tables):
+            raise ValueError('either every cube of a stack has a LineTable or none has')
+        molecule = None
+        if any(hasattr(t, 'molecule') for t in tables):
+            from .lte import check_one_molecule
+            molecule = check_one_molecule(tables)
+            group = self.hdf.require_group(MODEL_PARTITION_GROUP)
+            group.attrs.update(name=molecule.name)
+            group.create_dataset('temp', data=np.array(molecule.q_temp))
+            group.create_dataset('q', data=np.array(molecule.q_val))
         for k, t in enumerate(tables):
-            if t is None:
-                raise ValueError('either every cube of a stack has a LineTable or none has')
             group = self.hdf.require_group(f'{MODEL_LINES_GROUP}/spec{k}')
             group.attrs.update(nu=float(t.nu), name='' if t.name is None else t.name)
+            if molecule is not None:
+                group.attrs.update(e_up=float(t.e_up), g_up=float(t.g_up), a_ul=float(t.a_ul))
             group.create_dataset('voff', data=np.array(t.voff))
             group.create_dataset('tau_wts', data=np.array(t.tau_wts))
 
     def read_model_lines(self):
-        """The `LineTable`s the store was fitted with, in cube order ([] for a store without any)."""
+        """The `LineTable`s the store was fitted with, in cube order ([] for a store without any): `LteLines` of the
+        stored `Molecule` where the store has a partition table."""
         from .hyperfine import LineTable
+        from .lte import Molecule
         assert self.is_open
         if MODEL_LINES_GROUP not in self.hdf:
             return []
         top = self.hdf[MODEL_LINES_GROUP]
+        molecule = None
+        if MODEL_PARTITION_GROUP in self.hdf:
+            part = self.hdf[MODEL_PARTITION_GROUP]
+            molecule = Molecule(part.attrs['name'], np.asarray(part['temp'][...]), np.asarray(part['q'][...]))
         out = []
         for k in range(len(list(top))):
             g = top[f'spec{k}']
-            out.append(LineTable(g.attrs['nu'], np.asarray(g['voff'][...]), np.asarray(g['tau_wts'][...]),
-                                 name=g.attrs.get('name') or None))
+            voff, tau_wts, name = np.asarray(g['voff'][...]), np.asarray(g['tau_wts'][...]), g.attrs.get('name') or None
+            if molecule is not None:
+                out.append(molecule.transition(g.attrs['nu'], g.attrs['e_up'], g.attrs['g_up'], g.attrs['a_ul'],
+                                               voff, tau_wts, name=name))
+            else:
+                out.append(LineTable(g.attrs['nu'], voff, tau_wts, name=name))
         return out
 
     # ---- products -----------------------------------------------------------------------------
