@@ -37,25 +37,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "nfa_launch_plan.h"   // the layout constants (MAXSPEC, SM_*, LNL_PARTS, NFA_BL_NB, NFA_GROUP_MAX) and LnlGeom
 
-#define MAXSPEC   16
 #define MAXCOMP   10          // ResolvedPlacementPrior's own limit (core.pyx:399)
-#define T0_SIZE   1000
-// table layout inside g_tabs (doubles); the LDS copy starts at SM_EXP2
-#define SM_T0X    0
-#define SM_T0Y    1000
-#define NFA_EXP2_N 256        // entries of the polynomial mode's table
-#define SM_EXP2   2000        // 2^(i/256), i = 0..255        (poly)
-// (table; C first, A last: a lane outside the tables' range -- it is given its value by the branch for such
-// arguments -- still forms an address from its exponent bits, up to row 15 of a 10-row table: behind C lies B,
-// behind B lies A, behind A at least SM_TABLE_TAIL doubles of whatever the kernel keeps there)
-#define SM_FEC    (SM_EXP2 + NFA_EXP2_N)   // exp(-j 2^(l-28)) [10][256]
-#define SM_FEB    (SM_FEC + 2560)   // exp(-j 2^(l-20)) [10][256]
-#define SM_FEA    (SM_FEB + 2560)   // exp(-(128+j) 2^(l-12)) [10][128]
-#define SM_END_POLY   (SM_EXP2 + NFA_EXP2_N)
-#define SM_END_TABLE  (SM_FEA + 1280)   // 8432 doubles
-#define SM_TABLE_TAIL 768               // doubles that must follow the staged tables in LDS (row 15 of A ends there)
-
 // Transition indices of every model in one index space: 0..8 NH3 (1,1)..(9,9), 9..11 N2H+ 1-0, 2-1, 3-2, 12 the
 // Gaussian model's single "line" (offset 0, weight 1, rest frequency from the spectrum), 13 a spectrum of the
 // hyperfine model or of the LTE model, whose lines the caller supplies (nfa_specset_create_lines, _create_lte).
@@ -125,7 +109,6 @@ struct SpecDev {
 // of the basis P_0..P_order.  A direction the Cholesky factorisation drops (pivot <= 1e-12 G_kk) and the orders above
 // bl_order have zero rows and columns, so that ||L^-1 e||^2 is the weighted least-squares fit of e over the rest.
 #define NFA_BL_REC 16
-#define NFA_BL_NB  4            // moments every baseline form accumulates: P_0..P_3, whatever the order
 
 // P_1..P_3 of u = (2 j - (N - 1)) / (N - 1), ui = 1 / (N - 1) (0 for N = 1: u = 0); P_0 = 1
 __device__ __forceinline__ void bl_basis(int j, int N, double ui, double &p1, double &p2, double &p3) {
@@ -192,12 +175,6 @@ __host__ __device__ inline int drec_size(int ncomp, int nspec) { return 4 * ncom
 // Up to NFA_GROUP_MAX batches of `each` rows that a caller enqueues one after the other travel as ONE launch (the
 // engine coalesces them, nfa_engine.hip): item b of the launch is row b - c * each of batch c = b / each, and every
 // batch keeps its own pixel, unit-cube and result arrays.
-// (Eight since round 5 -- four before: the table mode's launch of 16384 evaluations spends its last ~80 of ~200 us with
-// fewer and fewer waves per SIMD, profiles/r05/queue_timeline.txt; eight batches in a launch halve that share:
-// 86.3 -> 87.8 M evaluations/s on the metric shape, 26.0 -> 27.2 M on config 4, the fast mode unchanged.)
-#ifndef NFA_GROUP_MAX
-#define NFA_GROUP_MAX 8
-#endif
 struct BatchGroup {
     const int *pix[NFA_GROUP_MAX];
     double    *U[NFA_GROUP_MAX];
@@ -214,23 +191,7 @@ __device__ __forceinline__ int group_of(const BatchGroup &g, long b) {
     return c;
 }
 
-#define LNL_PARTS 4      // row parts of a unit: the fixed shape of its chi^2 sum
 #define NFA_TRACE_WAVES 8192   // waves the queue kernel's trace buffer holds (test library, nfa_test_queue_trace)
-struct LnlGeom {
-    int nhf_max;       // lines per component slot in the LDS line table
-    int wave_doubles;  // LDS doubles per wave
-    unsigned inv_nspec; // floor(2^32 / nspec) + 1: unit / nspec = mulhi(unit, inv_nspec) for unit < 2^28; 0: nspec == 1
-    unsigned inv_nhf;   // floor(2^32 / nhf_max) + 1: p / nhf_max = mulhi(p, inv_nhf) for the few hundred (component, line) slots; 0: nhf_max == 1
-    int split;          // waves that share one (item, spectrum) unit (1, 2, 4), each taking LNL_PARTS / split row parts
-#ifdef NFA_TEST_HOOKS
-    unsigned long long *trace;   // measurement (test library): per wave of the queue kernel 8 records {start, end, unit, position} in 10 ns ticks
-#endif
-    unsigned *queue;    // table mode, split == 1, launches of several units per wave slot (lnl_kernel_queue): the launch's
-                        // chunk counter and, a 128-byte line behind it, its count of workgroups that have left
-                        // (NFA_QUEUE_WORDS words, zero between launches); nullptr: one unit per wave (lnl_kernel)
-    int ablate;        // timing experiments only: 1 skip Tb, 2 skip the line loop, 4 skip rows, 8 skip line set-up
-};
-
 // ---------------------------------------------------------------------------
 //  wave-level helpers
 // ---------------------------------------------------------------------------

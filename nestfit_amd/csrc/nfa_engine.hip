@@ -49,7 +49,7 @@ struct Engine {
     int    exp_mode = 2;             // "fast": see include/nestfit_amd.h, nfa_set_exp_mode
     int    wpb = 1;                  // waves per workgroup of the likelihood kernel (fast / poly mode): one -- a workgroup
                                      // retires, and its slot is refilled, wave by wave (4: -1.5 %, 8: -9 %, profiles/r02/sweep_lanes.txt)
-    int    wpb_table = 0;            // the same in table mode; 0 = chosen per spectra set (table_waves)
+    int    wpb_table = 0;            // the same in table mode; 0 = chosen per spectra set (nfa_launch_plan.h: table_waves)
     int    lnl_split = 0;            // waves per (item, spectrum) unit of the likelihood kernel: 1, 2, 4, or
                                      // 0 = by launch size (resolve_split).  The chi^2 of a unit is a sum of LNL_PARTS
                                      // row blocks in a fixed order whatever the split, so every evaluation is bitwise
@@ -90,7 +90,6 @@ struct Engine {
     double t0_xmin = 0, t0_xmax = 0, t0_inv_dx = 0;
 };
 static Engine g_eng;
-static const size_t LDS_PER_CU = 160 * 1024;      // LDS of a compute unit (gfx950), the most one workgroup can ask for
 struct nfa_runner;
 static int flush_pending(nfa_runner *r);
 static int flush_all_runners();
@@ -212,7 +211,7 @@ struct nfa_runner {
     // numerical mode: -1 = the process default at call time (nfa_set_exp_mode), 0..2 = pinned to
     // this runner (nfa_runner_set_exp_mode): runners of different modes may then work side by side
     int exp_mode = -1;
-    int wpb = 1, wpb_table = 0, lnl_cap = 0, lnl_split = 0;   // launch geometry, taken from the process options at creation
+    LpShape shape = {};              // what the launch plans read of all that, and the launch geometry (nfa_launch_plan.h)
     // Stream lanes: consecutive batches go to different HIP streams (round robin), so the
     // tail of one batch (few workgroups left, SIMDs draining) overlaps the start of the
     // next; inside a lane the set-up kernel and the likelihood kernel run in order and own
@@ -258,6 +257,12 @@ struct nfa_runner {
 #define RUNNER_LOCK(r) std::lock_guard<std::recursive_mutex> runner_lock_((r)->mu)
 // numerical mode of a runner's launches: its own, or the process default at call time
 static int runner_mode(const nfa_runner *r) { return r->exp_mode >= 0 ? r->exp_mode : g_eng.exp_mode; }
+// the inputs of the launch plans: the options as they stand now, and a launch of B items of the runner's set as it is now
+static LpKnobs plan_knobs() { return {g_eng.n_cu, g_eng.setup_ti, g_eng.setup_threads, g_eng.setup_sub, g_eng.lnl_queue, g_eng.lnl_queue_wg, g_eng.coalesce, g_eng.ablate}; }
+static LpLaunch plan_launch(const nfa_runner *r, int64_t B, int mode, bool write_spec, bool has_prior, int slot) {
+    return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl != nullptr,
+                    r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr};
+}
 
 extern "C" {
 
@@ -931,7 +936,11 @@ int nfa_runner_create(nfa_runner **out, nfa_specset *ss, nfa_priors *priors, int
     r->ndim = ss->dev.npar * ncomp;
     r->lanes_auto = g_eng.streams == 0;
     r->n_lanes = r->lanes_auto ? 4 : std::max(1, std::min(g_eng.streams, NFA_MAX_LANES));     // automatic: two more on demand (run_batch)
-    r->wpb = g_eng.wpb; r->wpb_table = g_eng.wpb_table; r->lnl_cap = g_eng.lnl_cap; r->lnl_split = g_eng.lnl_split;
+    static_assert(sizeof(PriorProg) == 3624 && sizeof(LineRec) == 32, "LDS layouts of nfa_launch_plan.h (and of its test)");
+    r->shape = LpShape{ss->dev.n_spec, {}, ss->nhf_max, ncomp, r->ndim, ss->dev.model, priors ? priors->prog.n_stage : 0,
+                       priors ? priors->prog.stage_doubles : 0, g_eng.wpb, g_eng.wpb_table, g_eng.lnl_cap, g_eng.lnl_split,
+                       (int)sizeof(PriorProg), (int)sizeof(LineRec)};
+    std::copy(ss->dev.size, ss->dev.size + MAXSPEC, r->shape.size);
     for (int k = 0; k < r->n_lanes; ++k) HIP_TRY(hipStreamCreateWithFlags(&r->lanes[k], hipStreamNonBlocking));
     r->stream = r->lanes[0];
     { std::lock_guard<std::mutex> lk(g_runners_m); g_runners.push_back(r); }
@@ -1040,29 +1049,6 @@ static int reserve_lane(nfa_runner *r, int slot, int64_t B) {
     return NFA_OK;
 }
 
-// LDS of the set-up stage: exponential tables (`tables`: FastExp's product tables too, setup_uses_tables), theta +
-// partition records + the prior program and `stage_doubles` of its tables
-static bool setup_uses_tables(const nfa_runner *r, int mode) { return mode == 0 && r->ss->dev.model == NFA_MODEL_AMMONIA; }
-static size_t setup_lds_layout(const nfa_runner *r, bool tables, int nsub, int stage_doubles) {
-    const size_t work = (size_t)nsub * ((size_t)64 * r->ndim + (size_t)SETUP_TI * r->ncomp * QREC) + sizeof(PriorProg) / sizeof(double) + 1
-                        + (size_t)stage_doubles;
-    return sizeof(double) * ((tables ? (SM_END_TABLE - SM_EXP2) : NFA_EXP2_N) + work);
-}
-// Whether a launch stages the prior tables the priors were created with.  Whether they fit is only known here: in the
-// table mode, 500-point irdc tables (10 of them staged) and 8 or more components need more than 160 KiB.  Such a launch
-// takes the copy of the program that reads the tables from global memory (nfa_priors::d_prog_global): the same values, so
-// the same bits, as priors created under option prior_stage 0.
-static bool setup_staged(const nfa_runner *r, bool tables, bool has_prior, int nsub) {
-    return has_prior && r->pr->prog.n_stage > 0 && setup_lds_layout(r, tables, nsub, r->pr->prog.stage_doubles) <= LDS_PER_CU;
-}
-static size_t setup_lds_bytes(const nfa_runner *r, bool tables, bool has_prior, int nsub = 1) {
-    return setup_lds_layout(r, tables, nsub, setup_staged(r, tables, has_prior, nsub) ? r->pr->prog.stage_doubles : 0);
-}
-static const PriorProg *setup_prog(const nfa_runner *r, bool tables, bool has_prior, int nsub = 1) {
-    if (!has_prior) return nullptr;
-    return (const PriorProg *)(setup_staged(r, tables, has_prior, nsub) ? r->pr->d_prog : r->pr->d_prog_global);
-}
-
 // Set-up stage of a batch (the arrays travel in r->cur_group) on stream lane `slot`: [unit cube -> theta in place] ->
 // partition sums -> derived records r->d_D[slot], one launch (setup_kernel, nfa_setup.h)
 static int launch_setup(nfa_runner *r, int64_t B, bool has_prior, int slot, int mode) {
@@ -1070,167 +1056,19 @@ static int launch_setup(nfa_runner *r, int64_t B, bool has_prior, int slot, int 
     hipStream_t st = r->lanes[slot];
     int rc = reserve_lane(r, slot, B); if (rc) return rc;
     if (has_prior && !r->pr) return fail(NFA_ERR_STATE, "runner has no priors (predict-only)");
-    // items per workgroup and waves per workgroup (options setup_ti, setup_threads: A/B knobs)
-    const int ti = g_eng.setup_ti > 0 ? g_eng.setup_ti : SETUP_TI;
-    const bool tables = setup_uses_tables(r, mode);
-    // Eight waves per workgroup where the partition sums go through FastExp's tables (52 KB of LDS per workgroup: two per
-    // CU whatever their size, and the sums are eight rounds of a four-wave workgroup): 57.7 -> 48.8 us per 32768 items,
-    // 88.4 -> 90.5 M evaluations/s on the metric shape.  The polynomial's set-up (fast mode) is faster with four
-    // (156.5 against 149.8 M): its workgroups are many per CU (scripts/gpu_setup_shape.sh).
-    int threads = g_eng.setup_threads > 0 ? g_eng.setup_threads : tables ? 2 * SETUP_THREADS : SETUP_THREADS;
-    // ... and two such groups per workgroup behind one copy of the tables (115 KB of LDS for one group: one workgroup per CU
-    // and two rounds of them for 32768 items; 133 KB for two: one round): 48.4 -> see profiles/r05/ab_table_linestep.txt.
-    // Every batch of a group must hold whole workgroups; a launch of ONE batch may have any size (the last workgroup's
-    // second group then has fewer items, or none: the sampler's batches).  Small launches keep one group per workgroup:
-    // they are latency, not rounds.  Two groups only with the prior tables staged (as the priors were created).
-    int nsub = 1;
-    const bool whole = r->cur_group.n <= 1 || (B % (2 * ti) == 0 && r->cur_group.each % (2 * ti) == 0);
-    if (tables && g_eng.setup_threads == 0 && g_eng.setup_sub != 1 && ti == SETUP_TI && whole && B > (int64_t)ti * g_eng.n_cu
-        && setup_lds_layout(r, tables, 2, has_prior ? r->pr->prog.stage_doubles : 0) <= LDS_PER_CU) {
-        nsub = 2;
-        threads = 1024;
-    }
-    const unsigned blocks = (unsigned)((B + (int64_t)ti * nsub - 1) / ((int64_t)ti * nsub));
-    const size_t lds = setup_lds_bytes(r, tables, has_prior, nsub);
-    if (lds > LDS_PER_CU) return fail(NFA_ERR_ARG, "too many parameters for the set-up kernel");
-    const PriorProg *prog = setup_prog(r, tables, has_prior, nsub);
-    auto kern = nsub == 2 ? setup_kernel<0, false, 2> : tables ? setup_kernel<0, false> : mode == 2 ? setup_kernel<1, true> : setup_kernel<1, false>;
-    { int rc2 = ensure_dynamic_lds((const void *)kern, lds); if (rc2) return rc2; }
+    const SetupPlan P = plan_setup(r->shape, plan_knobs(), plan_launch(r, B, mode, false, has_prior, slot));
+    if (P.error) return fail(NFA_ERR_ARG, P.error);
+    const PriorProg *prog = !has_prior ? nullptr : P.staged ? r->pr->d_prog : r->pr->d_prog_global;
+    const auto kern = P.inst == SETUP_TABLE_2 ? setup_kernel<0, false, 2> : P.inst == SETUP_TABLE ? setup_kernel<0, false>
+                    : P.inst == SETUP_FAST ? setup_kernel<1, true> : setup_kernel<1, false>;
+    { int rc2 = ensure_dynamic_lds((const void *)kern, P.lds); if (rc2) return rc2; }
     if (r->ev_cur)      // profiling: the events ride on the dispatch itself -- its own start and stop, as a tracer sees them
-        hipExtLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, st, r->ev_cur[0], r->ev_cur[1], 0, prog, S, r->cur_group, r->d_D[slot], (long)B,
-                              has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, ti);
+        hipExtLaunchKernelGGL(kern, dim3(P.blocks), dim3(P.threads), P.lds, st, r->ev_cur[0], r->ev_cur[1], 0, prog, S, r->cur_group, r->d_D[slot], (long)B,
+                              has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, P.ti);
     else
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, st, prog, S, r->cur_group, r->d_D[slot], (long)B,
-                           has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, ti);
+        hipLaunchKernelGGL(kern, dim3(P.blocks), dim3(P.threads), P.lds, st, prog, S, r->cur_group, r->d_D[slot], (long)B,
+                           has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, P.ti);
     HIP_TRY(hipGetLastError());
-    return NFA_OK;
-}
-
-// the fast mode's narrow form (FastRec records, fp32 window test): at most 26 lines per transition (a 32-bit line
-// mask per component) and channel indices that fp32 holds to the half (nfa_device.h: FastRec)
-static bool lnl_wide(const nfa_runner *r) {
-    int max_size = 0;
-    for (int k = 0; k < r->ss->dev.n_spec; ++k) max_size = std::max(max_size, r->ss->dev.size[k]);
-    return r->ss->nhf_max > 26 || max_size > (1 << 22);
-}
-// LDS doubles per (item, spectrum) unit: the line table (32-byte records, nhf_max per component) followed by the
-// windows (two ints per line)
-static int lnl_wave_doubles(const nfa_runner *r) {
-    const int per_line = (int)(sizeof(LineRec) / sizeof(double)) + 1;
-    return (r->ncomp * r->ss->nhf_max * per_line + 1) & ~1;          // 16-byte records: an even number of doubles
-}
-
-// waves per workgroup of a table-mode launch with one wave per unit: the workgroup stages 51 KB of product tables, so it
-// is made as fat as keeps the most waves resident per CU (ties: more workgroups, so that one stages while another computes)
-static int table_waves(const nfa_runner *r) {
-    if (r->wpb_table > 0) return r->wpb_table;
-    const int n_shared = SM_END_TABLE - SM_EXP2, wave_doubles = lnl_wave_doubles(r);
-    int best = -1, best_blocks = 0, waves = 16;
-    for (int w = 4; w <= 16; w += 2) {
-        const size_t need = sizeof(double) * ((size_t)n_shared + (size_t)wave_doubles * w);
-        const int blocks = (int)(LDS_PER_CU / need);
-        const int resident = std::min(32, blocks * w);
-        if (resident > best || (resident == best && blocks > best_blocks)) { best = resident; best_blocks = blocks; waves = w; }
-    }
-    return waves;
-}
-
-// waves per unit of a launch of B items (runner option lnl_split; 0 = by the size of the launch).  A launch with fewer
-// units than a few per wave slot is latency bound: its waves are placed once and every SIMD waits for its own longest;
-// splitting the rows of a unit over 2 or 4 waves gives the hardware shorter waves to place as slots free up (a single
-// point: 2 units -> 8 waves).
-static int resolve_split(const nfa_runner *r, const SpecDev &S, int64_t B) {
-    int split = r->lnl_split;
-    if (split == 0) {
-        const int64_t slots = (int64_t)g_eng.n_cu * 32;
-        split = 1;
-        while (split < LNL_PARTS && B * S.n_spec * split * 2 <= slots) split *= 2;
-    }
-    int min_rows = 1 << 30;
-    for (int k = 0; k < S.n_spec; ++k) min_rows = std::min(min_rows, (S.size[k] + 63) / 64);
-    while (split > 1 && split > min_rows) split /= 2;
-    return split;
-}
-
-// workgroups of `waves` waves of the table mode that a CU holds at once (LDS: the tables, the waves' line tables, the queue's words)
-static int table_wg_per_cu(const nfa_runner *r, int waves) {
-    const size_t need = sizeof(double) * ((size_t)(SM_END_TABLE - SM_EXP2) + (size_t)lnl_wave_doubles(r) * waves) + 16;
-    return std::max(1, std::min((int)(LDS_PER_CU / need), 32 / waves));
-}
-
-// What of LnlGeom the runner and the size of the launch (B items) decide.  The queue and the test library's trace stay
-// null and the timing switches off: plan_lnl sets them for a batch launch, the fused kernels have none.
-static LnlGeom lnl_geom(const nfa_runner *r, int64_t B) {
-    const SpecDev &S = r->ss->dev;
-    LnlGeom G = {};
-    G.nhf_max = r->ss->nhf_max;
-    G.inv_nspec = S.n_spec == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)S.n_spec) + 1u;
-    G.inv_nhf = G.nhf_max == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)G.nhf_max) + 1u;
-    G.split = resolve_split(r, S, B);
-    G.wave_doubles = lnl_wave_doubles(r);
-    return G;
-}
-
-// ---- the likelihood launch of a batch: which kernel form, how many waves, how much LDS, how many workgroups -----------
-enum LnlForm { LNL_PLAIN, LNL_W8, LNL_QUEUE, LNL_WEIGHTED, LNL_BASELINE };     // lnl_kernel, _w8, _queue, _wt, _bl
-struct LnlPlan { LnlForm form; bool wide; LnlGeom G; int waves; size_t lds; int64_t blocks; };   // waves per workgroup, its dynamic LDS in bytes, workgroups
-
-// Plans the launch for B items of spectra set S in `mode` on stream lane `slot` (the source of the table in DESIGN 4.2).
-// Arithmetic only, no call into the runtime and no allocation: it runs per launch, inside the ~10 us the host spends on
-// enqueueing a step.
-static int plan_lnl(const nfa_runner *r, const SpecDev &S, int64_t B, int mode, bool write_spec, int slot, LnlPlan *out) {
-    const int64_t units = B * S.n_spec;
-    if (units * 8 >= (1LL << 28)) return fail(NFA_ERR_ARG, "batch too large for one launch");
-    const bool table = mode == 0;
-    // table mode: more than 26 lines in a transition (N2H+ 2-1, 3-2): 64-bit line masks, a mask per component;
-    // fast mode: more lines than any NH3 transition (or 2^22 channels): fp64 running sum of tau
-    const bool wide = lnl_wide(r);
-    LnlGeom G = lnl_geom(r, B);
-    G.ablate = g_eng.ablate;
-#ifdef NFA_TEST_HOOKS
-    G.trace = g_eng.d_trace;
-#endif
-    const int split = G.split;
-    // Waves per workgroup: option wpb, made a multiple of the split.  Table mode stages 51 KB of product tables per
-    // workgroup, so the workgroup is made as fat as keeps the most waves resident per CU (table_waves); its split launches take eight.
-    int waves = std::max(1, std::min(r->wpb, 16));
-    waves = std::max(waves, split);
-    waves -= waves % split;
-    if (table) waves = split > 1 ? std::max(8, split) : table_waves(r);
-    const int upw = waves / split;                               // units per workgroup
-    // What the queue form asks of the launch's size: units of eight rows and more (short units -- config 1's 256 channels
-    // are four rows -- finish before the draw has paid: 348 M evaluations/s one unit per wave against 335 M through the
-    // queue), and two units and more per wave of the workgroups that are resident at once.
-    bool long_units = true;
-    for (int k = 0; k < S.n_spec; ++k) if (S.size[k] < 512) long_units = false;
-    const int wg_per_cu = table_wg_per_cu(r, waves);
-    const bool fills_twice = units >= 2 * ((int64_t)g_eng.n_cu * wg_per_cu) * waves;
-    // The form: the first line that applies.
-    LnlForm form = LNL_PLAIN;
-    if (S.bl) form = LNL_BASELINE;                   // every mode, wide, spectra out; such a set is weighted too
-    else if (S.chan_w) form = LNL_WEIGHTED;          // every mode, wide, spectra out: no queue or w8 form of its own (the
-                                                     // units give the same bits whatever the form, so none is instantiated)
-    else if (table && !wide && split == 1            // the queue kernel is table mode, narrow, one wave per unit ...
-             && g_eng.lnl_queue != 0                 // ... unless switched off (option lnl_queue) ...
-             && long_units && fills_twice            // ... pays for launches like these only ...
-             && r->d_queue[slot])                    // ... and needs the lane's counters (reserve_lane)
-        form = LNL_QUEUE;
-    else if (table && write_spec) form = LNL_W8;     // table mode with spectra out asks for 66 registers left alone
-    const bool queue = form == LNL_QUEUE;
-    if (queue) G.queue = r->d_queue[slot];
-    // LDS: [table mode: the product tables][per unit of the workgroup: the line table; split > 1: the parts' sums
-    // (a baseline: and those of the moments of the unit)][queue: the workgroup's queue word and count]
-    const int n_shared = table ? (SM_END_TABLE - SM_EXP2) : 0;
-    const size_t part_doubles = split > 1 ? (size_t)LNL_PARTS * 64 * (form == LNL_BASELINE ? 1 + NFA_BL_NB : 1) : 0;
-    size_t lds = sizeof(double) * ((size_t)n_shared + ((size_t)G.wave_doubles + part_doubles) * upw) + (queue ? 16 : 0);
-    if (table) lds = std::max(lds, sizeof(double) * (size_t)(n_shared + SM_TABLE_TAIL));
-    if (lds > LDS_PER_CU) return fail(NFA_ERR_ARG, "ncomp too large for the LDS line table");
-    if (!table && r->lnl_cap > 0 && waves * r->lnl_cap < 32)         // residency cap: see Engine::lnl_cap
-        lds = std::max(lds, (LDS_PER_CU / r->lnl_cap) & ~(size_t)15);
-    // the queue form: as many workgroups as are resident at once (option lnl_queue_wg: A/B); else one per upw units
-    const int64_t blocks = queue ? (int64_t)g_eng.n_cu * (g_eng.lnl_queue_wg > 0 ? g_eng.lnl_queue_wg : wg_per_cu) : (units + upw - 1) / upw;
-    if (blocks > 0x7fffffffLL) return fail(NFA_ERR_ARG, "batch too large for one launch");
-    *out = LnlPlan{form, wide, G, waves, lds, blocks};
     return NFA_OK;
 }
 
@@ -1262,11 +1100,15 @@ static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, 
 // -- want_lnl, and nobody else sums the parts -- lnL of the items (lnl_sum_kernel)
 static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, int64_t B, int mode) {
     const SpecDev S = runner_specdev(r);
-    LnlPlan P;
-    int rc = plan_lnl(r, S, B, mode, d_spec != nullptr, slot, &P); if (rc) return rc;
+    LnlPlan P = plan_lnl(r->shape, plan_knobs(), plan_launch(r, B, mode, d_spec != nullptr, false, slot));
+    if (P.error) return fail(NFA_ERR_ARG, P.error);
+    if (P.form == LNL_QUEUE) P.G.queue = r->d_queue[slot];
+#ifdef NFA_TEST_HOOKS
+    P.G.trace = g_eng.d_trace;
+#endif
     const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
-    rc = ensure_dynamic_lds((const void *)kern, P.lds); if (rc) return rc;
+    int rc = ensure_dynamic_lds((const void *)kern, P.lds); if (rc) return rc;
     hipStream_t st = r->lanes[slot];
     double *part = want_lnl ? r->d_part[slot] : nullptr;
     if (r->ev_cur) {
@@ -1291,13 +1133,9 @@ static int run_group(nfa_runner *r, const BatchGroup &grp, double *d_spec, bool 
     const int64_t B = (int64_t)grp.each * grp.n;
     int rc0 = engine_init(); if (rc0) return rc0;            // binds the calling thread to the device
     if (!g_eng.have_t0) return fail(NFA_ERR_STATE, "nfa_set_iemtex_table has not been called");
-    // Lanes a sequence of batches rotates over.  Four overlap the draining tail of one batch with the next;
-    // a batch of about one wave per wave slot (the metric's 4096 rows x 2 spectra) leaves the longest tail and
-    // gains another 3 % from six, smaller and larger ones lose with more than four (profiles/r02/sweep_lanes.txt).
     int n_use = r->n_lanes;
     if (r->lanes_auto) {
-        const int64_t units = B * r->ss->dev.n_spec, slots = (int64_t)g_eng.n_cu * 32;
-        n_use = (4 * units >= 3 * slots && 2 * units <= 3 * slots) ? 6 : 4;
+        n_use = lp_lanes(r->shape, plan_knobs(), B);
         // The fifth and sixth stream exist only once a batch of that size has come by: idle streams are not free --
         // with six streams mapped the small launches of a sampler round trip 25 % slower even on the three they use
         // (config 5, one component: 1.25 -> 1.56 s).
@@ -1373,20 +1211,18 @@ extern "C" {
 
 // a device-pointer batch: launched with its neighbours of the same kind and shape, or on its own
 static int enqueue_dev(nfa_runner *r, const int32_t *d_pix, double *d_U, double *d_lnL, double *d_spec, int64_t B, bool has_prior) {
-    const int ti = g_eng.setup_ti > 0 ? g_eng.setup_ti : SETUP_TI;
-    const int64_t units = B * r->ss->dev.n_spec, slots = (int64_t)g_eng.n_cu * 32;
     BatchGroup &p = r->pending;
-    const int group = g_eng.coalesce;                  // read per call: a knob, not part of a runner's identity
-    const bool fits = group > 1 && !r->profiling && B % ti == 0 && 2 * units <= NFA_GROUP_MAX * slots;   // (a group stays below NFA_GROUP_MAX waves per slot)
+    const LpKnobs knobs = plan_knobs();                // read per call: knobs, not part of a runner's identity
+    const bool fits = lp_may_hold(r->shape, knobs, B, r->profiling);
     if (p.n > 0 && (!fits || p.each != (long)B || r->pending_prior != has_prior || (p.pix[0] == nullptr) != (d_pix == nullptr) ||
                     (p.lnL[0] == nullptr) != (d_lnL == nullptr) || (p.spec[0] == nullptr) != (d_spec == nullptr) ||
-                    (int64_t)(p.n + 1) * units > NFA_GROUP_MAX * slots)) {
+                    lp_group_full(r->shape, knobs, p.n, B))) {
         int rc = flush_pending(r); if (rc) return rc;
     }
     if (!fits) return run_batch(r, d_pix, d_U, d_lnL, d_spec, B, has_prior, -1);
     p.pix[p.n] = d_pix; p.U[p.n] = d_U; p.lnL[p.n] = d_lnL; p.spec[p.n] = d_spec; p.each = (long)B; p.n += 1;
     r->pending_prior = has_prior;
-    if (p.n >= group || (int64_t)(p.n + 1) * units > NFA_GROUP_MAX * slots) return flush_pending(r);
+    if (lp_group_full(r->shape, knobs, p.n, B)) return flush_pending(r);
     return NFA_OK;
 }
 
@@ -1459,29 +1295,6 @@ int nfa_runner_synchronize(nfa_runner *r) {
 
 }  // extern "C"
 
-// ---- the fused kernels: point_kernel (nfa_setup.h) and ring_serve_kernel (nfa_ring_serve.h) --------------------------
-// Both run setup_body and lnl_body<MODE, false, false, NCOMP> (narrow, unweighted) in one workgroup of POINT_WAVES waves.
-// Why they cannot serve a runner's points (nullptr: they can; `split`: of a launch of one item), in the words
-// nfa_ring_serve_device fails with; few_points_kernel takes the batch path instead.
-static const char *fused_refusal(const nfa_runner *r, int split) {
-    if (r->ndim > NFA_POINT_MAXDIM || lnl_wide(r)) return "this runner's points go through the batch kernels: use nfa_ring_serve";
-    // (weighted sets, baseline sets among them: lnl_kernel_wt / lnl_kernel_bl.  The unweighted body would compute the unweighted sum.)
-    if (r->ss->dev.bl) return "the resident kernel has no form for a baseline: use nfa_ring_serve";
-    if (r->ss->dev.chan_w) return "the resident kernel has no form for a noise per channel: use nfa_ring_serve";
-    if (split > POINT_WAVES) return "spectra too short for the point kernel's split";
-    return nullptr;
-}
-// LDS of their stages in bytes.  `setup`: the set-up stage's layout with the prior tables it stages, behind the exponential
-// tables -- the kernel stages those itself (table mode: FastExp's product tables whatever the model), so the stage's
-// layout and program (setup_prog) are asked for without them; `tables`: the likelihood's; `units`: line tables and
-// split parts of the POINT_WAVES / split units of a pass.  How the pieces lie in LDS differs: see the two callers.
-struct FusedLds { size_t setup, tables, units; };
-static FusedLds fused_lds(const nfa_runner *r, int mode, const LnlGeom &G) {
-    const size_t n_tables = mode == 0 ? (SM_END_TABLE - SM_EXP2) : 0, n_staged = mode == 0 ? n_tables : NFA_EXP2_N;
-    return FusedLds{setup_lds_bytes(r, false, true) + sizeof(double) * (n_staged - NFA_EXP2_N), sizeof(double) * n_tables,
-                    sizeof(double) * (((size_t)G.wave_doubles + (G.split > 1 ? LNL_PARTS * 64 : 0)) * (POINT_WAVES / G.split))};
-}
-
 // One point, or the few a broker gathered, through the point kernel (nfa_setup.h); returns 1 when the call
 // was served, 0 when another path has to do it, a negative value on a device error.
 #define POINT_HOST_DOUBLES (NFA_POINT_MAXB * (2 * NFA_POINT_MAXDIM + 2) + 8)
@@ -1498,15 +1311,10 @@ static decltype(&point_kernel<MODE, 0>) point_kernel_of(int ncomp) {
 static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, double *lnL, int64_t B) {
     const int ndim = r->ndim;
     if (!g_eng.point || r->profiling || B > NFA_POINT_MAXB) return 0;
-    const LnlGeom G = lnl_geom(r, 1);
-    if (fused_refusal(r, G.split)) return 0;
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
-    const int upw = POINT_WAVES / G.split;                       // units per pass of the workgroup
-    // the set-up stage and the likelihood waves use the same LDS one after the other, behind the staged tables
-    const FusedLds L = fused_lds(r, mode, G);
-    const size_t lds = std::max(L.setup, L.tables + L.units);
-    if (lds > LDS_PER_CU) return 0;
+    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr);
+    if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {
         bool ok = hipHostMalloc((void **)&r->h_point, sizeof(double) * POINT_HOST_DOUBLES, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess
@@ -1528,7 +1336,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     memset(&in, 0, sizeof in);
     in.seq = ++r->pt_seq;
     in.n = (int)B;
-    in.n_blocks = (S.n_spec + upw - 1) / upw;
+    in.n_blocks = P.n_blocks;
     if (B == 1) {
         memcpy(in.u, U, sizeof(double) * ndim);
         in.pix = pix ? pix[0] : -1;
@@ -1542,9 +1350,10 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     *flag = 0;                                                   // the slot holds other data when B changes
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
     const auto kern = mode == 0 ? point_kernel_of<0>(r->ncomp) : point_kernel_of<2>(r->ncomp);
-    (void)ensure_dynamic_lds((const void *)kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)in.n), dim3(POINT_THREADS), lds, r->lanes[0], setup_prog(r, false, true), S, in,
-                       r->d_pix, r->d_U, r->d_D[0], r->d_part[0], r->d_point, r->d_point_done, G,
+    (void)ensure_dynamic_lds((const void *)kern, P.lds_point);
+    hipLaunchKernelGGL(kern, dim3((unsigned)in.n), dim3(POINT_THREADS), P.lds_point, r->lanes[0],
+                       (const PriorProg *)(P.staged ? r->pr->d_prog : r->pr->d_prog_global), S, in,
+                       r->d_pix, r->d_U, r->d_D[0], r->d_part[0], r->d_point, r->d_point_done, P.G,
                        (const double *)g_eng.d_tabs);
     if (hipGetLastError() != hipSuccess) { fail(NFA_ERR_DEVICE, "point kernel launch failed"); return -1; }
     // the kernel's last store is the sequence number; the host reads it straight from the mapped buffer

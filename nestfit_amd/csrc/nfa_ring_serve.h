@@ -189,25 +189,18 @@ int nfa_ring_serve_device(nfa_ring *ring, nfa_runner *run, int lifetime_ms, int 
     RingHeader *h = ring->hdr;
     if (run->ndim != h->ndim) return fail(NFA_ERR_ARG, "ring and runner disagree on ndim");
     if (h->max_points != 1) return fail(NFA_ERR_ARG, "the resident kernel serves one point per slot: use nfa_ring_serve for this ring");
-    const LnlGeom G = lnl_geom(run, 1);
-    if (const char *why = fused_refusal(run, G.split)) return fail(NFA_ERR_ARG, why);
-    if (lifetime_ms <= 0) lifetime_ms = 20;
-    if (lifetime_ms > 1000) lifetime_ms = 1000;
     RUNNER_LOCK(run);
-    { int rc = sync_all_lanes(run); if (rc) return rc; }
     const int mode = runner_mode(run);
     const SpecDev S = runner_specdev(run);
-    const int upw = POINT_WAVES / G.split;
-    // [exponential tables][theta, partition records][prior program + tables: staged once][line tables of the likelihood waves]
-    const FusedLds L = fused_lds(run, mode, G);
-    size_t lds = L.setup + L.units;
-    if (mode == 0) lds = std::max(lds, L.tables + sizeof(double) * SM_TABLE_TAIL);
-    lds = (lds + 15) & ~(size_t)15;
-    const int ctl_double = (int)(lds / sizeof(double));
-    lds += 16;                                                   // the workgroup's control words
-    if (lds > LDS_PER_CU) return fail(NFA_ERR_ARG, "too many parameters for the resident kernel");
+    const FusedPlan P = plan_fused(run->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr);
+    if (P.refusal) return fail(NFA_ERR_ARG, P.refusal);
+    if (lifetime_ms <= 0) lifetime_ms = 20;
+    if (lifetime_ms > 1000) lifetime_ms = 1000;
+    { int rc = sync_all_lanes(run); if (rc) return rc; }
+    if (P.ring_error) return fail(NFA_ERR_ARG, P.ring_error);
+    const PriorProg *prog = P.staged ? run->pr->d_prog : run->pr->d_prog_global;
     const auto kern = mode == 0 ? ring_serve_kernel_of<0>(run->ncomp) : ring_serve_kernel_of<2>(run->ncomp);
-    { int rc = ensure_dynamic_lds((const void *)kern, lds); if (rc) return rc; }
+    { int rc = ensure_dynamic_lds((const void *)kern, P.lds_ring); if (rc) return rc; }
     const int n_wg = std::max(1, std::min(h->n_slots, 64));
     { int rc = runner_reserve(run, n_wg, false); if (rc) return rc; }
     { int rc = reserve_lane(run, 0, n_wg); if (rc) return rc; }
@@ -229,11 +222,11 @@ int nfa_ring_serve_device(nfa_ring *ring, nfa_runner *run, int lifetime_ms, int 
     A.slot0 = sizeof(RingHeader); A.stride = h->slot_stride;
     A.stop_off = (unsigned long long)((unsigned char *)&h->stop - (unsigned char *)h);
     A.n_slots = h->n_slots; A.ndim = h->ndim; A.max_points = h->max_points;
-    A.n_blocks = (S.n_spec + upw - 1) / upw;
+    A.n_blocks = P.n_blocks;
     A.n_pix = run->ss->n_pix; A.has_pix = run->ss->n_pix > 1 ? 1 : 0;
     A.lifetime_ticks = (unsigned long long)lifetime_ms * 100000ull;          // wall_clock64: 100 MHz
     A.counters = d_cnt;
-    A.ctl_double = ctl_double;
+    A.ctl_double = P.ctl_double;
     A.pause = getenv("NFA_RING_PAUSE") ? atoi(getenv("NFA_RING_PAUSE")) : 4;     // ~1 us
     h->n_servers.fetch_add(1, std::memory_order_acq_rel);
     int rc_out = NFA_OK;
@@ -242,8 +235,8 @@ int nfa_ring_serve_device(nfa_ring *ring, nfa_runner *run, int lifetime_ms, int 
     hipStream_t st = run->lanes[0];
     for (;;) {
         if (h->stop.load(std::memory_order_acquire)) break;
-        hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(POINT_THREADS), lds, st, setup_prog(run, false, true), S, A,
-                           run->d_pix, run->d_U, run->d_D[0], run->d_part[0], G, (const double *)g_eng.d_tabs);
+        hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(POINT_THREADS), P.lds_ring, st, prog, S, A,
+                           run->d_pix, run->d_U, run->d_D[0], run->d_part[0], P.G, (const double *)g_eng.d_tabs);
         hipError_t q = hipGetLastError();
         if (q != hipSuccess) { rc_out = fail(NFA_ERR_DEVICE, std::string("launching the resident kernel: ") + hipGetErrorString(q)); break; }
         // while the instance lives: heartbeat, wake-ups for clients asleep on a finished slot

@@ -262,7 +262,6 @@ __global__ void __launch_bounds__(64) prior_items_kernel(const PriorProg *__rest
 //  not run.  Below ~100 K that leaves the first pass -- the sum of a lone item is then ONE exponential deep
 //  (it was seven with eight lanes of seven levels), and a batch runs a quarter of the exponentials.
 // ---------------------------------------------------------------------------
-#define QREC 12
 #define QSUM_LANES 16
 template <int MODE>
 __device__ __forceinline__ void qsum_lane(bool on, double trot_in, int cold, int j0, double *qrec,
@@ -458,8 +457,6 @@ __device__ __forceinline__ void derive_simple_lane(const SpecDev &S, const doubl
 //  stream lanes.
 //  LDS: [exp tables][theta: ndim x 64][Q: 64 x ncomp x QREC][PriorProg copy][staged prior tables]
 // ---------------------------------------------------------------------------
-#define SETUP_TI 64
-#define SETUP_THREADS 256
 // the set-up stage of the 64 items of workgroup `block_id`, by the blockDim.x threads of the workgroup (`sm` =
 // the staged exponential tables, n_shared doubles at the start of smem)
 // STAGED: the prior program and its tables are in LDS already (setup_stage_priors, once per resident workgroup)
@@ -609,10 +606,7 @@ __global__ void __launch_bounds__(512 * NSUB) __attribute__((amdgpu_waves_per_eu
 //  Same device functions as the batch kernels, so a point gives the same bits either way.
 //  Mapped buffer (doubles): [theta out: n x ndim][lnL out: n][sequence number][unit cube in: n x ndim][pixel in: n ints]
 // ---------------------------------------------------------------------------
-#define NFA_POINT_MAXDIM 24
 #define NFA_POINT_MAXB 128
-#define POINT_THREADS 512
-#define POINT_WAVES (POINT_THREADS / 64)
 struct PointIn {
     double u[NFA_POINT_MAXDIM];        // n == 1: the point
     unsigned long long seq;            // written to the host buffer last

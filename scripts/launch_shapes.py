@@ -2,8 +2,8 @@
        python scripts/launch_shapes.py --reduce kernel_trace.csv [...]   the trace of such a run as a list of launches
        python scripts/launch_shapes.py --shapes kernel_trace.csv [...]   that list's checksum and its distinct launches
 
-The first form sends one launch through every branch of the host's launch planning (nfa_engine.hip: plan_lnl,
-launch_setup, few_points_kernel) and prints a checksum of every result array.  It is deterministic -- fixed seeds, one
+The first form sends one launch through every branch of the host's launch planning (nfa_launch_plan.h: plan_lnl,
+plan_setup, plan_fused) and prints a checksum of every result array.  It is deterministic -- fixed seeds, one
 process, no timing, a synchronisation after every launch -- so that two builds of the engine can be compared: run it
 under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/launch_shapes.py` with each, reduce the
 two traces with the second form to (kernel, grid, workgroup, LDS) in dispatch order, and diff the two lists and the two
@@ -188,6 +188,18 @@ def main():
         utg = uniform_priors([(-20, 20), (0.2, 3.0), (0.0, 5.0)])
         gauss = na.GaussianRunner.from_data([x, rng.normal(0, 0.3, 1500), 0.3, nu0], utg, ncomp=3)
         host_calls(f'{mode} gaussian', gauss, (1, 16, 300, 4096), 52, spectra_rows=300)
+        # caller-supplied line tables: a hyperfine set of one line, one of 40 lines (the wide forms), an LTE set of two
+        # transitions -- batches, spectra out and single points each
+        axis = lambda nu, n, v: nu * (1.0 - np.linspace(v, -v, n) / CKMS)
+        rows = lambda tables, n, v: [[axis(t.nu, n, v), rng.normal(0, 0.2, n), 0.2, t] for t in tables]
+        one_line = na.LineTable(115.271202e9, [0.0], [1.0])
+        forty = na.LineTable(N2HP_NU[2], np.linspace(-19.5, 19.5, 40), np.linspace(0.5, 1.5, 40) / 40)
+        mol = na.Molecule('rotor', [5.0, 10.0, 20.0, 40.0, 80.0], [2.2, 4.1, 7.9, 15.5, 30.7])
+        lte = [na.LteLines(mol, 110.201354e9, 5.29, 3, 6.3e-8), na.LteLines(mol, 220.398684e9, 15.87, 5, 6.0e-7, voff=[-0.8, 0.0, 0.9], tau_wts=[0.2, 0.5, 0.3])]
+        utl = uniform_priors([(-6, 6), (2.8, 20), (12.0, 14.0), (0.1, 1.5)])
+        host_calls(f'{mode} hyperfine 1 line', na.HyperfineRunner.from_data(rows([one_line], 700, 20), ut, ncomp=2), (1, 16, 300, 4096), 53, spectra_rows=300)
+        host_calls(f'{mode} hyperfine 40 lines', na.HyperfineRunner.from_data(rows([forty], 1024, 45), ut, ncomp=2), (1, 16, 300, 4096), 54, spectra_rows=300)
+        host_calls(f'{mode} lte 2 transitions', na.LteRunner.from_data(rows(lte, 800, 20), utl, ncomp=2), (1, 16, 300, 4096), 55, spectra_rows=300)
         # weighted sets and baselines: the split parts' LDS differs with a baseline
         for what, kw in (('channel noise', dict(chan_noise=True)), ('baseline 1', dict(baseline_order=1)),
                          ('channel noise, baseline 3', dict(chan_noise=True, baseline_order=3))):

@@ -5,7 +5,7 @@ array and lnL array (and spectra), all of one kind inside ONE allocation between
 for bit unchanged; every batch must give the host-pointer call's bits (that call runs each batch alone) and the CPU
 oracle's values to the parity tolerances (test_gpu_parity.py).
 
-The paths named in the comments are those of a 256-CU MI355X (engine: plan_lnl, launch_setup);
+The paths named in the comments are those of a 256-CU MI355X (nfa_launch_plan.h: plan_lnl, plan_setup);
 test_the_queue_kernel_runs_for_every_batch_of_the_group proves the queue ones with the test library's trace."""
 import contextlib
 import json

@@ -2,7 +2,7 @@
 against each other bit for bit.  Counts 1-3 are compiled with the component loop unrolled; every other count takes the
 general form (NCOMP == 0) of the likelihood, point and queue kernels.  In the table mode the set-up stage of a runner
 with 500-point irdc tables needs more than 160 KiB of LDS from 8 components on, and reads its prior tables from global
-memory there (nfa_engine.hip: setup_staged).
+memory there (nfa_launch_plan.h: setup_staged).
 
 Safety: at high counts the minimum separations of the placement prior overflow a narrow velocity axis and the
 reference's draw is an artefact (NaN centroids among them).  Every unit-cube row is screened on the CPU with the closed
