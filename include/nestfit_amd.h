@@ -86,6 +86,9 @@ int nfa_get_exp_mode(void);
  *                   the set-up kernel: A/B knobs, see DESIGN.md;
  *   "setup_sub"     1: one group of 64 items per set-up workgroup in the table mode; 0 (default): two groups behind one
  *                   copy of the tables where every batch of the launch is a multiple of 128 rows;
+ *   "setup_overlap" 1 (default) / 0: the set-up stage runs a resolved prior's velocities (placement, centre and
+ *                   separation) beside the partition sums and the derived records where the prior program allows it,
+ *                   or every phase after the other; the same bits either way (A/B knob, read when a launch is made);
  *   "point"         1 / 0: single points and small batches (nfa_runner_loglike_batch with B <= 128,
  *                   nfa_loglike_callback) go through the one-launch point kernel (default: one workgroup per
  *                   point, the result written to a mapped host buffer) or through the batch kernels;

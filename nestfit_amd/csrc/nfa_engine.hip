@@ -83,6 +83,7 @@ struct Engine {
                                      // this many (1 = every batch its own launches)
     int    prior_stage = 1;          // prior tables staged in LDS by the set-up kernel (priors created afterwards)
     int    setup_ti = 0, setup_threads = 0;   // set-up kernel: items and threads per workgroup (0 = 64 / 256)
+    int    setup_overlap = 1;                 // set-up stage: a resolved prior's velocities beside the sums and records (0: in sequence, A/B)
     int    setup_sub = 0;                     // table mode: 1 = one group of items per set-up workgroup (0 = two where the batch allows)
     int    point = 1;                // single points: 1 = the one-launch point kernel, 0 = the batch kernels (graph replay)
     bool   have_t0 = false;
@@ -327,6 +328,7 @@ int nfa_set_option(const char *key, int value) {
     if (key && !strcmp(key, "coalesce") && value >= 1 && value <= NFA_GROUP_MAX) { g_eng.coalesce = value; return NFA_OK; }
     if (key && !strcmp(key, "prior_stage") && (value == 0 || value == 1)) { g_eng.prior_stage = value; return NFA_OK; }
     if (key && !strcmp(key, "setup_ti") && (value == 0 || value == 8 || value == 16 || value == 32 || value == 64)) { g_eng.setup_ti = value; return NFA_OK; }
+    if (key && !strcmp(key, "setup_overlap") && (value == 0 || value == 1)) { g_eng.setup_overlap = value; return NFA_OK; }
     if (key && !strcmp(key, "setup_sub") && (value == 0 || value == 1)) { g_eng.setup_sub = value; return NFA_OK; }
     if (key && !strcmp(key, "setup_threads") && (value == 0 || value == 256 || value == 320 || value == 384 || value == 448 || value == 512)) { g_eng.setup_threads = value; return NFA_OK; }
     if (key && !strcmp(key, "sampler_parts") && value >= 1 && value <= 4) { g_eng.sampler_parts = value; return NFA_OK; }
@@ -864,6 +866,21 @@ static int priors_fill(nfa_priors *p, const nfa_prior_desc *priors, int n_prior,
             seen |= mine;
         }
     }
+    // The set-up stage may run ONE resolved prior's part B (its velocities: prior_apply_lane) beside the partition sums and
+    // the derived records, if those read nothing that part B writes: the program is parallel, the prior's main slot is 0
+    // (the velocity, which enters a record only as d[2], written last) and its sub-prior's is not.  Parallel leaves no
+    // second prior on slot 0, so every other slot is complete before part B starts.  Anything else: the phases in sequence.
+    {
+        int n_b = 0, k_b = -1;
+        bool ok = g.parallel != 0;
+        for (int k = 0; k < n_prior; ++k) {
+            const nfa_prior_desc &q = priors[k];
+            if (q.kind != NFA_PRIOR_RESOLVED_CENSEP && q.kind != NFA_PRIOR_RESOLVED_PLACEMENT) continue;
+            n_b += 1; k_b = k;
+            if (q.p_ix != 0 || q.p_ix2 <= 0) ok = false;
+        }
+        g.overlap_k = ok && n_b == 1 ? k_b + 1 : 0;
+    }
     HIP_TRY(hipMalloc(&p->d_prog, sizeof(PriorProg)));
     HIP_TRY(hipMemcpy(p->d_prog, &p->prog, sizeof(PriorProg), hipMemcpyHostToDevice));
     if (g.n_stage == 0) { p->d_prog_global = p->d_prog; return NFA_OK; }
@@ -1064,10 +1081,10 @@ static int launch_setup(nfa_runner *r, int64_t B, bool has_prior, int slot, int 
     { int rc2 = ensure_dynamic_lds((const void *)kern, P.lds); if (rc2) return rc2; }
     if (r->ev_cur)      // profiling: the events ride on the dispatch itself -- its own start and stop, as a tracer sees them
         hipExtLaunchKernelGGL(kern, dim3(P.blocks), dim3(P.threads), P.lds, st, r->ev_cur[0], r->ev_cur[1], 0, prog, S, r->cur_group, r->d_D[slot], (long)B,
-                              has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, P.ti);
+                              has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, P.ti, g_eng.setup_overlap);
     else
         hipLaunchKernelGGL(kern, dim3(P.blocks), dim3(P.threads), P.lds, st, prog, S, r->cur_group, r->d_D[slot], (long)B,
-                           has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, P.ti);
+                           has_prior ? 1 : 0, (const double *)g_eng.d_tabs, g_eng.ablate, P.ti, g_eng.setup_overlap);
     HIP_TRY(hipGetLastError());
     return NFA_OK;
 }
@@ -1337,6 +1354,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     in.seq = ++r->pt_seq;
     in.n = (int)B;
     in.n_blocks = P.n_blocks;
+    in.overlap = g_eng.setup_overlap;
     if (B == 1) {
         memcpy(in.u, U, sizeof(double) * ndim);
         in.pix = pix ? pix[0] : -1;

@@ -28,6 +28,7 @@ struct RingServeArgs {
     unsigned long long *counters;        // device: [0] points served, [1] requests refused (bad pixel)
     int ctl_double;                      // index of the workgroup's control words inside its dynamic LDS
     int pause;                           // s_sleep(8) units (~0.2 us each) the workgroup sleeps after an empty turn
+    int overlap;                         // option setup_overlap as it stood when the instance was launched (setup_body)
 };
 
 // field offsets inside a RingSlot (nfa_ring.h): state, owner, asleep, gen, pix, rc, n_points, pad, data[]
@@ -134,7 +135,7 @@ __global__ void __launch_bounds__(POINT_THREADS) ring_serve_kernel(const PriorPr
         if (!bad) {
             if (tid == 0 && A.has_pix) d_pix[wg] = my_pix;
             __syncthreads();                                    // (the unit cube wave 0 wrote to U: the barrier's workgroup-scope release)
-            setup_body<SMODE, MODE == 2, 1, true>(ppp, S, U, D, 1, 1, g_tabs, 0, smem, sm, n_shared, 0u);
+            setup_body<SMODE, MODE == 2, 1, true>(ppp, S, U, D, 1, 1, g_tabs, 0, smem, sm, n_shared, 0u, A.overlap);
             __threadfence();                                    // theta in U, the derived record in D: at L2, stale lines of the last point gone
             __syncthreads();
             __builtin_amdgcn_s_dcache_inv();
@@ -228,6 +229,7 @@ int nfa_ring_serve_device(nfa_ring *ring, nfa_runner *run, int lifetime_ms, int 
     A.counters = d_cnt;
     A.ctl_double = P.ctl_double;
     A.pause = getenv("NFA_RING_PAUSE") ? atoi(getenv("NFA_RING_PAUSE")) : 4;     // ~1 us
+    A.overlap = g_eng.setup_overlap;
     h->n_servers.fetch_add(1, std::memory_order_acq_rel);
     int rc_out = NFA_OK;
     unsigned long long served_before = 0, h_cnt[2] = {0, 0};

@@ -12,7 +12,8 @@
 //   * partition sums: lane = (item, component, quarter of the 51 J levels), the four partial
 //                     sums meet through two DPP quad permutes;
 //   * derive:         lane = (item, component, spectrum).
-// theta and the partition sums pass from phase to phase through the wave's LDS.
+// theta and the partition sums pass from phase to phase through the wave's LDS.  The velocities of a resolved prior
+// (placement; centre and separation) run beside the sums and records where the program allows it: setup_body.
 // (prior_items_kernel = the first phase alone, for PriorTransformer.transform.)
 #pragma once
 
@@ -40,7 +41,9 @@ struct PriorProg {
     nfa_prior_desc pr[MAXPRIOR];
     DistDev        ds[MAXDIST];
     int            n_stage, stage_doubles;          // 0: the tables stay in global memory
-    int            parallel, pad;                   // 1: no two priors share a parameter slot (one wave each)
+    int            parallel;                        // 1: no two priors share a parameter slot (one wave each)
+    int            overlap_k;                       // k + 1 of the one resolved prior whose part B may run beside the sums and
+                                                    // records (setup_body; priors_fill decides), 0: none, the phases in sequence
     const double  *stage_image;                     // the staged tables back to back, in LDS order
     StageItem      stage[MAXSTAGE];
 };
@@ -147,12 +150,16 @@ __device__ double d_placement_draw(const DistDev &d, double x_lo, double x_hi, d
 }
 
 // prior k of PriorTransformer.c_transform (core.pyx:459-476) for the item of this lane
+// part: the resolved kinds come in two parts, A their sub-prior (the widths, `p_ix2`) and B the rest (the velocities, `p_ix`);
+// PRIOR_PART_A runs every other kind whole and a resolved one up to the end of A, PRIOR_PART_B the B of a resolved one.
+// A then B of one prior are the operations of PRIOR_ALL on the same operands in the same order: theta keeps its bits.
 // (Inlined into its kernels since round 5: as a function of its own it was compiled to 248 vector registers -- a callee
 // has no occupancy to aim for -- and every kernel that calls it is allotted its callees' maximum: the set-up kernel ran
 // two waves per SIMD for a body that needs 165.  Inlined: three waves, and the launch stands less in the way of the
 // likelihood launches of the neighbouring lanes -- 152.7 -> 157.4 M evaluations/s on the metric shape in the fast mode,
 // config 5 (rounds 2-4's cube) 3.41 -> 3.38 s.  Held to 128 registers (four waves) it gains nothing more.)
-__device__ __forceinline__ void prior_apply_lane(const PriorProg &pp, int k, double *u, int n) {
+enum { PRIOR_ALL = 0, PRIOR_PART_A = 1, PRIOR_PART_B = 2 };
+__device__ __forceinline__ void prior_apply_lane(const PriorProg &pp, int k, double *u, int n, int part = PRIOR_ALL) {
     {
         const nfa_prior_desc &p = pp.pr[k];
         const int ix = p.p_ix * n;
@@ -188,7 +195,8 @@ __device__ __forceinline__ void prior_apply_lane(const PriorProg &pp, int k, dou
         } break;
         case NFA_PRIOR_RESOLVED_CENSEP: {                     // core.pyx:347-366
             const int ix_s = p.p_ix2 * n;
-            d_simple_interp(pp, p.sub_kind, p.dist2, p.p_ix2, p.value, u, n);
+            if (part != PRIOR_PART_B) d_simple_interp(pp, p.sub_kind, p.dist2, p.p_ix2, p.value, u, n);
+            if (part == PRIOR_PART_A) break;
             const double vcen = d_ppf_interp(pp.ds[p.dist0], TH(ix));
             if (n == 1) TH(ix) = vcen;
             else if (n == 2) {
@@ -204,7 +212,8 @@ __device__ __forceinline__ void prior_apply_lane(const PriorProg &pp, int k, dou
             const DistDev &vd = pp.ds[p.dist0];
             const int ix_s = p.p_ix2 * n;
             double v_lo = vd.xmin, v_hi = vd.xmax;
-            d_simple_interp(pp, p.sub_kind, p.dist2, p.p_ix2, p.value, u, n);
+            if (part != PRIOR_PART_B) d_simple_interp(pp, p.sub_kind, p.dist2, p.p_ix2, p.value, u, n);
+            if (part == PRIOR_PART_A) break;
             if (n == 1) { TH(ix) = d_ppf_interp(vd, TH(ix)); break; }
             double sep_tot = 0.0;                             // core.pyx:409-415
             for (int i = 1; i < n; ++i) sep_tot += p.sep_scale * sqrt(TH(ix_s + i) * TH(ix_s + i - 1));
@@ -355,7 +364,7 @@ __device__ __forceinline__ void write_y_model(double *dk, const SpecDev &S, int 
 // that the exact modes make as well.
 template <bool FAST>
 __device__ __forceinline__ void derive_lane(const SpecDev &S, const double *th, const double *qrec, double *Db,
-                                            int c, int s, const double *__restrict__ g_tabs) {
+                                            int c, int s, const double *__restrict__ g_tabs, bool with_v = true) {
     const int ncomp = S.ncomp, nspec = S.n_spec;
     const int t = S.trans[s] - 1;
     const double nu0 = c_nu[t];
@@ -381,7 +390,7 @@ __device__ __forceinline__ void derive_lane(const SpecDev &S, const double *th, 
         double *d = Db + c * 4;
         d[0] = tex;
         d[1] = sigm / NFA_CKMS;                               // hyperfine.pyx:72
-        d[2] = TH(c) / NFA_CKMS;                              // hyperfine.pyx:73
+        if (with_v) d[2] = TH(c) / NFA_CKMS;                  // hyperfine.pyx:73 (setup_body's overlapped flow writes it last)
         d[3] = 1.0 / tex;
     }
     double *dk = Db + 4 * ncomp + (c * nspec + s) * DREC_CS;
@@ -417,10 +426,9 @@ __device__ __forceinline__ double derive_lte_lane(const SpecDev &S, int s, doubl
 //  Gaussian (gaussian.pyx:17-35): voff, sigm, peak -> one line of weight `peak`, no Tb pass
 template <bool FAST>
 __device__ __forceinline__ void derive_simple_lane(const SpecDev &S, const double *th, double *Db, int c, int s,
-                                                   const double *__restrict__ g_tabs) {
+                                                   const double *__restrict__ g_tabs, bool with_v = true) {
     const int ncomp = S.ncomp, nspec = S.n_spec;
     const bool gauss = S.model == NFA_MODEL_GAUSSIAN;
-    const double voff = TH(c);
     const double tex  = gauss ? 1.0 : TH(ncomp + c);
     const double sigm = gauss ? TH(ncomp + c) : TH(3 * ncomp + c);
     const double amp  = gauss ? TH(2 * ncomp + c)
@@ -430,7 +438,7 @@ __device__ __forceinline__ void derive_simple_lane(const SpecDev &S, const doubl
         double *d = Db + c * 4;
         d[0] = tex;
         d[1] = sigm / NFA_CKMS;
-        d[2] = voff / NFA_CKMS;
+        if (with_v) d[2] = TH(c) / NFA_CKMS;
         d[3] = 1.0 / tex;
     }
     double *dk = Db + 4 * ncomp + (c * nspec + s) * DREC_CS;
@@ -455,16 +463,28 @@ __device__ __forceinline__ void derive_simple_lane(const SpecDev &S, const doubl
 //  work, set the pace of a 4096-row batch).  The waves raise their priority: there are few of
 //  them, each a long dependent chain, beside thousands of likelihood waves of the neighbouring
 //  stream lanes.
+//  The phases need not follow each other: the one long chain of the stage is the second part of a resolved prior (the
+//  placement of the velocities, a bisection per component), and the sums and records read no velocity -- it enters a
+//  record only as d[2] = voff / c.  Where the prior program allows it (PriorProg::overlap_k, decided by priors_fill) and
+//  option setup_overlap is on, the flow of a group of items is therefore
+//      one wave per prior                   the priors, a resolved one only its sub-prior (the widths)  | barrier
+//      the resolved prior's wave            the rest of that prior: the velocities                      |
+//      every other wave, a run of pairs     partition sums, wave-local hand-over, derived records       | barrier
+//      all threads                          d[2] of the records, theta -> U
+//  with the operations of the flow in sequence on the same operands: the same bits.  Every wave of the workgroup passes
+//  the same barriers on either flow, whatever its group holds (the conditions are the launch's, not the group's).
 //  LDS: [exp tables][theta: ndim x 64][Q: 64 x ncomp x QREC][PriorProg copy][staged prior tables]
 // ---------------------------------------------------------------------------
 // the set-up stage of the 64 items of workgroup `block_id`, by the blockDim.x threads of the workgroup (`sm` =
 // the staged exponential tables, n_shared doubles at the start of smem)
 // STAGED: the prior program and its tables are in LDS already (setup_stage_priors, once per resident workgroup)
+// overlap: option setup_overlap (the same for every thread of the workgroup)
 template <int MODE, bool FAST = false, int NSUB = 1, bool STAGED = false>
 __device__ __forceinline__ void setup_body(const PriorProg *__restrict__ ppp, const SpecDev &S,
                                            double *__restrict__ U, double *__restrict__ D, long B, int has_prior,
                                            const double *__restrict__ g_tabs, int ablate_in, double *smem,
-                                           const double *sm, int n_shared, unsigned block_id, int ti = SETUP_TI) {
+                                           const double *sm, int n_shared, unsigned block_id, int overlap,
+                                           int ti = SETUP_TI) {
     constexpr int nsub = NSUB;
 #ifdef NFA_ABLATE
     const int ablate = ablate_in;      // timing experiments: 16 skip the priors, 32 the partition sums, 64 the derive phase
@@ -512,43 +532,73 @@ __device__ __forceinline__ void setup_body(const PriorProg *__restrict__ ppp, co
     }
     // ---- phase 1: lanes = items (core.pyx:459-476); priors that share no parameter slot take a wave each
     // (a wave interprets ONE prior for its 64 items: no divergence, and the longest prior sets the time)
+    const int lane = tid & 63, wave = tid >> 6, n_waves = nthr >> 6;
+    // the overlapped flow (option setup_overlap, and a program that allows it: PriorProg::overlap_k); the same for every
+    // thread of the workgroup, as every condition a barrier stands behind
+    const int kb = __builtin_amdgcn_readfirstlane(do_prior && overlap && n_waves > 1 ? lp->overlap_k - 1 : -1);
     if (do_prior) {
-        const int lane = tid & 63, wave = tid >> 6, n_waves = nthr >> 6;
         if (lp->parallel) {
             for (int k = wave; k < lp->n_prior; k += n_waves)
-                if (lane < n_it) prior_apply_lane(*lp, k, th_all + lane, ncomp);
+                if (lane < n_it) prior_apply_lane(*lp, k, th_all + lane, ncomp, kb >= 0 ? PRIOR_PART_A : PRIOR_ALL);
         } else if (tid < n_it) {
             prior_transform_lane(*lp, th_all + tid, ncomp);
         }
     }
     __syncthreads();
-    if (do_prior)
+    const bool ammonia = S.model == NFA_MODEL_AMMONIA;
+    // Phases 2 and 3 walk a run of (item, component) pairs -- `n_pair` of them from `pair0` on -- with `step` threads, of
+    // which this one is number `t`.  In sequence: all pairs of the group, all its threads, the workgroup meets in between.
+    int t = tid, step = nthr, pair0 = 0, n_pair = n_it * ncomp;
+    if (kb >= 0) {
+        // Overlapped: the wave that interpreted prior kb goes on with its part B (the long chain of the stage: it writes
+        // slot 0, the velocities, and nothing else) and has no pairs; every other wave takes a run of pairs of its own
+        // through the partition sums AND the derived records, which read every slot but 0.  The Q records of a wave's
+        // pairs pass wave-locally, and the workgroup meets once, at the end.
+        const int wv = __builtin_amdgcn_readfirstlane(wave);    // (the compiler does not know that it is the wave's)
+        const int wb = kb % n_waves;
+        const int each = (n_pair + n_waves - 2) / (n_waves - 1);
+        t = lane; step = 64;
+        pair0 = (wv - (wv > wb ? 1 : 0)) * each;
+        n_pair = wv == wb ? 0 : n_pair - pair0 < each ? (n_pair - pair0 > 0 ? n_pair - pair0 : 0) : each;
+        if (wv == wb && lane < n_it) prior_apply_lane(*lp, kb, th_all + lane, ncomp, PRIOR_PART_B);
+    } else if (do_prior) {
         for (int q = tid; q < n_it * ndim; q += nthr) {
             const int it = q / ndim, k = q - it * ndim;
             U[b0 * ndim + q] = th_all[k * 64 + it];
         }
-    const bool ammonia = S.model == NFA_MODEL_AMMONIA;
+    }
     // ---- phase 2: lanes = (item, component, J mod 16)
     if (ammonia && !(ablate & 32)) {
-        const int n_task = n_it * ncomp * QSUM_LANES;           // whole groups of sixteen are on or off
-        for (int q0 = 0; q0 < n_task; q0 += nthr) {
-            const int q = q0 + tid;
-            const int pair = q / QSUM_LANES, chunk = q % QSUM_LANES;
+        const int n_task = n_pair * QSUM_LANES;                 // whole groups of sixteen are on or off
+        for (int q0 = 0; q0 < n_task; q0 += step) {
+            const int q = q0 + t;
+            const int pair = pair0 + q / QSUM_LANES, chunk = q % QSUM_LANES;
             const int it = pair / ncomp, c = pair - it * ncomp;
             const bool on = q < n_task;
             const double trot = on ? th_all[(ncomp + c) * 64 + it] : 1.0;
             qsum_lane<MODE>(on, trot, S.cold, chunk, q_all + (on ? pair : 0) * QREC, sm);
         }
     }
-    __syncthreads();
+    if (kb >= 0) wave_lds_sync(); else __syncthreads();
     // ---- phase 3: lanes = (item, component, spectrum)
-    const int per_item = ncomp * nspec;
-    for (int q = tid; q < n_it * per_item && !(ablate & 64); q += nthr) {
-        const int it = q / per_item, k = q - it * per_item;
-        const int c = k / nspec, s = k - c * nspec;
+    for (int q = t; q < n_pair * nspec && !(ablate & 64); q += step) {
+        const int pair = pair0 + q / nspec, s = q % nspec;
+        const int it = pair / ncomp, c = pair - it * ncomp;
         double *Db = D + (b0 + it) * drec;
-        if (ammonia) derive_lane<FAST>(S, th_all + it, q_all + (it * ncomp + c) * QREC, Db, c, s, g_tabs);
-        else derive_simple_lane<FAST>(S, th_all + it, Db, c, s, g_tabs);
+        if (ammonia) derive_lane<FAST>(S, th_all + it, q_all + pair * QREC, Db, c, s, g_tabs, kb < 0);
+        else derive_simple_lane<FAST>(S, th_all + it, Db, c, s, g_tabs, kb < 0);
+    }
+    if (kb >= 0) {
+        // ---- the velocities are there: into the records (hyperfine.pyx:73), and theta back to U
+        __syncthreads();
+        for (int q = tid; q < n_it * ncomp && !(ablate & 64); q += nthr) {
+            const int it = q / ncomp, c = q - it * ncomp;
+            D[(b0 + it) * drec + c * 4 + 2] = th_all[c * 64 + it] / NFA_CKMS;
+        }
+        for (int q = tid; q < n_it * ndim; q += nthr) {
+            const int it = q / ndim, k = q - it * ndim;
+            U[b0 * ndim + q] = th_all[k * 64 + it];
+        }
     }
 }
 
@@ -584,7 +634,7 @@ template <int MODE, bool FAST = false, int NSUB = 1>
 __global__ void __launch_bounds__(512 * NSUB) __attribute__((amdgpu_waves_per_eu(3))) setup_kernel(const PriorProg *__restrict__ ppp, SpecDev S,
                                                     BatchGroup grp, double *__restrict__ D,
                                                     long B, int has_prior,
-                                                    const double *__restrict__ g_tabs, int ablate_in, int ti) {
+                                                    const double *__restrict__ g_tabs, int ablate_in, int ti, int overlap) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     // the workgroup's items belong to one batch of the group (the host sees to it that `each` is a multiple of ti):
     // its unit-cube array, shifted so that the body can go on indexing it with the item's number in the launch
@@ -593,7 +643,7 @@ __global__ void __launch_bounds__(512 * NSUB) __attribute__((amdgpu_waves_per_eu
     __builtin_amdgcn_s_setprio(3);
     int n_shared;
     const double *sm = stage_exp_tables<MODE>(smem, g_tabs, &n_shared);
-    setup_body<MODE, FAST, NSUB>(ppp, S, U, D, B, has_prior, g_tabs, ablate_in, smem, sm, n_shared, blockIdx.x, ti);
+    setup_body<MODE, FAST, NSUB>(ppp, S, U, D, B, has_prior, g_tabs, ablate_in, smem, sm, n_shared, blockIdx.x, overlap, ti);
 }
 
 // ---------------------------------------------------------------------------
@@ -613,7 +663,7 @@ struct PointIn {
     int n;                             // points of this launch = workgroups
     int pix;                           // n == 1: its pixel (< 0: the runner has one pixel); n > 1: pixels given or not
     int n_blocks;                      // likelihood workgroups the one workgroup stands in for
-    int pad;
+    int overlap;                       // option setup_overlap (setup_body)
 };
 template <int MODE, int NCOMP>
 __global__ void __launch_bounds__(POINT_THREADS) point_kernel(const PriorProg *__restrict__ ppp, SpecDev S, PointIn in,
@@ -645,7 +695,7 @@ __global__ void __launch_bounds__(POINT_THREADS) point_kernel(const PriorProg *_
     }
     if (tid == 0 && in.pix >= 0) d_pix[b] = my_pix;
     __syncthreads();
-    setup_body<SMODE, MODE == 2>(ppp, S, U, D, 1, 1, g_tabs, 0, smem, sm, n_shared, 0u);
+    setup_body<SMODE, MODE == 2>(ppp, S, U, D, 1, 1, g_tabs, 0, smem, sm, n_shared, 0u, in.overlap);
     __threadfence();                                            // theta in U, the derived record in D: at L2 ...
     __syncthreads();
     __builtin_amdgcn_s_dcache_inv();                            // ... where the scalar loads of the record find them
