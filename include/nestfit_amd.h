@@ -439,7 +439,7 @@ int  nfa_ring_stats(nfa_ring *r, int64_t *out);
  * likelihoods; check_every = rounds between two compactions of the active-pixel list.
  * Outputs are the raw material of what mn_dump stores (core.pyx:627-687): dead points with
  * their ln-weights, the final live points, iteration and evaluation counts; nestfit_amd/sampler.py
- * assembles posteriors / lnZ from them and holds the bit-compatible host twin of the algorithm. */
+ * assembles the results from them and nestfit_amd/nested.py holds the bit-compatible host twin of the algorithm. */
 typedef struct nfa_sampler nfa_sampler;
 int nfa_sampler_create(nfa_sampler **out, nfa_runner *r, const int32_t *pix, int64_t n_pix, int nlive,
                        int n_cand, int64_t batch_target, int64_t cap_iter, const int32_t *free_mask);

@@ -26,10 +26,6 @@
 #include "nfa_sampler_plan.h"   // the policy constants, the knobs and ns_plan: the run's form, decided once
 
 #define NS_MAXD      60          // 6 parameters x MAXCOMP
-#define NS_TAG_LIVE  (1ull << 62)
-#define NS_B_RADIUS  255ull
-#define NS_B_START   250ull      // stream index of a walker's starting live point
-#define NS_WALK_TARGET 0.5     // acceptance the walk scale is tuned to
 #define NS_W         64          // walkers per lane slice of the update wave
 #define NS_WMAX      256         // walkers per pixel at most
 
@@ -52,28 +48,7 @@ __host__ __device__ inline double ns_uniform_of(uint64_t stream, uint64_t b) {
     return ((double)(h >> 11) + 0.5) * (1.0 / 9007199254740992.0);
 }
 
-// Several bounding ellipsoids per pixel (MultiNest's `mmodal` bound in its simplest form): up to NS_ME of them where at
-// most NS_ME_MAXD dimensions are sampled.  A cluster of live points is cut in two across its principal axis at its
-// centre; the cut is kept when the two halves' ellipsoids together have less than NS_ME_GAIN of the parent's volume.
-#define NS_ME_GAIN 0.7
 static_assert(NS_ME_MAXD <= 6, "ns_refit_kernel dispatches the cluster fits for up to six sampled dimensions");
-#define NS_B_ELL 253ull            // random-stream slots of a proposal: which ellipsoid, and the 1 / (number that hold it) test
-#define NS_B_KEEP 254ull
-// Free rejections of a one-ellipsoid bound: a proposal outside the bounding box of the live points -- in the unit cube's
-// axes, in the ellipsoid's own (Cholesky) frame, or in one of NS_FRAMES fixed rotations of that frame -- is dropped before
-// its likelihood is evaluated.  Every box holds the live region, so what passes is uniform over the intersection.  A face
-// lies beyond the extreme live point by c max(0.1 s, extreme - mean - 1.5 s), s = the spread along the face's direction:
-// small where the marginal ends abruptly (a flat direction), large where it thins out (the projection of a round body).
-// scripts/proto_intersection.py measured what each family of bounds cuts off the true region and what it saves; the
-// numpy twin's _fit_boxes / _box_veto hold the same arithmetic.
-#define NS_MARGIN_A 1.5
-#define NS_MARGIN_FLOOR 0.1
-#define NS_FRAME_SEED 0x5EEDF00Dull
-// A volume-preserving shear in front of the one-ellipsoid bound (the twin's _fit_shear): every sampled coordinate minus a
-// quadratic function of the earlier ones -- the curved tex / ntot ridges of faint pixels come out straight, and an
-// ellipsoid around straight things is small
-#define NS_SHEAR_RIDGE 1e-6        // on the Gram matrix's diagonal, times the live points
-#define NS_SHEAR_PIVOT 1e-9        // a Cholesky pivot below this fraction of its diagonal entry: the monomial is dropped
 struct NsDev {
     int     P, N, D, K;                 // pixels, live points, SAMPLED dimensions, candidates per round (at least)
     int     DT;                         // length of a theta row (all unit-cube slots of the runner)

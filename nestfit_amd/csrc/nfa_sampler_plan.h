@@ -1,8 +1,9 @@
 // nfa_sampler_plan.h -- what form a run of the device sampler takes, decided once on the host.
 //
 // Standard C++17 without a HIP include: a host compiler builds this header alone, so the decision can be tested on a
-// machine without a GPU against the numpy twin's `_plan` (nestfit_amd/sampler.py), which holds the same chain under the
-// same field names.  It holds the policy defaults and limits the plan uses, the knobs in one convention, and ns_plan.
+// machine without a GPU against the numpy twin's `_plan` (nestfit_amd/nested.py), which holds the same chain under the
+// same field names.  It holds the policy defaults and limits the plan uses, the constants the kernels share with the
+// twin, the knobs in one convention, and ns_plan.
 #pragma once
 
 #include <climits>
@@ -46,6 +47,33 @@
 #define NS_WALK_LOWD 6             // up to this many sampled dimensions ...
 #define NS_WALK_FACTOR_LOWD 64     // ... the switch to walks waits for an acceptance below 1 / (64 n_steps)
 #define NS_WALK_FACTOR 2           // above: 1 / (2 n_steps)
+
+// What the kernels share with the numpy twin beside the plan (nestfit_amd/nested.py holds every NS_X below as _NS_X;
+// tests/test_sampler_plan.py compares them): the random stream's slots, the walk's target, the bound-fitting constants.
+#define NS_TAG_LIVE  (1ull << 62)
+#define NS_B_RADIUS  255ull
+#define NS_B_START   250ull      // stream index of a walker's starting live point
+#define NS_WALK_TARGET 0.5     // acceptance the walk scale is tuned to
+// Several ellipsoids: a cluster of live points is cut in two across its principal axis at its
+// centre; the cut is kept when the two halves' ellipsoids together have less than NS_ME_GAIN of the parent's volume.
+#define NS_ME_GAIN 0.7
+#define NS_B_ELL 253ull            // random-stream slots of a proposal: which ellipsoid, and the 1 / (number that hold it) test
+#define NS_B_KEEP 254ull
+// Free rejections of a one-ellipsoid bound: a proposal outside the bounding box of the live points -- in the unit cube's
+// axes, in the ellipsoid's own (Cholesky) frame, or in one of NS_FRAMES fixed rotations of that frame -- is dropped before
+// its likelihood is evaluated.  Every box holds the live region, so what passes is uniform over the intersection.  A face
+// lies beyond the extreme live point by c max(0.1 s, extreme - mean - 1.5 s), s = the spread along the face's direction:
+// small where the marginal ends abruptly (a flat direction), large where it thins out (the projection of a round body).
+// scripts/proto_intersection.py measured what each family of bounds cuts off the true region and what it saves; the
+// numpy twin's _fit_boxes / _box_veto hold the same arithmetic.
+#define NS_MARGIN_A 1.5
+#define NS_MARGIN_FLOOR 0.1
+#define NS_FRAME_SEED 0x5EEDF00Dull
+// A volume-preserving shear in front of the one-ellipsoid bound (the twin's _fit_shear): every sampled coordinate minus a
+// quadratic function of the earlier ones -- the curved tex / ntot ridges of faint pixels come out straight, and an
+// ellipsoid around straight things is small
+#define NS_SHEAR_RIDGE 1e-6        // on the Gram matrix's diagonal, times the live points
+#define NS_SHEAR_PIVOT 1e-9        // a Cholesky pivot below this fraction of its diagonal entry: the monomial is dropped
 
 // Walkers of a pixel with n live points: a cycle's walkers are harvested against a threshold that rises with every
 // replacement, so many more than a third of n mostly harvest each other's leftovers (of k walkers n ln(1 + k / n) pass);

@@ -1,4 +1,4 @@
-"""usage: python scripts/kernel_registers.py [filter ...]  -- vector / scalar registers and scratch of every kernel of the engine, read
+"""usage: python scripts/kernel_registers.py [filter ...]  -- vector / scalar registers, scratch and static LDS of every kernel of the engine, read
 from the gfx950 assembly hipcc makes of nestfit_amd/csrc/nfa_engine.hip (the flags of nestfit_amd/build.py)."""
 import re, subprocess, sys, tempfile
 from pathlib import Path
@@ -19,7 +19,7 @@ for m in re.finditer(r'\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel', s, re.S):
     if flt and not any(f in dem for f in flt):
         continue
     g = lambda k: int(re.search(k + r' (\d+)', body).group(1))
-    rows.append((dem, g('next_free_vgpr'), g('next_free_sgpr'), g('private_segment_fixed_size')))
-for dem, v, sg, sc in sorted(rows):
+    rows.append((dem, g('next_free_vgpr'), g('next_free_sgpr'), g('private_segment_fixed_size'), g('group_segment_fixed_size')))
+for dem, v, sg, sc, lds in sorted(rows):
     alloc = -(-v // 8) * 8
-    print(f'{dem:64s} vgpr {v:4d} (waves/SIMD {min(8, 512 // alloc)})  sgpr {sg:4d}  scratch {sc:5d} B')
+    print(f'{dem:64s} vgpr {v:4d} (waves/SIMD {min(8, 512 // alloc)})  sgpr {sg:4d}  scratch {sc:5d} B  lds {lds:6d} B')

@@ -5,7 +5,7 @@ end.  GPU part: the same sampler, same seed, fed by the HIP engine and by the CP
 import numpy as np
 import pytest
 
-from nestfit_amd import sampler
+from nestfit_amd import nested, sampler
 from nestfit_amd.synth import freq_axis
 
 
@@ -468,7 +468,7 @@ def test_box_vetoes_of_a_one_ellipsoid_bound():
     fixed rotations of it) are dropped before they are evaluated.  The frames are orthogonal; on a region no ellipsoid
     bounds well -- a flat likelihood inside a small cube, eight dimensions -- the evidence stays inside its error and a
     third of the evaluations go; on a Gaussian, which the ellipsoid bounds as well as anything, nothing changes."""
-    Q = sampler._frames(8, 5)
+    Q = nested._frames(8, 5)
     for k in range(5):
         np.testing.assert_allclose(Q[k].T @ Q[k], np.eye(8), atol=1e-12)
     assert not np.allclose(Q[0], Q[1])
@@ -500,23 +500,23 @@ def test_shear_in_front_of_the_ellipsoid():
     parabola the sampler needs a fraction of the evaluations for the same evidence."""
     rng = np.random.default_rng(5)
     comp = np.arange(10) % 2
-    mono, start = sampler._shear_monomials(comp)
+    mono, start = nested._shear_monomials(comp)
     assert mono.shape == (36, 2) and list(start) == [1, 3, 5, 8, 11, 15, 19, 24, 29, 35]
     assert all(tuple(mono[start[j]]) == (j, -1) for j in range(10))
     U = rng.uniform(0.3, 0.7, size=(400, 10))
     U[:, 6] = 0.5 + 8.0 * (U[:, 4] - 0.5) ** 2 + 0.004 * rng.normal(size=400)          # coordinate 6 bends with coordinate 4 (same component)
-    mu, sg, beta = sampler._fit_shear(U, mono, start)
-    W = sampler._shear_fwd(U, mu, sg, beta, mono, start)
-    np.testing.assert_allclose(sampler._shear_inv(W, mu, sg, beta, mono, start), U, atol=1e-13)
+    mu, sg, beta = nested._fit_shear(U, mono, start)
+    W = nested._shear_fwd(U, mu, sg, beta, mono, start)
+    np.testing.assert_allclose(nested._shear_inv(W, mu, sg, beta, mono, start), U, atol=1e-13)
     Z = (U - mu) / sg
     for j in (3, 6, 9):                                                                 # = ridge regression, coordinate by coordinate
-        F = sampler._shear_phi(Z, mono, start[j])
-        ref = np.linalg.solve(F.T @ F + sampler._NS_SHEAR_RIDGE * 400 * np.eye(start[j]), F.T @ Z[:, j])
+        F = nested._shear_phi(Z, mono, start[j])
+        ref = np.linalg.solve(F.T @ F + nested._NS_SHEAR_RIDGE * 400 * np.eye(start[j]), F.T @ Z[:, j])
         np.testing.assert_allclose(beta[j, :start[j]], ref, atol=1e-9)
     assert W[:, 6].std() < 0.05 and abs(W[:, 4].std() - 1.0) < 0.05                     # the bend is gone, the rest untouched
     # a unit Jacobian: the sheared image of a box has the box's volume (Monte Carlo over the unit cube)
     X = rng.uniform(size=(200000, 10))
-    Wx = sampler._shear_fwd(X, mu, sg, beta, mono, start)
+    Wx = nested._shear_fwd(X, mu, sg, beta, mono, start)
     lo, hi = np.quantile(W, 0.1, axis=0), np.quantile(W, 0.9, axis=0)
     inside = np.all((Wx[:, [4, 6]] >= lo[[4, 6]]) & (Wx[:, [4, 6]] <= hi[[4, 6]]), axis=1).mean()
     assert inside == pytest.approx(np.prod((hi - lo)[[4, 6]] * sg[[4, 6]]), rel=0.05)
@@ -541,8 +541,8 @@ def test_shear_in_front_of_the_ellipsoid():
     assert sum(r.n_evals for r in both) < sum(r.n_evals for r in bent)
     # the pair ellipses: every live point inside every one of them, a point half as far again outside some
     Wp = rng.normal(size=(300, 10)) @ rng.normal(size=(10, 10))
-    pt = sampler._fit_pairs(Wp, 1.75)
-    assert pt.shape == (45, 5) and sampler._pair_veto(Wp, pt).all() and not sampler._pair_veto(1.6 * (Wp - Wp.mean(axis=0)) + Wp.mean(axis=0), pt).all()
+    pt = nested._fit_pairs(Wp, 1.75)
+    assert pt.shape == (45, 5) and nested._pair_veto(Wp, pt).all() and not nested._pair_veto(1.6 * (Wp - Wp.mean(axis=0)) + Wp.mean(axis=0), pt).all()
     fewer = sampler.run_nested(ridge, 12, 1, pairs=1.75, **kw)
     none = sampler.run_nested(ridge, 12, 1, pairs=0, **kw)
     assert fewer[0].n_evals < none[0].n_evals and abs(fewer[0].lnZ - truth) < 4 * fewer[0].lnZ_err + 0.3

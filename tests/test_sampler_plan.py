@@ -1,6 +1,8 @@
-"""The form of a device-sampler run is decided by `ns_plan` (csrc/nfa_sampler_plan.h) and, for the numpy twin, by
-`sampler._plan`.  Every GPU sampler test rests on the two taking the same decisions; this one checks the decisions
-themselves, on a machine without a GPU: the header is plain C++17, g++ compiles it alone."""
+"""The form of a device-sampler run is decided by `ns_plan` (csrc/nfa_sampler_plan.h) and, for the numpy twin
+(nestfit_amd/nested.py), by `nested._plan`.  Every GPU sampler test rests on the two taking the same decisions, and on
+the twin's stages (`_refit`, `_propose`, `_update_reject`, `_walk_step`, `_chunk_kr`) working with the kernels' constants;
+this one checks the decisions themselves and every shared constant, the header's NS_X against the twin's _NS_X, on a
+machine without a GPU: the header is plain C++17, g++ compiles it alone."""
 import ctypes as C
 import itertools
 import subprocess
@@ -9,7 +11,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from nestfit_amd import sampler
+from nestfit_amd import nested
 
 ROOT = Path(__file__).resolve().parent.parent
 UNSET = -2 ** 31                                    # NS_UNSET
@@ -20,6 +22,12 @@ INT_FIELDS = ['max_ell', 'stage_live', 'multi', 'shear', 'sh_M', 'boxes', 'n_fra
               'refit_every', 'w_fixed', 'w_stride', 'ratio_max', 'kmax', 'refit_threads']
 DBL_FIELDS = ['shear_enlarge', 'margin_c', 'pairs_enlarge']
 SHARED = [f for f in INT_FIELDS + DBL_FIELDS if f != 'refit_threads']      # (the twin launches nothing)
+# every constant of the header the twin mirrors, by the type it has there
+INT_CONSTS = ['NS_ME', 'NS_ME_MAXD', 'NS_STAGE_BYTES', 'NS_FRAMES', 'NS_RATIO_MAX', 'NS_KMAX', 'NS_SHEAR_MMAX', 'NS_KP_START',
+              'NS_K_TARGET', 'NS_REFIT_EVERY', 'NS_WALK_LOWD', 'NS_WALK_FACTOR_LOWD', 'NS_WALK_FACTOR']
+DBL_CONSTS = ['NS_MARGIN_C', 'NS_SHEAR_ENLARGE', 'NS_PAIRS_ENLARGE', 'NS_WALK_TARGET', 'NS_ME_GAIN', 'NS_MARGIN_A',
+              'NS_MARGIN_FLOOR', 'NS_SHEAR_RIDGE', 'NS_SHEAR_PIVOT']
+U64_CONSTS = ['NS_TAG_LIVE', 'NS_B_RADIUS', 'NS_B_START', 'NS_B_ELL', 'NS_B_KEEP', 'NS_FRAME_SEED']
 
 
 class NsKnobs(C.Structure):
@@ -38,13 +46,18 @@ def plan_lib(tmp_path_factory):
     src.write_text('#include "nfa_sampler_plan.h"\n'
                    'extern "C" void plan(int D, int DT, int N, const int *fm, const NsKnobs *k, NsPlan *out) { *out = ns_plan(D, DT, N, fm, *k); }\n'
                    'extern "C" void merge(const NsKnobs *a, const NsKnobs *b, NsKnobs *out) { *out = ns_merge(*a, *b); }\n'
-                   'extern "C" int sizes(int i) { const int s[] = {sizeof(NsKnobs), sizeof(NsPlan), NS_SHEAR_MMAX, NS_STAGE_BYTES}; return s[i]; }\n')
+                   'extern "C" int sizes(int i) { const int s[] = {sizeof(NsKnobs), sizeof(NsPlan), NS_SHEAR_MMAX, NS_STAGE_BYTES}; return s[i]; }\n'
+                   'extern "C" int const_int(int i) { const int v[] = {%s}; return v[i]; }\n'
+                   'extern "C" double const_dbl(int i) { const double v[] = {%s}; return v[i]; }\n'
+                   'extern "C" unsigned long long const_u64(int i) { const unsigned long long v[] = {%s}; return v[i]; }\n'
+                   % (', '.join(INT_CONSTS), ', '.join(DBL_CONSTS), ', '.join(U64_CONSTS)))
     so = tmp / 'libplan.so'
     res = subprocess.run(['g++', '-std=c++17', '-Wall', '-Werror', '-shared', '-fPIC', f'-I{ROOT / "nestfit_amd" / "csrc"}',
                           str(src), '-o', str(so)], capture_output=True, text=True)
     assert res.returncode == 0, res.stderr
     lib = C.CDLL(str(so))
     assert lib.sizes(0) == C.sizeof(NsKnobs) and lib.sizes(1) == C.sizeof(NsPlan)
+    lib.const_dbl.restype, lib.const_u64.restype = C.c_double, C.c_ulonglong
     return lib
 
 
@@ -68,7 +81,7 @@ def shapes():
 
 
 def nlives(ndim, D):
-    edge = sampler._NS_STAGE_BYTES // (8 * D)                               # the most live points that are staged
+    edge = nested._NS_STAGE_BYTES // (8 * D)                               # the most live points that are staged
     return sorted({n for n in (ndim + 2, 100, 383, 384, 400, 768, 1000, 8192, edge, edge + 1) if ndim + 2 <= n <= 8192})
 
 
@@ -122,7 +135,7 @@ def test_device_plan_equals_the_twins(plan_lib):
         for k in DBL_KNOBS:
             setattr(kn, k, float(UNSET) if knobs[k] is None else knobs[k])
         plan_lib.plan(D, ndim, N, (C.c_int * D)(*fm), C.byref(kn), C.byref(out))
-        tw = sampler._plan(D, ndim, N, np.array(fm), **knobs)
+        tw = nested._plan(D, ndim, N, np.array(fm), **knobs)
         where = (ndim, fm, N, knobs)
         assert out.error is None and tw.error is None, where
         for f in SHARED:
@@ -157,9 +170,21 @@ def test_a_default_changed_on_one_side_is_caught(plan_lib, monkeypatch):
     for k in DBL_KNOBS:
         setattr(kn, k, float(UNSET))
     plan_lib.plan(5, 6, 400, (C.c_int * 5)(*range(5)), C.byref(kn), C.byref(out))
-    assert out.margin_c == sampler._plan(5, 6, 400, np.arange(5)).margin_c
-    monkeypatch.setattr(sampler, '_NS_MARGIN_C', 1.75)
-    assert out.margin_c != sampler._plan(5, 6, 400, np.arange(5)).margin_c
+    assert out.margin_c == nested._plan(5, 6, 400, np.arange(5)).margin_c
+    monkeypatch.setattr(nested, '_NS_MARGIN_C', 1.75)
+    assert out.margin_c != nested._plan(5, 6, 400, np.arange(5)).margin_c
+
+
+def test_shared_constants_equal_the_twins(plan_lib):
+    """Every NS_X of the header that the twin holds as _NS_X has the same value there, exactly and in the same kind of
+    number -- the stream slots and the frame seed as 64-bit integers -- and the twin holds no _NS_ name the header lacks."""
+    for names, get, kind in ((INT_CONSTS, plan_lib.const_int, int), (DBL_CONSTS, plan_lib.const_dbl, float),
+                             (U64_CONSTS, plan_lib.const_u64, np.uint64)):
+        for i, name in enumerate(names):
+            twin = getattr(nested, '_' + name)
+            assert type(twin) is kind and twin == kind(get(i)), (name, twin, get(i))
+    assert {n for n in vars(nested) if n.startswith('_NS_')} == {'_' + n for n in INT_CONSTS + DBL_CONSTS + U64_CONSTS}
+    assert int(nested._NS_TAG_LIVE) == 1 << 62 and plan_lib.const_u64(U64_CONSTS.index('NS_TAG_LIVE')) == 1 << 62     # (no 32-bit wrap)
 
 
 def test_setter_before_option_before_constant(plan_lib):
