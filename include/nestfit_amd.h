@@ -211,6 +211,25 @@ int nfa_specset_create_lte(nfa_specset **out, int n_spec, const int64_t *sizes, 
                            int n_q, const double *q_temp, const double *q_val,
                            const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                            const double *chan_noise);
+/* LTE bands: nfa_specset_create_lte with SEVERAL transitions of the species inside one spectrum (the K components of a
+ * symmetric top in one window).  Spectrum s covers n_trans[s] (1..8) transitions; the arrays n_lines, trans_freqs, e_up, g_up
+ * and a_ul have one entry per transition (sum of n_trans in all), voff and tau_wts one per line, the transitions of a
+ * spectrum and the spectra one after the other.  The offsets of a transition's lines are in km/s from its own rest frequency,
+ * its weights sum to 1, and the transitions of a spectrum have at most 50 lines together.  Line i of transition g:
+ *     hf_freq_i = (1 - voff_i / CKMS) nu_g
+ *     tau_i     = tau_main_g(tex, lncol, sigm) tau_wts_i          (tau_main_g: the formula above with nu_g, e_up_g, g_up_g, a_ul_g)
+ * and the spectrum follows as for model 3 from all its lines.  The model stays NFA_MODEL_LTE and the parameters voff, tex,
+ * lncol, sigm.  The order in which a spectrum's transitions are listed does not change the result.  If every n_trans is 1
+ * this is nfa_specset_create_lte, bit for bit.  A set with a banded spectrum is served by the batch entry points, the
+ * broker and the callback; nfa_ring_serve_device refuses it.  Returns NFA_ERR_ARG, with a message, for everything
+ * nfa_specset_create_lte refuses (per transition) and for an n_trans outside 1..8, more than 50 lines in a spectrum, and
+ * a spectrum that lists the same transition (equal frequency, e_up, g_up and a_ul) twice. */
+int nfa_specset_create_lte_bands(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
+                                 const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
+                                 const double *e_up, const double *g_up, const double *a_ul,
+                                 int n_q, const double *q_temp, const double *q_val,
+                                 const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                                 const double *chan_noise);
 /* A shipped line table, as a template for nfa_specset_create_lines: model 0 (trans_id 1..9) or 1 (trans_id 1..3);
  * voff and tau_wts take 50 doubles each (zero behind the *n lines), *nu the rest frequency in Hz.  Needs no device. */
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n);

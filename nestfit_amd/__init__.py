@@ -12,7 +12,7 @@ from .diazenylium import DiazenyliumRunner, DiazenyliumSpectrum, nnhp_predict
 from .gaussian import GaussianRunner, gauss_predict
 from . import ammonia, diazenylium, gaussian, hyperfine, lte
 from .hyperfine import HyperfineRunner, LineTable
-from .lte import LteLines, LteRunner, LteSpectrum, Molecule, lte_predict
+from .lte import LteBand, LteLines, LteRunner, LteSpectrum, Molecule, lte_predict
 
 # registry like nestfit/models/__init__.py:3-7
 MODELS = {m.NAME: m for m in (ammonia, diazenylium, gaussian)}
@@ -33,5 +33,5 @@ __all__ = [
     'AmmoniaSpectrum', 'AmmoniaRunner', 'amm_predict', 'get_irdc_priors', 'get_synth_priors',
     'DiazenyliumSpectrum', 'DiazenyliumRunner', 'nnhp_predict', 'GaussianRunner', 'gauss_predict',
     'MODELS', 'hyperfine', 'LineTable', 'HyperfineRunner', 'model_module',
-    'lte', 'Molecule', 'LteLines', 'LteSpectrum', 'LteRunner', 'lte_predict',
+    'lte', 'Molecule', 'LteLines', 'LteBand', 'LteSpectrum', 'LteRunner', 'lte_predict',
 ]

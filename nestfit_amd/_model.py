@@ -63,7 +63,8 @@ class _SpecSet:
         """xarrs: list of 1-D axes; data [n_pix, sum(sizes)]; noise [n_pix, n_spec], or [n_pix, sum(sizes)]
         for a noise per channel (nfa_specset_create_channel_noise: inf masks a channel).  lines: the hyperfine
         model's `LineTable` of every spectrum (nfa_specset_create_lines; `trans_ids` and `rest_freqs` are then unused), or
-        the LTE model's `LteLines` of every spectrum, all of one `Molecule` (nfa_specset_create_lte)."""
+        the LTE model's `LteLines` of every spectrum, all of one `Molecule` (nfa_specset_create_lte); where a spectrum covers
+        several transitions, its `LteBand` (nfa_specset_create_lte_bands)."""
         self.model = int(model)
         if (self.model in (MODEL_HYPERFINE, MODEL_LTE)) != (lines is not None):
             raise ValueError('the hyperfine model (3) and the LTE model (4), and no other, take `lines`: one LineTable '
@@ -71,12 +72,14 @@ class _SpecSet:
         molecule = None
         if lines is not None:
             from .hyperfine import LineTable
+            from .lte import LteBand, check_one_molecule, transitions_of
             lines = list(lines)
-            if len(lines) != len(xarrs) or not all(isinstance(t, LineTable) for t in lines):
+            if len(lines) != len(xarrs) or not all(isinstance(t, (LineTable, LteBand)) for t in lines):
                 raise ValueError('`lines` must hold one LineTable per spectrum')
             if self.model == MODEL_LTE:
-                from .lte import check_one_molecule
                 molecule = check_one_molecule(lines)
+            elif any(isinstance(t, LteBand) for t in lines):
+                raise ValueError('an LteBand belongs to the LTE model (4)')
             trans_ids = [-1] * len(lines)
         self.molecule = molecule
         self.lines = lines
@@ -102,20 +105,26 @@ class _SpecSet:
                            else np.ascontiguousarray(rest_freqs, dtype=np.float64))
         sizes_p = self.sizes.ctypes.data_as(_ffi._lp)
         if lines is not None:                       # the caller's tables: exactly one of the two noise arguments
-            n_lines = np.array([t.n for t in lines], dtype=np.int32)
             self.rest_freqs = np.array([t.nu for t in lines], dtype=np.float64)
+            banded = any(isinstance(t, LteBand) for t in lines)
+            n_trans = np.array([len(transitions_of(t)) for t in lines], dtype=np.int32)
+            if banded:                              # one entry per transition, the spectra one after the other
+                lines = [t for band in lines for t in transitions_of(band)]
+            n_lines = np.array([t.n for t in lines], dtype=np.int32)
+            freqs = np.array([t.nu for t in lines], dtype=np.float64)
             voff = np.ascontiguousarray(np.concatenate([t.voff for t in lines]), dtype=np.float64)
             tau_wts = np.ascontiguousarray(np.concatenate([t.tau_wts for t in lines]), dtype=np.float64)
-            head = (C.byref(h), self.n_spec, sizes_p, n_lines.ctypes.data_as(_ffi._ip), _ffi.dptr(self.rest_freqs),
-                    _ffi.dptr(voff), _ffi.dptr(tau_wts))
+            head = (C.byref(h), self.n_spec, sizes_p, *((n_trans.ctypes.data_as(_ffi._ip),) if banded else ()),
+                    n_lines.ctypes.data_as(_ffi._ip), _ffi.dptr(freqs), _ffi.dptr(voff), _ffi.dptr(tau_wts))
             tail = (xp, self.n_pix, _ffi.dptr(data),
                     None if self.per_channel else _ffi.dptr(noise), _ffi.dptr(noise) if self.per_channel else None)
             if molecule is not None:
                 e_up, g_up, a_ul = (np.array([getattr(t, k) for t in lines], dtype=np.float64)
                                     for k in ('e_up', 'g_up', 'a_ul'))
                 q_temp, q_val = np.ascontiguousarray(molecule.q_temp), np.ascontiguousarray(molecule.q_val)
-                rc = lib.nfa_specset_create_lte(*head, _ffi.dptr(e_up), _ffi.dptr(g_up), _ffi.dptr(a_ul), molecule.n,
-                                                _ffi.dptr(q_temp), _ffi.dptr(q_val), *tail)
+                create = lib.nfa_specset_create_lte_bands if banded else lib.nfa_specset_create_lte
+                rc = create(*head, _ffi.dptr(e_up), _ffi.dptr(g_up), _ffi.dptr(a_ul), molecule.n,
+                            _ffi.dptr(q_temp), _ffi.dptr(q_val), *tail)
             else:
                 rc = lib.nfa_specset_create_lines(*head, *tail)
         else:

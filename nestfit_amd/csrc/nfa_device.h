@@ -76,6 +76,19 @@ struct LteRec {
     double ln_t[NFA_LTE_MAXQ], ln_q[NFA_LTE_MAXQ], slope[NFA_LTE_MAXQ];
 };
 
+// LTE bands (nfa_specset_create_lte_bands): a spectrum that covers several transitions g of the species, each
+// with lines of its own.  One record per banded spectra set in device memory (null for every other set): the number of
+// transitions of every spectrum and the transition of every line, and per (spectrum, transition), formed on the host in
+// doubles against the spectrum's reference transition 0 (the one of the lowest lower-level energy, whose numbers
+// SpecDev.rest and LteRec hold):  t0 = h nu_g / k,  de = (E_g - t0_g) - (E_0 - t0_0) >= 0,
+// k = (g_g A_g / nu_g^3) / (g_0 A_0 / nu_0^3).  lte_band_kernel (nfa_setup.h) reads the numbers, lnl_body grp.
+#define NFA_BAND_MAXT 8
+struct BandRec {
+    int           n_trans[MAXSPEC];
+    unsigned char grp[MAXSPEC][NFA_MAX_HF_N];
+    double        t0[MAXSPEC][NFA_BAND_MAXT], de[MAXSPEC][NFA_BAND_MAXT], k[MAXSPEC][NFA_BAND_MAXT];
+};
+
 struct SpecDev {
     int     n_spec, ncomp, cold, lte;
     int     model, npar;                 // NFA_MODEL_*, parameters per component (6 / 4 / 3 / 4 / 4)
@@ -102,6 +115,9 @@ struct SpecDev {
     int     bl_order;
     const LineRow *lines;                // [n_spec]: the lines of every spectrum, in device memory
     const LteRec  *lte_rec;              // the LTE model's transitions and partition function (null for models 0..3)
+    const BandRec *band;                 // LTE bands: the transitions inside the spectra (null for every set without a band)
+    const double  *band_tau;             // ... and tau_main of [item][component][spectrum][transition] of the launch's lane
+                                         // (lte_band_kernel; set per launch by launch_lnl, null otherwise)
 };
 
 // Baseline record of a (pixel, spectrum), DESIGN 4.5: [0, 4) m_k(d) = sum_j w_j P_k(u_j) d_j, the Legendre moments of the
@@ -889,7 +905,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
             if (!(fabs(lc.nucen) < INFINITY) || !(lc.idenom < INFINITY)) lo = hi;
             r_nucen = lc.nucen;
             r_idenom = lc.idenom;
-            r_htau = D[b * drec + 4 * ncomp + (c * nspec + s) * DREC_CS + DK_TMAIN] * lrow->tauw[i];
+            r_htau = S.band ? S.band_tau[((b * ncomp + c) * nspec + s) * NFA_BAND_MAXT + S.band->grp[s][i]] * lrow->tauw[i]
+                            : D[b * drec + 4 * ncomp + (c * nspec + s) * DREC_CS + DK_TMAIN] * lrow->tauw[i];
             r_lo = lo;
             r_len = hi > lo ? hi - lo : 0;
             slot = c * G.nhf_max + lrow->rank[i];                 // velocity order: the lines of a row are neighbours

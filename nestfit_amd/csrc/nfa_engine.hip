@@ -120,6 +120,23 @@ static void line_row_fill(LineRow &row, int n, double nu, const double *voff, co
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return voff[a] > voff[b]; });
     for (int k = 0; k < n; ++k) row.rank[order[k]] = (unsigned char)k;
 }
+// The line row of a banded LTE spectrum (nfa_specset_create_lte_bands): every line against the rest frequency of its own
+// transition, nu[i], with the same two operations; the rank is the stable rank of ascending hf_freq -- for one
+// transition the permutation line_row_fill's descending offsets give.
+static void line_row_fill_band(LineRow &row, int n, const double *nu, const double *voff, const double *tauw) {
+    row.nhf = n;
+    for (int i = 0; i < NFA_MAX_HF_N; ++i) {
+        volatile double q = (i < n ? voff[i] : 0.0) / NFA_CKMS;
+        volatile double f = 1.0 - q;
+        row.hfreq[i] = f * nu[i < n ? i : 0];
+        row.tauw[i] = i < n ? tauw[i] : 0.0;
+        row.rank[i] = (unsigned char)i;
+    }
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return row.hfreq[a] < row.hfreq[b]; });
+    for (int k = 0; k < n; ++k) row.rank[order[k]] = (unsigned char)k;
+}
 // The shipped table of global transition index tg (NFA_T_*): the line count, the rest frequency, offsets and weights
 static int builtin_table(int tg, double *nu, const double **voff, const double **tauw) {
     static const double gauss_voff[NFA_MAX_HF_N] = {0.0}, gauss_w[NFA_MAX_HF_N] = {1.0};
@@ -192,6 +209,7 @@ struct nfa_specset {
     double *d_bl = nullptr;                         // a baseline: SpecDev.bl (nfa_specset_set_baseline)
     LineRow *d_lines = nullptr;                     // the line rows of the spectra: SpecDev.lines
     LteRec  *d_lte = nullptr;                       // the LTE model's record: SpecDev.lte_rec (null for the other models)
+    BandRec *d_band = nullptr;                      // LTE bands: SpecDev.band (null for a set without a banded spectrum)
     int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
     bool    bl_w1 = false;                          // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
 };
@@ -221,6 +239,7 @@ struct nfa_runner {
     bool        lanes_auto = false;      // four lanes, six once batches of about one wave per slot have come by (run_batch)
     hipStream_t lanes[NFA_MAX_LANES] = {};
     double     *d_D[NFA_MAX_LANES] = {};
+    double     *d_band[NFA_MAX_LANES] = {};  // LTE bands: tau_main per (item, component, spectrum, transition) (lte_band_kernel)
     double     *d_part[NFA_MAX_LANES] = {};  // per (item, spectrum) log-likelihood terms
     unsigned   *d_queue[NFA_MAX_LANES] = {}; // unit counters of the lane's table-mode launches (lnl_kernel_queue), zero between launches
     int64_t     cap_D[NFA_MAX_LANES] = {};
@@ -407,8 +426,10 @@ static int launch_bl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_b
 }
 
 // The caller's line tables of the hyperfine model (nfa_specset_create_lines): n_lines[n_spec], and the spectra's offsets
-// and weights concatenated; `lte`: the LTE model's record as well (nfa_specset_create_lte), null for the hyperfine model
-struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; const LteRec *lte; };
+// and weights concatenated; `lte`: the LTE model's record as well (nfa_specset_create_lte), null for the hyperfine model;
+// `band`, `line_nu`: a banded LTE set's record and the rest frequency of every line's own transition
+// (nfa_specset_create_lte_bands), null otherwise
+struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; const LteRec *lte; const BandRec *band; const double *line_nu; };
 
 static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *sizes, const int32_t *trans_ids,
                         const double *rest_freqs, const double *const *xarr, int64_t n_pix, const double *data,
@@ -455,7 +476,8 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
                 n = builtin_table(tglob, &nu, &voff, &tauw);
             }
             ss->h_nhf[s] = n;
-            line_row_fill(h_lines[s], n, nu, voff, tauw);
+            if (tabled && lines->band) line_row_fill_band(h_lines[s], n, lines->line_nu + (line0 - n), voff, tauw);
+            else line_row_fill(h_lines[s], n, nu, voff, tauw);
         }
         const double nu_chan = xarr[s][1] - xarr[s][0];
         if (!(nu_chan > 0)) return fail(NFA_ERR_ARG, "frequency axis must be ascending");   // core.pyx:503-504
@@ -504,6 +526,11 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
         HIP_TRY(hipMalloc(&ss->d_lte, sizeof(LteRec)));
         HIP_TRY(hipMemcpy(ss->d_lte, lines->lte, sizeof(LteRec), hipMemcpyHostToDevice));
         d.lte_rec = ss->d_lte;
+    }
+    if (model == NFA_MODEL_LTE && lines->band) {
+        HIP_TRY(hipMalloc(&ss->d_band, sizeof(BandRec)));
+        HIP_TRY(hipMemcpy(ss->d_band, lines->band, sizeof(BandRec), hipMemcpyHostToDevice));
+        d.band = ss->d_band;
     }
     if (chan_noise) {
         HIP_TRY(hipMalloc(&ss->d_w, sizeof(double) * tot * n_pix));
@@ -584,6 +611,22 @@ int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, c
     return specset_create_channel_noise(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, chan_noise, nullptr);
 }
 
+// the checks of nfa_specset_create_lines on one table of n lines (`at`: where, for the message)
+static int check_one_table(int n, double nu, const double *voff, const double *tau_wts, const std::string &at) {
+    if (n < 1 || n > NFA_MAX_HF_N) return fail(NFA_ERR_ARG, "a line table must have 1..50 lines" + at);
+    if (!(std::isfinite(nu) && nu > 0)) return fail(NFA_ERR_ARG, "a rest frequency must be finite and positive" + at);
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const double v = voff[i], w = tau_wts[i];
+        if (!(std::isfinite(v) && std::fabs(v) < NFA_CKMS))
+            return fail(NFA_ERR_ARG, "a velocity offset must be finite and below the speed of light" + at);
+        if (!(std::isfinite(w) && w >= 0)) return fail(NFA_ERR_ARG, "a line weight must be finite and not negative" + at);
+        any = any || w > 0;
+    }
+    if (!any) return fail(NFA_ERR_ARG, "the weights of a line table are all zero" + at);
+    return NFA_OK;
+}
+
 // the checks of nfa_specset_create_lines on its own arguments
 static int check_line_tables(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
                              const double *rest_freqs, const double *voff, const double *tau_wts,
@@ -596,21 +639,45 @@ static int check_line_tables(nfa_specset **out, int n_spec, const int64_t *sizes
     int64_t l0 = 0;
     for (int s = 0; s < n_spec; ++s) {
         const int n = n_lines[s];
-        const std::string at = " (spectrum " + std::to_string(s) + ")";
-        if (n < 1 || n > NFA_MAX_HF_N) return fail(NFA_ERR_ARG, "a line table must have 1..50 lines" + at);
-        if (!(std::isfinite(rest_freqs[s]) && rest_freqs[s] > 0))
-            return fail(NFA_ERR_ARG, "a rest frequency must be finite and positive" + at);
-        bool any = false;
-        for (int i = 0; i < n; ++i) {
-            const double v = voff[l0 + i], w = tau_wts[l0 + i];
-            if (!(std::isfinite(v) && std::fabs(v) < NFA_CKMS))
-                return fail(NFA_ERR_ARG, "a velocity offset must be finite and below the speed of light" + at);
-            if (!(std::isfinite(w) && w >= 0)) return fail(NFA_ERR_ARG, "a line weight must be finite and not negative" + at);
-            any = any || w > 0;
-        }
-        if (!any) return fail(NFA_ERR_ARG, "the weights of a line table are all zero" + at);
+        int rc = check_one_table(n, rest_freqs[s], voff + l0, tau_wts + l0, " (spectrum " + std::to_string(s) + ")");
+        if (rc) return rc;
         l0 += n;
     }
+    return NFA_OK;
+}
+
+// the checks of nfa_specset_create_lte on one transition beyond its line table's
+static int check_one_transition(double e_up, double g_up, double a_ul, int n, const double *tau_wts, const std::string &at) {
+    if (!(std::isfinite(e_up) && e_up >= 0))
+        return fail(NFA_ERR_ARG, "an upper-level energy must be finite and not negative (K)" + at);
+    if (!(std::isfinite(g_up) && g_up > 0))
+        return fail(NFA_ERR_ARG, "an upper-level weight must be finite and positive" + at);
+    if (!(std::isfinite(a_ul) && a_ul > 0))
+        return fail(NFA_ERR_ARG, "an Einstein coefficient must be finite and positive (1/s)" + at);
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) sum += tau_wts[i];
+    if (!(std::fabs(sum - 1.0) <= 1e-6))
+        return fail(NFA_ERR_ARG, "the weights of a transition must sum to 1 within 1e-6" + at);
+    return NFA_OK;
+}
+
+// ... and on the partition function, which it leaves in the record as ln Q over ln T with the segments' slopes
+static int lte_partition_fill(LteRec &rec, int n_q, const double *q_temp, const double *q_val) {
+    if (n_q < 2 || n_q > NFA_LTE_MAXQ) return fail(NFA_ERR_ARG, "a partition table must have 2..64 entries");
+    for (int k = 0; k < n_q; ++k) {
+        if (!(std::isfinite(q_temp[k]) && q_temp[k] > 0 && (k == 0 || q_temp[k] > q_temp[k - 1])))
+            return fail(NFA_ERR_ARG, "the temperatures of a partition table must be finite, positive and strictly ascending");
+        if (!(std::isfinite(q_val[k]) && q_val[k] > 0))
+            return fail(NFA_ERR_ARG, "a partition function value must be finite and positive");
+        rec.ln_t[k] = log(q_temp[k]);
+        rec.ln_q[k] = log(q_val[k]);
+    }
+    for (int k = 0; k + 1 < n_q; ++k) {
+        if (!(rec.ln_t[k + 1] > rec.ln_t[k]))
+            return fail(NFA_ERR_ARG, "the temperatures of a partition table must be finite, positive and strictly ascending");
+        rec.slope[k] = (rec.ln_q[k + 1] - rec.ln_q[k]) / (rec.ln_t[k + 1] - rec.ln_t[k]);
+    }
+    rec.n_q = n_q;
     return NFA_OK;
 }
 
@@ -620,7 +687,7 @@ int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes
                              const double *chan_noise) {
     int rc = check_line_tables(out, n_spec, sizes, n_lines, rest_freqs, voff, tau_wts, xarr, data, noise, chan_noise);
     if (rc) return rc;
-    const LineTables lt = {n_lines, voff, tau_wts, nullptr};
+    const LineTables lt = {n_lines, voff, tau_wts, nullptr, nullptr, nullptr};
     if (chan_noise)
         return specset_create_channel_noise(out, NFA_MODEL_HYPERFINE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data,
                                             chan_noise, &lt);
@@ -639,40 +706,102 @@ int nfa_specset_create_lte(nfa_specset **out, int n_spec, const int64_t *sizes, 
     LteRec rec = {};
     int64_t l0 = 0;
     for (int s = 0; s < n_spec; ++s) {
-        const std::string at = " (spectrum " + std::to_string(s) + ")";
-        if (!(std::isfinite(e_up[s]) && e_up[s] >= 0))
-            return fail(NFA_ERR_ARG, "an upper-level energy must be finite and not negative (K)" + at);
-        if (!(std::isfinite(g_up[s]) && g_up[s] > 0))
-            return fail(NFA_ERR_ARG, "an upper-level weight must be finite and positive" + at);
-        if (!(std::isfinite(a_ul[s]) && a_ul[s] > 0))
-            return fail(NFA_ERR_ARG, "an Einstein coefficient must be finite and positive (1/s)" + at);
-        double sum = 0.0;
-        for (int i = 0; i < n_lines[s]; ++i) sum += tau_wts[l0 + i];
-        if (!(std::fabs(sum - 1.0) <= 1e-6))
-            return fail(NFA_ERR_ARG, "the weights of a transition must sum to 1 within 1e-6" + at);
+        rc = check_one_transition(e_up[s], g_up[s], a_ul[s], n_lines[s], tau_wts + l0, " (spectrum " + std::to_string(s) + ")");
+        if (rc) return rc;
         l0 += n_lines[s];
         rec.e_up[s] = e_up[s]; rec.g_up[s] = g_up[s]; rec.a_ul[s] = a_ul[s];
     }
-    if (n_q < 2 || n_q > NFA_LTE_MAXQ) return fail(NFA_ERR_ARG, "a partition table must have 2..64 entries");
-    for (int k = 0; k < n_q; ++k) {
-        if (!(std::isfinite(q_temp[k]) && q_temp[k] > 0 && (k == 0 || q_temp[k] > q_temp[k - 1])))
-            return fail(NFA_ERR_ARG, "the temperatures of a partition table must be finite, positive and strictly ascending");
-        if (!(std::isfinite(q_val[k]) && q_val[k] > 0))
-            return fail(NFA_ERR_ARG, "a partition function value must be finite and positive");
-        rec.ln_t[k] = log(q_temp[k]);
-        rec.ln_q[k] = log(q_val[k]);
-    }
-    for (int k = 0; k + 1 < n_q; ++k) {
-        if (!(rec.ln_t[k + 1] > rec.ln_t[k]))
-            return fail(NFA_ERR_ARG, "the temperatures of a partition table must be finite, positive and strictly ascending");
-        rec.slope[k] = (rec.ln_q[k + 1] - rec.ln_q[k]) / (rec.ln_t[k + 1] - rec.ln_t[k]);
-    }
-    rec.n_q = n_q;
-    const LineTables lt = {n_lines, voff, tau_wts, &rec};
+    rc = lte_partition_fill(rec, n_q, q_temp, q_val); if (rc) return rc;
+    const LineTables lt = {n_lines, voff, tau_wts, &rec, nullptr, nullptr};
     if (chan_noise)
         return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data,
                                             chan_noise, &lt);
     return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data, noise, nullptr, &lt);
+}
+
+int nfa_specset_create_lte_bands(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
+                                 const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
+                                 const double *e_up, const double *g_up, const double *a_ul,
+                                 int n_q, const double *q_temp, const double *q_val,
+                                 const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                                 const double *chan_noise) {
+    if (!out || !sizes || !n_trans || !n_lines || !trans_freqs || !voff || !tau_wts || !xarr || !data)
+        return fail(NFA_ERR_ARG, "null argument");
+    if ((noise != nullptr) == (chan_noise != nullptr))
+        return fail(NFA_ERR_ARG, "exactly one of noise and chan_noise must be given");
+    if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
+    bool banded = false;
+    for (int s = 0; s < n_spec; ++s) {
+        if (n_trans[s] < 1 || n_trans[s] > NFA_BAND_MAXT)
+            return fail(NFA_ERR_ARG, "a spectrum must have 1..8 transitions (spectrum " + std::to_string(s) + ")");
+        banded = banded || n_trans[s] > 1;
+    }
+    // a transition per spectrum: nfa_specset_create_lte's set, bit for bit, on its routes
+    if (!banded)
+        return nfa_specset_create_lte(out, n_spec, sizes, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, n_q, q_temp, q_val,
+                                      xarr, n_pix, data, noise, chan_noise);
+    if (!e_up || !g_up || !a_ul || !q_temp || !q_val) return fail(NFA_ERR_ARG, "null argument");
+    LteRec rec = {};
+    BandRec band = {};
+    // the spectra's transitions in the engine's order -- ascending lower-level energy, then rest frequency, then the caller's
+    // order -- and their lines one after the other: what the caller's order of a spectrum's transitions cannot change
+    std::vector<int32_t> s_lines((size_t)n_spec);
+    std::vector<double> s_rest((size_t)n_spec), l_voff, l_wts, l_nu;
+    int64_t tr0 = 0, l0 = 0;
+    for (int s = 0; s < n_spec; ++s) {
+        const int nt = n_trans[s];
+        std::vector<int64_t> first((size_t)nt);                     // the first line of every transition
+        std::vector<double> e_low((size_t)nt);
+        int total = 0;
+        for (int j = 0; j < nt; ++j) {
+            const int64_t t = tr0 + j;
+            const std::string at = " (spectrum " + std::to_string(s) + ", transition " + std::to_string(j) + ")";
+            first[j] = l0;
+            if (n_lines[t] >= 1 && n_lines[t] <= NFA_MAX_HF_N && total + n_lines[t] > NFA_MAX_HF_N)
+                return fail(NFA_ERR_ARG, "the transitions of a spectrum must have at most 50 lines together (spectrum " + std::to_string(s) + ")");
+            int rc = check_one_table(n_lines[t], trans_freqs[t], voff + l0, tau_wts + l0, at); if (rc) return rc;
+            rc = check_one_transition(e_up[t], g_up[t], a_ul[t], n_lines[t], tau_wts + l0, at); if (rc) return rc;
+            for (int i = 0; i < j; ++i)
+                if (trans_freqs[tr0 + i] == trans_freqs[t] && e_up[tr0 + i] == e_up[t] && g_up[tr0 + i] == g_up[t] && a_ul[tr0 + i] == a_ul[t])
+                    return fail(NFA_ERR_ARG, "a spectrum lists the same transition twice" + at);
+            e_low[j] = e_up[t] - NFA_H * trans_freqs[t] / NFA_KB;
+            total += n_lines[t];
+            l0 += n_lines[t];
+        }
+        std::vector<int> order((size_t)nt);
+        for (int j = 0; j < nt; ++j) order[j] = j;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+            return e_low[a] != e_low[b] ? e_low[a] < e_low[b] : trans_freqs[tr0 + a] < trans_freqs[tr0 + b];
+        });
+        const int64_t r = tr0 + order[0];                           // the reference transition
+        const double ref_t0 = NFA_H * trans_freqs[r] / NFA_KB;
+        const double ref_k = g_up[r] * a_ul[r] / (trans_freqs[r] * trans_freqs[r] * trans_freqs[r]);
+        s_rest[s] = trans_freqs[r];
+        rec.e_up[s] = e_up[r]; rec.g_up[s] = g_up[r]; rec.a_ul[s] = a_ul[r];
+        band.n_trans[s] = nt;
+        int line = 0;
+        for (int g = 0; g < nt; ++g) {
+            const int64_t t = tr0 + order[g];
+            const double nu = trans_freqs[t], tg = NFA_H * nu / NFA_KB;
+            band.t0[s][g] = tg;
+            band.de[s][g] = (e_up[t] - tg) - (e_up[r] - ref_t0);
+            band.k[s][g] = (g_up[t] * a_ul[t] / (nu * nu * nu)) / ref_k;
+            for (int i = 0; i < n_lines[t]; ++i, ++line) {
+                band.grp[s][line] = (unsigned char)g;
+                l_voff.push_back(voff[first[order[g]] + i]);
+                l_wts.push_back(tau_wts[first[order[g]] + i]);
+                l_nu.push_back(nu);
+            }
+        }
+        s_lines[s] = line;
+        tr0 += nt;
+    }
+    int rc = lte_partition_fill(rec, n_q, q_temp, q_val); if (rc) return rc;
+    const LineTables lt = {s_lines.data(), l_voff.data(), l_wts.data(), &rec, &band, l_nu.data()};
+    if (chan_noise)
+        return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, s_rest.data(), xarr, n_pix, data,
+                                            chan_noise, &lt);
+    return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, s_rest.data(), xarr, n_pix, data, noise, nullptr, &lt);
 }
 
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n) {
@@ -693,7 +822,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_xarr); (void)hipFree(ss->d_t0); (void)hipFree(ss->d_tbg); (void)hipFree(ss->d_data); (void)hipFree(ss->d_noise);
     (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq);
     (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl); (void)hipFree(ss->d_lines);
-    (void)hipFree(ss->d_lte);
+    (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band);
     delete ss;
     return NFA_OK;
 }
@@ -974,7 +1103,7 @@ int nfa_runner_destroy(nfa_runner *r) {
     { RUNNER_LOCK(r); r->pending.n = 0; }
     for (int k = 0; k < r->n_lanes; ++k) (void)hipStreamSynchronize(r->lanes[k]);
     (void)hipFree(r->d_U); (void)hipFree(r->d_lnL); (void)hipFree(r->d_pix); (void)hipFree(r->d_spec);
-    for (int k = 0; k < r->n_lanes; ++k) { (void)hipFree(r->d_D[k]); (void)hipFree(r->d_part[k]); (void)hipFree(r->d_queue[k]); }
+    for (int k = 0; k < r->n_lanes; ++k) { (void)hipFree(r->d_D[k]); (void)hipFree(r->d_part[k]); (void)hipFree(r->d_queue[k]); (void)hipFree(r->d_band[k]); }
     if (r->g1) (void)hipGraphExecDestroy(r->g1);
     if (r->h_pin) (void)hipHostFree(r->h_pin);
     if (r->h_point) (void)hipHostFree(r->h_point);
@@ -1051,10 +1180,11 @@ static int reserve_lane(nfa_runner *r, int slot, int64_t B) {
     const int n_spec = r->ss->dev.n_spec;
     if (slot == 0 && r->g1) { (void)hipGraphExecDestroy(r->g1); r->g1 = nullptr; }
     HIP_TRY(hipStreamSynchronize(r->lanes[slot]));
-    (void)hipFree(r->d_D[slot]); (void)hipFree(r->d_part[slot]);
-    r->d_D[slot] = nullptr; r->d_part[slot] = nullptr; r->cap_D[slot] = 0;
+    (void)hipFree(r->d_D[slot]); (void)hipFree(r->d_part[slot]); (void)hipFree(r->d_band[slot]);
+    r->d_D[slot] = nullptr; r->d_part[slot] = nullptr; r->d_band[slot] = nullptr; r->cap_D[slot] = 0;
     const int64_t cap = std::max<int64_t>(B, 4096);
     HIP_TRY(hipMalloc(&r->d_D[slot], sizeof(double) * cap * drec_size(r->ncomp, n_spec)));
+    if (r->ss->dev.band) HIP_TRY(hipMalloc(&r->d_band[slot], sizeof(double) * cap * r->ncomp * n_spec * NFA_BAND_MAXT));
     HIP_TRY(hipMalloc(&r->d_part[slot], sizeof(double) * cap * n_spec));
     if (!r->d_queue[slot]) {
         HIP_TRY(hipMalloc(&r->d_queue[slot], sizeof(unsigned) * NFA_QUEUE_WORDS));
@@ -1089,6 +1219,17 @@ static int launch_setup(nfa_runner *r, int64_t B, bool has_prior, int slot, int 
     return NFA_OK;
 }
 
+// LTE bands: tau_main of every (item, component, spectrum, transition) of the B items whose records the set-up stage has
+// just written on this lane (lte_band_kernel, nfa_setup.h), one small launch between the two stages
+static int launch_band(nfa_runner *r, int slot, int64_t B) {
+    const int n_spec = r->ss->dev.n_spec;
+    const int64_t lanes = B * r->ncomp * n_spec * NFA_BAND_MAXT;
+    hipLaunchKernelGGL(lte_band_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, r->lanes[slot],
+                       (const BandRec *)r->ss->d_band, (const double *)r->d_D[slot], r->d_band[slot], (long)B, r->ncomp, n_spec);
+    HIP_TRY(hipGetLastError());
+    return NFA_OK;
+}
+
 // The kernel of a plan.  Naming an instance compiles it, so this names the instances a plan can ask for and no others:
 // lnl_kernel, _wt and _bl for all 32 (mode, spectra out, wide, NCOMP), lnl_kernel_w8 for the table mode with spectra out,
 // lnl_kernel_queue for the table mode's narrow sets.  NCOMP 1..3: the component loop unrolled; 0: the general form.
@@ -1116,7 +1257,8 @@ static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, 
 // Likelihood stage of the batch in r->cur_group on stream lane `slot`: chi^2 parts of the units (and spectra out), then
 // -- want_lnl, and nobody else sums the parts -- lnL of the items (lnl_sum_kernel)
 static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, int64_t B, int mode) {
-    const SpecDev S = runner_specdev(r);
+    SpecDev S = runner_specdev(r);
+    S.band_tau = r->d_band[slot];                             // (null unless the set is banded)
     LnlPlan P = plan_lnl(r->shape, plan_knobs(), plan_launch(r, B, mode, d_spec != nullptr, false, slot));
     if (P.error) return fail(NFA_ERR_ARG, P.error);
     if (P.form == LNL_QUEUE) P.G.queue = r->d_queue[slot];
@@ -1174,6 +1316,7 @@ static int run_group(nfa_runner *r, const BatchGroup &grp, double *d_spec, bool 
     r->cur_group = grp;
     int rc = launch_setup(r, B, has_prior, slot, mode);
     if (rc) return rc;
+    if (r->ss->dev.band) { rc = launch_band(r, slot, B); if (rc) return rc; }
     rc = launch_lnl(r, slot, grp.lnL[0] != nullptr, d_spec, B, mode);
     if (rc) return rc;
     r->n_calls++;
@@ -1330,7 +1473,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     if (!g_eng.point || r->profiling || B > NFA_POINT_MAXB) return 0;
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
-    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr);
+    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr, S.band != nullptr);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

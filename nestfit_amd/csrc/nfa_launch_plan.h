@@ -262,13 +262,15 @@ inline SetupPlan plan_setup(const LpShape &s, const LpKnobs &k, const LpLaunch &
 // G: of a launch of one item; n_blocks: passes of the workgroup over the units; staged: d_prog, not d_prog_global;
 // lds_point: more than LDS_PER_CU sends the points the batch path; ctl_double: the resident kernel's control words
 struct FusedPlan { const char *refusal, *ring_error; LnlGeom G; int n_blocks, ctl_double; bool staged; size_t lds_point, lds_ring; };
-inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted) {
+// banded: an LTE set with several transitions inside a spectrum (lte_band_kernel runs between the stages of a batch)
+inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted, bool banded = false) {
     FusedPlan P = {};
     P.G = lnl_geom(s, k, 1);
     if (s.ndim > NFA_POINT_MAXDIM || lnl_wide(s)) P.refusal = "this runner's points go through the batch kernels: use nfa_ring_serve";
     // (weighted sets, baseline sets among them: lnl_kernel_wt / lnl_kernel_bl.  The unweighted body would compute the unweighted sum.)
     else if (baseline) P.refusal = "the resident kernel has no form for a baseline: use nfa_ring_serve";
     else if (weighted) P.refusal = "the resident kernel has no form for a noise per channel: use nfa_ring_serve";
+    else if (banded) P.refusal = "the resident kernel has no form for LTE bands: use nfa_ring_serve";
     else if (P.G.split > POINT_WAVES) P.refusal = "spectra too short for the point kernel's split";
     if ((P.ring_error = P.refusal)) return P;
     const int upw = POINT_WAVES / P.G.split;                     // units per pass of the workgroup

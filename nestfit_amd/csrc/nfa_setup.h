@@ -722,3 +722,39 @@ __global__ void __launch_bounds__(POINT_THREADS) point_kernel(const PriorProg *_
     }
 }
 #undef TH
+
+// ---------------------------------------------------------------------------
+//  lte_band_kernel: LTE bands (BandRec).  The set-up stage has written tau_main of every spectrum's
+//  reference transition 0 into the records; this gives every other transition g of the spectrum its own, as the ratio
+//  of the LTE formula for g to the same formula for 0 -- the partition function, 10^lncol and sigm cancel, and with
+//  exp(-E_u/tex) expm1(T0/tex) = exp(-E_low/tex) (-expm1(-T0/tex)):
+//      T[b][c][s][g] = tau_main_0 k_g exp(-de_g / tex) expm1(-t0_g / tex) / expm1(-t0_0 / tex)
+//  de_g >= 0 (transition 0 has the lowest lower level), so every factor is bounded: no 0 * inf where a cold component's
+//  upper levels underflow.  g = 0, and so every spectrum of one transition: tau_main_0 itself, no arithmetic.  A NaN
+//  tau_main_0 (a tex or sigm that is no ordinary positive number) gives NaN.  Lanes = (item, component, spectrum,
+//  transition) of the launch's B items; the slots behind a spectrum's last transition are zeroed and never read.
+__global__ void __launch_bounds__(256)
+lte_band_kernel(const BandRec *__restrict__ R, const double *__restrict__ D, double *__restrict__ T, long B, int ncomp, int nspec) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * ncomp * nspec * NFA_BAND_MAXT) return;
+    const int g = (int)(i % NFA_BAND_MAXT);
+    const long u = i / NFA_BAND_MAXT;
+    const int s = (int)(u % nspec);
+    const long bc = u / nspec;
+    const int c = (int)(bc % ncomp);
+    const long b = bc / ncomp;
+    const double *Db = D + b * drec_size(ncomp, nspec);
+    const double tau0 = Db[4 * ncomp + (c * nspec + s) * DREC_CS + DK_TMAIN];
+    double out = tau0;
+    if (g >= R->n_trans[s]) out = 0.0;
+    else if (g > 0) {
+        const double tex = Db[c * 4];
+        // exp(-de / tex) carries the quotient's rounding error times the quotient -- 6e-14 of the result at de / tex = 600,
+        // where a cold component's upper transitions sit -- unless the division's remainder, one fma, is put back
+        const double de = R->de[s][g], q = de / tex, rem = __builtin_fma(-q, tex, de);
+        const double e = exp(-q);
+        const double boltz = e == 0.0 ? 0.0 : e * (1.0 - rem / tex);
+        out = tau0 * R->k[s][g] * boltz * expm1(-R->t0[s][g] / tex) / expm1(-R->t0[s][0] / tex);
+    }
+    T[i] = out;
+}

@@ -49,8 +49,8 @@ class CubeRunner:
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
                  model=0, rest_freqs=None, baseline_order=None, lines=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
-        one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines` per spectrum, all of
-        one `Molecule`)."""
+        one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
+        transitions, per spectrum, all of one `Molecule`)."""
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs, lines=lines)

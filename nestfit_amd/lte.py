@@ -14,6 +14,15 @@ the partition function on a table of temperatures.  In cgs units, with T0 = h nu
 `tau_main` is the transition's peak optical depth summed over its lines; line i gets tau_main * tau_wts[i], and the
 spectrum follows as for the hyperfine model (the reference's c_hf_predict, nestfit/models/hyperfine.pyx:52-118).
 
+A spectrum may also cover SEVERAL transitions of the species at once -- the K components of a symmetric top in one
+window -- as an `LteBand` (`Molecule.band`): 1..8 `LteLines`, each with offsets from its own rest frequency, at most 50
+lines together.  Line i of transition g then has
+
+    hf_freq_i = (1 - voff_i / CKMS) * nu_g
+    tau_i     = tau_main_g(tex, lncol, sigm) * tau_wts_i
+
+and the spectrum follows from all the lines together, blended or not.  The parameters stay the four above.
+
 No molecular data ship with this module: rest frequencies, level energies, Einstein coefficients and the partition
 function come from a catalogue of the user's.
 """
@@ -21,9 +30,10 @@ import numpy as np
 
 from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, par_names
 from .core import HyperfineSpectrum as _HyperfineBase
-from .hyperfine import CKMS, LineTable
+from .hyperfine import CKMS, MAX_LINES, LineTable
 
 N_PARAMS = 4
+MAX_TRANS = 8             # NFA_BAND_MAXT
 MAX_Q = 64                # NFA_LTE_MAXQ
 H_CGS = 6.62607015e-27    # csrc/nh3_data.h: NFA_H, NFA_KB, NFA_CCMS
 KB_CGS = 1.380649e-16
@@ -98,6 +108,10 @@ class Molecule:
         and statistical weight `g_up`, Einstein coefficient `a_ul` (1/s), and its hyperfine lines."""
         return LteLines(self, nu, e_up, g_up, a_ul, voff, tau_wts, name=name, normalise=normalise)
 
+    def band(self, transitions, name=None):
+        """Several transitions of this species inside one spectrum, as an `LteBand`: 1..8 `LteLines` of this molecule."""
+        return LteBand(self, transitions, name=name)
+
 
 class LteLines(LineTable):
     """The lines of one rotational transition of a `Molecule`: a `LineTable` whose weights sum to 1 (within 1e-6; with
@@ -171,11 +185,92 @@ class LteLines(LineTable):
         return pop_upper * fracterm * np.expm1(t0 / tex) * widthterm
 
 
+class LteBand:
+    """The transitions of one `Molecule` that one spectrum covers: a sequence of 1..8 `LteLines` in the caller's order,
+    at most 50 lines together, no transition twice.  Immutable, compared by value (the transitions in their order; the
+    name is a label) and hashable; everything the engine would refuse raises ValueError here.  The order of the
+    transitions does not change the model."""
+    __slots__ = ('_molecule', '_transitions', '_name')
+
+    def __init__(self, molecule, transitions, name=None):
+        if not isinstance(molecule, Molecule):
+            raise ValueError(f'`molecule` must be a Molecule, not {type(molecule).__name__}')
+        try:
+            transitions = tuple(transitions)
+        except TypeError:
+            raise ValueError('a band takes a sequence of LteLines') from None
+        if not all(isinstance(t, LteLines) for t in transitions):
+            raise ValueError('a band takes LteLines (Molecule.transition), one per transition')
+        if not 1 <= len(transitions) <= MAX_TRANS:
+            raise ValueError(f'a band must have 1..{MAX_TRANS} transitions, not {len(transitions)}')
+        if any(t.molecule != molecule for t in transitions):
+            raise ValueError('the transitions of a band are of one Molecule: '
+                             + ', '.join(sorted({t.molecule.name for t in transitions} | {molecule.name})))
+        n_lines = sum(t.n for t in transitions)
+        if n_lines > MAX_LINES:
+            raise ValueError(f'the transitions of a band must have at most {MAX_LINES} lines together, not {n_lines}')
+        keys = [(t.nu, t.e_up, t.g_up, t.a_ul) for t in transitions]
+        if len(set(keys)) != len(keys):
+            raise ValueError('a band lists the same transition (nu, e_up, g_up, a_ul) twice')
+        for key, value in (('_molecule', molecule), ('_transitions', transitions), ('_name', None if name is None else str(name))):
+            object.__setattr__(self, key, value)
+
+    molecule = property(lambda self: self._molecule)
+    transitions = property(lambda self: self._transitions)
+    name = property(lambda self: self._name)
+    n_trans = property(lambda self: len(self._transitions))
+    n_lines = property(lambda self: sum(t.n for t in self._transitions))
+    n = n_lines                                                      # as a LineTable counts: the lines of the spectrum
+    nu = property(lambda self: self._transitions[0].nu)             # the first transition's: axes and labels
+
+    def __setattr__(self, key, value):
+        raise AttributeError('an LteBand is immutable')
+
+    def __delattr__(self, key):
+        raise AttributeError('an LteBand is immutable')
+
+    def __len__(self):
+        return len(self._transitions)
+
+    def __getitem__(self, k):
+        return self._transitions[k]
+
+    def __iter__(self):
+        return iter(self._transitions)
+
+    def __eq__(self, other):
+        if not isinstance(other, LteBand):
+            return NotImplemented
+        return self._transitions == other._transitions
+
+    def __ne__(self, other):
+        r = self.__eq__(other)
+        return r if r is NotImplemented else not r
+
+    def __hash__(self):
+        return hash(('band',) + self._transitions)
+
+    def __repr__(self):
+        return (f'LteBand({self.molecule.name!r}, {self.n_trans} transitions at '
+                f'{", ".join(format(t.nu, "g") for t in self._transitions)} Hz, {self.n_lines} lines, name={self.name!r})')
+
+    def tau_main(self, tex, lncol, sigm):
+        """The peak optical depth of every transition, in the band's order: numpy, one value per transition along the
+        first axis, the arguments broadcasting behind it."""
+        return np.stack([t.tau_main(tex, lncol, sigm) for t in self._transitions])
+
+
+def transitions_of(lines):
+    """The `LteLines` of a spectrum's `lines`: those of an `LteBand`, or the one `LteLines` itself."""
+    return lines.transitions if isinstance(lines, LteBand) else (lines,)
+
+
 def check_one_molecule(lines):
-    """The `Molecule` the `LteLines` of a runner share; ValueError if one is no LteLines or they name different ones."""
+    """The `Molecule` the `LteLines` and `LteBand`s of a runner share; ValueError if one is neither or they name
+    different ones."""
     lines = list(lines)
-    if not lines or not all(isinstance(t, LteLines) for t in lines):
-        raise ValueError('the LTE model takes one LteLines per spectrum (Molecule.transition)')
+    if not lines or not all(isinstance(t, (LteLines, LteBand)) for t in lines):
+        raise ValueError('the LTE model takes one LteLines (Molecule.transition) or LteBand (Molecule.band) per spectrum')
     if any(t.molecule != lines[0].molecule for t in lines[1:]):
         raise ValueError('the spectra of an LTE runner share one Molecule (one species, one partition function): '
                          + ', '.join(sorted({t.molecule.name for t in lines})))
@@ -183,20 +278,20 @@ def check_one_molecule(lines):
 
 
 class LteSpectrum(EngineSpectrumMixin, _HyperfineBase):
-    """A spectrum of one transition, `lines` (an `LteLines`).
+    """A spectrum of one transition, `lines` (an `LteLines`), or of several at once (an `LteBand`).
 
     Parameters
     ----------
     xarr : array, Hz, ascending
     data : array, K
     noise : number, K; or one value per channel (inf masks a channel)
-    lines : LteLines
+    lines : LteLines or LteBand
     """
     MODEL = MODEL_LTE
 
     def __init__(self, xarr, data, noise, lines):
-        if not isinstance(lines, LteLines):
-            raise ValueError(f'`lines` must be an LteLines, not {type(lines).__name__}')
+        if not isinstance(lines, (LteLines, LteBand)):
+            raise ValueError(f'`lines` must be an LteLines or an LteBand, not {type(lines).__name__}')
         _HyperfineBase.__init__(self, xarr, data, noise, rest_freq=lines.nu)
         self.lines = lines
         self._attach(-1, lines=lines)
@@ -213,7 +308,7 @@ def lte_predict(s, params):
 
 
 class LteRunner(EngineRunner):
-    """Prior transform + model + log-likelihood of spectra with an `LteLines` each, all of one `Molecule`."""
+    """Prior transform + model + log-likelihood of spectra with an `LteLines` or an `LteBand` each, all of one `Molecule`."""
     MODEL = MODEL_LTE
     N_MODEL = N_PARAMS
 
@@ -226,7 +321,7 @@ class LteRunner(EngineRunner):
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
-        """spec_data: rows [xarr, data, noise, LteLines]."""
+        """spec_data: rows [xarr, data, noise, LteLines or LteBand]."""
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         spec_data = list(spec_data)
         check_one_molecule([row[3] for row in spec_data])

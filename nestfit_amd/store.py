@@ -439,7 +439,8 @@ class HdfStore:
         """The line table of every cube that has one (hyperfine model) under /model_lines/spec<k>: attributes `nu` and
         `name`, datasets `voff` and `tau_wts`.  Nothing for the models whose tables ship with the engine.  The LTE model's
         `LteLines` add the attributes `e_up`, `g_up` and `a_ul`, and their molecule's partition table goes under
-        /model_partition: datasets `temp` and `q`, attribute `name`."""
+        /model_partition: datasets `temp` and `q`, attribute `name`.  A cube with an `LteBand` has the attributes `n_trans`
+        and `name` on its spec<k> and one subgroup trans<j> per transition, each laid out as a single transition's spec<k>."""
         assert self.is_open
         tables = [getattr(dc, 'lines', None) for dc in stack.cubes]
         if all(t is None for t in tables):
@@ -457,17 +458,26 @@ class HdfStore:
             group.attrs.update(name=molecule.name)
             group.create_dataset('temp', data=np.array(molecule.q_temp))
             group.create_dataset('q', data=np.array(molecule.q_val))
-        for k, t in enumerate(tables):
-            group = self.hdf.require_group(f'{MODEL_LINES_GROUP}/spec{k}')
+        def write(path, t):
+            group = self.hdf.require_group(path)
             group.attrs.update(nu=float(t.nu), name='' if t.name is None else t.name)
             if molecule is not None:
                 group.attrs.update(e_up=float(t.e_up), g_up=float(t.g_up), a_ul=float(t.a_ul))
             group.create_dataset('voff', data=np.array(t.voff))
             group.create_dataset('tau_wts', data=np.array(t.tau_wts))
+        for k, t in enumerate(tables):
+            path = f'{MODEL_LINES_GROUP}/spec{k}'
+            if hasattr(t, 'transitions'):                            # an LteBand
+                group = self.hdf.require_group(path)
+                group.attrs.update(n_trans=len(t.transitions), name='' if t.name is None else t.name)
+                for j, tr in enumerate(t.transitions):
+                    write(f'{path}/trans{j}', tr)
+            else:
+                write(path, t)
 
     def read_model_lines(self):
         """The `LineTable`s the store was fitted with, in cube order ([] for a store without any): `LteLines` of the
-        stored `Molecule` where the store has a partition table."""
+        stored `Molecule` where the store has a partition table, an `LteBand` for a spec<k> with the attribute `n_trans`."""
         from .hyperfine import LineTable
         from .lte import Molecule
         assert self.is_open
@@ -478,15 +488,19 @@ class HdfStore:
         if MODEL_PARTITION_GROUP in self.hdf:
             part = self.hdf[MODEL_PARTITION_GROUP]
             molecule = Molecule(part.attrs['name'], np.asarray(part['temp'][...]), np.asarray(part['q'][...]))
+        def read(g):
+            voff, tau_wts, name = np.asarray(g['voff'][...]), np.asarray(g['tau_wts'][...]), g.attrs.get('name') or None
+            if molecule is not None:
+                return molecule.transition(g.attrs['nu'], g.attrs['e_up'], g.attrs['g_up'], g.attrs['a_ul'], voff, tau_wts, name=name)
+            return LineTable(g.attrs['nu'], voff, tau_wts, name=name)
         out = []
         for k in range(len(list(top))):
             g = top[f'spec{k}']
-            voff, tau_wts, name = np.asarray(g['voff'][...]), np.asarray(g['tau_wts'][...]), g.attrs.get('name') or None
-            if molecule is not None:
-                out.append(molecule.transition(g.attrs['nu'], g.attrs['e_up'], g.attrs['g_up'], g.attrs['a_ul'],
-                                               voff, tau_wts, name=name))
+            if 'n_trans' in g.attrs:
+                out.append(molecule.band([read(g[f'trans{j}']) for j in range(int(g.attrs['n_trans']))],
+                                         name=g.attrs.get('name') or None))
             else:
-                out.append(LineTable(g.attrs['nu'], voff, tau_wts, name=name))
+                out.append(read(g))
         return out
 
     # ---- products -----------------------------------------------------------------------------
