@@ -518,11 +518,18 @@ int nfa_sampler_run(nfa_sampler *s, double tol, double efr, int64_t seed, int64_
  * (nfa_sampler_run uses enlarge = 1.5: safety factor on the volume of the ellipsoid that just
  * encloses the live points, before MultiNest's floor X / efr is applied)
  * the same in two steps: begin = live points + first ellipsoids; advance = up to max_chunks groups
- * of check_every rounds (0 = to the end); *n_active = pixels still running (progress, time limits) */
+ * of check_every rounds (0 = to the end); *n_active = pixels still running (progress, time limits).
+ * A pixel stops when its live points could add less than tol to lnZ, at maxiter iterations, when its dead-point slots
+ * are full -- and when all its live points carry one lnL (a constant likelihood, or every draw non-finite and hence
+ * log_zero): nothing can be proposed above such a threshold and the rest of the evidence is exactly L + ln X.  Such
+ * a pixel is done before its first round (n_iter = 0) or after the replacement that made it so. */
 int nfa_sampler_begin(nfa_sampler *s, double tol, double efr, int64_t seed, int64_t maxiter, int upd,
                       double log_zero, int check_every, double enlarge, int method, int n_steps);
 int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active);
 int nfa_sampler_counts(nfa_sampler *s, int64_t *n_iter, int64_t *n_evals, int64_t *rounds);
+/* The first n dead points of pixel p, in the order they died: theta[n][ndim], lnL[n], lnw[n] (ln of the prior mass each
+ * carries), n <= min(n_iter[p], the pixel's dead-point slots).  Asking for more than a pixel holds is NFA_ERR_ARG here,
+ * in nfa_sampler_dead_packed and in nfa_sampler_posterior_packed: the slots behind were never written. */
 int nfa_sampler_dead(nfa_sampler *s, int64_t p, int64_t n, double *theta, double *lnL, double *lnw);
 /* The same for all pixels in one call: offsets[P + 1] with offsets[0] = 0 and offsets[p + 1] - offsets[p] the
  * number of dead points wanted of pixel p (at most min(n_iter[p], cap_iter)); rows offsets[p] .. offsets[p + 1]

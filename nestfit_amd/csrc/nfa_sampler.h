@@ -589,6 +589,23 @@ __device__ __forceinline__ double ns_logaddexp(double a, double b) {
     return m + log1p(exp(-fabs(a - b)));
 }
 
+// A pixel whose live points all carry one lnL is done (nested._plateau): a replacement needs a proposal ABOVE the smallest
+// of them, so its rounds would never end -- and nothing is left to find: the rest of its evidence is exactly L + ln X,
+// the live points' share of the result.  (Every draw non-finite: all log_zero; lines narrower than a channel: the same
+// prediction, zero, everywhere.)  Here before the first round, one wave per pixel; ns_update_kernel holds the same test
+// behind every replacement.
+__global__ void __launch_bounds__(64) ns_plateau_kernel(NsDev S) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    if (p >= S.P) return;
+    const int N = ns_n(S, p);
+    const double *Ll = S.Llive + (long)p * S.N;
+    double mx = -INFINITY, mn = INFINITY;
+    for (int i = lane; i < N; i += 64) { mx = fmax(mx, Ll[i]); mn = fmin(mn, Ll[i]); }
+    mx = ns_wave_max(mx);
+    mn = -ns_wave_max(-mn);
+    if (lane == 0 && mx == mn) S.active[p] = 0;
+}
+
 // Bounding ellipsoid of the live points of pixel p (same arithmetic as _fit_ellipsoids in
 // nestfit_amd/sampler.py): centre = mean, A = chol(cov) * sqrt(max Mahalanobis^2) * growth, the
 // growth bringing the volume up to X / efr where the bounding ellipsoid is smaller than that.
@@ -1251,7 +1268,7 @@ __global__ void __launch_bounds__(NS_UPD_THREADS) NFA_UPD_ATTR ns_update_kernel(
         worst_point(Lmin, w);
         tw = w == w_old ? ct : (lane < S.DT ? S.Tlive[((long)p * NS + w) * S.DT + lane] : 0.0);
         const double remain = Lmax - (double)it / N;
-        done = (ns_logaddexp(lnZ, remain) - lnZ < S.tol) || it >= S.maxiter || it >= cap;
+        done = (ns_logaddexp(lnZ, remain) - lnZ < S.tol) || it >= S.maxiter || it >= cap || Lmax == Lmin;     // (the last: a plateau)
     };
     if (was_walking) {
         // ---- one Metropolis step of every walker (lane = walker), cycle end every n_steps rounds
@@ -1632,6 +1649,7 @@ struct nfa_sampler {
     size_t k_alloc = 0;         // proposal rows allocated per pixel
     long raw_sum = 0, val_sum = 0;   // proposals drawn / evaluated since the last look at the active pixels
     std::vector<int> h_nlive;   // per-pixel live points (empty: d.N for everybody)
+    std::vector<long> h_cap;    // per-pixel dead-point slots (empty: d.cap for everybody)
     std::vector<int> h_active, h_act;
     long rounds = 0;
     int  n_act = 0, check_every = 8;
@@ -1805,6 +1823,16 @@ static int ns_wait_rows(const nfa_sampler *s, int h, hipStream_t st, int *n_rows
     return NFA_OK;
 }
 
+// The dead points every pixel holds, min(n_iter[p], its dead-point slots): the most a read-back may ask for -- the slots
+// behind them were never written
+static int ns_dead_held(const nfa_sampler *s, std::vector<long> &held) {
+    const size_t P = (size_t)s->d.P;
+    held.resize(P);
+    HIP_TRY(hipMemcpy(held.data(), s->d.n_iter, sizeof(long) * P, hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < P; ++p) held[p] = std::min(held[p], s->h_cap.empty() ? s->d.cap : s->h_cap[p]);
+    return NFA_OK;
+}
+
 extern "C" {
 
 int nfa_sampler_destroy(nfa_sampler *s) {
@@ -1884,6 +1912,7 @@ int nfa_sampler_set_pixel_nlive(nfa_sampler *s, const int32_t *nlive, const int6
     HIP_TRY(hipMemcpy(dc, hc.data(), sizeof(long) * P, hipMemcpyHostToDevice));
     d.nlive = dn; d.updp = du; d.capp = dc;       // (only now: the kernels take a null pointer as "everybody the same")
     s->h_nlive = hn;
+    s->h_cap = hc;
     return NFA_OK;
 }
 
@@ -2003,14 +2032,17 @@ int nfa_sampler_begin(nfa_sampler *s, double tol, double efr, int64_t seed, int6
         HIP_TRY(hipFuncSetAttribute((const void *)ns_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_update));
     if (plan.lds_refit > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void *)ns_refit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_refit));
+    if (maxiter > 0) hipLaunchKernelGGL(ns_plateau_kernel, dim3((unsigned)P), dim3(64), 0, st, d);      // (behind the flags' upload)
     ns_launch_refit(s, d, P, 1, st);                             // first ellipsoids
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     s->rounds = 0;
-    s->n_act = maxiter > 0 ? P : 0;
+    // the list of the first rounds: every pixel but the plateaus (the twin's `_begin` drops them in the same place)
+    if (maxiter > 0) HIP_TRY(hipMemcpy(s->h_active.data(), d.active, sizeof(int) * P, hipMemcpyDeviceToHost));
+    s->n_act = 0;
     s->h_act.resize((size_t)P);
-    for (int p = 0; p < P; ++p) s->h_act[p] = p;
-    if (s->n_act) HIP_TRY(hipMemcpy(ns_mut(d.actlist), s->h_act.data(), sizeof(int) * P, hipMemcpyHostToDevice));
+    for (int p = 0; p < P; ++p) if (s->h_active[p]) s->h_act[s->n_act++] = p;
+    if (s->n_act) HIP_TRY(hipMemcpy(ns_mut(d.actlist), s->h_act.data(), sizeof(int) * s->n_act, hipMemcpyHostToDevice));
     s->ran = true;
     return NFA_OK;
 }
@@ -2083,6 +2115,7 @@ int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active_ou
 
 int nfa_sampler_run(nfa_sampler *s, double tol, double efr, int64_t seed, int64_t maxiter, int upd,
                     double log_zero, int check_every) {
+    if (!s) return fail(NFA_ERR_ARG, "null sampler");
     int rc = nfa_sampler_begin(s, tol, efr, seed, maxiter, upd, log_zero, check_every, 1.5, 1, 10 * s->d.D);
     if (rc) return rc;
     return nfa_sampler_advance(s, 0, nullptr);
@@ -2102,7 +2135,11 @@ int nfa_sampler_counts(nfa_sampler *s, int64_t *n_iter, int64_t *n_evals, int64_
 int nfa_sampler_dead(nfa_sampler *s, int64_t p, int64_t n, double *theta, double *lnL, double *lnw) {
     if (!s || !s->ran || p < 0 || p >= s->d.P || n < 0 || n > s->d.cap) return fail(NFA_ERR_ARG, "bad argument");
     if (n == 0) return NFA_OK;
+    if (!theta || !lnL || !lnw) return fail(NFA_ERR_ARG, "bad argument");
     const NsDev &d = s->d;
+    std::vector<long> held;
+    { int rc = ns_dead_held(s, held); if (rc) return rc; }
+    if (n > held[(size_t)p]) return fail(NFA_ERR_ARG, "more dead points asked for than the pixel holds (min(n_iter, cap))");
     HIP_TRY(hipMemcpy(theta, d.deadT + (size_t)p * d.cap * d.DT, sizeof(double) * n * d.DT, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(lnL, d.deadL + (size_t)p * d.cap, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(lnw, d.deadlnw + (size_t)p * d.cap, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -2116,8 +2153,11 @@ int nfa_sampler_dead_packed(nfa_sampler *s, const int64_t *offsets, double *thet
     const NsDev &d = s->d;
     const int P = d.P;
     if (offsets[0] != 0) return fail(NFA_ERR_ARG, "offsets must start at 0");
+    std::vector<long> held;
+    { int rc = ns_dead_held(s, held); if (rc) return rc; }
     for (int p = 0; p < P; ++p)
-        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > d.cap) return fail(NFA_ERR_ARG, "bad offsets");
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > held[(size_t)p])
+            return fail(NFA_ERR_ARG, "bad offsets: more dead points asked for than a pixel holds (min(n_iter, cap))");
     const int64_t total = offsets[P];
     if (total == 0) return NFA_OK;
     NsTemp tmp;
@@ -2143,9 +2183,12 @@ int nfa_sampler_posterior_packed(nfa_sampler *s, const int64_t *offsets, const d
     const NsDev &d = s->d;
     const int P = d.P;
     if (offsets[0] != 0) return fail(NFA_ERR_ARG, "offsets must start at 0");
+    std::vector<long> held;
+    { int rc = ns_dead_held(s, held); if (rc) return rc; }
     for (int p = 0; p < P; ++p) {
         const int64_t nl = s->h_nlive.empty() ? d.N : s->h_nlive[(size_t)p];
-        if (offsets[p + 1] - offsets[p] < nl || offsets[p + 1] - offsets[p] - nl > d.cap) return fail(NFA_ERR_ARG, "bad offsets");
+        if (offsets[p + 1] - offsets[p] < nl || offsets[p + 1] - offsets[p] - nl > held[(size_t)p])
+            return fail(NFA_ERR_ARG, "bad offsets: a pixel's rows are its live points and at most the dead points it holds (min(n_iter, cap))");
     }
     const int64_t total = offsets[P];
     const size_t n_st = (size_t)P * (6 + 4 * d.DT);

@@ -3,7 +3,7 @@ the same counter-based random stream and the same decisions, so that the same se
 device's specification: the GPU sampler tests assert "device = twin, decision for decision".  One state (`TwinState`,
 fields named like `NsDev`'s) and one function per stage of the device: `_begin` (nfa_sampler_begin + ns_init_live_kernel),
 `_refit` (ns_refit / ns_refit_multi / ns_shear_fit), `_propose` (ns_propose_one), `_update_reject`, `_walk_step` and
-`_replace` (the scan branch, the walk branch and the replacement of ns_update_kernel), `_chunk_kr` (ns_chunk_kr);
+`_replace` (the scan branch, the walk branch and the replacement of ns_update_kernel), `_plateau` (ns_plateau_kernel and the same test after a replacement), `_chunk_kr` (ns_chunk_kr);
 `run_nested` is the loop over rounds around them.  `nestfit_amd.sampler` imports from here, never the other way round."""
 import math
 import types
@@ -463,8 +463,19 @@ def _assemble(ndim, nlive, n_iter, n_evals, dead, Tlive, Llive, tol=None):
                                     n_evals[p], n_iter[p], Hp))
         if tol is not None:
             remain = Llive[p][:nlive].max() - n_iter[p] / nlive
-            results[-1].truncated = bool(not (np.logaddexp(lnZ_dead, remain) - lnZ_dead < tol))
+            # (a plateau -- every live point at one lnL, `_plateau` -- is a finished run: what is left is exactly L + ln X)
+            results[-1].truncated = bool(not (np.logaddexp(lnZ_dead, remain) - lnZ_dead < tol) and not _plateau(Llive[p][:nlive]))
     return results
+
+
+def _plateau(Llive):
+    """The stop rule beside `tol`, `maxiter` and the dead-point cap: live points that all carry one lnL.  No proposal can
+    be above the threshold of such a pixel (a replacement needs L > min), so its run would never end; and nothing is
+    left to find -- the rest of its evidence is exactly L + ln X, which the live points' share of `_assemble` adds.  (A
+    pixel whose every draw is non-finite is all log_zero; lines narrower than a channel predict exactly zero.)  The
+    device tests the same where it tests the others: ns_plateau_kernel before the first round, ns_update_kernel after
+    every replacement."""
+    return bool(Llive.max() == Llive.min())
 
 
 def _resolve_seed(seed):
@@ -613,6 +624,8 @@ def _begin(loglike, ndim, cv, tol, efr, maxiter, log_zero, chunk, cap_iter, batc
     S.Tlive = T.reshape(P, N, S.DT)
     S.n_evals, S.n_iter, S.cand_base = cv.nl.copy(), np.zeros(P, dtype=np.int64), np.zeros(P, dtype=np.int64)
     S.lnZ, S.active, S.since_fit = np.full(P, -np.inf), np.full(P, maxiter > 0), np.zeros(P, dtype=np.int64)
+    for p in range(P):                                          # (ns_plateau_kernel: such a pixel never enters a round)
+        S.active[p] &= not _plateau(S.Llive[p, :int(cv.nl[p])])
     S.dead = [[] for _ in range(P)]                             # per pixel: theta, lnL, ln w of its dead points
     S.rnd, S.Kr, S.n_chunk, S.b_target = 0, S.K, P, max(P * S.K, int(batch_target))
     S.raw_sum = S.val_sum = 0                                   # proposals drawn / evaluated since the last `_chunk_kr`
@@ -736,7 +749,8 @@ def _replace(S, p, cU, cT, Lk):
     S.n_iter[p] += 1
     S.since_fit[p] += 1
     remain = Llive.max() - S.n_iter[p] / nlive
-    return bool((np.logaddexp(S.lnZ[p], remain) - S.lnZ[p] < S.tol) or S.n_iter[p] >= S.maxiter or S.n_iter[p] >= cap)
+    return bool((np.logaddexp(S.lnZ[p], remain) - S.lnZ[p] < S.tol) or S.n_iter[p] >= S.maxiter or S.n_iter[p] >= cap
+                or _plateau(Llive))
 
 
 def _scan(S, p, cU, cT, cL):
@@ -920,7 +934,7 @@ def run_nested(loglike, ndim, n_pix, nlive=400, tol=0.5, efr=0.3, seed=-1, maxit
         if progress is not None:
             progress(int(S.active.sum()), int(S.n_iter.max()))
             if hasattr(progress, 'detail'):                     # (debugging aid: the round's state)
-                progress.detail(dict(rnd=S.rnd, n_iter=S.n_iter, n_evals=S.n_evals, walk=S.walk, use_cube=S.use_cube, lnvol=S.lnvol,
+                progress.detail(dict(rnd=S.rnd, n_iter=S.n_iter, n_evals=S.n_evals, walk=S.walk, use_cube=S.use_cube, lnvol=S.lnvol, nell=S.nell,
                                      Kr=S.Kr, rj=(S.rj_scan, S.rj_acc, S.rj_raw, S.rj_val), ln_pass=S.ln_pass, Llive=S.Llive,
                                      Ulive=S.Ulive))
     return _finish(S)

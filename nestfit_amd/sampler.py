@@ -45,7 +45,9 @@ def _assemble_packed(nlive, n_iter, n_evals, off, table, tol, stats):
         r = NestedResult.from_stats(table[off[p]:off[p + 1]], stats[p], nl, n_evals[p], n_iter[p])
         if tol is not None:
             remain = stats[p, 4] - n_iter[p] / nl
-            r.truncated = bool(not (np.logaddexp(stats[p, 1], remain) - stats[p, 1] < tol))
+            # (the live rows' -2 lnL: all equal = a plateau, a finished run -- `nested._plateau`)
+            live = table[off[p + 1] - nl:off[p + 1], -2]
+            r.truncated = bool(not (np.logaddexp(stats[p, 1], remain) - stats[p, 1] < tol) and not live.max() == live.min())
         results.append(r)
     return results
 

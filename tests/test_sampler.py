@@ -155,6 +155,44 @@ def test_maxiter_and_logzero():
     assert np.isfinite(r.lnZ) and r.posterior[r.posterior[:, -1] > 1e-6, 0].min() >= 0.2
 
 
+PLATEAU_CHILD = r"""
+import json, sys
+import numpy as np
+from nestfit_amd import sampler
+out = {}
+for name, f in (('zero', lambda pix, T: np.zeros(len(T))), ('nan', lambda pix, T: np.full(len(T), np.nan)),
+                ('step', lambda pix, T: np.where(T[:, 0] < 0.5, 0.0, 1.0))):
+    r = sampler.run_nested(f, 4, 1, nlive=50, seed=1, maxiter=200)[0]
+    out[name] = dict(lnZ=r.lnZ, H=r.information, err=r.lnZ_err, truncated=r.truncated, n_iter=r.n_iter, n_samples=r.n_samples,
+                     max_loglike=r.max_loglike, live=sorted(set((-0.5 * r.posterior[-50:, -2]).tolist())))
+print(json.dumps(out))
+"""
+
+
+def test_a_constant_likelihood_ends_the_run():
+    """Live points that all carry one lnL (`nested._plateau`): no proposal can ever be above the threshold, so before the
+    rule the run never ended (neither `maxiter` nor `tol` is looked at without a replacement) -- hence the child process
+    and its time limit, which is a failure here, not a skip.  With the rule the pixel is done before its first round:
+    lnZ = L + ln 1 exactly, no information, not truncated.  The same for a likelihood that is never finite (all
+    log_zero), and for a plateau that replacements lead to: two levels, the lower one dies out, the run ends there."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    done = subprocess.run([sys.executable, '-c', PLATEAU_CHILD], capture_output=True, text=True, timeout=120,
+                          cwd=str(Path(__file__).resolve().parent.parent))
+    assert done.returncode == 0, done.stderr
+    out = json.loads(done.stdout.strip().splitlines()[-1])
+    zero, nan, step = out['zero'], out['nan'], out['step']
+    assert abs(zero['lnZ']) < 1e-14 and abs(zero['H']) < 1e-14 and zero['err'] < 1e-7
+    assert zero['truncated'] is False and zero['n_iter'] == 0 and zero['n_samples'] == 50 and zero['max_loglike'] == 0.0
+    assert nan['lnZ'] == pytest.approx(nested.LOG_ZERO, rel=1e-15) and abs(nan['H']) < 1e-14
+    assert nan['truncated'] is False and nan['n_iter'] == 0 and nan['max_loglike'] == nested.LOG_ZERO
+    # the step: Z = (1 + e) / 2; the run ends, untruncated and short of maxiter, with every live point on the upper level
+    assert step['live'] == [1.0] and step['truncated'] is False and 0 < step['n_iter'] < 200
+    assert abs(step['lnZ'] - np.log(0.5 * (1.0 + np.e))) < 4 * step['err'] + 0.05
+
+
 class _FakeRunner:
     ndim = n_params = 3
     ncomp = 1
