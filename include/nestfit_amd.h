@@ -230,6 +230,26 @@ int nfa_specset_create_lte_bands(nfa_specset **out, int n_spec, const int64_t *s
                                  int n_q, const double *q_temp, const double *q_val,
                                  const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                                  const double *chan_noise);
+/* LTE mixes: nfa_specset_create_lte_bands with the transitions belonging to n_species (1..4) SPECIES that share a velocity,
+ * a width and an excitation temperature along the line of sight -- a molecule and its isotopologue, the A and E species of
+ * one -- each with a column density and a partition function of its own.  species[t] (0..n_species - 1) is the species of
+ * transition t, one entry per transition like n_lines; n_q[k] the length of species k's partition table, and q_temp and
+ * q_val hold the tables one after the other (sum of n_q entries).  The model stays NFA_MODEL_LTE; the parameters of a
+ * component are 3 + n_species, parameter-major:
+ *     voff, tex, lncol_0, sigm, lncol_1, ..., lncol_{n_species - 1}
+ * and transition g of species k has tau_main of the formula above with nu_g, e_up_g, g_up_g, a_ul_g, lncol_k and Q_k(tex).
+ * Lines and spectrum follow as for a band, all the species' lines in one optical depth.  A prior program for such a set
+ * covers 3 + n_species parameters.  With n_species == 1 this is nfa_specset_create_lte_bands, bit for bit, on its routes.
+ * A set of several species is served like a banded one: the batch entry points, the broker and the callback;
+ * nfa_ring_serve_device refuses it.  Returns NFA_ERR_ARG, with a message, for everything nfa_specset_create_lte_bands
+ * refuses (the same transition twice: within a species), for n_species outside 1..4, a species index outside 0..n_species - 1,
+ * a species without a transition in any spectrum, and a bad partition table, naming the species. */
+int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
+                               const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
+                               const double *e_up, const double *g_up, const double *a_ul,
+                               int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
+                               const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                               const double *chan_noise);
 /* A shipped line table, as a template for nfa_specset_create_lines: model 0 (trans_id 1..9) or 1 (trans_id 1..3);
  * voff and tau_wts take 50 doubles each (zero behind the *n lines), *nu the rest frequency in Hz.  Needs no device. */
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n);

@@ -12,7 +12,7 @@ from .diazenylium import DiazenyliumRunner, DiazenyliumSpectrum, nnhp_predict
 from .gaussian import GaussianRunner, gauss_predict
 from . import ammonia, diazenylium, gaussian, hyperfine, lte
 from .hyperfine import HyperfineRunner, LineTable
-from .lte import LteBand, LteLines, LteRunner, LteSpectrum, Molecule, lte_predict
+from .lte import LteBand, LteBlend, LteLines, LteMix, LteRunner, LteSpectrum, Molecule, lte_predict
 
 # registry like nestfit/models/__init__.py:3-7
 MODELS = {m.NAME: m for m in (ammonia, diazenylium, gaussian)}
@@ -20,8 +20,10 @@ MODELS = {m.NAME: m for m in (ammonia, diazenylium, gaussian)}
 
 def model_module(name):
     """The model module of a store's `model_name`: one of MODELS (the reference's three), `hyperfine`, the model of
-    caller-supplied line tables, or `lte`, one species in LTE across several transitions; None for an unknown name."""
-    return {hyperfine.NAME: hyperfine, lte.NAME: lte}.get(name) or MODELS.get(name)
+    caller-supplied line tables, `lte`, one species in LTE across several transitions, or `LteMix` for 'lte_mix', several
+    species in LTE (the class: the parameter slots every mix shares, `IX_VCEN` and `IX_SIGM`; names and the number of
+    parameters belong to a mix of given species, which a store's root attributes describe); None for an unknown name."""
+    return {hyperfine.NAME: hyperfine, lte.NAME: lte, LteMix.NAME: LteMix}.get(name) or MODELS.get(name)
 
 
 from .prior_constructors import get_irdc_priors, get_synth_priors
@@ -33,5 +35,5 @@ __all__ = [
     'AmmoniaSpectrum', 'AmmoniaRunner', 'amm_predict', 'get_irdc_priors', 'get_synth_priors',
     'DiazenyliumSpectrum', 'DiazenyliumRunner', 'nnhp_predict', 'GaussianRunner', 'gauss_predict',
     'MODELS', 'hyperfine', 'LineTable', 'HyperfineRunner', 'model_module',
-    'lte', 'Molecule', 'LteLines', 'LteBand', 'LteSpectrum', 'LteRunner', 'lte_predict',
+    'lte', 'Molecule', 'LteLines', 'LteBand', 'LteSpectrum', 'LteRunner', 'lte_predict', 'LteBlend', 'LteMix',
 ]

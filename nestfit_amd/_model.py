@@ -59,12 +59,14 @@ def channel_weights(noise, size):
 class _SpecSet:
     """Owner of a device-resident set of spectra (one pixel or a cube)."""
 
-    def __init__(self, xarrs, trans_ids, data, noise, model=MODEL_AMMONIA, rest_freqs=None, lines=None):
+    def __init__(self, xarrs, trans_ids, data, noise, model=MODEL_AMMONIA, rest_freqs=None, lines=None, species=None):
         """xarrs: list of 1-D axes; data [n_pix, sum(sizes)]; noise [n_pix, n_spec], or [n_pix, sum(sizes)]
         for a noise per channel (nfa_specset_create_channel_noise: inf masks a channel).  lines: the hyperfine
         model's `LineTable` of every spectrum (nfa_specset_create_lines; `trans_ids` and `rest_freqs` are then unused), or
         the LTE model's `LteLines` of every spectrum, all of one `Molecule` (nfa_specset_create_lte); where a spectrum covers
-        several transitions, its `LteBand` (nfa_specset_create_lte_bands)."""
+        several transitions, its `LteBand` (nfa_specset_create_lte_bands).  species: the ordered `Molecule`s of an LTE mix,
+        whose `lines` may be `LteBlend`s as well and of any of them (nfa_specset_create_lte_mix); 3 + len(species) parameters
+        per component."""
         self.model = int(model)
         if (self.model in (MODEL_HYPERFINE, MODEL_LTE)) != (lines is not None):
             raise ValueError('the hyperfine model (3) and the LTE model (4), and no other, take `lines`: one LineTable '
@@ -72,16 +74,27 @@ class _SpecSet:
         molecule = None
         if lines is not None:
             from .hyperfine import LineTable
-            from .lte import LteBand, check_one_molecule, transitions_of
+            from .lte import LteBand, LteBlend, check_mix_lines, check_one_molecule, transitions_of
             lines = list(lines)
-            if len(lines) != len(xarrs) or not all(isinstance(t, (LineTable, LteBand)) for t in lines):
+            if species is not None:
+                if self.model != MODEL_LTE:
+                    raise ValueError('`species` belong to the LTE model (4)')
+                if len(lines) != len(xarrs):
+                    raise ValueError('`lines` must hold one LineTable per spectrum')
+                lines = check_mix_lines(species, lines)
+                species = tuple(species)
+            elif len(lines) != len(xarrs) or not all(isinstance(t, (LineTable, LteBand)) for t in lines):
                 raise ValueError('`lines` must hold one LineTable per spectrum')
-            if self.model == MODEL_LTE:
+            elif self.model == MODEL_LTE:
                 molecule = check_one_molecule(lines)
             elif any(isinstance(t, LteBand) for t in lines):
                 raise ValueError('an LteBand belongs to the LTE model (4)')
             trans_ids = [-1] * len(lines)
+        elif species is not None:
+            raise ValueError('`species` come with `lines`')
         self.molecule = molecule
+        self.species = species
+        self.n_model = N_MODEL[self.model] if species is None else 3 + len(species)
         self.lines = lines
         lib = _ffi.engine()
         self.n_spec = len(xarrs)
@@ -106,7 +119,7 @@ class _SpecSet:
         sizes_p = self.sizes.ctypes.data_as(_ffi._lp)
         if lines is not None:                       # the caller's tables: exactly one of the two noise arguments
             self.rest_freqs = np.array([t.nu for t in lines], dtype=np.float64)
-            banded = any(isinstance(t, LteBand) for t in lines)
+            banded = species is not None or any(isinstance(t, LteBand) for t in lines)
             n_trans = np.array([len(transitions_of(t)) for t in lines], dtype=np.int32)
             if banded:                              # one entry per transition, the spectra one after the other
                 lines = [t for band in lines for t in transitions_of(band)]
@@ -118,7 +131,17 @@ class _SpecSet:
                     n_lines.ctypes.data_as(_ffi._ip), _ffi.dptr(freqs), _ffi.dptr(voff), _ffi.dptr(tau_wts))
             tail = (xp, self.n_pix, _ffi.dptr(data),
                     None if self.per_channel else _ffi.dptr(noise), _ffi.dptr(noise) if self.per_channel else None)
-            if molecule is not None:
+            if species is not None:
+                e_up, g_up, a_ul = (np.array([getattr(t, k) for t in lines], dtype=np.float64)
+                                    for k in ('e_up', 'g_up', 'a_ul'))
+                of = np.array([species.index(t.molecule) for t in lines], dtype=np.int32)
+                n_q = np.array([m.n for m in species], dtype=np.int32)
+                q_temp = np.ascontiguousarray(np.concatenate([m.q_temp for m in species]))
+                q_val = np.ascontiguousarray(np.concatenate([m.q_val for m in species]))
+                rc = lib.nfa_specset_create_lte_mix(*head, _ffi.dptr(e_up), _ffi.dptr(g_up), _ffi.dptr(a_ul), len(species),
+                                                    of.ctypes.data_as(_ffi._ip), n_q.ctypes.data_as(_ffi._ip),
+                                                    _ffi.dptr(q_temp), _ffi.dptr(q_val), *tail)
+            elif molecule is not None:
                 e_up, g_up, a_ul = (np.array([getattr(t, k) for t in lines], dtype=np.float64)
                                     for k in ('e_up', 'g_up', 'a_ul'))
                 q_temp, q_val = np.ascontiguousarray(molecule.q_temp), np.ascontiguousarray(molecule.q_val)
@@ -206,11 +229,11 @@ class EngineSpectrumMixin:
     one pixel, runner handles cached per (ncomp, cold, lte)."""
     MODEL = MODEL_AMMONIA
 
-    def _attach(self, trans_id, rest_freq=None, lines=None):
+    def _attach(self, trans_id, rest_freq=None, lines=None, species=None):
         self._ss = _SpecSet([self.xarr], [trans_id], self.data.reshape(1, -1),
                             np.reshape(self.noise, (1, -1)), model=self.MODEL,
                             rest_freqs=None if rest_freq is None else [rest_freq],
-                            lines=None if lines is None else [lines])
+                            lines=None if lines is None else [lines], species=species)
         self.null_lnZ = float(self._ss.null_lnZ()[0, 0])
         self._runners = {}
 
@@ -281,7 +304,8 @@ class EngineRunner(Runner):
             noise = np.array([[s.noise for s in spectra]])
         self._ss = _SpecSet([s.xarr for s in spectra], [s.trans_id for s in spectra], data, noise,
                             model=self.MODEL, rest_freqs=rest_freqs,
-                            lines=[s.lines for s in spectra] if self.MODEL in (MODEL_HYPERFINE, MODEL_LTE) else None)
+                            lines=[s.lines for s in spectra] if self.MODEL in (MODEL_HYPERFINE, MODEL_LTE) else None,
+                            species=getattr(self, 'SPECIES', None))
         self._run = _RunnerHandle(self._ss, utrans, self.ncomp, cold, lte)
         self.baseline_order = baseline_order
         if baseline_order is not None:

@@ -89,9 +89,23 @@ struct BandRec {
     double        t0[MAXSPEC][NFA_BAND_MAXT], de[MAXSPEC][NFA_BAND_MAXT], k[MAXSPEC][NFA_BAND_MAXT];
 };
 
+// LTE mixes (nfa_specset_create_lte_mix): a set whose transitions belong to K = 2..4 species that share voff,
+// tex and sigm, each with a column density (parameter 3 + k of a component for species k >= 1; species 0's stays
+// parameter 2) and a partition table of its own.  One record per such set in device memory (null for every other set)
+// beside a BandRec, which a mix set always owns: the species of every (spectrum, transition) in the band's order, and the
+// partition tables of species 1..K-1 as LteRec holds species 0's (entry k - 1: species k).  Only lte_mix_kernel
+// (nfa_setup.h) reads it.
+#define NFA_LTE_MAXSP 4
+struct MixRec {
+    int           n_species, pad;
+    unsigned char species[MAXSPEC][NFA_BAND_MAXT];
+    int           n_q[NFA_LTE_MAXSP - 1], pad2;
+    double        ln_t[NFA_LTE_MAXSP - 1][NFA_LTE_MAXQ], ln_q[NFA_LTE_MAXSP - 1][NFA_LTE_MAXQ], slope[NFA_LTE_MAXSP - 1][NFA_LTE_MAXQ];
+};
+
 struct SpecDev {
     int     n_spec, ncomp, cold, lte;
-    int     model, npar;                 // NFA_MODEL_*, parameters per component (6 / 4 / 3 / 4 / 4)
+    int     model, npar;                 // NFA_MODEL_*, parameters per component (6 / 4 / 3 / 4 / 4; an LTE mix 3 + K)
     double  rest[MAXSPEC];               // line rest frequency (tables, or Spectrum.rest_freq)
     int     size[MAXSPEC], trans[MAXSPEC], off[MAXSPEC];
     double  nu_min[MAXSPEC], nu_chan[MAXSPEC];
@@ -117,7 +131,8 @@ struct SpecDev {
     const LteRec  *lte_rec;              // the LTE model's transitions and partition function (null for models 0..3)
     const BandRec *band;                 // LTE bands: the transitions inside the spectra (null for every set without a band)
     const double  *band_tau;             // ... and tau_main of [item][component][spectrum][transition] of the launch's lane
-                                         // (lte_band_kernel; set per launch by launch_lnl, null otherwise)
+                                         // (lte_band_kernel or lte_mix_kernel; set per launch by launch_lnl, null otherwise)
+    const MixRec  *mix;                  // LTE mixes: the species of the transitions and their tables (null for every other set)
 };
 
 // Baseline record of a (pixel, spectrum), DESIGN 4.5: [0, 4) m_k(d) = sum_j w_j P_k(u_j) d_j, the Legendre moments of the

@@ -210,6 +210,7 @@ struct nfa_specset {
     LineRow *d_lines = nullptr;                     // the line rows of the spectra: SpecDev.lines
     LteRec  *d_lte = nullptr;                       // the LTE model's record: SpecDev.lte_rec (null for the other models)
     BandRec *d_band = nullptr;                      // LTE bands: SpecDev.band (null for a set without a banded spectrum)
+    MixRec  *d_mix = nullptr;                       // LTE mixes: SpecDev.mix (null for a set of one species)
     int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
     bool    bl_w1 = false;                          // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
 };
@@ -428,8 +429,10 @@ static int launch_bl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_b
 // The caller's line tables of the hyperfine model (nfa_specset_create_lines): n_lines[n_spec], and the spectra's offsets
 // and weights concatenated; `lte`: the LTE model's record as well (nfa_specset_create_lte), null for the hyperfine model;
 // `band`, `line_nu`: a banded LTE set's record and the rest frequency of every line's own transition
-// (nfa_specset_create_lte_bands), null otherwise
-struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; const LteRec *lte; const BandRec *band; const double *line_nu; };
+// (nfa_specset_create_lte_bands), null otherwise; `mix`: the record of a set of several species, which has 3 + n_species
+// parameters per component (nfa_specset_create_lte_mix), null otherwise
+struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; const LteRec *lte; const BandRec *band; const double *line_nu;
+                    const MixRec *mix = nullptr; };
 
 static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *sizes, const int32_t *trans_ids,
                         const double *rest_freqs, const double *const *xarr, int64_t n_pix, const double *data,
@@ -440,6 +443,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     const bool tabled = model == NFA_MODEL_HYPERFINE || model == NFA_MODEL_LTE;      // the caller's line tables
     d.npar = model == NFA_MODEL_DIAZENYLIUM || tabled ? NFA_N2HP_PARAMS
            : model == NFA_MODEL_GAUSSIAN ? NFA_GAUSS_PARAMS : NFA_N_PARAMS;
+    if (model == NFA_MODEL_LTE && lines->mix) d.npar = 3 + lines->mix->n_species;
     std::vector<LineRow> h_lines((size_t)n_spec, LineRow{});          // the line rows of the spectra
     int64_t tot = 0, rows = 0, line0 = 0;
     for (int s = 0; s < n_spec; ++s) {
@@ -531,6 +535,11 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
         HIP_TRY(hipMalloc(&ss->d_band, sizeof(BandRec)));
         HIP_TRY(hipMemcpy(ss->d_band, lines->band, sizeof(BandRec), hipMemcpyHostToDevice));
         d.band = ss->d_band;
+    }
+    if (model == NFA_MODEL_LTE && lines->mix) {
+        HIP_TRY(hipMalloc(&ss->d_mix, sizeof(MixRec)));
+        HIP_TRY(hipMemcpy(ss->d_mix, lines->mix, sizeof(MixRec), hipMemcpyHostToDevice));
+        d.mix = ss->d_mix;
     }
     if (chan_noise) {
         HIP_TRY(hipMalloc(&ss->d_w, sizeof(double) * tot * n_pix));
@@ -719,6 +728,78 @@ int nfa_specset_create_lte(nfa_specset **out, int n_spec, const int64_t *sizes, 
     return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data, noise, nullptr, &lt);
 }
 
+// What the bands creator and the mix creator share: the checks per transition, and the spectra's transitions in the engine's
+// order with their lines one after the other -- the band record, the reference transitions' numbers for the set-up stage
+// (rec, s_rest) and the flattened line arrays.  `species` (null: one species): the species of every transition, which goes
+// into the mix record in the band's order; the same transition twice is then refused within a species.
+struct BandLayout {
+    LteRec rec = {};
+    BandRec band = {};
+    MixRec mix = {};
+    std::vector<int32_t> s_lines;
+    std::vector<double> s_rest, l_voff, l_wts, l_nu;
+};
+static int band_layout(BandLayout &L, int n_spec, const int32_t *n_trans, const int32_t *n_lines, const double *trans_freqs,
+                       const double *voff, const double *tau_wts, const double *e_up, const double *g_up, const double *a_ul,
+                       const int32_t *species) {
+    // the spectra's transitions in the engine's order -- ascending lower-level energy, then rest frequency, then the caller's
+    // order -- and their lines one after the other: what the caller's order of a spectrum's transitions cannot change
+    L.s_lines.assign((size_t)n_spec, 0);
+    L.s_rest.assign((size_t)n_spec, 0.0);
+    int64_t tr0 = 0, l0 = 0;
+    for (int s = 0; s < n_spec; ++s) {
+        const int nt = n_trans[s];
+        std::vector<int64_t> first((size_t)nt);                     // the first line of every transition
+        std::vector<double> e_low((size_t)nt);
+        int total = 0;
+        for (int j = 0; j < nt; ++j) {
+            const int64_t t = tr0 + j;
+            const std::string at = " (spectrum " + std::to_string(s) + ", transition " + std::to_string(j) + ")";
+            first[j] = l0;
+            if (n_lines[t] >= 1 && n_lines[t] <= NFA_MAX_HF_N && total + n_lines[t] > NFA_MAX_HF_N)
+                return fail(NFA_ERR_ARG, "the transitions of a spectrum must have at most 50 lines together (spectrum " + std::to_string(s) + ")");
+            int rc = check_one_table(n_lines[t], trans_freqs[t], voff + l0, tau_wts + l0, at); if (rc) return rc;
+            rc = check_one_transition(e_up[t], g_up[t], a_ul[t], n_lines[t], tau_wts + l0, at); if (rc) return rc;
+            for (int i = 0; i < j; ++i)
+                if ((!species || species[tr0 + i] == species[t]) && trans_freqs[tr0 + i] == trans_freqs[t] && e_up[tr0 + i] == e_up[t] &&
+                    g_up[tr0 + i] == g_up[t] && a_ul[tr0 + i] == a_ul[t])
+                    return fail(NFA_ERR_ARG, (species ? "a spectrum lists the same transition of a species twice" : "a spectrum lists the same transition twice") + at);
+            e_low[j] = e_up[t] - NFA_H * trans_freqs[t] / NFA_KB;
+            total += n_lines[t];
+            l0 += n_lines[t];
+        }
+        std::vector<int> order((size_t)nt);
+        for (int j = 0; j < nt; ++j) order[j] = j;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+            return e_low[a] != e_low[b] ? e_low[a] < e_low[b] : trans_freqs[tr0 + a] < trans_freqs[tr0 + b];
+        });
+        const int64_t r = tr0 + order[0];                           // the reference transition
+        const double ref_t0 = NFA_H * trans_freqs[r] / NFA_KB;
+        const double ref_k = g_up[r] * a_ul[r] / (trans_freqs[r] * trans_freqs[r] * trans_freqs[r]);
+        L.s_rest[s] = trans_freqs[r];
+        L.rec.e_up[s] = e_up[r]; L.rec.g_up[s] = g_up[r]; L.rec.a_ul[s] = a_ul[r];
+        L.band.n_trans[s] = nt;
+        int line = 0;
+        for (int g = 0; g < nt; ++g) {
+            const int64_t t = tr0 + order[g];
+            const double nu = trans_freqs[t], tg = NFA_H * nu / NFA_KB;
+            L.band.t0[s][g] = tg;
+            L.band.de[s][g] = (e_up[t] - tg) - (e_up[r] - ref_t0);
+            L.band.k[s][g] = (g_up[t] * a_ul[t] / (nu * nu * nu)) / ref_k;
+            if (species) L.mix.species[s][g] = (unsigned char)species[t];
+            for (int i = 0; i < n_lines[t]; ++i, ++line) {
+                L.band.grp[s][line] = (unsigned char)g;
+                L.l_voff.push_back(voff[first[order[g]] + i]);
+                L.l_wts.push_back(tau_wts[first[order[g]] + i]);
+                L.l_nu.push_back(nu);
+            }
+        }
+        L.s_lines[s] = line;
+        tr0 += nt;
+    }
+    return NFA_OK;
+}
+
 int nfa_specset_create_lte_bands(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
                                  const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
                                  const double *e_up, const double *g_up, const double *a_ul,
@@ -741,67 +822,75 @@ int nfa_specset_create_lte_bands(nfa_specset **out, int n_spec, const int64_t *s
         return nfa_specset_create_lte(out, n_spec, sizes, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, n_q, q_temp, q_val,
                                       xarr, n_pix, data, noise, chan_noise);
     if (!e_up || !g_up || !a_ul || !q_temp || !q_val) return fail(NFA_ERR_ARG, "null argument");
-    LteRec rec = {};
-    BandRec band = {};
-    // the spectra's transitions in the engine's order -- ascending lower-level energy, then rest frequency, then the caller's
-    // order -- and their lines one after the other: what the caller's order of a spectrum's transitions cannot change
-    std::vector<int32_t> s_lines((size_t)n_spec);
-    std::vector<double> s_rest((size_t)n_spec), l_voff, l_wts, l_nu;
-    int64_t tr0 = 0, l0 = 0;
-    for (int s = 0; s < n_spec; ++s) {
-        const int nt = n_trans[s];
-        std::vector<int64_t> first((size_t)nt);                     // the first line of every transition
-        std::vector<double> e_low((size_t)nt);
-        int total = 0;
-        for (int j = 0; j < nt; ++j) {
-            const int64_t t = tr0 + j;
-            const std::string at = " (spectrum " + std::to_string(s) + ", transition " + std::to_string(j) + ")";
-            first[j] = l0;
-            if (n_lines[t] >= 1 && n_lines[t] <= NFA_MAX_HF_N && total + n_lines[t] > NFA_MAX_HF_N)
-                return fail(NFA_ERR_ARG, "the transitions of a spectrum must have at most 50 lines together (spectrum " + std::to_string(s) + ")");
-            int rc = check_one_table(n_lines[t], trans_freqs[t], voff + l0, tau_wts + l0, at); if (rc) return rc;
-            rc = check_one_transition(e_up[t], g_up[t], a_ul[t], n_lines[t], tau_wts + l0, at); if (rc) return rc;
-            for (int i = 0; i < j; ++i)
-                if (trans_freqs[tr0 + i] == trans_freqs[t] && e_up[tr0 + i] == e_up[t] && g_up[tr0 + i] == g_up[t] && a_ul[tr0 + i] == a_ul[t])
-                    return fail(NFA_ERR_ARG, "a spectrum lists the same transition twice" + at);
-            e_low[j] = e_up[t] - NFA_H * trans_freqs[t] / NFA_KB;
-            total += n_lines[t];
-            l0 += n_lines[t];
-        }
-        std::vector<int> order((size_t)nt);
-        for (int j = 0; j < nt; ++j) order[j] = j;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-            return e_low[a] != e_low[b] ? e_low[a] < e_low[b] : trans_freqs[tr0 + a] < trans_freqs[tr0 + b];
-        });
-        const int64_t r = tr0 + order[0];                           // the reference transition
-        const double ref_t0 = NFA_H * trans_freqs[r] / NFA_KB;
-        const double ref_k = g_up[r] * a_ul[r] / (trans_freqs[r] * trans_freqs[r] * trans_freqs[r]);
-        s_rest[s] = trans_freqs[r];
-        rec.e_up[s] = e_up[r]; rec.g_up[s] = g_up[r]; rec.a_ul[s] = a_ul[r];
-        band.n_trans[s] = nt;
-        int line = 0;
-        for (int g = 0; g < nt; ++g) {
-            const int64_t t = tr0 + order[g];
-            const double nu = trans_freqs[t], tg = NFA_H * nu / NFA_KB;
-            band.t0[s][g] = tg;
-            band.de[s][g] = (e_up[t] - tg) - (e_up[r] - ref_t0);
-            band.k[s][g] = (g_up[t] * a_ul[t] / (nu * nu * nu)) / ref_k;
-            for (int i = 0; i < n_lines[t]; ++i, ++line) {
-                band.grp[s][line] = (unsigned char)g;
-                l_voff.push_back(voff[first[order[g]] + i]);
-                l_wts.push_back(tau_wts[first[order[g]] + i]);
-                l_nu.push_back(nu);
-            }
-        }
-        s_lines[s] = line;
-        tr0 += nt;
-    }
-    int rc = lte_partition_fill(rec, n_q, q_temp, q_val); if (rc) return rc;
-    const LineTables lt = {s_lines.data(), l_voff.data(), l_wts.data(), &rec, &band, l_nu.data()};
+    BandLayout L;
+    int rc = band_layout(L, n_spec, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, nullptr); if (rc) return rc;
+    rc = lte_partition_fill(L.rec, n_q, q_temp, q_val); if (rc) return rc;
+    const LineTables lt = {L.s_lines.data(), L.l_voff.data(), L.l_wts.data(), &L.rec, &L.band, L.l_nu.data()};
     if (chan_noise)
-        return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, s_rest.data(), xarr, n_pix, data,
+        return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data,
                                             chan_noise, &lt);
-    return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, s_rest.data(), xarr, n_pix, data, noise, nullptr, &lt);
+    return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data, noise, nullptr, &lt);
+}
+
+int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
+                               const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
+                               const double *e_up, const double *g_up, const double *a_ul,
+                               int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
+                               const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                               const double *chan_noise) {
+    if (!out || !sizes || !n_trans || !n_lines || !trans_freqs || !voff || !tau_wts || !xarr || !data || !species || !n_q)
+        return fail(NFA_ERR_ARG, "null argument");
+    if (n_species < 1 || n_species > NFA_LTE_MAXSP) return fail(NFA_ERR_ARG, "n_species must be in 1..4");
+    if ((noise != nullptr) == (chan_noise != nullptr))
+        return fail(NFA_ERR_ARG, "exactly one of noise and chan_noise must be given");
+    if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
+    int64_t n_all = 0;
+    for (int s = 0; s < n_spec; ++s) {
+        if (n_trans[s] < 1 || n_trans[s] > NFA_BAND_MAXT)
+            return fail(NFA_ERR_ARG, "a spectrum must have 1..8 transitions (spectrum " + std::to_string(s) + ")");
+        n_all += n_trans[s];
+    }
+    bool seen[NFA_LTE_MAXSP] = {};
+    for (int64_t t = 0; t < n_all; ++t) {
+        if (species[t] < 0 || species[t] >= n_species)
+            return fail(NFA_ERR_ARG, "a species index must be in 0..n_species - 1 (transition " + std::to_string(t) + ")");
+        seen[species[t]] = true;
+    }
+    for (int k = 0; k < n_species; ++k)
+        if (!seen[k])
+            return fail(NFA_ERR_ARG, "a species without a transition in any spectrum: its column density would be unconstrained (species "
+                                     + std::to_string(k) + ")");
+    // one species: the bands creator's set, bit for bit, on its routes
+    if (n_species == 1)
+        return nfa_specset_create_lte_bands(out, n_spec, sizes, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul,
+                                            n_q[0], q_temp, q_val, xarr, n_pix, data, noise, chan_noise);
+    if (!e_up || !g_up || !a_ul || !q_temp || !q_val) return fail(NFA_ERR_ARG, "null argument");
+    BandLayout L;
+    LteRec &rec = L.rec;
+    MixRec &mix = L.mix;
+    mix.n_species = n_species;
+    int rc = band_layout(L, n_spec, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, species); if (rc) return rc;
+    // the partition tables: species 0's where the set-up stage reads it, the others' in the mix record
+    int64_t q0 = 0;
+    for (int k = 0; k < n_species; ++k) {
+        LteRec one = {};
+        const int nq = n_q[k];
+        rc = lte_partition_fill(k == 0 ? rec : one, nq, q_temp + q0, q_val + q0);
+        if (rc) { const std::string why = g_err; return fail(rc, why + " (species " + std::to_string(k) + ")"); }
+        if (k > 0) {
+            mix.n_q[k - 1] = nq;
+            std::copy(one.ln_t, one.ln_t + NFA_LTE_MAXQ, mix.ln_t[k - 1]);
+            std::copy(one.ln_q, one.ln_q + NFA_LTE_MAXQ, mix.ln_q[k - 1]);
+            std::copy(one.slope, one.slope + NFA_LTE_MAXQ, mix.slope[k - 1]);
+        }
+        q0 += nq;
+    }
+    LineTables lt = {L.s_lines.data(), L.l_voff.data(), L.l_wts.data(), &rec, &L.band, L.l_nu.data()};
+    lt.mix = &mix;
+    if (chan_noise)
+        return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data,
+                                            chan_noise, &lt);
+    return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data, noise, nullptr, &lt);
 }
 
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n) {
@@ -822,7 +911,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_xarr); (void)hipFree(ss->d_t0); (void)hipFree(ss->d_tbg); (void)hipFree(ss->d_data); (void)hipFree(ss->d_noise);
     (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq);
     (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl); (void)hipFree(ss->d_lines);
-    (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band);
+    (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
 }
@@ -1075,7 +1164,7 @@ int nfa_runner_create(nfa_runner **out, nfa_specset *ss, nfa_priors *priors, int
     if (!out || !ss) return fail(NFA_ERR_ARG, "null argument");
     if (ncomp < 1 || ncomp > MAXCOMP) return fail(NFA_ERR_ARG, "ncomp must be in 1..10");   // ammonia.pyx:401
     if (priors && priors->prog.n_param != ss->dev.npar)
-        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+, hyperfine and LTE, 3 Gaussian)");
+        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+, hyperfine and LTE, 3 Gaussian, 3 + the species of an LTE mix)");
     int rc = engine_init(); if (rc) return rc;
     nfa_runner *r = new nfa_runner();
     r->ss = ss; r->pr = priors; r->ncomp = ncomp; r->cold = cold ? 1 : 0; r->lte = lte ? 1 : 0;
@@ -1221,9 +1310,18 @@ static int launch_setup(nfa_runner *r, int64_t B, bool has_prior, int slot, int 
 
 // LTE bands: tau_main of every (item, component, spectrum, transition) of the B items whose records the set-up stage has
 // just written on this lane (lte_band_kernel, nfa_setup.h), one small launch between the two stages
+// An LTE mix: lte_mix_kernel in its place, which also reads the column densities of the further species from the theta
+// of the batches in r->cur_group (written back by the set-up launch before it on this lane)
 static int launch_band(nfa_runner *r, int slot, int64_t B) {
     const int n_spec = r->ss->dev.n_spec;
     const int64_t lanes = B * r->ncomp * n_spec * NFA_BAND_MAXT;
+    if (r->ss->dev.mix) {
+        hipLaunchKernelGGL(lte_mix_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, r->lanes[slot],
+                           (const BandRec *)r->ss->d_band, (const MixRec *)r->ss->d_mix, (const LteRec *)r->ss->d_lte,
+                           (const double *)r->d_D[slot], r->d_band[slot], r->cur_group, (long)B, r->ncomp, n_spec, r->ss->dev.npar);
+        HIP_TRY(hipGetLastError());
+        return NFA_OK;
+    }
     hipLaunchKernelGGL(lte_band_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, r->lanes[slot],
                        (const BandRec *)r->ss->d_band, (const double *)r->d_D[slot], r->d_band[slot], (long)B, r->ncomp, n_spec);
     HIP_TRY(hipGetLastError());

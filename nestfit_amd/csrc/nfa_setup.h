@@ -758,3 +758,60 @@ lte_band_kernel(const BandRec *__restrict__ R, const double *__restrict__ D, dou
     }
     T[i] = out;
 }
+
+// ---------------------------------------------------------------------------
+//  lte_mix_kernel: LTE mixes (MixRec), in lte_band_kernel's place for the sets that have species beside
+//  species 0.  The set-up stage has written tau_main of every spectrum's reference transition 0 AS IF IT WERE OF SPECIES 0
+//  (transition 0's constants, lncol_0, Q_0: the stage knows no species); a transition g of species k gets
+//      T[b][c][s][g] = [the band's ratio to transition 0, as lte_band_kernel forms it; nothing for g = 0]
+//                    . 10^(lncol_k - lncol_0) exp(ln Q_0(tex) - ln Q_k(tex))                       (k != 0 only)
+//  which is the LTE formula for g with species k's column density and partition function: it is linear in N / Q.  The
+//  extra factor is finite and positive while |lncol_k - lncol_0| stays below about 300 (exp10 neither overflows nor
+//  underflows: any sensible prior), so the band's bounds hold there; beyond it 0 * inf = NaN is possible where tau_ref has
+//  underflowed.  tau_ref is formed with lncol_0: for a cold component it can underflow to 0 where species k's own optical
+//  depth, at a much larger lncol_k, would not -- the result is then 0, not that depth.  For species 0 the arithmetic is the
+//  band's, operation for operation.  ln Q of a species: derive_lte_lane's scan over its table.  The column densities are not in the records:
+//  they are read from the batch's theta, which the set-up stage has written back to U on this stream (predict: U holds
+//  theta as given) -- item b of the launch is row b - c each of batch c = group_of(b), a row npar ncomp doubles.
+__device__ __forceinline__ double lte_ln_q(int n_q, const double *__restrict__ ln_t, const double *__restrict__ ln_q,
+                                           const double *__restrict__ slope, double ln_tex) {
+    int k = 0;
+    for (int i = 1; i < n_q - 1; ++i) k += ln_tex >= ln_t[i] ? 1 : 0;
+    return ln_q[k] + slope[k] * (ln_tex - ln_t[k]);
+}
+__global__ void __launch_bounds__(256)
+lte_mix_kernel(const BandRec *__restrict__ R, const MixRec *__restrict__ M, const LteRec *__restrict__ L,
+               const double *__restrict__ D, double *__restrict__ T, BatchGroup grp, long B, int ncomp, int nspec, int npar) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * ncomp * nspec * NFA_BAND_MAXT) return;
+    const int g = (int)(i % NFA_BAND_MAXT);
+    const long u = i / NFA_BAND_MAXT;
+    const int s = (int)(u % nspec);
+    const long bc = u / nspec;
+    const int c = (int)(bc % ncomp);
+    const long b = bc / ncomp;
+    const double *Db = D + b * drec_size(ncomp, nspec);
+    const double tau0 = Db[4 * ncomp + (c * nspec + s) * DREC_CS + DK_TMAIN];
+    double out = tau0;
+    if (g >= R->n_trans[s]) out = 0.0;
+    else {
+        const double tex = Db[c * 4];
+        if (g > 0) {                                              // lte_band_kernel's lines
+            const double de = R->de[s][g], q = de / tex, rem = __builtin_fma(-q, tex, de);
+            const double e = exp(-q);
+            const double boltz = e == 0.0 ? 0.0 : e * (1.0 - rem / tex);
+            out = tau0 * R->k[s][g] * boltz * expm1(-R->t0[s][g] / tex) / expm1(-R->t0[s][0] / tex);
+        }
+        const int k = M->species[s][g];
+        if (k > 0) {
+            const int cg = group_of(grp, b);
+            const double *th = grp.U[cg] + (b - (long)cg * grp.each) * (npar * ncomp);
+            const double dcol = th[(3 + k) * ncomp + c] - th[2 * ncomp + c];
+            const double ln_tex = log(tex);
+            const double dq = lte_ln_q(L->n_q, L->ln_t, L->ln_q, L->slope, ln_tex)
+                            - lte_ln_q(M->n_q[k - 1], M->ln_t[k - 1], M->ln_q[k - 1], M->slope[k - 1], ln_tex);
+            out = out * exp10(dcol) * exp(dq);
+        }
+    }
+    T[i] = out;
+}

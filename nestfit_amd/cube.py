@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import N_MODEL, _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order
 from .core import _as_inplace_matrix
 
 
@@ -47,13 +47,22 @@ class CubeRunner:
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
-                 model=0, rest_freqs=None, baseline_order=None, lines=None):
+                 model=0, rest_freqs=None, baseline_order=None, lines=None, species=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
-        transitions, per spectrum, all of one `Molecule`)."""
+        transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
+        spectrum of the ordered `Molecule`s `species` -- without `species`, lines of several molecules take them in the order of
+        their first appearance).  An LTE mix has 3 + len(species) parameters per component."""
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
-        self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs, lines=lines)
+        if species is None and int(model) == 4 and lines is not None:
+            from .lte import LteBand, LteBlend, LteLines, lines_species
+            lines = list(lines)
+            if all(isinstance(t, (LteLines, LteBand, LteBlend)) for t in lines):
+                found = lines_species(lines)
+                if len(found) > 1 or any(isinstance(t, LteBlend) for t in lines):
+                    species = found
+        self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs, lines=lines, species=species)
         self._run = _RunnerHandle(self._ss, utrans, ncomp, cold, lte)
         self.baseline_order = baseline_order
         if baseline_order is not None:
@@ -61,7 +70,7 @@ class CubeRunner:
         self._data, self._noise = data, noise                # (fit_baseline)
         self.utrans = utrans
         self.ncomp = int(ncomp)
-        self.n_model = N_MODEL[int(model)]
+        self.n_model = self._ss.n_model                      # (an LTE mix: from the species of its lines, not from N_MODEL)
         self.n_params = self.ndim = self.n_model * self.ncomp
         self.n_pix = self._ss.n_pix
         self.n_spec = self._ss.n_spec

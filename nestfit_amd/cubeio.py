@@ -300,11 +300,12 @@ class DataCube:
     anything with its attributes); `noise_map` a number or a noise-map object."""
 
     def __init__(self, cube, noise_map, trans_id=None, lines=None):
-        """lines: the cube's `LineTable` (hyperfine model), `LteLines` or `LteBand` (LTE model), the alternative to `trans_id`."""
+        """lines: the cube's `LineTable` (hyperfine model), `LteLines` or `LteBand` (LTE model) or `LteBlend` (LTE mix), the
+        alternative to `trans_id`."""
         if lines is not None:
             from .hyperfine import LineTable
-            from .lte import LteBand
-            if trans_id is not None or not isinstance(lines, (LineTable, LteBand)):
+            from .lte import LteBand, LteBlend
+            if trans_id is not None or not isinstance(lines, (LineTable, LteBand, LteBlend)):
                 raise ValueError('a cube takes a trans_id or a LineTable (lines=), not both')
         self.trans_id = trans_id
         self.lines = lines

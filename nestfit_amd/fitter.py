@@ -16,7 +16,7 @@ from . import sampler
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
-_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4}
+_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4, 'lte_mix': 4}
 
 
 class _RunInfo:
@@ -67,8 +67,10 @@ class CubeFitter:
         nlive, kw) -> (results, null_lnZ, n_chan_tot: one number, or one per pixel) that fits the given pixels some other way (the
         tests plug in the numpy twin of the sampler fed by the CPU oracle, so that the driver logic
         runs without a GPU)."""
-        model = inspect.getmodule(runner_cls)
+        # the model's description: the runner class's own where it has one (an LteMix's Runner: MODEL_INFO), else its module
+        model = getattr(runner_cls, 'MODEL_INFO', None) or inspect.getmodule(runner_cls)
         self.model_id, self.n_model = _MODEL_ID[model.NAME], model.N
+        self.species = getattr(model, 'species', None)   # an LTE mix: the ordered molecules (to_device, the store)
         self.stack, self.utrans, self.runner_cls = stack, utrans, runner_cls
         self.runner_kwargs = dict(runner_kwargs or {})
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
@@ -143,8 +145,9 @@ class CubeFitter:
 
     def _fit_on_device(self, lon, lat, ncomp, nlive, kw):
         with self._tree_lock:
+            kwargs = self.runner_kwargs if self.species is None else dict(self.runner_kwargs, species=self.species)
             runner, rlon, rlat = self.stack.to_device(self.utrans, ncomp=ncomp, lon=lon, lat=lat,
-                                                      model=self.model_id, **self.runner_kwargs)
+                                                      model=self.model_id, **kwargs)
         assert np.array_equal(rlon, lon) and np.array_equal(rlat, lat)
         # the sampler keeps every dead point of every pixel on the device: fit the group in passes that fit
         # the memory budget (a pass's pixels keep their slot numbers' random streams; the seed moves on)
@@ -230,7 +233,7 @@ class CubeFitter:
             store.insert_header(self.stack)
         store.insert_fitter_pars(self)
         store.insert_model_metadata(self.runner_cls)
-        store.insert_model_lines(self.stack)
+        store.insert_model_lines(self.stack, species=self.species)
         todo = range(store.nchunks) if rank is None else [0]
         written = {}
         for k in todo:

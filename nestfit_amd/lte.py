@@ -23,6 +23,16 @@ lines together.  Line i of transition g then has
 
 and the spectrum follows from all the lines together, blended or not.  The parameters stay the four above.
 
+Several SPECIES that share voff, tex and sigm along the line of sight -- a molecule and its isotopologue, whose ladder
+lies inside the main one's window and fixes its optical depth; the A and E species of one molecule -- are one fit with a
+column density per species: `LteMix(species)` describes the model of an ordered list of 1..4 `Molecule`s, an `LteBlend`
+the transitions of any of them that one spectrum covers.  Parameters per component, parameter-major, 3 + K of them:
+
+    voff, tex, lncol (species 0), sigm, lncol2 (species 1), ..., lncolK (species K - 1)
+
+and a transition of species k has the tau_main above with lncol_k and Q_k(tex).  `LteBand`, `LteRunner` and
+`check_one_molecule` stay what they were: one species.
+
 No molecular data ship with this module: rest frequencies, level energies, Einstein coefficients and the partition
 function come from a catalogue of the user's.
 """
@@ -34,6 +44,7 @@ from .hyperfine import CKMS, MAX_LINES, LineTable
 
 N_PARAMS = 4
 MAX_TRANS = 8             # NFA_BAND_MAXT
+MAX_SPECIES = 4           # NFA_LTE_MAXSP
 MAX_Q = 64                # NFA_LTE_MAXQ
 H_CGS = 6.62607015e-27    # csrc/nh3_data.h: NFA_H, NFA_KB, NFA_CCMS
 KB_CGS = 1.380649e-16
@@ -260,9 +271,82 @@ class LteBand:
         return np.stack([t.tau_main(tex, lncol, sigm) for t in self._transitions])
 
 
+class LteBlend:
+    """The transitions that one spectrum covers, of ANY `Molecule`s: a sequence of 1..8 `LteLines` in the caller's
+    order, at most 50 lines together, no transition of a molecule twice.  For an `LteMix`; shaped like an `LteBand`:
+    immutable, compared by value (the transitions in their order; the name is a label) and hashable; everything the
+    engine would refuse raises ValueError here.  The order of the transitions does not change the model."""
+    __slots__ = ('_transitions', '_name')
+
+    def __init__(self, transitions, name=None):
+        try:
+            transitions = tuple(transitions)
+        except TypeError:
+            raise ValueError('a blend takes a sequence of LteLines') from None
+        if not all(isinstance(t, LteLines) for t in transitions):
+            raise ValueError('a blend takes LteLines (Molecule.transition), one per transition')
+        if not 1 <= len(transitions) <= MAX_TRANS:
+            raise ValueError(f'a blend must have 1..{MAX_TRANS} transitions, not {len(transitions)}')
+        n_lines = sum(t.n for t in transitions)
+        if n_lines > MAX_LINES:
+            raise ValueError(f'the transitions of a blend must have at most {MAX_LINES} lines together, not {n_lines}')
+        keys = [(t.molecule, t.nu, t.e_up, t.g_up, t.a_ul) for t in transitions]
+        if len(set(keys)) != len(keys):
+            raise ValueError('a blend lists the same transition (nu, e_up, g_up, a_ul) of a molecule twice')
+        for key, value in (('_transitions', transitions), ('_name', None if name is None else str(name))):
+            object.__setattr__(self, key, value)
+
+    transitions = property(lambda self: self._transitions)
+    name = property(lambda self: self._name)
+    n_trans = property(lambda self: len(self._transitions))
+    n_lines = property(lambda self: sum(t.n for t in self._transitions))
+    n = n_lines                                                      # as a LineTable counts: the lines of the spectrum
+    nu = property(lambda self: self._transitions[0].nu)             # the first transition's: axes and labels
+
+    @property
+    def molecules(self):
+        """The distinct molecules of the transitions, in the order of their first appearance."""
+        out = []
+        for t in self._transitions:
+            if t.molecule not in out:
+                out.append(t.molecule)
+        return tuple(out)
+
+    def __setattr__(self, key, value):
+        raise AttributeError('an LteBlend is immutable')
+
+    def __delattr__(self, key):
+        raise AttributeError('an LteBlend is immutable')
+
+    def __len__(self):
+        return len(self._transitions)
+
+    def __getitem__(self, k):
+        return self._transitions[k]
+
+    def __iter__(self):
+        return iter(self._transitions)
+
+    def __eq__(self, other):
+        if not isinstance(other, LteBlend):
+            return NotImplemented
+        return self._transitions == other._transitions
+
+    def __ne__(self, other):
+        r = self.__eq__(other)
+        return r if r is NotImplemented else not r
+
+    def __hash__(self):
+        return hash(('blend',) + self._transitions)
+
+    def __repr__(self):
+        return (f'LteBlend({", ".join(repr(m.name) for m in self.molecules)}: {self.n_trans} transitions at '
+                f'{", ".join(format(t.nu, "g") for t in self._transitions)} Hz, {self.n_lines} lines, name={self.name!r})')
+
+
 def transitions_of(lines):
-    """The `LteLines` of a spectrum's `lines`: those of an `LteBand`, or the one `LteLines` itself."""
-    return lines.transitions if isinstance(lines, LteBand) else (lines,)
+    """The `LteLines` of a spectrum's `lines`: those of an `LteBand` or an `LteBlend`, or the one `LteLines` itself."""
+    return lines.transitions if isinstance(lines, (LteBand, LteBlend)) else (lines,)
 
 
 def check_one_molecule(lines):
@@ -366,3 +450,181 @@ TEX_LABELS_WITH_UNITS = [
 
 def get_par_names(ncomp=None):
     return par_names(PAR_NAMES_SHORT, ncomp)
+
+
+# ---------------------------------------------------------------------------- several species: one column density each
+def check_species(species):
+    """The ordered tuple of 1..4 distinct `Molecule`s of an `LteMix`; ValueError otherwise."""
+    try:
+        species = tuple(species)
+    except TypeError:
+        raise ValueError('the species of an LTE mix are a sequence of Molecules') from None
+    if not all(isinstance(m, Molecule) for m in species):
+        raise ValueError('the species of an LTE mix are Molecules')
+    if not 1 <= len(species) <= MAX_SPECIES:
+        raise ValueError(f'an LTE mix has 1..{MAX_SPECIES} species, not {len(species)}')
+    if len(set(species)) != len(species):
+        raise ValueError('an LTE mix lists a Molecule twice: ' + ', '.join(m.name for m in species))
+    return species
+
+
+def check_mix_lines(species, lines, all_species=True):
+    """The `lines` of the spectra of a mix of `species` (an `LteLines`, `LteBand` or `LteBlend` each) as a list; ValueError
+    if one is none of these, a transition is of a molecule that is no species of the mix, or (all_species) a species has
+    no transition in any spectrum, which would leave its column density unconstrained."""
+    species = check_species(species)
+    lines = list(lines)
+    if not lines or not all(isinstance(t, (LteLines, LteBand, LteBlend)) for t in lines):
+        raise ValueError('an LTE mix takes one LteLines (Molecule.transition), LteBand or LteBlend per spectrum')
+    seen = set()
+    for k, table in enumerate(lines):
+        for t in transitions_of(table):
+            if t.molecule not in species:
+                raise ValueError(f'spectrum {k} has a transition of {t.molecule.name!r}, which is no species of the mix ('
+                                 + ', '.join(m.name for m in species) + ')')
+            seen.add(species.index(t.molecule))
+    if all_species and len(seen) != len(species):
+        missing = ', '.join(m.name for k, m in enumerate(species) if k not in seen)
+        raise ValueError(f'a species of the mix has no transition in any spectrum (its column density would be unconstrained): {missing}')
+    return lines
+
+
+def lines_species(lines):
+    """The distinct molecules of the spectra's `lines`, in the order of their first appearance."""
+    out = []
+    for table in lines:
+        for t in transitions_of(table):
+            if t.molecule not in out:
+                out.append(t.molecule)
+    return tuple(out)
+
+
+class _MixSpectrum(EngineSpectrumMixin, _HyperfineBase):
+    """A spectrum of an `LteMix` (its `Spectrum`): `lines` an `LteLines`, an `LteBand` or an `LteBlend` of the mix's species.
+    Its own model values (`LteMix.predict`) come from a set of this spectrum alone, with the species that have a transition
+    in it."""
+    MODEL = MODEL_LTE
+    MIX = None
+
+    def __init__(self, xarr, data, noise, lines):
+        check_mix_lines(self.MIX.species, [lines], all_species=False)
+        _HyperfineBase.__init__(self, xarr, data, noise, rest_freq=lines.nu)
+        self.lines = lines
+        present = [k for k, m in enumerate(self.MIX.species) if m in lines_species([lines])]
+        # the rows of a component's parameters this spectrum's own set takes, in its order
+        self._rows = [0, 1, self.MIX.lncol_row(present[0]), 3] + [self.MIX.lncol_row(k) for k in present[1:]]
+        self._attach(-1, lines=lines, species=[self.MIX.species[k] for k in present])
+
+    @property
+    def tbg_arr(self):
+        return self._ss.tbg()
+
+
+class _MixRunner(EngineRunner):
+    """Prior transform + model + log-likelihood of the spectra of an `LteMix` (its `Runner`)."""
+    MODEL = MODEL_LTE
+    MIX = None
+
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None):
+        assert ncomp > 0
+        baseline_order = check_baseline_order(baseline_order)
+        self.spectra = list(spectra)
+        check_mix_lines(self.MIX.species, [s.lines for s in self.spectra])
+        self.species = self.MIX.species
+        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order)
+
+    @classmethod
+    def from_data(cls, spec_data, utrans, **kwargs):
+        """spec_data: rows [xarr, data, noise, LteLines | LteBand | LteBlend]."""
+        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
+        spec_data = list(spec_data)
+        check_mix_lines(cls.MIX.species, [row[3] for row in spec_data])
+        spectra = np.array([cls.MIX.Spectrum(*args) for args in spec_data])
+        return cls(spectra, utrans, **kwargs)
+
+    def get_spectra(self):
+        return np.array(self.spectra)
+
+    def predict(self, params):
+        params = self._check_params(params)
+        for s in self.spectra:
+            self.MIX.predict(s, params)
+
+
+class LteMix:
+    """The model of K = 1..4 species in LTE that share voff, tex and sigm, each with a column density of its own: an ordered
+    list of distinct `Molecule`s.  Immutable, compared by the species.  What a model module offers, bound to the species:
+    `N = 3 + K`, `NAME`, `IX_VCEN`, `IX_SIGM`, the parameter names and labels, `Runner`, `Spectrum`, `predict`."""
+    NAME = 'lte_mix'
+    IX_VCEN = 0
+    IX_SIGM = 3
+
+    def __init__(self, species):
+        species = check_species(species)
+        K = len(species)
+        more = range(2, K + 1)
+        attrs = {
+            'species': species, 'N': 3 + K,
+            'PAR_NAMES': PAR_NAMES + [f'lncol{k}' for k in more],
+            'PAR_NAMES_SHORT': PAR_NAMES_SHORT + [f'lN{k}' for k in more],
+            'TEX_LABELS': TEX_LABELS + [rf'$\log(N_{k})$' for k in more],
+            'TEX_LABELS_WITH_UNITS': TEX_LABELS_WITH_UNITS + [rf'$\log(N_{k}) \ [\mathrm{{cm^{{-2}}}}]$' for k in more],
+        }
+        bound = {'MIX': self, 'N_MODEL': 3 + K, 'MODEL_INFO': self, 'SPECIES': species}
+        attrs['Runner'] = type('LteMixRunner', (_MixRunner,), dict(bound))
+        attrs['Spectrum'] = type('LteMixSpectrum', (_MixSpectrum,), dict(bound))
+        for key, value in attrs.items():
+            object.__setattr__(self, key, value)
+
+    n_species = property(lambda self: len(self.species))
+    ModelRunner = property(lambda self: self.Runner)
+    ModelSpectrum = property(lambda self: self.Spectrum)
+
+    def __setattr__(self, key, value):
+        raise AttributeError('an LteMix is immutable')
+
+    def __delattr__(self, key):
+        raise AttributeError('an LteMix is immutable')
+
+    def __eq__(self, other):
+        if not isinstance(other, LteMix):
+            return NotImplemented
+        return self.species == other.species
+
+    def __ne__(self, other):
+        r = self.__eq__(other)
+        return r if r is NotImplemented else not r
+
+    def __hash__(self):
+        return hash(('lte_mix',) + self.species)
+
+    def __repr__(self):
+        return f'LteMix({", ".join(repr(m.name) for m in self.species)})'
+
+    @staticmethod
+    def lncol_row(k):
+        """The parameter (row of a parameter-major vector) that holds the column density of species k."""
+        return 2 if k == 0 else 3 + k
+
+    def get_par_names(self, ncomp=None):
+        return par_names(self.PAR_NAMES_SHORT, ncomp)
+
+    def predict(self, s, params):
+        """Model spectrum of `s` (a `Spectrum` of this mix) for parameter-major `params` (voff, tex, lncol, sigm, lncol2, ...
+        of every component); result in ``s.get_spec()`` / ``s.loglikelihood``."""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.ndim != 1 or params.shape[0] == 0 or params.shape[0] % self.N != 0:
+            raise ValueError(f'Invalid parameter vector length: {params.shape}')
+        own = params.reshape(self.N, -1)[s._rows]
+        s._predict(own.ravel(), own.shape[0])
+
+    model_predict = predict
+
+    def tau_main(self, lines, tex, lncols, sigm):
+        """The peak optical depth of every transition of `lines` (an `LteLines`, `LteBand` or `LteBlend`), in its order, each
+        with the column density of its own species: `lncols[k]` is species k's.  numpy, one value per transition along the
+        first axis, the other arguments broadcasting behind it."""
+        check_mix_lines(self.species, [lines], all_species=False)
+        if len(lncols) != len(self.species):
+            raise ValueError(f'`lncols` takes one column density per species: {len(self.species)}, not {len(lncols)}')
+        return np.stack([t.tau_main(tex, lncols[self.species.index(t.molecule)], sigm) for t in transitions_of(lines)])

@@ -12,7 +12,7 @@ order (..., b, l).
 """
 import numpy as np
 
-_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4}
+_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4, 'lte_mix': 4}
 N_PDF_BINS = 200                 # edges when `aggregate_run_pdfs` makes its own bins (main.py:905-917)
 PDF_FLOOR = 1e-32                # zero-probability bins before the logarithm (main.py:980)
 PREDICT_ROWS = 4096              # (pixel, component) rows per device batch
@@ -283,6 +283,15 @@ def check_model_lines(store, stack):
     if any(t is None for t in tables):
         raise ValueError('the store was fitted with the hyperfine model: every cube of the stack needs its LineTable (DataCube(..., lines=))')
     stored = store.read_model_lines()
+    if store.read_model_species():
+        # an LTE mix: a cube's LteLines, LteBand or LteBlend against the stored blend, transition by transition in their order
+        # (a transition compares its molecule, so its species' table, too); the species' own order is the store's
+        from .lte import LteBand, LteBlend, LteLines, transitions_of
+        same = (len(stored) == len(tables) and all(isinstance(t, (LteLines, LteBand, LteBlend)) for t in tables)
+                and all(tuple(transitions_of(a)) == tuple(transitions_of(b)) for a, b in zip(stored, tables)))
+        if not same:
+            raise ValueError("the stack's line tables differ from the ones the store was fitted with (/model_lines)")
+        return tables
     if len(stored) != len(tables) or any(a != b for a, b in zip(stored, tables)):
         raise ValueError("the stack's line tables differ from the ones the store was fitted with (/model_lines)")
     return tables
@@ -308,6 +317,8 @@ def _device_predictor(store, stack):
         extra['rest_freqs'] = [float(dc.full_header.get('RESTFRQ', dc.full_header.get('RESTFREQ'))) for dc in stack.cubes]
     if model_id in (3, 4):                               # the caller's line tables: the stack's, which must be the store's
         extra['lines'] = check_model_lines(store, stack)
+        if store.read_model_species():                   # an LTE mix: the species in the order of the fit
+            extra['species'] = store.read_model_species()
     runner = CubeRunner(xarrs, trans, np.zeros((1, chan_tot)), np.ones((1, len(xarrs))), None, ncomp=1,
                         model=model_id, **extra)
     runner.set_exp_mode('table')                         # map products in the reference's own arithmetic: a one-off, not a rate
@@ -411,7 +422,7 @@ def create_fits_from_store(store, prefix='source'):
 def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, post_kernel=None,
                     evid_weight=True, predict_backend=None):
     """All steps in the reference's order (main.py:1240-1276)."""
-    if store.hdf.attrs.get('model_name') in ('hyperfine', 'lte'):     # before any product is written
+    if store.hdf.attrs.get('model_name') in ('hyperfine', 'lte', 'lte_mix'):     # before any product is written
         check_model_lines(store, stack)
     aggregate_run_attributes(store)
     convolve_evidence(store, evid_kernel)

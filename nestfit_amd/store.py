@@ -432,15 +432,20 @@ class HdfStore:
 
     def insert_model_metadata(self, runner_cls):
         assert self.is_open
-        module = inspect.getmodule(runner_cls)
+        # (an LteMix's Runner describes its model itself, MODEL_INFO: the names and the number of parameters follow the species)
+        module = getattr(runner_cls, 'MODEL_INFO', None) or inspect.getmodule(runner_cls)
         self.hdf.attrs.update({name: getattr(module, attr) for name, attr in MODEL_ATTRS})
 
-    def insert_model_lines(self, stack):
+    def insert_model_lines(self, stack, species=None):
         """The line table of every cube that has one (hyperfine model) under /model_lines/spec<k>: attributes `nu` and
         `name`, datasets `voff` and `tau_wts`.  Nothing for the models whose tables ship with the engine.  The LTE model's
         `LteLines` add the attributes `e_up`, `g_up` and `a_ul`, and their molecule's partition table goes under
         /model_partition: datasets `temp` and `q`, attribute `name`.  A cube with an `LteBand` has the attributes `n_trans`
-        and `name` on its spec<k> and one subgroup trans<j> per transition, each laid out as a single transition's spec<k>."""
+        and `name` on its spec<k> and one subgroup trans<j> per transition, each laid out as a single transition's spec<k>.
+        An LTE mix (`species`: its ordered molecules, two or more, or lines with an `LteBlend`): /model_partition has the
+        attribute `n_species` and one subgroup species<k> per species, each laid out as a single species' /model_partition, and
+        every transition carries the attribute `species`, the index of its molecule.  A store of one species is written as
+        it always was."""
         assert self.is_open
         tables = [getattr(dc, 'lines', None) for dc in stack.cubes]
         if all(t is None for t in tables):
@@ -451,6 +456,29 @@ class HdfStore:
         if any(t is None for t in tables):
             raise ValueError('either every cube of a stack has a LineTable or none has')
         molecule = None
+        if species is not None and (len(species) > 1 or any(type(t).__name__ == 'LteBlend' for t in tables)):
+            from .lte import check_mix_lines, transitions_of
+            species = tuple(species)
+            check_mix_lines(species, tables)
+            top = self.hdf.require_group(MODEL_PARTITION_GROUP)
+            top.attrs.update(n_species=len(species))
+            for k, m in enumerate(species):
+                group = self.hdf.require_group(f'{MODEL_PARTITION_GROUP}/species{k}')
+                group.attrs.update(name=m.name)
+                group.create_dataset('temp', data=np.array(m.q_temp))
+                group.create_dataset('q', data=np.array(m.q_val))
+            for k, t in enumerate(tables):
+                path = f'{MODEL_LINES_GROUP}/spec{k}'
+                group = self.hdf.require_group(path)
+                parts = transitions_of(t)
+                group.attrs.update(n_trans=len(parts), name='' if t.name is None else t.name)
+                for j, tr in enumerate(parts):
+                    sub = self.hdf.require_group(f'{path}/trans{j}')
+                    sub.attrs.update(nu=float(tr.nu), name='' if tr.name is None else tr.name, e_up=float(tr.e_up), g_up=float(tr.g_up),
+                                     a_ul=float(tr.a_ul), species=int(species.index(tr.molecule)))
+                    sub.create_dataset('voff', data=np.array(tr.voff))
+                    sub.create_dataset('tau_wts', data=np.array(tr.tau_wts))
+            return
         if any(hasattr(t, 'molecule') for t in tables):
             from .lte import check_one_molecule
             molecule = check_one_molecule(tables)
@@ -475,15 +503,42 @@ class HdfStore:
             else:
                 write(path, t)
 
-    def read_model_lines(self):
-        """The `LineTable`s the store was fitted with, in cube order ([] for a store without any): `LteLines` of the
-        stored `Molecule` where the store has a partition table, an `LteBand` for a spec<k> with the attribute `n_trans`."""
-        from .hyperfine import LineTable
+    def read_model_species(self):
+        """The ordered `Molecule`s of a store fitted with an LTE mix; () for every other store."""
         from .lte import Molecule
         assert self.is_open
+        if MODEL_PARTITION_GROUP not in self.hdf or 'n_species' not in self.hdf[MODEL_PARTITION_GROUP].attrs:
+            return ()
+        part = self.hdf[MODEL_PARTITION_GROUP]
+        return tuple(Molecule(g.attrs['name'], np.asarray(g['temp'][...]), np.asarray(g['q'][...]))
+                     for g in (part[f'species{k}'] for k in range(int(part.attrs['n_species']))))
+
+    def read_model_lines(self, with_species=False):
+        """The `LineTable`s the store was fitted with, in cube order ([] for a store without any): `LteLines` of the
+        stored `Molecule` where the store has a partition table, an `LteBand` for a spec<k> with the attribute `n_trans`.
+        A store fitted with an LTE mix: an `LteBlend` per cube, its transitions of the stored species.  with_species: the
+        pair (lines, `read_model_species()`)."""
+        from .hyperfine import LineTable
+        from .lte import LteBlend, Molecule
+        assert self.is_open
+        species = self.read_model_species()
+        if with_species:
+            return self.read_model_lines(), species
         if MODEL_LINES_GROUP not in self.hdf:
             return []
         top = self.hdf[MODEL_LINES_GROUP]
+        if species:
+            out = []
+            for k in range(len(list(top))):
+                g = top[f'spec{k}']
+                parts = []
+                for j in range(int(g.attrs['n_trans'])):
+                    t = g[f'trans{j}']
+                    parts.append(species[int(t.attrs['species'])].transition(
+                        t.attrs['nu'], t.attrs['e_up'], t.attrs['g_up'], t.attrs['a_ul'], np.asarray(t['voff'][...]),
+                        np.asarray(t['tau_wts'][...]), name=t.attrs.get('name') or None))
+                out.append(LteBlend(parts, name=g.attrs.get('name') or None))
+            return out
         molecule = None
         if MODEL_PARTITION_GROUP in self.hdf:
             part = self.hdf[MODEL_PARTITION_GROUP]
