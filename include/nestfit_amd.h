@@ -250,6 +250,29 @@ int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *siz
                                int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
                                const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                                const double *chan_noise);
+/* LTE with a beam filling factor: nfa_specset_create_lte_mix, argument for argument and check for check (n_species == 1 is
+ * allowed and the common case), whose components have one more parameter, the LAST one: lnff = log10 f, the fraction of the
+ * beam the component's gas fills (decadic like lncol).  4 + n_species parameters per component, parameter-major:
+ *     voff, tex, lncol_0, sigm, lncol_1, ..., lncol_{n_species - 1}, lnff
+ * and the model spectrum is
+ *     sum over components c of  10^lnff_c . T0 (y(T0 / tex_c) - tbg) (1 - e^{-tau_c})
+ * with tau_c exactly as nfa_specset_create_lte_mix forms it: a thick line reads f (J(tex) - J(Tbg)), not J(tex) - J(Tbg).
+ * Nothing bounds f here (a prior does; f > 1 is arithmetic like any other); lnff = -inf gives a component that adds
+ * nothing, a NaN lnff NaN spectra and lnL.  The model stays NFA_MODEL_LTE, and a prior program for such a set covers
+ * 4 + n_species parameters.
+ * DEGENERACY: where every line of a component is optically thin, 1 - e^{-tau} = tau and the spectrum depends on f and the
+ * column densities only through f N_k: lnff and the lncol_k are then not separately constrained.  A thick line (which
+ * measures f J(tex)) beside thin ones (whose ratios measure tex, whose intensities f N) lifts it; a prior must otherwise.
+ * Served by the batch entry points (host and device pointers, predict), single points and a broker's handful (through
+ * the batch kernels), the broker, the callback and the device sampler up to 60 dimensions; nfa_ring_serve_device refuses
+ * such a set ("the resident kernel has no form for a filling factor: use nfa_ring_serve").  Errors as
+ * nfa_specset_create_lte_mix. */
+int nfa_specset_create_lte_filled(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
+                                  const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
+                                  const double *e_up, const double *g_up, const double *a_ul,
+                                  int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
+                                  const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                                  const double *chan_noise);
 /* A shipped line table, as a template for nfa_specset_create_lines: model 0 (trans_id 1..9) or 1 (trans_id 1..3);
  * voff and tau_wts take 50 doubles each (zero behind the *n lines), *nu the rest frequency in Hz.  Needs no device. */
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n);

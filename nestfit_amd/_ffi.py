@@ -61,6 +61,8 @@ SIGNATURES = {
                                                C.c_int, _dp, _dp, C.POINTER(_dp), C.c_int64, _dp, _dp, _dp]),
     'nfa_specset_create_lte_mix': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _lp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
                                              C.c_int, _ip, _ip, _dp, _dp, C.POINTER(_dp), C.c_int64, _dp, _dp, _dp]),
+    'nfa_specset_create_lte_filled': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _lp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                C.c_int, _ip, _ip, _dp, _dp, C.POINTER(_dp), C.c_int64, _dp, _dp, _dp]),
     'nfa_builtin_lines': (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     'nfa_specset_destroy': (C.c_int, [C.c_void_p]),
     'nfa_specset_set_data': (C.c_int, [C.c_void_p, C.c_int64, _dp]),

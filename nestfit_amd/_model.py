@@ -59,14 +59,15 @@ def channel_weights(noise, size):
 class _SpecSet:
     """Owner of a device-resident set of spectra (one pixel or a cube)."""
 
-    def __init__(self, xarrs, trans_ids, data, noise, model=MODEL_AMMONIA, rest_freqs=None, lines=None, species=None):
+    def __init__(self, xarrs, trans_ids, data, noise, model=MODEL_AMMONIA, rest_freqs=None, lines=None, species=None, fill=False):
         """xarrs: list of 1-D axes; data [n_pix, sum(sizes)]; noise [n_pix, n_spec], or [n_pix, sum(sizes)]
         for a noise per channel (nfa_specset_create_channel_noise: inf masks a channel).  lines: the hyperfine
         model's `LineTable` of every spectrum (nfa_specset_create_lines; `trans_ids` and `rest_freqs` are then unused), or
         the LTE model's `LteLines` of every spectrum, all of one `Molecule` (nfa_specset_create_lte); where a spectrum covers
         several transitions, its `LteBand` (nfa_specset_create_lte_bands).  species: the ordered `Molecule`s of an LTE mix,
         whose `lines` may be `LteBlend`s as well and of any of them (nfa_specset_create_lte_mix); 3 + len(species) parameters
-        per component."""
+        per component.  fill: such a set with a beam filling factor per component as one more parameter, the last
+        (nfa_specset_create_lte_filled)."""
         self.model = int(model)
         if (self.model in (MODEL_HYPERFINE, MODEL_LTE)) != (lines is not None):
             raise ValueError('the hyperfine model (3) and the LTE model (4), and no other, take `lines`: one LineTable '
@@ -92,9 +93,12 @@ class _SpecSet:
             trans_ids = [-1] * len(lines)
         elif species is not None:
             raise ValueError('`species` come with `lines`')
+        if fill and species is None:
+            raise ValueError('a filling factor (`fill`) belongs to an LTE mix: `species` and `lines`')
+        self.fill = bool(fill)
         self.molecule = molecule
         self.species = species
-        self.n_model = N_MODEL[self.model] if species is None else 3 + len(species)
+        self.n_model = N_MODEL[self.model] if species is None else 3 + len(species) + (1 if fill else 0)
         self.lines = lines
         lib = _ffi.engine()
         self.n_spec = len(xarrs)
@@ -138,9 +142,9 @@ class _SpecSet:
                 n_q = np.array([m.n for m in species], dtype=np.int32)
                 q_temp = np.ascontiguousarray(np.concatenate([m.q_temp for m in species]))
                 q_val = np.ascontiguousarray(np.concatenate([m.q_val for m in species]))
-                rc = lib.nfa_specset_create_lte_mix(*head, _ffi.dptr(e_up), _ffi.dptr(g_up), _ffi.dptr(a_ul), len(species),
-                                                    of.ctypes.data_as(_ffi._ip), n_q.ctypes.data_as(_ffi._ip),
-                                                    _ffi.dptr(q_temp), _ffi.dptr(q_val), *tail)
+                create = lib.nfa_specset_create_lte_filled if fill else lib.nfa_specset_create_lte_mix
+                rc = create(*head, _ffi.dptr(e_up), _ffi.dptr(g_up), _ffi.dptr(a_ul), len(species), of.ctypes.data_as(_ffi._ip),
+                            n_q.ctypes.data_as(_ffi._ip), _ffi.dptr(q_temp), _ffi.dptr(q_val), *tail)
             elif molecule is not None:
                 e_up, g_up, a_ul = (np.array([getattr(t, k) for t in lines], dtype=np.float64)
                                     for k in ('e_up', 'g_up', 'a_ul'))
@@ -229,11 +233,11 @@ class EngineSpectrumMixin:
     one pixel, runner handles cached per (ncomp, cold, lte)."""
     MODEL = MODEL_AMMONIA
 
-    def _attach(self, trans_id, rest_freq=None, lines=None, species=None):
+    def _attach(self, trans_id, rest_freq=None, lines=None, species=None, fill=False):
         self._ss = _SpecSet([self.xarr], [trans_id], self.data.reshape(1, -1),
                             np.reshape(self.noise, (1, -1)), model=self.MODEL,
                             rest_freqs=None if rest_freq is None else [rest_freq],
-                            lines=None if lines is None else [lines], species=species)
+                            lines=None if lines is None else [lines], species=species, fill=fill)
         self.null_lnZ = float(self._ss.null_lnZ()[0, 0])
         self._runners = {}
 
@@ -305,7 +309,7 @@ class EngineRunner(Runner):
         self._ss = _SpecSet([s.xarr for s in spectra], [s.trans_id for s in spectra], data, noise,
                             model=self.MODEL, rest_freqs=rest_freqs,
                             lines=[s.lines for s in spectra] if self.MODEL in (MODEL_HYPERFINE, MODEL_LTE) else None,
-                            species=getattr(self, 'SPECIES', None))
+                            species=getattr(self, 'SPECIES', None), fill=getattr(self, 'FILL', False))
         self._run = _RunnerHandle(self._ss, utrans, self.ncomp, cold, lte)
         self.baseline_order = baseline_order
         if baseline_order is not None:

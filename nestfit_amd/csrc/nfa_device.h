@@ -105,7 +105,7 @@ struct MixRec {
 
 struct SpecDev {
     int     n_spec, ncomp, cold, lte;
-    int     model, npar;                 // NFA_MODEL_*, parameters per component (6 / 4 / 3 / 4 / 4; an LTE mix 3 + K)
+    int     model, npar;                 // NFA_MODEL_*, parameters per component (6 / 4 / 3 / 4 / 4; an LTE mix 3 + K, 4 + K filled)
     double  rest[MAXSPEC];               // line rest frequency (tables, or Spectrum.rest_freq)
     int     size[MAXSPEC], trans[MAXSPEC], off[MAXSPEC];
     double  nu_min[MAXSPEC], nu_chan[MAXSPEC];
@@ -201,6 +201,11 @@ __device__ __forceinline__ double bl_quad(const double *R, const double *mp) {
 #define DK_XS 12
 #define DK_XLO 13
 #define DK_YLO 14
+// slot 15: 0.0 as the set-up stage leaves it (write_y_model), read by nobody -- except in a FILLED LTE set
+// (nfa_specset_create_lte_filled), where lte_fill_kernel (nfa_setup.h) writes the component's beam filling
+// factor 10^lnff there, in the record of every spectrum, between the two stages, and lnl_body<..., FILL> multiplies the
+// component's Tb by it
+#define DK_FILL 15
 __host__ __device__ inline int drec_size(int ncomp, int nspec) { return 4 * ncomp + ncomp * nspec * DREC_CS; }
 
 // Up to NFA_GROUP_MAX batches of `each` rows that a caller enqueues one after the other travel as ONE launch (the
@@ -815,7 +820,10 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // operations with w == 1.0 are exactly those of the unweighted form (multiplying by 1.0 changes no bits).
 // BASELINE (weighted sets only): a polynomial baseline per spectrum is profiled out, chi^2_min = that chi^2 minus
 // ||L^-1 (m(d) - m(p))||^2 (SpecDev.bl); the moments m_k(p) = sum w P_k(u) p are summed like chi^2 itself.
-template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false>
+// FILL (the general component form of the batch kernels only): a component's T0 (y - tbg) is multiplied by its beam filling
+// factor (DK_FILL of its record: one more scalar load beside the ones of the Tb pass) at every site that adds to `pred`;
+// spectra out, the weighted sum and the baseline's moments are formed from `pred` and carry it without further code.
+template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -1009,6 +1017,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     int pend_j = -1;
     // BASELINE: the moments m_k(p) of the lane's channels, per part (bl_acc) and over the parts in part order (bl_tot)
     static_assert(!BASELINE || (WEIGHTED && !DYN), "the baseline form is a weighted batch form");
+    static_assert(!FILL || (NCOMP == 0 && !DYN), "a filling factor: the general component form of the batch kernels");
     constexpr int NBL = BASELINE ? NFA_BL_NB : 1;
     double bl_acc[NBL], bl_tot[NBL];
 #pragma unroll
@@ -1189,6 +1198,9 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                 const int cls = MODE == 2 ? tb_class(kind) : cls_unit;
                 int cls_hot = __builtin_amdgcn_readfirstlane(cls);
                 if (MODE != 2) asm volatile("" : "+s"(cls_hot));
+                // FILL: the component's beam filling factor (the same in the record of every spectrum)
+                double ff = 1.0;
+                if constexpr (FILL) ff = Dk[4 * ncomp + (c * nspec + s) * DREC_CS + DK_FILL];
                 if (cls_hot == 1) {
                     // The band lies in ONE cell of the 1/(e^x - 1) table (hyperfine.pyx:23-45; the usual case, first in the
                     // chain: one scalar compare and a branch between the optical depth and the pass): the cell's
@@ -1201,7 +1213,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     // its own strict build by 1e-11.  FastExp of the optical depth, the factor with the table
                     // indices, is the reference's to the bit in the table mode.  Lanes with tau == 0 (skipped by the
                     // reference, hyperfine.pyx:104-105) get g * (1 - 1) = +-0: the sum needs no per-lane select.
-                    const double g = __builtin_fma(xj, __builtin_fma(b0x, xj, a0x), -p3);
+                    double g = __builtin_fma(xj, __builtin_fma(b0x, xj, a0x), -p3);
+                    if constexpr (FILL) g *= ff;
                     if (MODE == 2) pred = __builtin_fma(g, one_minus_fastexp_f32((float)tau, livem), pred);
                     else pred = __builtin_fma(g, MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm), pred);
                     return;
@@ -1230,6 +1243,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                         const double y = nf_iemtex(T0 / Dk[c * 4], g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
                         g = T0 * (y - tbg);
                     }
+                    if constexpr (FILL) g *= ff;
                     pred = __builtin_fma(g, one_minus_fastexp_f32((float)tau, livem), pred);
                 } else {
                     unsigned jr = jo;
@@ -1256,10 +1270,14 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                         // the product adds +0 there and needs no select
                         const double y = (HOISTX && NCOMP > 0) ? cx_xs[c] * (x - cx_xlo[c]) + cx_ylo[c]
                                                    : Dk[dko + DK_XS] * (x - Dk[dko + DK_XLO]) + Dk[dko + DK_YLO];
-                        pred += (T0 * (y - tbg)) * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
+                        double g = T0 * (y - tbg);
+                        if constexpr (FILL) g *= ff;
+                        pred += g * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
                     } else {
                         const double y = nf_iemtex(x, g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
-                        const double tb = (T0 * (y - tbg)) * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
+                        double g = T0 * (y - tbg);
+                        if constexpr (FILL) g *= ff;
+                        const double tb = g * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
                         pred += !(tau == 0) ? tb : 0.0;
                     }
                 }
@@ -1376,6 +1394,40 @@ lnl_kernel_bl(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *_
     const double *sm = smem;
     if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
     lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP, false, true, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+}
+
+// The kernels of a FILLED LTE set (a beam filling factor per component): lnl_kernel, lnl_kernel_wt and
+// lnl_kernel_bl in the general component form with lnl_body's FILL flag.  Such sets take no other form -- no unrolled
+// component loop, no queue, no w8 -- so these are 3 x 8 instances over (MODE, WRITE_SPEC, WIDE).
+template <int MODE, bool WRITE_SPEC, bool WIDE>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_fill(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, false, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+}
+template <int MODE, bool WRITE_SPEC, bool WIDE>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_wt_fill(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                   double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+}
+template <int MODE, bool WRITE_SPEC, bool WIDE>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_bl_fill(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                   double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one

@@ -212,6 +212,7 @@ struct nfa_specset {
     BandRec *d_band = nullptr;                      // LTE bands: SpecDev.band (null for a set without a banded spectrum)
     MixRec  *d_mix = nullptr;                       // LTE mixes: SpecDev.mix (null for a set of one species)
     int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
+    bool    filled = false;                         // an LTE set with a beam filling factor per component: the last parameter
     bool    bl_w1 = false;                          // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
 };
 
@@ -282,7 +283,7 @@ static int runner_mode(const nfa_runner *r) { return r->exp_mode >= 0 ? r->exp_m
 static LpKnobs plan_knobs() { return {g_eng.n_cu, g_eng.setup_ti, g_eng.setup_threads, g_eng.setup_sub, g_eng.lnl_queue, g_eng.lnl_queue_wg, g_eng.coalesce, g_eng.ablate}; }
 static LpLaunch plan_launch(const nfa_runner *r, int64_t B, int mode, bool write_spec, bool has_prior, int slot) {
     return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl != nullptr,
-                    r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr};
+                    r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr, r->ss->filled};
 }
 
 extern "C" {
@@ -430,9 +431,10 @@ static int launch_bl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_b
 // and weights concatenated; `lte`: the LTE model's record as well (nfa_specset_create_lte), null for the hyperfine model;
 // `band`, `line_nu`: a banded LTE set's record and the rest frequency of every line's own transition
 // (nfa_specset_create_lte_bands), null otherwise; `mix`: the record of a set of several species, which has 3 + n_species
-// parameters per component (nfa_specset_create_lte_mix), null otherwise
+// parameters per component (nfa_specset_create_lte_mix), null otherwise; `filled`: with a beam filling factor as one more,
+// the last (nfa_specset_create_lte_filled)
 struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; const LteRec *lte; const BandRec *band; const double *line_nu;
-                    const MixRec *mix = nullptr; };
+                    const MixRec *mix = nullptr; bool filled = false; };
 
 static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *sizes, const int32_t *trans_ids,
                         const double *rest_freqs, const double *const *xarr, int64_t n_pix, const double *data,
@@ -443,7 +445,8 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     const bool tabled = model == NFA_MODEL_HYPERFINE || model == NFA_MODEL_LTE;      // the caller's line tables
     d.npar = model == NFA_MODEL_DIAZENYLIUM || tabled ? NFA_N2HP_PARAMS
            : model == NFA_MODEL_GAUSSIAN ? NFA_GAUSS_PARAMS : NFA_N_PARAMS;
-    if (model == NFA_MODEL_LTE && lines->mix) d.npar = 3 + lines->mix->n_species;
+    if (model == NFA_MODEL_LTE && lines->mix) d.npar = 3 + lines->mix->n_species + (lines->filled ? 1 : 0);
+    ss->filled = model == NFA_MODEL_LTE && lines->mix && lines->filled;
     std::vector<LineRow> h_lines((size_t)n_spec, LineRow{});          // the line rows of the spectra
     int64_t tot = 0, rows = 0, line0 = 0;
     for (int s = 0; s < n_spec; ++s) {
@@ -832,12 +835,15 @@ int nfa_specset_create_lte_bands(nfa_specset **out, int n_spec, const int64_t *s
     return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data, noise, nullptr, &lt);
 }
 
-int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
-                               const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
-                               const double *e_up, const double *g_up, const double *a_ul,
-                               int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
-                               const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
-                               const double *chan_noise) {
+// nfa_specset_create_lte_mix, and with `filled` nfa_specset_create_lte_filled: the same checks and records, one more
+// parameter per component.  A filled set owns its band and mix records whatever it holds -- one species, a transition per
+// spectrum -- so that launch_band runs for it.
+static int create_lte_mix(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
+                          const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
+                          const double *e_up, const double *g_up, const double *a_ul,
+                          int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
+                          const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                          const double *chan_noise, bool filled) {
     if (!out || !sizes || !n_trans || !n_lines || !trans_freqs || !voff || !tau_wts || !xarr || !data || !species || !n_q)
         return fail(NFA_ERR_ARG, "null argument");
     if (n_species < 1 || n_species > NFA_LTE_MAXSP) return fail(NFA_ERR_ARG, "n_species must be in 1..4");
@@ -861,7 +867,7 @@ int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *siz
             return fail(NFA_ERR_ARG, "a species without a transition in any spectrum: its column density would be unconstrained (species "
                                      + std::to_string(k) + ")");
     // one species: the bands creator's set, bit for bit, on its routes
-    if (n_species == 1)
+    if (n_species == 1 && !filled)
         return nfa_specset_create_lte_bands(out, n_spec, sizes, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul,
                                             n_q[0], q_temp, q_val, xarr, n_pix, data, noise, chan_noise);
     if (!e_up || !g_up || !a_ul || !q_temp || !q_val) return fail(NFA_ERR_ARG, "null argument");
@@ -887,10 +893,31 @@ int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *siz
     }
     LineTables lt = {L.s_lines.data(), L.l_voff.data(), L.l_wts.data(), &rec, &L.band, L.l_nu.data()};
     lt.mix = &mix;
+    lt.filled = filled;
     if (chan_noise)
         return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data,
                                             chan_noise, &lt);
     return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data, noise, nullptr, &lt);
+}
+
+int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
+                               const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
+                               const double *e_up, const double *g_up, const double *a_ul,
+                               int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
+                               const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                               const double *chan_noise) {
+    return create_lte_mix(out, n_spec, sizes, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, n_species, species, n_q,
+                          q_temp, q_val, xarr, n_pix, data, noise, chan_noise, false);
+}
+
+int nfa_specset_create_lte_filled(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
+                                  const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
+                                  const double *e_up, const double *g_up, const double *a_ul,
+                                  int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
+                                  const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                                  const double *chan_noise) {
+    return create_lte_mix(out, n_spec, sizes, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, n_species, species, n_q,
+                          q_temp, q_val, xarr, n_pix, data, noise, chan_noise, true);
 }
 
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n) {
@@ -1164,7 +1191,7 @@ int nfa_runner_create(nfa_runner **out, nfa_specset *ss, nfa_priors *priors, int
     if (!out || !ss) return fail(NFA_ERR_ARG, "null argument");
     if (ncomp < 1 || ncomp > MAXCOMP) return fail(NFA_ERR_ARG, "ncomp must be in 1..10");   // ammonia.pyx:401
     if (priors && priors->prog.n_param != ss->dev.npar)
-        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+, hyperfine and LTE, 3 Gaussian, 3 + the species of an LTE mix)");
+        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+, hyperfine and LTE, 3 Gaussian, 3 + the species of an LTE mix, one more with a filling factor)");
     int rc = engine_init(); if (rc) return rc;
     nfa_runner *r = new nfa_runner();
     r->ss = ss; r->pr = priors; r->ncomp = ncomp; r->cold = cold ? 1 : 0; r->lte = lte ? 1 : 0;
@@ -1320,6 +1347,13 @@ static int launch_band(nfa_runner *r, int slot, int64_t B) {
                            (const BandRec *)r->ss->d_band, (const MixRec *)r->ss->d_mix, (const LteRec *)r->ss->d_lte,
                            (const double *)r->d_D[slot], r->d_band[slot], r->cur_group, (long)B, r->ncomp, n_spec, r->ss->dev.npar);
         HIP_TRY(hipGetLastError());
+        // a filled set: the components' filling factors from the same theta into the records (lte_fill_kernel)
+        if (r->ss->filled) {
+            const int64_t recs = B * r->ncomp * n_spec;
+            hipLaunchKernelGGL(lte_fill_kernel, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, r->lanes[slot],
+                               r->d_D[slot], r->cur_group, (long)B, r->ncomp, n_spec, r->ss->dev.npar);
+            HIP_TRY(hipGetLastError());
+        }
         return NFA_OK;
     }
     hipLaunchKernelGGL(lte_band_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, r->lanes[slot],
@@ -1331,6 +1365,8 @@ static int launch_band(nfa_runner *r, int slot, int64_t B) {
 // The kernel of a plan.  Naming an instance compiles it, so this names the instances a plan can ask for and no others:
 // lnl_kernel, _wt and _bl for all 32 (mode, spectra out, wide, NCOMP), lnl_kernel_w8 for the table mode with spectra out,
 // lnl_kernel_queue for the table mode's narrow sets.  NCOMP 1..3: the component loop unrolled; 0: the general form.
+// A filled LTE set (a plan with `filled`): lnl_kernel_fill, _wt_fill, _bl_fill over (mode, spectra out, wide), the
+// general form whatever the component count.
 typedef void (*LnlKernel)(SpecDev, BatchGroup, const double *, double *, double *, long, LnlGeom, const double *);
 template <int I>     // I: bit 4 fast mode, bit 3 spectra out, bit 2 wide, bits 0-1 NCOMP
 static LnlKernel lnl_kernel_inst(LnlForm form) {
@@ -1347,7 +1383,21 @@ static LnlKernel lnl_kernel_at(int i, LnlForm form, std::index_sequence<I...>) {
     static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_inst<(int)I>...};
     return inst[i](form);
 }
-static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, LnlForm form) {
+template <int I>     // I: bit 2 fast mode, bit 1 spectra out, bit 0 wide
+static LnlKernel lnl_kernel_fill_inst(LnlForm form) {
+    constexpr int MODE = (I & 4) ? 2 : 0;
+    constexpr bool WS = (I & 2) != 0, WIDE = (I & 1) != 0;
+    if (form == LNL_BASELINE) return lnl_kernel_bl_fill<MODE, WS, WIDE>;
+    if (form == LNL_WEIGHTED) return lnl_kernel_wt_fill<MODE, WS, WIDE>;
+    return form == LNL_PLAIN ? lnl_kernel_fill<MODE, WS, WIDE> : nullptr;
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_fill_at(int i, LnlForm form, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_fill_inst<(int)I>...};
+    return inst[i](form);
+}
+static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, LnlForm form, bool filled) {
+    if (filled) return lnl_kernel_fill_at((mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0), form, std::make_index_sequence<8>());
     const int i = (mode == 0 ? 0 : 16) | (write_spec ? 8 : 0) | (wide ? 4 : 0) | (ncomp >= 1 && ncomp <= 3 ? ncomp : 0);
     return lnl_kernel_at(i, form, std::make_index_sequence<32>());
 }
@@ -1363,7 +1413,7 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form);
+    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form, P.filled);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
     int rc = ensure_dynamic_lds((const void *)kern, P.lds); if (rc) return rc;
     hipStream_t st = r->lanes[slot];
@@ -1571,7 +1621,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     if (!g_eng.point || r->profiling || B > NFA_POINT_MAXB) return 0;
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
-    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr, S.band != nullptr);
+    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr, S.band != nullptr, r->ss->filled);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

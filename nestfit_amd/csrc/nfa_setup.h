@@ -815,3 +815,24 @@ lte_mix_kernel(const BandRec *__restrict__ R, const MixRec *__restrict__ M, cons
     }
     T[i] = out;
 }
+
+// ---------------------------------------------------------------------------
+//  lte_fill_kernel: a FILLED LTE set (nfa_specset_create_lte_filled).  The last parameter of a component is
+//  lnff = log10 of its beam filling factor; the set-up stage knows nothing of it (its records stay what they are, slot
+//  DK_FILL = 0.0).  This kernel, behind lte_mix_kernel on the lane, puts f = 10^lnff into DK_FILL of the record of every
+//  (item, component, spectrum), where lnl_body<..., FILL> finds it with a scalar load beside the Tb constants it reads
+//  anyway.  The value comes from the batch's theta exactly as lte_mix_kernel reads lncol_k: item b of the launch is row
+//  b - c each of batch c = group_of(b), a row npar ncomp doubles, lnff the row's parameter npar - 1.  Nothing bounds it:
+//  -inf gives 0 (the component adds nothing), NaN gives NaN.  One lane per (item, component, spectrum).
+__global__ void __launch_bounds__(256)
+lte_fill_kernel(double *__restrict__ D, BatchGroup grp, long B, int ncomp, int nspec, int npar) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * ncomp * nspec) return;
+    const int s = (int)(i % nspec);
+    const long bc = i / nspec;
+    const int c = (int)(bc % ncomp);
+    const long b = bc / ncomp;
+    const int cg = group_of(grp, b);
+    const double *th = grp.U[cg] + (b - (long)cg * grp.each) * (npar * ncomp);
+    D[b * drec_size(ncomp, nspec) + 4 * ncomp + (c * nspec + s) * DREC_CS + DK_FILL] = exp10(th[(npar - 1) * ncomp + c]);
+}

@@ -47,12 +47,13 @@ class CubeRunner:
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
-                 model=0, rest_freqs=None, baseline_order=None, lines=None, species=None):
+                 model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
         spectrum of the ordered `Molecule`s `species` -- without `species`, lines of several molecules take them in the order of
-        their first appearance).  An LTE mix has 3 + len(species) parameters per component."""
+        their first appearance).  An LTE mix has 3 + len(species) parameters per component; fill: and a beam filling factor
+        as one more, the last (`LteMix(species, fill=True)`; one species included)."""
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         if species is None and int(model) == 4 and lines is not None:
@@ -60,9 +61,10 @@ class CubeRunner:
             lines = list(lines)
             if all(isinstance(t, (LteLines, LteBand, LteBlend)) for t in lines):
                 found = lines_species(lines)
-                if len(found) > 1 or any(isinstance(t, LteBlend) for t in lines):
+                if len(found) > 1 or fill or any(isinstance(t, LteBlend) for t in lines):
                     species = found
-        self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs, lines=lines, species=species)
+        self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs, lines=lines, species=species,
+                            fill=fill)
         self._run = _RunnerHandle(self._ss, utrans, ncomp, cold, lte)
         self.baseline_order = baseline_order
         if baseline_order is not None:

@@ -71,6 +71,7 @@ class CubeFitter:
         model = getattr(runner_cls, 'MODEL_INFO', None) or inspect.getmodule(runner_cls)
         self.model_id, self.n_model = _MODEL_ID[model.NAME], model.N
         self.species = getattr(model, 'species', None)   # an LTE mix: the ordered molecules (to_device, the store)
+        self.fill = bool(getattr(model, 'fill', False))  # ... and whether its components have a filling factor
         self.stack, self.utrans, self.runner_cls = stack, utrans, runner_cls
         self.runner_kwargs = dict(runner_kwargs or {})
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
@@ -145,7 +146,7 @@ class CubeFitter:
 
     def _fit_on_device(self, lon, lat, ncomp, nlive, kw):
         with self._tree_lock:
-            kwargs = self.runner_kwargs if self.species is None else dict(self.runner_kwargs, species=self.species)
+            kwargs = self.runner_kwargs if self.species is None else dict(self.runner_kwargs, species=self.species, fill=self.fill)
             runner, rlon, rlat = self.stack.to_device(self.utrans, ncomp=ncomp, lon=lon, lat=lat,
                                                       model=self.model_id, **kwargs)
         assert np.array_equal(rlon, lon) and np.array_equal(rlat, lat)
@@ -233,7 +234,7 @@ class CubeFitter:
             store.insert_header(self.stack)
         store.insert_fitter_pars(self)
         store.insert_model_metadata(self.runner_cls)
-        store.insert_model_lines(self.stack, species=self.species)
+        store.insert_model_lines(self.stack, species=self.species, fill=self.fill)
         todo = range(store.nchunks) if rank is None else [0]
         written = {}
         for k in todo:

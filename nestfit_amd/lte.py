@@ -33,6 +33,15 @@ the transitions of any of them that one spectrum covers.  Parameters per compone
 and a transition of species k has the tau_main above with lncol_k and Q_k(tex).  `LteBand`, `LteRunner` and
 `check_one_molecule` stay what they were: one species.
 
+All of the above assume that the gas fills the beam.  `LteMix(species, fill=True)` -- one species is the common case --
+gives every component a BEAM FILLING FACTOR f as one more parameter, the last: `lnff` = log10 f, 4 + K per component,
+
+    voff, tex, lncol, sigm, lncol2, ..., lncolK, lnff          Tb = sum_c 10^lnff_c T0 (y(T0 / tex_c) - tbg) (1 - e^-tau_c)
+
+so that a thick line of a compact source reads f (J(tex) - J(Tbg)).  Nothing bounds f but the prior.  Where all lines are
+optically thin the spectrum depends on f and the column densities only through f N: a thick line beside thin ones (a
+main ladder and its isotopologue's) is what makes `lnff` identifiable.
+
 No molecular data ship with this module: rest frequencies, level energies, Einstein coefficients and the partition
 function come from a catalogue of the user's.
 """
@@ -513,7 +522,9 @@ class _MixSpectrum(EngineSpectrumMixin, _HyperfineBase):
         present = [k for k, m in enumerate(self.MIX.species) if m in lines_species([lines])]
         # the rows of a component's parameters this spectrum's own set takes, in its order
         self._rows = [0, 1, self.MIX.lncol_row(present[0]), 3] + [self.MIX.lncol_row(k) for k in present[1:]]
-        self._attach(-1, lines=lines, species=[self.MIX.species[k] for k in present])
+        if self.MIX.fill:                                             # the filling factor: the last row, here as there
+            self._rows.append(self.MIX.N - 1)
+        self._attach(-1, lines=lines, species=[self.MIX.species[k] for k in present], fill=self.MIX.fill)
 
     @property
     def tbg_arr(self):
@@ -554,23 +565,30 @@ class _MixRunner(EngineRunner):
 class LteMix:
     """The model of K = 1..4 species in LTE that share voff, tex and sigm, each with a column density of its own: an ordered
     list of distinct `Molecule`s.  Immutable, compared by the species.  What a model module offers, bound to the species:
-    `N = 3 + K`, `NAME`, `IX_VCEN`, `IX_SIGM`, the parameter names and labels, `Runner`, `Spectrum`, `predict`."""
+    `N = 3 + K`, `NAME`, `IX_VCEN`, `IX_SIGM`, the parameter names and labels, `Runner`, `Spectrum`, `predict`.
+    fill=True: with a beam filling factor per component as the last parameter, `lnff` = log10 f (`N = 4 + K`; `.fill`);
+    a filled and an unfilled mix of the same species are different models."""
     NAME = 'lte_mix'
     IX_VCEN = 0
     IX_SIGM = 3
 
-    def __init__(self, species):
+    def __init__(self, species, fill=False):
         species = check_species(species)
+        if not isinstance(fill, (bool, np.bool_)):
+            raise ValueError('`fill` is True or False: whether a component has a beam filling factor')
+        fill = bool(fill)
         K = len(species)
+        N = 3 + K + (1 if fill else 0)
         more = range(2, K + 1)
         attrs = {
-            'species': species, 'N': 3 + K,
-            'PAR_NAMES': PAR_NAMES + [f'lncol{k}' for k in more],
-            'PAR_NAMES_SHORT': PAR_NAMES_SHORT + [f'lN{k}' for k in more],
-            'TEX_LABELS': TEX_LABELS + [rf'$\log(N_{k})$' for k in more],
-            'TEX_LABELS_WITH_UNITS': TEX_LABELS_WITH_UNITS + [rf'$\log(N_{k}) \ [\mathrm{{cm^{{-2}}}}]$' for k in more],
+            'species': species, 'N': N, 'fill': fill,
+            'PAR_NAMES': PAR_NAMES + [f'lncol{k}' for k in more] + (['lnff'] if fill else []),
+            'PAR_NAMES_SHORT': PAR_NAMES_SHORT + [f'lN{k}' for k in more] + (['lf'] if fill else []),
+            'TEX_LABELS': TEX_LABELS + [rf'$\log(N_{k})$' for k in more] + ([r'$\log(f)$'] if fill else []),
+            'TEX_LABELS_WITH_UNITS': TEX_LABELS_WITH_UNITS + [rf'$\log(N_{k}) \ [\mathrm{{cm^{{-2}}}}]$' for k in more]
+                                     + ([r'$\log(f)$'] if fill else []),
         }
-        bound = {'MIX': self, 'N_MODEL': 3 + K, 'MODEL_INFO': self, 'SPECIES': species}
+        bound = {'MIX': self, 'N_MODEL': N, 'MODEL_INFO': self, 'SPECIES': species, 'FILL': fill}
         attrs['Runner'] = type('LteMixRunner', (_MixRunner,), dict(bound))
         attrs['Spectrum'] = type('LteMixSpectrum', (_MixSpectrum,), dict(bound))
         for key, value in attrs.items():
@@ -589,17 +607,17 @@ class LteMix:
     def __eq__(self, other):
         if not isinstance(other, LteMix):
             return NotImplemented
-        return self.species == other.species
+        return self.species == other.species and self.fill == other.fill
 
     def __ne__(self, other):
         r = self.__eq__(other)
         return r if r is NotImplemented else not r
 
     def __hash__(self):
-        return hash(('lte_mix',) + self.species)
+        return hash(('lte_mix',) + self.species + ((True,) if self.fill else ()))
 
     def __repr__(self):
-        return f'LteMix({", ".join(repr(m.name) for m in self.species)})'
+        return f'LteMix({", ".join(repr(m.name) for m in self.species)}{", fill=True" if self.fill else ""})'
 
     @staticmethod
     def lncol_row(k):
@@ -611,7 +629,7 @@ class LteMix:
 
     def predict(self, s, params):
         """Model spectrum of `s` (a `Spectrum` of this mix) for parameter-major `params` (voff, tex, lncol, sigm, lncol2, ...
-        of every component); result in ``s.get_spec()`` / ``s.loglikelihood``."""
+        and, filled, lnff of every component); result in ``s.get_spec()`` / ``s.loglikelihood``."""
         params = np.ascontiguousarray(params, dtype=np.float64)
         if params.ndim != 1 or params.shape[0] == 0 or params.shape[0] % self.N != 0:
             raise ValueError(f'Invalid parameter vector length: {params.shape}')

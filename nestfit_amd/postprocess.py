@@ -297,6 +297,24 @@ def check_model_lines(store, stack):
     return tables
 
 
+def check_model_fill(store, runner=None):
+    """Whether the store was fitted with a beam filling factor per component (`HdfStore.read_model_fill`), after checking it
+    against the store's own parameter count and, where the caller hands one, against the `runner` (a runner or runner class
+    of an `LteMix`): ValueError where they differ -- the last parameter row would be read as something it is not."""
+    fill = store.read_model_fill()
+    species = store.read_model_species()
+    if fill and not species:
+        raise ValueError('the store has a filling factor (`fill`) but no species: not an LTE mix store')
+    if species and int(store.hdf.attrs['n_params']) != 3 + len(species) + (1 if fill else 0):
+        raise ValueError(f"the store's parameters ({int(store.hdf.attrs['n_params'])}) do not match its species ({len(species)}) "
+                         f"{'with' if fill else 'without'} a filling factor")
+    info = getattr(runner, 'MODEL_INFO', None)
+    if info is not None and bool(getattr(info, 'fill', False)) != fill:
+        raise ValueError(f"the store was fitted {'with' if fill else 'without'} a filling factor, the runner's model is "
+                         f"{'filled' if info.fill else 'not'}: {info!r}")
+    return fill
+
+
 def _spec_name(k, dc):
     """Dataset name of cube k under model_spec: trans<ID> (main.py:1190), spec<k> for a cube with a `LineTable` (hyperfine model)."""
     return f'spec{k}' if getattr(dc, 'lines', None) is not None else f'trans{dc.trans_id}'
@@ -319,6 +337,7 @@ def _device_predictor(store, stack):
         extra['lines'] = check_model_lines(store, stack)
         if store.read_model_species():                   # an LTE mix: the species in the order of the fit
             extra['species'] = store.read_model_species()
+            extra['fill'] = check_model_fill(store)      # ... with a filling factor as the last parameter, if the fit had one
     runner = CubeRunner(xarrs, trans, np.zeros((1, chan_tot)), np.ones((1, len(xarrs))), None, ncomp=1,
                         model=model_id, **extra)
     runner.set_exp_mode('table')                         # map products in the reference's own arithmetic: a one-off, not a rate
@@ -424,6 +443,7 @@ def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, 
     """All steps in the reference's order (main.py:1240-1276)."""
     if store.hdf.attrs.get('model_name') in ('hyperfine', 'lte', 'lte_mix'):     # before any product is written
         check_model_lines(store, stack)
+        check_model_fill(store, runner)
     aggregate_run_attributes(store)
     convolve_evidence(store, evid_kernel)
     aggregate_run_products(store)

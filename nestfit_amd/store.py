@@ -435,8 +435,17 @@ class HdfStore:
         # (an LteMix's Runner describes its model itself, MODEL_INFO: the names and the number of parameters follow the species)
         module = getattr(runner_cls, 'MODEL_INFO', None) or inspect.getmodule(runner_cls)
         self.hdf.attrs.update({name: getattr(module, attr) for name, attr in MODEL_ATTRS})
+        # an LTE mix with a beam filling factor per component: root attribute `fill`.  A store without it was fitted without one.
+        if getattr(module, 'fill', False):
+            self.hdf.attrs['fill'] = True
 
-    def insert_model_lines(self, stack, species=None):
+    def read_model_fill(self):
+        """Whether the store was fitted with a beam filling factor per component (`LteMix(species, fill=True)`): the root
+        attribute `fill`; False for a store without it."""
+        assert self.is_open
+        return bool(self.hdf.attrs.get('fill', False))
+
+    def insert_model_lines(self, stack, species=None, fill=False):
         """The line table of every cube that has one (hyperfine model) under /model_lines/spec<k>: attributes `nu` and
         `name`, datasets `voff` and `tau_wts`.  Nothing for the models whose tables ship with the engine.  The LTE model's
         `LteLines` add the attributes `e_up`, `g_up` and `a_ul`, and their molecule's partition table goes under
@@ -445,7 +454,7 @@ class HdfStore:
         An LTE mix (`species`: its ordered molecules, two or more, or lines with an `LteBlend`): /model_partition has the
         attribute `n_species` and one subgroup species<k> per species, each laid out as a single species' /model_partition, and
         every transition carries the attribute `species`, the index of its molecule.  A store of one species is written as
-        it always was."""
+        it always was -- unless it has a filling factor (`fill`), which takes the mix's layout whatever its species."""
         assert self.is_open
         tables = [getattr(dc, 'lines', None) for dc in stack.cubes]
         if all(t is None for t in tables):
@@ -456,7 +465,7 @@ class HdfStore:
         if any(t is None for t in tables):
             raise ValueError('either every cube of a stack has a LineTable or none has')
         molecule = None
-        if species is not None and (len(species) > 1 or any(type(t).__name__ == 'LteBlend' for t in tables)):
+        if species is not None and (len(species) > 1 or fill or any(type(t).__name__ == 'LteBlend' for t in tables)):
             from .lte import check_mix_lines, transitions_of
             species = tuple(species)
             check_mix_lines(species, tables)
@@ -517,7 +526,7 @@ class HdfStore:
         """The `LineTable`s the store was fitted with, in cube order ([] for a store without any): `LteLines` of the
         stored `Molecule` where the store has a partition table, an `LteBand` for a spec<k> with the attribute `n_trans`.
         A store fitted with an LTE mix: an `LteBlend` per cube, its transitions of the stored species.  with_species: the
-        pair (lines, `read_model_species()`)."""
+        pair (lines, `read_model_species()`); with `read_model_fill()` that rebuilds the model, `LteMix(species, fill=...)`."""
         from .hyperfine import LineTable
         from .lte import LteBlend, Molecule
         assert self.is_open
