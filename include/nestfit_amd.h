@@ -296,6 +296,24 @@ int nfa_specset_null_lnz(const nfa_specset *ss, double *out);
  * batch kernels, and nfa_ring_serve_device refuses its runners (NFA_ERR_ARG; nfa_ring_serve serves them). */
 #define NFA_BASELINE_MAX 3
 int nfa_specset_set_baseline(nfa_specset *ss, int order);
+/* Layered radiative transfer: the components of a parameter vector are layers along the line of sight, component 0 the
+ * FARTHEST from the observer and the last the nearest, and each absorbs what lies behind it.  The model spectrum, measured
+ * against the background like the summed one, is built in component order,
+ *     pred <- pred + (g_c - pred) a_c        g_c = T0 (y(T0 / tex_c) - tbg),  a_c = 1 - e^{-tau_c}
+ * (a filled LTE set: a_c = 10^lnff_c (1 - e^{-tau_c}), exact where the layers in front fill the beam, a random-covering
+ * approximation where they cover it partly), where the summed model is sum_c g_c a_c (hyperfine.pyx:104-118).  A component
+ * with tau_c = 0 in a channel leaves it as it is; one component is the summed model; components that do not overlap in
+ * velocity are too.  The layout of the parameter vector does not change, but the component labels are no longer
+ * exchangeable: an ordered-velocity prior now ties the order along the line of sight to the order in velocity.
+ * on != 0 sets, 0 clears (a new set is summed).  Every set kind takes it -- ammonia, N2H+, line tables, LTE, bands, mixes,
+ * filled sets, with a channel noise and a baseline or without -- but the Gaussian model, which has no optical depth:
+ * NFA_ERR_ARG.  Like nfa_specset_set_baseline it launches held batches first, synchronises the device and drops the
+ * runners' captured single-point graphs: call it between batches.  Layered sets go through the batch kernels (the general
+ * component form); single points and a broker's handful too, and nfa_ring_serve_device refuses their runners ("the resident
+ * kernel has no form for layered transfer: use nfa_ring_serve"). */
+int nfa_specset_set_layered(nfa_specset *ss, int on);
+/* 1 for a layered set, 0 for a summed one (and for null) */
+int nfa_specset_layered(const nfa_specset *ss);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

@@ -56,6 +56,16 @@ def channel_weights(noise, size):
     return 1.0 / np.asarray(noise, dtype=np.float64) ** 2
 
 
+def check_layered(layered, model=None):
+    """`layered` as a bool; ValueError for anything but True / False, and for the Gaussian model, which has no optical
+    depth.  Needs no device."""
+    if not isinstance(layered, (bool, np.bool_)):
+        raise ValueError('`layered` is True or False: whether a component absorbs the components behind it')
+    if layered and model is not None and int(model) == MODEL_GAUSSIAN:
+        raise ValueError('the Gaussian model has no optical depth: its components cannot absorb one another (`layered`)')
+    return bool(layered)
+
+
 class _SpecSet:
     """Owner of a device-resident set of spectra (one pixel or a cube)."""
 
@@ -163,6 +173,14 @@ class _SpecSet:
         self.handle = h
         self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
         self.baseline_order = None
+        self.layered = False
+
+    def set_layered(self, on):
+        """Layered transfer (True) or the summed model (False): nfa_specset_set_layered.  Layered, component 0 is the
+        farthest from the observer and each component absorbs those behind it."""
+        on = check_layered(on)
+        _ffi.check(_ffi.load().nfa_specset_set_layered(self.handle, int(on)))
+        self.layered = on
 
     def set_baseline(self, order):
         """A polynomial baseline of degree <= `order` per (pixel, spectrum) profiled out of the likelihood, or none
@@ -282,13 +300,17 @@ class EngineRunner(Runner):
     MODEL = MODEL_AMMONIA
     N_MODEL = 6
 
-    def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None):
-        """baseline_order: None, or 0..3 for a polynomial baseline of that degree per spectrum, profiled out of the
+    def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False):
+        """layered: layered radiative transfer (nfa_specset_set_layered) -- the components are layers along the
+        line of sight, component 0 the farthest, and each absorbs those behind it; False: the components are summed.
+        `predict` of a layered runner goes through the runner's own spectra set (`_predict_layered`).
+        baseline_order: None, or 0..3 for a polynomial baseline of that degree per spectrum, profiled out of the
         likelihood in closed form (nfa_specset_set_baseline).  null_lnZ is then the baseline-only model's, from
         the runner's own spectra set (the spectra keep the reference's spectrum-alone value), and lnZ - null_lnZ is a Bayes
         factor of baseline-marginalised models."""
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
+        layered = check_layered(layered, self.MODEL)
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -311,10 +333,25 @@ class EngineRunner(Runner):
                             lines=[s.lines for s in spectra] if self.MODEL in (MODEL_HYPERFINE, MODEL_LTE) else None,
                             species=getattr(self, 'SPECIES', None), fill=getattr(self, 'FILL', False))
         self._run = _RunnerHandle(self._ss, utrans, self.ncomp, cold, lte)
+        self.layered = layered
+        if layered:
+            self._ss.set_layered(True)
         self.baseline_order = baseline_order
         if baseline_order is not None:
             self._ss.set_baseline(baseline_order)
             self.null_lnZ = float(self._ss.null_lnZ().sum())
+
+    def _predict_layered(self, params):
+        """`predict` of a layered runner: the spectra's own one-spectrum sets are summed ones, so the model comes from the
+        runner's set (`predict_batch`) and goes into every spectrum, with the spectrum's lnL formed on the host."""
+        spec, _ = self.predict_batch(params.reshape(1, -1))
+        off = self._ss.offsets
+        for k, s in enumerate(self._model_spectra()):
+            s._pred = spec[0, off[k]:off[k + 1]].copy()
+            w = channel_weights(s.noise, s.size)
+            resid = np.where(w > 0, s.data - s._pred, 0.0)
+            scale = 1.0 if np.ndim(s.noise) else float(s.noise) ** 2           # (channel_weights: 1 / sigma_c^2, or ones)
+            s._lnL = float(-np.sum(w * resid * resid) / (2.0 * scale))
 
     def _model_spectra(self):
         return list(self.spectra)

@@ -5,7 +5,7 @@ behaviour; all arithmetic runs in the HIP engine through the C ABI.
 import numpy as np
 
 from ._model import (MODEL_AMMONIA, EngineRunner, EngineSpectrumMixin, _pix_ptr, _RunnerHandle,  # noqa: F401
-                     _SpecSet, check_baseline_order, par_names)
+                     _SpecSet, check_baseline_order, check_layered, par_names)
 from .core import HyperfineSpectrum
 
 N_LEVELS = 9
@@ -55,17 +55,19 @@ class AmmoniaRunner(EngineRunner):
     MODEL = MODEL_AMMONIA
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None):
+    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None, layered=False):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
+        layered = check_layered(layered)
         self.spectra = list(spectra)
         self.cold = bool(cold)
         self.lte = bool(lte)
-        self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, baseline_order=baseline_order)
+        self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, baseline_order=baseline_order, layered=layered)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
+        check_layered(kwargs.get('layered', False))
         spectra = np.array([AmmoniaSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 
@@ -76,6 +78,8 @@ class AmmoniaRunner(EngineRunner):
         """Model spectra for physical `params` into every spectrum of the runner
         (reference: ammonia.pyx:437-447)."""
         params = self._check_params(params)
+        if self.layered:
+            return self._predict_layered(params)
         for s in self.spectra:
             amm_predict(s, params, self.cold, self.lte)
 

@@ -823,7 +823,12 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // FILL (the general component form of the batch kernels only): a component's T0 (y - tbg) is multiplied by its beam filling
 // factor (DK_FILL of its record: one more scalar load beside the ones of the Tb pass) at every site that adds to `pred`;
 // spectra out, the weighted sum and the baseline's moments are formed from `pred` and carry it without further code.
-template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false>
+// LAYER (the same form only): layered transfer.  The components are layers along the line of sight, component
+// 0 the farthest, and each absorbs what lies behind it: pred <- pred + (g - pred) a at the sites that add g a, in the index
+// order this loop already walks.  A component without a window in the row, or a lane with tau == 0 (a == 0), leaves pred as
+// it is.  The Gaussian class has no optical depth: nfa_specset_set_layered refuses that model.
+template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false,
+          bool LAYER = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -1018,6 +1023,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     // BASELINE: the moments m_k(p) of the lane's channels, per part (bl_acc) and over the parts in part order (bl_tot)
     static_assert(!BASELINE || (WEIGHTED && !DYN), "the baseline form is a weighted batch form");
     static_assert(!FILL || (NCOMP == 0 && !DYN), "a filling factor: the general component form of the batch kernels");
+    static_assert(!LAYER || (NCOMP == 0 && !DYN), "layered transfer: the general component form of the batch kernels");
     constexpr int NBL = BASELINE ? NFA_BL_NB : 1;
     double bl_acc[NBL], bl_tot[NBL];
 #pragma unroll
@@ -1214,7 +1220,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     // indices, is the reference's to the bit in the table mode.  Lanes with tau == 0 (skipped by the
                     // reference, hyperfine.pyx:104-105) get g * (1 - 1) = +-0: the sum needs no per-lane select.
                     double g = __builtin_fma(xj, __builtin_fma(b0x, xj, a0x), -p3);
-                    if constexpr (FILL) g *= ff;
+                    if constexpr (LAYER) g -= pred;                   // the layer absorbs what lies behind it, over the
+                    if constexpr (FILL) g *= ff;                      // fraction of the beam it fills: ((g - pred) f) a
                     if (MODE == 2) pred = __builtin_fma(g, one_minus_fastexp_f32((float)tau, livem), pred);
                     else pred = __builtin_fma(g, MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm), pred);
                     return;
@@ -1243,6 +1250,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                         const double y = nf_iemtex(T0 / Dk[c * 4], g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
                         g = T0 * (y - tbg);
                     }
+                    if constexpr (LAYER) g -= pred;
                     if constexpr (FILL) g *= ff;
                     pred = __builtin_fma(g, one_minus_fastexp_f32((float)tau, livem), pred);
                 } else {
@@ -1271,11 +1279,13 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                         const double y = (HOISTX && NCOMP > 0) ? cx_xs[c] * (x - cx_xlo[c]) + cx_ylo[c]
                                                    : Dk[dko + DK_XS] * (x - Dk[dko + DK_XLO]) + Dk[dko + DK_YLO];
                         double g = T0 * (y - tbg);
+                        if constexpr (LAYER) g -= pred;
                         if constexpr (FILL) g *= ff;
                         pred += g * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
                     } else {
                         const double y = nf_iemtex(x, g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
                         double g = T0 * (y - tbg);
+                        if constexpr (LAYER) g -= pred;
                         if constexpr (FILL) g *= ff;
                         const double tb = g * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
                         pred += !(tau == 0) ? tb : 0.0;
@@ -1428,6 +1438,40 @@ lnl_kernel_bl_fill(SpecDev S, BatchGroup grp, const double *__restrict__ D, doub
     const double *sm = smem;
     if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
     lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+}
+
+// The kernels of a LAYERED set (nfa_specset_set_layered): lnl_kernel, lnl_kernel_wt and lnl_kernel_bl in the
+// general component form with lnl_body's LAYER flag, and FILL for a filled LTE set.  Like the filled family they take no
+// other form -- no unrolled component loop, no queue, no w8: 3 x 16 instances over (MODE, WRITE_SPEC, WIDE, FILL).
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_layer(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                 double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, false, false, FILL, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+}
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_wt_layer(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                    double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, FILL, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+}
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_bl_layer(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                    double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one

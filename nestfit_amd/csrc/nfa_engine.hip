@@ -213,6 +213,7 @@ struct nfa_specset {
     MixRec  *d_mix = nullptr;                       // LTE mixes: SpecDev.mix (null for a set of one species)
     int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
     bool    filled = false;                         // an LTE set with a beam filling factor per component: the last parameter
+    bool    layered = false;                        // layered transfer: a component absorbs those behind it (nfa_specset_set_layered)
     bool    bl_w1 = false;                          // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
 };
 
@@ -283,7 +284,7 @@ static int runner_mode(const nfa_runner *r) { return r->exp_mode >= 0 ? r->exp_m
 static LpKnobs plan_knobs() { return {g_eng.n_cu, g_eng.setup_ti, g_eng.setup_threads, g_eng.setup_sub, g_eng.lnl_queue, g_eng.lnl_queue_wg, g_eng.coalesce, g_eng.ablate}; }
 static LpLaunch plan_launch(const nfa_runner *r, int64_t B, int mode, bool write_spec, bool has_prior, int slot) {
     return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl != nullptr,
-                    r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr, r->ss->filled};
+                    r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr, r->ss->filled, r->ss->layered};
 }
 
 extern "C" {
@@ -992,6 +993,26 @@ int nfa_specset_set_baseline(nfa_specset *ss, int order) {
     return launch_bl_setup(ss, 0, ss->n_pix, true);
 }
 
+int nfa_specset_set_layered(nfa_specset *ss, int on) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    if (ss->dev.model == NFA_MODEL_GAUSSIAN)
+        return fail(NFA_ERR_ARG, "the Gaussian model has no optical depth: its components cannot absorb one another (no layered transfer)");
+    int rc = engine_init(); if (rc) return rc;
+    // as nfa_specset_set_baseline: held batches were accepted for the old likelihood, launches in flight were planned for
+    // it, and a runner's captured single-point graph holds the old kernel
+    rc = flush_all_runners(); if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    {
+        std::lock_guard<std::mutex> lk(g_runners_m);
+        for (nfa_runner *r : g_runners)
+            if (r->ss == ss) { RUNNER_LOCK(r); if (r->g1) { (void)hipGraphExecDestroy(r->g1); r->g1 = nullptr; } }
+    }
+    ss->layered = on != 0;
+    return NFA_OK;
+}
+
+int nfa_specset_layered(const nfa_specset *ss) { return ss && ss->layered ? 1 : 0; }
+
 int nfa_specset_null_lnz(const nfa_specset *ss, double *out) {
     if (!ss || !out) return fail(NFA_ERR_ARG, "null argument");
     const int64_t n = ss->n_pix * ss->dev.n_spec;
@@ -1366,7 +1387,8 @@ static int launch_band(nfa_runner *r, int slot, int64_t B) {
 // lnl_kernel, _wt and _bl for all 32 (mode, spectra out, wide, NCOMP), lnl_kernel_w8 for the table mode with spectra out,
 // lnl_kernel_queue for the table mode's narrow sets.  NCOMP 1..3: the component loop unrolled; 0: the general form.
 // A filled LTE set (a plan with `filled`): lnl_kernel_fill, _wt_fill, _bl_fill over (mode, spectra out, wide), the
-// general form whatever the component count.
+// general form whatever the component count.  A layered set (a plan with `layered`): lnl_kernel_layer, _wt_layer, _bl_layer
+// over (mode, spectra out, wide, filled), the same.
 typedef void (*LnlKernel)(SpecDev, BatchGroup, const double *, double *, double *, long, LnlGeom, const double *);
 template <int I>     // I: bit 4 fast mode, bit 3 spectra out, bit 2 wide, bits 0-1 NCOMP
 static LnlKernel lnl_kernel_inst(LnlForm form) {
@@ -1396,7 +1418,23 @@ static LnlKernel lnl_kernel_fill_at(int i, LnlForm form, std::index_sequence<I..
     static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_fill_inst<(int)I>...};
     return inst[i](form);
 }
-static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, LnlForm form, bool filled) {
+template <int I>     // I: bit 3 filled, bit 2 fast mode, bit 1 spectra out, bit 0 wide
+static LnlKernel lnl_kernel_layer_inst(LnlForm form) {
+    constexpr int MODE = (I & 4) ? 2 : 0;
+    constexpr bool FILL = (I & 8) != 0, WS = (I & 2) != 0, WIDE = (I & 1) != 0;
+    if (form == LNL_BASELINE) return lnl_kernel_bl_layer<MODE, WS, WIDE, FILL>;
+    if (form == LNL_WEIGHTED) return lnl_kernel_wt_layer<MODE, WS, WIDE, FILL>;
+    return form == LNL_PLAIN ? lnl_kernel_layer<MODE, WS, WIDE, FILL> : nullptr;
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_layer_at(int i, LnlForm form, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_layer_inst<(int)I>...};
+    return inst[i](form);
+}
+static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, LnlForm form, bool filled, bool layered) {
+    if (layered)
+        return lnl_kernel_layer_at((filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0), form,
+                                   std::make_index_sequence<16>());
     if (filled) return lnl_kernel_fill_at((mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0), form, std::make_index_sequence<8>());
     const int i = (mode == 0 ? 0 : 16) | (write_spec ? 8 : 0) | (wide ? 4 : 0) | (ncomp >= 1 && ncomp <= 3 ? ncomp : 0);
     return lnl_kernel_at(i, form, std::make_index_sequence<32>());
@@ -1413,7 +1451,7 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form, P.filled);
+    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form, P.filled, P.layered);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
     int rc = ensure_dynamic_lds((const void *)kern, P.lds); if (rc) return rc;
     hipStream_t st = r->lanes[slot];
@@ -1621,7 +1659,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     if (!g_eng.point || r->profiling || B > NFA_POINT_MAXB) return 0;
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
-    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr, S.band != nullptr, r->ss->filled);
+    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

@@ -69,8 +69,9 @@ struct LpShape {
 };
 // One launch: B items in `mode` (0 table, 2 fast), of a group of `group_n` batches of `group_each` rows; what the
 // spectra set is right now (nfa_specset_set_baseline changes it) and whether the lane has its queue counters; filled: an
-// LTE set with a beam filling factor per component (nfa_specset_create_lte_filled; in the struct's tail padding)
-struct LpLaunch { int64_t B; int mode, group_n; int64_t group_each; bool write_spec, has_prior, baseline, weighted, has_queue, filled; };
+// LTE set with a beam filling factor per component (nfa_specset_create_lte_filled; in the struct's tail padding); layered:
+// a set whose components absorb those behind them (nfa_specset_set_layered; the next byte of that padding, zero = summed)
+struct LpLaunch { int64_t B; int mode, group_n; int64_t group_each; bool write_spec, has_prior, baseline, weighted, has_queue, filled, layered; };
 // The process options the decisions read, as they stand at the call (nfa_set_option)
 struct LpKnobs { int n_cu, setup_ti, setup_threads, setup_sub, lnl_queue, lnl_queue_wg, coalesce, ablate; };
 
@@ -157,8 +158,9 @@ enum LnlForm { LNL_PLAIN, LNL_W8, LNL_QUEUE, LNL_WEIGHTED, LNL_BASELINE };     /
 // waves per workgroup, its dynamic LDS in bytes, workgroups; error: null, or why there is no plan
 // filled (in the padding behind `wide`): the form's instance of the filled family, lnl_kernel_fill / _wt_fill / _bl_fill --
 // the general component form with the filling factor in the Tb pass.  The form keeps its five values; only LNL_PLAIN,
-// LNL_WEIGHTED and LNL_BASELINE come with `filled`.
-struct LnlPlan { LnlForm form; bool wide, filled; LnlGeom G; int waves; size_t lds; int64_t blocks; const char *error; };
+// LNL_WEIGHTED and LNL_BASELINE come with `filled`.  layered (the next padding byte; zero = summed): the form's instance of
+// the layered family, lnl_kernel_layer / _wt_layer / _bl_layer, over `filled` as well; the same three forms only.
+struct LnlPlan { LnlForm form; bool wide, filled, layered; LnlGeom G; int waves; size_t lds; int64_t blocks; const char *error; };
 // Plans the likelihood launch of L.B items (the table of forms in DESIGN 4.2 is tested against this chain).
 inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     LnlPlan P = {};
@@ -171,6 +173,7 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     P.G = lnl_geom(s, k, L.B);
     P.G.ablate = k.ablate;
     P.filled = L.filled;
+    P.layered = L.layered;
     const int split = P.G.split;
     // Waves per workgroup: option wpb, made a multiple of the split.  Table mode stages 51 KB of product tables per
     // workgroup, so the workgroup is made as fat as keeps the most waves resident per CU (table_waves); its split launches take eight.
@@ -192,7 +195,8 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     if (L.baseline) P.form = LNL_BASELINE;           // every mode, wide, spectra out; such a set is weighted too
     else if (L.weighted) P.form = LNL_WEIGHTED;      // every mode, wide, spectra out: no queue or w8 form of its own (the
                                                      // units give the same bits whatever the form, so none is instantiated)
-    else if (L.filled) P.form = LNL_PLAIN;           // a filling factor: baseline, weighted or plain, never the queue or w8 form
+    else if (L.filled || L.layered) P.form = LNL_PLAIN;   // a filling factor, layered transfer: baseline, weighted or plain,
+                                                     // never the queue or w8 form
     else if (table && !P.wide && split == 1          // the queue kernel is table mode, narrow, one wave per unit ...
              && k.lnl_queue != 0                     // ... unless switched off (option lnl_queue) ...
              && long_units && fills_twice            // ... pays for launches like these only ...
@@ -269,12 +273,15 @@ inline SetupPlan plan_setup(const LpShape &s, const LpKnobs &k, const LpLaunch &
 // lds_point: more than LDS_PER_CU sends the points the batch path; ctl_double: the resident kernel's control words
 struct FusedPlan { const char *refusal, *ring_error; LnlGeom G; int n_blocks, ctl_double; bool staged; size_t lds_point, lds_ring; };
 // banded: an LTE set with several transitions inside a spectrum (lte_band_kernel runs between the stages of a batch);
-// filled: one with a beam filling factor per component (lte_fill_kernel runs there, and only the batch kernels have the form)
+// filled: one with a beam filling factor per component (lte_fill_kernel runs there, and only the batch kernels have the form);
+// layered: a set whose components absorb those behind them (nfa_specset_set_layered: the batch kernels only, and the first
+// refusal of all -- whatever else the set is, its points must not reach a kernel that sums)
 inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted, bool banded = false,
-                            bool filled = false) {
+                            bool filled = false, bool layered = false) {
     FusedPlan P = {};
     P.G = lnl_geom(s, k, 1);
-    if (s.ndim > NFA_POINT_MAXDIM || lnl_wide(s)) P.refusal = "this runner's points go through the batch kernels: use nfa_ring_serve";
+    if (layered) P.refusal = "the resident kernel has no form for layered transfer: use nfa_ring_serve";
+    else if (s.ndim > NFA_POINT_MAXDIM || lnl_wide(s)) P.refusal = "this runner's points go through the batch kernels: use nfa_ring_serve";
     else if (filled) P.refusal = "the resident kernel has no form for a filling factor: use nfa_ring_serve";
     // (weighted sets, baseline sets among them: lnl_kernel_wt / lnl_kernel_bl.  The unweighted body would compute the unweighted sum.)
     else if (baseline) P.refusal = "the resident kernel has no form for a baseline: use nfa_ring_serve";

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_layered
 from .core import _as_inplace_matrix
 
 
@@ -44,10 +44,12 @@ class CubeRunner:
     utrans : PriorTransformer
     baseline_order : None, or 0..3: a polynomial baseline of that degree per (pixel, spectrum), profiled out of the
         likelihood in closed form; null_lnZ is then the baseline-only model's
+    layered : layered radiative transfer: component 0 is the farthest from the observer and every component
+        absorbs those behind it; False (default): the components are summed.  Not for the Gaussian model (ValueError).
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
-                 model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False):
+                 model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
@@ -56,6 +58,7 @@ class CubeRunner:
         as one more, the last (`LteMix(species, fill=True)`; one species included)."""
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
+        layered = check_layered(layered, model)                      # before any device call
         if species is None and int(model) == 4 and lines is not None:
             from .lte import LteBand, LteBlend, LteLines, lines_species
             lines = list(lines)
@@ -66,6 +69,9 @@ class CubeRunner:
         self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs, lines=lines, species=species,
                             fill=fill)
         self._run = _RunnerHandle(self._ss, utrans, ncomp, cold, lte)
+        self.layered = layered
+        if layered:
+            self._ss.set_layered(True)
         self.baseline_order = baseline_order
         if baseline_order is not None:
             self._ss.set_baseline(baseline_order)

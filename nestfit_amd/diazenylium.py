@@ -5,7 +5,7 @@ nestfit/models/hyperfine.pyx:52-118).  Parameters per component: voff, tex, ltau
 """
 import numpy as np
 
-from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_baseline_order, par_names
+from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_layered, par_names
 from .core import HyperfineSpectrum
 
 N_LEVELS = 3
@@ -46,15 +46,17 @@ class DiazenyliumRunner(EngineRunner):
     MODEL = MODEL_DIAZENYLIUM
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
+        layered = check_layered(layered)
         self.spectra = list(spectra)
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order)
+        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
+        check_layered(kwargs.get('layered', False))
         spectra = np.array([DiazenyliumSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 
@@ -63,6 +65,8 @@ class DiazenyliumRunner(EngineRunner):
 
     def predict(self, params):
         params = self._check_params(params)
+        if self.layered:
+            return self._predict_layered(params)
         for s in self.spectra:
             nnhp_predict(s, params)
 

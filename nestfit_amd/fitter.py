@@ -13,6 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import sampler
+from ._model import check_layered
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
@@ -74,6 +75,8 @@ class CubeFitter:
         self.fill = bool(getattr(model, 'fill', False))  # ... and whether its components have a filling factor
         self.stack, self.utrans, self.runner_cls = stack, utrans, runner_cls
         self.runner_kwargs = dict(runner_kwargs or {})
+        # layered transfer (runner_kwargs['layered']): checked here, before any pixel is fitted
+        self.layered = check_layered(self.runner_kwargs.get('layered', False), self.model_id)
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
         self.lnZ_thresh, self.ncomp_max, self.nlive_snr_fact = lnZ_thresh, ncomp_max, nlive_snr_fact
         self.nlive_quantum = max(1, int(nlive_quantum))

@@ -47,7 +47,7 @@ function come from a catalogue of the user's.
 """
 import numpy as np
 
-from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, par_names
+from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_layered, par_names
 from .core import HyperfineSpectrum as _HyperfineBase
 from .hyperfine import CKMS, MAX_LINES, LineTable
 
@@ -405,17 +405,19 @@ class LteRunner(EngineRunner):
     MODEL = MODEL_LTE
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
+        layered = check_layered(layered)
         self.spectra = list(spectra)
         self.molecule = check_one_molecule([s.lines for s in self.spectra])
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order)
+        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         """spec_data: rows [xarr, data, noise, LteLines or LteBand]."""
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
+        check_layered(kwargs.get('layered', False))
         spec_data = list(spec_data)
         check_one_molecule([row[3] for row in spec_data])
         spectra = np.array([LteSpectrum(*args) for args in spec_data])
@@ -426,6 +428,8 @@ class LteRunner(EngineRunner):
 
     def predict(self, params):
         params = self._check_params(params)
+        if self.layered:
+            return self._predict_layered(params)
         for s in self.spectra:
             lte_predict(s, params)
 
@@ -536,18 +540,20 @@ class _MixRunner(EngineRunner):
     MODEL = MODEL_LTE
     MIX = None
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
+        layered = check_layered(layered)
         self.spectra = list(spectra)
         check_mix_lines(self.MIX.species, [s.lines for s in self.spectra])
         self.species = self.MIX.species
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order)
+        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         """spec_data: rows [xarr, data, noise, LteLines | LteBand | LteBlend]."""
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
+        check_layered(kwargs.get('layered', False))
         spec_data = list(spec_data)
         check_mix_lines(cls.MIX.species, [row[3] for row in spec_data])
         spectra = np.array([cls.MIX.Spectrum(*args) for args in spec_data])
@@ -558,6 +564,8 @@ class _MixRunner(EngineRunner):
 
     def predict(self, params):
         params = self._check_params(params)
+        if self.layered:
+            return self._predict_layered(params)
         for s in self.spectra:
             self.MIX.predict(s, params)
 

@@ -315,15 +315,31 @@ def check_model_fill(store, runner=None):
     return fill
 
 
+def check_model_layered(store, runner=None):
+    """Whether the store was fitted with layered radiative transfer (`HdfStore.read_model_layered`), after checking it against
+    the `runner` where the caller hands one that says (`.layered`): ValueError where they differ -- the runner's spectra
+    would not be the model of the fit.  The Gaussian model has no layered form."""
+    layered = store.read_model_layered()
+    if layered and store.hdf.attrs.get('model_name') == 'gaussian':
+        raise ValueError('the store says `layered`, but the Gaussian model has no optical depth and no layered form')
+    theirs = getattr(runner, 'layered', None)
+    if isinstance(theirs, (bool, np.bool_)) and bool(theirs) != layered:
+        raise ValueError(f"the store was fitted with {'layered' if layered else 'summed'} components, the runner is "
+                         f"{'layered' if theirs else 'summed'}")
+    return layered
+
+
 def _spec_name(k, dc):
     """Dataset name of cube k under model_spec: trans<ID> (main.py:1190), spec<k> for a cube with a `LineTable` (hyperfine model)."""
     return f'spec{k}' if getattr(dc, 'lines', None) is not None else f'trans{dc.trans_id}'
 
 
-def _device_predictor(store, stack):
+def _device_predictor(store, stack, ncomp=1, layered=False):
     """predict(lon[B], lat[B], theta[B, p], want_spectra) -> (spectra[B, chan_tot] or None, peak[B, t],
     integrated[B, t]) on the GPU: every pixel's data stay where the fit left them conceptually -- a predict
-    needs only the axes, so the spectra set is built over the requested pixels alone."""
+    needs only the axes, so the spectra set is built over the requested pixels alone.  ncomp, layered: a predictor of
+    whole models of that many layers (theta[B, p * ncomp], parameter-major) for `model_spec_total`; the default is the
+    reference's one-component predictor, for which layered and summed are the same thing."""
     from .cube import CubeRunner
     model_id = _MODEL_ID[store.hdf.attrs['model_name']]
     xarrs = [dc.xarr for dc in stack.cubes]
@@ -338,8 +354,8 @@ def _device_predictor(store, stack):
         if store.read_model_species():                   # an LTE mix: the species in the order of the fit
             extra['species'] = store.read_model_species()
             extra['fill'] = check_model_fill(store)      # ... with a filling factor as the last parameter, if the fit had one
-    runner = CubeRunner(xarrs, trans, np.zeros((1, chan_tot)), np.ones((1, len(xarrs))), None, ncomp=1,
-                        model=model_id, **extra)
+    runner = CubeRunner(xarrs, trans, np.zeros((1, chan_tot)), np.ones((1, len(xarrs))), None, ncomp=ncomp,
+                        model=model_id, layered=layered, **extra)
     runner.set_exp_mode('table')                         # map products in the reference's own arithmetic: a one-off, not a rate
 
     scratch = {}
@@ -419,6 +435,36 @@ def generate_predicted_profiles(store, stack, runner=None, predict_backend=None)
             cube[m[s], :, b[s], l[s]] = spec[:, edges[k]:edges[k + 1]]
     for k, (cube, dc) in enumerate(zip(cubes, stack.cubes)):
         store.create_dataset(_spec_name(k, dc), cube, group=f'{store.dpath}/model_spec')
+    if check_model_layered(store):
+        generate_total_profiles(store, stack, predict_backend=predict_backend)
+
+
+def generate_total_profiles(store, stack, predict_backend=None):
+    """A layered store: 'model_spec_total/<name>' (S, b, l), float32 -- the whole model of every pixel, its
+    best number of components through a layered runner of that many layers, NaN where the pixel has none.  The cubes under
+    'model_spec' are each layer seen alone, unattenuated, and do not add up to this one where layers overlap.
+    `predict_backend` stands in for the device as elsewhere, here with theta[B, p * n] (parameter-major) of n layers."""
+    print(':: Generating MAP total (layered) model spectral profiles')
+    pmap = _product(store, 'nbest_MAP')                  # (m, p, b, l)
+    n_lat, n_lon = pmap.shape[2], pmap.shape[3]
+    ok = np.all(np.isfinite(pmap), axis=1)               # (m, b, l)
+    n_layers = ok.sum(axis=0)                            # the pixel's components: the first n_layers rows of the MAP cube
+    cubes = [np.full((dc.nchan, n_lat, n_lon), np.nan, dtype=np.float32) for dc in stack.cubes]
+    edges = np.concatenate([[0], np.cumsum([dc.nchan for dc in stack.cubes])])
+    for n in np.unique(n_layers[n_layers > 0]):
+        b, l = np.nonzero((n_layers == n) & np.all(ok[:n], axis=0))
+        if not b.size:
+            continue
+        # parameter-major rows: parameter q of layer c at q * n + c
+        theta = np.ascontiguousarray(pmap[:n][:, :, b, l].transpose(2, 1, 0).reshape(b.size, -1))     # (n, p, B) -> (B, p n)
+        predict = predict_backend or _device_predictor(store, stack, ncomp=int(n), layered=True)
+        for a in range(0, theta.shape[0], PREDICT_ROWS):
+            s = slice(a, a + PREDICT_ROWS)
+            spec, _, _ = predict(l[s], b[s], theta[s], True)
+            for k, cube in enumerate(cubes):
+                cube[:, b[s], l[s]] = spec[:, edges[k]:edges[k + 1]].T
+    for k, (cube, dc) in enumerate(zip(cubes, stack.cubes)):
+        store.create_dataset(_spec_name(k, dc), cube, group=f'{store.dpath}/model_spec_total')
 
 
 def create_fits_from_store(store, prefix='source'):
@@ -444,6 +490,7 @@ def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, 
     if store.hdf.attrs.get('model_name') in ('hyperfine', 'lte', 'lte_mix'):     # before any product is written
         check_model_lines(store, stack)
         check_model_fill(store, runner)
+    check_model_layered(store, runner)
     aggregate_run_attributes(store)
     convolve_evidence(store, evid_kernel)
     aggregate_run_products(store)

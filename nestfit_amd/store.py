@@ -426,6 +426,10 @@ class HdfStore:
         # a store without the attribute was fitted without one
         order = (getattr(fitter, 'runner_kwargs', None) or {}).get('baseline_order')
         self.hdf.attrs['baseline_order'] = -1 if order is None else int(order)
+        # layered radiative transfer (runner_kwargs['layered']): root attribute `layered`.  A store without it
+        # was fitted with summed components.
+        if (getattr(fitter, 'runner_kwargs', None) or {}).get('layered', False):
+            self.hdf.attrs['layered'] = True
         quantum = getattr(fitter, 'nlive_quantum', 1)
         if quantum != 1:                 # a deviation from main.py:445-447 is written down where the results are
             self.hdf.attrs['nlive_quantum'] = int(quantum)
@@ -438,6 +442,12 @@ class HdfStore:
         # an LTE mix with a beam filling factor per component: root attribute `fill`.  A store without it was fitted without one.
         if getattr(module, 'fill', False):
             self.hdf.attrs['fill'] = True
+
+    def read_model_layered(self):
+        """Whether the store was fitted with layered radiative transfer (`runner_kwargs={'layered': True}`): the root
+        attribute `layered`; False -- summed components -- for a store without it."""
+        assert self.is_open
+        return bool(self.hdf.attrs.get('layered', False))
 
     def read_model_fill(self):
         """Whether the store was fitted with a beam filling factor per component (`LteMix(species, fill=True)`): the root
