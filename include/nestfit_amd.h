@@ -314,6 +314,26 @@ int nfa_specset_set_baseline(nfa_specset *ss, int order);
 int nfa_specset_set_layered(nfa_specset *ss, int on);
 /* 1 for a layered set, 0 for a summed one (and for null) */
 int nfa_specset_layered(const nfa_specset *ss);
+/* A calibration uncertainty per spectrum, integrated out of the likelihood in closed form (no sampler dimension).  The data
+ * of spectrum s are d = g p(theta) + baseline + noise with a gain g ~ N(1, cal[s]^2): cal[n_spec] are the fractional 1-sigma
+ * uncertainties of the spectra's intensity scales, shared by all pixels, each finite and in [0, 1].  With the weighted
+ * products <x,y> = sum_c w_c x_c y_c (the baseline, if any, projected out of both), A = <p,p>, B = <d,p> and chi2_1 the value
+ * at g = 1 (what the set computes without a calibration):
+ *     lnL_s = -[chi2_1 - s^2 (B - A)^2 / (sigma^2 + s^2 A)] / (2 sigma^2) - log1p(s^2 A / sigma^2) / 2
+ * The last term depends on theta and belongs to the marginal; nfa_specset_null_lnz (p = 0) is unchanged, so lnZ - null_lnZ
+ * stays a Bayes factor.  A spectrum with cal[s] = 0 keeps chi2_1 to the bit.  The gain is a marginalised nuisance with a
+ * proper prior, independent per (pixel, spectrum): it is no parameter of an information criterion.
+ * cal = NULL or all zeros removes the calibration (the set's former kernels and results bit for bit); a value that is not
+ * finite or lies outside [0, 1] returns NFA_ERR_ARG and leaves the set as it was.  Every set kind and model takes it, with
+ * a channel noise, a baseline or layering or without; it commutes with nfa_specset_set_baseline.  Like that call it
+ * launches held batches first, synchronises the device and drops the runners' captured single-point graphs: call it
+ * between batches.  nfa_specset_set_data keeps it.  Spectra out are unchanged: the model at g = 1.  Calibrated sets go
+ * through the batch kernels (the general component form); single points and a broker's handful too, and
+ * nfa_ring_serve_device refuses their runners ("the resident kernel has no form for a calibration uncertainty: use
+ * nfa_ring_serve"). */
+int nfa_specset_set_calibration(nfa_specset *ss, const double *cal);
+/* 1 and out[n_spec] = the values set (out may be null), or 0 for a set without a calibration uncertainty (and for null) */
+int nfa_specset_calibration(const nfa_specset *ss, double *out);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

@@ -70,6 +70,8 @@ SIGNATURES = {
     'nfa_specset_set_baseline': (C.c_int, [C.c_void_p, C.c_int]),
     'nfa_specset_set_layered': (C.c_int, [C.c_void_p, C.c_int]),
     'nfa_specset_layered': (C.c_int, [C.c_void_p]),
+    'nfa_specset_set_calibration': (C.c_int, [C.c_void_p, _dp]),
+    'nfa_specset_calibration': (C.c_int, [C.c_void_p, _dp]),
     'nfa_specset_tbg': (C.c_int, [C.c_void_p, _dp]),
     'nfa_specset_chan_tot': (C.c_int64, [C.c_void_p]),
     'nfa_priors_create': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(PriorDesc), C.c_int,

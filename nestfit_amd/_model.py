@@ -26,6 +26,47 @@ def check_baseline_order(order):
     return None if order == -1 else order
 
 
+def check_calibration(cal, n_spec=None):
+    """`calibration` of a runner: the fractional 1-sigma uncertainty of every spectrum's intensity scale.  None
+    for none; a number applies to all `n_spec` spectra; else one value per spectrum.  Every value is a finite number in
+    [0, 1]; all zeros is None.  Returns None or a float64 array (of n_spec values when n_spec is given); ValueError
+    otherwise.  Needs no device."""
+    if cal is None:
+        return None
+    what = 'calibration must be None, a number in [0, 1] or one such number per spectrum'
+    is_num = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    if is_num(cal):
+        vals = [cal] * (1 if n_spec is None else int(n_spec))
+    elif isinstance(cal, np.ndarray) and cal.ndim == 1 and cal.dtype.kind in 'iuf':
+        vals = list(cal)
+    elif isinstance(cal, (list, tuple)) and all(is_num(v) for v in cal):
+        vals = list(cal)
+    else:
+        raise ValueError(f'{what}, not {cal!r}')
+    if not is_num(cal) and n_spec is not None and len(vals) != int(n_spec):
+        raise ValueError(f'{what}: {len(vals)} values for {int(n_spec)} spectra')
+    out = np.array(vals, dtype=np.float64)
+    if out.size == 0 or not np.all(np.isfinite(out)) or np.any(out < 0.0) or np.any(out > 1.0):
+        raise ValueError(f'{what}, not {cal!r}')
+    return out if np.any(out > 0.0) else None
+
+
+def gain_fit(data, pred, weight, sigma, cal, order=None):
+    """Posterior (mean, standard deviation) of the gain of ONE spectrum at a given model `pred`: data =
+    g pred + baseline + noise, g ~ N(1, cal^2), channel weights `weight` (0: masked), sigma the noise of weight 1; with a
+    baseline of degree <= `order`, `baseline_fit`'s projection is taken out of data and model first.  numpy on the host."""
+    w = np.asarray(weight, dtype=np.float64)
+    d = np.where(w > 0, np.asarray(data, dtype=np.float64), 0.0)
+    p = np.asarray(pred, dtype=np.float64)
+    if order is not None:
+        d = d - baseline_fit(d, w, order)
+        p = p - baseline_fit(p, w, order)
+    A, B = float(np.sum(w * p * p)), float(np.sum(w * d * p))
+    s2, sig2 = float(cal) ** 2, float(sigma) ** 2
+    den = sig2 + s2 * A
+    return 1.0 + s2 * (B - A) / den, float(cal) * float(sigma) / np.sqrt(den)
+
+
 def baseline_fit(resid, weight, order):
     """Best-fit baselines of residual spectra resid[..., N] under channel weights weight[..., N] (0: masked, whose residual
     is ignored; the scale of the weights does not matter): the polynomial of degree <= `order` in the channel index that
@@ -174,6 +215,14 @@ class _SpecSet:
         self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
         self.baseline_order = None
         self.layered = False
+        self.calibration = None
+
+    def set_calibration(self, cal):
+        """A calibration uncertainty per spectrum, integrated out of the likelihood (`check_calibration`'s argument), or
+        none (None, zeros): nfa_specset_set_calibration.  null_lnZ() does not change."""
+        cal = check_calibration(cal, self.n_spec)
+        _ffi.check(_ffi.load().nfa_specset_set_calibration(self.handle, None if cal is None else _ffi.dptr(cal)))
+        self.calibration = cal
 
     def set_layered(self, on):
         """Layered transfer (True) or the summed model (False): nfa_specset_set_layered.  Layered, component 0 is the
@@ -300,8 +349,12 @@ class EngineRunner(Runner):
     MODEL = MODEL_AMMONIA
     N_MODEL = 6
 
-    def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False):
-        """layered: layered radiative transfer (nfa_specset_set_layered) -- the components are layers along the
+    def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False,
+               calibration=None):
+        """calibration: None, or the fractional 1-sigma uncertainty of the spectra's intensity scales -- a number for all of
+        them or one per spectrum, each in [0, 1] -- integrated out of the likelihood in closed form per spectrum
+        (nfa_specset_set_calibration); all zeros is None.  null_lnZ is unchanged.
+        layered: layered radiative transfer (nfa_specset_set_layered) -- the components are layers along the
         line of sight, component 0 the farthest, and each absorbs those behind it; False: the components are summed.
         `predict` of a layered runner goes through the runner's own spectra set (`_predict_layered`).
         baseline_order: None, or 0..3 for a polynomial baseline of that degree per spectrum, profiled out of the
@@ -311,6 +364,7 @@ class EngineRunner(Runner):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered, self.MODEL)
+        calibration = check_calibration(calibration, len(spectra))
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -340,6 +394,24 @@ class EngineRunner(Runner):
         if baseline_order is not None:
             self._ss.set_baseline(baseline_order)
             self.null_lnZ = float(self._ss.null_lnZ().sum())
+        if calibration is not None:
+            self._ss.set_calibration(calibration)
+
+    @property
+    def calibration(self):
+        """None, or the float64 array of the spectra's fractional calibration uncertainties."""
+        cal = self._ss.calibration
+        return None if cal is None else cal.copy()
+
+    def set_calibration(self, cal):
+        """Sets (a number, or one per spectrum) or removes (None, zeros) the calibration uncertainty of this runner's spectra."""
+        self._ss.set_calibration(cal)
+
+    def set_baseline(self, order):
+        """Sets (0..3) or removes (None) the baseline of this runner's spectra; null_lnZ follows."""
+        self._ss.set_baseline(order)
+        self.baseline_order = self._ss.baseline_order
+        self.null_lnZ = float(self._ss.null_lnZ().sum())
 
     def _predict_layered(self, params):
         """`predict` of a layered runner: the spectra's own one-spectrum sets are summed ones, so the model comes from the
@@ -369,6 +441,21 @@ class EngineRunner(Runner):
             resid = np.where(w > 0, s.data - s.get_spec(), 0.0)
             out.append(baseline_fit(resid, w, self.baseline_order))
         return np.concatenate(out)
+
+    def fit_gain(self, params):
+        """Posterior mean and standard deviation of every spectrum's gain at physical `params` (after `predict`, which
+        this calls): two arrays of n_spec values, 1 and 0 for a spectrum whose uncertainty is 0.  numpy on the host
+        (`gain_fit`, with `fit_baseline`'s projection where there is a baseline).  ValueError without a calibration."""
+        cal = self.calibration
+        if cal is None:
+            raise ValueError('this runner has no calibration uncertainty (calibration=None)')
+        self.predict(params)
+        mean, std = np.ones(self.n_spec), np.zeros(self.n_spec)
+        for k, s in enumerate(self._model_spectra()):
+            w = channel_weights(s.noise, s.size)
+            sigma = 1.0 if np.ndim(s.noise) else float(s.noise)            # (channel_weights: 1 / sigma_c^2, or ones)
+            mean[k], std[k] = gain_fit(s.data, s.get_spec(), w, sigma, cal[k], self.baseline_order)
+        return mean, std
 
     def set_exp_mode(self, mode):
         """Numerical mode of this runner alone (None: the process default again): runners of different

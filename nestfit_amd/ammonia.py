@@ -5,7 +5,7 @@ behaviour; all arithmetic runs in the HIP engine through the C ABI.
 import numpy as np
 
 from ._model import (MODEL_AMMONIA, EngineRunner, EngineSpectrumMixin, _pix_ptr, _RunnerHandle,  # noqa: F401
-                     _SpecSet, check_baseline_order, check_layered, par_names)
+                     _SpecSet, check_baseline_order, check_calibration, check_layered, par_names)
 from .core import HyperfineSpectrum
 
 N_LEVELS = 9
@@ -55,19 +55,21 @@ class AmmoniaRunner(EngineRunner):
     MODEL = MODEL_AMMONIA
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None, layered=False):
+    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None, layered=False, calibration=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
         self.cold = bool(cold)
         self.lte = bool(lte)
-        self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, baseline_order=baseline_order, layered=layered)
+        self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, baseline_order=baseline_order, layered=layered,
+                    calibration=calibration)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         check_layered(kwargs.get('layered', False))
+        check_calibration(kwargs.get('calibration'), len(spec_data))
         spectra = np.array([AmmoniaSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

@@ -21,6 +21,8 @@
 //     the line windows selects the lines that touch a row;
 //   * chi^2 is reduced with DPP lane permutes; the per-spectrum terms of an item are
 //     added in spectrum order by lnl_sum_kernel (bitwise reproducible).
+// What a spectra set adds to that -- a noise per channel, a polynomial baseline profiled out, a calibration uncertainty
+// integrated out, a filling factor, layered transfer -- are flags of lnl_body and kernel families of their own (below).
 // No MFMA: the path is elementwise fp64/fp32 plus reductions.
 //
 // Numerical modes (template MODE): 0 "table" evaluates FastExp like the reference
@@ -133,6 +135,10 @@ struct SpecDev {
     const double  *band_tau;             // ... and tau_main of [item][component][spectrum][transition] of the launch's lane
                                          // (lte_band_kernel or lte_mix_kernel; set per launch by launch_lnl, null otherwise)
     const MixRec  *mix;                  // LTE mixes: the species of the transitions and their tables (null for every other set)
+    // Spectra sets with a calibration uncertainty per spectrum (nfa_specset_set_calibration; null without one): [n_spec],
+    // s^2 of the spectrum's gain g ~ N(1, s^2), shared by all pixels.  Such a set always has chan_w, wdata and bl (a
+    // zeroed record, bl_order -1, without a baseline) and runs lnl_kernel_cal.
+    const double  *cal2;
 };
 
 // Baseline record of a (pixel, spectrum), DESIGN 4.5: [0, 4) m_k(d) = sum_j w_j P_k(u_j) d_j, the Legendre moments of the
@@ -162,6 +168,27 @@ __device__ __forceinline__ double bl_quad(const double *R, const double *mp) {
 #pragma unroll
         for (int k = 0; k <= i; ++k) y = __builtin_fma(R[o++], e[k], y);
         q = __builtin_fma(y, y, q);
+    }
+    return q;
+}
+
+// bl_quad's value and, for a calibrated set, the two other products of u = L^-1 m(p) and v = L^-1 m(d):
+// returns ||v - u||^2 by bl_quad's operations in its row order; uu = ||u||^2, ue = u . (v - u)
+__device__ __forceinline__ double bl_quad_cal(const double *R, const double *mp, double &uu, double &ue) {
+    double e[NFA_BL_NB];
+#pragma unroll
+    for (int k = 0; k < NFA_BL_NB; ++k) e[k] = R[k] - mp[k];
+    double q = 0.0;
+    uu = 0.0; ue = 0.0;
+    int o = NFA_BL_NB;
+#pragma unroll
+    for (int i = 0; i < NFA_BL_NB; ++i) {
+        double y = 0.0, u = 0.0;
+#pragma unroll
+        for (int k = 0; k <= i; ++k) { u = __builtin_fma(R[o], mp[k], u); y = __builtin_fma(R[o++], e[k], y); }
+        q = __builtin_fma(y, y, q);
+        uu = __builtin_fma(u, u, uu);
+        ue = __builtin_fma(u, y, ue);
     }
     return q;
 }
@@ -827,8 +854,11 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // 0 the farthest, and each absorbs what lies behind it: pred <- pred + (g - pred) a at the sites that add g a, in the index
 // order this loop already walks.  A component without a window in the row, or a lane with tau == 0 (a == 0), leaves pred as
 // it is.  The Gaussian class has no optical depth: nfa_specset_set_layered refuses that model.
+// CALIB (the baseline form in the general component form only): the spectrum's gain g ~ N(1, s^2), s^2 = SpecDev.cal2, is
+// integrated out in closed form.  The row step forms one more sum, cal_acc = sum w p^2, by chi^2's rule; chi^2
+// and the moments keep their operations, so the epilogue's chi^2_1 has the baseline form's bits and s = 0 returns them.
 template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false,
-          bool LAYER = false>
+          bool LAYER = false, bool CALIB = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -884,8 +914,9 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     LineRec *w_line = (LineRec *)(smem + n_shared + (size_t)ulocal * G.wave_doubles);
     int2 *w_win = (int2 *)(w_line + (NCOMP > 0 ? NCOMP : S.ncomp) * G.nhf_max);   // the windows [lo, hi) follow the table
     // split > 1: the parts' per-lane sums meet here, [unit of the workgroup][part][lane]
-    // (BASELINE: the parts' moment sums follow, [unit][1 + k][part][lane])
-    double *w_part = smem + n_shared + (size_t)upw * G.wave_doubles + (size_t)ulocal * (LNL_PARTS * 64 * (BASELINE ? 1 + NFA_BL_NB : 1));
+    // (BASELINE: the parts' moment sums follow, [unit][1 + k][part][lane]; CALIB: and those of sum w p^2, slot 1 + NFA_BL_NB)
+    constexpr int PART_SLOTS = 1 + (BASELINE ? NFA_BL_NB : 0) + (CALIB ? 1 : 0);      // lnl_part_slots of the plan
+    double *w_part = smem + n_shared + (size_t)upw * G.wave_doubles + (size_t)ulocal * (LNL_PARTS * 64 * PART_SLOTS);
     if (unit >= units) {
         if (split > 1) { __syncthreads(); __syncthreads(); }         // the two barriers of the waves at work
         return;
@@ -1024,14 +1055,17 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     static_assert(!BASELINE || (WEIGHTED && !DYN), "the baseline form is a weighted batch form");
     static_assert(!FILL || (NCOMP == 0 && !DYN), "a filling factor: the general component form of the batch kernels");
     static_assert(!LAYER || (NCOMP == 0 && !DYN), "layered transfer: the general component form of the batch kernels");
+    static_assert(!CALIB || (BASELINE && NCOMP == 0 && !DYN), "a calibration uncertainty: the baseline form in the general component form");
     constexpr int NBL = BASELINE ? NFA_BL_NB : 1;
     double bl_acc[NBL], bl_tot[NBL];
 #pragma unroll
     for (int k = 0; k < NBL; ++k) bl_tot[k] = 0.0;
     const double bl_ui = BASELINE && N > 1 ? 1.0 / (double)(N - 1) : 0.0;
+    double cal_acc = 0.0, cal_tot = 0.0;                           // CALIB: sum w p^2, per part and over the parts in part order
     for (int hp = 0; hp < parts_per_wave; ++hp) {
     const int h = rpart * parts_per_wave + hp;                 // part h = rows h, h + LNL_PARTS, h + 2 LNL_PARTS, ...
     acc = 0.0;
+    cal_acc = 0.0;
 #pragma unroll
     for (int k = 0; k < NBL; ++k) bl_acc[k] = 0.0;
     for (int row = h; row < n_rows; row += LNL_PARTS) {
@@ -1318,6 +1352,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                 bl_acc[1 % NBL] = __builtin_fma(wp, p1, bl_acc[1 % NBL]);
                 bl_acc[2 % NBL] = __builtin_fma(wp, p2, bl_acc[2 % NBL]);
                 bl_acc[3 % NBL] = __builtin_fma(wp, p3, bl_acc[3 % NBL]);
+                if constexpr (CALIB) cal_acc = __builtin_fma(wp, pred, cal_acc);
             }
         }
     }
@@ -1325,10 +1360,12 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
         tot += acc;
 #pragma unroll
         for (int k = 0; k < NBL && BASELINE; ++k) bl_tot[k] += bl_acc[k];
+        if constexpr (CALIB) cal_tot += cal_acc;
     } else {
         w_part[h * 64 + lane] = acc;
 #pragma unroll
         for (int k = 0; k < NBL && BASELINE; ++k) w_part[((1 + k) * LNL_PARTS + h) * 64 + lane] = bl_acc[k];
+        if constexpr (CALIB) w_part[((1 + NFA_BL_NB) * LNL_PARTS + h) * 64 + lane] = cal_acc;
     }
     }
     if (SPEC_DEFER && pend_j >= 0) __builtin_nontemporal_store(pend_v, so + pend_j);
@@ -1339,13 +1376,33 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
 #pragma unroll
         for (int k = 0; k < NBL && BASELINE; ++k)
             for (int h = 0; h < LNL_PARTS; ++h) bl_tot[k] += w_part[((1 + k) * LNL_PARTS + h) * 64 + lane];
+        if constexpr (CALIB)
+            for (int h = 0; h < LNL_PARTS; ++h) cal_tot += w_part[((1 + NFA_BL_NB) * LNL_PARTS + h) * 64 + lane];
     }
     tot = wave_sum(tot);
     double bl_q = 0.0;                                             // BASELINE: what the best baseline takes away
     if (BASELINE) {
 #pragma unroll
         for (int k = 0; k < NBL; ++k) bl_tot[k] = wave_sum(bl_tot[k]);
-        bl_q = bl_quad(S.bl + (p_ix * nspec + s) * NFA_BL_REC, bl_tot);
+        if constexpr (!CALIB) bl_q = bl_quad(S.bl + (p_ix * nspec + s) * NFA_BL_REC, bl_tot);
+    }
+    if constexpr (CALIB) {
+        // The gain integrated out, A = <p,p>_P, B = <d,p>_P with the baseline projected out of both:
+        //   part = chi^2_1 - s^2 (B - A)^2 / (sigma^2 + s^2 A) + sigma^2 log1p(s^2 A / sigma^2),
+        // so that -part / (2 sigma^2), which lnl_sum_kernel forms, is the marginal likelihood.  fp64 in every mode, once per unit.
+        cal_tot = wave_sum(cal_tot);
+        if (lane == 0 && part) {
+            double uu, ue;
+            bl_q = bl_quad_cal(S.bl + (p_ix * nspec + s) * NFA_BL_REC, bl_tot, uu, ue);
+            const double chi2 = (S.totsq[p_ix * nspec + s] + tot) - bl_q;          // the baseline form's value, g = 1
+            const double s2 = S.cal2[s], sig = S.noise[p_ix * nspec + s], sig2 = sig * sig;
+            const double A = fmax(cal_tot - uu, 0.0);
+            const double BA = -0.5 * (tot + cal_tot) - ue;
+            const double den = __builtin_fma(s2, A, sig2);
+            // s == 0: the spectrum's scale is exact, and the value is chi^2_1 to the bit whatever B - A is
+            part[unit] = s2 == 0.0 ? chi2 : chi2 - s2 * (BA * BA) / den + sig2 * log1p(s2 * A / sig2);
+        }
+        return;
     }
     // sum of squared deviations of the unit; lnl_sum_kernel scales and adds
     if (lane == 0 && part) {
@@ -1474,6 +1531,21 @@ lnl_kernel_bl_layer(SpecDev S, BatchGroup grp, const double *__restrict__ D, dou
     lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
+// The kernels of a CALIBRATED set (a calibration uncertainty per spectrum, nfa_specset_set_calibration):
+// lnl_kernel_bl in the general component form with lnl_body's CALIB flag, over FILL and LAYER as well -- 32 instances over
+// (MODE, WRITE_SPEC, WIDE, FILL, LAYER), one family for every set kind: a set without a baseline has a zeroed record, one
+// with a scalar noise w == 1.  No unrolled component loop, no queue, no w8, no fused form.
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_cal(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+               double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, LAYER, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+}
+
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one
 // 51 KB copy of the product tables, and in lnl_kernel the wave slots of the waves that are done stay empty until the
 // longest of the sixteen is: units differ by the widths of their lines, and at the metric's shape 4.5 of 8 waves per
@@ -1492,7 +1564,7 @@ lnl_kernel_bl_layer(SpecDev S, BatchGroup grp, const double *__restrict__ D, dou
 #define NFA_QUEUE_WORDS  (2 * NFA_QUEUE_STRIDE)
 struct QueueArgs { SpecDev S; BatchGroup grp; const double *D; double *part; double *spec_out; long B; LnlGeom G; const double *g_tabs; };
 // (the argument segment places every argument at the next multiple of its alignment: 8 for all of these, so the struct's
-// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 896, 1008, 1016, 1024, 1032, 1040, 1080)
+// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 904, 1016, 1024, 1032, 1040, 1048, 1088)
 static_assert(sizeof(SpecDev) % 8 == 0 && sizeof(BatchGroup) % 8 == 0 && sizeof(LnlGeom) % 8 == 0 && alignof(SpecDev) == 8 &&
               alignof(BatchGroup) == 8 && alignof(LnlGeom) == 8, "QueueArgs must mirror the kernel argument segment");
 template <bool WRITE_SPEC, int NCOMP>

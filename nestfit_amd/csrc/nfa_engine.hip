@@ -214,7 +214,9 @@ struct nfa_specset {
     int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
     bool    filled = false;                         // an LTE set with a beam filling factor per component: the last parameter
     bool    layered = false;                        // layered transfer: a component absorbs those behind it (nfa_specset_set_layered)
-    bool    bl_w1 = false;                          // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
+    bool    bl_w1 = false;                          // a baseline or a calibration on a scalar noise: d_w (== 1) and d_wdata were made for it
+    double *d_cal2 = nullptr;                       // a calibration uncertainty: SpecDev.cal2 (nfa_specset_set_calibration)
+    double  h_cal[MAXSPEC] = {};                    // ... the caller's fractional 1-sigma values
 };
 
 struct nfa_priors {
@@ -283,8 +285,8 @@ static int runner_mode(const nfa_runner *r) { return r->exp_mode >= 0 ? r->exp_m
 // the inputs of the launch plans: the options as they stand now, and a launch of B items of the runner's set as it is now
 static LpKnobs plan_knobs() { return {g_eng.n_cu, g_eng.setup_ti, g_eng.setup_threads, g_eng.setup_sub, g_eng.lnl_queue, g_eng.lnl_queue_wg, g_eng.coalesce, g_eng.ablate}; }
 static LpLaunch plan_launch(const nfa_runner *r, int64_t B, int mode, bool write_spec, bool has_prior, int slot) {
-    return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl != nullptr,
-                    r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr, r->ss->filled, r->ss->layered};
+    return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl_order >= 0,
+                    r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr, r->ss->filled, r->ss->layered, r->ss->dev.cal2 != nullptr};
 }
 
 extern "C" {
@@ -527,6 +529,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     d.xarr = ss->d_xarr; d.t0 = ss->d_t0; d.tbg = ss->d_tbg; d.data = ss->d_data; d.noise = ss->d_noise;
     d.t0tbg = ss->d_t0tbg; d.rowsq = ss->d_rowsq; d.totsq = ss->d_totsq;
     d.bl = nullptr; d.bl_order = -1;                                    // no baseline (nfa_specset_set_baseline)
+    d.cal2 = nullptr;                                                   // no calibration uncertainty (nfa_specset_set_calibration)
     HIP_TRY(hipMalloc(&ss->d_lines, sizeof(LineRow) * n_spec));
     HIP_TRY(hipMemcpy(ss->d_lines, h_lines.data(), sizeof(LineRow) * n_spec, hipMemcpyHostToDevice));
     d.lines = ss->d_lines;
@@ -939,6 +942,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_xarr); (void)hipFree(ss->d_t0); (void)hipFree(ss->d_tbg); (void)hipFree(ss->d_data); (void)hipFree(ss->d_noise);
     (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq);
     (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl); (void)hipFree(ss->d_lines);
+    (void)hipFree(ss->d_cal2);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
@@ -954,43 +958,109 @@ int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data) {
     return ss->dev.bl ? launch_bl_setup(ss, pix, 1, false) : NFA_OK;                             // the basis stays
 }
 
-int nfa_specset_set_baseline(nfa_specset *ss, int order) {
-    if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
-    int rc = engine_init(); if (rc) return rc;
-    // held batches were accepted for the old likelihood, launches in flight read the buffers changed here, and a runner's
-    // captured single-point graph holds the old SpecDev
-    rc = flush_all_runners(); if (rc) return rc;
+// What nfa_specset_set_baseline and nfa_specset_set_calibration do before they change a set: held batches were accepted for
+// the old likelihood, launches in flight read the buffers changed there, and a runner's captured single-point graph holds
+// the old SpecDev
+static int specset_quiesce(nfa_specset *ss) {
+    int rc = flush_all_runners(); if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    {
-        std::lock_guard<std::mutex> lk(g_runners_m);
-        for (nfa_runner *r : g_runners)
-            if (r->ss == ss) { RUNNER_LOCK(r); if (r->g1) { (void)hipGraphExecDestroy(r->g1); r->g1 = nullptr; } }
-    }
+    std::lock_guard<std::mutex> lk(g_runners_m);
+    for (nfa_runner *r : g_runners)
+        if (r->ss == ss) { RUNNER_LOCK(r); if (r->g1) { (void)hipGraphExecDestroy(r->g1); r->g1 = nullptr; } }
+    return NFA_OK;
+}
+
+// The weighted arrays and the baseline records as the set's baseline order and calibration ask for them, whichever of the
+// two setters changed last: both run the baseline form (a scalar noise with w == 1; a calibrated set without
+// a baseline with a zeroed record: bl_setup_kernel leaves L^-1 = 0 for order -1 and m(d) as it is), neither needs them.
+static int specset_form_records(nfa_specset *ss) {
     SpecDev &d = ss->dev;
-    if (order < 0) {
+    if (d.bl_order < 0 && !d.cal2) {
         if (ss->bl_w1) {                  // back to the scalar set, whose totsq the w == 1 form left as they were
             (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata);
             ss->d_w = ss->d_wdata = nullptr; d.chan_w = d.wdata = nullptr;
             ss->bl_w1 = false;
         }
         (void)hipFree(ss->d_bl);
-        ss->d_bl = nullptr; d.bl = nullptr; d.bl_order = -1;
+        ss->d_bl = nullptr; d.bl = nullptr;
         return NFA_OK;
     }
     const size_t n = (size_t)(ss->n_pix * d.chan_tot);
     if (!d.chan_w) {                      // a scalar noise runs as the weighted form with w == 1: its bits
-        HIP_TRY(hipMalloc(&ss->d_w, sizeof(double) * n));
-        HIP_TRY(hipMalloc(&ss->d_wdata, sizeof(double) * n));
+        double *w = nullptr, *wdata = nullptr;                // both, or neither
+        HIP_TRY(hipMalloc(&w, sizeof(double) * n));
+        if (hipMalloc(&wdata, sizeof(double) * n) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(w); return fail(NFA_ERR_DEVICE, "out of device memory for the channel weights"); }
+        ss->d_w = w; ss->d_wdata = wdata;
         ss->bl_w1 = true;
         std::vector<double> one(n, 1.0);
         HIP_TRY(hipMemcpy(ss->d_w, one.data(), sizeof(double) * n, hipMemcpyHostToDevice));
         d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
-        rc = launch_chan_weight(ss, 0, ss->n_pix, false); if (rc) return rc;
+        int rc = launch_chan_weight(ss, 0, ss->n_pix, false); if (rc) return rc;
     }
     if (!ss->d_bl) HIP_TRY(hipMalloc(&ss->d_bl, sizeof(double) * NFA_BL_REC * ss->n_pix * d.n_spec));
-    d.bl = ss->d_bl; d.bl_order = order;
+    d.bl = ss->d_bl;
     return launch_bl_setup(ss, 0, ss->n_pix, true);
+}
+
+int nfa_specset_set_baseline(nfa_specset *ss, int order) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    const int was = ss->dev.bl_order;
+    ss->dev.bl_order = order;
+    rc = specset_form_records(ss);
+    if (rc) {                                                 // the set stays as it was: the old order, its records formed again
+        const std::string why = g_err;
+        ss->dev.bl_order = was;
+        (void)specset_form_records(ss);
+        g_err = why;
+    }
+    return rc;
+}
+
+int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    SpecDev &d = ss->dev;
+    bool any = false;
+    for (int s = 0; cal && s < d.n_spec; ++s) {
+        if (!(cal[s] >= 0.0 && cal[s] <= 1.0))                // (NaN fails both)
+            return fail(NFA_ERR_ARG, "a calibration uncertainty is a finite fraction in [0, 1] per spectrum");
+        any = any || cal[s] > 0.0;
+    }
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    if (!any) {                                               // null, or all zeros: the set's former kernels and bits
+        if (!d.cal2) return NFA_OK;
+        (void)hipFree(ss->d_cal2);
+        ss->d_cal2 = nullptr; d.cal2 = nullptr;
+        for (int s = 0; s < MAXSPEC; ++s) ss->h_cal[s] = 0.0;
+        return d.bl_order >= 0 ? NFA_OK : specset_form_records(ss);      // (a baseline's records stay as they are)
+    }
+    double s2[MAXSPEC];
+    for (int s = 0; s < d.n_spec; ++s) s2[s] = cal[s] * cal[s];
+    if (!ss->d_cal2) HIP_TRY(hipMalloc(&ss->d_cal2, sizeof(double) * d.n_spec));
+    HIP_TRY(hipMemcpy(ss->d_cal2, s2, sizeof(double) * d.n_spec, hipMemcpyHostToDevice));
+    for (int s = 0; s < d.n_spec; ++s) ss->h_cal[s] = cal[s];
+    const bool formed = d.cal2 != nullptr || d.bl_order >= 0;           // the records are there already
+    d.cal2 = ss->d_cal2;
+    if (formed) return NFA_OK;
+    rc = specset_form_records(ss);
+    if (rc) {                                                 // the set stays as it was: without a calibration, and without
+        const std::string why = g_err;                        // whatever was made for it
+        (void)hipFree(ss->d_cal2);
+        ss->d_cal2 = nullptr; d.cal2 = nullptr;
+        for (int s = 0; s < MAXSPEC; ++s) ss->h_cal[s] = 0.0;
+        (void)specset_form_records(ss);
+        g_err = why;
+    }
+    return rc;
+}
+
+int nfa_specset_calibration(const nfa_specset *ss, double *out) {
+    if (!ss || !ss->dev.cal2) return 0;
+    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->h_cal[s];
+    return 1;
 }
 
 int nfa_specset_set_layered(nfa_specset *ss, int on) {
@@ -1000,13 +1070,7 @@ int nfa_specset_set_layered(nfa_specset *ss, int on) {
     int rc = engine_init(); if (rc) return rc;
     // as nfa_specset_set_baseline: held batches were accepted for the old likelihood, launches in flight were planned for
     // it, and a runner's captured single-point graph holds the old kernel
-    rc = flush_all_runners(); if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    {
-        std::lock_guard<std::mutex> lk(g_runners_m);
-        for (nfa_runner *r : g_runners)
-            if (r->ss == ss) { RUNNER_LOCK(r); if (r->g1) { (void)hipGraphExecDestroy(r->g1); r->g1 = nullptr; } }
-    }
+    rc = specset_quiesce(ss); if (rc) return rc;
     ss->layered = on != 0;
     return NFA_OK;
 }
@@ -1018,7 +1082,7 @@ int nfa_specset_null_lnz(const nfa_specset *ss, double *out) {
     const int64_t n = ss->n_pix * ss->dev.n_spec;
     double *d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(double) * n));
-    if (ss->dev.bl)                                           // the baseline-only model
+    if (ss->dev.bl_order >= 0)                                // the baseline-only model (a calibrated set's zeroed record is no baseline)
         hipLaunchKernelGGL(null_lnz_bl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
     else
         hipLaunchKernelGGL(ss->dev.chan_w ? null_lnz_w_kernel : null_lnz_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0,
@@ -1388,7 +1452,8 @@ static int launch_band(nfa_runner *r, int slot, int64_t B) {
 // lnl_kernel_queue for the table mode's narrow sets.  NCOMP 1..3: the component loop unrolled; 0: the general form.
 // A filled LTE set (a plan with `filled`): lnl_kernel_fill, _wt_fill, _bl_fill over (mode, spectra out, wide), the
 // general form whatever the component count.  A layered set (a plan with `layered`): lnl_kernel_layer, _wt_layer, _bl_layer
-// over (mode, spectra out, wide, filled), the same.
+// over (mode, spectra out, wide, filled), the same.  A calibrated set (a plan with `calibrated`): lnl_kernel_cal over (mode,
+// spectra out, wide, filled, layered), the baseline form only.
 typedef void (*LnlKernel)(SpecDev, BatchGroup, const double *, double *, double *, long, LnlGeom, const double *);
 template <int I>     // I: bit 4 fast mode, bit 3 spectra out, bit 2 wide, bits 0-1 NCOMP
 static LnlKernel lnl_kernel_inst(LnlForm form) {
@@ -1431,7 +1496,21 @@ static LnlKernel lnl_kernel_layer_at(int i, LnlForm form, std::index_sequence<I.
     static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_layer_inst<(int)I>...};
     return inst[i](form);
 }
-static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, LnlForm form, bool filled, bool layered) {
+template <int I>     // I: bit 4 layered, bit 3 filled, bit 2 fast mode, bit 1 spectra out, bit 0 wide
+static LnlKernel lnl_kernel_cal_inst(LnlForm form) {
+    constexpr int MODE = (I & 4) ? 2 : 0;
+    constexpr bool LAYER = (I & 16) != 0, FILL = (I & 8) != 0, WS = (I & 2) != 0, WIDE = (I & 1) != 0;
+    return form == LNL_BASELINE ? lnl_kernel_cal<MODE, WS, WIDE, FILL, LAYER> : nullptr;
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_cal_at(int i, LnlForm form, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_cal_inst<(int)I>...};
+    return inst[i](form);
+}
+static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, LnlForm form, bool filled, bool layered, bool calibrated) {
+    if (calibrated)
+        return lnl_kernel_cal_at((layered ? 16 : 0) | (filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0), form,
+                                 std::make_index_sequence<32>());
     if (layered)
         return lnl_kernel_layer_at((filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0), form,
                                    std::make_index_sequence<16>());
@@ -1451,7 +1530,7 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form, P.filled, P.layered);
+    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form, P.filled, P.layered, P.calibrated);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
     int rc = ensure_dynamic_lds((const void *)kern, P.lds); if (rc) return rc;
     hipStream_t st = r->lanes[slot];
@@ -1659,7 +1738,8 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     if (!g_eng.point || r->profiling || B > NFA_POINT_MAXB) return 0;
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
-    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl != nullptr, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered);
+    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
+                                     S.cal2 != nullptr);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

@@ -70,8 +70,10 @@ struct LpShape {
 // One launch: B items in `mode` (0 table, 2 fast), of a group of `group_n` batches of `group_each` rows; what the
 // spectra set is right now (nfa_specset_set_baseline changes it) and whether the lane has its queue counters; filled: an
 // LTE set with a beam filling factor per component (nfa_specset_create_lte_filled; in the struct's tail padding); layered:
-// a set whose components absorb those behind them (nfa_specset_set_layered; the next byte of that padding, zero = summed)
-struct LpLaunch { int64_t B; int mode, group_n; int64_t group_each; bool write_spec, has_prior, baseline, weighted, has_queue, filled, layered; };
+// a set whose components absorb those behind them (nfa_specset_set_layered; the next byte of that padding, zero = summed);
+// calibrated: a set with a calibration uncertainty per spectrum (nfa_specset_set_calibration; the last byte of that
+// padding, zero = none)
+struct LpLaunch { int64_t B; int mode, group_n; int64_t group_each; bool write_spec, has_prior, baseline, weighted, has_queue, filled, layered, calibrated; };
 // The process options the decisions read, as they stand at the call (nfa_set_option)
 struct LpKnobs { int n_cu, setup_ti, setup_threads, setup_sub, lnl_queue, lnl_queue_wg, coalesce, ablate; };
 
@@ -154,13 +156,34 @@ inline LnlGeom lnl_geom(const LpShape &s, const LpKnobs &k, int64_t B) {
     return G;
 }
 
+// per-lane sums a part of a unit leaves in LDS when several waves share the unit: chi^2's, a baseline's NFA_BL_NB moments,
+// a calibrated set's sum w p^2
+inline int lnl_part_slots(bool baseline, bool calibrated) { return 1 + (baseline ? NFA_BL_NB : 0) + (calibrated ? 1 : 0); }
+// Waves per workgroup of a launch with `split` waves per unit: option wpb, made a multiple of the split.  Table mode stages
+// 51 KB of product tables per workgroup, so the workgroup is made as fat as keeps the most waves resident per CU
+// (table_waves); its split launches take eight.
+inline int lnl_waves(const LpShape &s, bool table, int split) {
+    int waves = std::max(1, std::min(s.wpb, 16));
+    waves = std::max(waves, split);
+    waves -= waves % split;
+    if (table) waves = split > 1 ? std::max(8, split) : table_waves(s);
+    return waves;
+}
+// LDS in bytes of the units of a workgroup: per unit the line table and, split > 1, `slots` sums per part and lane
+inline size_t lnl_units_lds(const LpShape &s, bool table, int split, int waves, int slots) {
+    const size_t part_doubles = split > 1 ? (size_t)LNL_PARTS * 64 * slots : 0;
+    return sizeof(double) * ((size_t)(table ? SM_TABLE_DOUBLES : 0) + ((size_t)lnl_wave_doubles(s) + part_doubles) * (waves / split));
+}
+
 enum LnlForm { LNL_PLAIN, LNL_W8, LNL_QUEUE, LNL_WEIGHTED, LNL_BASELINE };     // lnl_kernel, _w8, _queue, _wt, _bl
 // waves per workgroup, its dynamic LDS in bytes, workgroups; error: null, or why there is no plan
 // filled (in the padding behind `wide`): the form's instance of the filled family, lnl_kernel_fill / _wt_fill / _bl_fill --
 // the general component form with the filling factor in the Tb pass.  The form keeps its five values; only LNL_PLAIN,
 // LNL_WEIGHTED and LNL_BASELINE come with `filled`.  layered (the next padding byte; zero = summed): the form's instance of
 // the layered family, lnl_kernel_layer / _wt_layer / _bl_layer, over `filled` as well; the same three forms only.
-struct LnlPlan { LnlForm form; bool wide, filled, layered; LnlGeom G; int waves; size_t lds; int64_t blocks; const char *error; };
+// calibrated (the last padding byte; zero = none): lnl_kernel_cal, the baseline form's general component instance with the
+// gain marginalised in the epilogue, over `filled` and `layered`; LNL_BASELINE only, whatever the set is otherwise.
+struct LnlPlan { LnlForm form; bool wide, filled, layered, calibrated; LnlGeom G; int waves; size_t lds; int64_t blocks; const char *error; };
 // Plans the likelihood launch of L.B items (the table of forms in DESIGN 4.2 is tested against this chain).
 inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     LnlPlan P = {};
@@ -174,13 +197,20 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     P.G.ablate = k.ablate;
     P.filled = L.filled;
     P.layered = L.layered;
+    P.calibrated = L.calibrated;
+    int waves = lnl_waves(s, table, P.G.split);
+    // A calibrated set keeps one more sum per part than a baseline set.  Where that sixth slot is what does not fit, the
+    // workgroup takes one unit (waves = split): less LDS than any baseline workgroup of two units and more; and should a
+    // baseline workgroup of ONE unit have fitted where this one does not, half the split, down to one wave per unit, which
+    // keeps no sums in LDS at all.  So whatever plans with a baseline plans calibrated.  The bits depend on neither.
+    // (G.split is lowered after lnl_geom filled G: of LnlGeom only `split` itself depends on the split -- nhf_max,
+    // wave_doubles, inv_nspec and inv_nhf are the runner's -- and waves, LDS and workgroups are computed below from the
+    // lowered value.  The GPU suite launches the waves = split case; the halving is held to its arithmetic without a GPU only.)
+    if (L.calibrated && lnl_units_lds(s, table, P.G.split, waves, lnl_part_slots(true, true)) > LDS_PER_CU) {
+        waves = P.G.split;
+        while (P.G.split > 1 && lnl_units_lds(s, table, P.G.split, waves, lnl_part_slots(true, true)) > LDS_PER_CU) waves = P.G.split /= 2;
+    }
     const int split = P.G.split;
-    // Waves per workgroup: option wpb, made a multiple of the split.  Table mode stages 51 KB of product tables per
-    // workgroup, so the workgroup is made as fat as keeps the most waves resident per CU (table_waves); its split launches take eight.
-    int waves = std::max(1, std::min(s.wpb, 16));
-    waves = std::max(waves, split);
-    waves -= waves % split;
-    if (table) waves = split > 1 ? std::max(8, split) : table_waves(s);
     P.waves = waves;
     const int upw = waves / split;                               // units per workgroup
     // What the queue form asks of the launch's size: units of eight rows and more (short units -- config 1's 256 channels
@@ -192,7 +222,8 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     const bool fills_twice = units >= 2 * ((int64_t)k.n_cu * wg_per_cu) * waves;
     // The form: the first line that applies.
     P.form = LNL_PLAIN;
-    if (L.baseline) P.form = LNL_BASELINE;           // every mode, wide, spectra out; such a set is weighted too
+    if (L.calibrated) P.form = LNL_BASELINE;         // a calibration uncertainty: the baseline form (a zeroed record without one)
+    else if (L.baseline) P.form = LNL_BASELINE;      // every mode, wide, spectra out; such a set is weighted too
     else if (L.weighted) P.form = LNL_WEIGHTED;      // every mode, wide, spectra out: no queue or w8 form of its own (the
                                                      // units give the same bits whatever the form, so none is instantiated)
     else if (L.filled || L.layered) P.form = LNL_PLAIN;   // a filling factor, layered transfer: baseline, weighted or plain,
@@ -205,10 +236,9 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     else if (table && L.write_spec) P.form = LNL_W8; // table mode with spectra out asks for 66 registers left alone
     const bool queue = P.form == LNL_QUEUE;
     // LDS: [table mode: the product tables][per unit of the workgroup: the line table; split > 1: the parts' sums
-    // (a baseline: and those of the moments of the unit)][queue: the workgroup's queue word and count]
+    // (a baseline: and those of the moments of the unit; calibrated: and that of sum w p^2)][queue: the workgroup's queue word and count]
     const int n_shared = table ? SM_TABLE_DOUBLES : 0;
-    const size_t part_doubles = split > 1 ? (size_t)LNL_PARTS * 64 * (P.form == LNL_BASELINE ? 1 + NFA_BL_NB : 1) : 0;
-    P.lds = sizeof(double) * ((size_t)n_shared + ((size_t)P.G.wave_doubles + part_doubles) * upw) + (queue ? 16 : 0);
+    P.lds = lnl_units_lds(s, table, split, waves, lnl_part_slots(P.form == LNL_BASELINE, L.calibrated)) + (queue ? 16 : 0);
     if (table) P.lds = std::max(P.lds, sizeof(double) * (size_t)(n_shared + SM_TABLE_TAIL));
     if (P.lds > LDS_PER_CU) { P.error = "ncomp too large for the LDS line table"; return P; }
     if (!table && s.lnl_cap > 0 && waves * s.lnl_cap < LP_WAVES_PER_CU)      // residency cap: see Engine::lnl_cap
@@ -276,11 +306,13 @@ struct FusedPlan { const char *refusal, *ring_error; LnlGeom G; int n_blocks, ct
 // filled: one with a beam filling factor per component (lte_fill_kernel runs there, and only the batch kernels have the form);
 // layered: a set whose components absorb those behind them (nfa_specset_set_layered: the batch kernels only, and the first
 // refusal of all -- whatever else the set is, its points must not reach a kernel that sums)
+// calibrated: a set with a calibration uncertainty per spectrum (nfa_specset_set_calibration: the batch kernels only)
 inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted, bool banded = false,
-                            bool filled = false, bool layered = false) {
+                            bool filled = false, bool layered = false, bool calibrated = false) {
     FusedPlan P = {};
     P.G = lnl_geom(s, k, 1);
-    if (layered) P.refusal = "the resident kernel has no form for layered transfer: use nfa_ring_serve";
+    if (calibrated) P.refusal = "the resident kernel has no form for a calibration uncertainty: use nfa_ring_serve";
+    else if (layered) P.refusal = "the resident kernel has no form for layered transfer: use nfa_ring_serve";
     else if (s.ndim > NFA_POINT_MAXDIM || lnl_wide(s)) P.refusal = "this runner's points go through the batch kernels: use nfa_ring_serve";
     else if (filled) P.refusal = "the resident kernel has no form for a filling factor: use nfa_ring_serve";
     // (weighted sets, baseline sets among them: lnl_kernel_wt / lnl_kernel_bl.  The unweighted body would compute the unweighted sum.)

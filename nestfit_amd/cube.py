@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_layered
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_layered, gain_fit
 from .core import _as_inplace_matrix
 
 
@@ -46,10 +46,14 @@ class CubeRunner:
         likelihood in closed form; null_lnZ is then the baseline-only model's
     layered : layered radiative transfer: component 0 is the farthest from the observer and every component
         absorbs those behind it; False (default): the components are summed.  Not for the Gaussian model (ValueError).
+    calibration : None, or the fractional 1-sigma uncertainty of the spectra's intensity scales (a number, or one per
+        spectrum, each in [0, 1]; shared by all pixels), integrated out of the likelihood per (pixel, spectrum) in closed
+        form; null_lnZ is unchanged
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
-                 model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False):
+                 model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False,
+                 calibration=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
@@ -59,6 +63,7 @@ class CubeRunner:
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered, model)                      # before any device call
+        calibration = check_calibration(calibration, len(xarrs))
         if species is None and int(model) == 4 and lines is not None:
             from .lte import LteBand, LteBlend, LteLines, lines_species
             lines = list(lines)
@@ -75,7 +80,9 @@ class CubeRunner:
         self.baseline_order = baseline_order
         if baseline_order is not None:
             self._ss.set_baseline(baseline_order)
-        self._data, self._noise = data, noise                # (fit_baseline)
+        if calibration is not None:
+            self._ss.set_calibration(calibration)
+        self._data, self._noise = data, noise                # (fit_baseline, fit_gain)
         self.utrans = utrans
         self.ncomp = int(ncomp)
         self.n_model = self._ss.n_model                      # (an LTE mix: from the species of its lines, not from N_MODEL)
@@ -147,6 +154,33 @@ class CubeRunner:
             resid = np.where(w > 0, data[:, sl] - spec[:, sl], 0.0)
             out[:, sl] = baseline_fit(resid, w, self.baseline_order)
         return out
+
+    @property
+    def calibration(self):
+        """None, or the float64 array of the spectra's fractional calibration uncertainties."""
+        cal = self._ss.calibration
+        return None if cal is None else cal.copy()
+
+    def fit_gain(self, pix, theta):
+        """Posterior mean and standard deviation [B, n_spec] each of the spectra's gains at physical parameter rows
+        theta[B, ndim] against pixels pix[B] (1 and 0 where a spectrum's uncertainty is 0): numpy on `predict_batch`'s
+        spectra, with `fit_baseline`'s projection where there is a baseline.  ValueError without a calibration."""
+        cal = self.calibration
+        if cal is None:
+            raise ValueError('this runner has no calibration uncertainty (calibration=None)')
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        spec, _ = self.predict_batch(pix, theta)
+        data = np.asarray(self._data, dtype=np.float64)[pix]
+        noise = np.asarray(self._noise, dtype=np.float64)[pix]
+        off = self._ss.offsets
+        mean, std = np.ones((len(pix), self.n_spec)), np.zeros((len(pix), self.n_spec))
+        for k in range(self.n_spec):
+            sl = slice(off[k], off[k + 1])
+            for b in range(len(pix)):
+                w = 1.0 / noise[b, sl] ** 2 if self._ss.per_channel else np.ones(off[k + 1] - off[k])
+                sigma = 1.0 if self._ss.per_channel else noise[b, k]
+                mean[b, k], std[b, k] = gain_fit(data[b, sl], spec[b, sl], w, sigma, cal[k], self.baseline_order)
+        return mean, std
 
     def peak_and_integrated(self, pix, theta):
         """max_spec and sum_spec of every spectrum for parameter rows (core.pyx:532-539 as

@@ -5,7 +5,7 @@ nestfit/models/hyperfine.pyx:52-118).  Parameters per component: voff, tex, ltau
 """
 import numpy as np
 
-from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_layered, par_names
+from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_layered, par_names
 from .core import HyperfineSpectrum
 
 N_LEVELS = 3
@@ -46,17 +46,19 @@ class DiazenyliumRunner(EngineRunner):
     MODEL = MODEL_DIAZENYLIUM
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered)
+        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
+                    calibration=calibration)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         check_layered(kwargs.get('layered', False))
+        check_calibration(kwargs.get('calibration'), len(spec_data))
         spectra = np.array([DiazenyliumSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _ffi
 from ._model import (MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, EngineRunner, EngineSpectrumMixin,
-                     check_baseline_order, check_layered, par_names)
+                     check_baseline_order, check_calibration, check_layered, par_names)
 from .core import HyperfineSpectrum as _HyperfineBase
 
 N_PARAMS = 4
@@ -133,18 +133,20 @@ class HyperfineRunner(EngineRunner):
     MODEL = MODEL_HYPERFINE
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered)
+        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
+                    calibration=calibration)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         """spec_data: rows [xarr, data, noise, LineTable]."""
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         check_layered(kwargs.get('layered', False))
+        check_calibration(kwargs.get('calibration'), len(spec_data))
         spectra = np.array([HyperfineSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

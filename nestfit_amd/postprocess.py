@@ -9,6 +9,10 @@ array operations here, and the two steps that touch the hot path -- `deblend_hf_
 Axis codes (store_spec.rst:124-135): b latitude, l longitude, m component, p parameter, M quantile,
 r run (1 .. n components), h PDF bin, t transition, S channel.  Arrays are built directly in the stored
 order (..., b, l).
+
+A store fitted with a calibration uncertainty (`HdfStore.read_model_calibration`) gets the same products: the
+model at gain g = 1, the intensity scale the parameters refer to.  The spectra's gains are no product here (`fit_gain` of a
+runner gives them).
 """
 import numpy as np
 

@@ -430,6 +430,13 @@ class HdfStore:
         # was fitted with summed components.
         if (getattr(fitter, 'runner_kwargs', None) or {}).get('layered', False):
             self.hdf.attrs['layered'] = True
+        # a calibration uncertainty per spectrum integrated out of the likelihood (runner_kwargs['calibration']):
+        # root attribute `calibration`, float64 [n_spec].  A store without it was fitted without one.
+        from ._model import check_calibration
+        cubes = getattr(getattr(fitter, 'stack', None), 'cubes', None)
+        cal = check_calibration((getattr(fitter, 'runner_kwargs', None) or {}).get('calibration'), None if cubes is None else len(cubes))
+        if cal is not None:
+            self.hdf.attrs['calibration'] = cal
         quantum = getattr(fitter, 'nlive_quantum', 1)
         if quantum != 1:                 # a deviation from main.py:445-447 is written down where the results are
             self.hdf.attrs['nlive_quantum'] = int(quantum)
@@ -448,6 +455,13 @@ class HdfStore:
         attribute `layered`; False -- summed components -- for a store without it."""
         assert self.is_open
         return bool(self.hdf.attrs.get('layered', False))
+
+    def read_model_calibration(self):
+        """The fractional calibration uncertainty of every spectrum the store was fitted with (`runner_kwargs={'calibration':
+        ...}`): the root attribute `calibration` as a float64 array [n_spec]; None for a store without it."""
+        assert self.is_open
+        cal = self.hdf.attrs.get('calibration')
+        return None if cal is None else np.asarray(cal, dtype=np.float64)
 
     def read_model_fill(self):
         """Whether the store was fitted with a beam filling factor per component (`LteMix(species, fill=True)`): the root
