@@ -137,7 +137,7 @@ struct SpecDev {
     const MixRec  *mix;                  // LTE mixes: the species of the transitions and their tables (null for every other set)
     // Spectra sets with a calibration uncertainty per spectrum (nfa_specset_set_calibration; null without one): [n_spec],
     // s^2 of the spectrum's gain g ~ N(1, s^2), shared by all pixels.  Such a set always has chan_w, wdata and bl (a
-    // zeroed record, bl_order -1, without a baseline) and runs lnl_kernel_cal.
+    // zeroed record, bl_order -1, without a baseline) and runs the LNL_K_CALIB kind.
     const double  *cal2;
 };
 
@@ -1436,114 +1436,23 @@ lnl_kernel_w8(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *_
     lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
-// lnl_kernel of a weighted spectra set (SpecDev.chan_w).  Weighted sets take this form in every mode: not the queue form
-// nor lnl_kernel_w8 (the table mode with spectra out), whose units give the same bits (tests/test_row_split.py) and which
-// are not instantiated a second time.
-template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP>
+// lnl_kernel of every other kind of spectra set: KIND's bits (LNL_K_*, nfa_launch_plan.h) are lnl_body's WEIGHTED,
+// BASELINE, FILL, LAYER and CALIB flags.  Which (MODE, WRITE_SPEC, WIDE, NCOMP, KIND) exist is lnl_instance_exists' to
+// say: a weighted set (SpecDev.chan_w) and one with a baseline (SpecDev.bl; one instance for all orders: the four moments
+// are always formed, the record's rows above the order are zero) in every mode, WIDE, spectra out and NCOMP -- not the
+// queue form nor lnl_kernel_w8, whose units give the same bits (tests/test_row_split.py) and which are not instantiated
+// a second time; a filled LTE set, a layered set (4.11) and a calibrated set (4.12: over a zeroed record
+// without a baseline, w == 1 with a scalar noise) in the general component form only.
+template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, unsigned KIND>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_wt(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-              double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
-}
-
-// lnl_kernel of a spectra set with a baseline (SpecDev.bl; always weighted): every mode, WIDE and spectra out, one
-// instance for all orders (the four moments are always formed; the record's rows above the order are zero)
-template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_bl(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-              double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP, false, true, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
-}
-
-// The kernels of a FILLED LTE set (a beam filling factor per component): lnl_kernel, lnl_kernel_wt and
-// lnl_kernel_bl in the general component form with lnl_body's FILL flag.  Such sets take no other form -- no unrolled
-// component loop, no queue, no w8 -- so these are 3 x 8 instances over (MODE, WRITE_SPEC, WIDE).
-template <int MODE, bool WRITE_SPEC, bool WIDE>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_fill(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+lnl_kernel_kind(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
                 double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     int n_shared = 0;
     const double *sm = smem;
     if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, false, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
-}
-template <int MODE, bool WRITE_SPEC, bool WIDE>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_wt_fill(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                   double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
-}
-template <int MODE, bool WRITE_SPEC, bool WIDE>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_bl_fill(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                   double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
-}
-
-// The kernels of a LAYERED set (nfa_specset_set_layered): lnl_kernel, lnl_kernel_wt and lnl_kernel_bl in the
-// general component form with lnl_body's LAYER flag, and FILL for a filled LTE set.  Like the filled family they take no
-// other form -- no unrolled component loop, no queue, no w8: 3 x 16 instances over (MODE, WRITE_SPEC, WIDE, FILL).
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_layer(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                 double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, false, false, FILL, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
-}
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_wt_layer(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                    double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, FILL, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
-}
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_bl_layer(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                    double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
-}
-
-// The kernels of a CALIBRATED set (a calibration uncertainty per spectrum, nfa_specset_set_calibration):
-// lnl_kernel_bl in the general component form with lnl_body's CALIB flag, over FILL and LAYER as well -- 32 instances over
-// (MODE, WRITE_SPEC, WIDE, FILL, LAYER), one family for every set kind: a set without a baseline has a zeroed record, one
-// with a scalar noise w == 1.  No unrolled component loop, no queue, no w8, no fused form.
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_cal(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-               double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, LAYER, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+    lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP, false, (KIND & LNL_K_WEIGHTED) != 0, (KIND & LNL_K_BASELINE) != 0, (KIND & LNL_K_FILL) != 0,
+             (KIND & LNL_K_LAYER) != 0, (KIND & LNL_K_CALIB) != 0>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one

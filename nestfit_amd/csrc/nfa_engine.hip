@@ -1447,76 +1447,34 @@ static int launch_band(nfa_runner *r, int slot, int64_t B) {
     return NFA_OK;
 }
 
-// The kernel of a plan.  Naming an instance compiles it, so this names the instances a plan can ask for and no others:
-// lnl_kernel, _wt and _bl for all 32 (mode, spectra out, wide, NCOMP), lnl_kernel_w8 for the table mode with spectra out,
-// lnl_kernel_queue for the table mode's narrow sets.  NCOMP 1..3: the component loop unrolled; 0: the general form.
-// A filled LTE set (a plan with `filled`): lnl_kernel_fill, _wt_fill, _bl_fill over (mode, spectra out, wide), the
-// general form whatever the component count.  A layered set (a plan with `layered`): lnl_kernel_layer, _wt_layer, _bl_layer
-// over (mode, spectra out, wide, filled), the same.  A calibrated set (a plan with `calibrated`): lnl_kernel_cal over (mode,
-// spectra out, wide, filled, layered), the baseline form only.
+// The kernel of a plan.  Naming an instance compiles it, so entry I of the table names its instance only where
+// lnl_instance_exists (nfa_launch_plan.h) says there is one: that predicate is what keeps the instance count where it is.
 typedef void (*LnlKernel)(SpecDev, BatchGroup, const double *, double *, double *, long, LnlGeom, const double *);
-template <int I>     // I: bit 4 fast mode, bit 3 spectra out, bit 2 wide, bits 0-1 NCOMP
+template <int I>     // I: lnl_inst_index
 static LnlKernel lnl_kernel_inst(LnlForm form) {
-    constexpr int MODE = (I & 16) ? 2 : 0, NCOMP = I & 3;
-    constexpr bool WS = (I & 8) != 0, WIDE = (I & 4) != 0;
-    if (form == LNL_BASELINE) return lnl_kernel_bl<MODE, WS, WIDE, NCOMP>;
-    if (form == LNL_WEIGHTED) return lnl_kernel_wt<MODE, WS, WIDE, NCOMP>;
-    if constexpr (MODE == 0 && !WIDE) if (form == LNL_QUEUE) return lnl_kernel_queue<WS, NCOMP>;
-    if constexpr (MODE == 0 && WS) if (form == LNL_W8) return lnl_kernel_w8<MODE, WS, WIDE, NCOMP>;
-    return form == LNL_PLAIN ? lnl_kernel<MODE, WS, WIDE, NCOMP> : nullptr;      // (null: not a form of this instance)
+    constexpr LnlInst N = lnl_inst_at(I);
+    if constexpr (N.kind != 0) {
+        // (a kind has one form, lnl_kind_form: the predicate is asked about that one, and so decides on the bits and NCOMP alone)
+        if constexpr (lnl_instance_exists(lnl_kind_form(N.kind), N.mode, N.write_spec, N.wide, N.ncomp, N.kind))
+            if (form == lnl_kind_form(N.kind)) return lnl_kernel_kind<N.mode, N.write_spec, N.wide, N.ncomp, N.kind>;
+    } else {
+        if constexpr (lnl_instance_exists(LNL_QUEUE, N.mode, N.write_spec, N.wide, N.ncomp, 0))
+            if (form == LNL_QUEUE) return lnl_kernel_queue<N.write_spec, N.ncomp>;
+        if constexpr (lnl_instance_exists(LNL_W8, N.mode, N.write_spec, N.wide, N.ncomp, 0))
+            if (form == LNL_W8) return lnl_kernel_w8<N.mode, N.write_spec, N.wide, N.ncomp>;
+        if constexpr (lnl_instance_exists(LNL_PLAIN, N.mode, N.write_spec, N.wide, N.ncomp, 0))
+            if (form == LNL_PLAIN) return lnl_kernel<N.mode, N.write_spec, N.wide, N.ncomp>;
+    }
+    return nullptr;                                           // (null: no instance of this form here)
 }
 template <size_t... I>
 static LnlKernel lnl_kernel_at(int i, LnlForm form, std::index_sequence<I...>) {
     static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_inst<(int)I>...};
     return inst[i](form);
 }
-template <int I>     // I: bit 2 fast mode, bit 1 spectra out, bit 0 wide
-static LnlKernel lnl_kernel_fill_inst(LnlForm form) {
-    constexpr int MODE = (I & 4) ? 2 : 0;
-    constexpr bool WS = (I & 2) != 0, WIDE = (I & 1) != 0;
-    if (form == LNL_BASELINE) return lnl_kernel_bl_fill<MODE, WS, WIDE>;
-    if (form == LNL_WEIGHTED) return lnl_kernel_wt_fill<MODE, WS, WIDE>;
-    return form == LNL_PLAIN ? lnl_kernel_fill<MODE, WS, WIDE> : nullptr;
-}
-template <size_t... I>
-static LnlKernel lnl_kernel_fill_at(int i, LnlForm form, std::index_sequence<I...>) {
-    static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_fill_inst<(int)I>...};
-    return inst[i](form);
-}
-template <int I>     // I: bit 3 filled, bit 2 fast mode, bit 1 spectra out, bit 0 wide
-static LnlKernel lnl_kernel_layer_inst(LnlForm form) {
-    constexpr int MODE = (I & 4) ? 2 : 0;
-    constexpr bool FILL = (I & 8) != 0, WS = (I & 2) != 0, WIDE = (I & 1) != 0;
-    if (form == LNL_BASELINE) return lnl_kernel_bl_layer<MODE, WS, WIDE, FILL>;
-    if (form == LNL_WEIGHTED) return lnl_kernel_wt_layer<MODE, WS, WIDE, FILL>;
-    return form == LNL_PLAIN ? lnl_kernel_layer<MODE, WS, WIDE, FILL> : nullptr;
-}
-template <size_t... I>
-static LnlKernel lnl_kernel_layer_at(int i, LnlForm form, std::index_sequence<I...>) {
-    static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_layer_inst<(int)I>...};
-    return inst[i](form);
-}
-template <int I>     // I: bit 4 layered, bit 3 filled, bit 2 fast mode, bit 1 spectra out, bit 0 wide
-static LnlKernel lnl_kernel_cal_inst(LnlForm form) {
-    constexpr int MODE = (I & 4) ? 2 : 0;
-    constexpr bool LAYER = (I & 16) != 0, FILL = (I & 8) != 0, WS = (I & 2) != 0, WIDE = (I & 1) != 0;
-    return form == LNL_BASELINE ? lnl_kernel_cal<MODE, WS, WIDE, FILL, LAYER> : nullptr;
-}
-template <size_t... I>
-static LnlKernel lnl_kernel_cal_at(int i, LnlForm form, std::index_sequence<I...>) {
-    static constexpr LnlKernel (*inst[])(LnlForm) = {lnl_kernel_cal_inst<(int)I>...};
-    return inst[i](form);
-}
-static LnlKernel lnl_kernel_of(int mode, bool write_spec, bool wide, int ncomp, LnlForm form, bool filled, bool layered, bool calibrated) {
-    if (calibrated)
-        return lnl_kernel_cal_at((layered ? 16 : 0) | (filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0), form,
-                                 std::make_index_sequence<32>());
-    if (layered)
-        return lnl_kernel_layer_at((filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0), form,
-                                   std::make_index_sequence<16>());
-    if (filled) return lnl_kernel_fill_at((mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0), form, std::make_index_sequence<8>());
-    const int i = (mode == 0 ? 0 : 16) | (write_spec ? 8 : 0) | (wide ? 4 : 0) | (ncomp >= 1 && ncomp <= 3 ? ncomp : 0);
-    return lnl_kernel_at(i, form, std::make_index_sequence<32>());
+static LnlKernel lnl_kernel_of(int mode, bool write_spec, int ncomp, const LnlPlan &P) {
+    return lnl_kernel_at(lnl_inst_index({mode, write_spec, P.wide, lnl_plan_ncomp(P, ncomp), lnl_plan_kind(P)}), P.form,
+                         std::make_index_sequence<LNL_INSTANCES>());
 }
 
 // Likelihood stage of the batch in r->cur_group on stream lane `slot`: chi^2 parts of the units (and spectra out), then
@@ -1530,7 +1488,7 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, P.wide, r->ncomp, P.form, P.filled, P.layered, P.calibrated);
+    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
     int rc = ensure_dynamic_lds((const void *)kern, P.lds); if (rc) return rc;
     hipStream_t st = r->lanes[slot];

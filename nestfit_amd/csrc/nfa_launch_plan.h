@@ -175,15 +175,54 @@ inline size_t lnl_units_lds(const LpShape &s, bool table, int split, int waves, 
     return sizeof(double) * ((size_t)(table ? SM_TABLE_DOUBLES : 0) + ((size_t)lnl_wave_doubles(s) + part_doubles) * (waves / split));
 }
 
-enum LnlForm { LNL_PLAIN, LNL_W8, LNL_QUEUE, LNL_WEIGHTED, LNL_BASELINE };     // lnl_kernel, _w8, _queue, _wt, _bl
-// waves per workgroup, its dynamic LDS in bytes, workgroups; error: null, or why there is no plan
-// filled (in the padding behind `wide`): the form's instance of the filled family, lnl_kernel_fill / _wt_fill / _bl_fill --
-// the general component form with the filling factor in the Tb pass.  The form keeps its five values; only LNL_PLAIN,
-// LNL_WEIGHTED and LNL_BASELINE come with `filled`.  layered (the next padding byte; zero = summed): the form's instance of
-// the layered family, lnl_kernel_layer / _wt_layer / _bl_layer, over `filled` as well; the same three forms only.
-// calibrated (the last padding byte; zero = none): lnl_kernel_cal, the baseline form's general component instance with the
-// gain marginalised in the epilogue, over `filled` and `layered`; LNL_BASELINE only, whatever the set is otherwise.
+enum LnlForm { LNL_PLAIN, LNL_W8, LNL_QUEUE, LNL_WEIGHTED, LNL_BASELINE };
+// waves per workgroup, its dynamic LDS in bytes, workgroups; error: null, or why there is no plan.  filled, layered,
+// calibrated: the launch's (in the padding behind `wide`).  Which kernel instance a plan names: lnl_instance_exists below.
 struct LnlPlan { LnlForm form; bool wide, filled, layered, calibrated; LnlGeom G; int waves; size_t lds; int64_t blocks; const char *error; };
+
+// The kind of a spectra set: which of lnl_body's WEIGHTED, BASELINE, FILL, LAYER, CALIB flags its kernel switches on
+// (lnl_kernel_kind<..., KIND>, nfa_device.h).  Kind 0 is the plain set: lnl_kernel, lnl_kernel_w8, lnl_kernel_queue.
+enum : unsigned { LNL_K_WEIGHTED = 1, LNL_K_BASELINE = 2, LNL_K_FILL = 4, LNL_K_LAYER = 8, LNL_K_CALIB = 16 };
+constexpr unsigned LNL_KINDS = 32;      // kinds 0 .. 31: every set of the five bits
+constexpr unsigned lnl_plan_kind(const LnlPlan &P) {
+    return (P.form == LNL_WEIGHTED || P.form == LNL_BASELINE ? LNL_K_WEIGHTED : 0u) | (P.form == LNL_BASELINE ? LNL_K_BASELINE : 0u) |
+           (P.filled ? LNL_K_FILL : 0u) | (P.layered ? LNL_K_LAYER : 0u) | (P.calibrated ? LNL_K_CALIB : 0u);
+}
+// NCOMP of a plan's instance for a runner of `ncomp` components: 1..3, the component loop unrolled; 0, the general form
+constexpr int lnl_plan_ncomp(const LnlPlan &P, int ncomp) {
+    return P.filled || P.layered || P.calibrated || ncomp < 1 || ncomp > 3 ? 0 : ncomp;
+}
+// the form of a set of kind != 0: what its weighted and baseline bits say
+constexpr LnlForm lnl_kind_form(unsigned kind) {
+    return (kind & LNL_K_BASELINE) ? LNL_BASELINE : (kind & LNL_K_WEIGHTED) ? LNL_WEIGHTED : LNL_PLAIN;
+}
+// The rule: whether the engine has the likelihood kernel of `form` for (mode 0 table / 2 fast, spectra out, wide,
+// NCOMP 0..3, kind).  The engine instantiates exactly the instances this admits (nfa_engine.hip: lnl_kernel_inst) and
+// tests/test_launch_plan.py holds every plan of plan_lnl to it; DESIGN 4.2 counts them.
+constexpr bool lnl_instance_exists(LnlForm form, int mode, bool write_spec, bool wide, int ncomp_inst, unsigned kind) {
+    if ((mode != 0 && mode != 2) || ncomp_inst < 0 || ncomp_inst > 3 || kind >= LNL_KINDS) return false;
+    if (kind == 0)               // a plain set: every instance; w8 for the table mode with spectra out, the queue for its narrow sets
+        return form == LNL_PLAIN || (form == LNL_W8 && mode == 0 && write_spec) || (form == LNL_QUEUE && mode == 0 && !wide);
+    if ((kind & LNL_K_BASELINE) && !(kind & LNL_K_WEIGHTED)) return false;       // a baseline is profiled out of weighted sums
+    if ((kind & LNL_K_CALIB) && !(kind & LNL_K_BASELINE)) return false;          // the gain is marginalised in the baseline form
+    if ((kind & (LNL_K_FILL | LNL_K_LAYER | LNL_K_CALIB)) && ncomp_inst != 0) return false;     // the general component form only
+    return form == lnl_kind_form(kind);         // never w8 or the queue: the units give the same bits whatever the form
+}
+// An entry of the engine's table of instances and its index: bits 0-1 NCOMP, 2 wide, 3 spectra out, 4 fast mode, 5-9 kind
+struct LnlInst { int mode; bool write_spec, wide; int ncomp; unsigned kind; };
+constexpr int LNL_INSTANCES = 32 * LNL_KINDS;
+constexpr int lnl_inst_index(const LnlInst &i) {
+    return (int)(i.kind << 5) | (i.mode == 0 ? 0 : 16) | (i.write_spec ? 8 : 0) | (i.wide ? 4 : 0) | i.ncomp;
+}
+constexpr LnlInst lnl_inst_at(int i) { return {(i & 16) ? 2 : 0, (i & 8) != 0, (i & 4) != 0, i & 3, (unsigned)i >> 5}; }
+constexpr bool lnl_inst_round_trip() {
+    for (int i = 0; i < LNL_INSTANCES; ++i) {
+        const LnlInst a = lnl_inst_at(i);
+        if (lnl_inst_index(a) != i || a.ncomp > 3 || a.kind >= LNL_KINDS || (a.mode != 0 && a.mode != 2)) return false;
+    }
+    return true;
+}
+static_assert(lnl_inst_round_trip(), "lnl_inst_at must invert lnl_inst_index over the whole table");
 // Plans the likelihood launch of L.B items (the table of forms in DESIGN 4.2 is tested against this chain).
 inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     LnlPlan P = {};
@@ -315,7 +354,7 @@ inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool b
     else if (layered) P.refusal = "the resident kernel has no form for layered transfer: use nfa_ring_serve";
     else if (s.ndim > NFA_POINT_MAXDIM || lnl_wide(s)) P.refusal = "this runner's points go through the batch kernels: use nfa_ring_serve";
     else if (filled) P.refusal = "the resident kernel has no form for a filling factor: use nfa_ring_serve";
-    // (weighted sets, baseline sets among them: lnl_kernel_wt / lnl_kernel_bl.  The unweighted body would compute the unweighted sum.)
+    // (weighted sets, baseline sets among them: the fused kernels run the unweighted body, which would compute the unweighted sum.)
     else if (baseline) P.refusal = "the resident kernel has no form for a baseline: use nfa_ring_serve";
     else if (weighted) P.refusal = "the resident kernel has no form for a noise per channel: use nfa_ring_serve";
     else if (banded) P.refusal = "the resident kernel has no form for LTE bands: use nfa_ring_serve";

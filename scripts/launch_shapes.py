@@ -7,7 +7,7 @@ plan_setup, plan_fused) and prints a checksum of every result array.  It is dete
 process, no timing, a synchronisation after every launch -- so that two builds of the engine can be compared: run it
 under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/launch_shapes.py` with each, reduce the
 two traces with the second form to (kernel, grid, workgroup, LDS) in dispatch order, and diff the two lists and the two
-outputs (profiles/launch_plan/README.md).  The resident ring kernel needs a client process: tests/test_ring.py."""
+outputs (profiles/launch_plan/README.md, profiles/set_kinds/README.md).  The resident ring kernel needs a client process: tests/test_ring.py."""
 import csv
 import ctypes as C
 import hashlib
@@ -200,6 +200,19 @@ def main():
         host_calls(f'{mode} hyperfine 1 line', na.HyperfineRunner.from_data(rows([one_line], 700, 20), ut, ncomp=2), (1, 16, 300, 4096), 53, spectra_rows=300)
         host_calls(f'{mode} hyperfine 40 lines', na.HyperfineRunner.from_data(rows([forty], 1024, 45), ut, ncomp=2), (1, 16, 300, 4096), 54, spectra_rows=300)
         host_calls(f'{mode} lte 2 transitions', na.LteRunner.from_data(rows(lte, 800, 20), utl, ncomp=2), (1, 16, 300, 4096), 55, spectra_rows=300)
+        # the set kinds of the general component form, on short spectra: a filled LTE mix; layered sets (ammonia, the filled
+        # mix); calibrated sets (ammonia without and with a baseline, the filled layered mix)
+        iso = na.Molecule('rotor-iso', [5.0, 10.0, 20.0, 40.0, 80.0], [2.3, 4.3, 8.3, 16.3, 32.3])
+        mix_rows = rows([lte[0], na.LteLines(iso, 109.782176e9, 5.27, 3, 6.2e-8)], 300, 20)
+        utm = uniform_priors([(-6, 6), (2.8, 20), (12.0, 14.0), (0.1, 1.5), (11.0, 13.0), (-1.0, 0.0)])
+        filled = lambda **kw: na.LteMix((mol, iso), fill=True).Runner.from_data(mix_rows, utm, ncomp=2, **kw)
+        ammonia = lambda **kw: na.AmmoniaRunner.from_data(ammonia_spectra(320, 3), na.get_irdc_priors(size=500), ncomp=2, **kw)
+        for seed, (what, make, kw) in enumerate((('filled mix', filled, {}), ('ammonia layered', ammonia, dict(layered=True)),
+                                                 ('filled mix layered', filled, dict(layered=True)),
+                                                 ('ammonia calibrated', ammonia, dict(calibration=0.1)),
+                                                 ('ammonia calibrated, baseline 3', ammonia, dict(calibration=0.1, baseline_order=3)),
+                                                 ('filled mix layered calibrated', filled, dict(layered=True, calibration=0.1)))):
+            host_calls(f'{mode} {what}', make(**kw), (1, 16, 300, 4096), 56 + seed, spectra_rows=300)
         # weighted sets and baselines: the split parts' LDS differs with a baseline
         for what, kw in (('channel noise', dict(chan_noise=True)), ('baseline 1', dict(baseline_order=1)),
                          ('channel noise, baseline 3', dict(chan_noise=True, baseline_order=3))):

@@ -1,8 +1,8 @@
 """usage: python scripts/measure_baseline.py [--steps N] [--warmup W] [--reps R] [--out FILE]
 
 lnL evaluations/s at the metric shape -- 4096-row batches, two spectra of 1024 channels, two components -- of one weighted
-spectra set (a noise per channel, constant over each spectrum) without a baseline (lnl_kernel_wt) against the same data
-with a polynomial baseline of order 0..3 profiled out (nfa_specset_set_baseline: lnl_kernel_bl), in the table mode (the
+spectra set (a noise per channel, constant over each spectrum) without a baseline (the weighted kind) against the same data
+with a polynomial baseline of order 0..3 profiled out (nfa_specset_set_baseline: the baseline kind), in the table mode (the
 unit queue off, which weighted sets skip anyway) and the fast mode.  The data carry a tilted baseline of a few sigma.
 Device-pointer batches (nfa_runner_loglike_batch_dev) like bench.py; the sets are timed in turn, R times each, and the
 median of each is reported.  One JSON line per (mode, set)."""

@@ -2,10 +2,10 @@
 
 lnL evaluations/s at the metric shape -- 4096-row batches, two spectra of 1024 channels, two components -- of one weighted
 spectra set (a noise per channel, constant over each spectrum) with a baseline of order 1 and no calibration uncertainty
-(lnl_kernel_bl, the component loop unrolled) against the same data with a calibration uncertainty of 0.1 per spectrum
-(nfa_specset_set_calibration: lnl_kernel_cal, the general component form), with that baseline and without one (a zeroed
+(the baseline kind, the component loop unrolled) against the same data with a calibration uncertainty of 0.1 per spectrum
+(nfa_specset_set_calibration: the calibrated kind, the general component form), with that baseline and without one (a zeroed
 baseline record), in the table mode (the unit queue off, which weighted sets skip anyway) and the fast mode.  The weighted set
-without either (lnl_kernel_wt) is timed beside them.  --ncomp 4: every set takes the general component form, so that the
+without either (the weighted kind) is timed beside them.  --ncomp 4: every set takes the general component form, so that the
 kernels differ by the calibration's accumulator and epilogue alone (the set-up stage of four components dominates those
 steps).  At two components the general form and the accumulator are not timed apart.  The data carry a tilted baseline of
 a few sigma and gains of 1.12 and 0.90.  Device-pointer batches (nfa_runner_loglike_batch_dev) like bench.py; the sets are timed in turn, R times each, and

@@ -2,8 +2,8 @@
 
 lnL evaluations/s at the metric shape -- 4096-row batches, two spectra of 1024 channels, two components -- of one spectra
 set with a noise per spectrum against the same data with a noise per channel (nfa_specset_create_channel_noise), on the
-same kernel form: table mode with the unit queue off (lnl_kernel against lnl_kernel_wt) and fast mode (lnl_kernel against
-lnl_kernel_wt).  Per-channel sets: the scalar noise repeated over the channels (weights 1), and a noise varying by a
+same kernel form: table mode with the unit queue off (lnl_kernel against the weighted kind of lnl_kernel_kind) and fast mode (the
+same).  Per-channel sets: the scalar noise repeated over the channels (weights 1), and a noise varying by a
 factor of ten with 10 % of the channels masked.  Device-pointer batches (nfa_runner_loglike_batch_dev) like bench.py;
 the sets are timed in turn, R times each, and the median of each is reported.  One JSON line per (mode, set)."""
 import argparse
@@ -91,7 +91,7 @@ def main():
     lines = []
     try:
         for mode in ('table', 'fast'):
-            _ffi.set_option('lnl_queue', 0)                 # table mode: lnl_kernel, the form lnl_kernel_wt shares
+            _ffi.set_option('lnl_queue', 0)                 # table mode: lnl_kernel, the form the weighted kind shares
             for r in sets.values():
                 r.set_exp_mode(mode)
             secs = {name: [] for name in sets}

@@ -1,5 +1,6 @@
 """A calibration uncertainty per spectrum on the device (nfa_specset_set_calibration, `calibration=`): the gain g ~
-N(1, s^2) of every spectrum is integrated out of the likelihood in closed form inside lnl_kernel_cal.
+N(1, s^2) of every spectrum is integrated out of the likelihood in closed form inside the calibrated kind of
+lnl_kernel_kind.
 
 The reference is tests/calib_restatement.py (the unsimplified closed form in longdouble, checked against a numerical integral
 in tests/test_calibration_cpu.py) on model spectra of the other restatements and the oracle, at the sizes of the sibling

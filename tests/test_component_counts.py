@@ -376,7 +376,7 @@ def test_single_points_at_the_point_kernel_boundary(engine, nfo, mode):
 # ------------------------------------------------------------------------------------------ e. channel noise at ten
 @pytest.mark.parametrize('mode', MODES)
 def test_constant_channel_noise_gives_the_scalar_bits_at_ten_components(engine, mode):
-    """A noise array of one constant value per spectrum (lnl_kernel_wt, general form) against the scalar noise: theta,
+    """A noise array of one constant value per spectrum (the weighted kind, general form) against the scalar noise: theta,
     lnL and predict_batch bit for bit at 10 components."""
     engine.set_exp_mode(mode)
     ut = _wide(engine)

@@ -89,6 +89,16 @@ void lnl_many(long long n, const long long *in, long long *out) {
         out[5] = P.waves; out[6] = (long long)P.lds; out[7] = P.blocks; out[8] = P.G.inv_nspec; out[9] = P.G.inv_nhf;
     }
 }
+// the instance rule (lnl_instance_exists) and, for a plan of a launch with the three set flags, {error, form, wide, kind, ncomp}
+int inst_exists(int form, int mode, int ws, int wide, int ncomp_inst, unsigned kind) {
+    return lnl_instance_exists((LnlForm)form, mode, ws != 0, wide != 0, ncomp_inst, kind);
+}
+void plan_inst(const LpShape *s, const LpKnobs *k, const LpLaunch *L, int filled, int layered, int calibrated, int *out) {
+    LpLaunch l = *L;
+    l.filled = filled != 0; l.layered = layered != 0; l.calibrated = calibrated != 0;
+    const LnlPlan P = plan_lnl(*s, *k, l);
+    out[0] = P.error != nullptr; out[1] = P.form; out[2] = P.wide; out[3] = (int)lnl_plan_kind(P); out[4] = lnl_plan_ncomp(P, s->ncomp);
+}
 int sizes(int i) {
     const int s[] = {sizeof(LpShape), sizeof(LpLaunch), sizeof(LpKnobs), sizeof(LnlGeom), sizeof(LnlPlan), sizeof(SetupPlan), sizeof(FusedPlan),
                      SM_TABLE_DOUBLES, SM_TABLE_TAIL, (int)LDS_PER_CU, LNL_PARTS, NFA_BL_NB, SETUP_TI, QREC, POINT_WAVES, NFA_POINT_MAXDIM, NFA_GROUP_MAX};
@@ -249,6 +259,60 @@ def test_likelihood_plans_follow_the_form_table_and_the_kernels_layout(lib):
         forms |= set(np.unique(got['form'][ok])); splits |= set(np.unique(got['split'][ok])); errors |= set(texts.values())
     assert forms == {PLAIN, W8, QUEUE, WEIGHTED, BASELINE} and splits == {1, 2, 4} and len(errors) == 1
     print(f'{n} likelihood plans checked')
+
+
+# ---- the instances of the likelihood kernel ------------------------------------------------------------------------
+K_WEIGHTED, K_BASELINE, K_FILL, K_LAYER, K_CALIB = 1, 2, 4, 8, 16
+
+
+def test_the_instance_rule_gives_the_documented_families(lib):
+    """lnl_instance_exists over every (form, mode, spectra out, wide, NCOMP 0..3, kind 0..31) against the counts DESIGN
+    states: 4.2 (plain, weighted and baseline: 32 each over mode, spectra out, wide, NCOMP; w8: the table mode with spectra
+    out; queue: the table mode, narrow), 4.10 (filled: plain, weighted, baseline over mode, spectra out, wide), 4.11
+    (layered: those over filled as well), 4.12 (calibrated: the baseline form over filled and layered)."""
+    count = dict.fromkeys(('plain', 'w8', 'queue', 'weighted', 'baseline', 'filled', 'layered', 'calibrated'), 0)
+    for form, mode, ws, wide, ncomp, kind in itertools.product(range(5), (0, 2), (0, 1), (0, 1), range(4), range(32)):
+        if not lib.inst_exists(form, mode, ws, wide, ncomp, kind):
+            continue
+        if kind == 0:
+            family = {PLAIN: 'plain', W8: 'w8', QUEUE: 'queue'}[form]          # (no other form without a kind)
+        else:
+            family = ('calibrated' if kind & K_CALIB else 'layered' if kind & K_LAYER else 'filled' if kind & K_FILL
+                      else 'baseline' if kind & K_BASELINE else 'weighted')
+        count[family] += 1
+    assert count == dict(plain=32, w8=8, queue=8, weighted=32, baseline=32, filled=24, layered=48, calibrated=32)
+    assert sum(count.values()) == 216
+    # outside the enumeration there is nothing: the polynomial mode, NCOMP 4, a kind of six bits
+    assert not any(lib.inst_exists(PLAIN, *a) for a in ((1, 0, 0, 0, 0), (0, 0, 0, 4, 0), (0, 0, 0, -1, 0), (0, 0, 0, 0, 32)))
+
+
+def test_every_plan_has_its_instance(lib):
+    """The sweep of tests/test_calibration_cpu.py crossed with filled, layered and calibrated: every plan names an instance
+    that exists, and its kind and NCOMP are what the rule says in words: weighted for the weighted and the baseline form,
+    baseline for the baseline form, the three flags as the launch has them; NCOMP 1..3 unrolled, else and for every filled,
+    layered or calibrated set the general form."""
+    out = (C.c_int * 5)()
+    n, kinds = 0, set()
+    for mode, B, (nhf_max, size, model), ncomp, write_spec in itertools.product(
+            (0, 2), (1, 11, 64, 4096, 32768), ((9, 300, 4), (21, 1024, 0), (33, 1024, 1)), (1, 2, 3, 4, 8), (False, True)):
+        s, k = shape(n_spec=2, size=size, nhf_max=nhf_max, ncomp=ncomp, model=model), knobs()
+        for baseline, weighted, has_queue, filled, layered, calibrated in itertools.product((False, True), repeat=6):
+            L = LpLaunch(B=B, mode=mode, group_n=1, group_each=B, write_spec=write_spec, has_prior=True, baseline=baseline,
+                         weighted=weighted, has_queue=has_queue)
+            lib.plan_inst(C.byref(s), C.byref(k), C.byref(L), filled, layered, calibrated, out)
+            error, form, wide, kind, ncomp_inst = out
+            assert not error, (mode, B, nhf_max, ncomp)               # (none of these shapes is refused: no plan is left out)
+            want_kind = ((K_WEIGHTED if form in (WEIGHTED, BASELINE) else 0) | (K_BASELINE if form == BASELINE else 0)
+                         | (K_FILL if filled else 0) | (K_LAYER if layered else 0) | (K_CALIB if calibrated else 0))
+            want_ncomp = 0 if filled or layered or calibrated or ncomp > 3 else ncomp
+            assert (kind, ncomp_inst) == (want_kind, want_ncomp)
+            assert lib.inst_exists(form, mode, write_spec, wide, ncomp_inst, kind), (form, mode, write_spec, wide, ncomp_inst, kind)
+            n += 1
+            kinds.add(kind)
+    assert n == 2 * 5 * 3 * 5 * 2 * 64
+    # every kind the rule admits is planned by some launch: 1 + weighted, baseline + 3 filled + 6 layered + 4 calibrated
+    assert len(kinds) == 16 and kinds == {kd for kd in range(32) if lib.inst_exists(
+        BASELINE if kd & K_BASELINE else WEIGHTED if kd & K_WEIGHTED else PLAIN, 2, 0, 0, 0, kd)}
 
 
 def one_lnl(lib, s, k, L):
