@@ -42,6 +42,13 @@ int nfa_test_callback_latency(nfa_loglike_callback_fn callback, void *runner, in
 int nfa_test_queue_trace(int on);
 int nfa_test_queue_trace_read(unsigned long long *out);
 
+/* Likelihood launches since the last reset, counted on the host where they are made, each on the entry of the engine's
+ * table of instances that holds the kernel the launch was given: out[1024][5], indexed by the
+ * engine's instance index (csrc/nfa_launch_plan.h, lnl_inst_index: bits 0-1 NCOMP, 2 wide, 3 spectra out, 4 fast mode,
+ * 5-9 kind) and the launch form (LnlForm: plain, w8, queue, weighted, baseline).  out NULL: nothing is copied;
+ * reset != 0: the counts are cleared as they are read. */
+int nfa_test_lnl_launches(int64_t *out, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,7 @@ TEST_SIGNATURES = {
     'nfa_test_callback_latency': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _dp, C.c_int, _dp, _dp]),
     'nfa_test_queue_trace': (C.c_int, [C.c_int]),
     'nfa_test_queue_trace_read': (C.c_int, [C.POINTER(C.c_ulonglong)]),
+    'nfa_test_lnl_launches': (C.c_int, [_lp, C.c_int]),
 }
 TEST_LIB_PATH = HERE / 'lib' / 'libnestfit_amd_test.so'
 

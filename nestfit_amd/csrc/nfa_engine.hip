@@ -1448,7 +1448,8 @@ static int launch_band(nfa_runner *r, int slot, int64_t B) {
 }
 
 // The kernel of a plan.  Naming an instance compiles it, so entry I of the table names its instance only where
-// lnl_instance_exists (nfa_launch_plan.h) says there is one: that predicate is what keeps the instance count where it is.
+// lnl_instance_exists (nfa_launch_plan.h) says there is one: that predicate is what keeps the instance count where it is
+// (208: the plain form of the table mode with spectra out is not among them, no plan of plan_lnl names it).
 typedef void (*LnlKernel)(SpecDev, BatchGroup, const double *, double *, double *, long, LnlGeom, const double *);
 template <int I>     // I: lnl_inst_index
 static LnlKernel lnl_kernel_inst(LnlForm form) {
@@ -1476,6 +1477,25 @@ static LnlKernel lnl_kernel_of(int mode, bool write_spec, int ncomp, const LnlPl
     return lnl_kernel_at(lnl_inst_index({mode, write_spec, P.wide, lnl_plan_ncomp(P, ncomp), lnl_plan_kind(P)}), P.form,
                          std::make_index_sequence<LNL_INSTANCES>());
 }
+#ifdef NFA_TEST_HOOKS
+#include <atomic>
+// Likelihood launches by (lnl_inst_index, LnlForm) since the last reset (nfa_test_lnl_launches): host side, counted where
+// the launch is made; atomic, a broker's runners launch from several threads.  A launch is counted on the entry of the
+// table that holds the kernel it was given -- found by the kernel's address, not by the index lnl_kernel_of formed -- so a
+// slip in that index shows as a launch on another instance (every instance is a function of its own: one entry per address).
+static std::atomic<int64_t> g_lnl_launches[LNL_INSTANCES][LNL_BASELINE + 1];
+static void count_lnl_launch(LnlKernel kern) {
+    static thread_local LnlKernel last = nullptr;             // (a thread's launches are mostly of one kernel: the table is
+    static thread_local std::atomic<int64_t> *slot = nullptr; //  searched when the kernel changes)
+    if (kern != last) {
+        last = kern, slot = nullptr;
+        for (int i = 0; i < LNL_INSTANCES && !slot; ++i)
+            for (int f = 0; f <= LNL_BASELINE && !slot; ++f)
+                if (lnl_kernel_at(i, (LnlForm)f, std::make_index_sequence<LNL_INSTANCES>()) == kern) slot = &g_lnl_launches[i][f];
+    }
+    if (slot) slot->fetch_add(1, std::memory_order_relaxed);
+}
+#endif
 
 // Likelihood stage of the batch in r->cur_group on stream lane `slot`: chi^2 parts of the units (and spectra out), then
 // -- want_lnl, and nobody else sums the parts -- lnL of the items (lnl_sum_kernel)
@@ -1490,6 +1510,9 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #endif
     const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
+#ifdef NFA_TEST_HOOKS
+    count_lnl_launch(kern);
+#endif
     int rc = ensure_dynamic_lds((const void *)kern, P.lds); if (rc) return rc;
     hipStream_t st = r->lanes[slot];
     double *part = want_lnl ? r->d_part[slot] : nullptr;

@@ -201,8 +201,10 @@ constexpr LnlForm lnl_kind_form(unsigned kind) {
 // tests/test_launch_plan.py holds every plan of plan_lnl to it; DESIGN 4.2 counts them.
 constexpr bool lnl_instance_exists(LnlForm form, int mode, bool write_spec, bool wide, int ncomp_inst, unsigned kind) {
     if ((mode != 0 && mode != 2) || ncomp_inst < 0 || ncomp_inst > 3 || kind >= LNL_KINDS) return false;
-    if (kind == 0)               // a plain set: every instance; w8 for the table mode with spectra out, the queue for its narrow sets
-        return form == LNL_PLAIN || (form == LNL_W8 && mode == 0 && write_spec) || (form == LNL_QUEUE && mode == 0 && !wide);
+    if (kind == 0)               // a plain set: the table mode with spectra out is w8's (plan_lnl sends no such launch to the plain
+                                 // form), every other instance plain; the queue for the table mode's narrow sets
+        return (form == LNL_PLAIN && !(mode == 0 && write_spec)) || (form == LNL_W8 && mode == 0 && write_spec) ||
+               (form == LNL_QUEUE && mode == 0 && !wide);
     if ((kind & LNL_K_BASELINE) && !(kind & LNL_K_WEIGHTED)) return false;       // a baseline is profiled out of weighted sums
     if ((kind & LNL_K_CALIB) && !(kind & LNL_K_BASELINE)) return false;          // the gain is marginalised in the baseline form
     if ((kind & (LNL_K_FILL | LNL_K_LAYER | LNL_K_CALIB)) && ncomp_inst != 0) return false;     // the general component form only

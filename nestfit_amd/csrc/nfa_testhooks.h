@@ -198,6 +198,18 @@ int nfa_test_callback_latency(nfa_loglike_callback_fn callback, void *runner, in
     return NFA_OK;
 }
 
+// Likelihood launches since the last reset, by (lnl_inst_index, LnlForm) of the table entry whose kernel was launched:
+// out[LNL_INSTANCES][5], null: nothing is copied; reset != 0: the counts read are cleared.  Host code only (launch_lnl counts).
+int nfa_test_lnl_launches(int64_t *out, int reset) {
+    for (int i = 0; i < LNL_INSTANCES; ++i)
+        for (int f = 0; f <= LNL_BASELINE; ++f) {
+            const int64_t n = reset ? g_lnl_launches[i][f].exchange(0, std::memory_order_relaxed)
+                                    : g_lnl_launches[i][f].load(std::memory_order_relaxed);
+            if (out) out[i * (LNL_BASELINE + 1) + f] = n;
+        }
+    return NFA_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

@@ -280,8 +280,11 @@ def test_the_instance_rule_gives_the_documented_families(lib):
             family = ('calibrated' if kind & K_CALIB else 'layered' if kind & K_LAYER else 'filled' if kind & K_FILL
                       else 'baseline' if kind & K_BASELINE else 'weighted')
         count[family] += 1
-    assert count == dict(plain=32, w8=8, queue=8, weighted=32, baseline=32, filled=24, layered=48, calibrated=32)
-    assert sum(count.values()) == 216
+    assert count == dict(plain=24, w8=8, queue=8, weighted=32, baseline=32, filled=24, layered=48, calibrated=32)
+    assert sum(count.values()) == 208
+    # the plain form of kind 0: everything but the table mode with spectra out, which is w8's or the queue's
+    for mode, ws, wide, ncomp in itertools.product((0, 2), (0, 1), (0, 1), range(4)):
+        assert bool(lib.inst_exists(PLAIN, mode, ws, wide, ncomp, 0)) == (not (mode == 0 and ws))
     # outside the enumeration there is nothing: the polynomial mode, NCOMP 4, a kind of six bits
     assert not any(lib.inst_exists(PLAIN, *a) for a in ((1, 0, 0, 0, 0), (0, 0, 0, 4, 0), (0, 0, 0, -1, 0), (0, 0, 0, 0, 32)))
 
@@ -313,6 +316,72 @@ def test_every_plan_has_its_instance(lib):
     # every kind the rule admits is planned by some launch: 1 + weighted, baseline + 3 filled + 6 layered + 4 calibrated
     assert len(kinds) == 16 and kinds == {kd for kd in range(32) if lib.inst_exists(
         BASELINE if kd & K_BASELINE else WEIGHTED if kd & K_WEIGHTED else PLAIN, 2, 0, 0, 0, kd)}
+
+
+def admitted(lib):
+    """{(lnl_inst_index, form)} of everything lnl_instance_exists admits."""
+    return {((kind << 5) | (16 if mode else 0) | (8 if ws else 0) | (4 if wide else 0) | ncomp, form)
+            for form, mode, ws, wide, ncomp, kind in itertools.product(range(5), (0, 2), (0, 1), (0, 1), range(4), range(32))
+            if lib.inst_exists(form, mode, ws, wide, ncomp, kind)}
+
+
+def planned(lib, s, k, L, filled, layered, calibrated, out=None):
+    """(lnl_inst_index, form) of the plan of a launch; it has no error and names an instance that exists."""
+    out = (C.c_int * 5)() if out is None else out
+    lib.plan_inst(C.byref(s), C.byref(k), C.byref(L), filled, layered, calibrated, out)
+    error, form, wide, kind, ncomp_inst = out
+    assert not error
+    return (kind << 5) | (16 if L.mode else 0) | (8 if L.write_spec else 0) | (4 if wide else 0) | ncomp_inst, form
+
+
+def test_every_instance_is_the_plan_of_some_launch(lib):
+    """The converse of test_every_plan_has_its_instance: everything the rule admits -- everything the engine compiles -- is
+    what plan_lnl names for some runner, launch and options.  One and two spectra of 128 and 1024 channels, 21 and 40 lines, 1
+    to 4 components, lnl_split 0 and 1, from one row to 40000, both modes, spectra out or not, the lane's counters there or
+    not, every set of the five flags."""
+    want = admitted(lib)
+    assert len(want) == 208
+    got, out, k = set(), (C.c_int * 5)(), knobs()
+    for n_spec, size, nhf_max, ncomp, split in itertools.product((1, 2), (128, 1024), (21, 40), (1, 2, 3, 4), (0, 1)):
+        s = shape(n_spec=n_spec, size=size, nhf_max=nhf_max, ncomp=ncomp, lnl_split=split)
+        for mode, B, write_spec, has_queue, baseline, weighted in itertools.product((0, 2), (1, 4096, 40000), (False, True), (False, True),
+                                                                                   (False, True), (False, True)):
+            L = LpLaunch(B=B, mode=mode, group_n=1, group_each=B, write_spec=write_spec, has_prior=False, baseline=baseline,
+                         weighted=weighted, has_queue=has_queue)
+            for filled, layered, calibrated in itertools.product((0, 1), repeat=3):
+                got.add(planned(lib, s, k, L, filled, layered, calibrated, out))
+    assert got == want, (sorted(want - got), sorted(got - want))
+
+
+def test_the_census_names_every_instance_and_every_case_plans_its_own(lib):
+    """tests/instance_census.py: the (instance, form) pairs its cases name are the pairs the rule admits, one case each, and
+    at 256 compute units plan_lnl gives every case exactly its pair, at lnl_split 0 and 1 -- what tests/test_instance_census.py
+    then finds in the launch counters of the device."""
+    import instance_census as ic
+    assert (ic.PLAIN, ic.W8, ic.QUEUE, ic.WEIGHTED, ic.BASELINE) == (PLAIN, W8, QUEUE, WEIGHTED, BASELINE)
+    named = [(c.index, c.form) for c in ic.CASES]
+    assert len(named) == len(set(named)) == 208 and set(named) == admitted(lib)
+    assert len(ic.GROUPS) == 9 and all(c.group in ic.GROUPS for c in ic.CASES)
+    k = knobs(n_cu=256)
+
+    def plan(c, B, split):
+        st = ic.SETS[c.set]
+        s = shape(n_spec=len(st['sizes']), size=list(st['sizes']), nhf_max=st['nhf_max'], ncomp=c.ncomp, lnl_split=split)
+        L = LpLaunch(B=B, mode={'table': 0, 'fast': 2}[c.mode], group_n=1, group_each=B, write_spec=c.spectra, has_prior=False,
+                     baseline=c.order is not None, weighted=c.chan, has_queue=True)
+        assert st['filled'] == c.filled and ic.wide_of(c.set) == bool(c.index & 4)
+        return planned(lib, s, k, L, c.filled, c.layered, c.cal)
+    for c in ic.CASES:
+        for split in (0, 1):
+            assert plan(c, ic.rows_of(c, 256), split) == (c.index, c.form), c
+        if c.form == QUEUE:
+            # the queue's launches are the smallest the plan queues, and 17 rows; one row fewer than the smallest is not
+            # queued, nor is the cases' first launch: both land on the plain or w8 instance of the same NCOMP
+            smallest = ic.queue_rows(256, c.ncomp, c.set)
+            assert ic.rows_of(c, 256) == smallest + 17 and (2 * (smallest + 17)) % 16 != 0
+            assert plan(c, smallest, 0) == (c.index, QUEUE)
+            for B in (smallest - 1, ic.N_ROWS):
+                assert plan(c, B, 0) == (c.index, ic.small_form(c)), (c, B)
 
 
 def one_lnl(lib, s, k, L):
