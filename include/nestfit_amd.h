@@ -334,6 +334,29 @@ int nfa_specset_layered(const nfa_specset *ss);
 int nfa_specset_set_calibration(nfa_specset *ss, const double *cal);
 /* 1 and out[n_spec] = the values set (out may be null), or 0 for a set without a calibration uncertainty (and for null) */
 int nfa_specset_calibration(const nfa_specset *ss, double *out);
+/* Channel noise correlated along the spectral axis (Hanning smoothing, regridding, an oversampling correlator).  The noise
+ * of spectrum s is n_c = sigma_c eps_c, sigma_c the set's scalar or per-channel noise and eps the zero-mean, unit-variance
+ * stationary Gaussian AR(2) process whose first two autocorrelations are rho[s][0], rho[s][1] (the maximum-entropy process
+ * with those two; AR(1) is rho_2 = rho_1^2).  Yule-Walker: phi_1 = rho_1 (1 - rho_2) / (1 - rho_1^2), phi_2 = (rho_2 -
+ * rho_1^2) / (1 - rho_1^2), v = 1 - phi_1 rho_1 - phi_2 rho_2; the inverse of the correlation matrix R is pentadiagonal
+ * in closed form, and with u_c = sigma_ref / sigma_c, Q = diag(u) R^-1 diag(u):
+ *     lnL_s = -(d - p)^T Q (d - p) / (2 sigma_ref^2)
+ * without a normalisation term, like every likelihood here (-ln det R / 2, ln det R = (N - 2) ln v + ln(1 - rho_1^2), is
+ * a constant of the data).  nfa_specset_null_lnz is the same expression at p = 0.
+ * rho[n_spec][2], shared by all pixels.  rho = NULL or all zeros removes the correlation (the set's former kernels and
+ * results bit for bit); a spectrum whose pair is (0, 0) beside correlated ones keeps white noise.  NFA_ERR_ARG, the set
+ * left as it was: a value that is not finite, |rho_1| >= 1, rho_2 outside (2 rho_1^2 - 1, 1), v < 0.01 (the noise nearly
+ * determined by its neighbours: Q ill-conditioned), a spectrum of fewer than 4 channels; a set with a masked channel
+ * (channel noise inf), a baseline or a calibration uncertainty -- and nfa_specset_set_baseline (order >= 0) and
+ * nfa_specset_set_calibration (a value > 0) refuse a correlated set likewise.  Every model, filled and layered sets too.
+ * Like nfa_specset_set_baseline it launches held batches first, synchronises the device and drops the runners' captured
+ * single-point graphs: call it between batches.  nfa_specset_set_data keeps it.  Spectra out are the model, unchanged.
+ * Correlated sets go through the batch kernels (the general component form); single points and a broker's handful too, and
+ * nfa_ring_serve_device refuses their runners ("the resident kernel has no form for correlated channel noise: use
+ * nfa_ring_serve"). */
+int nfa_specset_set_correlation(nfa_specset *ss, const double *rho);
+/* 1 and out[n_spec][2] = the pairs set (out may be null), or 0 for a set without a noise correlation (and for null) */
+int nfa_specset_correlation(const nfa_specset *ss, double *out);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

@@ -51,6 +51,97 @@ def check_calibration(cal, n_spec=None):
     return out if np.any(out > 0.0) else None
 
 
+HANNING = (2.0 / 3.0, 1.0 / 6.0)      # (rho_1, rho_2) of white noise smoothed with the Hanning kernel (1/4, 1/2, 1/4)
+CORR_V_MIN = 0.01                     # smallest innovations variance a noise correlation may have
+
+
+def ar1(rho):
+    """The pair (rho, rho^2) of an AR(1) process: `correlation=ar1(0.5)`."""
+    rho = float(rho)
+    return (rho, rho * rho)
+
+
+def yule_walker(rho1, rho2):
+    """(phi_1, phi_2, v) of the unit-variance AR(2) process whose first two autocorrelations are (rho1, rho2): the
+    coefficients and the innovations variance."""
+    den = 1.0 - rho1 * rho1
+    phi1, phi2 = rho1 * (1.0 - rho2) / den, (rho2 - rho1 * rho1) / den
+    return phi1, phi2, 1.0 - phi1 * rho1 - phi2 * rho2
+
+
+def corr_bands(rho1, rho2, n):
+    """The three bands of R^-1, the inverse (exactly pentadiagonal) of the n x n correlation matrix of the AR(2) process
+    with autocorrelations (rho1, rho2), n >= 4: the diagonal [n], the first [n - 1] and the second [n - 2] off-diagonal."""
+    phi1, phi2, v = yule_walker(rho1, rho2)
+    d0 = np.full(n, 1.0 + phi1 * phi1 + phi2 * phi2)
+    d0[[1, n - 2]] = 1.0 + phi1 * phi1
+    d0[[0, n - 1]] = 1.0
+    d1 = np.full(n - 1, -phi1 * (1.0 - phi2))
+    d1[[0, n - 2]] = -phi1
+    return d0 / v, d1 / v, np.full(n - 2, -phi2) / v
+
+
+def corr_lndet(rho1, rho2, n):
+    """ln det R of that matrix: (n - 2) ln v + ln(1 - rho1^2)."""
+    return (n - 2) * np.log(yule_walker(rho1, rho2)[2]) + np.log(1.0 - rho1 * rho1)
+
+
+def check_correlation(corr, n_spec=None, sizes=None, masked=False, baseline_order=None, calibration=None):
+    """`correlation` of a runner: the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis
+    (DESIGN 4.13).  None for none; a pair applies to all `n_spec` spectra; an array [n_spec, 2] gives one pair per spectrum
+    (a one-dimensional value is always ONE pair).  Every pair is finite with |rho_1| < 1, 2 rho_1^2 - 1 < rho_2 < 1 and an
+    innovations variance v >= 0.01, or (0, 0) for white noise; all zeros is None.  A correlation goes with neither a masked
+    channel (`masked`), a baseline (`baseline_order`) nor a calibration uncertainty (`calibration`), and needs spectra of 4
+    channels and more (`sizes`).  Returns None or a float64 array [n_spec, 2] ([1, 2] without n_spec); ValueError otherwise.
+    Needs no device."""
+    if corr is None:
+        return None
+    what = 'correlation must be None, a pair (rho_1, rho_2) or an array [n_spec, 2] of such pairs'
+    try:
+        out = np.array(corr, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}, not {corr!r}') from None
+    if isinstance(corr, np.ndarray) and corr.dtype.kind not in 'iuf':
+        raise ValueError(f'{what}, not {corr!r}')
+    if out.ndim == 1 and out.shape == (2,):
+        out = np.tile(out, (1 if n_spec is None else int(n_spec), 1))
+    elif out.ndim != 2 or out.shape[1] != 2 or out.shape[0] == 0:
+        raise ValueError(f'{what}, not {corr!r}')
+    elif n_spec is not None and out.shape[0] != int(n_spec):
+        raise ValueError(f'{what}: {out.shape[0]} pairs for {int(n_spec)} spectra')
+    if not np.all(np.isfinite(out)):
+        raise ValueError(f'{what}: every value finite, not {corr!r}')
+    for r1, r2 in out:
+        if r1 == 0.0 and r2 == 0.0:
+            continue
+        if not abs(r1) < 1.0:
+            raise ValueError(f'correlation: |rho_1| < 1, not {r1!r}')
+        if not 2.0 * r1 * r1 - 1.0 < r2 < 1.0:
+            raise ValueError(f'correlation: 2 rho_1^2 - 1 < rho_2 < 1 (a positive definite correlation matrix), not ({r1!r}, {r2!r})')
+        if not yule_walker(r1, r2)[2] >= CORR_V_MIN:
+            raise ValueError(f'correlation: the innovations variance of ({r1!r}, {r2!r}) is below {CORR_V_MIN}: the noise is '
+                             'nearly determined by its neighbours')
+    if not np.any(out != 0.0):
+        return None
+    if sizes is not None and np.any(np.asarray(sizes) < 4):
+        raise ValueError('a noise correlation needs spectra of 4 channels and more')
+    if masked:
+        raise ValueError('a noise correlation does not go with masked channels (channel noise inf)')
+    if baseline_order is not None and baseline_order != -1:
+        raise ValueError('a noise correlation does not go with a baseline (baseline_order)')
+    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
+        raise ValueError('a noise correlation does not go with a calibration uncertainty (calibration)')
+    return out
+
+
+def spec_data_sizes_masked(spec_data):
+    """(sizes, masked) of `from_data`'s rows [xarr, data, noise, ...] for `check_correlation`: the channels of every spectrum, and
+    whether any channel noise masks a channel (inf).  numpy only."""
+    sizes = [int(np.size(row[0])) for row in spec_data]
+    masked = any(np.ndim(row[2]) > 0 and not np.all(np.isfinite(np.asarray(row[2], dtype=np.float64))) for row in spec_data)
+    return sizes, masked
+
+
 def gain_fit(data, pred, weight, sigma, cal, order=None):
     """Posterior (mean, standard deviation) of the gain of ONE spectrum at a given model `pred`: data =
     g pred + baseline + noise, g ~ N(1, cal^2), channel weights `weight` (0: masked), sigma the noise of weight 1; with a
@@ -216,11 +307,23 @@ class _SpecSet:
         self.baseline_order = None
         self.layered = False
         self.calibration = None
+        self.correlation = None
+        self.masked = bool(self.per_channel and not np.all(np.isfinite(noise)))
+
+    def set_correlation(self, corr):
+        """The autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis (`check_correlation`'s argument),
+        or none (None, zeros): nfa_specset_set_correlation.  null_lnZ() follows."""
+        corr = check_correlation(corr, self.n_spec, self.sizes, self.masked, self.baseline_order, self.calibration)
+        corr = None if corr is None else np.ascontiguousarray(corr)
+        _ffi.check(_ffi.load().nfa_specset_set_correlation(self.handle, None if corr is None else _ffi.dptr(corr)))
+        self.correlation = corr
 
     def set_calibration(self, cal):
         """A calibration uncertainty per spectrum, integrated out of the likelihood (`check_calibration`'s argument), or
         none (None, zeros): nfa_specset_set_calibration.  null_lnZ() does not change."""
         cal = check_calibration(cal, self.n_spec)
+        if cal is not None and self.correlation is not None:
+            raise ValueError('a calibration uncertainty does not go with a noise correlation (correlation)')
         _ffi.check(_ffi.load().nfa_specset_set_calibration(self.handle, None if cal is None else _ffi.dptr(cal)))
         self.calibration = cal
 
@@ -235,6 +338,8 @@ class _SpecSet:
         """A polynomial baseline of degree <= `order` per (pixel, spectrum) profiled out of the likelihood, or none
         (None / -1): nfa_specset_set_baseline.  null_lnZ() then is the baseline-only model's."""
         order = check_baseline_order(order)
+        if order is not None and self.correlation is not None:
+            raise ValueError('a baseline does not go with a noise correlation (correlation)')
         _ffi.check(_ffi.load().nfa_specset_set_baseline(self.handle, -1 if order is None else order))
         self.baseline_order = order
 
@@ -350,8 +455,12 @@ class EngineRunner(Runner):
     N_MODEL = 6
 
     def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False,
-               calibration=None):
-        """calibration: None, or the fractional 1-sigma uncertainty of the spectra's intensity scales -- a number for all of
+               calibration=None, correlation=None):
+        """correlation: None, or the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis -- a
+        pair for all spectra (`HANNING`, `ar1(rho)`) or an array [n_spec, 2] -- for cubes that were smoothed, regridded or
+        oversampled (nfa_specset_set_correlation); all zeros is None.  Not with masked channels, a baseline or a
+        calibration.  null_lnZ is then d^T Q d's, and the spectra's `prefactor` gains -ln det R / 2.
+        calibration: None, or the fractional 1-sigma uncertainty of the spectra's intensity scales -- a number for all of
         them or one per spectrum, each in [0, 1] -- integrated out of the likelihood in closed form per spectrum
         (nfa_specset_set_calibration); all zeros is None.  null_lnZ is unchanged.
         layered: layered radiative transfer (nfa_specset_set_layered) -- the components are layers along the
@@ -365,6 +474,8 @@ class EngineRunner(Runner):
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered, self.MODEL)
         calibration = check_calibration(calibration, len(spectra))
+        check_correlation(correlation, len(spectra), [s.size for s in spectra],
+                          any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -396,6 +507,26 @@ class EngineRunner(Runner):
             self.null_lnZ = float(self._ss.null_lnZ().sum())
         if calibration is not None:
             self._ss.set_calibration(calibration)
+        if correlation is not None:
+            self.set_correlation(correlation)
+
+    @property
+    def correlation(self):
+        """None, or the float64 array [n_spec, 2] of the spectra's noise autocorrelations (rho_1, rho_2)."""
+        corr = self._ss.correlation
+        return None if corr is None else corr.copy()
+
+    def set_correlation(self, corr):
+        """Sets (a pair, or one per spectrum) or removes (None, zeros) the noise correlation of this runner's spectra;
+        null_lnZ follows, and the spectra's `prefactor`.  The spectra's private one-spectrum sets stay white: a spectrum's own
+        `loglikelihood` and `null_lnZ` (and what `predict` leaves there) are white-noise values and must not be combined with
+        its correlated `prefactor`; the runner's `loglikelihood`, `loglikelihood_batch` and `predict_batch` are the
+        correlated ones."""
+        self._ss.set_correlation(corr)
+        self.null_lnZ = float(self._ss.null_lnZ().sum())
+        corr = self._ss.correlation
+        for k, s in enumerate(self._model_spectra()):
+            s.set_correlation(None if corr is None else corr[k])
 
     @property
     def calibration(self):

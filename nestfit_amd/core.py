@@ -340,6 +340,8 @@ class Spectrum:
             self.noise = float(noise)
             self.n_chan = int(xarr.shape[0])
             self.prefactor = -xarr.shape[0] / 2 * np.log(2 * np.pi * noise**2)
+        self._prefactor_white = self.prefactor
+        self.correlation = None
         self.xarr = xarr
         self.data = data
         self.size = int(xarr.shape[0])
@@ -350,6 +352,21 @@ class Spectrum:
         self.nu_max = float(xarr[self.size - 1])
         self._pred = np.zeros_like(data)
         self._lnL = None
+
+
+    def set_correlation(self, pair):
+        """The normalisation of a likelihood with correlated channel noise: `prefactor` is the white-noise
+        value minus ln det R / 2, R the correlation matrix of the AR(2) process with autocorrelations `pair` = (rho_1,
+        rho_2); None or (0, 0): the white-noise value again.  A runner's `set_correlation` calls this."""
+        if pair is None or (pair[0] == 0.0 and pair[1] == 0.0):
+            self.correlation, self.prefactor = None, self._prefactor_white
+            return
+        r1, r2 = float(pair[0]), float(pair[1])
+        den = 1.0 - r1 * r1
+        phi1, phi2 = r1 * (1.0 - r2) / den, (r2 - r1 * r1) / den
+        v = 1.0 - phi1 * r1 - phi2 * r2
+        self.correlation = (r1, r2)
+        self.prefactor = self._prefactor_white - 0.5 * ((self.size - 2) * np.log(v) + np.log(den))
 
 
 class HyperfineSpectrum(Spectrum):

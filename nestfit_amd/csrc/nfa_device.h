@@ -139,13 +139,24 @@ struct SpecDev {
     // s^2 of the spectrum's gain g ~ N(1, s^2), shared by all pixels.  Such a set always has chan_w, wdata and bl (a
     // zeroed record, bl_order -1, without a baseline) and runs the LNL_K_CALIB kind.
     const double  *cal2;
+    // Spectra sets whose channel noise is correlated along the spectral axis (nfa_specset_set_correlation; null
+    // without): n_c = sigma_c eps_c, eps the unit-variance AR(2) process of the spectrum's (rho_1, rho_2), whose correlation
+    // matrix R has a pentadiagonal inverse.  With u = sigma_ref / sigma_c, Q = diag(u) R^-1 diag(u) and chi^2 = (d - p)^T Q (d - p):
+    // chan_w then holds Q's diagonal and wdata = Q d (the set's own u^2 stay in its buffer behind them), corr_q1[j] = Q[j][j+1] and
+    // corr_q2[j] = Q[j][j+2], 0 beyond the spectrum's end, [n_pix][chan_tot] like `data`; corr_coef [n_spec][NFA_CORR_NC], the
+    // entries of R^-1 (corr_setup_kernel).  Such a set runs lnl_kernel_corr.
+    const double  *corr_q1, *corr_q2, *corr_coef;
 };
+// entries of R^-1 of a spectrum: its diagonal at channels 0 and N-1, 1 and N-2, and between; its first off-diagonal at
+// (0, 1) and (N-2, N-1), and between; its second off-diagonal
+#define NFA_CORR_NC 6
 
 // Baseline record of a (pixel, spectrum), DESIGN 4.5: [0, 4) m_k(d) = sum_j w_j P_k(u_j) d_j, the Legendre moments of the
 // data; [4, 14) L^-1 packed by rows (L00, L10, L11, L20, ...), G = L L^T the Gram matrix G_kl = sum_j w_j P_k(u_j) P_l(u_j)
 // of the basis P_0..P_order.  A direction the Cholesky factorisation drops (pivot <= 1e-12 G_kk) and the orders above
 // bl_order have zero rows and columns, so that ||L^-1 e||^2 is the weighted least-squares fit of e over the rest.
 #define NFA_BL_REC 16
+#define NFA_CORR_ROW 62        // channels a row of a correlated set advances by: 64 lanes less the halo of two
 
 // P_1..P_3 of u = (2 j - (N - 1)) / (N - 1), ui = 1 / (N - 1) (0 for N = 1: u = 0); P_0 = 1
 __device__ __forceinline__ void bl_basis(int j, int N, double ui, double &p1, double &p2, double &p3) {
@@ -285,6 +296,14 @@ __device__ __forceinline__ double wave_sum(double v) {
     v += dpp_move<0x141>(v);     // row_half_mirror
     v += dpp_move<0x140>(v);     // row_mirror
     return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
+}
+
+// The value of the next lane (lane 63: 0): one DPP wave shift per register half, no LDS traffic
+__device__ __forceinline__ double wave_shl1(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, true);      // wave_shl:1, bound_ctrl: the last lane reads 0
+    hi = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
 }
 
 __device__ __forceinline__ double wave_excl_scan(double v, int lane, double *total) {
@@ -857,8 +876,15 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // CALIB (the baseline form in the general component form only): the spectrum's gain g ~ N(1, s^2), s^2 = SpecDev.cal2, is
 // integrated out in closed form.  The row step forms one more sum, cal_acc = sum w p^2, by chi^2's rule; chi^2
 // and the moments keep their operations, so the epilogue's chi^2_1 has the baseline form's bits and s = 0 returns them.
+// CORR (the weighted form in the general component form only): channel noise correlated along the spectrum,
+// chi^2 = (d - p)^T Q (d - p) with Q pentadiagonal.  chan_w is Q's diagonal and wdata = Q d, so the weighted term is the
+// diagonal part; what is new is 2 sum_j p_j (q1_j p_{j+1} + q2_j p_{j+2}), for which a lane must see its neighbours' model
+// values.  A row therefore advances by NFA_CORR_ROW = 62 channels and lanes 62 and 63 are a halo: they evaluate the model at
+// the next row's first two channels and own nothing -- no term of the sum, no store of spectra out.  Every neighbour product
+// lies inside one wave, whatever part or wave holds the next row: no LDS, no barrier, and the per-lane, per-part, part-order
+// summation rule (hence the independence of the bits from the split and the batch) stands.
 template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false,
-          bool LAYER = false, bool CALIB = false>
+          bool LAYER = false, bool CALIB = false, bool CORR = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -1045,7 +1071,10 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     // spectrum), formed once (SpecDev.totsq); the second has a term only where the model is not zero -- rows no
     // line window touches are never read, and a lane outside every window adds pred (...) = 0 to its row's sum
     double acc = 0.0;
-    const int n_rows = (ablate & 4) ? 0 : (N + 63) >> 6;
+    const int n_rows = (ablate & 4) ? 0 : CORR ? (N + NFA_CORR_ROW - 1) / NFA_CORR_ROW : (N + 63) >> 6;
+    // CORR: the lane owns its channel (lanes 62, 63: the halo); the off-diagonals of Q of the (pixel, spectrum)
+    const bool owner = !CORR || lane < NFA_CORR_ROW;
+    const double *q1s = CORR ? S.corr_q1 + p_ix * S.chan_tot + off : nullptr, *q2s = CORR ? S.corr_q2 + p_ix * S.chan_tot + off : nullptr;
     const int parts_per_wave = LNL_PARTS >> split_log2;
     double tot = 0.0;
     constexpr bool SPEC_DEFER = WRITE_SPEC && MODE == 2;
@@ -1056,6 +1085,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     static_assert(!FILL || (NCOMP == 0 && !DYN), "a filling factor: the general component form of the batch kernels");
     static_assert(!LAYER || (NCOMP == 0 && !DYN), "layered transfer: the general component form of the batch kernels");
     static_assert(!CALIB || (BASELINE && NCOMP == 0 && !DYN), "a calibration uncertainty: the baseline form in the general component form");
+    static_assert(!CORR || (WEIGHTED && !BASELINE && NCOMP == 0 && !DYN), "correlated noise: the weighted form in the general component form");
     constexpr int NBL = BASELINE ? NFA_BL_NB : 1;
     double bl_acc[NBL], bl_tot[NBL];
 #pragma unroll
@@ -1069,7 +1099,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
 #pragma unroll
     for (int k = 0; k < NBL; ++k) bl_acc[k] = 0.0;
     for (int row = h; row < n_rows; row += LNL_PARTS) {
-        const int r0 = row << 6;
+        const int r0 = CORR ? row * NFA_CORR_ROW : row << 6;           // (CORR: the hit masks below still test [r0, r0 + 64))
         const int j = r0 + lane;
         const float jf = (float)j;                                 // FASTN: the window test runs in fp32
         // lines of each component that touch this row
@@ -1100,7 +1130,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
         // Spectra out (main.py:1106-1113, 1182-1188): a row no line window touches is zeros, written without reading the row
         // (write-once data, past the caches: non-temporal).
         if (WRITE_SPEC && !any) {
-            if (j < N) __builtin_nontemporal_store(0.0, so + j);
+            if (j < N && owner) __builtin_nontemporal_store(0.0, so + j);
             continue;
         }
         if (any) {
@@ -1109,6 +1139,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
             const double xj = *(const double *)((const char *)xs + jo);
             const double dj = *(const double *)((const char *)ds + jo);
             const double wj = WEIGHTED ? *(const double *)((const char *)ws + jo) : 1.0;
+            const double q1j = CORR ? *(const double *)((const char *)q1s + jo) : 0.0, q2j = CORR ? *(const double *)((const char *)q2s + jo) : 0.0;
             double p3;
             // T0 tbg of the channel; T0 and tbg themselves are read inside the rare pass that needs them (y(T0) not a single
             // table cell): carried through the row as "maybe loaded" values they cost two register copies per row
@@ -1340,8 +1371,18 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     component(c, mask, Dk[dko + DK_KIND], tb_class(Dk[dko + DK_KIND]), Dk[dko + DK_A0X], Dk[dko + DK_B0X]);
                 }
             }
-            if (SPEC_DEFER) { pend_v = pred; pend_j = valid ? j : -1; }
-            else if (WRITE_SPEC) { if (valid) __builtin_nontemporal_store(pred, so + j); }
+            if (SPEC_DEFER) { pend_v = pred; pend_j = valid && owner ? j : -1; }
+            else if (WRITE_SPEC) { if (valid && owner) __builtin_nontemporal_store(pred, so + j); }
+            if constexpr (CORR) {
+                // The model at channels j + 1 and j + 2: the values of lanes + 1 and + 2 (all lanes are here: `any` is the
+                // wave's), a halo lane's taken from nowhere and never used.  A halo lane's own value then leaves the sums: its
+                // channel belongs to the next row.  Lanes beyond N have pred = 0, so Q's entries across a spectrum's end
+                // (stored as 0 besides) multiply nothing.
+                const double pn1 = wave_shl1(pred), pn2 = wave_shl1(pn1);
+                if (!owner) pred = 0.0;
+                acc = __builtin_fma(pred, __builtin_fma(-2.0, dj, wj * pred), acc);
+                acc = __builtin_fma(2.0 * pred, __builtin_fma(q1j, pn1, q2j * pn2), acc);
+            } else
             // lanes beyond N: pred = 0
             if (any) acc = __builtin_fma(pred, __builtin_fma(-2.0, dj, WEIGHTED ? wj * pred : pred), acc);
             if (BASELINE && any) {                                 // (lanes beyond N and masked channels: w p = 0)
@@ -1455,6 +1496,22 @@ lnl_kernel_kind(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
              (KIND & LNL_K_LAYER) != 0, (KIND & LNL_K_CALIB) != 0>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
+// The kernels of a set with CORRELATED channel noise (nfa_specset_set_correlation): the weighted form in the
+// general component form with lnl_body's CORR flag, 32 instances over (MODE, WRITE_SPEC, WIDE, FILL, LAYER) beside the table
+// of kinds (which stays at its 32 kinds).  launch_lnl takes them for such a set with the weighted form's plan: the same waves,
+// LDS and workgroups.  No unrolled component loop, no queue, no w8, no fused form.
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_corr(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, FILL, LAYER, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared,
+                                                                                     blockIdx.x, &grp);
+}
+
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one
 // 51 KB copy of the product tables, and in lnl_kernel the wave slots of the waves that are done stay empty until the
 // longest of the sixteen is: units differ by the widths of their lines, and at the metric's shape 4.5 of 8 waves per
@@ -1473,7 +1530,7 @@ lnl_kernel_kind(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
 #define NFA_QUEUE_WORDS  (2 * NFA_QUEUE_STRIDE)
 struct QueueArgs { SpecDev S; BatchGroup grp; const double *D; double *part; double *spec_out; long B; LnlGeom G; const double *g_tabs; };
 // (the argument segment places every argument at the next multiple of its alignment: 8 for all of these, so the struct's
-// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 904, 1016, 1024, 1032, 1040, 1048, 1088)
+// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 928, 1040, 1048, 1056, 1064, 1072, 1112)
 static_assert(sizeof(SpecDev) % 8 == 0 && sizeof(BatchGroup) % 8 == 0 && sizeof(LnlGeom) % 8 == 0 && alignof(SpecDev) == 8 &&
               alignof(BatchGroup) == 8 && alignof(LnlGeom) == 8, "QueueArgs must mirror the kernel argument segment");
 template <bool WRITE_SPEC, int NCOMP>
@@ -1684,6 +1741,44 @@ __device__ __forceinline__ void null_lnz_body(const SpecDev &S, long n_pix, doub
 }
 __global__ void null_lnz_kernel(SpecDev S, long n_pix, double *__restrict__ out) { null_lnz_body<false>(S, n_pix, out); }
 __global__ void null_lnz_w_kernel(SpecDev S, long n_pix, double *__restrict__ out) { null_lnz_body<true>(S, n_pix, out); }
+
+// Correlated channel noise, pixels [pix0, pix0 + n_pix): Q = diag(u) R^-1 diag(u), u = sqrt(w) of the set's own
+// weights `w` (u^2 = (sigma_ref / sigma_c)^2; 1 for a scalar noise), R^-1 from the spectrum's NFA_CORR_NC entries.  form_q: the
+// bands q0 (the diagonal), q1, q2 (0 where j + 1, j + 2 lie beyond the spectrum); always wdata = Q d, five terms in the fixed
+// order j, j + 1, j - 1, j + 2, j - 2 (nfa_specset_set_data forms only that again).  One lane per channel.
+__device__ __forceinline__ double corr_diag(const double *c, int j, int N) { return j == 0 || j == N - 1 ? c[0] : j == 1 || j == N - 2 ? c[1] : c[2]; }
+__device__ __forceinline__ double corr_off1(const double *c, int j, int N) { return j < 0 || j > N - 2 ? 0.0 : j == 0 || j == N - 2 ? c[3] : c[4]; }
+__device__ __forceinline__ double corr_off2(const double *c, int j, int N) { return j < 0 || j > N - 3 ? 0.0 : c[5]; }
+__global__ void corr_setup_kernel(SpecDev S, long pix0, long n_pix, const double *__restrict__ w, double *__restrict__ q0,
+                                  double *__restrict__ q1, double *__restrict__ q2, double *__restrict__ wdata, int form_q) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix * S.chan_tot) return;
+    const long p = pix0 + i / S.chan_tot;
+    const int c = (int)(i - (p - pix0) * S.chan_tot);
+    int s = 0;
+    while (s + 1 < S.n_spec && c >= S.off[s + 1]) ++s;
+    const int j = c - S.off[s], N = S.size[s];
+    const long k = p * S.chan_tot + c;
+    const double *cf = S.corr_coef + s * NFA_CORR_NC;
+    // u of channels j - 2 .. j + 2 (0 outside the spectrum) and the data there
+    double u[5], d[5];
+#pragma unroll
+    for (int o = -2; o <= 2; ++o) {
+        const bool in = j + o >= 0 && j + o < N;
+        u[o + 2] = in ? sqrt(w[k + o]) : 0.0;
+        d[o + 2] = in ? S.data[k + o] : 0.0;
+    }
+    const double a0 = w[k] * corr_diag(cf, j, N);
+    const double a1 = u[2] * u[3] * corr_off1(cf, j, N), a2 = u[2] * u[4] * corr_off2(cf, j, N);
+    const double b1 = u[1] * u[2] * corr_off1(cf, j - 1, N), b2 = u[0] * u[2] * corr_off2(cf, j - 2, N);
+    if (form_q) { q0[k] = a0; q1[k] = a1; q2[k] = a2; }
+    double v = a0 * d[2];
+    v = __builtin_fma(a1, d[3], v);
+    v = __builtin_fma(b1, d[1], v);
+    v = __builtin_fma(a2, d[4], v);
+    v = __builtin_fma(b2, d[0], v);
+    wdata[k] = v;
+}
 
 // Baseline records (SpecDev.bl, NFA_BL_REC) of pixels [pix0, pix0 + n_pix): one wave per (pixel, spectrum).  m_k(d) =
 // sum_j wdata_j P_k(u_j) always; with form_basis also the Gram matrix G_kl = sum_j w_j P_k P_l of P_0..P_order, its

@@ -217,6 +217,12 @@ struct nfa_specset {
     bool    bl_w1 = false;                          // a baseline or a calibration on a scalar noise: d_w (== 1) and d_wdata were made for it
     double *d_cal2 = nullptr;                       // a calibration uncertainty: SpecDev.cal2 (nfa_specset_set_calibration)
     double  h_cal[MAXSPEC] = {};                    // ... the caller's fractional 1-sigma values
+    bool    masked = false;                         // a noise per channel with a masked channel (w = 0) somewhere
+    // correlated channel noise (nfa_specset_set_correlation): Q's diagonal (SpecDev.chan_w while it lasts; d_w keeps u^2) and
+    // off-diagonals, the entries of R^-1 per spectrum, the caller's (rho_1, rho_2)
+    double *d_q0 = nullptr, *d_q1 = nullptr, *d_q2 = nullptr, *d_corr = nullptr;
+    double  h_rho[MAXSPEC][2] = {};
+    bool    corr_w1 = false;                        // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
 };
 
 struct nfa_priors {
@@ -420,6 +426,15 @@ static int launch_chan_weight(nfa_specset *ss, int64_t pix0, int64_t n, bool for
     return NFA_OK;
 }
 
+// correlated channel noise: wdata = Q d of pixels [pix0, pix0 + n) (form_q: Q's bands too) from the set's own weights in d_w
+static int launch_corr_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_q) {
+    const int64_t items = n * ss->dev.chan_tot;
+    hipLaunchKernelGGL(corr_setup_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, 0, ss->dev,
+                       (long)pix0, (long)n, (const double *)ss->d_w, ss->d_q0, ss->d_q1, ss->d_q2, ss->d_wdata, (int)form_q);
+    HIP_TRY(hipGetLastError());
+    return NFA_OK;
+}
+
 // baseline records of pixels [pix0, pix0 + n) (form_basis: the Gram matrix and L^-1 too, not only m(d))
 static int launch_bl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_basis) {
     const int64_t waves = n * ss->dev.n_spec;
@@ -603,6 +618,7 @@ static int specset_create_channel_noise(nfa_specset **out, int model, int n_spec
         tot += sizes[s];
     }
     std::vector<double> ref((size_t)(n_pix * n_spec));
+    bool masked = false;
     for (int64_t p = 0; p < n_pix; ++p) {
         int64_t c = p * tot;
         for (int s = 0; s < n_spec; ++s) {
@@ -610,7 +626,7 @@ static int specset_create_channel_noise(nfa_specset **out, int model, int n_spec
             for (int64_t j = 0; j < sizes[s]; ++j, ++c) {
                 const double sg = chan_noise[c];
                 if (!(sg > 0)) return fail(NFA_ERR_ARG, "channel noise must be > 0 (NaN is not allowed; inf masks the channel)");
-                if (sg == INFINITY) continue;
+                if (sg == INFINITY) { masked = true; continue; }
                 if (std::isnan(data[c])) return fail(NFA_ERR_ARG, "NaN data in a channel that is not masked (channel noise inf masks it)");
                 lo = std::min(lo, sg);
             }
@@ -618,7 +634,9 @@ static int specset_create_channel_noise(nfa_specset **out, int model, int n_spec
             ref[(size_t)(p * n_spec + s)] = lo;
         }
     }
-    return specset_create(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, ref.data(), chan_noise, lines);
+    const int rc = specset_create(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, ref.data(), chan_noise, lines);
+    if (rc == NFA_OK) (*out)->masked = masked;
+    return rc;
 }
 int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
                                      const int32_t *trans_ids, const double *rest_freqs,
@@ -943,6 +961,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq);
     (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl); (void)hipFree(ss->d_lines);
     (void)hipFree(ss->d_cal2);
+    (void)hipFree(ss->d_q0); (void)hipFree(ss->d_q1); (void)hipFree(ss->d_q2); (void)hipFree(ss->d_corr);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
@@ -953,7 +972,8 @@ int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data) {
     int rc = engine_init(); if (rc) return rc;
     HIP_TRY(hipMemcpy(ss->d_data + pix * ss->dev.chan_tot, data, sizeof(double) * ss->dev.chan_tot,
                       hipMemcpyHostToDevice));
-    if (ss->dev.chan_w) { rc = launch_chan_weight(ss, pix, 1, false); if (rc) return rc; }      // the mask stays
+    if (ss->dev.corr_q1) { rc = launch_corr_setup(ss, pix, 1, false); if (rc) return rc; }      // Q stays, Q d again
+    else if (ss->dev.chan_w) { rc = launch_chan_weight(ss, pix, 1, false); if (rc) return rc; }      // the mask stays
     rc = launch_rowsq(ss, pix, 1); if (rc) return rc;
     return ss->dev.bl ? launch_bl_setup(ss, pix, 1, false) : NFA_OK;                             // the basis stays
 }
@@ -1005,6 +1025,7 @@ static int specset_form_records(nfa_specset *ss) {
 int nfa_specset_set_baseline(nfa_specset *ss, int order) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
     if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
+    if (order >= 0 && ss->dev.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no baseline");
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     const int was = ss->dev.bl_order;
@@ -1028,6 +1049,7 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
             return fail(NFA_ERR_ARG, "a calibration uncertainty is a finite fraction in [0, 1] per spectrum");
         any = any || cal[s] > 0.0;
     }
+    if (any && d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no calibration uncertainty");
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any) {                                               // null, or all zeros: the set's former kernels and bits
@@ -1060,6 +1082,116 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
 int nfa_specset_calibration(const nfa_specset *ss, double *out) {
     if (!ss || !ss->dev.cal2) return 0;
     for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->h_cal[s];
+    return 1;
+}
+
+// The entries of R^-1 (NFA_CORR_NC of them) of the unit-variance AR(2) process with autocorrelations (r1, r2) by Yule-Walker;
+// null if the pair is outside the domain, `why` then says how
+static bool corr_coef(double r1, double r2, double *c, const char **why) {
+    if (!std::isfinite(r1) || !std::isfinite(r2)) { *why = "a noise correlation is a pair of finite numbers (rho_1, rho_2) per spectrum"; return false; }
+    if (!(std::fabs(r1) < 1.0)) { *why = "a noise correlation needs |rho_1| < 1"; return false; }
+    if (!(r2 > 2.0 * r1 * r1 - 1.0 && r2 < 1.0)) { *why = "a noise correlation needs 2 rho_1^2 - 1 < rho_2 < 1 (a positive definite correlation matrix)"; return false; }
+    const double den = 1.0 - r1 * r1;
+    const double f1 = r1 * (1.0 - r2) / den, f2 = (r2 - r1 * r1) / den;
+    const double v = 1.0 - f1 * r1 - f2 * r2;
+    if (!(v >= 0.01)) { *why = "a noise correlation needs an innovations variance v >= 0.01: the noise is nearly determined by its neighbours"; return false; }
+    c[0] = 1.0 / v; c[1] = (1.0 + f1 * f1) / v; c[2] = (1.0 + f1 * f1 + f2 * f2) / v;
+    c[3] = -f1 / v; c[4] = -f1 * (1.0 - f2) / v; c[5] = -f2 / v;
+    return true;
+}
+
+// The set without a correlation again: its own weights behind chan_w, wdata = w d and the sums of w d^2 (a scalar noise:
+// no weights at all), bit for bit what the set was created with
+static int corr_remove(nfa_specset *ss) {
+    SpecDev &d = ss->dev;
+    (void)hipFree(ss->d_q0); (void)hipFree(ss->d_q1); (void)hipFree(ss->d_q2); (void)hipFree(ss->d_corr);
+    ss->d_q0 = ss->d_q1 = ss->d_q2 = ss->d_corr = nullptr;
+    d.corr_q1 = d.corr_q2 = d.corr_coef = nullptr;
+    for (int s = 0; s < MAXSPEC; ++s) ss->h_rho[s][0] = ss->h_rho[s][1] = 0.0;
+    if (ss->corr_w1) {
+        (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata);
+        ss->d_w = ss->d_wdata = nullptr; d.chan_w = d.wdata = nullptr;
+        ss->corr_w1 = false;
+    } else if (ss->d_w) {
+        d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
+        int rc = launch_chan_weight(ss, 0, ss->n_pix, false); if (rc) return rc;
+    } else {                              // a scalar noise whose weights were never made (the first allocation failed): nothing to form
+        d.chan_w = d.wdata = nullptr;
+    }
+    return launch_rowsq(ss, 0, ss->n_pix);
+}
+
+// Q's bands, Q d and the sums d^T Q d for the pairs rho[n_spec][2] (their entries of R^-1 in coef)
+static int corr_apply(nfa_specset *ss, const double *rho, const double (*coef)[NFA_CORR_NC]) {
+    SpecDev &d = ss->dev;
+    const size_t n = (size_t)(ss->n_pix * d.chan_tot);
+    if (!ss->d_w) {                       // a scalar noise: u == 1
+        double *w = nullptr, *wdata = nullptr;                // both, or neither
+        HIP_TRY(hipMalloc(&w, sizeof(double) * n));
+        if (hipMalloc(&wdata, sizeof(double) * n) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(w); return fail(NFA_ERR_DEVICE, "out of device memory for the channel weights"); }
+        ss->d_w = w; ss->d_wdata = wdata;
+        ss->corr_w1 = true;
+        std::vector<double> one(n, 1.0);
+        HIP_TRY(hipMemcpy(ss->d_w, one.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    }
+    if (!ss->d_q0) HIP_TRY(hipMalloc(&ss->d_q0, sizeof(double) * n));
+    if (!ss->d_q1) HIP_TRY(hipMalloc(&ss->d_q1, sizeof(double) * n));
+    if (!ss->d_q2) HIP_TRY(hipMalloc(&ss->d_q2, sizeof(double) * n));
+    if (!ss->d_corr) HIP_TRY(hipMalloc(&ss->d_corr, sizeof(double) * NFA_CORR_NC * MAXSPEC));
+    HIP_TRY(hipMemcpy(ss->d_corr, coef, sizeof(double) * NFA_CORR_NC * d.n_spec, hipMemcpyHostToDevice));
+    d.chan_w = ss->d_q0; d.wdata = ss->d_wdata;
+    d.corr_q1 = ss->d_q1; d.corr_q2 = ss->d_q2; d.corr_coef = ss->d_corr;
+    for (int s = 0; s < d.n_spec; ++s) { ss->h_rho[s][0] = rho[2 * s]; ss->h_rho[s][1] = rho[2 * s + 1]; }
+    int rc = launch_corr_setup(ss, 0, ss->n_pix, true); if (rc) return rc;
+    return launch_rowsq(ss, 0, ss->n_pix);
+}
+
+int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    SpecDev &d = ss->dev;
+    double coef[MAXSPEC][NFA_CORR_NC];
+    bool any = false;
+    for (int s = 0; rho && s < d.n_spec; ++s) {
+        const double r1 = rho[2 * s], r2 = rho[2 * s + 1];
+        if (r1 == 0.0 && r2 == 0.0) {                         // white noise in this spectrum: R = 1
+            const double white[NFA_CORR_NC] = {1.0, 1.0, 1.0, 0.0, 0.0, 0.0};
+            memcpy(coef[s], white, sizeof white);
+            continue;
+        }
+        const char *why = nullptr;
+        if (!corr_coef(r1, r2, coef[s], &why)) return fail(NFA_ERR_ARG, why);
+        any = true;
+    }
+    if (any) {
+        for (int s = 0; s < d.n_spec; ++s)
+            if (d.size[s] < 4) return fail(NFA_ERR_ARG, "a noise correlation needs spectra of 4 channels and more");
+        if (ss->masked) return fail(NFA_ERR_ARG, "a set with a masked channel takes no noise correlation");
+        if (d.bl_order >= 0) return fail(NFA_ERR_ARG, "a set with a baseline takes no noise correlation");
+        if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no noise correlation");
+    }
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    if (!any) return d.corr_q1 ? corr_remove(ss) : NFA_OK;    // null, or all zeros: the set's former kernels and bits
+    const bool had = d.corr_q1 != nullptr;
+    double was[MAXSPEC][2];
+    memcpy(was, ss->h_rho, sizeof was);
+    rc = corr_apply(ss, rho, coef);
+    if (rc) {                                                 // the set stays as it was: its former pairs, or none
+        const std::string why = g_err;
+        double old[MAXSPEC][NFA_CORR_NC];
+        const char *w2 = nullptr;
+        for (int s = 0; had && s < d.n_spec; ++s)
+            if (was[s][0] == 0.0 && was[s][1] == 0.0) { old[s][0] = old[s][1] = old[s][2] = 1.0; old[s][3] = old[s][4] = old[s][5] = 0.0; }
+            else (void)corr_coef(was[s][0], was[s][1], old[s], &w2);
+        if (had) (void)corr_apply(ss, &was[0][0], old); else (void)corr_remove(ss);
+        g_err = why;
+    }
+    return rc;
+}
+
+int nfa_specset_correlation(const nfa_specset *ss, double *out) {
+    if (!ss || !ss->dev.corr_q1) return 0;
+    for (int s = 0; out && s < ss->dev.n_spec; ++s) { out[2 * s] = ss->h_rho[s][0]; out[2 * s + 1] = ss->h_rho[s][1]; }
     return 1;
 }
 
@@ -1477,6 +1609,22 @@ static LnlKernel lnl_kernel_of(int mode, bool write_spec, int ncomp, const LnlPl
     return lnl_kernel_at(lnl_inst_index({mode, write_spec, P.wide, lnl_plan_ncomp(P, ncomp), lnl_plan_kind(P)}), P.form,
                          std::make_index_sequence<LNL_INSTANCES>());
 }
+// The kernel of a set with correlated channel noise: lnl_kernel_corr over (mode, spectra out, wide, filled, layered), beside
+// the table (its launches are on no entry of it, so count_lnl_launch counts none of them)
+template <int I>     // I: bit 4 layered, bit 3 filled, bit 2 fast mode, bit 1 spectra out, bit 0 wide
+static LnlKernel lnl_kernel_corr_inst() {
+    return lnl_kernel_corr<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_corr_at(int i, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])() = {lnl_kernel_corr_inst<(int)I>...};
+    return inst[i]();
+}
+static LnlKernel lnl_kernel_corr_of(int mode, bool write_spec, const LnlPlan &P) {
+    if (P.form != LNL_WEIGHTED) return nullptr;               // the weighted form's plan: waves, LDS, workgroups
+    return lnl_kernel_corr_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
+                              std::make_index_sequence<32>());
+}
 #ifdef NFA_TEST_HOOKS
 #include <atomic>
 // Likelihood launches by (lnl_inst_index, LnlForm) since the last reset (nfa_test_lnl_launches): host side, counted where
@@ -1508,7 +1656,7 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
+    const LnlKernel kern = S.corr_q1 ? lnl_kernel_corr_of(mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
 #ifdef NFA_TEST_HOOKS
     count_lnl_launch(kern);
@@ -1720,7 +1868,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
     const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
-                                     S.cal2 != nullptr);
+                                     S.cal2 != nullptr, S.corr_q1 != nullptr);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

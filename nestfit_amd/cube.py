@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_layered, gain_fit
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_correlation, check_layered, gain_fit
 from .core import _as_inplace_matrix
 
 
@@ -49,11 +49,14 @@ class CubeRunner:
     calibration : None, or the fractional 1-sigma uncertainty of the spectra's intensity scales (a number, or one per
         spectrum, each in [0, 1]; shared by all pixels), integrated out of the likelihood per (pixel, spectrum) in closed
         form; null_lnZ is unchanged
+    correlation : None, or the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis (a pair
+        such as `HANNING` or `ar1(rho)`, or an array [n_spec, 2]; shared by all pixels) for cubes that were smoothed, regridded
+        or oversampled; not with masked channels, a baseline or a calibration; null_lnZ follows
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
                  model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False,
-                 calibration=None):
+                 calibration=None, correlation=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
@@ -64,6 +67,9 @@ class CubeRunner:
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered, model)                      # before any device call
         calibration = check_calibration(calibration, len(xarrs))
+        sizes = [np.size(x) for x in xarrs]
+        masked = np.shape(noise)[-1] == sum(sizes) and not np.all(np.isfinite(noise))
+        correlation = check_correlation(correlation, len(xarrs), sizes, masked, baseline_order, calibration)
         if species is None and int(model) == 4 and lines is not None:
             from .lte import LteBand, LteBlend, LteLines, lines_species
             lines = list(lines)
@@ -82,6 +88,8 @@ class CubeRunner:
             self._ss.set_baseline(baseline_order)
         if calibration is not None:
             self._ss.set_calibration(calibration)
+        if correlation is not None:
+            self._ss.set_correlation(correlation)
         self._data, self._noise = data, noise                # (fit_baseline, fit_gain)
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -154,6 +162,17 @@ class CubeRunner:
             resid = np.where(w > 0, data[:, sl] - spec[:, sl], 0.0)
             out[:, sl] = baseline_fit(resid, w, self.baseline_order)
         return out
+
+    @property
+    def correlation(self):
+        """None, or the float64 array [n_spec, 2] of the spectra's noise autocorrelations (rho_1, rho_2)."""
+        corr = self._ss.correlation
+        return None if corr is None else corr.copy()
+
+    def set_correlation(self, corr):
+        """Sets (a pair, or one per spectrum) or removes (None, zeros) the noise correlation; null_lnZ follows."""
+        self._ss.set_correlation(corr)
+        self.null_lnZ = self._ss.null_lnZ().sum(axis=1)
 
     @property
     def calibration(self):

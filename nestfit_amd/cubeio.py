@@ -286,6 +286,35 @@ class NoiseCube(_Noise):
         return np.broadcast_to(self.data.reshape(1, -1), (np.size(lon), self.data.size))
 
 
+def estimate_correlation(cube, line_free):
+    """(rho_1, rho_2) of the channel noise along the spectral axis, estimated from channels without line emission and
+    pooled over the pixels: what `correlation=` of a runner takes for a cube that was smoothed, regridded or oversampled
+    (DESIGN 4.13).  cube: a `DataCube`, or an array whose LAST axis is the channels (`DataCube.data`: [lon, lat, chan]);
+    line_free: a boolean mask of the channels, or a slice or index array into them.  Per pixel the mean of its line-free
+    channels is taken off; rho_k = sum of x_c x_{c+k} over the pairs of line-free channels k apart, over all pixels, divided
+    by the like sum of squares scaled to as many terms.  Pixels with a NaN in a line-free channel are left out.  A noise
+    whose sigma varies along the axis should be divided by its sigma first.  numpy on the host."""
+    data = np.asarray(getattr(cube, 'data', cube), dtype=np.float64)
+    n = data.shape[-1]
+    keep = np.zeros(n, dtype=bool)
+    keep[line_free] = True
+    if keep.sum() < 8:
+        raise ValueError('estimate_correlation needs 8 line-free channels and more')
+    x = data.reshape(-1, n)
+    x = x[np.all(np.isfinite(x[:, keep]), axis=1)]
+    if x.shape[0] == 0:
+        raise ValueError('estimate_correlation: no pixel without a NaN in its line-free channels')
+    x = np.where(keep, x - x[:, keep].mean(axis=1, keepdims=True), 0.0)
+    c0 = np.sum(x * x) / (keep.sum() * x.shape[0])
+    rho = []
+    for k in (1, 2):
+        pairs = keep[:-k] & keep[k:]
+        if not pairs.any():
+            raise ValueError(f'estimate_correlation: no two line-free channels {k} apart')
+        rho.append(float(np.sum(x[:, :-k] * x[:, k:]) / (pairs.sum() * x.shape[0]) / c0))
+    return tuple(rho)
+
+
 # celestial keywords a two-dimensional map product inherits from the cube
 _MAP_KEYWORDS = ('SIMPLE', 'BITPIX', 'NAXIS', 'NAXIS1', 'NAXIS2', 'WCSAXES') + tuple(
     f'{stem}{axis}' for stem in ('CRPIX', 'CDELT', 'CUNIT', 'CTYPE', 'CRVAL') for axis in (1, 2)) + ('RADESYS', 'EQUINOX')

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import sampler
-from ._model import check_calibration, check_layered
+from ._model import check_calibration, check_correlation, check_layered
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
@@ -80,6 +80,9 @@ class CubeFitter:
         # a calibration uncertainty per spectrum (runner_kwargs['calibration']): checked here as well
         cubes = getattr(stack, 'cubes', None)
         self.calibration = check_calibration(self.runner_kwargs.get('calibration'), None if cubes is None else len(cubes))
+        # correlated channel noise (runner_kwargs['correlation']): and this
+        self.correlation = check_correlation(self.runner_kwargs.get('correlation'), None if cubes is None else len(cubes),
+                                             baseline_order=self.runner_kwargs.get('baseline_order'), calibration=self.calibration)
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
         self.lnZ_thresh, self.ncomp_max, self.nlive_snr_fact = lnZ_thresh, ncomp_max, nlive_snr_fact
         self.nlive_quantum = max(1, int(nlive_quantum))

@@ -7,7 +7,7 @@ radiative-transfer pass.
 import numpy as np
 
 from . import core
-from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_layered, par_names
+from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_layered, spec_data_sizes_masked, par_names
 
 N_PARAMS = 3
 
@@ -33,19 +33,21 @@ class GaussianRunner(EngineRunner):
     MODEL = MODEL_GAUSSIAN
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectrum, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None):
+    def __init__(self, spectrum, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         check_layered(layered, MODEL_GAUSSIAN)                        # ValueError for True: no optical depth, nothing absorbs
         self.spectrum = spectrum
         self._setup([spectrum], utrans, ncomp, rest_freqs=[float(spectrum.rest_freq)], baseline_order=baseline_order,
-                    calibration=calibration)
+                    calibration=calibration, correlation=correlation)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         check_layered(kwargs.get('layered', False), MODEL_GAUSSIAN)
         check_calibration(kwargs.get('calibration'), 1)
+        check_correlation(kwargs.get('correlation'), 1, *spec_data_sizes_masked([spec_data]),
+                          baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         return cls(Spectrum(*spec_data), utrans, **kwargs)
 
     def get_spectrum(self):

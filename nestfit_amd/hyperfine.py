@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _ffi
 from ._model import (MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, EngineRunner, EngineSpectrumMixin,
-                     check_baseline_order, check_calibration, check_layered, par_names)
+                     check_baseline_order, check_calibration, check_correlation, check_layered, spec_data_sizes_masked, par_names)
 from .core import HyperfineSpectrum as _HyperfineBase
 
 N_PARAMS = 4
@@ -133,13 +133,13 @@ class HyperfineRunner(EngineRunner):
     MODEL = MODEL_HYPERFINE
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration)
+                    calibration=calibration, correlation=correlation)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -147,6 +147,8 @@ class HyperfineRunner(EngineRunner):
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         check_layered(kwargs.get('layered', False))
         check_calibration(kwargs.get('calibration'), len(spec_data))
+        check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
+                          baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         spectra = np.array([HyperfineSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

@@ -24,6 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import hdf5
+from ._model import check_calibration, check_correlation
 
 HDF5_SUFFIXES = ('.hdf', '.h5', '.hdf5')
 
@@ -432,11 +433,15 @@ class HdfStore:
             self.hdf.attrs['layered'] = True
         # a calibration uncertainty per spectrum integrated out of the likelihood (runner_kwargs['calibration']):
         # root attribute `calibration`, float64 [n_spec].  A store without it was fitted without one.
-        from ._model import check_calibration
         cubes = getattr(getattr(fitter, 'stack', None), 'cubes', None)
         cal = check_calibration((getattr(fitter, 'runner_kwargs', None) or {}).get('calibration'), None if cubes is None else len(cubes))
         if cal is not None:
             self.hdf.attrs['calibration'] = cal
+        # channel noise correlated along the spectral axis (runner_kwargs['correlation']): root attribute
+        # `noise_correlation`, float64 [n_spec, 2], the pairs (rho_1, rho_2).  A store without it was fitted with white noise.
+        corr = check_correlation((getattr(fitter, 'runner_kwargs', None) or {}).get('correlation'), None if cubes is None else len(cubes))
+        if corr is not None:
+            self.hdf.attrs['noise_correlation'] = corr
         quantum = getattr(fitter, 'nlive_quantum', 1)
         if quantum != 1:                 # a deviation from main.py:445-447 is written down where the results are
             self.hdf.attrs['nlive_quantum'] = int(quantum)
@@ -462,6 +467,14 @@ class HdfStore:
         assert self.is_open
         cal = self.hdf.attrs.get('calibration')
         return None if cal is None else np.asarray(cal, dtype=np.float64)
+
+    def read_model_correlation(self):
+        """The autocorrelations (rho_1, rho_2) of the channel noise of every spectrum the store was fitted with
+        (`runner_kwargs={'correlation': ...}`): the root attribute `noise_correlation` as a float64 array [n_spec, 2]; None
+        for a store without it."""
+        assert self.is_open
+        corr = self.hdf.attrs.get('noise_correlation')
+        return None if corr is None else np.asarray(corr, dtype=np.float64).reshape(-1, 2)
 
     def read_model_fill(self):
         """Whether the store was fitted with a beam filling factor per component (`LteMix(species, fill=True)`): the root
