@@ -39,6 +39,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "nfa_line_window.h"   // the quotients behind a line's channel window: the reference's sequence and the short form
 #include "nfa_launch_plan.h"   // the layout constants (MAXSPEC, SM_*, LNL_PARTS, NFA_BL_NB, NFA_GROUP_MAX) and LnlGeom
 
 #define MAXCOMP   10          // ResolvedPlacementPrior's own limit (core.pyx:399)
@@ -265,6 +266,19 @@ __device__ __forceinline__ int group_of(const BatchGroup &g, long b) {
     return c;
 }
 
+// group_of for the likelihood kernels' item index, which lies below 2^28 (the host keeps B * nspec * split below 2^28, so
+// k * each < 2^31 too), in 32-bit integer arithmetic of the scalar unit.  An ordered 64-bit compare has no scalar form, and
+// group_of's seven are vector compares, each with a select and a v_readfirstlane behind it (a 32-bit compare's truth value
+// takes the same way into the sum) -- per unit, on the pipe that bounds the table mode.
+__device__ __forceinline__ int group_of_u32(const BatchGroup &g, unsigned b) {
+    if (g.n <= 1) return 0;
+    const unsigned each = (unsigned)g.each;
+    int c = 0;
+#pragma unroll
+    for (unsigned k = 1; k < NFA_GROUP_MAX; ++k) c += (int)((k * each - 1u - b) >> 31);      // b >= k each: the difference's sign bit
+    return c;
+}
+
 #define NFA_TRACE_WAVES 8192   // waves the queue kernel's trace buffer holds (test library, nfa_test_queue_trace)
 // ---------------------------------------------------------------------------
 //  wave-level helpers
@@ -469,7 +483,12 @@ __device__ __forceinline__ double nf_partition_level(int j, double trot, const d
 // hf_freq is `hfreq` (LineRow.hfreq)
 // (reference: nestfit/models/hyperfine.pyx:70-91).  Plain double arithmetic,
 // no contraction: the floor() arguments must round like the reference's.
+// SHORT_CUTOFF (the table mode's line set-up): the window's quotients with the cut-off as 5 |hf_width| (nfa_line_window.h: one
+// multiplication where the reference's sequence is a division and a square root, per line and unit), and the reference's
+// sequence for the whole wave where a lane's quotient lies too near an integer for that to prove the same floor() -- one line
+// in 10^10.  The same windows, always.
 struct LineConst { double nucen, idenom; int lo, hi; };
+template <bool SHORT_CUTOFF = false>
 __device__ __forceinline__ LineConst nf_line(int t, const double *__restrict__ hfreq, int i, double v_over_c, double s_over_c, double nu0,
                                              double nu_min, double nu_chan, int N, double r_chan = 0.0) {
     LineConst r;
@@ -481,6 +500,15 @@ __device__ __forceinline__ LineConst nf_line(int t, const double *__restrict__ h
     // the Gaussian model forms its centre as rest_freq * (1 - voff / CKMS) (gaussian.pyx:33)
     const double hf_nucen  = t == NFA_T_GAUSS ? nu0 * (1 - v_over_c) : hf_freq - hf_offset;
     const double hf_idenom = 0.5 / (hf_width * hf_width);
+    double q_lo, q_hi;
+    if constexpr (SHORT_CUTOFF) {
+        const double a_cen = hf_nucen - nu_min;              // (hf_nucen - nu_min -+ nu_cutoff, left to right: hyperfine.pyx:77)
+        const bool same = nf_window_quot_short(a_cen, hf_width, nu_chan, r_chan, q_lo, q_hi);
+        if (__builtin_amdgcn_ballot_w64(!same) != 0ull) {
+            asm volatile("" ::: "memory");                    // keep the rare sequence a branch
+            nf_window_quot_ref(a_cen, hf_idenom, nu_chan, r_chan, q_lo, q_hi);
+        }
+    } else {
     const double nu_cutoff = sqrt(12.5 / hf_idenom);
     const double nu_lo = (hf_nucen - nu_min - nu_cutoff);
     const double nu_hi = (hf_nucen - nu_min + nu_cutoff);
@@ -488,7 +516,6 @@ __device__ __forceinline__ LineConst nf_line(int t, const double *__restrict__ h
     // r = RN(1 / nu_chan), q = a r, e = a - nu_chan q (exact, fused), x = q + e r is RN(a / nu_chan) -- Markstein's
     // final step, as in the Tb pass (the same bits as the division; the host passes r = 0 for a width whose mantissa
     // is all ones, the one case the theorem leaves out; a centre that is not finite ends as an empty window either way)
-    double q_lo, q_hi;
     if (r_chan != 0.0) {
         const double ql = nu_lo * r_chan, qh = nu_hi * r_chan;
         q_lo = __builtin_fma(__builtin_fma(-nu_chan, ql, nu_lo), r_chan, ql);
@@ -496,6 +523,7 @@ __device__ __forceinline__ LineConst nf_line(int t, const double *__restrict__ h
     } else {
         q_lo = nu_lo / nu_chan;
         q_hi = nu_hi / nu_chan;
+    }
     }
     // (long) floor(.) of both, `continue` on an empty window, clipping to the spectrum (hyperfine.pyx:78-86) -- in
     // doubles, then ONE conversion each: the integers are below 2^31 once they are clipped, and a double converts to a
@@ -956,7 +984,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     long p_ix = 0;
     double *so = WRITE_SPEC ? spec_out + b * S.chan_tot + off : nullptr;     // spectra out: the unit's model spectrum
     if (grp) {                                                    // batch kernels: the item's batch of the group has the pixels
-        const int c = group_of(*grp, b);
+        const int c = MODE == 0 ? group_of_u32(*grp, bu) : group_of(*grp, b);
         const int *pp = grp->pix[c];
         if (pp) p_ix = (long)__builtin_amdgcn_readfirstlane(pp[b - c * grp->each]);
         if (WRITE_SPEC && grp->spec[0]) so = grp->spec[c] + (b - c * grp->each) * S.chan_tot + off;     // every batch its own array
@@ -973,7 +1001,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
         double r_nucen = 0.0, r_idenom = 0.0, r_htau = 0.0;
         int r_lo = 0, r_len = 0, slot = p;
         if (i < nhf) {
-            const LineConst lc = nf_line(t, lrow->hfreq, i, D[b * drec + c * 4 + 2], D[b * drec + c * 4 + 1], nu0, S.nu_min[s],
+            const LineConst lc = nf_line<MODE == 0>(t, lrow->hfreq, i, D[b * drec + c * 4 + 2], D[b * drec + c * 4 + 1], nu0, S.nu_min[s],
                                          S.nu_chan[s], N, S.r_chan[s]);
             int lo = lc.lo;
             const int hi = lc.hi;
@@ -1167,6 +1195,9 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     asm volatile("" : "+v"(lbase));
                 }
                 tau_t tau = 0;
+                // (table mode: ONE zero per (row, component).  Left to itself the compiler forms it before the branch around
+                // the odd line and a second time inside it.)
+                if (MODE == 0) asm volatile("" : "+v"(tau));
                 double td = 0.0;                                      // WIDE: fp64 running sum
                 typedef double v2d __attribute__((ext_vector_type(2)));
                 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -1261,7 +1292,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                 // are in no window: tau == 0 there too)
                 const unsigned long long livem = MODE == 2 ? __builtin_amdgcn_fcmpf((float)tau, 0.0f, NF_FCMP_UNE)
                                                            : __builtin_amdgcn_fcmp((double)tau, 0.0, NF_FCMP_UNE);
-                if (livem == 0ull) return;
+                if (MODE == 0 ? __builtin_expect(livem == 0ull, 0) : livem == 0ull) return;
                 // (the class is tested through a copy the compiler cannot see through: left to itself it makes one switch of
                 // the chain below and the structured form of that costs a dozen scalar instructions on the way to the usual case)
                 // (fast mode: the class from the record's double where it is used, as round 4 had it -- one scalar register per
@@ -1272,7 +1303,16 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                 // FILL: the component's beam filling factor (the same in the record of every spectrum)
                 double ff = 1.0;
                 if constexpr (FILL) ff = Dk[4 * ncomp + (c * nspec + s) * DREC_CS + DK_FILL];
-                if (cls_hot == 1) {
+                // Table mode: every class hands its two factors to ONE multiply-add behind the chain, pred <- fx fy + pred.  The
+                // usual class: fx = T0 (y - tbg), fy = 1 - FastExp(tau).  The rare classes, whose reference order is a rounded
+                // product added to pred: fx = that product, fy = 1.0 -- fx * 1.0 + pred rounds once, like the addition: the same
+                // bits.  (With an update of pred in every class the classes' results met in a register of their own, and the
+                // usual class paid two 64-bit moves per (row, component) on its way through the join.)
+                // (the rare classes' 1.0 through a copy the compiler cannot see through, or it forms the constant on the usual
+                // class's way)
+                auto rare_one = [&]() { double one = 1.0; asm volatile("" : "+v"(one)); return one; };
+                auto tb_pass = [&](double &fx, double &fy) -> bool {
+                if (MODE == 0 ? __builtin_expect(cls_hot == 1, 1) : cls_hot == 1) {
                     // The band lies in ONE cell of the 1/(e^x - 1) table (hyperfine.pyx:23-45; the usual case, first in the
                     // chain: one scalar compare and a branch between the optical depth and the pass): the cell's
                     // straight line in x = T0 / tex is a straight line in the channel's frequency, and
@@ -1288,12 +1328,14 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     if constexpr (LAYER) g -= pred;                   // the layer absorbs what lies behind it, over the
                     if constexpr (FILL) g *= ff;                      // fraction of the beam it fills: ((g - pred) f) a
                     if (MODE == 2) pred = __builtin_fma(g, one_minus_fastexp_f32((float)tau, livem), pred);
-                    else pred = __builtin_fma(g, MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm), pred);
-                    return;
+                    else if (MODE == 0) { fx = g; fy = one_minus_fastexp_table_row((double)tau); return true; }
+                    else pred = __builtin_fma(g, nf_one_minus_fastexp_row<MODE>((double)tau, sm), pred);
+                    return false;
                 }
                 if (cls == 3) {                                       // gaussian.pyx:50: pred += peak * e
+                    if (MODE == 0) { fx = (double)tau; fy = rare_one(); return true; }
                     pred += (double)tau;                              // tau == 0 adds nothing
-                    return;
+                    return false;
                 }
                 const int dko = 4 * ncomp + (c * nspec + s) * DREC_CS;
                 if (MODE == 2) {
@@ -1346,16 +1388,22 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                         double g = T0 * (y - tbg);
                         if constexpr (LAYER) g -= pred;
                         if constexpr (FILL) g *= ff;
-                        pred += g * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
+                        if (MODE == 0) { fx = g * one_minus_fastexp_table_row((double)tau); fy = rare_one(); return true; }
+                        pred += g * nf_one_minus_fastexp_row<MODE>((double)tau, sm);
                     } else {
                         const double y = nf_iemtex(x, g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
                         double g = T0 * (y - tbg);
                         if constexpr (LAYER) g -= pred;
                         if constexpr (FILL) g *= ff;
                         const double tb = g * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
+                        if (MODE == 0) { fx = !(tau == 0) ? tb : 0.0; fy = rare_one(); return true; }
                         pred += !(tau == 0) ? tb : 0.0;
                     }
                 }
+                return false;
+                };
+                double fx, fy;
+                if (tb_pass(fx, fy)) pred = __builtin_fma(fx, fy, pred);
             };
             if (NCOMP > 0) {
 #pragma unroll

@@ -61,7 +61,7 @@ __global__ void test_partition_kernel(const double *trot, double *qpara, double 
 __global__ void test_windows_kernel(SpecDev S, int s, double voff, double sigm, int *lo, int *hi) {
     const int t = S.trans[s] - 1, i = threadIdx.x;
     if (i >= S.lines[s].nhf) return;
-    const LineConst lc = nf_line(t, S.lines[s].hfreq, i, voff / NFA_CKMS, sigm / NFA_CKMS, S.rest[s], S.nu_min[s], S.nu_chan[s],
+    const LineConst lc = nf_line<true>(t, S.lines[s].hfreq, i, voff / NFA_CKMS, sigm / NFA_CKMS, S.rest[s], S.nu_min[s], S.nu_chan[s],
                                  S.size[s]);
     lo[i] = lc.lo; hi[i] = lc.hi;
 }
