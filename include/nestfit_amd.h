@@ -357,6 +357,27 @@ int nfa_specset_calibration(const nfa_specset *ss, double *out);
 int nfa_specset_set_correlation(nfa_specset *ss, const double *rho);
 /* 1 and out[n_spec][2] = the pairs set (out may be null), or 0 for a set without a noise correlation (and for null) */
 int nfa_specset_correlation(const nfa_specset *ss, double *out);
+/* The channel response of the spectrometer (Hanning smoothing, regridding): the operation that correlates the noise also
+ * convolves the signal.  taps[n_spec][5] = (h_-2, h_-1, h_0, h_1, h_2) per spectrum in units of channels, shared by all
+ * pixels; a response of three taps has zero ends.  The model that enters the likelihood is then
+ *     p~_j = sum_{k = -2..2} h_k p_{j+k},    p_i := 0 for i < 0 and i >= N,
+ * p the model spectrum at the channel centres, and everything downstream takes p~ for p: lnL = -(d - p~)^T Q (d - p~) /
+ * (2 sigma_ref^2) with nfa_specset_set_correlation's Q, or diag(w) or 1 without a correlation; spectra out (predict_batch)
+ * are p~.  nfa_specset_null_lnz does not change (p = 0 gives p~ = 0).  A line within two channels of a band end loses the
+ * part of the response that reaches beyond it.
+ * taps = NULL or the identity (0, 0, 1, 0, 0) in every spectrum removes the response (the set's former kernels and results
+ * bit for bit); the identity beside real responses is an unfiltered spectrum.  NFA_ERR_ARG, the set left as it was: a tap
+ * that is not finite, |sum h - 1| > 1e-9 (a response conserves the integrated intensity), h_0 <= 0, a spectrum of fewer than
+ * 4 channels; a set with a masked channel (channel noise inf), a baseline or a calibration uncertainty -- and
+ * nfa_specset_set_baseline (order >= 0) and nfa_specset_set_calibration (a value > 0) refuse a set with a response likewise.
+ * It goes with and without nfa_specset_set_correlation, in either order.  Every model, filled and layered sets too.
+ * Like nfa_specset_set_correlation it launches held batches first, synchronises the device and drops the runners' captured
+ * single-point graphs: call it between batches.  nfa_specset_set_data keeps it.  Such sets go through the batch kernels (the
+ * general component form); single points and a broker's handful too, and nfa_ring_serve_device refuses their runners ("the
+ * resident kernel has no form for a channel response: use nfa_ring_serve"). */
+int nfa_specset_set_response(nfa_specset *ss, const double *taps);
+/* 1 and out[n_spec][5] = the taps set (out may be null), or 0 for a set without a channel response (and for null) */
+int nfa_specset_response(const nfa_specset *ss, double *out);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

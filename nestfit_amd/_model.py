@@ -134,6 +134,76 @@ def check_correlation(corr, n_spec=None, sizes=None, masked=False, baseline_orde
     return out
 
 
+HANNING_RESPONSE = (0.25, 0.5, 0.25)  # the Hanning kernel as a channel response: `response=HANNING_RESPONSE`
+RESP_SUM_TOL = 1e-9                   # how far the taps of a channel response may miss the sum 1
+
+
+def check_response(resp, n_spec=None, sizes=None, masked=False, baseline_order=None, calibration=None):
+    """`response` of a runner: the channel response of the spectrometer, an odd number of taps, 3 or 5, (h_-T .. h_0 .. h_T)
+    in units of channels; the model that meets the data is sum_k h_k p_{j+k}.  None for none; one response
+    applies to all `n_spec` spectra; an array [n_spec, 3 | 5] gives one per spectrum (a one-dimensional value is always ONE
+    response).  Every tap is finite, the taps sum to 1 within 1e-9 and h_0 > 0; (0, 1, 0) is an unfiltered spectrum, and
+    the identity everywhere is None.  A response goes with neither a masked channel (`masked`), a baseline
+    (`baseline_order`) nor a calibration uncertainty (`calibration`), and needs spectra of 4 channels and more (`sizes`).
+    Returns None or a float64 array [n_spec, 5] ([1, 5] without n_spec), three taps padded with zero ends; ValueError
+    otherwise.  Needs no device."""
+    if resp is None:
+        return None
+    what = 'response must be None, 3 or 5 taps (h_-T .. h_T) or an array [n_spec, 3 | 5] of such taps'
+    if isinstance(resp, (list, tuple)) and len(resp) > 0 and all(isinstance(r, (list, tuple, np.ndarray)) and np.ndim(r) == 1 and
+                                                                 len(r) in (3, 5) for r in resp):
+        resp = [[0.0, *r, 0.0] if len(r) == 3 else list(r) for r in resp]      # responses of three and of five taps side by side
+    try:
+        out = np.array(resp, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}, not {resp!r}') from None
+    if isinstance(resp, np.ndarray) and resp.dtype.kind not in 'iuf':
+        raise ValueError(f'{what}, not {resp!r}')
+    if out.ndim == 1 and out.shape[0] in (3, 5):
+        out = np.tile(out, (1 if n_spec is None else int(n_spec), 1))
+    elif out.ndim != 2 or out.shape[1] not in (3, 5) or out.shape[0] == 0:
+        raise ValueError(f'{what}, not {resp!r}')
+    elif n_spec is not None and out.shape[0] != int(n_spec):
+        raise ValueError(f'{what}: {out.shape[0]} responses for {int(n_spec)} spectra')
+    if not np.all(np.isfinite(out)):
+        raise ValueError(f'{what}: every tap finite, not {resp!r}')
+    if out.shape[1] == 3:
+        out = np.pad(out, ((0, 0), (1, 1)))
+    for h in out:
+        if not abs(float(np.sum(h)) - 1.0) <= RESP_SUM_TOL:
+            raise ValueError(f'channel response: the taps sum to 1 (it conserves the integrated intensity), not {float(np.sum(h))!r}')
+        if not h[2] > 0.0:
+            raise ValueError(f'channel response: the central tap is > 0, not {float(h[2])!r}')
+    if np.all(out == np.array([0.0, 0.0, 1.0, 0.0, 0.0])):
+        return None
+    if sizes is not None and np.any(np.asarray(sizes) < 4):
+        raise ValueError('a channel response needs spectra of 4 channels and more')
+    if masked:
+        raise ValueError('a channel response does not go with masked channels (channel noise inf)')
+    if baseline_order is not None and baseline_order != -1:
+        raise ValueError('a channel response does not go with a baseline (baseline_order)')
+    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
+        raise ValueError('a channel response does not go with a calibration uncertainty (calibration)')
+    return np.ascontiguousarray(out)
+
+
+def correlation_of_response(taps):
+    """The pair (rho_1, rho_2) = (sum_j h_j h_{j+1}, sum_j h_j h_{j+2}) / sum_j h_j^2 that smoothing WHITE noise with the
+    taps `h` (3 or 5 of them, one response) produces: `correlation=` beside `response=taps` for a cube whose signal and
+    noise were smoothed together.  `correlation_of_response(HANNING_RESPONSE)` is `HANNING`."""
+    h = np.asarray(taps, dtype=np.float64)
+    if h.ndim != 1 or h.shape[0] not in (3, 5):
+        raise ValueError(f'correlation_of_response takes one response of 3 or 5 taps, not {taps!r}')
+    c0 = float(np.sum(h * h))
+    return (float(np.sum(h[:-1] * h[1:])) / c0, float(np.sum(h[:-2] * h[2:])) / c0)
+
+
+def smoothed(taps):
+    """`{'response': taps, 'correlation': correlation_of_response(taps)}`: a cube smoothed with `taps` after the noise was
+    white, to splat into a runner's `from_data` or a `CubeFitter`'s `runner_kwargs`."""
+    return {'response': taps, 'correlation': correlation_of_response(taps)}
+
+
 def spec_data_sizes_masked(spec_data):
     """(sizes, masked) of `from_data`'s rows [xarr, data, noise, ...] for `check_correlation`: the channels of every spectrum, and
     whether any channel noise masks a channel (inf).  numpy only."""
@@ -308,7 +378,15 @@ class _SpecSet:
         self.layered = False
         self.calibration = None
         self.correlation = None
+        self.response = None
         self.masked = bool(self.per_channel and not np.all(np.isfinite(noise)))
+
+    def set_response(self, resp):
+        """The channel response of the spectra (`check_response`'s argument), or none (None, the identity):
+        nfa_specset_set_response.  null_lnZ() does not change."""
+        resp = check_response(resp, self.n_spec, self.sizes, self.masked, self.baseline_order, self.calibration)
+        _ffi.check(_ffi.load().nfa_specset_set_response(self.handle, None if resp is None else _ffi.dptr(resp)))
+        self.response = resp
 
     def set_correlation(self, corr):
         """The autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis (`check_correlation`'s argument),
@@ -322,6 +400,8 @@ class _SpecSet:
         """A calibration uncertainty per spectrum, integrated out of the likelihood (`check_calibration`'s argument), or
         none (None, zeros): nfa_specset_set_calibration.  null_lnZ() does not change."""
         cal = check_calibration(cal, self.n_spec)
+        if cal is not None and self.response is not None:
+            raise ValueError('a calibration uncertainty does not go with a channel response (response)')
         if cal is not None and self.correlation is not None:
             raise ValueError('a calibration uncertainty does not go with a noise correlation (correlation)')
         _ffi.check(_ffi.load().nfa_specset_set_calibration(self.handle, None if cal is None else _ffi.dptr(cal)))
@@ -338,6 +418,8 @@ class _SpecSet:
         """A polynomial baseline of degree <= `order` per (pixel, spectrum) profiled out of the likelihood, or none
         (None / -1): nfa_specset_set_baseline.  null_lnZ() then is the baseline-only model's."""
         order = check_baseline_order(order)
+        if order is not None and self.response is not None:
+            raise ValueError('a baseline does not go with a channel response (response)')
         if order is not None and self.correlation is not None:
             raise ValueError('a baseline does not go with a noise correlation (correlation)')
         _ffi.check(_ffi.load().nfa_specset_set_baseline(self.handle, -1 if order is None else order))
@@ -455,8 +537,11 @@ class EngineRunner(Runner):
     N_MODEL = 6
 
     def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False,
-               calibration=None, correlation=None):
-        """correlation: None, or the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis -- a
+               calibration=None, correlation=None, response=None):
+        """response: None, or the channel response of the spectrometer -- 3 or 5 taps for all spectra (`HANNING_RESPONSE`) or
+        an array [n_spec, 3 | 5] -- with which the model is convolved before it meets the data (nfa_specset_set_response,
+        DESIGN 4.14); the identity is None.  Not with masked channels, a baseline or a calibration.  null_lnZ is unchanged.
+        correlation: None, or the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis -- a
         pair for all spectra (`HANNING`, `ar1(rho)`) or an array [n_spec, 2] -- for cubes that were smoothed, regridded or
         oversampled (nfa_specset_set_correlation); all zeros is None.  Not with masked channels, a baseline or a
         calibration.  null_lnZ is then d^T Q d's, and the spectra's `prefactor` gains -ln det R / 2.
@@ -476,6 +561,8 @@ class EngineRunner(Runner):
         calibration = check_calibration(calibration, len(spectra))
         check_correlation(correlation, len(spectra), [s.size for s in spectra],
                           any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
+        check_response(response, len(spectra), [s.size for s in spectra],
+                       any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -509,6 +596,21 @@ class EngineRunner(Runner):
             self._ss.set_calibration(calibration)
         if correlation is not None:
             self.set_correlation(correlation)
+        if response is not None:
+            self.set_response(response)
+
+    @property
+    def response(self):
+        """None, or the float64 array [n_spec, 5] of the spectra's channel responses (h_-2 .. h_2)."""
+        resp = self._ss.response
+        return None if resp is None else resp.copy()
+
+    def set_response(self, resp):
+        """Sets (3 or 5 taps, or such a row per spectrum) or removes (None, the identity) the channel response of this
+        runner's spectra; null_lnZ is untouched.  The spectra's private one-spectrum sets stay unfiltered: `predict(params)`
+        leaves the unsmoothed model in the spectra; the runner's `loglikelihood`, `loglikelihood_batch` and `predict_batch`
+        are the filtered ones."""
+        self._ss.set_response(resp)
 
     @property
     def correlation(self):

@@ -147,6 +147,12 @@ struct SpecDev {
     // corr_q2[j] = Q[j][j+2], 0 beyond the spectrum's end, [n_pix][chan_tot] like `data`; corr_coef [n_spec][NFA_CORR_NC], the
     // entries of R^-1 (corr_setup_kernel).  Such a set runs lnl_kernel_corr.
     const double  *corr_q1, *corr_q2, *corr_coef;
+    // Spectra sets with a channel response (nfa_specset_set_response; null without): [n_spec][NFA_RESP_NT], the
+    // taps h_-2 .. h_2 of every spectrum (three taps: zero ends; an unfiltered spectrum beside filtered ones: 0, 0, 1, 0, 0).
+    // The model that meets the data is p~_j = sum_k h_k p_{j+k}, p = 0 beyond the spectrum's ends.  Such a set always has
+    // chan_w, wdata, corr_q1, corr_q2 and corr_coef (the white entries 1, 1, 1, 0, 0, 0 without a correlation) and runs
+    // lnl_kernel_resp.
+    const double  *resp;
 };
 // entries of R^-1 of a spectrum: its diagonal at channels 0 and N-1, 1 and N-2, and between; its first off-diagonal at
 // (0, 1) and (N-2, N-1), and between; its second off-diagonal
@@ -158,6 +164,8 @@ struct SpecDev {
 // bl_order have zero rows and columns, so that ||L^-1 e||^2 is the weighted least-squares fit of e over the rest.
 #define NFA_BL_REC 16
 #define NFA_CORR_ROW 62        // channels a row of a correlated set advances by: 64 lanes less the halo of two
+#define NFA_RESP_NT 5          // taps of a channel response as they are stored
+#define NFA_RESP_ROW 58        // channels a row of a set with a response advances by: 64 lanes less 2 * 2 of the filter less that halo
 
 // P_1..P_3 of u = (2 j - (N - 1)) / (N - 1), ui = 1 / (N - 1) (0 for N = 1: u = 0); P_0 = 1
 __device__ __forceinline__ void bl_basis(int j, int N, double ui, double &p1, double &p2, double &p3) {
@@ -911,8 +919,13 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // the next row's first two channels and own nothing -- no term of the sum, no store of spectra out.  Every neighbour product
 // lies inside one wave, whatever part or wave holds the next row: no LDS, no barrier, and the per-lane, per-part, part-order
 // summation rule (hence the independence of the bits from the split and the batch) stands.
+// RESP (the CORR form only): a channel response, p~_j = sum_k h_k p_{j+k} over k = -2..2 in p's place.  A row
+// advances by NFA_RESP_ROW = 58 channels.  Lane l EVALUATES the model at channel j_e = 58 row - 2 + l (0 outside [0, N)) and,
+// after four more wave shifts and five multiply-adds in the fixed order k = -2..2, HOLDS p~ of channel j_o = 58 row + l:
+// lanes 0..57 own j_o (data, Q, spectra out there), lanes 58, 59 are CORR's halo of p~, lanes 60..63 hold nothing.  x, T0
+// and tbg are read at j_e, everything else at j_o.  Still no LDS, no barrier, and the same summation rule.
 template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false,
-          bool LAYER = false, bool CALIB = false, bool CORR = false>
+          bool LAYER = false, bool CALIB = false, bool CORR = false, bool RESP = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -1099,9 +1112,17 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     // spectrum), formed once (SpecDev.totsq); the second has a term only where the model is not zero -- rows no
     // line window touches are never read, and a lane outside every window adds pred (...) = 0 to its row's sum
     double acc = 0.0;
-    const int n_rows = (ablate & 4) ? 0 : CORR ? (N + NFA_CORR_ROW - 1) / NFA_CORR_ROW : (N + 63) >> 6;
+    constexpr int ROW_STEP = RESP ? NFA_RESP_ROW : CORR ? NFA_CORR_ROW : 64;
+    const int n_rows = (ablate & 4) ? 0 : CORR ? (N + ROW_STEP - 1) / ROW_STEP : (N + 63) >> 6;
     // CORR: the lane owns its channel (lanes 62, 63: the halo); the off-diagonals of Q of the (pixel, spectrum)
-    const bool owner = !CORR || lane < NFA_CORR_ROW;
+    const bool owner = !CORR || lane < ROW_STEP;
+    // RESP: the spectrum's taps, uniform over the unit
+    double rh[NFA_RESP_NT];
+    if constexpr (RESP) {
+        const k_dbl_p hs = (k_dbl_p)(S.resp + s * NFA_RESP_NT);
+#pragma unroll
+        for (int k = 0; k < NFA_RESP_NT; ++k) rh[k] = hs[k];
+    }
     const double *q1s = CORR ? S.corr_q1 + p_ix * S.chan_tot + off : nullptr, *q2s = CORR ? S.corr_q2 + p_ix * S.chan_tot + off : nullptr;
     const int parts_per_wave = LNL_PARTS >> split_log2;
     double tot = 0.0;
@@ -1114,6 +1135,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     static_assert(!LAYER || (NCOMP == 0 && !DYN), "layered transfer: the general component form of the batch kernels");
     static_assert(!CALIB || (BASELINE && NCOMP == 0 && !DYN), "a calibration uncertainty: the baseline form in the general component form");
     static_assert(!CORR || (WEIGHTED && !BASELINE && NCOMP == 0 && !DYN), "correlated noise: the weighted form in the general component form");
+    static_assert(!RESP || CORR, "a channel response: the correlated form (white coefficients without a correlation)");
     constexpr int NBL = BASELINE ? NFA_BL_NB : 1;
     double bl_acc[NBL], bl_tot[NBL];
 #pragma unroll
@@ -1127,8 +1149,11 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
 #pragma unroll
     for (int k = 0; k < NBL; ++k) bl_acc[k] = 0.0;
     for (int row = h; row < n_rows; row += LNL_PARTS) {
-        const int r0 = CORR ? row * NFA_CORR_ROW : row << 6;           // (CORR: the hit masks below still test [r0, r0 + 64))
+        // (CORR: the hit masks below still test [r0, r0 + 64); RESP: that is the evaluated range, which starts two channels
+        // before the row's own, and j is the channel the lane evaluates the model at, jw the one whose p~ it holds)
+        const int r0 = RESP ? row * ROW_STEP - 2 : CORR ? row * ROW_STEP : row << 6;
         const int j = r0 + lane;
+        const int jw = RESP ? j + 2 : j;
         const float jf = (float)j;                                 // FASTN: the window test runs in fp32
         // lines of each component that touch this row
         unsigned long long hitm[NC];
@@ -1158,16 +1183,18 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
         // Spectra out (main.py:1106-1113, 1182-1188): a row no line window touches is zeros, written without reading the row
         // (write-once data, past the caches: non-temporal).
         if (WRITE_SPEC && !any) {
-            if (j < N && owner) __builtin_nontemporal_store(0.0, so + j);
+            if (jw < N && owner) __builtin_nontemporal_store(0.0, so + jw);
             continue;
         }
         if (any) {
-            const bool valid = j < N;
-            const unsigned jo = (unsigned)(valid ? j : N - 1) * 8u;           // byte offset of the lane's channel
+            const bool valid = RESP ? (unsigned)j < (unsigned)N : j < N;
+            const unsigned jo = (unsigned)(RESP ? (j < 0 ? 0 : j < N ? j : N - 1) : valid ? j : N - 1) * 8u;   // byte offset of the lane's channel
+            const bool validw = RESP ? jw < N : valid;             // RESP: ... and of the channel whose p~ it holds
+            const unsigned jwo = RESP ? (unsigned)(validw ? jw : N - 1) * 8u : jo;
             const double xj = *(const double *)((const char *)xs + jo);
-            const double dj = *(const double *)((const char *)ds + jo);
-            const double wj = WEIGHTED ? *(const double *)((const char *)ws + jo) : 1.0;
-            const double q1j = CORR ? *(const double *)((const char *)q1s + jo) : 0.0, q2j = CORR ? *(const double *)((const char *)q2s + jo) : 0.0;
+            const double dj = *(const double *)((const char *)ds + jwo);
+            const double wj = WEIGHTED ? *(const double *)((const char *)ws + jwo) : 1.0;
+            const double q1j = CORR ? *(const double *)((const char *)q1s + jwo) : 0.0, q2j = CORR ? *(const double *)((const char *)q2s + jwo) : 0.0;
             double p3;
             // T0 tbg of the channel; T0 and tbg themselves are read inside the rare pass that needs them (y(T0) not a single
             // table cell): carried through the row as "maybe loaded" values they cost two register copies per row
@@ -1419,8 +1446,22 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     component(c, mask, Dk[dko + DK_KIND], tb_class(Dk[dko + DK_KIND]), Dk[dko + DK_A0X], Dk[dko + DK_B0X]);
                 }
             }
-            if (SPEC_DEFER) { pend_v = pred; pend_j = valid && owner ? j : -1; }
-            else if (WRITE_SPEC) { if (valid && owner) __builtin_nontemporal_store(pred, so + j); }
+            if constexpr (RESP) {
+                // p~ of channel jw = j + 2 from the model at j .. j + 4, the values of this lane and the next four (all lanes
+                // are here: `any` is the wave's).  A lane outside [0, N) evaluated nothing: no window holds it, and the select
+                // says so.  fp64 and this order in both modes.  Lanes 60..63 miss a neighbour and a lane with jw >= N has no
+                // channel: their values leave below, before any sum or store sees them.
+                if (!valid) pred = 0.0;
+                const double e1 = wave_shl1(pred), e2 = wave_shl1(e1), e3 = wave_shl1(e2), e4 = wave_shl1(e3);
+                double pt = rh[0] * pred;
+                pt = __builtin_fma(rh[1], e1, pt);
+                pt = __builtin_fma(rh[2], e2, pt);
+                pt = __builtin_fma(rh[3], e3, pt);
+                pt = __builtin_fma(rh[4], e4, pt);
+                pred = validw ? pt : 0.0;
+            }
+            if (SPEC_DEFER) { pend_v = pred; pend_j = validw && owner ? jw : -1; }
+            else if (WRITE_SPEC) { if (validw && owner) __builtin_nontemporal_store(pred, so + jw); }
             if constexpr (CORR) {
                 // The model at channels j + 1 and j + 2: the values of lanes + 1 and + 2 (all lanes are here: `any` is the
                 // wave's), a halo lane's taken from nowhere and never used.  A halo lane's own value then leaves the sums: its
@@ -1560,6 +1601,21 @@ lnl_kernel_corr(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
                                                                                      blockIdx.x, &grp);
 }
 
+// The kernels of a set with a CHANNEL RESPONSE (nfa_specset_set_response): lnl_kernel_corr's form with lnl_body's
+// RESP flag, 32 more instances over the same five flags, beside the table like those.  launch_lnl takes them when SpecDev.resp
+// is set, with the weighted form's plan.  A response without a correlation runs them over white coefficients.
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_resp(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, FILL, LAYER, false, true, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm,
+                                                                                           n_shared, blockIdx.x, &grp);
+}
+
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one
 // 51 KB copy of the product tables, and in lnl_kernel the wave slots of the waves that are done stay empty until the
 // longest of the sixteen is: units differ by the widths of their lines, and at the metric's shape 4.5 of 8 waves per
@@ -1578,7 +1634,7 @@ lnl_kernel_corr(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
 #define NFA_QUEUE_WORDS  (2 * NFA_QUEUE_STRIDE)
 struct QueueArgs { SpecDev S; BatchGroup grp; const double *D; double *part; double *spec_out; long B; LnlGeom G; const double *g_tabs; };
 // (the argument segment places every argument at the next multiple of its alignment: 8 for all of these, so the struct's
-// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 928, 1040, 1048, 1056, 1064, 1072, 1112)
+// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1008, 1280, 1288, 1296, 1304, 1312, 1352)
 static_assert(sizeof(SpecDev) % 8 == 0 && sizeof(BatchGroup) % 8 == 0 && sizeof(LnlGeom) % 8 == 0 && alignof(SpecDev) == 8 &&
               alignof(BatchGroup) == 8 && alignof(LnlGeom) == 8, "QueueArgs must mirror the kernel argument segment");
 template <bool WRITE_SPEC, int NCOMP>

@@ -223,6 +223,10 @@ struct nfa_specset {
     double *d_q0 = nullptr, *d_q1 = nullptr, *d_q2 = nullptr, *d_corr = nullptr;
     double  h_rho[MAXSPEC][2] = {};
     bool    corr_w1 = false;                        // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
+    bool    has_corr = false;                       // ... some pair is not (0, 0): Q's arrays also serve a response alone, over white entries
+    // a channel response (nfa_specset_set_response): SpecDev.resp and the caller's taps
+    double *d_resp = nullptr;
+    double  h_resp[MAXSPEC][NFA_RESP_NT] = {};
 };
 
 struct nfa_priors {
@@ -962,6 +966,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl); (void)hipFree(ss->d_lines);
     (void)hipFree(ss->d_cal2);
     (void)hipFree(ss->d_q0); (void)hipFree(ss->d_q1); (void)hipFree(ss->d_q2); (void)hipFree(ss->d_corr);
+    (void)hipFree(ss->d_resp);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
@@ -1025,6 +1030,7 @@ static int specset_form_records(nfa_specset *ss) {
 int nfa_specset_set_baseline(nfa_specset *ss, int order) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
     if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
+    if (order >= 0 && ss->dev.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no baseline");
     if (order >= 0 && ss->dev.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no baseline");
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1049,6 +1055,7 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
             return fail(NFA_ERR_ARG, "a calibration uncertainty is a finite fraction in [0, 1] per spectrum");
         any = any || cal[s] > 0.0;
     }
+    if (any && d.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no calibration uncertainty");
     if (any && d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no calibration uncertainty");
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1146,20 +1153,61 @@ static int corr_apply(nfa_specset *ss, const double *rho, const double (*coef)[N
     return launch_rowsq(ss, 0, ss->n_pix);
 }
 
+static void corr_coef_white(double *c) { c[0] = c[1] = c[2] = 1.0; c[3] = c[4] = c[5] = 0.0; }
+
+// The device's state for the pairs rho[n_spec][2] (null: no correlation) and the taps resp[n_spec][NFA_RESP_NT] (null: no
+// response), both valid: neither -- the set's own weights and its former kernels; either -- Q's arrays, over the white entries
+// of R^-1 where there is no correlation, and the taps where there is a response
+static int qstate_apply(nfa_specset *ss, const double *rho, const double *resp) {
+    SpecDev &d = ss->dev;
+    if (!resp) {
+        (void)hipFree(ss->d_resp);
+        ss->d_resp = nullptr; d.resp = nullptr;
+        memset(ss->h_resp, 0, sizeof ss->h_resp);
+    }
+    ss->has_corr = rho != nullptr;
+    if (!rho && !resp) return d.corr_q1 ? corr_remove(ss) : NFA_OK;
+    double coef[MAXSPEC][NFA_CORR_NC], pairs[MAXSPEC][2] = {};
+    for (int s = 0; s < d.n_spec; ++s) {
+        const char *why = nullptr;
+        if (rho) { pairs[s][0] = rho[2 * s]; pairs[s][1] = rho[2 * s + 1]; }
+        if (pairs[s][0] == 0.0 && pairs[s][1] == 0.0) corr_coef_white(coef[s]);      // white noise in this spectrum: R = 1
+        else if (!corr_coef(pairs[s][0], pairs[s][1], coef[s], &why)) return fail(NFA_ERR_ARG, why);
+    }
+    if (resp) {
+        if (!ss->d_resp) HIP_TRY(hipMalloc(&ss->d_resp, sizeof(double) * NFA_RESP_NT * MAXSPEC));
+        HIP_TRY(hipMemcpy(ss->d_resp, resp, sizeof(double) * NFA_RESP_NT * d.n_spec, hipMemcpyHostToDevice));
+        if (resp != &ss->h_resp[0][0]) memcpy(ss->h_resp, resp, sizeof(double) * NFA_RESP_NT * d.n_spec);
+        d.resp = ss->d_resp;
+    }
+    return corr_apply(ss, &pairs[0][0], coef);
+}
+
+// qstate_apply, and after a failure the former state again (the failure's reason stays)
+static int qstate_change(nfa_specset *ss, const double *rho, const double *resp) {
+    const bool had_corr = ss->has_corr, had_resp = ss->dev.resp != nullptr;
+    double was_rho[MAXSPEC][2], was_resp[MAXSPEC][NFA_RESP_NT];
+    memcpy(was_rho, ss->h_rho, sizeof was_rho);
+    memcpy(was_resp, ss->h_resp, sizeof was_resp);
+    const int rc = qstate_apply(ss, rho, resp);
+    if (rc) {
+        const std::string why = g_err;
+        (void)qstate_apply(ss, had_corr ? &was_rho[0][0] : nullptr, had_resp ? &was_resp[0][0] : nullptr);
+        g_err = why;
+    }
+    return rc;
+}
+
 int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
     SpecDev &d = ss->dev;
-    double coef[MAXSPEC][NFA_CORR_NC];
+    double coef[NFA_CORR_NC];
     bool any = false;
     for (int s = 0; rho && s < d.n_spec; ++s) {
         const double r1 = rho[2 * s], r2 = rho[2 * s + 1];
-        if (r1 == 0.0 && r2 == 0.0) {                         // white noise in this spectrum: R = 1
-            const double white[NFA_CORR_NC] = {1.0, 1.0, 1.0, 0.0, 0.0, 0.0};
-            memcpy(coef[s], white, sizeof white);
-            continue;
-        }
+        if (r1 == 0.0 && r2 == 0.0) continue;                 // white noise in this spectrum: R = 1
         const char *why = nullptr;
-        if (!corr_coef(r1, r2, coef[s], &why)) return fail(NFA_ERR_ARG, why);
+        if (!corr_coef(r1, r2, coef, &why)) return fail(NFA_ERR_ARG, why);
         any = true;
     }
     if (any) {
@@ -1171,27 +1219,54 @@ int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
-    if (!any) return d.corr_q1 ? corr_remove(ss) : NFA_OK;    // null, or all zeros: the set's former kernels and bits
-    const bool had = d.corr_q1 != nullptr;
-    double was[MAXSPEC][2];
-    memcpy(was, ss->h_rho, sizeof was);
-    rc = corr_apply(ss, rho, coef);
-    if (rc) {                                                 // the set stays as it was: its former pairs, or none
-        const std::string why = g_err;
-        double old[MAXSPEC][NFA_CORR_NC];
-        const char *w2 = nullptr;
-        for (int s = 0; had && s < d.n_spec; ++s)
-            if (was[s][0] == 0.0 && was[s][1] == 0.0) { old[s][0] = old[s][1] = old[s][2] = 1.0; old[s][3] = old[s][4] = old[s][5] = 0.0; }
-            else (void)corr_coef(was[s][0], was[s][1], old[s], &w2);
-        if (had) (void)corr_apply(ss, &was[0][0], old); else (void)corr_remove(ss);
-        g_err = why;
-    }
-    return rc;
+    if (!any && !ss->has_corr) return NFA_OK;                 // null, or all zeros, and none before: nothing changes
+    // (null, or all zeros: the set's former kernels and bits, or a response's over white noise)
+    double resp[MAXSPEC][NFA_RESP_NT];
+    memcpy(resp, ss->h_resp, sizeof resp);
+    return qstate_change(ss, any ? rho : nullptr, d.resp ? &resp[0][0] : nullptr);
 }
 
 int nfa_specset_correlation(const nfa_specset *ss, double *out) {
-    if (!ss || !ss->dev.corr_q1) return 0;
+    if (!ss || !ss->has_corr) return 0;
     for (int s = 0; out && s < ss->dev.n_spec; ++s) { out[2 * s] = ss->h_rho[s][0]; out[2 * s + 1] = ss->h_rho[s][1]; }
+    return 1;
+}
+
+int nfa_specset_set_response(nfa_specset *ss, const double *taps) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    SpecDev &d = ss->dev;
+    bool any = false;
+    for (int s = 0; taps && s < d.n_spec; ++s) {
+        const double *h = taps + s * NFA_RESP_NT;
+        double sum = 0.0;
+        for (int k = 0; k < NFA_RESP_NT; ++k) {
+            if (!std::isfinite(h[k])) return fail(NFA_ERR_ARG, "a channel response is five finite taps per spectrum");
+            sum += h[k];
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-9)) return fail(NFA_ERR_ARG, "the taps of a channel response sum to 1 (within 1e-9): it conserves the integrated intensity");
+        if (!(h[2] > 0.0)) return fail(NFA_ERR_ARG, "a channel response needs a central tap > 0");
+        any = any || !(h[0] == 0.0 && h[1] == 0.0 && h[2] == 1.0 && h[3] == 0.0 && h[4] == 0.0);
+    }
+    if (any) {
+        for (int s = 0; s < d.n_spec; ++s)
+            if (d.size[s] < 4) return fail(NFA_ERR_ARG, "a channel response needs spectra of 4 channels and more");
+        if (ss->masked) return fail(NFA_ERR_ARG, "a set with a masked channel takes no channel response");
+        if (d.bl_order >= 0) return fail(NFA_ERR_ARG, "a set with a baseline takes no channel response");
+        if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no channel response");
+    }
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    if (!any && !d.resp) return NFA_OK;                       // null, or the identity everywhere, and none before: nothing changes
+    // (null, or the identity everywhere: the correlated set's kernels and bits, or the set's former ones)
+    double rho[MAXSPEC][2];
+    memcpy(rho, ss->h_rho, sizeof rho);
+    return qstate_change(ss, ss->has_corr ? &rho[0][0] : nullptr, any ? taps : nullptr);
+}
+
+int nfa_specset_response(const nfa_specset *ss, double *out) {
+    if (!ss || !ss->dev.resp) return 0;
+    for (int s = 0; out && s < ss->dev.n_spec; ++s)
+        for (int k = 0; k < NFA_RESP_NT; ++k) out[s * NFA_RESP_NT + k] = ss->h_resp[s][k];
     return 1;
 }
 
@@ -1625,6 +1700,21 @@ static LnlKernel lnl_kernel_corr_of(int mode, bool write_spec, const LnlPlan &P)
     return lnl_kernel_corr_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
                               std::make_index_sequence<32>());
 }
+// ... and of a set with a channel response: lnl_kernel_resp over the same five, chosen the same way
+template <int I>
+static LnlKernel lnl_kernel_resp_inst() {
+    return lnl_kernel_resp<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_resp_at(int i, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])() = {lnl_kernel_resp_inst<(int)I>...};
+    return inst[i]();
+}
+static LnlKernel lnl_kernel_resp_of(int mode, bool write_spec, const LnlPlan &P) {
+    if (P.form != LNL_WEIGHTED) return nullptr;
+    return lnl_kernel_resp_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
+                              std::make_index_sequence<32>());
+}
 #ifdef NFA_TEST_HOOKS
 #include <atomic>
 // Likelihood launches by (lnl_inst_index, LnlForm) since the last reset (nfa_test_lnl_launches): host side, counted where
@@ -1656,7 +1746,8 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = S.corr_q1 ? lnl_kernel_corr_of(mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
+    const LnlKernel kern = S.resp ? lnl_kernel_resp_of(mode, d_spec != nullptr, P)
+                         : S.corr_q1 ? lnl_kernel_corr_of(mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
 #ifdef NFA_TEST_HOOKS
     count_lnl_launch(kern);
@@ -1868,7 +1959,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
     const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
-                                     S.cal2 != nullptr, S.corr_q1 != nullptr);
+                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

@@ -350,11 +350,15 @@ struct FusedPlan { const char *refusal, *ring_error; LnlGeom G; int n_blocks, ct
 // calibrated: a set with a calibration uncertainty per spectrum (nfa_specset_set_calibration: the batch kernels only)
 // correlated: a set whose channel noise is correlated along the spectrum (nfa_specset_set_correlation: the batch kernels
 // only -- such a set is weighted too, and the weighted sum alone would leave out the products of neighbouring channels)
+// response: a set with a channel response (nfa_specset_set_response: the batch kernels only, and refused before everything
+// else -- such a set is "correlated" to its kernels even over white noise, and the reason must be its own)
 inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted, bool banded = false,
-                            bool filled = false, bool layered = false, bool calibrated = false, bool correlated = false) {
+                            bool filled = false, bool layered = false, bool calibrated = false, bool correlated = false,
+                            bool response = false) {
     FusedPlan P = {};
     P.G = lnl_geom(s, k, 1);
-    if (correlated) P.refusal = "the resident kernel has no form for correlated channel noise: use nfa_ring_serve";
+    if (response) P.refusal = "the resident kernel has no form for a channel response: use nfa_ring_serve";
+    else if (correlated) P.refusal = "the resident kernel has no form for correlated channel noise: use nfa_ring_serve";
     else if (calibrated) P.refusal = "the resident kernel has no form for a calibration uncertainty: use nfa_ring_serve";
     else if (layered) P.refusal = "the resident kernel has no form for layered transfer: use nfa_ring_serve";
     else if (s.ndim > NFA_POINT_MAXDIM || lnl_wide(s)) P.refusal = "this runner's points go through the batch kernels: use nfa_ring_serve";

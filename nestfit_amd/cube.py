@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_correlation, check_layered, gain_fit
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, gain_fit
 from .core import _as_inplace_matrix
 
 
@@ -52,11 +52,14 @@ class CubeRunner:
     correlation : None, or the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis (a pair
         such as `HANNING` or `ar1(rho)`, or an array [n_spec, 2]; shared by all pixels) for cubes that were smoothed, regridded
         or oversampled; not with masked channels, a baseline or a calibration; null_lnZ follows
+    response : None, or the channel response of the spectrometer (3 or 5 taps such as `HANNING_RESPONSE`, or an array
+        [n_spec, 3 | 5]; shared by all pixels) with which the model is convolved before it meets the data; not
+        with masked channels, a baseline or a calibration; null_lnZ is unchanged
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
                  model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False,
-                 calibration=None, correlation=None):
+                 calibration=None, correlation=None, response=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
@@ -70,6 +73,7 @@ class CubeRunner:
         sizes = [np.size(x) for x in xarrs]
         masked = np.shape(noise)[-1] == sum(sizes) and not np.all(np.isfinite(noise))
         correlation = check_correlation(correlation, len(xarrs), sizes, masked, baseline_order, calibration)
+        response = check_response(response, len(xarrs), sizes, masked, baseline_order, calibration)
         if species is None and int(model) == 4 and lines is not None:
             from .lte import LteBand, LteBlend, LteLines, lines_species
             lines = list(lines)
@@ -90,6 +94,8 @@ class CubeRunner:
             self._ss.set_calibration(calibration)
         if correlation is not None:
             self._ss.set_correlation(correlation)
+        if response is not None:
+            self._ss.set_response(response)
         self._data, self._noise = data, noise                # (fit_baseline, fit_gain)
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -162,6 +168,17 @@ class CubeRunner:
             resid = np.where(w > 0, data[:, sl] - spec[:, sl], 0.0)
             out[:, sl] = baseline_fit(resid, w, self.baseline_order)
         return out
+
+    @property
+    def response(self):
+        """None, or the float64 array [n_spec, 5] of the spectra's channel responses (h_-2 .. h_2)."""
+        resp = self._ss.response
+        return None if resp is None else resp.copy()
+
+    def set_response(self, resp):
+        """Sets (3 or 5 taps, or such a row per spectrum) or removes (None, the identity) the channel response; null_lnZ is
+        untouched."""
+        self._ss.set_response(resp)
 
     @property
     def correlation(self):

@@ -24,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import hdf5
-from ._model import check_calibration, check_correlation
+from ._model import check_calibration, check_correlation, check_response
 
 HDF5_SUFFIXES = ('.hdf', '.h5', '.hdf5')
 
@@ -442,6 +442,11 @@ class HdfStore:
         corr = check_correlation((getattr(fitter, 'runner_kwargs', None) or {}).get('correlation'), None if cubes is None else len(cubes))
         if corr is not None:
             self.hdf.attrs['noise_correlation'] = corr
+        # a channel response (runner_kwargs['response']): root attribute `channel_response`, float64 [n_spec, 5],
+        # the taps h_-2 .. h_2.  A store without it was fitted with the model at the channel centres.
+        resp = check_response((getattr(fitter, 'runner_kwargs', None) or {}).get('response'), None if cubes is None else len(cubes))
+        if resp is not None:
+            self.hdf.attrs['channel_response'] = resp
         quantum = getattr(fitter, 'nlive_quantum', 1)
         if quantum != 1:                 # a deviation from main.py:445-447 is written down where the results are
             self.hdf.attrs['nlive_quantum'] = int(quantum)
@@ -475,6 +480,13 @@ class HdfStore:
         assert self.is_open
         corr = self.hdf.attrs.get('noise_correlation')
         return None if corr is None else np.asarray(corr, dtype=np.float64).reshape(-1, 2)
+
+    def read_model_response(self):
+        """The channel response of every spectrum the store was fitted with (`runner_kwargs={'response': ...}`): the root
+        attribute `channel_response` as a float64 array [n_spec, 5]; None for a store without it."""
+        assert self.is_open
+        resp = self.hdf.attrs.get('channel_response')
+        return None if resp is None else np.asarray(resp, dtype=np.float64).reshape(-1, 5)
 
     def read_model_fill(self):
         """Whether the store was fitted with a beam filling factor per component (`LteMix(species, fill=True)`): the root
