@@ -378,6 +378,32 @@ int nfa_specset_correlation(const nfa_specset *ss, double *out);
 int nfa_specset_set_response(nfa_specset *ss, const double *taps);
 /* 1 and out[n_spec][5] = the taps set (out may be null), or 0 for a set without a channel response (and for null) */
 int nfa_specset_response(const nfa_specset *ss, double *out);
+/* Nuisance templates: fixed shapes on the channel grid that the caller knows up to an amplitude -- a standing wave of known
+ * period (its sine and cosine), a bandpass residual, an atmospheric feature, an RFI comb -- profiled out of the likelihood
+ * together with the polynomial baseline, in closed form and without a sampler dimension.  With nfa_specset_set_baseline's
+ * weights w_c and polynomial basis P_0..P_K (K = -1: none) and the templates t_1..t_T of spectrum s:
+ *     V = span{P_0..P_K, t_1..t_T},   chi2_min,s = min_{b in V} sum_c w_c (r_c - b_c)^2,   lnL = -sum_s chi2_min,s / (2 sigma_ref,s^2)
+ * nfa_specset_null_lnz is the same expression at p = 0, and the Bayes-factor argument of nfa_specset_set_baseline holds
+ * unchanged.  A direction of V that the others already span (a constant template beside order 0, a template given twice, a
+ * spectrum with fewer unmasked channels than basis functions) is dropped by that call's rank rule.
+ * t[NFA_TMPL_MAX][sum(sizes)]: slot k of every spectrum, the spectra concatenated like `data`; n_tmpl[n_spec] in
+ * 0..NFA_TMPL_MAX says how many slots of spectrum s are used (the others are not read).  The templates are shared by all
+ * pixels.  The engine scales each to max |t| = 1; nfa_specset_templates returns the caller's values.
+ * t = NULL, n_tmpl = NULL or all counts zero removes the templates (the set's former kernels and results bit for bit).
+ * NFA_ERR_ARG, the set left as it was: a count outside 0..NFA_TMPL_MAX, a value that is not finite, a template that is zero
+ * over its whole spectrum; a set with a calibration uncertainty, correlated channel noise or a channel response ("... takes
+ * no nuisance templates") -- and nfa_specset_set_calibration, nfa_specset_set_correlation and nfa_specset_set_response
+ * refuse a set with templates likewise.  With masked channels, a noise per channel, filled and layered sets: yes.  It
+ * commutes with nfa_specset_set_baseline.  Like that call it launches held batches first, synchronises the device and
+ * drops the runners' captured single-point graphs: call it between batches.  nfa_specset_set_data keeps the templates.
+ * Spectra out are unchanged: the model without nuisance terms.  Such sets go through the batch kernels (the general
+ * component form); single points and a broker's handful too, and nfa_ring_serve_device refuses their runners ("the resident
+ * kernel has no form for nuisance templates: use nfa_ring_serve"). */
+#define NFA_TMPL_MAX 4
+int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmpl);
+/* 1, out_t[NFA_TMPL_MAX][sum(sizes)] = the values set (unused slots zero) and out_n[n_spec] = the counts (either may be
+ * null), or 0 for a set without templates (and for null) */
+int nfa_specset_templates(const nfa_specset *ss, double *out_t, int *out_n);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

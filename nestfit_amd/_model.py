@@ -204,6 +204,102 @@ def smoothed(taps):
     return {'response': taps, 'correlation': correlation_of_response(taps)}
 
 
+TMPL_MAX = 4              # NFA_TMPL_MAX
+
+
+def ripple(n_chan, period, phase=None):
+    """Templates of a standing wave of `period` channels (any real number > 0) on a spectrum of `n_chan` channels, for
+    `templates=`: the rows sin(2 pi j / period) and cos(2 pi j / period), float64 [2, n_chan], whose two amplitudes stand for
+    an unknown amplitude and phase; with a known `phase` (radians) the one row sin(2 pi j / period + phase), [1, n_chan].
+    Several periods: `np.vstack` of several calls (at most 4 rows per spectrum)."""
+    n_chan, period = int(n_chan), float(period)
+    if n_chan < 1 or not (np.isfinite(period) and period > 0.0):
+        raise ValueError(f'ripple: n_chan >= 1 and a finite period > 0 (in channels), not ({n_chan!r}, {period!r})')
+    arg = 2.0 * np.pi * np.arange(n_chan, dtype=np.float64) / period
+    if phase is None:
+        return np.stack([np.sin(arg), np.cos(arg)])
+    if not np.isfinite(float(phase)):
+        raise ValueError(f'ripple: a finite phase (radians), not {phase!r}')
+    return np.sin(arg + float(phase))[None, :]
+
+
+def check_templates(tmpl, n_spec=None, sizes=None, calibration=None, correlation=None, response=None):
+    """`templates` of a runner: fixed shapes on the channel grid, known up to an amplitude, that are profiled out of the
+    likelihood with the baseline.  None for none; else a list with one entry per spectrum, each None or an
+    array [T, N_s] of 1 <= T <= 4 templates over the spectrum's N_s channels (one row may be given as a 1-D array).  Every
+    value is finite and no template is zero over its whole spectrum; all entries None is None.  Nuisance templates go with
+    neither a calibration uncertainty, a noise correlation nor a channel response.  Returns None or a list of n_spec entries,
+    None or float64 [T, N_s]; ValueError otherwise.  Needs no device."""
+    if tmpl is None:
+        return None
+    what = 'templates must be None or a list with one entry per spectrum, each None or an array [T, n_chan] of 1..4 templates'
+    if isinstance(tmpl, np.ndarray) and tmpl.ndim in (1, 2) and tmpl.dtype.kind in 'iuf' and n_spec in (None, 1):
+        tmpl = [tmpl]                                         # one spectrum: its array alone
+    if not isinstance(tmpl, (list, tuple)) or len(tmpl) == 0:
+        raise ValueError(f'{what}, not {tmpl!r}')
+    if n_spec is not None and len(tmpl) != int(n_spec):
+        raise ValueError(f'{what}: {len(tmpl)} entries for {int(n_spec)} spectra')
+    out = []
+    for k, t in enumerate(tmpl):
+        if t is None:
+            out.append(None)
+            continue
+        try:
+            a = np.array(t, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f'{what}; spectrum {k}: {t!r}') from None
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[1] == 0:
+            raise ValueError(f'{what}; spectrum {k} has shape {a.shape}')
+        if a.shape[0] == 0:
+            out.append(None)
+            continue
+        if a.shape[0] > TMPL_MAX:
+            raise ValueError(f'nuisance templates: at most {TMPL_MAX} per spectrum, not {a.shape[0]} (spectrum {k})')
+        if sizes is not None and a.shape[1] != int(sizes[k]):
+            raise ValueError(f'nuisance templates: spectrum {k} has {int(sizes[k])} channels, its templates {a.shape[1]}')
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f'nuisance templates: every value finite (spectrum {k})')
+        if np.any(np.all(a == 0.0, axis=1)):
+            raise ValueError(f'nuisance templates: a template is zero over its whole spectrum (spectrum {k})')
+        out.append(np.ascontiguousarray(a))
+    if all(a is None for a in out):
+        return None
+    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
+        raise ValueError('nuisance templates do not go with a calibration uncertainty (calibration)')
+    if check_correlation(correlation) is not None:            # (all zeros: none)
+        raise ValueError('nuisance templates do not go with a noise correlation (correlation)')
+    if check_response(response) is not None:                  # (the identity: none)
+        raise ValueError('nuisance templates do not go with a channel response (response)')
+    return out
+
+
+def nuisance_fit(resid, weight, order, templates):
+    """Best-fit nuisance curve of ONE residual spectrum resid[N] under channel weights weight[N] (0: masked) over the span of
+    the Legendre polynomials of degree <= `order` (None: none) and the rows of templates[T, N] (None: none): weighted least
+    squares with numpy (minimum norm where the span is degenerate).  Returns (curve[N], amplitudes[T] of the templates as
+    given)."""
+    resid, w = np.asarray(resid, dtype=np.float64), np.asarray(weight, dtype=np.float64)
+    n = resid.shape[-1]
+    u = (2.0 * np.arange(n) - (n - 1)) / (n - 1) if n > 1 else np.zeros(n)
+    cols = [] if order is None else [np.polynomial.legendre.legvander(u, int(order))]
+    n_poly = 0 if order is None else int(order) + 1
+    T = 0 if templates is None else len(templates)
+    if T:
+        cols.append(np.asarray(templates, dtype=np.float64).T)
+    if not cols:
+        return np.zeros(n), np.zeros(0)
+    V = np.concatenate(cols, axis=1)
+    live = w > 0
+    if not live.any():
+        return np.zeros(n), np.zeros(T)
+    sw = np.sqrt(w[live])
+    scale = np.maximum(np.max(np.abs(V), axis=0), 1e-300)    # (the caller's scaling must not enter the rank decision)
+    coef = np.linalg.lstsq(V[live] / scale * sw[:, None], resid[live] * sw, rcond=None)[0] / scale
+    return V @ coef, coef[n_poly:]
+
+
 def spec_data_sizes_masked(spec_data):
     """(sizes, masked) of `from_data`'s rows [xarr, data, noise, ...] for `check_correlation`: the channels of every spectrum, and
     whether any channel noise masks a channel (inf).  numpy only."""
@@ -379,12 +475,40 @@ class _SpecSet:
         self.calibration = None
         self.correlation = None
         self.response = None
+        self.templates = None
         self.masked = bool(self.per_channel and not np.all(np.isfinite(noise)))
+
+    def set_templates(self, tmpl):
+        """Nuisance templates per spectrum, profiled out of the likelihood with the baseline (`check_templates`'s argument),
+        or none (None): nfa_specset_set_templates.  null_lnZ() then is the model of baseline and templates alone."""
+        tmpl = check_templates(tmpl, self.n_spec, self.sizes, self.calibration, self.correlation, self.response)
+        if tmpl is None:
+            _ffi.check(_ffi.load().nfa_specset_set_templates(self.handle, None, None))
+        else:
+            vals = np.zeros((TMPL_MAX, self.chan_tot))
+            counts = np.zeros(self.n_spec, dtype=np.int32)
+            for k, a in enumerate(tmpl):
+                if a is not None:
+                    counts[k] = a.shape[0]
+                    vals[:a.shape[0], self.offsets[k]:self.offsets[k + 1]] = a
+            _ffi.check(_ffi.load().nfa_specset_set_templates(self.handle, _ffi.dptr(vals), counts.ctypes.data_as(_ffi._ip)))
+        self.templates = tmpl
+
+    def get_templates(self):
+        """The templates as the engine holds them (nfa_specset_templates): None, or a list of n_spec entries, None or
+        float64 [T, N_s], in the caller's scaling."""
+        vals = np.zeros((TMPL_MAX, self.chan_tot))
+        counts = np.zeros(self.n_spec, dtype=np.int32)
+        if not _ffi.load().nfa_specset_templates(self.handle, _ffi.dptr(vals), counts.ctypes.data_as(_ffi._ip)):
+            return None
+        return [vals[:counts[k], self.offsets[k]:self.offsets[k + 1]].copy() if counts[k] else None for k in range(self.n_spec)]
 
     def set_response(self, resp):
         """The channel response of the spectra (`check_response`'s argument), or none (None, the identity):
         nfa_specset_set_response.  null_lnZ() does not change."""
         resp = check_response(resp, self.n_spec, self.sizes, self.masked, self.baseline_order, self.calibration)
+        if resp is not None and self.templates is not None:
+            raise ValueError('a channel response does not go with nuisance templates (templates)')
         _ffi.check(_ffi.load().nfa_specset_set_response(self.handle, None if resp is None else _ffi.dptr(resp)))
         self.response = resp
 
@@ -393,6 +517,8 @@ class _SpecSet:
         or none (None, zeros): nfa_specset_set_correlation.  null_lnZ() follows."""
         corr = check_correlation(corr, self.n_spec, self.sizes, self.masked, self.baseline_order, self.calibration)
         corr = None if corr is None else np.ascontiguousarray(corr)
+        if corr is not None and self.templates is not None:
+            raise ValueError('a noise correlation does not go with nuisance templates (templates)')
         _ffi.check(_ffi.load().nfa_specset_set_correlation(self.handle, None if corr is None else _ffi.dptr(corr)))
         self.correlation = corr
 
@@ -404,6 +530,8 @@ class _SpecSet:
             raise ValueError('a calibration uncertainty does not go with a channel response (response)')
         if cal is not None and self.correlation is not None:
             raise ValueError('a calibration uncertainty does not go with a noise correlation (correlation)')
+        if cal is not None and self.templates is not None:
+            raise ValueError('a calibration uncertainty does not go with nuisance templates (templates)')
         _ffi.check(_ffi.load().nfa_specset_set_calibration(self.handle, None if cal is None else _ffi.dptr(cal)))
         self.calibration = cal
 
@@ -537,8 +665,12 @@ class EngineRunner(Runner):
     N_MODEL = 6
 
     def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False,
-               calibration=None, correlation=None, response=None):
-        """response: None, or the channel response of the spectrometer -- 3 or 5 taps for all spectra (`HANNING_RESPONSE`) or
+               calibration=None, correlation=None, response=None, templates=None):
+        """templates: None, or a list with one entry per spectrum, each None or an array [T, N_s] of 1..4 fixed shapes on the
+        spectrum's channels whose amplitudes are profiled out of the likelihood in closed form together with the baseline
+        (nfa_specset_set_templates): `ripple(n_chan, period)` for a standing wave of known period.  Not with a
+        calibration, a correlation or a response.  null_lnZ is then the model of baseline and templates alone.
+        response: None, or the channel response of the spectrometer -- 3 or 5 taps for all spectra (`HANNING_RESPONSE`) or
         an array [n_spec, 3 | 5] -- with which the model is convolved before it meets the data (nfa_specset_set_response,
         DESIGN 4.14); the identity is None.  Not with masked channels, a baseline or a calibration.  null_lnZ is unchanged.
         correlation: None, or the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis -- a
@@ -563,6 +695,8 @@ class EngineRunner(Runner):
                           any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
         check_response(response, len(spectra), [s.size for s in spectra],
                        any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
+        templates = check_templates(templates, len(spectra), [s.size for s in spectra], calibration,
+                                    check_correlation(correlation, len(spectra)), check_response(response, len(spectra)))
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -598,6 +732,25 @@ class EngineRunner(Runner):
             self.set_correlation(correlation)
         if response is not None:
             self.set_response(response)
+        if templates is not None:
+            self.set_templates(templates)
+
+    @property
+    def templates(self):
+        """None, or the list of the spectra's nuisance templates: per spectrum None or a float64 array [T, N_s]."""
+        tmpl = self._ss.templates
+        return None if tmpl is None else [None if a is None else a.copy() for a in tmpl]
+
+    def set_templates(self, tmpl):
+        """Sets (a list with an array [T, N_s] or None per spectrum) or removes (None) the nuisance templates of this
+        runner's spectra; null_lnZ follows.  The spectra's private one-spectrum sets have none: a spectrum's own
+        `loglikelihood` is the plain one; the runner's `loglikelihood`, `loglikelihood_batch` and `predict_batch` profile
+        the templates out."""
+        self._ss.set_templates(tmpl)
+        if self._ss.templates is not None or self.baseline_order is not None:
+            self.null_lnZ = float(self._ss.null_lnZ().sum())
+        else:
+            self.null_lnZ = float(sum(s.null_lnZ for s in self._model_spectra()))
 
     @property
     def response(self):
@@ -664,16 +817,36 @@ class EngineRunner(Runner):
     def fit_baseline(self, params):
         """Best-fit baseline of every spectrum for physical `params` (after `predict`, which this calls): one array of
         n_chan_tot values, the spectra concatenated.  numpy on the host (`baseline_fit`): for residual plots, not the hot
-        path.  ValueError without a baseline."""
-        if self.baseline_order is None:
+        path.  A runner with nuisance templates returns the whole nuisance curve, polynomial and templates
+        (`nuisance_fit`).  ValueError without a baseline and without templates."""
+        tmpl = self._ss.templates
+        if self.baseline_order is None and tmpl is None:
             raise ValueError('this runner has no baseline (baseline_order=None)')
         self.predict(params)
         out = []
-        for s in self._model_spectra():
+        for k, s in enumerate(self._model_spectra()):
             w = channel_weights(s.noise, s.size)
             resid = np.where(w > 0, s.data - s.get_spec(), 0.0)
-            out.append(baseline_fit(resid, w, self.baseline_order))
+            if tmpl is None:
+                out.append(baseline_fit(resid, w, self.baseline_order))
+            else:
+                out.append(nuisance_fit(resid, w, self.baseline_order, tmpl[k])[0])
         return np.concatenate(out)
+
+    def fit_templates(self, params):
+        """Best-fit amplitudes of every spectrum's templates, in the caller's scaling, for physical `params` (after `predict`,
+        which this calls): a list of n_spec arrays [T] (empty for a spectrum without templates).  numpy on the host
+        (`nuisance_fit`).  ValueError without templates."""
+        tmpl = self._ss.templates
+        if tmpl is None:
+            raise ValueError('this runner has no nuisance templates (templates=None)')
+        self.predict(params)
+        out = []
+        for k, s in enumerate(self._model_spectra()):
+            w = channel_weights(s.noise, s.size)
+            resid = np.where(w > 0, s.data - s.get_spec(), 0.0)
+            out.append(nuisance_fit(resid, w, self.baseline_order, tmpl[k])[1])
+        return out
 
     def fit_gain(self, params):
         """Posterior mean and standard deviation of every spectrum's gain at physical `params` (after `predict`, which

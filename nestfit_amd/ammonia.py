@@ -5,7 +5,7 @@ behaviour; all arithmetic runs in the HIP engine through the C ABI.
 import numpy as np
 
 from ._model import (MODEL_AMMONIA, EngineRunner, EngineSpectrumMixin, _pix_ptr, _RunnerHandle,  # noqa: F401
-                     _SpecSet, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, spec_data_sizes_masked, par_names)
+                     _SpecSet, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names)
 from .core import HyperfineSpectrum
 
 N_LEVELS = 9
@@ -55,7 +55,7 @@ class AmmoniaRunner(EngineRunner):
     MODEL = MODEL_AMMONIA
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None, layered=False, calibration=None, correlation=None, response=None):
+    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
@@ -63,7 +63,7 @@ class AmmoniaRunner(EngineRunner):
         self.cold = bool(cold)
         self.lte = bool(lte)
         self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response)
+                    calibration=calibration, correlation=correlation, response=response, templates=templates)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -74,6 +74,8 @@ class AmmoniaRunner(EngineRunner):
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
                        baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
+        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
+                        kwargs.get('correlation'), kwargs.get('response'))
         spectra = np.array([AmmoniaSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

@@ -153,6 +153,12 @@ struct SpecDev {
     // chan_w, wdata, corr_q1, corr_q2 and corr_coef (the white entries 1, 1, 1, 0, 0, 0 without a correlation) and runs
     // lnl_kernel_resp.
     const double  *resp;
+    // Spectra sets with nuisance templates (nfa_specset_set_templates; null without): tmpl
+    // [NFA_TMPL_MAX][chan_tot], slot k of every spectrum scaled to max |t| = 1, zeros where a spectrum leaves the slot
+    // unused, shared by all pixels; tp [n_pix][n_spec][NFA_TP_REC], the records of tmpl_setup_kernel (below).  Such a set
+    // always has chan_w and wdata (a scalar noise: chan_w == 1), keeps bl and bl_order for nfa_specset_set_baseline's sake
+    // and runs lnl_kernel_tmpl, which reads tp alone.
+    const double  *tmpl, *tp;
 };
 // entries of R^-1 of a spectrum: its diagonal at channels 0 and N-1, 1 and N-2, and between; its first off-diagonal at
 // (0, 1) and (N-2, N-1), and between; its second off-diagonal
@@ -163,6 +169,10 @@ struct SpecDev {
 // of the basis P_0..P_order.  A direction the Cholesky factorisation drops (pivot <= 1e-12 G_kk) and the orders above
 // bl_order have zero rows and columns, so that ||L^-1 e||^2 is the weighted least-squares fit of e over the rest.
 #define NFA_BL_REC 16
+// Record of a (pixel, spectrum) of a set with templates, DESIGN 4.15: the baseline record over the NFA_TP_NB basis functions
+// P_0..P_3, t_1..t_4 -- [0, 8) m_k(d); [8, 44) L^-1 packed by rows; padded to 48.  The orders above bl_order, the unused
+// slots (all zero: no pivot) and every direction the others span have zero rows and columns.
+#define NFA_TP_REC 48
 #define NFA_CORR_ROW 62        // channels a row of a correlated set advances by: 64 lanes less the halo of two
 #define NFA_RESP_NT 5          // taps of a channel response as they are stored
 #define NFA_RESP_ROW 58        // channels a row of a set with a response advances by: 64 lanes less 2 * 2 of the filter less that halo
@@ -184,6 +194,23 @@ __device__ __forceinline__ double bl_quad(const double *R, const double *mp) {
     int o = NFA_BL_NB;
 #pragma unroll
     for (int i = 0; i < NFA_BL_NB; ++i) {
+        double y = 0.0;
+#pragma unroll
+        for (int k = 0; k <= i; ++k) y = __builtin_fma(R[o++], e[k], y);
+        q = __builtin_fma(y, y, q);
+    }
+    return q;
+}
+
+// bl_quad over the NFA_TP_NB basis functions of a set with templates (record NFA_TP_REC)
+__device__ __forceinline__ double tp_quad(const double *R, const double *mp) {
+    double e[NFA_TP_NB];
+#pragma unroll
+    for (int k = 0; k < NFA_TP_NB; ++k) e[k] = R[k] - mp[k];
+    double q = 0.0;
+    int o = NFA_TP_NB;
+#pragma unroll
+    for (int i = 0; i < NFA_TP_NB; ++i) {
         double y = 0.0;
 #pragma unroll
         for (int k = 0; k <= i; ++k) y = __builtin_fma(R[o++], e[k], y);
@@ -924,8 +951,13 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // after four more wave shifts and five multiply-adds in the fixed order k = -2..2, HOLDS p~ of channel j_o = 58 row + l:
 // lanes 0..57 own j_o (data, Q, spectra out there), lanes 58, 59 are CORR's halo of p~, lanes 60..63 hold nothing.  x, T0
 // and tbg are read at j_e, everything else at j_o.  Still no LDS, no barrier, and the same summation rule.
+// TMPL (the baseline form in the general component form only): nuisance templates.  The baseline form over
+// NFA_TP_NB = 8 moments: the four of P_0..P_3 and m_{4+k}(p) = sum w p t_k of the four template slots, each lane reading the
+// slots at its channel (SpecDev.tmpl: shared by all pixels and rows, so cache-resident; unused slots hold zeros).  The
+// accumulators, the parts' slots in LDS, wave_sum and the part-order rule extend from four moments to eight; the epilogue is
+// tp_quad over SpecDev.tp.  One instance for every (order, number of templates).  No LDS beyond the slots, no new barrier.
 template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false,
-          bool LAYER = false, bool CALIB = false, bool CORR = false, bool RESP = false>
+          bool LAYER = false, bool CALIB = false, bool CORR = false, bool RESP = false, bool TMPL = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -981,8 +1013,9 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     LineRec *w_line = (LineRec *)(smem + n_shared + (size_t)ulocal * G.wave_doubles);
     int2 *w_win = (int2 *)(w_line + (NCOMP > 0 ? NCOMP : S.ncomp) * G.nhf_max);   // the windows [lo, hi) follow the table
     // split > 1: the parts' per-lane sums meet here, [unit of the workgroup][part][lane]
-    // (BASELINE: the parts' moment sums follow, [unit][1 + k][part][lane]; CALIB: and those of sum w p^2, slot 1 + NFA_BL_NB)
-    constexpr int PART_SLOTS = 1 + (BASELINE ? NFA_BL_NB : 0) + (CALIB ? 1 : 0);      // lnl_part_slots of the plan
+    // (BASELINE: the parts' moment sums follow, [unit][1 + k][part][lane]; CALIB: and those of sum w p^2, slot 1 + NFA_BL_NB;
+    // TMPL: NFA_TP_NB moment sums)
+    constexpr int PART_SLOTS = 1 + (TMPL ? NFA_TP_NB : BASELINE ? NFA_BL_NB : 0) + (CALIB ? 1 : 0);      // lnl_part_slots of the plan
     double *w_part = smem + n_shared + (size_t)upw * G.wave_doubles + (size_t)ulocal * (LNL_PARTS * 64 * PART_SLOTS);
     if (unit >= units) {
         if (split > 1) { __syncthreads(); __syncthreads(); }         // the two barriers of the waves at work
@@ -1136,7 +1169,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     static_assert(!CALIB || (BASELINE && NCOMP == 0 && !DYN), "a calibration uncertainty: the baseline form in the general component form");
     static_assert(!CORR || (WEIGHTED && !BASELINE && NCOMP == 0 && !DYN), "correlated noise: the weighted form in the general component form");
     static_assert(!RESP || CORR, "a channel response: the correlated form (white coefficients without a correlation)");
-    constexpr int NBL = BASELINE ? NFA_BL_NB : 1;
+    static_assert(!TMPL || (BASELINE && NCOMP == 0 && !DYN && !CALIB && !CORR), "nuisance templates: the baseline form in the general component form");
+    constexpr int NBL = TMPL ? NFA_TP_NB : BASELINE ? NFA_BL_NB : 1;
     double bl_acc[NBL], bl_tot[NBL];
 #pragma unroll
     for (int k = 0; k < NBL; ++k) bl_tot[k] = 0.0;
@@ -1483,6 +1517,12 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                 bl_acc[2 % NBL] = __builtin_fma(wp, p2, bl_acc[2 % NBL]);
                 bl_acc[3 % NBL] = __builtin_fma(wp, p3, bl_acc[3 % NBL]);
                 if constexpr (CALIB) cal_acc = __builtin_fma(wp, pred, cal_acc);
+                if constexpr (TMPL) {                             // always all four slots: an unused one holds zeros
+                    const char *tq = (const char *)(S.tmpl + off) + jo;
+#pragma unroll
+                    for (int k = 0; k < NFA_TMPL_MAX; ++k)
+                        bl_acc[NFA_BL_NB + k] = __builtin_fma(wp, *(const double *)(tq + (size_t)k * (size_t)S.chan_tot * 8u), bl_acc[NFA_BL_NB + k]);
+                }
             }
         }
     }
@@ -1514,7 +1554,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     if (BASELINE) {
 #pragma unroll
         for (int k = 0; k < NBL; ++k) bl_tot[k] = wave_sum(bl_tot[k]);
-        if constexpr (!CALIB) bl_q = bl_quad(S.bl + (p_ix * nspec + s) * NFA_BL_REC, bl_tot);
+        if constexpr (TMPL) bl_q = tp_quad(S.tp + (p_ix * nspec + s) * NFA_TP_REC, bl_tot);
+        else if constexpr (!CALIB) bl_q = bl_quad(S.bl + (p_ix * nspec + s) * NFA_BL_REC, bl_tot);
     }
     if constexpr (CALIB) {
         // The gain integrated out, A = <p,p>_P, B = <d,p>_P with the baseline projected out of both:
@@ -1616,6 +1657,22 @@ lnl_kernel_resp(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
                                                                                            n_shared, blockIdx.x, &grp);
 }
 
+// The kernels of a set with NUISANCE TEMPLATES (nfa_specset_set_templates): the baseline form in the general
+// component form with lnl_body's TMPL flag, 32 instances over the same five flags, beside the table like lnl_kernel_corr.
+// launch_lnl takes them when SpecDev.tmpl is set, with the baseline form's plan over nine sums per part (plan_lnl's
+// `templates`).  One instance serves every baseline order and every number of templates.
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_tmpl(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, LAYER, false, false, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem,
+                                                                                                  sm, n_shared, blockIdx.x, &grp);
+}
+
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one
 // 51 KB copy of the product tables, and in lnl_kernel the wave slots of the waves that are done stay empty until the
 // longest of the sixteen is: units differ by the widths of their lines, and at the metric's shape 4.5 of 8 waves per
@@ -1634,7 +1691,7 @@ lnl_kernel_resp(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
 #define NFA_QUEUE_WORDS  (2 * NFA_QUEUE_STRIDE)
 struct QueueArgs { SpecDev S; BatchGroup grp; const double *D; double *part; double *spec_out; long B; LnlGeom G; const double *g_tabs; };
 // (the argument segment places every argument at the next multiple of its alignment: 8 for all of these, so the struct's
-// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1008, 1280, 1288, 1296, 1304, 1312, 1352)
+// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1024, 1296, 1304, 1312, 1320, 1328, 1368)
 static_assert(sizeof(SpecDev) % 8 == 0 && sizeof(BatchGroup) % 8 == 0 && sizeof(LnlGeom) % 8 == 0 && alignof(SpecDev) == 8 &&
               alignof(BatchGroup) == 8 && alignof(LnlGeom) == 8, "QueueArgs must mirror the kernel argument segment");
 template <bool WRITE_SPEC, int NCOMP>
@@ -1980,6 +2037,121 @@ __global__ void null_lnz_bl_kernel(SpecDev S, long n_pix, double *__restrict__ o
     if (i >= n_pix * S.n_spec) return;
     const double zero[NFA_BL_NB] = {0.0, 0.0, 0.0, 0.0};
     const double chi2 = (S.totsq[i] + 0.0) - bl_quad(S.bl + i * NFA_BL_REC, zero);
+    const double noise = S.noise[i];
+    out[i] = -chi2 / (2 * (noise * noise));
+}
+
+// Records of a set with templates (SpecDev.tp, NFA_TP_REC) of pixels [pix0, pix0 + n_pix): bl_setup_kernel over the
+// NFA_TP_NB functions P_0..P_3, t_1..t_4, one wave per (pixel, spectrum).  m_k(d) = sum_j wdata_j phi_k(j) always; with
+// form_basis also the Gram matrix, its Cholesky factor by the same pivot rule (a pivot <= 1e-12 G_kk drops that direction:
+// a constant template beside order 0, a template given twice, a slot of zeros, a spectrum with fewer unmasked channels than
+// functions) and L^-1.  The polynomials above bl_order are left out as there.
+// (Workgroups of 256 threads, said here: the 36 sums of the Gram matrix and the two triangular factors of lane 0 want more
+// than the 128 vector registers a kernel that may be launched with 1024 threads can have, and must not go to scratch.)
+__global__ void __launch_bounds__(256) tmpl_setup_kernel(SpecDev S, long pix0, long n_pix, double *__restrict__ tp, int form_basis) {
+    const int lane = threadIdx.x & 63;
+    const long w = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (w >= n_pix * S.n_spec) return;
+    const long p = pix0 + w / S.n_spec;
+    const int s = (int)(w - (p - pix0) * S.n_spec);
+    const int N = S.size[s];
+    const double ui = N > 1 ? 1.0 / (double)(N - 1) : 0.0;
+    const double *wd = S.wdata + p * S.chan_tot + S.off[s], *wc = S.chan_w + p * S.chan_tot + S.off[s];
+    const double *ts = S.tmpl + S.off[s];
+    double m[NFA_TP_NB], g[NFA_TP_NB][NFA_TP_NB];
+#pragma unroll
+    for (int k = 0; k < NFA_TP_NB; ++k) {
+        m[k] = 0.0;
+#pragma unroll
+        for (int l = 0; l < NFA_TP_NB; ++l) g[k][l] = 0.0;
+    }
+    for (int j = lane; j < N; j += 64) {
+        double P[NFA_TP_NB];
+        P[0] = 1.0;
+        bl_basis(j, N, ui, P[1], P[2], P[3]);
+#pragma unroll
+        for (int k = 0; k < NFA_TMPL_MAX; ++k) P[NFA_BL_NB + k] = ts[(size_t)k * (size_t)S.chan_tot + j];
+        const double x = wd[j];
+#pragma unroll
+        for (int k = 0; k < NFA_TP_NB; ++k) m[k] = __builtin_fma(x, P[k], m[k]);
+        if (form_basis) {
+            const double wj = wc[j];
+#pragma unroll
+            for (int k = 0; k < NFA_TP_NB; ++k)
+#pragma unroll
+                for (int l = 0; l <= k; ++l) g[k][l] = __builtin_fma(wj * P[k], P[l], g[k][l]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NFA_TP_NB; ++k) m[k] = wave_sum(m[k]);
+    double *R = tp + (p * S.n_spec + s) * NFA_TP_REC;
+    if (form_basis) {
+#pragma unroll
+        for (int k = 0; k < NFA_TP_NB; ++k)
+#pragma unroll
+            for (int l = 0; l <= k; ++l) g[k][l] = wave_sum(g[k][l]);
+    }
+    if (lane != 0) return;
+#pragma unroll
+    for (int k = 0; k < NFA_TP_NB; ++k) R[k] = m[k];
+    if (!form_basis) return;
+    // G = L L^T over the kept directions of P_0..P_order, t_1..t_4 (L's other rows and columns: 0)
+    const int K = S.bl_order;
+    double L[NFA_TP_NB][NFA_TP_NB], M[NFA_TP_NB][NFA_TP_NB];
+    bool keep[NFA_TP_NB];
+#pragma unroll
+    for (int i = 0; i < NFA_TP_NB; ++i) {
+#pragma unroll
+        for (int k = 0; k < NFA_TP_NB; ++k) { L[i][k] = 0.0; M[i][k] = 0.0; }
+        keep[i] = false;
+        if (i < NFA_BL_NB && i > K) continue;
+#pragma unroll
+        for (int k = 0; k < i; ++k) {
+            if (!keep[k]) continue;
+            double v = g[i][k];
+#pragma unroll
+            for (int l = 0; l < k; ++l) v -= L[i][l] * L[k][l];
+            L[i][k] = v / L[k][k];
+        }
+        double d = g[i][i];
+#pragma unroll
+        for (int l = 0; l < i; ++l) d -= L[i][l] * L[i][l];
+        keep[i] = d > 1e-12 * g[i][i];
+        if (keep[i]) L[i][i] = sqrt(d);
+        else {
+#pragma unroll
+            for (int k = 0; k < i; ++k) L[i][k] = 0.0;
+        }
+    }
+    // M = L^-1 by forward substitution (a dropped direction: its row and column stay 0)
+#pragma unroll
+    for (int i = 0; i < NFA_TP_NB; ++i) {
+        if (!keep[i]) continue;
+        M[i][i] = 1.0 / L[i][i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) {
+            double v = 0.0;
+#pragma unroll
+            for (int l = k; l < i; ++l) v += L[i][l] * M[l][k];
+            M[i][k] = -v * M[i][i];
+        }
+    }
+    int o = NFA_TP_NB;
+#pragma unroll
+    for (int i = 0; i < NFA_TP_NB; ++i)
+#pragma unroll
+        for (int k = 0; k <= i; ++k) R[o++] = M[i][k];
+#pragma unroll
+    for (int k = NFA_TP_NB + NFA_TP_NB * (NFA_TP_NB + 1) / 2; k < NFA_TP_REC; ++k) R[k] = 0.0;
+}
+
+// null_lnZ of a set with templates: -(totsq - ||L^-1 m(d)||^2) / (2 sigma_ref^2), lnl_kernel_tmpl's own value at p = 0
+// (tot = 0 and m(p) = 0 there).  One lane per (pixel, spectrum).
+__global__ void null_lnz_tmpl_kernel(SpecDev S, long n_pix, double *__restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix * S.n_spec) return;
+    const double zero[NFA_TP_NB] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const double chi2 = (S.totsq[i] + 0.0) - tp_quad(S.tp + i * NFA_TP_REC, zero);
     const double noise = S.noise[i];
     out[i] = -chi2 / (2 * (noise * noise));
 }

@@ -227,6 +227,10 @@ struct nfa_specset {
     // a channel response (nfa_specset_set_response): SpecDev.resp and the caller's taps
     double *d_resp = nullptr;
     double  h_resp[MAXSPEC][NFA_RESP_NT] = {};
+    // nuisance templates (nfa_specset_set_templates): SpecDev.tmpl (scaled) and .tp, the caller's values and counts
+    double *d_tmpl = nullptr, *d_tp = nullptr;
+    std::vector<double> h_tmpl;                     // [NFA_TMPL_MAX][chan_tot], unused slots zero; empty without templates
+    int     h_ntmpl[MAXSPEC] = {};
 };
 
 struct nfa_priors {
@@ -449,6 +453,16 @@ static int launch_bl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_b
     return NFA_OK;
 }
 
+// records of a set with templates of pixels [pix0, pix0 + n) (form_basis: the Gram matrix and L^-1 too, not only m(d))
+static int launch_tmpl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form_basis) {
+    const int64_t waves = n * ss->dev.n_spec;
+    hipLaunchKernelGGL(tmpl_setup_kernel, dim3((unsigned)((waves * 64 + 255) / 256)), dim3(256), 0, 0, ss->dev,
+                       (long)pix0, (long)n, ss->d_tp, (int)form_basis);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return NFA_OK;
+}
+
 // The caller's line tables of the hyperfine model (nfa_specset_create_lines): n_lines[n_spec], and the spectra's offsets
 // and weights concatenated; `lte`: the LTE model's record as well (nfa_specset_create_lte), null for the hyperfine model;
 // `band`, `line_nu`: a banded LTE set's record and the rest frequency of every line's own transition
@@ -549,6 +563,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     d.t0tbg = ss->d_t0tbg; d.rowsq = ss->d_rowsq; d.totsq = ss->d_totsq;
     d.bl = nullptr; d.bl_order = -1;                                    // no baseline (nfa_specset_set_baseline)
     d.cal2 = nullptr;                                                   // no calibration uncertainty (nfa_specset_set_calibration)
+    d.tmpl = d.tp = nullptr;                                            // no nuisance templates (nfa_specset_set_templates)
     HIP_TRY(hipMalloc(&ss->d_lines, sizeof(LineRow) * n_spec));
     HIP_TRY(hipMemcpy(ss->d_lines, h_lines.data(), sizeof(LineRow) * n_spec, hipMemcpyHostToDevice));
     d.lines = ss->d_lines;
@@ -967,6 +982,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_cal2);
     (void)hipFree(ss->d_q0); (void)hipFree(ss->d_q1); (void)hipFree(ss->d_q2); (void)hipFree(ss->d_corr);
     (void)hipFree(ss->d_resp);
+    (void)hipFree(ss->d_tmpl); (void)hipFree(ss->d_tp);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
@@ -980,7 +996,8 @@ int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data) {
     if (ss->dev.corr_q1) { rc = launch_corr_setup(ss, pix, 1, false); if (rc) return rc; }      // Q stays, Q d again
     else if (ss->dev.chan_w) { rc = launch_chan_weight(ss, pix, 1, false); if (rc) return rc; }      // the mask stays
     rc = launch_rowsq(ss, pix, 1); if (rc) return rc;
-    return ss->dev.bl ? launch_bl_setup(ss, pix, 1, false) : NFA_OK;                             // the basis stays
+    if (ss->dev.bl) { rc = launch_bl_setup(ss, pix, 1, false); if (rc) return rc; }              // the basis stays
+    return ss->dev.tp ? launch_tmpl_setup(ss, pix, 1, false) : NFA_OK;                           // ... and the templates' too
 }
 
 // What nfa_specset_set_baseline and nfa_specset_set_calibration do before they change a set: held batches were accepted for
@@ -998,16 +1015,25 @@ static int specset_quiesce(nfa_specset *ss) {
 // The weighted arrays and the baseline records as the set's baseline order and calibration ask for them, whichever of the
 // two setters changed last: both run the baseline form (a scalar noise with w == 1; a calibrated set without
 // a baseline with a zeroed record: bl_setup_kernel leaves L^-1 = 0 for order -1 and m(d) as it is), neither needs them.
+// Nuisance templates (SpecDev.tmpl set by nfa_specset_set_templates) run the same weighted form and keep records of their own
+// (SpecDev.tp) beside the baseline's, formed here for the same reason.
 static int specset_form_records(nfa_specset *ss) {
     SpecDev &d = ss->dev;
-    if (d.bl_order < 0 && !d.cal2) {
+    const bool want_bl = d.bl_order >= 0 || d.cal2, want_tp = d.tmpl != nullptr;
+    if (!want_tp) {
+        (void)hipFree(ss->d_tp);
+        ss->d_tp = nullptr; d.tp = nullptr;
+    }
+    if (!want_bl) {
+        (void)hipFree(ss->d_bl);
+        ss->d_bl = nullptr; d.bl = nullptr;
+    }
+    if (!want_bl && !want_tp) {
         if (ss->bl_w1) {                  // back to the scalar set, whose totsq the w == 1 form left as they were
             (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata);
             ss->d_w = ss->d_wdata = nullptr; d.chan_w = d.wdata = nullptr;
             ss->bl_w1 = false;
         }
-        (void)hipFree(ss->d_bl);
-        ss->d_bl = nullptr; d.bl = nullptr;
         return NFA_OK;
     }
     const size_t n = (size_t)(ss->n_pix * d.chan_tot);
@@ -1022,9 +1048,17 @@ static int specset_form_records(nfa_specset *ss) {
         d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
         int rc = launch_chan_weight(ss, 0, ss->n_pix, false); if (rc) return rc;
     }
-    if (!ss->d_bl) HIP_TRY(hipMalloc(&ss->d_bl, sizeof(double) * NFA_BL_REC * ss->n_pix * d.n_spec));
-    d.bl = ss->d_bl;
-    return launch_bl_setup(ss, 0, ss->n_pix, true);
+    if (want_bl) {
+        if (!ss->d_bl) HIP_TRY(hipMalloc(&ss->d_bl, sizeof(double) * NFA_BL_REC * ss->n_pix * d.n_spec));
+        d.bl = ss->d_bl;
+        int rc = launch_bl_setup(ss, 0, ss->n_pix, true); if (rc) return rc;
+    }
+    if (want_tp) {
+        if (!ss->d_tp) HIP_TRY(hipMalloc(&ss->d_tp, sizeof(double) * NFA_TP_REC * ss->n_pix * d.n_spec));
+        d.tp = ss->d_tp;
+        int rc = launch_tmpl_setup(ss, 0, ss->n_pix, true); if (rc) return rc;
+    }
+    return NFA_OK;
 }
 
 int nfa_specset_set_baseline(nfa_specset *ss, int order) {
@@ -1057,6 +1091,7 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
     }
     if (any && d.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no calibration uncertainty");
     if (any && d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no calibration uncertainty");
+    if (any && d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no calibration uncertainty");
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any) {                                               // null, or all zeros: the set's former kernels and bits
@@ -1216,6 +1251,7 @@ int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
         if (ss->masked) return fail(NFA_ERR_ARG, "a set with a masked channel takes no noise correlation");
         if (d.bl_order >= 0) return fail(NFA_ERR_ARG, "a set with a baseline takes no noise correlation");
         if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no noise correlation");
+        if (d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no noise correlation");
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1253,6 +1289,7 @@ int nfa_specset_set_response(nfa_specset *ss, const double *taps) {
         if (ss->masked) return fail(NFA_ERR_ARG, "a set with a masked channel takes no channel response");
         if (d.bl_order >= 0) return fail(NFA_ERR_ARG, "a set with a baseline takes no channel response");
         if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no channel response");
+        if (d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no channel response");
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1267,6 +1304,84 @@ int nfa_specset_response(const nfa_specset *ss, double *out) {
     if (!ss || !ss->dev.resp) return 0;
     for (int s = 0; out && s < ss->dev.n_spec; ++s)
         for (int k = 0; k < NFA_RESP_NT; ++k) out[s * NFA_RESP_NT + k] = ss->h_resp[s][k];
+    return 1;
+}
+
+// The device's state for the caller's templates vals[NFA_TMPL_MAX][chan_tot] (unused slots zero) and counts[n_spec], both
+// valid; null: no templates.  Each template goes up scaled to max |t| = 1 over its spectrum.
+static int tmpl_apply(nfa_specset *ss, const double *vals, const int *counts) {
+    SpecDev &d = ss->dev;
+    if (!vals) {
+        (void)hipFree(ss->d_tmpl);
+        ss->d_tmpl = nullptr; d.tmpl = nullptr;
+        ss->h_tmpl.clear();
+        memset(ss->h_ntmpl, 0, sizeof ss->h_ntmpl);
+        return specset_form_records(ss);
+    }
+    const size_t n = (size_t)d.chan_tot;
+    std::vector<double> scaled(NFA_TMPL_MAX * n, 0.0), keep(vals, vals + NFA_TMPL_MAX * n);
+    for (int s = 0; s < d.n_spec; ++s)
+        for (int k = 0; k < counts[s]; ++k) {
+            const double *t = vals + k * n + d.off[s];
+            double top = 0.0;
+            for (int j = 0; j < d.size[s]; ++j) top = std::max(top, std::fabs(t[j]));
+            for (int j = 0; j < d.size[s]; ++j) scaled[k * n + d.off[s] + j] = t[j] / top;
+        }
+    if (!ss->d_tmpl) HIP_TRY(hipMalloc(&ss->d_tmpl, sizeof(double) * NFA_TMPL_MAX * n));
+    HIP_TRY(hipMemcpy(ss->d_tmpl, scaled.data(), sizeof(double) * NFA_TMPL_MAX * n, hipMemcpyHostToDevice));
+    d.tmpl = ss->d_tmpl;
+    ss->h_tmpl.swap(keep);
+    memset(ss->h_ntmpl, 0, sizeof ss->h_ntmpl);
+    for (int s = 0; s < d.n_spec; ++s) ss->h_ntmpl[s] = counts[s];
+    return specset_form_records(ss);
+}
+
+int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmpl) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    SpecDev &d = ss->dev;
+    const size_t n = (size_t)d.chan_tot;
+    bool any = false;
+    for (int s = 0; t && n_tmpl && s < d.n_spec; ++s) {
+        if (n_tmpl[s] < 0 || n_tmpl[s] > NFA_TMPL_MAX) return fail(NFA_ERR_ARG, "nuisance templates: 0..4 templates per spectrum");
+        any = any || n_tmpl[s] > 0;
+    }
+    std::vector<double> vals;
+    if (any) {
+        vals.assign(NFA_TMPL_MAX * n, 0.0);                   // the slots in use alone are read
+        for (int s = 0; s < d.n_spec; ++s)
+            for (int k = 0; k < n_tmpl[s]; ++k) {
+                const double *v = t + k * n + d.off[s];
+                bool zero = true;
+                for (int j = 0; j < d.size[s]; ++j) {
+                    if (!std::isfinite(v[j])) return fail(NFA_ERR_ARG, "nuisance templates: every value is finite");
+                    zero = zero && v[j] == 0.0;
+                    vals[k * n + d.off[s] + j] = v[j];
+                }
+                if (zero) return fail(NFA_ERR_ARG, "nuisance templates: a template is zero over its whole spectrum");
+            }
+        if (d.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no nuisance templates");
+        if (d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no nuisance templates");
+        if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no nuisance templates");
+    }
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    if (!any && !d.tmpl) return NFA_OK;                       // null, or no template anywhere, and none before: nothing changes
+    const std::vector<double> was = ss->h_tmpl;
+    int was_n[MAXSPEC];
+    memcpy(was_n, ss->h_ntmpl, sizeof was_n);
+    rc = tmpl_apply(ss, any ? vals.data() : nullptr, n_tmpl);
+    if (rc) {                                                 // the set stays as it was: its former templates, or none
+        const std::string why = g_err;
+        (void)tmpl_apply(ss, was.empty() ? nullptr : was.data(), was_n);
+        g_err = why;
+    }
+    return rc;
+}
+
+int nfa_specset_templates(const nfa_specset *ss, double *out_t, int *out_n) {
+    if (!ss || !ss->dev.tmpl) return 0;
+    if (out_t) memcpy(out_t, ss->h_tmpl.data(), sizeof(double) * ss->h_tmpl.size());
+    for (int s = 0; out_n && s < ss->dev.n_spec; ++s) out_n[s] = ss->h_ntmpl[s];
     return 1;
 }
 
@@ -1289,7 +1404,9 @@ int nfa_specset_null_lnz(const nfa_specset *ss, double *out) {
     const int64_t n = ss->n_pix * ss->dev.n_spec;
     double *d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(double) * n));
-    if (ss->dev.bl_order >= 0)                                // the baseline-only model (a calibrated set's zeroed record is no baseline)
+    if (ss->dev.tmpl)                                         // the model of baseline and templates alone
+        hipLaunchKernelGGL(null_lnz_tmpl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
+    else if (ss->dev.bl_order >= 0)                           // the baseline-only model (a calibrated set's zeroed record is no baseline)
         hipLaunchKernelGGL(null_lnz_bl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
     else
         hipLaunchKernelGGL(ss->dev.chan_w ? null_lnz_w_kernel : null_lnz_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0,
@@ -1715,6 +1832,22 @@ static LnlKernel lnl_kernel_resp_of(int mode, bool write_spec, const LnlPlan &P)
     return lnl_kernel_resp_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
                               std::make_index_sequence<32>());
 }
+// ... and of a set with nuisance templates: lnl_kernel_tmpl over the same five, with the baseline form's plan (plan_lnl's
+// `templates`: nine sums per part)
+template <int I>
+static LnlKernel lnl_kernel_tmpl_inst() {
+    return lnl_kernel_tmpl<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_tmpl_at(int i, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])() = {lnl_kernel_tmpl_inst<(int)I>...};
+    return inst[i]();
+}
+static LnlKernel lnl_kernel_tmpl_of(int mode, bool write_spec, const LnlPlan &P) {
+    if (P.form != LNL_BASELINE) return nullptr;
+    return lnl_kernel_tmpl_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
+                              std::make_index_sequence<32>());
+}
 #ifdef NFA_TEST_HOOKS
 #include <atomic>
 // Likelihood launches by (lnl_inst_index, LnlForm) since the last reset (nfa_test_lnl_launches): host side, counted where
@@ -1740,13 +1873,14 @@ static void count_lnl_launch(LnlKernel kern) {
 static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, int64_t B, int mode) {
     SpecDev S = runner_specdev(r);
     S.band_tau = r->d_band[slot];                             // (null unless the set is banded)
-    LnlPlan P = plan_lnl(r->shape, plan_knobs(), plan_launch(r, B, mode, d_spec != nullptr, false, slot));
+    LnlPlan P = plan_lnl(r->shape, plan_knobs(), plan_launch(r, B, mode, d_spec != nullptr, false, slot), S.tmpl != nullptr);
     if (P.error) return fail(NFA_ERR_ARG, P.error);
     if (P.form == LNL_QUEUE) P.G.queue = r->d_queue[slot];
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = S.resp ? lnl_kernel_resp_of(mode, d_spec != nullptr, P)
+    const LnlKernel kern = S.tmpl ? lnl_kernel_tmpl_of(mode, d_spec != nullptr, P)
+                         : S.resp ? lnl_kernel_resp_of(mode, d_spec != nullptr, P)
                          : S.corr_q1 ? lnl_kernel_corr_of(mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
 #ifdef NFA_TEST_HOOKS
@@ -1959,7 +2093,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
     const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
-                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr);
+                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

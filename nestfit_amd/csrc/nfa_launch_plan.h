@@ -31,6 +31,7 @@
 #define SM_TABLE_TAIL 768               // doubles that must follow the staged tables in LDS (row 15 of A ends there)
 #define SM_TABLE_DOUBLES (SM_END_TABLE - SM_EXP2)   // the table mode's staged tables: 6656 doubles, 52 KB
 #define NFA_BL_NB  4            // moments every baseline form accumulates: P_0..P_3, whatever the order
+#define NFA_TP_NB  (NFA_BL_NB + NFA_TMPL_MAX)   // ... and every form with nuisance templates: those and t_1..t_4, whatever their number
 #define LNL_PARTS 4      // row parts of a unit: the fixed shape of its chi^2 sum
 // (eight since round 5, four before: a table-mode launch spends its tail with fewer and fewer waves per SIMD, and eight
 // batches in a launch halve that share: profiles/r05/queue_timeline.txt, 86.3 -> 87.8 M evaluations/s on the metric shape)
@@ -156,9 +157,11 @@ inline LnlGeom lnl_geom(const LpShape &s, const LpKnobs &k, int64_t B) {
     return G;
 }
 
-// per-lane sums a part of a unit leaves in LDS when several waves share the unit: chi^2's, a baseline's NFA_BL_NB moments,
-// a calibrated set's sum w p^2
-inline int lnl_part_slots(bool baseline, bool calibrated) { return 1 + (baseline ? NFA_BL_NB : 0) + (calibrated ? 1 : 0); }
+// per-lane sums a part of a unit leaves in LDS when several waves share the unit: chi^2's, a baseline's NFA_BL_NB moments
+// (with nuisance templates: NFA_TP_NB), a calibrated set's sum w p^2
+inline int lnl_part_slots(bool baseline, bool calibrated, bool templates = false) {
+    return 1 + (templates ? NFA_TP_NB : baseline ? NFA_BL_NB : 0) + (calibrated ? 1 : 0);
+}
 // Waves per workgroup of a launch with `split` waves per unit: option wpb, made a multiple of the split.  Table mode stages
 // 51 KB of product tables per workgroup, so the workgroup is made as fat as keeps the most waves resident per CU
 // (table_waves); its split launches take eight.
@@ -226,7 +229,9 @@ constexpr bool lnl_inst_round_trip() {
 }
 static_assert(lnl_inst_round_trip(), "lnl_inst_at must invert lnl_inst_index over the whole table");
 // Plans the likelihood launch of L.B items (the table of forms in DESIGN 4.2 is tested against this chain).
-inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
+// templates: the set has nuisance templates (nfa_specset_set_templates): the baseline form's plan over nine
+// sums per part, for lnl_kernel_tmpl (beside the table: the plan names no instance of it).
+inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L, bool templates = false) {
     LnlPlan P = {};
     const int64_t units = L.B * s.n_spec;
     if (units * 8 >= (1LL << 28)) { P.error = "batch too large for one launch"; return P; }
@@ -247,9 +252,11 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     // (G.split is lowered after lnl_geom filled G: of LnlGeom only `split` itself depends on the split -- nhf_max,
     // wave_doubles, inv_nspec and inv_nhf are the runner's -- and waves, LDS and workgroups are computed below from the
     // lowered value.  The GPU suite launches the waves = split case; the halving is held to its arithmetic without a GPU only.)
-    if (L.calibrated && lnl_units_lds(s, table, P.G.split, waves, lnl_part_slots(true, true)) > LDS_PER_CU) {
+    // A set with templates keeps nine sums per part, and plans by the same rule.
+    const int slots_most = lnl_part_slots(true, L.calibrated, templates);
+    if ((L.calibrated || templates) && lnl_units_lds(s, table, P.G.split, waves, slots_most) > LDS_PER_CU) {
         waves = P.G.split;
-        while (P.G.split > 1 && lnl_units_lds(s, table, P.G.split, waves, lnl_part_slots(true, true)) > LDS_PER_CU) waves = P.G.split /= 2;
+        while (P.G.split > 1 && lnl_units_lds(s, table, P.G.split, waves, slots_most) > LDS_PER_CU) waves = P.G.split /= 2;
     }
     const int split = P.G.split;
     P.waves = waves;
@@ -263,7 +270,7 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     const bool fills_twice = units >= 2 * ((int64_t)k.n_cu * wg_per_cu) * waves;
     // The form: the first line that applies.
     P.form = LNL_PLAIN;
-    if (L.calibrated) P.form = LNL_BASELINE;         // a calibration uncertainty: the baseline form (a zeroed record without one)
+    if (L.calibrated || templates) P.form = LNL_BASELINE;      // a calibration uncertainty, templates: the baseline form (whatever the order)
     else if (L.baseline) P.form = LNL_BASELINE;      // every mode, wide, spectra out; such a set is weighted too
     else if (L.weighted) P.form = LNL_WEIGHTED;      // every mode, wide, spectra out: no queue or w8 form of its own (the
                                                      // units give the same bits whatever the form, so none is instantiated)
@@ -279,7 +286,7 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L) {
     // LDS: [table mode: the product tables][per unit of the workgroup: the line table; split > 1: the parts' sums
     // (a baseline: and those of the moments of the unit; calibrated: and that of sum w p^2)][queue: the workgroup's queue word and count]
     const int n_shared = table ? SM_TABLE_DOUBLES : 0;
-    P.lds = lnl_units_lds(s, table, split, waves, lnl_part_slots(P.form == LNL_BASELINE, L.calibrated)) + (queue ? 16 : 0);
+    P.lds = lnl_units_lds(s, table, split, waves, lnl_part_slots(P.form == LNL_BASELINE, L.calibrated, templates)) + (queue ? 16 : 0);
     if (table) P.lds = std::max(P.lds, sizeof(double) * (size_t)(n_shared + SM_TABLE_TAIL));
     if (P.lds > LDS_PER_CU) { P.error = "ncomp too large for the LDS line table"; return P; }
     if (!table && s.lnl_cap > 0 && waves * s.lnl_cap < LP_WAVES_PER_CU)      // residency cap: see Engine::lnl_cap
@@ -352,15 +359,18 @@ struct FusedPlan { const char *refusal, *ring_error; LnlGeom G; int n_blocks, ct
 // only -- such a set is weighted too, and the weighted sum alone would leave out the products of neighbouring channels)
 // response: a set with a channel response (nfa_specset_set_response: the batch kernels only, and refused before everything
 // else -- such a set is "correlated" to its kernels even over white noise, and the reason must be its own)
+// templates: a set with nuisance templates (nfa_specset_set_templates: the batch kernels only -- such a set is weighted too,
+// and the reason must be its own)
 inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted, bool banded = false,
                             bool filled = false, bool layered = false, bool calibrated = false, bool correlated = false,
-                            bool response = false) {
+                            bool response = false, bool templates = false) {
     FusedPlan P = {};
     P.G = lnl_geom(s, k, 1);
     if (response) P.refusal = "the resident kernel has no form for a channel response: use nfa_ring_serve";
     else if (correlated) P.refusal = "the resident kernel has no form for correlated channel noise: use nfa_ring_serve";
     else if (calibrated) P.refusal = "the resident kernel has no form for a calibration uncertainty: use nfa_ring_serve";
     else if (layered) P.refusal = "the resident kernel has no form for layered transfer: use nfa_ring_serve";
+    else if (templates) P.refusal = "the resident kernel has no form for nuisance templates: use nfa_ring_serve";
     else if (s.ndim > NFA_POINT_MAXDIM || lnl_wide(s)) P.refusal = "this runner's points go through the batch kernels: use nfa_ring_serve";
     else if (filled) P.refusal = "the resident kernel has no form for a filling factor: use nfa_ring_serve";
     // (weighted sets, baseline sets among them: the fused kernels run the unweighted body, which would compute the unweighted sum.)

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, gain_fit
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, check_templates, gain_fit, nuisance_fit
 from .core import _as_inplace_matrix
 
 
@@ -55,11 +55,15 @@ class CubeRunner:
     response : None, or the channel response of the spectrometer (3 or 5 taps such as `HANNING_RESPONSE`, or an array
         [n_spec, 3 | 5]; shared by all pixels) with which the model is convolved before it meets the data; not
         with masked channels, a baseline or a calibration; null_lnZ is unchanged
+    templates : None, or a list with one entry per spectrum, each None or an array [T, N_s] of 1..4 fixed shapes on the
+        spectrum's channels (`ripple(n_chan, period)`: a standing wave of known period; shared by all pixels) whose amplitudes
+        are profiled out of the likelihood per (pixel, spectrum) together with the baseline; not with a
+        calibration, a correlation or a response; null_lnZ is then the model of baseline and templates alone
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
                  model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False,
-                 calibration=None, correlation=None, response=None):
+                 calibration=None, correlation=None, response=None, templates=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
@@ -74,6 +78,7 @@ class CubeRunner:
         masked = np.shape(noise)[-1] == sum(sizes) and not np.all(np.isfinite(noise))
         correlation = check_correlation(correlation, len(xarrs), sizes, masked, baseline_order, calibration)
         response = check_response(response, len(xarrs), sizes, masked, baseline_order, calibration)
+        templates = check_templates(templates, len(xarrs), sizes, calibration, correlation, response)
         if species is None and int(model) == 4 and lines is not None:
             from .lte import LteBand, LteBlend, LteLines, lines_species
             lines = list(lines)
@@ -96,6 +101,8 @@ class CubeRunner:
             self._ss.set_correlation(correlation)
         if response is not None:
             self._ss.set_response(response)
+        if templates is not None:
+            self._ss.set_templates(templates)
         self._data, self._noise = data, noise                # (fit_baseline, fit_gain)
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -153,7 +160,10 @@ class CubeRunner:
     def fit_baseline(self, pix, theta):
         """Best-fit baselines [B, n_chan_tot] of physical parameter rows theta[B, ndim] against pixels pix[B]: the
         polynomials the likelihood profiles out, fitted with numpy to data - predict_batch (for residual plots, not the
-        hot path).  ValueError without a baseline."""
+        hot path).  A runner with nuisance templates returns the whole nuisance curve, polynomial and templates.  ValueError
+        without a baseline and without templates."""
+        if self._ss.templates is not None:
+            return self._fit_nuisance(pix, theta)[0]
         if self.baseline_order is None:
             raise ValueError('this runner has no baseline (baseline_order=None)')
         pix = np.ascontiguousarray(pix, dtype=np.int32)
@@ -168,6 +178,49 @@ class CubeRunner:
             resid = np.where(w > 0, data[:, sl] - spec[:, sl], 0.0)
             out[:, sl] = baseline_fit(resid, w, self.baseline_order)
         return out
+
+    def _fit_nuisance(self, pix, theta):
+        """(curves [B, n_chan_tot], amplitudes: per spectrum [B, T]) of `nuisance_fit` on data - predict_batch."""
+        tmpl = self._ss.templates
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        spec, _ = self.predict_batch(pix, theta)
+        data = np.asarray(self._data, dtype=np.float64)[pix]
+        noise = np.asarray(self._noise, dtype=np.float64)[pix]
+        off = self._ss.offsets
+        out = np.empty_like(spec)
+        amps = [np.zeros((len(pix), 0 if t is None else t.shape[0])) for t in tmpl]
+        for k in range(self.n_spec):
+            sl = slice(off[k], off[k + 1])
+            for b in range(len(pix)):
+                w = 1.0 / noise[b, sl] ** 2 if self._ss.per_channel else np.ones(off[k + 1] - off[k])
+                resid = np.where(w > 0, data[b, sl] - spec[b, sl], 0.0)
+                out[b, sl], amps[k][b] = nuisance_fit(resid, w, self.baseline_order, tmpl[k])
+        return out, amps
+
+    def fit_templates(self, pix, theta):
+        """Best-fit amplitudes of the templates, in the caller's scaling, of physical parameter rows theta[B, ndim] against
+        pixels pix[B]: a list of n_spec arrays [B, T].  numpy on `predict_batch`'s spectra.  ValueError without templates."""
+        if self._ss.templates is None:
+            raise ValueError('this runner has no nuisance templates (templates=None)')
+        return self._fit_nuisance(pix, theta)[1]
+
+    @property
+    def templates(self):
+        """None, or the list of the spectra's nuisance templates: per spectrum None or a float64 array [T, N_s]."""
+        tmpl = self._ss.templates
+        return None if tmpl is None else [None if a is None else a.copy() for a in tmpl]
+
+    def set_templates(self, tmpl):
+        """Sets (a list with an array [T, N_s] or None per spectrum) or removes (None) the nuisance templates; null_lnZ
+        follows."""
+        self._ss.set_templates(tmpl)
+        self.null_lnZ = self._ss.null_lnZ().sum(axis=1)
+
+    def set_baseline(self, order):
+        """Sets (0..3) or removes (None) the baseline; null_lnZ follows."""
+        self._ss.set_baseline(order)
+        self.baseline_order = self._ss.baseline_order
+        self.null_lnZ = self._ss.null_lnZ().sum(axis=1)
 
     @property
     def response(self):

@@ -5,7 +5,7 @@ nestfit/models/hyperfine.pyx:52-118).  Parameters per component: voff, tex, ltau
 """
 import numpy as np
 
-from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, spec_data_sizes_masked, par_names
+from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
 from .core import HyperfineSpectrum
 
 N_LEVELS = 3
@@ -46,13 +46,13 @@ class DiazenyliumRunner(EngineRunner):
     MODEL = MODEL_DIAZENYLIUM
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response)
+                    calibration=calibration, correlation=correlation, response=response, templates=templates)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -63,6 +63,8 @@ class DiazenyliumRunner(EngineRunner):
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
                        baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
+        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
+                        kwargs.get('correlation'), kwargs.get('response'))
         spectra = np.array([DiazenyliumSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

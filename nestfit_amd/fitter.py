@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import sampler
-from ._model import check_calibration, check_correlation, check_layered, check_response
+from ._model import check_calibration, check_correlation, check_layered, check_response, check_templates
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
@@ -86,6 +86,9 @@ class CubeFitter:
         # a channel response (runner_kwargs['response']): and this
         self.response = check_response(self.runner_kwargs.get('response'), None if cubes is None else len(cubes),
                                        baseline_order=self.runner_kwargs.get('baseline_order'), calibration=self.calibration)
+        # nuisance templates (runner_kwargs['templates']): and these
+        self.templates = check_templates(self.runner_kwargs.get('templates'), None if cubes is None else len(cubes),
+                                         calibration=self.calibration, correlation=self.correlation, response=self.response)
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
         self.lnZ_thresh, self.ncomp_max, self.nlive_snr_fact = lnZ_thresh, ncomp_max, nlive_snr_fact
         self.nlive_quantum = max(1, int(nlive_quantum))

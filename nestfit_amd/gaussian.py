@@ -7,7 +7,7 @@ radiative-transfer pass.
 import numpy as np
 
 from . import core
-from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, spec_data_sizes_masked, par_names
+from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
 
 N_PARAMS = 3
 
@@ -33,13 +33,13 @@ class GaussianRunner(EngineRunner):
     MODEL = MODEL_GAUSSIAN
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectrum, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None):
+    def __init__(self, spectrum, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         check_layered(layered, MODEL_GAUSSIAN)                        # ValueError for True: no optical depth, nothing absorbs
         self.spectrum = spectrum
         self._setup([spectrum], utrans, ncomp, rest_freqs=[float(spectrum.rest_freq)], baseline_order=baseline_order,
-                    calibration=calibration, correlation=correlation, response=response)
+                    calibration=calibration, correlation=correlation, response=response, templates=templates)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -50,6 +50,8 @@ class GaussianRunner(EngineRunner):
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), 1, *spec_data_sizes_masked([spec_data]),
                        baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
+        check_templates(kwargs.get('templates'), 1, spec_data_sizes_masked([spec_data])[0], kwargs.get('calibration'),
+                        kwargs.get('correlation'), kwargs.get('response'))
         return cls(Spectrum(*spec_data), utrans, **kwargs)
 
     def get_spectrum(self):

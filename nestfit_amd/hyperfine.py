@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _ffi
 from ._model import (MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, EngineRunner, EngineSpectrumMixin,
-                     check_baseline_order, check_calibration, check_correlation, check_layered, check_response, spec_data_sizes_masked, par_names)
+                     check_baseline_order, check_calibration, check_correlation, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names)
 from .core import HyperfineSpectrum as _HyperfineBase
 
 N_PARAMS = 4
@@ -133,13 +133,13 @@ class HyperfineRunner(EngineRunner):
     MODEL = MODEL_HYPERFINE
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response)
+                    calibration=calibration, correlation=correlation, response=response, templates=templates)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -151,6 +151,8 @@ class HyperfineRunner(EngineRunner):
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
                        baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
+        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
+                        kwargs.get('correlation'), kwargs.get('response'))
         spectra = np.array([HyperfineSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

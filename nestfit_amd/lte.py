@@ -47,7 +47,7 @@ function come from a catalogue of the user's.
 """
 import numpy as np
 
-from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, spec_data_sizes_masked, par_names
+from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
 from .core import HyperfineSpectrum as _HyperfineBase
 from .hyperfine import CKMS, MAX_LINES, LineTable
 
@@ -405,14 +405,14 @@ class LteRunner(EngineRunner):
     MODEL = MODEL_LTE
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
         self.molecule = check_one_molecule([s.lines for s in self.spectra])
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response)
+                    calibration=calibration, correlation=correlation, response=response, templates=templates)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -424,6 +424,8 @@ class LteRunner(EngineRunner):
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
                        baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
+        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
+                        kwargs.get('correlation'), kwargs.get('response'))
         spec_data = list(spec_data)
         check_one_molecule([row[3] for row in spec_data])
         spectra = np.array([LteSpectrum(*args) for args in spec_data])
@@ -546,7 +548,7 @@ class _MixRunner(EngineRunner):
     MODEL = MODEL_LTE
     MIX = None
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
@@ -554,7 +556,7 @@ class _MixRunner(EngineRunner):
         check_mix_lines(self.MIX.species, [s.lines for s in self.spectra])
         self.species = self.MIX.species
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response)
+                    calibration=calibration, correlation=correlation, response=response, templates=templates)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -566,6 +568,8 @@ class _MixRunner(EngineRunner):
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
                        baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
+        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
+                        kwargs.get('correlation'), kwargs.get('response'))
         spec_data = list(spec_data)
         check_mix_lines(cls.MIX.species, [row[3] for row in spec_data])
         spectra = np.array([cls.MIX.Spectrum(*args) for args in spec_data])

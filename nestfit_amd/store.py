@@ -24,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import hdf5
-from ._model import check_calibration, check_correlation, check_response
+from ._model import check_calibration, check_correlation, check_response, check_templates
 
 HDF5_SUFFIXES = ('.hdf', '.h5', '.hdf5')
 
@@ -447,6 +447,15 @@ class HdfStore:
         resp = check_response((getattr(fitter, 'runner_kwargs', None) or {}).get('response'), None if cubes is None else len(cubes))
         if resp is not None:
             self.hdf.attrs['channel_response'] = resp
+        # nuisance templates (runner_kwargs['templates']): root group `nuisance_templates`, one float64 dataset
+        # spec<k> [T, n_chan] per spectrum that has any.  A store without the group was fitted without templates.
+        tmpl = check_templates((getattr(fitter, 'runner_kwargs', None) or {}).get('templates'), None if cubes is None else len(cubes))
+        if tmpl is not None:
+            group = self.hdf.create_group('nuisance_templates')
+            group.attrs['n_spec'] = len(tmpl)
+            for k, a in enumerate(tmpl):
+                if a is not None:
+                    group.create_dataset(f'spec{k}', data=a)
         quantum = getattr(fitter, 'nlive_quantum', 1)
         if quantum != 1:                 # a deviation from main.py:445-447 is written down where the results are
             self.hdf.attrs['nlive_quantum'] = int(quantum)
@@ -487,6 +496,17 @@ class HdfStore:
         assert self.is_open
         resp = self.hdf.attrs.get('channel_response')
         return None if resp is None else np.asarray(resp, dtype=np.float64).reshape(-1, 5)
+
+    def read_model_templates(self):
+        """The nuisance templates the store was fitted with (`runner_kwargs={'templates': ...}`): the root group
+        `nuisance_templates` as a list with one entry per spectrum, None or a float64 array [T, n_chan]; None for a store
+        without it."""
+        assert self.is_open
+        if 'nuisance_templates' not in self.hdf:
+            return None
+        group = self.hdf['nuisance_templates']
+        return [np.asarray(group[f'spec{k}'][...], dtype=np.float64) if f'spec{k}' in group else None
+                for k in range(int(group.attrs['n_spec']))]
 
     def read_model_fill(self):
         """Whether the store was fitted with a beam filling factor per component (`LteMix(species, fill=True)`): the root
