@@ -404,6 +404,30 @@ int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmp
 /* 1, out_t[NFA_TMPL_MAX][sum(sizes)] = the values set (unused slots zero) and out_n[n_spec] = the counts (either may be
  * null), or 0 for a set without templates (and for null) */
 int nfa_specset_templates(const nfa_specset *ss, double *out_t, int *out_n);
+/* An uncertain noise level per spectrum, integrated out of the likelihood in closed form (no sampler dimension, DESIGN
+ * 4.16).  The true noise of spectrum s is t sigma_c, sigma_c the set's scalar or per-channel noise and t one unknown scale
+ * for all its channels; the precision tau = 1 / t^2 has a Gamma prior of shape a and rate a (mean 1), a = 1 / (4 f^2) for the
+ * fractional 1-sigma uncertainty f[s] of the noise level (std(tau) = 2 f to first order).  With nu the unmasked channels of
+ * the (pixel, spectrum) and X = chi2_s / sigma_ref^2 whatever the set's kind makes of it (baseline, templates, correlation
+ * and response included):
+ *     lnL = sum_s -(a_s + nu_s / 2) log1p( (chi2_s / (2 sigma_s^2)) / a_s )
+ * constants dropped as everywhere.  f -> 0 gives -chi2 / (2 sigma^2); a spectrum with f[s] = 0 keeps that expression to the
+ * bit.  nfa_specset_null_lnz is the same function of the set's own null value (what it returns without the uncertainty): the
+ * likelihood at p = 0 to rounding, and to the bit where the two already agree to the bit (spectra of 64 channels and less).  A
+ * row with a NaN parameter or NaN data is NaN, as in every set.  nu counts channels only (the profile
+ * convention): it does not subtract the rank of a baseline or of templates, depends on the masks alone, and the call
+ * commutes with nfa_specset_set_baseline, _set_templates, _set_correlation and _set_response.
+ * f[n_spec], shared by all pixels; f = NULL or all zeros removes it (the set's former results bit for bit).  NFA_ERR_ARG,
+ * the set left as it was, before any device call: a value that is not finite or lies outside [0, 0.5] ("a noise
+ * uncertainty is ...": above 0.5 the first-order relation between f and a means nothing); a set with a calibration
+ * uncertainty, whose part is no chi^2 -- and nfa_specset_set_calibration refuses a set with a noise uncertainty in the
+ * same words.  No likelihood kernel changes: every set kind, launch form, single points, a broker, nfa_ring_serve,
+ * nfa_ring_serve_device and the device sampler serve such a set.  Like nfa_specset_set_calibration it launches held
+ * batches first, synchronises the device and drops the runners' captured single-point graphs: call it between batches.
+ * nfa_specset_set_data keeps it.  Spectra out are unchanged. */
+int nfa_specset_set_noise_uncertainty(nfa_specset *ss, const double *f);
+/* 1 and out[n_spec] = the values set (out may be null), or 0 for a set without a noise uncertainty (and for null) */
+int nfa_specset_noise_uncertainty(const nfa_specset *ss, double *out);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

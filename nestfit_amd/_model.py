@@ -308,6 +308,107 @@ def spec_data_sizes_masked(spec_data):
     return sizes, masked
 
 
+NOISE_UNCERTAINTY_MAX = 0.5
+_NUNC_CALIB = 'a noise uncertainty does not go with a calibration uncertainty (calibration): a calibrated spectrum\'s part is no chi^2'
+
+
+def check_noise_uncertainty(f, n_spec=None, calibration=None):
+    """`noise_uncertainty` of a runner: the fractional 1-sigma uncertainty of every spectrum's noise level.
+    None for none; a number applies to all `n_spec` spectra; else one value per spectrum.  Every value is a finite number
+    in [0, 0.5] (above that the first-order relation a = 1 / (4 f^2) means nothing); all zeros is None.  Not with a
+    calibration uncertainty (`calibration`).  Returns None or a float64 array (of n_spec values when n_spec is given);
+    ValueError otherwise.  Needs no device."""
+    if f is None:
+        return None
+    what = 'noise uncertainty (noise_uncertainty) must be None, a number in [0, 0.5] or one such number per spectrum'
+    is_num = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    if is_num(f):
+        vals = [f] * (1 if n_spec is None else int(n_spec))
+    elif isinstance(f, np.ndarray) and f.ndim == 1 and f.dtype.kind in 'iuf':
+        vals = list(f)
+    elif isinstance(f, (list, tuple)) and all(is_num(v) for v in f):
+        vals = list(f)
+    else:
+        raise ValueError(f'{what}, not {f!r}')
+    if not is_num(f) and n_spec is not None and len(vals) != int(n_spec):
+        raise ValueError(f'{what}: {len(vals)} values for {int(n_spec)} spectra')
+    out = np.array(vals, dtype=np.float64)
+    if out.size == 0 or not np.all(np.isfinite(out)) or np.any(out < 0.0) or np.any(out > NOISE_UNCERTAINTY_MAX):
+        raise ValueError(f'{what}, not {f!r}')
+    if not np.any(out > 0.0):
+        return None
+    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
+        raise ValueError(_NUNC_CALIB)
+    return out
+
+
+def noise_shape(f):
+    """Shape (= rate) a = 1 / (4 f^2) of the Gamma prior of the noise precision tau = 1 / t^2 for a fractional uncertainty f
+    of the noise level: mean 1, std(tau) = 1 / sqrt(a) = 2 f, i.e. std(t) = f to first order."""
+    f = np.asarray(f, dtype=np.float64)
+    return 1.0 / (4.0 * f * f)
+
+
+def noise_marginal_lnl(half_chi2, nu, f):
+    """The log-likelihood term of a spectrum whose noise level has the fractional uncertainty f:
+    -(a + nu / 2) log1p(h / a) for h = chi^2 / (2 sigma^2) >= 0 and nu unmasked channels; -h for f = 0.  numpy, elementwise."""
+    h, nu, f = np.broadcast_arrays(np.asarray(half_chi2, dtype=np.float64), np.asarray(nu, dtype=np.float64),
+                                   np.asarray(f, dtype=np.float64))
+    on = f > 0.0
+    a = noise_shape(np.where(on, f, 1.0))
+    out = np.where(on, -(a + nu / 2.0) * np.log1p(np.maximum(h, 0.0) / a), -h)
+    return out if out.ndim else float(out)
+
+
+def half_chi2(data, pred, noise, order=None, templates=None, corr=None, resp=None):
+    """(h, nu) of ONE spectrum at a model `pred`: h = chi^2 / (2 sigma^2) as a spectra set forms it and nu the unmasked
+    channels.  `noise` is a scalar or one value per channel (inf: masked); `order` and `templates` are profiled out
+    (`nuisance_fit`), `resp` (five taps) filters the model first and `corr` = (rho_1, rho_2) correlates the noise
+    (`corr_bands`).  numpy on the host."""
+    d, p = np.asarray(data, dtype=np.float64), np.asarray(pred, dtype=np.float64)
+    n = d.shape[0]
+    sig = np.broadcast_to(np.asarray(noise, dtype=np.float64), (n,))
+    live = np.isfinite(sig)
+    if resp is not None:
+        p = np.correlate(p, np.asarray(resp, dtype=np.float64), 'same')          # p~_j = sum_k h_k p_{j+k}, 0 beyond the ends
+    w = np.where(live, 1.0 / np.where(live, sig, 1.0) ** 2, 0.0)
+    r = np.where(live, d - p, 0.0)
+    if order is not None or templates is not None:
+        r = np.where(live, r - nuisance_fit(r, w, order, templates)[0], 0.0)
+    e = r * np.sqrt(w)
+    if corr is None or (corr[0] == 0.0 and corr[1] == 0.0):
+        chi2 = float(np.sum(e * e))
+    else:
+        d0, d1, d2 = corr_bands(float(corr[0]), float(corr[1]), n)
+        chi2 = float(np.sum(d0 * e * e) + 2.0 * np.sum(d1 * e[:-1] * e[1:]) + 2.0 * np.sum(d2 * e[:-2] * e[2:]))
+    return 0.5 * chi2, int(np.count_nonzero(live))
+
+
+def noise_fit(h, nu, f):
+    """Posterior (mean, standard deviation) of the noise scale t of ONE spectrum, true noise = t * stated noise, at a model
+    with h = chi^2 / (2 sigma^2) (`half_chi2`) over `nu` unmasked channels: tau = 1 / t^2 given the data is
+    Gamma(c, rate r) with c = a + nu / 2 and r = a + h, so E t^k = r^(k/2) Gamma(c - k/2) / Gamma(c).  (1, 0) for f = 0."""
+    from math import exp, lgamma, sqrt
+    if not f > 0.0:
+        return 1.0, 0.0
+    a = float(noise_shape(f))
+    c, r = a + nu / 2.0, a + max(float(h), 0.0)
+    m1 = sqrt(r) * exp(lgamma(c - 0.5) - lgamma(c))
+    m2 = r / (c - 1.0) if c > 1.0 else np.inf                 # (c = 1: f = 0.5 and no channel at all)
+    return m1, sqrt(max(m2 - m1 * m1, 0.0))
+
+
+def noise_prefactor(nu, f):
+    """What `Spectrum.prefactor` gains with a noise uncertainty f over nu unmasked channels: the theta-independent constant
+    lgamma(a + nu / 2) - lgamma(a) - (nu / 2) ln a of the marginal (0 for f = 0), which makes -(a + nu/2) log1p(h / a) +
+    prefactor the log of the normalised marginal density as -h + prefactor is at a known noise."""
+    from math import lgamma, log
+    if f is None or not f > 0.0:
+        return 0.0
+    a = float(noise_shape(f))
+    return lgamma(a + nu / 2.0) - lgamma(a) - (nu / 2.0) * log(a)
+
+
 def gain_fit(data, pred, weight, sigma, cal, order=None):
     """Posterior (mean, standard deviation) of the gain of ONE spectrum at a given model `pred`: data =
     g pred + baseline + noise, g ~ N(1, cal^2), channel weights `weight` (0: masked), sigma the noise of weight 1; with a
@@ -476,6 +577,7 @@ class _SpecSet:
         self.correlation = None
         self.response = None
         self.templates = None
+        self.noise_uncertainty = None
         self.masked = bool(self.per_channel and not np.all(np.isfinite(noise)))
 
     def set_templates(self, tmpl):
@@ -522,10 +624,20 @@ class _SpecSet:
         _ffi.check(_ffi.load().nfa_specset_set_correlation(self.handle, None if corr is None else _ffi.dptr(corr)))
         self.correlation = corr
 
+    def set_noise_uncertainty(self, f):
+        """The fractional uncertainty of every spectrum's noise level, integrated out of the likelihood
+        (`check_noise_uncertainty`'s argument), or none (None, zeros): nfa_specset_set_noise_uncertainty.  null_lnZ()
+        follows."""
+        f = check_noise_uncertainty(f, self.n_spec, self.calibration)
+        _ffi.check(_ffi.load().nfa_specset_set_noise_uncertainty(self.handle, None if f is None else _ffi.dptr(f)))
+        self.noise_uncertainty = f
+
     def set_calibration(self, cal):
         """A calibration uncertainty per spectrum, integrated out of the likelihood (`check_calibration`'s argument), or
         none (None, zeros): nfa_specset_set_calibration.  null_lnZ() does not change."""
         cal = check_calibration(cal, self.n_spec)
+        if cal is not None and self.noise_uncertainty is not None:
+            raise ValueError(_NUNC_CALIB)
         if cal is not None and self.response is not None:
             raise ValueError('a calibration uncertainty does not go with a channel response (response)')
         if cal is not None and self.correlation is not None:
@@ -665,8 +777,12 @@ class EngineRunner(Runner):
     N_MODEL = 6
 
     def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False,
-               calibration=None, correlation=None, response=None, templates=None):
-        """templates: None, or a list with one entry per spectrum, each None or an array [T, N_s] of 1..4 fixed shapes on the
+               calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None):
+        """noise_uncertainty: None, or the fractional 1-sigma uncertainty of the spectra's noise levels -- a number for all of
+        them or one per spectrum, each in [0, 0.5] -- integrated out of the likelihood in closed form per spectrum
+        (nfa_specset_set_noise_uncertainty); all zeros is None.  Goes with everything but a calibration.
+        null_lnZ is then the same function of the parts at p = 0.
+        templates: None, or a list with one entry per spectrum, each None or an array [T, N_s] of 1..4 fixed shapes on the
         spectrum's channels whose amplitudes are profiled out of the likelihood in closed form together with the baseline
         (nfa_specset_set_templates): `ripple(n_chan, period)` for a standing wave of known period.  Not with a
         calibration, a correlation or a response.  null_lnZ is then the model of baseline and templates alone.
@@ -691,6 +807,7 @@ class EngineRunner(Runner):
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered, self.MODEL)
         calibration = check_calibration(calibration, len(spectra))
+        noise_uncertainty = check_noise_uncertainty(noise_uncertainty, len(spectra), calibration)
         check_correlation(correlation, len(spectra), [s.size for s in spectra],
                           any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
         check_response(response, len(spectra), [s.size for s in spectra],
@@ -734,6 +851,53 @@ class EngineRunner(Runner):
             self.set_response(response)
         if templates is not None:
             self.set_templates(templates)
+        if noise_uncertainty is not None:
+            self.set_noise_uncertainty(noise_uncertainty)
+
+    @property
+    def noise_uncertainty(self):
+        """None, or the float64 array of the fractional uncertainties of the spectra's noise levels."""
+        f = self._ss.noise_uncertainty
+        return None if f is None else f.copy()
+
+    def set_noise_uncertainty(self, f):
+        """Sets (a number, or one per spectrum) or removes (None, zeros) the uncertainty of the noise levels of this
+        runner's spectra; null_lnZ follows, and the spectra's `prefactor`.  The spectra's private one-spectrum sets keep
+        the noise exact: a spectrum's own `loglikelihood` is the plain one; the runner's `loglikelihood`,
+        `loglikelihood_batch` and `predict_batch` are the marginal ones."""
+        self._ss.set_noise_uncertainty(f)
+        f = self._ss.noise_uncertainty
+        self._refresh_null_lnZ()
+        for k, s in enumerate(self._model_spectra()):
+            s.set_noise_uncertainty(None if f is None else f[k])
+
+    def _refresh_null_lnZ(self):
+        """null_lnZ after a setter that can remove what it depended on: the runner's own set's wherever that set's likelihood is
+        not the plain one at p = 0 (a baseline, templates, a correlation, a noise uncertainty), else the spectra's own values
+        (the reference's spectrum-alone sum)."""
+        ss = self._ss
+        if (self.baseline_order is not None or ss.templates is not None or ss.correlation is not None
+                or ss.noise_uncertainty is not None):
+            self.null_lnZ = float(ss.null_lnZ().sum())
+        else:
+            self.null_lnZ = float(sum(s.null_lnZ for s in self._model_spectra()))
+
+    def fit_noise(self, params):
+        """Posterior mean and standard deviation of every spectrum's noise scale t (true noise = t * stated noise) at
+        physical `params`: two arrays of n_spec values, 1 and 0 for a spectrum whose uncertainty is 0.  numpy on the host
+        (`half_chi2`, `noise_fit`, after `predict`, which this calls) with the spectra's chi^2 as the runner's set forms
+        them, whatever it profiles out, filters or correlates.  ValueError without a noise uncertainty."""
+        f = self.noise_uncertainty
+        if f is None:
+            raise ValueError('this runner has no noise uncertainty (noise_uncertainty=None)')
+        self.predict(params)
+        tmpl, corr, resp = self._ss.templates, self._ss.correlation, self._ss.response
+        mean, std = np.ones(self.n_spec), np.zeros(self.n_spec)
+        for k, s in enumerate(self._model_spectra()):
+            h, nu = half_chi2(s.data, s.get_spec(), s.noise, self.baseline_order, None if tmpl is None else tmpl[k],
+                              None if corr is None else corr[k], None if resp is None else resp[k])
+            mean[k], std[k] = noise_fit(h, nu, f[k])
+        return mean, std
 
     @property
     def templates(self):
@@ -747,10 +911,7 @@ class EngineRunner(Runner):
         `loglikelihood` is the plain one; the runner's `loglikelihood`, `loglikelihood_batch` and `predict_batch` profile
         the templates out."""
         self._ss.set_templates(tmpl)
-        if self._ss.templates is not None or self.baseline_order is not None:
-            self.null_lnZ = float(self._ss.null_lnZ().sum())
-        else:
-            self.null_lnZ = float(sum(s.null_lnZ for s in self._model_spectra()))
+        self._refresh_null_lnZ()
 
     @property
     def response(self):

@@ -340,8 +340,10 @@ class Spectrum:
             self.noise = float(noise)
             self.n_chan = int(xarr.shape[0])
             self.prefactor = -xarr.shape[0] / 2 * np.log(2 * np.pi * noise**2)
-        self._prefactor_white = self.prefactor
+        self._prefactor_white = self._prefactor_base = self.prefactor          # (_base: with a correlation's -ln det R / 2)
+        self._prefactor_noise = 0.0
         self.correlation = None
+        self.noise_uncertainty = None
         self.xarr = xarr
         self.data = data
         self.size = int(xarr.shape[0])
@@ -359,14 +361,27 @@ class Spectrum:
         value minus ln det R / 2, R the correlation matrix of the AR(2) process with autocorrelations `pair` = (rho_1,
         rho_2); None or (0, 0): the white-noise value again.  A runner's `set_correlation` calls this."""
         if pair is None or (pair[0] == 0.0 and pair[1] == 0.0):
-            self.correlation, self.prefactor = None, self._prefactor_white
+            self.correlation, self._prefactor_base = None, self._prefactor_white
+            self.prefactor = self._prefactor_base + self._prefactor_noise
             return
         r1, r2 = float(pair[0]), float(pair[1])
         den = 1.0 - r1 * r1
         phi1, phi2 = r1 * (1.0 - r2) / den, (r2 - r1 * r1) / den
         v = 1.0 - phi1 * r1 - phi2 * r2
         self.correlation = (r1, r2)
-        self.prefactor = self._prefactor_white - 0.5 * ((self.size - 2) * np.log(v) + np.log(den))
+        self._prefactor_base = self._prefactor_white - 0.5 * ((self.size - 2) * np.log(v) + np.log(den))
+        self.prefactor = self._prefactor_base + self._prefactor_noise
+
+    def set_noise_uncertainty(self, f):
+        """The normalisation of a likelihood whose noise level has the fractional uncertainty `f`: `prefactor`
+        gains lgamma(a + nu / 2) - lgamma(a) - (nu / 2) ln a, a = 1 / (4 f^2) and nu = `n_chan`, the constant that the
+        marginal -(a + nu / 2) log1p(h / a) leaves out; None or 0: without it again.  A runner's `set_noise_uncertainty`
+        calls this."""
+        from ._model import noise_prefactor
+        f = None if f is None or float(f) == 0.0 else float(f)
+        self._prefactor_noise = noise_prefactor(self.n_chan, f)
+        self.noise_uncertainty = f
+        self.prefactor = self._prefactor_base + self._prefactor_noise
 
 
 class HyperfineSpectrum(Spectrum):

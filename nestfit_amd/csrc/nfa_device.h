@@ -159,6 +159,11 @@ struct SpecDev {
     // always has chan_w and wdata (a scalar noise: chan_w == 1), keeps bl and bl_order for nfa_specset_set_baseline's sake
     // and runs lnl_kernel_tmpl, which reads tp alone.
     const double  *tmpl, *tp;
+    // Spectra sets with an uncertain noise level per spectrum (nfa_specset_set_noise_uncertainty; null without):
+    // [n_pix][n_spec][2], a = 1 / (4 f^2) of the spectrum's fractional uncertainty f (0: the spectrum's noise is exact) and
+    // c = a + nu / 2, nu the unmasked channels of the (pixel, spectrum) (nmarg_setup_kernel).  No likelihood kernel reads it:
+    // lnl_of_item turns the chi^2 parts of every set kind into the marginal likelihood.
+    const double  *nmarg;
 };
 // entries of R^-1 of a spectrum: its diagonal at channels 0 and N-1, 1 and N-2, and between; its first off-diagonal at
 // (0, 1) and (N-2, N-1), and between; its second off-diagonal
@@ -1691,7 +1696,7 @@ lnl_kernel_tmpl(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
 #define NFA_QUEUE_WORDS  (2 * NFA_QUEUE_STRIDE)
 struct QueueArgs { SpecDev S; BatchGroup grp; const double *D; double *part; double *spec_out; long B; LnlGeom G; const double *g_tabs; };
 // (the argument segment places every argument at the next multiple of its alignment: 8 for all of these, so the struct's
-// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1024, 1296, 1304, 1312, 1320, 1328, 1368)
+// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1032, 1304, 1312, 1320, 1328, 1336, 1376)
 static_assert(sizeof(SpecDev) % 8 == 0 && sizeof(BatchGroup) % 8 == 0 && sizeof(LnlGeom) % 8 == 0 && alignof(SpecDev) == 8 &&
               alignof(BatchGroup) == 8 && alignof(LnlGeom) == 8, "QueueArgs must mirror the kernel argument segment");
 template <bool WRITE_SPEC, int NCOMP>
@@ -1784,14 +1789,31 @@ lnl_kernel_queue(SpecDev S, BatchGroup grp, const double *__restrict__ D, double
     }
 }
 
+// h = chi^2 / (2 sigma^2) of a (pixel, spectrum) -> its log-likelihood term.  nm null, or a = nm[0] == 0: -h, the noise level
+// is exact.  Else the level's scale t is integrated out, 1 / t^2 ~ Gamma(a, rate a): -c log1p(h / a), c = nm[1];
+// h of a set with templates can round below 0 and is clamped -- by a comparison, which leaves a NaN part NaN (fmax would make
+// it 0, the largest value there is: every set returns NaN for a row with a NaN parameter, and the sampler's update relies on it).
+__device__ __forceinline__ double nmarg_lnl(double h, const double *__restrict__ nm) {
+    if (!nm) return -h;
+    const double a = nm[0];
+    return a == 0.0 ? -h : -nm[1] * log1p((h < 0.0 ? 0.0 : h) / a);
+}
+
 // chi^2 parts of one item -> its log-likelihood: the sum over the spectra, in order (ammonia.pyx:425-432), of
-// -chi2_s / (2 noise_s^2) (core.pyx:530)
+// -chi2_s / (2 noise_s^2) (core.pyx:530); with an uncertain noise level (nmarg not null) of nmarg_lnl's terms
 __device__ __forceinline__ double lnl_of_item(const double *__restrict__ part, const double *__restrict__ noise,
-                                              long p_ix, long b, int nspec) {
+                                              const double *__restrict__ nmarg, long p_ix, long b, int nspec) {
     double tot = 0.0;
+    if (!nmarg) {
+        for (int s = 0; s < nspec; ++s) {
+            const double sigma = noise[p_ix * nspec + s];
+            tot += -part[b * nspec + s] / (2 * (sigma * sigma));
+        }
+        return tot;
+    }
     for (int s = 0; s < nspec; ++s) {
         const double sigma = noise[p_ix * nspec + s];
-        tot += -part[b * nspec + s] / (2 * (sigma * sigma));
+        tot += nmarg_lnl(part[b * nspec + s] / (2 * (sigma * sigma)), nmarg + 2 * (p_ix * nspec + s));
     }
     return tot;
 }
@@ -1805,7 +1827,20 @@ __global__ void lnl_sum_kernel(const double *__restrict__ part, const double *__
     const int c = group_of(grp, b);
     const long row = b - c * grp.each;
     const int *pix = grp.pix[c];
-    grp.lnL[c][row] = lnl_of_item(part, noise, pix ? (long)pix[row] : 0, b, nspec);
+    grp.lnL[c][row] = lnl_of_item(part, noise, nullptr, pix ? (long)pix[row] : 0, b, nspec);
+}
+
+// ... of a set with an uncertain noise level (SpecDev.nmarg not null): a kernel of its own, so that every other set runs
+// lnl_sum_kernel's instructions as they were
+__global__ void lnl_sum_nmarg_kernel(const double *__restrict__ part, const double *__restrict__ noise,
+                                     const double *__restrict__ nmarg, BatchGroup grp, long B, int nspec) {
+    __builtin_amdgcn_s_setprio(3);
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int c = group_of(grp, b);
+    const long row = b - c * grp.each;
+    const int *pix = grp.pix[c];
+    grp.lnL[c][row] = lnl_of_item(part, noise, nmarg, pix ? (long)pix[row] : 0, b, nspec);
 }
 
 #include "nfa_setup.h"
@@ -1902,6 +1937,37 @@ __device__ __forceinline__ void null_lnz_body(const SpecDev &S, long n_pix, doub
 }
 __global__ void null_lnz_kernel(SpecDev S, long n_pix, double *__restrict__ out) { null_lnz_body<false>(S, n_pix, out); }
 __global__ void null_lnz_w_kernel(SpecDev S, long n_pix, double *__restrict__ out) { null_lnz_body<true>(S, n_pix, out); }
+
+// An uncertain noise level: out[pix][spec] = {a, a + nu / 2}, a = a_of[spec] and nu the channels of the
+// (pixel, spectrum) whose own weight u^2 = w > 0 (w null, a scalar noise: all of them).  w is the set's own buffer, not
+// chan_w, which on a correlated set holds Q's diagonal.  One wave per (pixel, spectrum).
+struct NmargA { double a[MAXSPEC]; };
+__global__ void nmarg_setup_kernel(SpecDev S, long n_pix, const double *__restrict__ w, NmargA a_of, double *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long u = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (u >= n_pix * S.n_spec) return;
+    const long p = u / S.n_spec;
+    const int s = (int)(u - p * S.n_spec);
+    int nu = S.size[s];
+    if (w) {
+        const double *ws = w + p * S.chan_tot + S.off[s];
+        int n = 0;
+        for (int j = lane; j < S.size[s]; j += 64) n += ws[j] > 0.0 ? 1 : 0;
+        nu = (int)wave_sum((double)n);
+    }
+    if (lane == 0) {
+        const double a = a_of.a[s];
+        out[2 * u] = a;
+        out[2 * u + 1] = a == 0.0 ? 0.0 : a + 0.5 * nu;
+    }
+}
+
+// null_lnZ of a set with an uncertain noise level: every null_lnz_*_kernel leaves -h, and the term is nmarg_lnl's of h
+__global__ void null_lnz_nmarg_kernel(const double *__restrict__ nmarg, long n, double *__restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = nmarg_lnl(-out[i], nmarg + 2 * i);
+}
 
 // Correlated channel noise, pixels [pix0, pix0 + n_pix): Q = diag(u) R^-1 diag(u), u = sqrt(w) of the set's own
 // weights `w` (u^2 = (sigma_ref / sigma_c)^2; 1 for a scalar noise), R^-1 from the spectrum's NFA_CORR_NC entries.  form_q: the

@@ -231,6 +231,9 @@ struct nfa_specset {
     double *d_tmpl = nullptr, *d_tp = nullptr;
     std::vector<double> h_tmpl;                     // [NFA_TMPL_MAX][chan_tot], unused slots zero; empty without templates
     int     h_ntmpl[MAXSPEC] = {};
+    // an uncertain noise level (nfa_specset_set_noise_uncertainty): SpecDev.nmarg and the caller's fractional 1-sigma values
+    double *d_nmarg = nullptr;
+    double  h_nunc[MAXSPEC] = {};
 };
 
 struct nfa_priors {
@@ -983,6 +986,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_q0); (void)hipFree(ss->d_q1); (void)hipFree(ss->d_q2); (void)hipFree(ss->d_corr);
     (void)hipFree(ss->d_resp);
     (void)hipFree(ss->d_tmpl); (void)hipFree(ss->d_tp);
+    (void)hipFree(ss->d_nmarg);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
@@ -1080,6 +1084,10 @@ int nfa_specset_set_baseline(nfa_specset *ss, int order) {
     return rc;
 }
 
+// a calibrated set's part is chi^2 plus sigma^2 log1p(s^2 A / sigma^2): no chi^2 whose noise scale integrates
+// out in closed form.  The same words from either setter.
+#define NMARG_CALIB_REFUSAL "a set takes a calibration uncertainty or a noise uncertainty, not both: a calibrated set's part is no chi^2"
+
 int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
     SpecDev &d = ss->dev;
@@ -1092,6 +1100,7 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
     if (any && d.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no calibration uncertainty");
     if (any && d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no calibration uncertainty");
     if (any && d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no calibration uncertainty");
+    if (any && d.nmarg) return fail(NFA_ERR_ARG, NMARG_CALIB_REFUSAL);
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any) {                                               // null, or all zeros: the set's former kernels and bits
@@ -1124,6 +1133,62 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
 int nfa_specset_calibration(const nfa_specset *ss, double *out) {
     if (!ss || !ss->dev.cal2) return 0;
     for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->h_cal[s];
+    return 1;
+}
+
+// The records {a, a + nu / 2} of every (pixel, spectrum) for the fractional uncertainties f[n_spec], some of them > 0
+static int nmarg_form(nfa_specset *ss, const double *f) {
+    SpecDev &d = ss->dev;
+    NmargA a_of = {};
+    for (int s = 0; s < d.n_spec; ++s) a_of.a[s] = f[s] > 0.0 ? 1.0 / (4.0 * f[s] * f[s]) : 0.0;
+    const int64_t n = ss->n_pix * d.n_spec;
+    if (!ss->d_nmarg) HIP_TRY(hipMalloc(&ss->d_nmarg, sizeof(double) * 2 * n));
+    // the set's own weights u^2: d_w (ones where a baseline, templates or a correlation made it for a scalar noise); none: nu = N
+    hipLaunchKernelGGL(nmarg_setup_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0, d, (long)ss->n_pix,
+                       (const double *)ss->d_w, a_of, ss->d_nmarg);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return NFA_OK;
+}
+
+int nfa_specset_set_noise_uncertainty(nfa_specset *ss, const double *f) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    SpecDev &d = ss->dev;
+    bool any = false;
+    for (int s = 0; f && s < d.n_spec; ++s) {
+        if (!(f[s] >= 0.0 && f[s] <= 0.5))                    // (NaN fails both)
+            return fail(NFA_ERR_ARG, "a noise uncertainty is a finite fraction in [0, 0.5] per spectrum");
+        any = any || f[s] > 0.0;
+    }
+    if (any && d.cal2) return fail(NFA_ERR_ARG, NMARG_CALIB_REFUSAL);
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    if (!any) {                                               // null, or all zeros: the set's former arithmetic and bits
+        (void)hipFree(ss->d_nmarg);
+        ss->d_nmarg = nullptr; d.nmarg = nullptr;
+        for (int s = 0; s < MAXSPEC; ++s) ss->h_nunc[s] = 0.0;
+        return NFA_OK;
+    }
+    const bool had = d.nmarg != nullptr;
+    double was[MAXSPEC];
+    memcpy(was, ss->h_nunc, sizeof was);
+    d.nmarg = nullptr;                                        // (the set-up kernel's copy of the set reads none of it)
+    rc = nmarg_form(ss, f);
+    if (rc) {                                                 // the set stays as it was: its former values, or none
+        const std::string why = g_err;
+        if (!had || nmarg_form(ss, was) != NFA_OK) { (void)hipFree(ss->d_nmarg); ss->d_nmarg = nullptr; memset(ss->h_nunc, 0, sizeof ss->h_nunc); }
+        d.nmarg = ss->d_nmarg;
+        g_err = why;
+        return rc;
+    }
+    d.nmarg = ss->d_nmarg;
+    for (int s = 0; s < d.n_spec; ++s) ss->h_nunc[s] = f[s];
+    return NFA_OK;
+}
+
+int nfa_specset_noise_uncertainty(const nfa_specset *ss, double *out) {
+    if (!ss || !ss->dev.nmarg) return 0;
+    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->h_nunc[s];
     return 1;
 }
 
@@ -1412,6 +1477,10 @@ int nfa_specset_null_lnz(const nfa_specset *ss, double *out) {
         hipLaunchKernelGGL(ss->dev.chan_w ? null_lnz_w_kernel : null_lnz_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0,
                            ss->dev, (long)ss->n_pix, d_out);
     hipError_t e = hipGetLastError();
+    if (e == hipSuccess && ss->dev.nmarg) {                   // an uncertain noise level: lnl_of_item's term of the same h
+        hipLaunchKernelGGL(null_lnz_nmarg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev.nmarg, (long)n, d_out);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost);
     (void)hipFree(d_out);                                     // on every path
     if (e != hipSuccess) return fail(NFA_ERR_DEVICE, std::string("nfa_specset_null_lnz: ") + hipGetErrorString(e));
@@ -1898,8 +1967,12 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
                            (const double *)r->d_D[slot], part, d_spec, (long)B, P.G, (const double *)g_eng.d_tabs);
     HIP_TRY(hipGetLastError());
     if (want_lnl && !r->part_only) {
-        hipLaunchKernelGGL(lnl_sum_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st,
-                           (const double *)r->d_part[slot], S.noise, r->cur_group, (long)B, S.n_spec);
+        if (S.nmarg)
+            hipLaunchKernelGGL(lnl_sum_nmarg_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st,
+                               (const double *)r->d_part[slot], S.noise, S.nmarg, r->cur_group, (long)B, S.n_spec);
+        else
+            hipLaunchKernelGGL(lnl_sum_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st,
+                               (const double *)r->d_part[slot], S.noise, r->cur_group, (long)B, S.n_spec);
         HIP_TRY(hipGetLastError());
     }
     return NFA_OK;

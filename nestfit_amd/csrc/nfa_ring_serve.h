@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(POINT_THREADS) ring_serve_kernel(const PriorPr
         __syncthreads();
         if (tid == 0) {
             double lnl = NAN;
-            if (!bad) lnl = lnl_of_item(part, S.noise, A.has_pix ? (long)my_pix : 0, 0, S.n_spec);
+            if (!bad) lnl = lnl_of_item(part, S.noise, S.nmarg, A.has_pix ? (long)my_pix : 0, 0, S.n_spec);
             rs_store_f64(s_lnl, lnl);
             __hip_atomic_store((unsigned *)(s + RS_RC), bad ? (unsigned)NFA_ERR_ARG : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __threadfence_system();

@@ -75,7 +75,10 @@ struct NsDev {
     double *deadT, *deadL, *deadlnw;    // [P][cap][DT], [P][cap], [P][cap]
     double *candU, *candT, *candL;      // proposals [rows][D]; compact: theta [rows][DT], lnL [rows]
     int    *candpix, *valid;            // [rows]: pixel of a compact row; validity of a proposal
-    // the update wave sums a row's per-spectrum chi^2 parts itself (lnl_of_item's arithmetic): no summing launch per round
+    // the update wave sums a row's per-spectrum chi^2 parts itself (lnl_of_item's arithmetic): no summing launch per round.
+    // Not for a set with an uncertain noise level (SpecDev.nmarg): its log1p per (row, spectrum) goes to
+    // lnl_sum_nmarg_kernel's one lane per row, not to this kernel's eight rows per lane (22 us more per update, measured); the
+    // batch then leaves lnL in candL and `part` is null
     const double *part, *noise;         // [rows][nspec] of the round's batch (null: candL holds lnL); [pixels][nspec]
     int     nspec;
     int    *slot;                       // [rows] compact row of a valid proposal
@@ -1281,7 +1284,7 @@ __global__ void __launch_bounds__(NS_UPD_THREADS) NFA_UPD_ATTR ns_update_kernel(
             if (S.valid[g]) {
                 tot += 1;
                 const long row = S.slot[g];
-                double Lk = S.part ? lnl_of_item(S.part, S.noise, (long)S.candpix[row], row, S.nspec) : S.candL[row];
+                double Lk = S.part ? lnl_of_item(S.part, S.noise, nullptr, (long)S.candpix[row], row, S.nspec) : S.candL[row];
                 if (!isfinite(Lk)) Lk = S.log_zero;
                 if (Lk > Lthr) {
                     acc += 1;
@@ -1349,7 +1352,7 @@ __global__ void __launch_bounds__(NS_UPD_THREADS) NFA_UPD_ATTR ns_update_kernel(
 #pragma unroll
             for (int u = 0; u < NS_UPD_U; ++u) {
                 const bool mine = (vbits >> u) & 1u;
-                const double L = !mine ? 0.0 : S.part ? lnl_of_item(S.part, S.noise, (long)S.candpix[rows[u]], (long)rows[u], S.nspec) : S.candL[rows[u]];
+                const double L = !mine ? 0.0 : S.part ? lnl_of_item(S.part, S.noise, nullptr, (long)S.candpix[rows[u]], (long)rows[u], S.nspec) : S.candL[rows[u]];
                 Ls[u] = isfinite(L) ? L : S.log_zero;
             }
             if (timing) { S.dbg[10] += (long)(Ls[0] != 12345.678); S.dbg[9] += 1; }      // (the loads have landed)
@@ -2089,11 +2092,12 @@ int nfa_sampler_advance(nfa_sampler *s, int64_t max_chunks, int64_t *n_active_ou
                 s->val_sum += n_rows;
                 dh[h].part = nullptr;
                 if (n_rows > 0) {
-                    r->part_only = true;                                   // (the update wave sums the parts of a row)
+                    const bool parts = r->ss->dev.nmarg == nullptr;        // (an uncertain noise level: lnl_sum_kernel's lnL in candL)
+                    r->part_only = parts;                                  // (the update wave sums the parts of a row)
                     int rc = run_batch(r, dh[h].candpix, dh[h].candT, dh[h].candL, nullptr, n_rows, true, h);
                     r->part_only = false;
                     if (rc) return rc;
-                    dh[h].part = r->d_part[h];                             // (after the batch: its buffers may have grown)
+                    dh[h].part = parts ? r->d_part[h] : nullptr;           // (after the batch: its buffers may have grown)
                     dh[h].noise = r->ss->dev.noise; dh[h].nspec = r->ss->dev.n_spec;
                 }
                 hipLaunchKernelGGL(ns_update_kernel, dim3((unsigned)n_pix_h[h]), dim3(NS_UPD_THREADS), s->plan.lds_update, st, dh[h], n_pix_h[h], Kr, s->rounds);

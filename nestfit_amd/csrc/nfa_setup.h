@@ -709,7 +709,7 @@ __global__ void __launch_bounds__(POINT_THREADS) point_kernel(const PriorProg *_
     __threadfence_system();
     __syncthreads();
     if (tid == 0) {
-        *out_lnl = lnl_of_item(part, S.noise, in.pix >= 0 ? (long)my_pix : 0, 0, S.n_spec);
+        *out_lnl = lnl_of_item(part, S.noise, S.nmarg, in.pix >= 0 ? (long)my_pix : 0, 0, S.n_spec);
         __threadfence_system();
         // the last workgroup to get here publishes the sequence number (and leaves the counter at zero)
         bool last = true;

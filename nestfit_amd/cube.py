@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, check_templates, gain_fit, nuisance_fit
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_correlation, check_layered, check_noise_uncertainty, check_response, check_templates, gain_fit, half_chi2, noise_fit, nuisance_fit
 from .core import _as_inplace_matrix
 
 
@@ -59,11 +59,14 @@ class CubeRunner:
         spectrum's channels (`ripple(n_chan, period)`: a standing wave of known period; shared by all pixels) whose amplitudes
         are profiled out of the likelihood per (pixel, spectrum) together with the baseline; not with a
         calibration, a correlation or a response; null_lnZ is then the model of baseline and templates alone
+    noise_uncertainty : None, or the fractional 1-sigma uncertainty of the spectra's noise levels (a number, or one per
+        spectrum, each in [0, 0.5]; shared by all pixels), integrated out of the likelihood per (pixel, spectrum) in closed
+        form; with everything but a calibration; null_lnZ is the same function of the parts at p = 0
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
                  model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False,
-                 calibration=None, correlation=None, response=None, templates=None):
+                 calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
@@ -74,6 +77,7 @@ class CubeRunner:
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered, model)                      # before any device call
         calibration = check_calibration(calibration, len(xarrs))
+        noise_uncertainty = check_noise_uncertainty(noise_uncertainty, len(xarrs), calibration)
         sizes = [np.size(x) for x in xarrs]
         masked = np.shape(noise)[-1] == sum(sizes) and not np.all(np.isfinite(noise))
         correlation = check_correlation(correlation, len(xarrs), sizes, masked, baseline_order, calibration)
@@ -103,7 +107,9 @@ class CubeRunner:
             self._ss.set_response(response)
         if templates is not None:
             self._ss.set_templates(templates)
-        self._data, self._noise = data, noise                # (fit_baseline, fit_gain)
+        if noise_uncertainty is not None:
+            self._ss.set_noise_uncertainty(noise_uncertainty)
+        self._data, self._noise = data, noise                # (fit_baseline, fit_gain, fit_noise)
         self.utrans = utrans
         self.ncomp = int(ncomp)
         self.n_model = self._ss.n_model                      # (an LTE mix: from the species of its lines, not from N_MODEL)
@@ -269,6 +275,41 @@ class CubeRunner:
                 w = 1.0 / noise[b, sl] ** 2 if self._ss.per_channel else np.ones(off[k + 1] - off[k])
                 sigma = 1.0 if self._ss.per_channel else noise[b, k]
                 mean[b, k], std[b, k] = gain_fit(data[b, sl], spec[b, sl], w, sigma, cal[k], self.baseline_order)
+        return mean, std
+
+    @property
+    def noise_uncertainty(self):
+        """None, or the float64 array of the fractional uncertainties of the spectra's noise levels."""
+        f = self._ss.noise_uncertainty
+        return None if f is None else f.copy()
+
+    def set_noise_uncertainty(self, f):
+        """Sets (a number, or one per spectrum) or removes (None, zeros) the uncertainty of the spectra's noise levels;
+        null_lnZ follows."""
+        self._ss.set_noise_uncertainty(f)
+        self.null_lnZ = self._ss.null_lnZ().sum(axis=1)
+
+    def fit_noise(self, pix, theta):
+        """Posterior mean and standard deviation [B, n_spec] each of the spectra's noise scales t (true noise = t * stated
+        noise) at physical parameter rows theta[B, ndim] against pixels pix[B] (1 and 0 where a spectrum's uncertainty is
+        0): numpy on `predict_batch`'s spectra (`half_chi2`, `noise_fit`).  ValueError without a noise uncertainty."""
+        f = self.noise_uncertainty
+        if f is None:
+            raise ValueError('this runner has no noise uncertainty (noise_uncertainty=None)')
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        spec, _ = self.predict_batch(pix, theta)
+        data = np.asarray(self._data, dtype=np.float64)[pix]
+        noise = np.asarray(self._noise, dtype=np.float64)[pix]
+        off = self._ss.offsets
+        tmpl, corr, resp = self._ss.templates, self._ss.correlation, self._ss.response
+        mean, std = np.ones((len(pix), self.n_spec)), np.zeros((len(pix), self.n_spec))
+        for k in range(self.n_spec):
+            sl = slice(off[k], off[k + 1])
+            for b in range(len(pix)):
+                h, nu = half_chi2(data[b, sl], spec[b, sl], noise[b, sl] if self._ss.per_channel else noise[b, k],
+                                  self.baseline_order, None if tmpl is None else tmpl[k], None if corr is None else corr[k],
+                                  None if resp is None else resp[k])
+                mean[b, k], std[b, k] = noise_fit(h, nu, f[k])
         return mean, std
 
     def peak_and_integrated(self, pix, theta):

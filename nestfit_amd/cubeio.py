@@ -315,6 +315,31 @@ def estimate_correlation(cube, line_free):
     return tuple(rho)
 
 
+def estimate_noise(cube, line_free, correlation=None):
+    """(rms map, f): the noise level of every pixel from its channels without line emission, and the fractional 1-sigma
+    uncertainty of such a level -- what `noise=` and `noise_uncertainty=` of a runner take.  cube and
+    line_free as for `estimate_correlation`.  Per pixel the mean of its line-free channels is taken off and the rms is
+    sqrt(sum x^2 / (n_free - 1)); a pixel with a NaN in a line-free channel gets NaN.  f = 1 / sqrt(2 n_free), the relative
+    standard deviation of an rms over n_free independent Gaussian channels.  correlation: the pair (rho_1, rho_2) of the
+    channel noise, if any: neighbouring channels are then not independent and n_free is divided by 1 + 2 rho_1^2 + 2 rho_2^2
+    (the variance of a sample variance of a correlated Gaussian series, to the second lag).  numpy on the host."""
+    data = np.asarray(getattr(cube, 'data', cube), dtype=np.float64)
+    n = data.shape[-1]
+    keep = np.zeros(n, dtype=bool)
+    keep[line_free] = True
+    n_free = int(keep.sum())
+    if n_free < 8:
+        raise ValueError('estimate_noise needs 8 line-free channels and more')
+    x = data[..., keep]
+    x = x - x.mean(axis=-1, keepdims=True)
+    rms = np.sqrt(np.sum(x * x, axis=-1) / (n_free - 1))
+    n_eff = float(n_free)
+    if correlation is not None:
+        r1, r2 = float(correlation[0]), float(correlation[1])
+        n_eff /= 1.0 + 2.0 * r1 * r1 + 2.0 * r2 * r2
+    return rms, float(1.0 / np.sqrt(2.0 * n_eff))
+
+
 # celestial keywords a two-dimensional map product inherits from the cube
 _MAP_KEYWORDS = ('SIMPLE', 'BITPIX', 'NAXIS', 'NAXIS1', 'NAXIS2', 'WCSAXES') + tuple(
     f'{stem}{axis}' for stem in ('CRPIX', 'CDELT', 'CUNIT', 'CTYPE', 'CRVAL') for axis in (1, 2)) + ('RADESYS', 'EQUINOX')

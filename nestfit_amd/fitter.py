@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import sampler
-from ._model import check_calibration, check_correlation, check_layered, check_response, check_templates
+from ._model import check_calibration, check_correlation, check_layered, check_noise_uncertainty, check_response, check_templates
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
@@ -89,6 +89,9 @@ class CubeFitter:
         # nuisance templates (runner_kwargs['templates']): and these
         self.templates = check_templates(self.runner_kwargs.get('templates'), None if cubes is None else len(cubes),
                                          calibration=self.calibration, correlation=self.correlation, response=self.response)
+        # an uncertain noise level per spectrum (runner_kwargs['noise_uncertainty']): and this
+        self.noise_uncertainty = check_noise_uncertainty(self.runner_kwargs.get('noise_uncertainty'),
+                                                         None if cubes is None else len(cubes), self.calibration)
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
         self.lnZ_thresh, self.ncomp_max, self.nlive_snr_fact = lnZ_thresh, ncomp_max, nlive_snr_fact
         self.nlive_quantum = max(1, int(nlive_quantum))

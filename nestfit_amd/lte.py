@@ -47,7 +47,7 @@ function come from a catalogue of the user's.
 """
 import numpy as np
 
-from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
+from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
 from .core import HyperfineSpectrum as _HyperfineBase
 from .hyperfine import CKMS, MAX_LINES, LineTable
 
@@ -405,14 +405,16 @@ class LteRunner(EngineRunner):
     MODEL = MODEL_LTE
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
+                 noise_uncertainty=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
         self.molecule = check_one_molecule([s.lines for s in self.spectra])
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response, templates=templates)
+                    calibration=calibration, correlation=correlation, response=response, templates=templates,
+                    noise_uncertainty=noise_uncertainty)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -420,6 +422,7 @@ class LteRunner(EngineRunner):
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         check_layered(kwargs.get('layered', False))
         check_calibration(kwargs.get('calibration'), len(spec_data))
+        check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
         check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
@@ -548,7 +551,8 @@ class _MixRunner(EngineRunner):
     MODEL = MODEL_LTE
     MIX = None
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None):
+    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
+                 noise_uncertainty=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
@@ -556,7 +560,8 @@ class _MixRunner(EngineRunner):
         check_mix_lines(self.MIX.species, [s.lines for s in self.spectra])
         self.species = self.MIX.species
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response, templates=templates)
+                    calibration=calibration, correlation=correlation, response=response, templates=templates,
+                    noise_uncertainty=noise_uncertainty)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -564,6 +569,7 @@ class _MixRunner(EngineRunner):
         check_baseline_order(kwargs.get('baseline_order'))            # before any device call
         check_layered(kwargs.get('layered', False))
         check_calibration(kwargs.get('calibration'), len(spec_data))
+        check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
         check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),

@@ -24,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import hdf5
-from ._model import check_calibration, check_correlation, check_response, check_templates
+from ._model import check_calibration, check_correlation, check_noise_uncertainty, check_response, check_templates
 
 HDF5_SUFFIXES = ('.hdf', '.h5', '.hdf5')
 
@@ -456,6 +456,12 @@ class HdfStore:
             for k, a in enumerate(tmpl):
                 if a is not None:
                     group.create_dataset(f'spec{k}', data=a)
+        # an uncertain noise level per spectrum integrated out of the likelihood (runner_kwargs['noise_uncertainty'], DESIGN
+        # 4.16): root attribute `noise_uncertainty`, float64 [n_spec].  A store without it was fitted with the noise as given.
+        nunc = check_noise_uncertainty((getattr(fitter, 'runner_kwargs', None) or {}).get('noise_uncertainty'),
+                                       None if cubes is None else len(cubes))
+        if nunc is not None:
+            self.hdf.attrs['noise_uncertainty'] = nunc
         quantum = getattr(fitter, 'nlive_quantum', 1)
         if quantum != 1:                 # a deviation from main.py:445-447 is written down where the results are
             self.hdf.attrs['nlive_quantum'] = int(quantum)
@@ -507,6 +513,14 @@ class HdfStore:
         group = self.hdf['nuisance_templates']
         return [np.asarray(group[f'spec{k}'][...], dtype=np.float64) if f'spec{k}' in group else None
                 for k in range(int(group.attrs['n_spec']))]
+
+    def read_model_noise_uncertainty(self):
+        """The fractional uncertainty of the noise level of every spectrum the store was fitted with
+        (`runner_kwargs={'noise_uncertainty': ...}`): the root attribute `noise_uncertainty` as a float64 array [n_spec];
+        None for a store without it."""
+        assert self.is_open
+        nunc = self.hdf.attrs.get('noise_uncertainty')
+        return None if nunc is None else np.asarray(nunc, dtype=np.float64)
 
     def read_model_fill(self):
         """Whether the store was fitted with a beam filling factor per component (`LteMix(species, fill=True)`): the root
