@@ -428,6 +428,29 @@ int nfa_specset_templates(const nfa_specset *ss, double *out_t, int *out_n);
 int nfa_specset_set_noise_uncertainty(nfa_specset *ss, const double *f);
 /* 1 and out[n_spec] = the values set (out may be null), or 0 for a set without a noise uncertainty (and for null) */
 int nfa_specset_noise_uncertainty(const nfa_specset *ss, double *out);
+/* A continuum background: a source of brightness temperature Tc >= 0 (K, on the data's scale) behind all components of a
+ * (pixel, spectrum) -- an H II region, a dust peak, a quasar -- whose level was subtracted from the data, so that a line goes
+ * NEGATIVE wherever J(tex) < J(Tcmb) + Tc.  With g_c = T0 (y(T0 / tex_c) - tbg) and a_c = 1 - FastExp(tau_c) (a filled set:
+ * f_c times that):
+ *     summed:   pred = sum_c (g_c - Tc) a_c          layered:   pred <- pred + (g_c - Tc - pred) a_c
+ * Tc is DATA, not a parameter: it comes from the continuum map that was subtracted (the subtracted cube cannot give it back),
+ * and the sampler's dimensions, the optical depths and nfa_specset_null_lnz (the null model has no absorber) do not change.
+ * With nfa_specset_set_baseline(ss, 0) the same likelihood fits data whose continuum was NOT subtracted: the offset is
+ * profiled out, the depth still needs Tc.  On a filled set the form is exact where the layer covers the source.
+ * tc[n_pix][n_spec].  tc = NULL or all zeros removes the continuum (the set's former kernels and results bit for bit).
+ * NFA_ERR_ARG, the set left as it was: a value that is negative or not finite; the Gaussian model (no optical depth); a set with
+ * a calibration uncertainty, correlated channel noise, a channel response or nuisance templates ("... takes no continuum
+ * background") -- and nfa_specset_set_calibration, nfa_specset_set_correlation, nfa_specset_set_response and
+ * nfa_specset_set_templates refuse a set with a continuum in the same words.  With a scalar noise and a noise per channel,
+ * masked channels, a baseline (the two calls commute), layered and filled sets, every hyperfine and LTE model and
+ * nfa_specset_set_noise_uncertainty: yes.  Like nfa_specset_set_baseline it launches held batches first, synchronises the
+ * device and drops the runners' captured single-point graphs: call it between batches.  nfa_specset_set_data keeps the
+ * continuum.  Spectra out are the model against the off-line level, negative in absorption.  Such sets go through the batch
+ * kernels (the general component form); single points and a broker's handful too, and nfa_ring_serve_device refuses their
+ * runners ("the resident kernel has no form for a continuum background: use nfa_ring_serve"). */
+int nfa_specset_set_continuum(nfa_specset *ss, const double *tc);
+/* 1 and out[n_pix][n_spec] = the values set (out may be null), or 0 for a set without a continuum (and for null) */
+int nfa_specset_continuum(const nfa_specset *ss, double *out);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

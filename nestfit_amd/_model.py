@@ -342,6 +342,64 @@ def check_noise_uncertainty(f, n_spec=None, calibration=None):
     return out
 
 
+def check_continuum(tc, n_spec=None, n_pix=None, model=None, calibration=None, correlation=None, response=None, templates=None):
+    """`continuum` of a runner: the brightness temperature Tc >= 0 (K, on the data's scale) of a continuum source behind all
+    components, per spectrum (DESIGN 4.17) -- data of the continuum map that was subtracted, not a parameter.  None for none;
+    a number applies to all spectra (and pixels); one value per spectrum, [n_spec]; with `n_pix` given (a cube) also
+    [n_pix, n_spec].  Every value is finite and >= 0; all zeros is None.  A continuum goes with neither the Gaussian model
+    (`model`: no optical depth), a calibration uncertainty, a noise correlation, a channel response nor nuisance templates.
+    Returns None or a float64 array [n_spec] ([n_pix, n_spec] with n_pix; [1] for a number without n_spec); ValueError
+    otherwise.  Needs no device."""
+    if tc is None:
+        return None
+    what = ('continuum must be None, a brightness temperature >= 0 in K, one per spectrum'
+            + (' or an array [n_pix, n_spec]' if n_pix is not None else ''))
+    if isinstance(tc, (bool, np.bool_)) or (isinstance(tc, np.ndarray) and tc.dtype.kind not in 'iuf'):
+        raise ValueError(f'{what}, not {tc!r}')
+    try:
+        out = np.array(tc, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}, not {tc!r}') from None
+    if out.ndim == 0:
+        out = np.full(1 if n_spec is None else int(n_spec), float(out))
+    elif out.ndim == 1 and out.size > 0:
+        if n_spec is not None and out.shape[0] != int(n_spec):
+            raise ValueError(f'{what}: {out.shape[0]} values for {int(n_spec)} spectra')
+    elif out.ndim == 2 and n_pix is not None and out.size > 0:
+        if out.shape[0] != int(n_pix) or (n_spec is not None and out.shape[1] != int(n_spec)):
+            raise ValueError(f'{what}: shape {out.shape} for {int(n_pix)} pixels of {n_spec} spectra')
+    else:
+        raise ValueError(f'{what}, not an array of shape {out.shape}')
+    if not np.all(np.isfinite(out)) or np.any(out < 0.0):
+        raise ValueError(f'{what}: every value finite and >= 0, not {tc!r}')
+    if not np.any(out > 0.0):
+        return None
+    if n_pix is not None and out.ndim == 1:
+        out = np.tile(out, (int(n_pix), 1))
+    if model is not None and int(model) == MODEL_GAUSSIAN:
+        raise ValueError('the Gaussian model has no optical depth: its components cannot absorb a continuum background (continuum)')
+    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
+        raise ValueError('a continuum background does not go with a calibration uncertainty (calibration)')
+    if check_correlation(correlation) is not None:            # (all zeros: none)
+        raise ValueError('a continuum background does not go with a noise correlation (correlation)')
+    if check_response(response) is not None:                  # (the identity: none)
+        raise ValueError('a continuum background does not go with a channel response (response)')
+    if templates is not None and any(t is not None for t in templates):
+        raise ValueError('a continuum background does not go with nuisance templates (templates)')
+    return np.ascontiguousarray(out)
+
+
+def signed_peak(spec, axis=-1):
+    """The signed value of largest magnitude along `axis`, NaNs ignored (NaN where all are): the peak of a line that may
+    absorb (a runner with a continuum background) as `nanmax` is the peak of one that emits."""
+    spec = np.asarray(spec, dtype=np.float64)
+    bad = np.isnan(spec)
+    mag = np.where(bad, -1.0, np.abs(spec))
+    ix = np.expand_dims(np.argmax(mag, axis=axis), axis)
+    out = np.squeeze(np.take_along_axis(spec, ix, axis=axis), axis)
+    return np.where(np.all(bad, axis=axis), np.nan, out)
+
+
 def noise_shape(f):
     """Shape (= rate) a = 1 / (4 f^2) of the Gamma prior of the noise precision tau = 1 / t^2 for a fractional uncertainty f
     of the noise level: mean 1, std(tau) = 1 / sqrt(a) = 2 f, i.e. std(t) = f to first order."""
@@ -578,12 +636,28 @@ class _SpecSet:
         self.response = None
         self.templates = None
         self.noise_uncertainty = None
+        self.continuum = None
         self.masked = bool(self.per_channel and not np.all(np.isfinite(noise)))
+
+    def set_continuum(self, tc):
+        """The continuum brightness temperature behind the components, per (pixel, spectrum) (`check_continuum`'s argument:
+        a number, [n_spec] or [n_pix, n_spec]), or none (None, zeros): nfa_specset_set_continuum.  null_lnZ() does not
+        change: the null model has no absorber."""
+        tc = check_continuum(tc, self.n_spec, self.n_pix, self.model, self.calibration, self.correlation, self.response, self.templates)
+        _ffi.check(_ffi.load().nfa_specset_set_continuum(self.handle, None if tc is None else _ffi.dptr(tc)))
+        self.continuum = tc
+
+    def get_continuum(self):
+        """The continuum as the engine holds it (nfa_specset_continuum): None, or float64 [n_pix, n_spec]."""
+        out = np.zeros((self.n_pix, self.n_spec))
+        return out if _ffi.load().nfa_specset_continuum(self.handle, _ffi.dptr(out)) else None
 
     def set_templates(self, tmpl):
         """Nuisance templates per spectrum, profiled out of the likelihood with the baseline (`check_templates`'s argument),
         or none (None): nfa_specset_set_templates.  null_lnZ() then is the model of baseline and templates alone."""
         tmpl = check_templates(tmpl, self.n_spec, self.sizes, self.calibration, self.correlation, self.response)
+        if tmpl is not None and self.continuum is not None:
+            raise ValueError('nuisance templates do not go with a continuum background (continuum)')
         if tmpl is None:
             _ffi.check(_ffi.load().nfa_specset_set_templates(self.handle, None, None))
         else:
@@ -611,6 +685,8 @@ class _SpecSet:
         resp = check_response(resp, self.n_spec, self.sizes, self.masked, self.baseline_order, self.calibration)
         if resp is not None and self.templates is not None:
             raise ValueError('a channel response does not go with nuisance templates (templates)')
+        if resp is not None and self.continuum is not None:
+            raise ValueError('a channel response does not go with a continuum background (continuum)')
         _ffi.check(_ffi.load().nfa_specset_set_response(self.handle, None if resp is None else _ffi.dptr(resp)))
         self.response = resp
 
@@ -621,6 +697,8 @@ class _SpecSet:
         corr = None if corr is None else np.ascontiguousarray(corr)
         if corr is not None and self.templates is not None:
             raise ValueError('a noise correlation does not go with nuisance templates (templates)')
+        if corr is not None and self.continuum is not None:
+            raise ValueError('a noise correlation does not go with a continuum background (continuum)')
         _ffi.check(_ffi.load().nfa_specset_set_correlation(self.handle, None if corr is None else _ffi.dptr(corr)))
         self.correlation = corr
 
@@ -644,6 +722,8 @@ class _SpecSet:
             raise ValueError('a calibration uncertainty does not go with a noise correlation (correlation)')
         if cal is not None and self.templates is not None:
             raise ValueError('a calibration uncertainty does not go with nuisance templates (templates)')
+        if cal is not None and self.continuum is not None:
+            raise ValueError('a calibration uncertainty does not go with a continuum background (continuum)')
         _ffi.check(_ffi.load().nfa_specset_set_calibration(self.handle, None if cal is None else _ffi.dptr(cal)))
         self.calibration = cal
 
@@ -777,8 +857,13 @@ class EngineRunner(Runner):
     N_MODEL = 6
 
     def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False,
-               calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None):
-        """noise_uncertainty: None, or the fractional 1-sigma uncertainty of the spectra's noise levels -- a number for all of
+               calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None, continuum=None):
+        """continuum: None, or the brightness temperature Tc >= 0 (K) of a continuum source behind all components -- a number
+        for all spectra or one per spectrum -- taken from the continuum map that was subtracted from the data: data, not a
+        parameter (nfa_specset_set_continuum).  The line then goes negative wherever J(tex) < J(Tcmb) + Tc.  All
+        zeros is None.  Not with the Gaussian model, a calibration, a correlation, a response or templates.  null_lnZ is
+        unchanged.  `predict` of such a runner goes through the runner's own spectra set, as for `layered`.
+        noise_uncertainty: None, or the fractional 1-sigma uncertainty of the spectra's noise levels -- a number for all of
         them or one per spectrum, each in [0, 0.5] -- integrated out of the likelihood in closed form per spectrum
         (nfa_specset_set_noise_uncertainty); all zeros is None.  Goes with everything but a calibration.
         null_lnZ is then the same function of the parts at p = 0.
@@ -814,6 +899,7 @@ class EngineRunner(Runner):
                        any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
         templates = check_templates(templates, len(spectra), [s.size for s in spectra], calibration,
                                     check_correlation(correlation, len(spectra)), check_response(response, len(spectra)))
+        continuum = check_continuum(continuum, len(spectra), None, self.MODEL, calibration, correlation, response, templates)
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -853,6 +939,26 @@ class EngineRunner(Runner):
             self.set_templates(templates)
         if noise_uncertainty is not None:
             self.set_noise_uncertainty(noise_uncertainty)
+        if continuum is not None:
+            self.set_continuum(continuum)
+
+    @property
+    def continuum(self):
+        """None, or the float64 array [n_spec] of the continuum brightness temperatures behind the spectra (K)."""
+        tc = self._ss.continuum
+        return None if tc is None else tc[0].copy()
+
+    def set_continuum(self, tc):
+        """Sets (a number, or one per spectrum, in K) or removes (None, zeros) the continuum background of this runner's
+        spectra.  null_lnZ is read again and does not change: the null model has no absorber.  The spectra's private
+        one-spectrum sets have no continuum: `predict` fills them from the runner's own set (`_predict_layered`)."""
+        self._ss.set_continuum(check_continuum(tc, self.n_spec, None, self.MODEL))
+        self._refresh_null_lnZ()
+
+    def _predict_through_set(self):
+        """Whether `predict` takes the model from the runner's own spectra set: the spectra's one-spectrum sets are summed and
+        stand before the cosmic background alone."""
+        return self.layered or self._ss.continuum is not None
 
     @property
     def noise_uncertainty(self):
@@ -961,8 +1067,9 @@ class EngineRunner(Runner):
         self.null_lnZ = float(self._ss.null_lnZ().sum())
 
     def _predict_layered(self, params):
-        """`predict` of a layered runner: the spectra's own one-spectrum sets are summed ones, so the model comes from the
-        runner's set (`predict_batch`) and goes into every spectrum, with the spectrum's lnL formed on the host."""
+        """`predict` of a layered runner, and of one with a continuum background: the spectra's own one-spectrum sets are summed
+        ones before the cosmic background alone, so the model comes from the runner's set (`predict_batch`) and goes into every
+        spectrum, with the spectrum's lnL formed on the host."""
         spec, _ = self.predict_batch(params.reshape(1, -1))
         off = self._ss.offsets
         for k, s in enumerate(self._model_spectra()):

@@ -5,7 +5,7 @@ behaviour; all arithmetic runs in the HIP engine through the C ABI.
 import numpy as np
 
 from ._model import (MODEL_AMMONIA, EngineRunner, EngineSpectrumMixin, _pix_ptr, _RunnerHandle,  # noqa: F401
-                     _SpecSet, check_baseline_order, check_calibration, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names)
+                     _SpecSet, check_baseline_order, check_calibration, check_continuum, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names)
 from .core import HyperfineSpectrum
 
 N_LEVELS = 9
@@ -56,7 +56,7 @@ class AmmoniaRunner(EngineRunner):
     N_MODEL = N_PARAMS
 
     def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None):
+                 noise_uncertainty=None, continuum=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
@@ -65,7 +65,7 @@ class AmmoniaRunner(EngineRunner):
         self.lte = bool(lte)
         self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, baseline_order=baseline_order, layered=layered,
                     calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty)
+                    noise_uncertainty=noise_uncertainty, continuum=continuum)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -73,6 +73,8 @@ class AmmoniaRunner(EngineRunner):
         check_layered(kwargs.get('layered', False))
         check_calibration(kwargs.get('calibration'), len(spec_data))
         check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
+        check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
+                        kwargs.get('response'), kwargs.get('templates'))
         check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
@@ -89,7 +91,7 @@ class AmmoniaRunner(EngineRunner):
         """Model spectra for physical `params` into every spectrum of the runner
         (reference: ammonia.pyx:437-447)."""
         params = self._check_params(params)
-        if self.layered:
+        if self._predict_through_set():
             return self._predict_layered(params)
         for s in self.spectra:
             amm_predict(s, params, self.cold, self.lte)

@@ -164,6 +164,11 @@ struct SpecDev {
     // c = a + nu / 2, nu the unmasked channels of the (pixel, spectrum) (nmarg_setup_kernel).  No likelihood kernel reads it:
     // lnl_of_item turns the chi^2 parts of every set kind into the marginal likelihood.
     const double  *nmarg;
+    // Spectra sets with a continuum background behind the components (nfa_specset_set_continuum; null without):
+    // [n_pix][n_spec], Tc >= 0 in K of every (pixel, spectrum) -- data of the continuum map that was subtracted, no parameter.
+    // Every component's T0 (y - tbg) becomes T0 (y - tbg) - Tc.  Such a set always has chan_w, wdata and bl (a scalar noise:
+    // chan_w == 1; a zeroed record, bl_order -1, without a baseline) and runs lnl_kernel_cont.
+    const double  *cont;
 };
 // entries of R^-1 of a spectrum: its diagonal at channels 0 and N-1, 1 and N-2, and between; its first off-diagonal at
 // (0, 1) and (N-2, N-1), and between; its second off-diagonal
@@ -961,8 +966,13 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // slots at its channel (SpecDev.tmpl: shared by all pixels and rows, so cache-resident; unused slots hold zeros).  The
 // accumulators, the parts' slots in LDS, wave_sum and the part-order rule extend from four moments to eight; the epilogue is
 // tp_quad over SpecDev.tp.  One instance for every (order, number of templates).  No LDS beyond the slots, no new barrier.
+// CONT (the baseline form in the general component form only): a continuum source of brightness Tc behind all components
+// (DESIGN 4.17), SpecDev.cont of the (pixel, spectrum): one uniform load per unit.  Every component's g = T0 (y - tbg) becomes
+// g - Tc, before LAYER's "- pred" and FILL's factor.  The usual class forms g as fma(x, ., -T0 tbg): Tc joins T0 tbg once per
+// row and lane; the four rare sites subtract it.  The Gaussian class has no g: nfa_specset_set_continuum refuses that model.
+// Tc = 0 changes no bits (x - 0 is x for every x; T0 tbg > 0, so T0 tbg + 0 is itself).  No LDS, no barrier.
 template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false,
-          bool LAYER = false, bool CALIB = false, bool CORR = false, bool RESP = false, bool TMPL = false>
+          bool LAYER = false, bool CALIB = false, bool CORR = false, bool RESP = false, bool TMPL = false, bool CONT = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -1175,7 +1185,11 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     static_assert(!CORR || (WEIGHTED && !BASELINE && NCOMP == 0 && !DYN), "correlated noise: the weighted form in the general component form");
     static_assert(!RESP || CORR, "a channel response: the correlated form (white coefficients without a correlation)");
     static_assert(!TMPL || (BASELINE && NCOMP == 0 && !DYN && !CALIB && !CORR), "nuisance templates: the baseline form in the general component form");
+    static_assert(!CONT || (WEIGHTED && BASELINE && NCOMP == 0 && !DYN && !CALIB && !CORR && !TMPL),
+                  "a continuum background: the baseline form in the general component form");
     constexpr int NBL = TMPL ? NFA_TP_NB : BASELINE ? NFA_BL_NB : 1;
+    double tc = 0.0;                                               // CONT: Tc of the (pixel, spectrum), uniform over the unit
+    if constexpr (CONT) tc = ((k_dbl_p)S.cont)[p_ix * nspec + s];
     double bl_acc[NBL], bl_tot[NBL];
 #pragma unroll
     for (int k = 0; k < NBL; ++k) bl_tot[k] = 0.0;
@@ -1238,6 +1252,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
             // T0 tbg of the channel; T0 and tbg themselves are read inside the rare pass that needs them (y(T0) not a single
             // table cell): carried through the row as "maybe loaded" values they cost two register copies per row
             p3 = *(const double *)((const char *)p3s + jo);
+            if constexpr (CONT) p3 += tc;                          // the usual class: g - Tc = fma(x, ., -(T0 tbg + Tc))
             // Spectra out: the PREVIOUS row's store is issued here, behind this row's loads.  Vector-memory operations of a
             // wave complete in order (one counter, vmcnt): issued at the end of its own row, a store stood between the next
             // row's loads and their first use, and every row waited for the acknowledgement of 512 bytes written to HBM
@@ -1423,6 +1438,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                         const double y = nf_iemtex(T0 / Dk[c * 4], g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
                         g = T0 * (y - tbg);
                     }
+                    if constexpr (CONT) g -= tc;                      // the source behind all layers: g - Tc, then - pred, then f
                     if constexpr (LAYER) g -= pred;
                     if constexpr (FILL) g *= ff;
                     pred = __builtin_fma(g, one_minus_fastexp_f32((float)tau, livem), pred);
@@ -1452,6 +1468,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                         const double y = (HOISTX && NCOMP > 0) ? cx_xs[c] * (x - cx_xlo[c]) + cx_ylo[c]
                                                    : Dk[dko + DK_XS] * (x - Dk[dko + DK_XLO]) + Dk[dko + DK_YLO];
                         double g = T0 * (y - tbg);
+                        if constexpr (CONT) g -= tc;
                         if constexpr (LAYER) g -= pred;
                         if constexpr (FILL) g *= ff;
                         if (MODE == 0) { fx = g * one_minus_fastexp_table_row((double)tau); fy = rare_one(); return true; }
@@ -1459,6 +1476,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     } else {
                         const double y = nf_iemtex(x, g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
                         double g = T0 * (y - tbg);
+                        if constexpr (CONT) g -= tc;
                         if constexpr (LAYER) g -= pred;
                         if constexpr (FILL) g *= ff;
                         const double tb = g * (MODE == 0 ? one_minus_fastexp_table_row((double)tau) : nf_one_minus_fastexp_row<MODE>((double)tau, sm));
@@ -1678,6 +1696,22 @@ lnl_kernel_tmpl(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
                                                                                                   sm, n_shared, blockIdx.x, &grp);
 }
 
+// The kernels of a set with a CONTINUUM BACKGROUND (nfa_specset_set_continuum): the baseline form in the general
+// component form with lnl_body's CONT flag, 32 instances over the same five flags, beside the table like lnl_kernel_corr.
+// launch_lnl takes them when SpecDev.cont is set, with the baseline form's plan.  One instance serves every baseline order
+// (none: a zeroed record) and every Tc, a spectrum with Tc = 0 beside one with a continuum included.
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_cont(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, LAYER, false, false, false, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs,
+                                                                                                         smem, sm, n_shared, blockIdx.x, &grp);
+}
+
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one
 // 51 KB copy of the product tables, and in lnl_kernel the wave slots of the waves that are done stay empty until the
 // longest of the sixteen is: units differ by the widths of their lines, and at the metric's shape 4.5 of 8 waves per
@@ -1696,7 +1730,7 @@ lnl_kernel_tmpl(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
 #define NFA_QUEUE_WORDS  (2 * NFA_QUEUE_STRIDE)
 struct QueueArgs { SpecDev S; BatchGroup grp; const double *D; double *part; double *spec_out; long B; LnlGeom G; const double *g_tabs; };
 // (the argument segment places every argument at the next multiple of its alignment: 8 for all of these, so the struct's
-// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1032, 1304, 1312, 1320, 1328, 1336, 1376)
+// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1040, 1312, 1320, 1328, 1336, 1344, 1384)
 static_assert(sizeof(SpecDev) % 8 == 0 && sizeof(BatchGroup) % 8 == 0 && sizeof(LnlGeom) % 8 == 0 && alignof(SpecDev) == 8 &&
               alignof(BatchGroup) == 8 && alignof(LnlGeom) == 8, "QueueArgs must mirror the kernel argument segment");
 template <bool WRITE_SPEC, int NCOMP>

@@ -234,6 +234,9 @@ struct nfa_specset {
     // an uncertain noise level (nfa_specset_set_noise_uncertainty): SpecDev.nmarg and the caller's fractional 1-sigma values
     double *d_nmarg = nullptr;
     double  h_nunc[MAXSPEC] = {};
+    // a continuum background (nfa_specset_set_continuum): SpecDev.cont and the caller's values [n_pix][n_spec]; empty without
+    double *d_cont = nullptr;
+    std::vector<double> h_cont;
 };
 
 struct nfa_priors {
@@ -302,7 +305,7 @@ static int runner_mode(const nfa_runner *r) { return r->exp_mode >= 0 ? r->exp_m
 // the inputs of the launch plans: the options as they stand now, and a launch of B items of the runner's set as it is now
 static LpKnobs plan_knobs() { return {g_eng.n_cu, g_eng.setup_ti, g_eng.setup_threads, g_eng.setup_sub, g_eng.lnl_queue, g_eng.lnl_queue_wg, g_eng.coalesce, g_eng.ablate}; }
 static LpLaunch plan_launch(const nfa_runner *r, int64_t B, int mode, bool write_spec, bool has_prior, int slot) {
-    return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl_order >= 0,
+    return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl_order >= 0 || r->ss->dev.cont != nullptr,
                     r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr, r->ss->filled, r->ss->layered, r->ss->dev.cal2 != nullptr};
 }
 
@@ -567,6 +570,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     d.bl = nullptr; d.bl_order = -1;                                    // no baseline (nfa_specset_set_baseline)
     d.cal2 = nullptr;                                                   // no calibration uncertainty (nfa_specset_set_calibration)
     d.tmpl = d.tp = nullptr;                                            // no nuisance templates (nfa_specset_set_templates)
+    d.cont = nullptr;                                                   // no continuum background (nfa_specset_set_continuum)
     HIP_TRY(hipMalloc(&ss->d_lines, sizeof(LineRow) * n_spec));
     HIP_TRY(hipMemcpy(ss->d_lines, h_lines.data(), sizeof(LineRow) * n_spec, hipMemcpyHostToDevice));
     d.lines = ss->d_lines;
@@ -987,6 +991,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_resp);
     (void)hipFree(ss->d_tmpl); (void)hipFree(ss->d_tp);
     (void)hipFree(ss->d_nmarg);
+    (void)hipFree(ss->d_cont);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
@@ -1021,9 +1026,10 @@ static int specset_quiesce(nfa_specset *ss) {
 // a baseline with a zeroed record: bl_setup_kernel leaves L^-1 = 0 for order -1 and m(d) as it is), neither needs them.
 // Nuisance templates (SpecDev.tmpl set by nfa_specset_set_templates) run the same weighted form and keep records of their own
 // (SpecDev.tp) beside the baseline's, formed here for the same reason.
+// A continuum background (SpecDev.cont set by nfa_specset_set_continuum) runs the baseline form like a calibration.
 static int specset_form_records(nfa_specset *ss) {
     SpecDev &d = ss->dev;
-    const bool want_bl = d.bl_order >= 0 || d.cal2, want_tp = d.tmpl != nullptr;
+    const bool want_bl = d.bl_order >= 0 || d.cal2 || d.cont, want_tp = d.tmpl != nullptr;
     if (!want_tp) {
         (void)hipFree(ss->d_tp);
         ss->d_tp = nullptr; d.tp = nullptr;
@@ -1087,6 +1093,12 @@ int nfa_specset_set_baseline(nfa_specset *ss, int order) {
 // a calibrated set's part is chi^2 plus sigma^2 log1p(s^2 A / sigma^2): no chi^2 whose noise scale integrates
 // out in closed form.  The same words from either setter.
 #define NMARG_CALIB_REFUSAL "a set takes a calibration uncertainty or a noise uncertainty, not both: a calibrated set's part is no chi^2"
+// a continuum background (nfa_specset_set_continuum) has one kernel family, the baseline form's: the same words
+// from nfa_specset_set_continuum and from the other setter, whichever comes second
+#define CONT_CALIB_REFUSAL "a set with a calibration uncertainty takes no continuum background"
+#define CONT_CORR_REFUSAL  "a set with correlated channel noise takes no continuum background"
+#define CONT_RESP_REFUSAL  "a set with a channel response takes no continuum background"
+#define CONT_TMPL_REFUSAL  "a set with nuisance templates takes no continuum background"
 
 int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
@@ -1101,6 +1113,7 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
     if (any && d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no calibration uncertainty");
     if (any && d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no calibration uncertainty");
     if (any && d.nmarg) return fail(NFA_ERR_ARG, NMARG_CALIB_REFUSAL);
+    if (any && d.cont) return fail(NFA_ERR_ARG, CONT_CALIB_REFUSAL);
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any) {                                               // null, or all zeros: the set's former kernels and bits
@@ -1317,6 +1330,7 @@ int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
         if (d.bl_order >= 0) return fail(NFA_ERR_ARG, "a set with a baseline takes no noise correlation");
         if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no noise correlation");
         if (d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no noise correlation");
+        if (d.cont) return fail(NFA_ERR_ARG, CONT_CORR_REFUSAL);
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1355,6 +1369,7 @@ int nfa_specset_set_response(nfa_specset *ss, const double *taps) {
         if (d.bl_order >= 0) return fail(NFA_ERR_ARG, "a set with a baseline takes no channel response");
         if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no channel response");
         if (d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no channel response");
+        if (d.cont) return fail(NFA_ERR_ARG, CONT_RESP_REFUSAL);
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1427,6 +1442,7 @@ int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmp
         if (d.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no nuisance templates");
         if (d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no nuisance templates");
         if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no nuisance templates");
+        if (d.cont) return fail(NFA_ERR_ARG, CONT_TMPL_REFUSAL);
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1447,6 +1463,62 @@ int nfa_specset_templates(const nfa_specset *ss, double *out_t, int *out_n) {
     if (!ss || !ss->dev.tmpl) return 0;
     if (out_t) memcpy(out_t, ss->h_tmpl.data(), sizeof(double) * ss->h_tmpl.size());
     for (int s = 0; out_n && s < ss->dev.n_spec; ++s) out_n[s] = ss->h_ntmpl[s];
+    return 1;
+}
+
+// The device's state for the caller's continuum vals[n_pix][n_spec], valid and not all zero; null: no continuum.  The
+// weighted arrays and the baseline record follow (specset_form_records): such a set runs the baseline form.
+static int cont_apply(nfa_specset *ss, const double *vals) {
+    SpecDev &d = ss->dev;
+    if (!vals) {
+        (void)hipFree(ss->d_cont);
+        ss->d_cont = nullptr; d.cont = nullptr;
+        ss->h_cont.clear();
+        return specset_form_records(ss);
+    }
+    const size_t n = (size_t)(ss->n_pix * d.n_spec);
+    std::vector<double> keep(vals, vals + n);
+    if (!ss->d_cont) HIP_TRY(hipMalloc(&ss->d_cont, sizeof(double) * n));
+    HIP_TRY(hipMemcpy(ss->d_cont, keep.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    d.cont = ss->d_cont;
+    ss->h_cont.swap(keep);
+    return specset_form_records(ss);
+}
+
+int nfa_specset_set_continuum(nfa_specset *ss, const double *tc) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    SpecDev &d = ss->dev;
+    const int64_t n = ss->n_pix * d.n_spec;
+    bool any = false;
+    for (int64_t i = 0; tc && i < n; ++i) {
+        if (!(tc[i] >= 0.0 && tc[i] < INFINITY))              // (NaN fails both)
+            return fail(NFA_ERR_ARG, "a continuum background is a finite brightness temperature >= 0 K per (pixel, spectrum)");
+        any = any || tc[i] > 0.0;
+    }
+    if (any) {
+        if (d.model == NFA_MODEL_GAUSSIAN)
+            return fail(NFA_ERR_ARG, "the Gaussian model has no optical depth: its components cannot absorb a continuum background");
+        if (d.resp) return fail(NFA_ERR_ARG, CONT_RESP_REFUSAL);
+        if (d.corr_q1) return fail(NFA_ERR_ARG, CONT_CORR_REFUSAL);
+        if (d.cal2) return fail(NFA_ERR_ARG, CONT_CALIB_REFUSAL);
+        if (d.tmpl) return fail(NFA_ERR_ARG, CONT_TMPL_REFUSAL);
+    }
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    if (!any && !d.cont) return NFA_OK;                       // null, or all zeros, and none before: nothing changes
+    const std::vector<double> was = ss->h_cont;
+    rc = cont_apply(ss, any ? tc : nullptr);
+    if (rc) {                                                 // the set stays as it was: its former continuum, or none
+        const std::string why = g_err;
+        (void)cont_apply(ss, was.empty() ? nullptr : was.data());
+        g_err = why;
+    }
+    return rc;
+}
+
+int nfa_specset_continuum(const nfa_specset *ss, double *out) {
+    if (!ss || !ss->dev.cont) return 0;
+    if (out) memcpy(out, ss->h_cont.data(), sizeof(double) * ss->h_cont.size());
     return 1;
 }
 
@@ -1917,6 +1989,21 @@ static LnlKernel lnl_kernel_tmpl_of(int mode, bool write_spec, const LnlPlan &P)
     return lnl_kernel_tmpl_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
                               std::make_index_sequence<32>());
 }
+// ... and of a set with a continuum background: lnl_kernel_cont over the same five, with the baseline form's plan
+template <int I>
+static LnlKernel lnl_kernel_cont_inst() {
+    return lnl_kernel_cont<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_cont_at(int i, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])() = {lnl_kernel_cont_inst<(int)I>...};
+    return inst[i]();
+}
+static LnlKernel lnl_kernel_cont_of(int mode, bool write_spec, const LnlPlan &P) {
+    if (P.form != LNL_BASELINE) return nullptr;
+    return lnl_kernel_cont_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
+                              std::make_index_sequence<32>());
+}
 #ifdef NFA_TEST_HOOKS
 #include <atomic>
 // Likelihood launches by (lnl_inst_index, LnlForm) since the last reset (nfa_test_lnl_launches): host side, counted where
@@ -1948,7 +2035,8 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = S.tmpl ? lnl_kernel_tmpl_of(mode, d_spec != nullptr, P)
+    const LnlKernel kern = S.cont ? lnl_kernel_cont_of(mode, d_spec != nullptr, P)
+                         : S.tmpl ? lnl_kernel_tmpl_of(mode, d_spec != nullptr, P)
                          : S.resp ? lnl_kernel_resp_of(mode, d_spec != nullptr, P)
                          : S.corr_q1 ? lnl_kernel_corr_of(mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
@@ -2166,7 +2254,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
     const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
-                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr);
+                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

@@ -361,15 +361,18 @@ struct FusedPlan { const char *refusal, *ring_error; LnlGeom G; int n_blocks, ct
 // else -- such a set is "correlated" to its kernels even over white noise, and the reason must be its own)
 // templates: a set with nuisance templates (nfa_specset_set_templates: the batch kernels only -- such a set is weighted too,
 // and the reason must be its own)
+// continuum: a set with a continuum background (nfa_specset_set_continuum: the batch kernels only -- such a set is weighted and
+// runs the baseline form, and the reason must be its own)
 inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted, bool banded = false,
                             bool filled = false, bool layered = false, bool calibrated = false, bool correlated = false,
-                            bool response = false, bool templates = false) {
+                            bool response = false, bool templates = false, bool continuum = false) {
     FusedPlan P = {};
     P.G = lnl_geom(s, k, 1);
     if (response) P.refusal = "the resident kernel has no form for a channel response: use nfa_ring_serve";
     else if (correlated) P.refusal = "the resident kernel has no form for correlated channel noise: use nfa_ring_serve";
     else if (calibrated) P.refusal = "the resident kernel has no form for a calibration uncertainty: use nfa_ring_serve";
     else if (layered) P.refusal = "the resident kernel has no form for layered transfer: use nfa_ring_serve";
+    else if (continuum) P.refusal = "the resident kernel has no form for a continuum background: use nfa_ring_serve";
     else if (templates) P.refusal = "the resident kernel has no form for nuisance templates: use nfa_ring_serve";
     else if (s.ndim > NFA_POINT_MAXDIM || lnl_wide(s)) P.refusal = "this runner's points go through the batch kernels: use nfa_ring_serve";
     else if (filled) P.refusal = "the resident kernel has no form for a filling factor: use nfa_ring_serve";

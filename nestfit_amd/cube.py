@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_correlation, check_layered, check_noise_uncertainty, check_response, check_templates, gain_fit, half_chi2, noise_fit, nuisance_fit
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_response, check_templates, gain_fit, half_chi2, noise_fit, nuisance_fit, signed_peak
 from .core import _as_inplace_matrix
 
 
@@ -62,11 +62,15 @@ class CubeRunner:
     noise_uncertainty : None, or the fractional 1-sigma uncertainty of the spectra's noise levels (a number, or one per
         spectrum, each in [0, 0.5]; shared by all pixels), integrated out of the likelihood per (pixel, spectrum) in closed
         form; with everything but a calibration; null_lnZ is the same function of the parts at p = 0
+    continuum : None, or the brightness temperature Tc >= 0 (K) of a continuum source behind all components: a number, one
+        value per spectrum or an array [n_pix, n_spec], from the continuum map that was subtracted from the data -- data, not
+        a parameter; the line goes negative wherever J(tex) < J(Tcmb) + Tc; not with the Gaussian model, a
+        calibration, a correlation, a response or templates; null_lnZ is unchanged
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
                  model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False,
-                 calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None):
+                 calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None, continuum=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
@@ -83,6 +87,7 @@ class CubeRunner:
         correlation = check_correlation(correlation, len(xarrs), sizes, masked, baseline_order, calibration)
         response = check_response(response, len(xarrs), sizes, masked, baseline_order, calibration)
         templates = check_templates(templates, len(xarrs), sizes, calibration, correlation, response)
+        continuum = check_continuum(continuum, len(xarrs), int(np.shape(data)[0]), model, calibration, correlation, response, templates)
         if species is None and int(model) == 4 and lines is not None:
             from .lte import LteBand, LteBlend, LteLines, lines_species
             lines = list(lines)
@@ -109,6 +114,8 @@ class CubeRunner:
             self._ss.set_templates(templates)
         if noise_uncertainty is not None:
             self._ss.set_noise_uncertainty(noise_uncertainty)
+        if continuum is not None:
+            self._ss.set_continuum(continuum)
         self._data, self._noise = data, noise                # (fit_baseline, fit_gain, fit_noise)
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -278,6 +285,18 @@ class CubeRunner:
         return mean, std
 
     @property
+    def continuum(self):
+        """None, or the float64 array [n_pix, n_spec] of the continuum brightness temperatures behind the spectra (K)."""
+        tc = self._ss.continuum
+        return None if tc is None else tc.copy()
+
+    def set_continuum(self, tc):
+        """Sets (a number, one value per spectrum or [n_pix, n_spec], in K) or removes (None, zeros) the continuum background;
+        null_lnZ is read again and does not change: the null model has no absorber."""
+        self._ss.set_continuum(tc)
+        self.null_lnZ = self._ss.null_lnZ().sum(axis=1)
+
+    @property
     def noise_uncertainty(self):
         """None, or the float64 array of the fractional uncertainties of the spectra's noise levels."""
         f = self._ss.noise_uncertainty
@@ -314,11 +333,13 @@ class CubeRunner:
 
     def peak_and_integrated(self, pix, theta):
         """max_spec and sum_spec of every spectrum for parameter rows (core.pyx:532-539 as
-        `deblend_hf_intensity` uses them, main.py:1110-1113): two arrays [B, n_spec]."""
+        `deblend_hf_intensity` uses them, main.py:1110-1113): two arrays [B, n_spec].  A runner with a continuum background
+        returns the signed value of largest magnitude (`signed_peak`) in place of the maximum: the line may absorb."""
         if getattr(self, '_scratch_spec', None) is None or self._scratch_spec.shape[0] < theta.shape[0]:
             self._scratch_spec = _ffi.pinned_empty((max(theta.shape[0], 1), self.n_chan_tot))
         spec, _ = self.predict_batch(pix, theta, out=self._scratch_spec[:theta.shape[0]])
         off = self._ss.offsets
-        peak = np.stack([np.nanmax(spec[:, off[k]:off[k + 1]], axis=1) for k in range(self.n_spec)], axis=1)
+        top = np.nanmax if self._ss.continuum is None else signed_peak
+        peak = np.stack([top(spec[:, off[k]:off[k + 1]], axis=1) for k in range(self.n_spec)], axis=1)
         tot = np.stack([np.nansum(spec[:, off[k]:off[k + 1]], axis=1) for k in range(self.n_spec)], axis=1)
         return peak, tot

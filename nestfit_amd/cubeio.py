@@ -353,9 +353,12 @@ class DataCube:
     (descending) radio velocities in km/s, `dv` the channel width in km/s.  `cube` is a `SimpleCube` (or
     anything with its attributes); `noise_map` a number or a noise-map object."""
 
-    def __init__(self, cube, noise_map, trans_id=None, lines=None):
+    def __init__(self, cube, noise_map, trans_id=None, lines=None, continuum=None):
         """lines: the cube's `LineTable` (hyperfine model), `LteLines` or `LteBand` (LTE model) or `LteBlend` (LTE mix), the
-        alternative to `trans_id`."""
+        alternative to `trans_id`.
+        continuum: None, or the brightness temperature in K of the continuum source behind the line, as it was subtracted
+        from the cube: a number for every pixel, or a map in FITS order (lat, lon) like a `NoiseMap`'s data.
+        Values are >= 0; a pixel whose continuum is NaN is no good pixel.  `continuum` then is the map as [lon, lat]."""
         if lines is not None:
             from .hyperfine import LineTable
             from .lte import LteBand, LteBlend
@@ -372,6 +375,15 @@ class DataCube:
         self.spatial_shape, self.nchan = kelvin.shape[:2], kelvin.shape[2]
         if self.noise_map.shape is not None and tuple(self.noise_map.shape) != tuple(self.spatial_shape):
             raise AssertionError(f'noise map {self.noise_map.shape} does not match the cube {self.spatial_shape}')
+        self.continuum = None
+        if continuum is not None:
+            tc = np.asarray(continuum, dtype=np.float64)
+            tc = np.full(self.spatial_shape, float(tc)) if tc.ndim == 0 else tc.T
+            if tuple(tc.shape) != tuple(self.spatial_shape):
+                raise AssertionError(f'continuum map {tc.shape} does not match the cube {self.spatial_shape}')
+            if np.any(tc < 0.0) or np.any(np.isinf(tc)):
+                raise ValueError('a continuum map holds brightness temperatures >= 0 in K (NaN: no good pixel)')
+            self.continuum = np.ascontiguousarray(tc)
 
     def _ingest(self, cube):
         """(data in K as [lon, lat, chan], ascending Hz axis, matching km/s axis)."""
@@ -464,9 +476,17 @@ class CubeStack:
         rows = [dc.get_spec_data(i_lon, i_lat) for dc in self.cubes]
         return [list(r[:4]) for r in rows], any(r[4] for r in rows)
 
+    def continuum_maps(self):
+        """None where no cube has a continuum, else float64 [n_cubes, lon, lat]: the cubes' maps, zeros for a cube without."""
+        if all(getattr(dc, 'continuum', None) is None for dc in self.cubes):
+            return None
+        return np.stack([np.zeros(self.spatial_shape) if getattr(dc, 'continuum', None) is None else dc.continuum for dc in self.cubes])
+
     def get_max_snr(self, i_lon, i_lat):
         snr = []
-        for _, spec, noise, _, _ in (dc.get_spec_data(i_lon, i_lat) for dc in self.cubes):
+        for dc, (_, spec, noise, _, _) in ((dc, dc.get_spec_data(i_lon, i_lat)) for dc in self.cubes):
+            if getattr(dc, 'continuum', None) is not None:  # the line may absorb: its depth counts like a peak
+                spec = np.abs(spec)
             if np.ndim(noise):                             # over the unmasked channels of a noise per channel
                 unmasked = np.isfinite(noise)
                 snr.append(np.max(spec[unmasked] / noise[unmasked]) if unmasked.any() else 0.0)
@@ -492,6 +512,9 @@ class CubeStack:
             bad |= np.isnan(dcube.data[lon, lat, :]).any(axis=1)
             noise = dcube.noise_map.values_at(lon, lat)
             bad |= ~(noise > 0) | ~np.isfinite(noise)
+        for dcube in self.cubes:                           # (a pixel without a continuum value: the depth means nothing there)
+            if getattr(dcube, 'continuum', None) is not None:
+                bad |= np.isnan(dcube.continuum[lon, lat])
         return lon[~bad], lat[~bad]
 
     def masked_beam_pixels(self, lon=None, lat=None):
@@ -513,6 +536,9 @@ class CubeStack:
             noise = dcube.noise_map.values_at(lon, lat)
             nan |= np.isnan(dcube.data[lon, lat, :]).any(axis=1) | np.isnan(noise)
             inf |= np.isinf(noise)
+        for dcube in self.cubes:
+            if getattr(dcube, 'continuum', None) is not None:
+                nan |= np.isnan(dcube.continuum[lon, lat])
         keep = inf & ~nan
         return lon[keep], lat[keep]
 
@@ -530,6 +556,11 @@ class CubeStack:
             noise = np.stack([dc.noise_map.values_at(lon, lat) for dc in self.cubes], axis=1)
         if model in (3, 4):                                          # the hyperfine and LTE models: the cubes' line tables
             runner_kwargs = dict(runner_kwargs, lines=[getattr(dc, 'lines', None) for dc in self.cubes])
+        maps = self.continuum_maps()
+        if maps is not None:                                         # the cubes' continuum maps: [n_pix, n_spec]
+            if runner_kwargs.get('continuum') is not None:
+                raise ValueError("the continuum of a cube's pixels comes from its cubes (DataCube(..., continuum=)), not from `continuum=`")
+            runner_kwargs = dict(runner_kwargs, continuum=np.ascontiguousarray(maps[:, lon, lat].T))
         runner = CubeRunner([dc.xarr for dc in self.cubes], [dc.trans_id for dc in self.cubes], data, noise,
                             utrans, ncomp=ncomp, model=model, **runner_kwargs)
         return runner, lon, lat

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import sampler
-from ._model import check_calibration, check_correlation, check_layered, check_noise_uncertainty, check_response, check_templates
+from ._model import check_calibration, check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_response, check_templates
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
@@ -92,6 +92,12 @@ class CubeFitter:
         # an uncertain noise level per spectrum (runner_kwargs['noise_uncertainty']): and this
         self.noise_uncertainty = check_noise_uncertainty(self.runner_kwargs.get('noise_uncertainty'),
                                                          None if cubes is None else len(cubes), self.calibration)
+        # a continuum background (DataCube(..., continuum=)): the cubes' maps, and what they do not go with
+        if self.runner_kwargs.get('continuum') is not None:
+            raise ValueError("the continuum of a cube fit comes from its cubes (DataCube(..., continuum=)), not from runner_kwargs")
+        self.continuum = getattr(stack, 'continuum_maps', lambda: None)()
+        if self.continuum is not None and np.any(np.nan_to_num(self.continuum) > 0.0):
+            check_continuum(1.0, None, None, self.model_id, self.calibration, self.correlation, self.response, self.templates)
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
         self.lnZ_thresh, self.ncomp_max, self.nlive_snr_fact = lnZ_thresh, ncomp_max, nlive_snr_fact
         self.nlive_quantum = max(1, int(nlive_quantum))

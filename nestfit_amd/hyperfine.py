@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _ffi
 from ._model import (MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, EngineRunner, EngineSpectrumMixin,
-                     check_baseline_order, check_calibration, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names)
+                     check_baseline_order, check_calibration, check_continuum, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names)
 from .core import HyperfineSpectrum as _HyperfineBase
 
 N_PARAMS = 4
@@ -134,14 +134,14 @@ class HyperfineRunner(EngineRunner):
     N_MODEL = N_PARAMS
 
     def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None):
+                 noise_uncertainty=None, continuum=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
         self.spectra = list(spectra)
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
                     calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty)
+                    noise_uncertainty=noise_uncertainty, continuum=continuum)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -150,6 +150,8 @@ class HyperfineRunner(EngineRunner):
         check_layered(kwargs.get('layered', False))
         check_calibration(kwargs.get('calibration'), len(spec_data))
         check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
+        check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
+                        kwargs.get('response'), kwargs.get('templates'))
         check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
                           baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
         check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
@@ -164,7 +166,7 @@ class HyperfineRunner(EngineRunner):
 
     def predict(self, params):
         params = self._check_params(params)
-        if self.layered:
+        if self._predict_through_set():
             return self._predict_layered(params)
         for s in self.spectra:
             hf_predict(s, params)

@@ -333,6 +333,34 @@ def check_model_layered(store, runner=None):
     return layered
 
 
+def check_model_continuum(store, stack=None, runner=None):
+    """The continuum maps the store was fitted with (`HdfStore.read_model_continuum`: (t, b, l) or None), after checking
+    them against the stack's maps, where it has any, and against the `runner` where the caller hands one that says
+    (`.continuum`: [n_spec] of a one-pixel runner, [n_pix, n_spec] over the stack's good pixels of a `CubeRunner`): ValueError
+    where they differ -- the runner's spectra would not be the model of the fit."""
+    stored = store.read_model_continuum()
+    same = lambda a, b: a.shape == b.shape and np.array_equal(np.nan_to_num(a), np.nan_to_num(b))
+    maps = getattr(stack, 'continuum_maps', lambda: None)()
+    if maps is not None and (stored is None or not same(np.asarray(maps).transpose(0, 2, 1), stored)):
+        raise ValueError("the stack's continuum maps differ from the ones the store was fitted with (/model_continuum)")
+    if runner is not None and hasattr(runner, 'continuum'):
+        theirs = runner.continuum
+        if (theirs is None) != (stored is None or not np.any(np.nan_to_num(stored) > 0.0)):
+            raise ValueError(f"the store was fitted {'without' if theirs is not None else 'with'} a continuum background, the runner "
+                             f"has {'one' if theirs is not None else 'none'}")
+        if theirs is not None:
+            theirs = np.asarray(theirs, dtype=np.float64)
+            if theirs.ndim == 1:                             # one pixel's row: every pixel of the store has it
+                ok = np.isfinite(stored).all(axis=0)
+                agree = theirs.shape[0] == stored.shape[0] and np.all(stored[:, ok] == theirs[:, None])
+            else:                                            # a CubeRunner over the stack's good pixels, in their order
+                lon, lat = stack.good_pixels() if stack is not None else (np.zeros(0, int), np.zeros(0, int))
+                agree = theirs.shape == (lon.size, stored.shape[0]) and np.array_equal(theirs, stored[:, lat, lon].T)
+            if not agree:
+                raise ValueError("the runner's continuum differs from the one the store was fitted with (/model_continuum)")
+    return stored
+
+
 def _spec_name(k, dc):
     """Dataset name of cube k under model_spec: trans<ID> (main.py:1190), spec<k> for a cube with a `LineTable` (hyperfine model)."""
     return f'spec{k}' if getattr(dc, 'lines', None) is not None else f'trans{dc.trans_id}'
@@ -358,7 +386,17 @@ def _device_predictor(store, stack, ncomp=1, layered=False):
         if store.read_model_species():                   # an LTE mix: the species in the order of the fit
             extra['species'] = store.read_model_species()
             extra['fill'] = check_model_fill(store)      # ... with a filling factor as the last parameter, if the fit had one
-    runner = CubeRunner(xarrs, trans, np.zeros((1, chan_tot)), np.ones((1, len(xarrs))), None, ncomp=ncomp,
+    # ... unless the store has continuum maps: then every map pixel is a pixel of the set, with its own Tc, and
+    # a component alone is that component against the pixel's continuum
+    cont = check_model_continuum(store, stack)
+    n_lat = 1
+    if cont is not None and np.any(np.nan_to_num(cont) > 0.0):
+        n_lat = cont.shape[1]
+        n_pix = cont.shape[1] * cont.shape[2]
+        extra['continuum'] = np.ascontiguousarray(np.nan_to_num(cont).transpose(2, 1, 0).reshape(n_pix, -1))     # pixel l * n_lat + b
+    else:
+        cont, n_pix = None, 1
+    runner = CubeRunner(xarrs, trans, np.zeros((n_pix, chan_tot)), np.ones((n_pix, len(xarrs))), None, ncomp=ncomp,
                         model=model_id, layered=layered, **extra)
     runner.set_exp_mode('table')                         # map products in the reference's own arithmetic: a one-off, not a rate
 
@@ -366,6 +404,8 @@ def _device_predictor(store, stack, ncomp=1, layered=False):
 
     def predict(lon, lat, theta, want_spectra):
         pix = np.zeros(theta.shape[0], dtype=np.int32)
+        if cont is not None:
+            pix = (np.asarray(lon, dtype=np.int64) * n_lat + np.asarray(lat, dtype=np.int64)).astype(np.int32)
         if want_spectra:
             # (one buffer the device addresses itself serves every batch: the callers use a batch's spectra before
             # they ask for the next)
@@ -495,6 +535,7 @@ def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, 
         check_model_lines(store, stack)
         check_model_fill(store, runner)
     check_model_layered(store, runner)
+    check_model_continuum(store, stack, runner)
     aggregate_run_attributes(store)
     convolve_evidence(store, evid_kernel)
     aggregate_run_products(store)

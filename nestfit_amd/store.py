@@ -462,6 +462,12 @@ class HdfStore:
                                        None if cubes is None else len(cubes))
         if nunc is not None:
             self.hdf.attrs['noise_uncertainty'] = nunc
+        # a continuum background behind the components (DataCube(..., continuum=)): root dataset
+        # `model_continuum`, float64 (t, b, l) like the per-spectrum map products, in K, NaN where a map has none.  A store
+        # without it was fitted against the cosmic background alone.
+        maps = getattr(getattr(fitter, 'stack', None), 'continuum_maps', lambda: None)()
+        if maps is not None:
+            self.hdf.create_dataset('model_continuum', data=np.ascontiguousarray(np.asarray(maps, dtype=np.float64).transpose(0, 2, 1)))
         quantum = getattr(fitter, 'nlive_quantum', 1)
         if quantum != 1:                 # a deviation from main.py:445-447 is written down where the results are
             self.hdf.attrs['nlive_quantum'] = int(quantum)
@@ -521,6 +527,14 @@ class HdfStore:
         assert self.is_open
         nunc = self.hdf.attrs.get('noise_uncertainty')
         return None if nunc is None else np.asarray(nunc, dtype=np.float64)
+
+    def read_model_continuum(self):
+        """The continuum maps the store was fitted with (`DataCube(..., continuum=)`): the root dataset `model_continuum` as a
+        float64 array (t, b, l) in K, zeros for a spectrum without a continuum beside one with; None for a store without it."""
+        assert self.is_open
+        if 'model_continuum' not in self.hdf:
+            return None
+        return np.asarray(self.hdf['model_continuum'][...], dtype=np.float64)
 
     def read_model_fill(self):
         """Whether the store was fitted with a beam filling factor per component (`LteMix(species, fill=True)`): the root
