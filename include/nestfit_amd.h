@@ -451,6 +451,27 @@ int nfa_specset_noise_uncertainty(const nfa_specset *ss, double *out);
 int nfa_specset_set_continuum(nfa_specset *ss, const double *tc);
 /* 1 and out[n_pix][n_spec] = the values set (out may be null), or 0 for a set without a continuum (and for null) */
 int nfa_specset_continuum(const nfa_specset *ss, double *out);
+/* A robust likelihood: each channel's noise is Student-t with nu degrees of freedom and scale sigma_j instead of Gaussian
+ * -- a Gaussian whose precision per CHANNEL is Gamma(nu / 2, nu / 2)-distributed and integrated out in closed form -- so that
+ * an interference spike or a bad channel nobody flagged costs the logarithm of its residual, not its square.  With the
+ * weights w_j of a noise per channel (1 for a scalar noise, 0 where masked) and a_j = w_j / (nu sigma_ref^2),
+ *     lnL_s = -(nu + 1) / 2 sum_j log1p(a_j (d_j - p_j)^2)
+ * without the normalisation, as everywhere; Gaussian in the limit of large nu.  It adds no sampler dimension.
+ * nfa_specset_null_lnz is the same expression at p = 0, bit for bit the likelihood kernel's value there.
+ * nu[n_spec]: 0 keeps that spectrum Gaussian beside robust ones.  nu = NULL or all zeros removes it (the set's former kernels
+ * and results bit for bit).  NFA_ERR_ARG, the set left as it was: a value that is not finite, or neither 0 nor in [1, 1e6]
+ * (beyond 1e6 the value is the Gaussian one within 1e-6: leave it out); a set with a baseline, nuisance templates, a
+ * calibration uncertainty, a channel response, correlated channel noise, a noise uncertainty or a continuum background
+ * ("a set with ... takes no robust likelihood": under a t likelihood no linear nuisance has a closed form and a part is no
+ * chi^2) -- and those setters refuse a robust set ("a set with a robust likelihood takes no ...").  With a scalar noise
+ * and a noise per channel, masked channels, layered and filled sets, every model: yes.  Like nfa_specset_set_baseline it
+ * launches held batches first, synchronises the device and drops the runners' captured single-point graphs: call it between
+ * batches.  nfa_specset_set_data keeps it.  Spectra out do not change.  Such sets go through the batch kernels (the general
+ * component form); single points and a broker's handful too, and nfa_ring_serve_device refuses their runners ("the resident
+ * kernel has no form for a robust likelihood: use nfa_ring_serve"). */
+int nfa_specset_set_robust(nfa_specset *ss, const double *nu);
+/* 1 and out[n_spec] = the values set (out may be null), or 0 for a set without a robust likelihood (and for null) */
+int nfa_specset_robust(const nfa_specset *ss, double *out);
 /* tbg[sum(sizes)] = 1/expm1(h nu / (k TCMB))           (ammonia.pyx:273-277) */
 int nfa_specset_tbg(const nfa_specset *ss, double *out);
 int64_t nfa_specset_chan_tot(const nfa_specset *ss);

@@ -10,7 +10,7 @@ from .core import (ConstantPrior, CenSepPrior, Distribution, DuplicatePrior, Ord
 from .ammonia import AmmoniaRunner, AmmoniaSpectrum, amm_predict
 from .diazenylium import DiazenyliumRunner, DiazenyliumSpectrum, nnhp_predict
 from .gaussian import GaussianRunner, gauss_predict
-from ._model import HANNING, HANNING_RESPONSE, ar1, correlation_of_response, ripple, smoothed
+from ._model import HANNING, HANNING_RESPONSE, ar1, check_robust, correlation_of_response, ripple, robust_lnl, smoothed
 from . import ammonia, diazenylium, gaussian, hyperfine, lte
 from .hyperfine import HyperfineRunner, LineTable
 from .lte import LteBand, LteBlend, LteLines, LteMix, LteRunner, LteSpectrum, Molecule, lte_predict

@@ -82,6 +82,8 @@ SIGNATURES = {
     'nfa_specset_noise_uncertainty': (C.c_int, [C.c_void_p, _dp]),
     'nfa_specset_set_continuum': (C.c_int, [C.c_void_p, _dp]),
     'nfa_specset_continuum': (C.c_int, [C.c_void_p, _dp]),
+    'nfa_specset_set_robust': (C.c_int, [C.c_void_p, _dp]),
+    'nfa_specset_robust': (C.c_int, [C.c_void_p, _dp]),
     'nfa_specset_tbg': (C.c_int, [C.c_void_p, _dp]),
     'nfa_specset_chan_tot': (C.c_int64, [C.c_void_p]),
     'nfa_priors_create': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(PriorDesc), C.c_int,

@@ -389,6 +389,102 @@ def check_continuum(tc, n_spec=None, n_pix=None, model=None, calibration=None, c
     return np.ascontiguousarray(out)
 
 
+ROBUST_MIN, ROBUST_MAX = 1.0, 1e6
+_ROB_NOT_WITH = 'a robust likelihood (robust) does not go with {}: under Student-t noise no linear nuisance has a closed form and a part is no chi^2'
+
+
+def check_robust(nu, n_spec=None, baseline_order=None, calibration=None, correlation=None, response=None, templates=None,
+                 noise_uncertainty=None, continuum=None):
+    """`robust` of a runner: the degrees of freedom nu of the Student-t channel noise of every spectrum.  None
+    for none; a number applies to all `n_spec` spectra; else one value per spectrum.  Every value is finite and either 0
+    (that spectrum stays Gaussian) or in [1, 1e6] (beyond, the value is the Gaussian one within 1e-6: leave it out); all
+    zeros is None.  A robust likelihood goes with none of a baseline, a calibration uncertainty, a noise correlation, a
+    channel response, nuisance templates, a noise uncertainty and a continuum background.  Returns None or a float64 array
+    (of n_spec values when n_spec is given); ValueError otherwise.  Needs no device."""
+    if nu is None:
+        return None
+    what = 'robust must be None, degrees of freedom in [1, 1e6] (0: Gaussian) or one such number per spectrum'
+    is_num = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    if is_num(nu):
+        vals = [nu] * (1 if n_spec is None else int(n_spec))
+    elif isinstance(nu, np.ndarray) and nu.ndim == 1 and nu.dtype.kind in 'iuf':
+        vals = list(nu)
+    elif isinstance(nu, (list, tuple)) and all(is_num(v) for v in nu):
+        vals = list(nu)
+    else:
+        raise ValueError(f'{what}, not {nu!r}')
+    if not is_num(nu) and n_spec is not None and len(vals) != int(n_spec):
+        raise ValueError(f'{what}: {len(vals)} values for {int(n_spec)} spectra')
+    out = np.array(vals, dtype=np.float64)
+    if out.size == 0 or not np.all(np.isfinite(out)) or np.any((out != 0.0) & ((out < ROBUST_MIN) | (out > ROBUST_MAX))):
+        raise ValueError(f'{what}, not {nu!r}')
+    if not np.any(out > 0.0):
+        return None
+    if check_baseline_order(baseline_order) is not None:
+        raise ValueError(_ROB_NOT_WITH.format('a baseline (baseline_order)'))
+    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
+        raise ValueError(_ROB_NOT_WITH.format('a calibration uncertainty (calibration)'))
+    if check_correlation(correlation) is not None:            # (all zeros: none)
+        raise ValueError(_ROB_NOT_WITH.format('a noise correlation (correlation)'))
+    if check_response(response) is not None:                  # (the identity: none)
+        raise ValueError(_ROB_NOT_WITH.format('a channel response (response)'))
+    if templates is not None and any(t is not None for t in templates):
+        raise ValueError(_ROB_NOT_WITH.format('nuisance templates (templates)'))
+    if check_noise_uncertainty(noise_uncertainty) is not None:
+        raise ValueError(_ROB_NOT_WITH.format('a noise uncertainty (noise_uncertainty)'))
+    if continuum is not None and np.any(np.asarray(continuum, dtype=np.float64) > 0.0):
+        raise ValueError(_ROB_NOT_WITH.format('a continuum background (continuum)'))
+    return out
+
+
+def _robust_a(noise, n, nu):
+    """(a_j, sigma_ref) of one spectrum: a_j = w_j / (nu sigma_ref^2), w_j = (sigma_ref / sigma_j)^2, 0 where masked (inf)."""
+    sig = np.broadcast_to(np.asarray(noise, dtype=np.float64), (n,))
+    live = np.isfinite(sig)
+    ref = float(np.min(sig[live])) if np.any(live) else 1.0
+    w = np.where(live, (ref / np.where(live, sig, 1.0)) ** 2, 0.0)
+    return w / (nu * (ref * ref)), ref
+
+
+def robust_lnl(data, pred, noise, nu):
+    """The log-likelihood of ONE spectrum under Student-t channel noise with `nu` degrees of freedom, in the form the engine
+    takes: with a_j = w_j / (nu sigma_ref^2), g = a / (1 + a d^2) and t = p (g p - 2 g d),
+    -(nu + 1) / 2 (sum_j log1p(a_j d_j^2) + sum_j log1p(t_j)).  `noise` is a scalar or one value per channel (inf: masked);
+    nu = 0: the Gaussian -chi^2 / (2 sigma^2).  numpy on the host."""
+    d, p = np.asarray(data, dtype=np.float64), np.asarray(pred, dtype=np.float64)
+    if not nu > 0.0:
+        return -half_chi2(d, p, noise)[0]
+    a, _ = _robust_a(noise, d.shape[0], float(nu))
+    d = np.where(a > 0.0, d, 0.0)
+    ad2 = a * d * d
+    g = a / (1.0 + ad2)
+    gd = g * d
+    t = p * (g * p - 2.0 * gd)
+    return float(-0.5 * (nu + 1.0) * (np.sum(np.log1p(ad2)) + np.sum(np.log1p(t))))
+
+
+def robust_outliers(data, pred, noise, nu):
+    """The posterior mean of every channel's precision factor under Student-t noise: (nu + 1) / (nu + r_j^2 /
+    sigma_j^2), r = data - pred -- about 1 for a good channel, towards 0 for one the fit distrusted; 1 everywhere for nu = 0
+    and NaN at a masked channel.  numpy on the host."""
+    d, p = np.asarray(data, dtype=np.float64), np.asarray(pred, dtype=np.float64)
+    sig = np.broadcast_to(np.asarray(noise, dtype=np.float64), d.shape)
+    live = np.isfinite(sig)
+    if not nu > 0.0:
+        return np.where(live, 1.0, np.nan)
+    z = np.where(live, (d - p) / np.where(live, sig, 1.0), 0.0)
+    return np.where(live, (nu + 1.0) / (nu + z * z), np.nan)
+
+
+def robust_prefactor(noise, n, nu):
+    """`Spectrum.prefactor` under Student-t channel noise: the sum over the unmasked channels of lgamma((nu + 1) / 2) -
+    lgamma(nu / 2) - ln(nu pi sigma_j^2) / 2, the constant that -(nu + 1) / 2 sum log1p(a r^2) leaves out."""
+    from math import lgamma, log, pi
+    sig = np.broadcast_to(np.asarray(noise, dtype=np.float64), (int(n),))
+    sig = sig[np.isfinite(sig)]
+    return float(sig.size * (lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * log(nu * pi)) - np.sum(np.log(sig)))
+
+
 def signed_peak(spec, axis=-1):
     """The signed value of largest magnitude along `axis`, NaNs ignored (NaN where all are): the peak of a line that may
     absorb (a runner with a continuum background) as `nanmax` is the peak of one that emits."""
@@ -637,13 +733,33 @@ class _SpecSet:
         self.templates = None
         self.noise_uncertainty = None
         self.continuum = None
+        self.robust = None
         self.masked = bool(self.per_channel and not np.all(np.isfinite(noise)))
+
+    def set_robust(self, nu):
+        """The degrees of freedom of the spectra's Student-t channel noise (`check_robust`'s argument), or none (None,
+        zeros): nfa_specset_set_robust.  null_lnZ() follows."""
+        nu = check_robust(nu, self.n_spec, self.baseline_order, self.calibration, self.correlation, self.response, self.templates,
+                          self.noise_uncertainty, self.continuum)
+        _ffi.check(_ffi.load().nfa_specset_set_robust(self.handle, None if nu is None else _ffi.dptr(nu)))
+        self.robust = nu
+
+    def get_robust(self):
+        """The degrees of freedom as the engine holds them (nfa_specset_robust): None, or float64 [n_spec]."""
+        out = np.zeros(self.n_spec)
+        return out if _ffi.load().nfa_specset_robust(self.handle, _ffi.dptr(out)) else None
+
+    def _no_robust(self, what):
+        if self.robust is not None:
+            raise ValueError(_ROB_NOT_WITH.format(what))
 
     def set_continuum(self, tc):
         """The continuum brightness temperature behind the components, per (pixel, spectrum) (`check_continuum`'s argument:
         a number, [n_spec] or [n_pix, n_spec]), or none (None, zeros): nfa_specset_set_continuum.  null_lnZ() does not
         change: the null model has no absorber."""
         tc = check_continuum(tc, self.n_spec, self.n_pix, self.model, self.calibration, self.correlation, self.response, self.templates)
+        if tc is not None:
+            self._no_robust('a continuum background (continuum)')
         _ffi.check(_ffi.load().nfa_specset_set_continuum(self.handle, None if tc is None else _ffi.dptr(tc)))
         self.continuum = tc
 
@@ -658,6 +774,8 @@ class _SpecSet:
         tmpl = check_templates(tmpl, self.n_spec, self.sizes, self.calibration, self.correlation, self.response)
         if tmpl is not None and self.continuum is not None:
             raise ValueError('nuisance templates do not go with a continuum background (continuum)')
+        if tmpl is not None:
+            self._no_robust('nuisance templates (templates)')
         if tmpl is None:
             _ffi.check(_ffi.load().nfa_specset_set_templates(self.handle, None, None))
         else:
@@ -687,6 +805,8 @@ class _SpecSet:
             raise ValueError('a channel response does not go with nuisance templates (templates)')
         if resp is not None and self.continuum is not None:
             raise ValueError('a channel response does not go with a continuum background (continuum)')
+        if resp is not None:
+            self._no_robust('a channel response (response)')
         _ffi.check(_ffi.load().nfa_specset_set_response(self.handle, None if resp is None else _ffi.dptr(resp)))
         self.response = resp
 
@@ -699,6 +819,8 @@ class _SpecSet:
             raise ValueError('a noise correlation does not go with nuisance templates (templates)')
         if corr is not None and self.continuum is not None:
             raise ValueError('a noise correlation does not go with a continuum background (continuum)')
+        if corr is not None:
+            self._no_robust('a noise correlation (correlation)')
         _ffi.check(_ffi.load().nfa_specset_set_correlation(self.handle, None if corr is None else _ffi.dptr(corr)))
         self.correlation = corr
 
@@ -707,6 +829,8 @@ class _SpecSet:
         (`check_noise_uncertainty`'s argument), or none (None, zeros): nfa_specset_set_noise_uncertainty.  null_lnZ()
         follows."""
         f = check_noise_uncertainty(f, self.n_spec, self.calibration)
+        if f is not None:
+            self._no_robust('a noise uncertainty (noise_uncertainty)')
         _ffi.check(_ffi.load().nfa_specset_set_noise_uncertainty(self.handle, None if f is None else _ffi.dptr(f)))
         self.noise_uncertainty = f
 
@@ -724,6 +848,8 @@ class _SpecSet:
             raise ValueError('a calibration uncertainty does not go with nuisance templates (templates)')
         if cal is not None and self.continuum is not None:
             raise ValueError('a calibration uncertainty does not go with a continuum background (continuum)')
+        if cal is not None:
+            self._no_robust('a calibration uncertainty (calibration)')
         _ffi.check(_ffi.load().nfa_specset_set_calibration(self.handle, None if cal is None else _ffi.dptr(cal)))
         self.calibration = cal
 
@@ -742,6 +868,8 @@ class _SpecSet:
             raise ValueError('a baseline does not go with a channel response (response)')
         if order is not None and self.correlation is not None:
             raise ValueError('a baseline does not go with a noise correlation (correlation)')
+        if order is not None:
+            self._no_robust('a baseline (baseline_order)')
         _ffi.check(_ffi.load().nfa_specset_set_baseline(self.handle, -1 if order is None else order))
         self.baseline_order = order
 
@@ -857,8 +985,13 @@ class EngineRunner(Runner):
     N_MODEL = 6
 
     def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False,
-               calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None, continuum=None):
-        """continuum: None, or the brightness temperature Tc >= 0 (K) of a continuum source behind all components -- a number
+               calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None, continuum=None, robust=None):
+        """robust: None, or the degrees of freedom nu of Student-t channel noise -- a number for all spectra or one per
+        spectrum, each 0 (that spectrum stays Gaussian) or in [1, 1e6] -- so that an interference spike or an unflagged bad
+        channel costs the logarithm of its residual, not its square (nfa_specset_set_robust); 4 is a common
+        choice, `cubeio.estimate_tails` measures one.  With a scalar noise, a noise per channel, masked channels, `layered`
+        and filled sets; with none of the other likelihood options.  null_lnZ is the same expression at p = 0.
+        continuum: None, or the brightness temperature Tc >= 0 (K) of a continuum source behind all components -- a number
         for all spectra or one per spectrum -- taken from the continuum map that was subtracted from the data: data, not a
         parameter (nfa_specset_set_continuum).  The line then goes negative wherever J(tex) < J(Tcmb) + Tc.  All
         zeros is None.  Not with the Gaussian model, a calibration, a correlation, a response or templates.  null_lnZ is
@@ -900,6 +1033,8 @@ class EngineRunner(Runner):
         templates = check_templates(templates, len(spectra), [s.size for s in spectra], calibration,
                                     check_correlation(correlation, len(spectra)), check_response(response, len(spectra)))
         continuum = check_continuum(continuum, len(spectra), None, self.MODEL, calibration, correlation, response, templates)
+        robust = check_robust(robust, len(spectra), baseline_order, calibration, correlation, response, templates, noise_uncertainty,
+                              continuum)
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -941,6 +1076,37 @@ class EngineRunner(Runner):
             self.set_noise_uncertainty(noise_uncertainty)
         if continuum is not None:
             self.set_continuum(continuum)
+        if robust is not None:
+            self.set_robust(robust)
+
+    @property
+    def robust(self):
+        """None, or the float64 array [n_spec] of the degrees of freedom of the spectra's Student-t channel noise."""
+        nu = self._ss.robust
+        return None if nu is None else nu.copy()
+
+    def set_robust(self, nu):
+        """Sets (a number, or one per spectrum) or removes (None, zeros) the robust likelihood of this runner's spectra;
+        null_lnZ follows, and the spectra's `prefactor`.  The spectra's private one-spectrum sets stay Gaussian: a
+        spectrum's own `loglikelihood` is the plain one; the runner's `loglikelihood`, `loglikelihood_batch` and
+        `predict_batch` are the robust ones."""
+        self._ss.set_robust(nu)
+        nu = self._ss.robust
+        self._refresh_null_lnZ()
+        for k, s in enumerate(self._model_spectra()):
+            s.set_robust(None if nu is None else nu[k])
+
+    def fit_outliers(self, params):
+        """Per spectrum, every channel's posterior mean precision factor (nu + 1) / (nu + r_j^2 / sigma_j^2) at physical
+        `params`: a list of n_spec arrays, about 1 for a good channel and towards 0 for one the fit distrusted (1 everywhere
+        in a spectrum with nu = 0, NaN at a masked channel).  numpy on the host (`robust_outliers`) over `predict_batch`'s
+        spectra.  ValueError without a robust likelihood."""
+        nu = self.robust
+        if nu is None:
+            raise ValueError('this runner has no robust likelihood (robust=None)')
+        spec = self.predict_batch(np.asarray(params, dtype=np.float64).reshape(1, -1))[0][0]
+        off = self._ss.offsets
+        return [robust_outliers(s.data, spec[off[k]:off[k + 1]], s.noise, nu[k]) for k, s in enumerate(self._model_spectra())]
 
     @property
     def continuum(self):
@@ -983,7 +1149,7 @@ class EngineRunner(Runner):
         (the reference's spectrum-alone sum)."""
         ss = self._ss
         if (self.baseline_order is not None or ss.templates is not None or ss.correlation is not None
-                or ss.noise_uncertainty is not None):
+                or ss.noise_uncertainty is not None or ss.robust is not None):
             self.null_lnZ = float(ss.null_lnZ().sum())
         else:
             self.null_lnZ = float(sum(s.null_lnZ for s in self._model_spectra()))

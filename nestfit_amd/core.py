@@ -344,6 +344,7 @@ class Spectrum:
         self._prefactor_noise = 0.0
         self.correlation = None
         self.noise_uncertainty = None
+        self.robust = None
         self.xarr = xarr
         self.data = data
         self.size = int(xarr.shape[0])
@@ -382,6 +383,17 @@ class Spectrum:
         self._prefactor_noise = noise_prefactor(self.n_chan, f)
         self.noise_uncertainty = f
         self.prefactor = self._prefactor_base + self._prefactor_noise
+
+    def set_robust(self, nu):
+        """The normalisation of a likelihood under Student-t channel noise with `nu` degrees of freedom:
+        `prefactor` is the sum over the unmasked channels of lgamma((nu + 1) / 2) - lgamma(nu / 2) - ln(nu pi sigma_j^2) / 2;
+        None or 0: the Gaussian value again.  (A robust likelihood goes with neither a correlation nor a noise uncertainty.)
+        A runner's `set_robust` calls this."""
+        from ._model import robust_prefactor
+        nu = None if nu is None or float(nu) == 0.0 else float(nu)
+        self.robust = nu
+        self.prefactor = (self._prefactor_base + self._prefactor_noise if nu is None
+                          else robust_prefactor(self.noise, self.size, nu))
 
 
 class HyperfineSpectrum(Spectrum):

@@ -169,6 +169,13 @@ struct SpecDev {
     // Every component's T0 (y - tbg) becomes T0 (y - tbg) - Tc.  Such a set always has chan_w, wdata and bl (a scalar noise:
     // chan_w == 1; a zeroed record, bl_order -1, without a baseline) and runs lnl_kernel_cont.
     const double  *cont;
+    // Spectra sets with a robust likelihood (nfa_specset_set_robust; null without): [n_pix][n_spec][2], {nu, k}:
+    // the degrees of freedom of the spectrum's Student-t channel noise (0: the spectrum stays Gaussian) and k = (nu + 1)
+    // sigma_ref^2 (1 for nu = 0).  While it lasts chan_w holds g = a / (1 + a d^2), a = w / (nu sigma_ref^2), and wdata g d
+    // (rob_setup_kernel; the set's own weights stay in its buffer behind them; a Gaussian spectrum: w and w d), and totsq
+    // k sum log1p(a d^2): part = totsq + k sum log1p(p (g p - 2 g d)) makes -part / (2 sigma_ref^2) the likelihood.  Such a
+    // set runs lnl_kernel_robust.
+    const double  *rob;
 };
 // entries of R^-1 of a spectrum: its diagonal at channels 0 and N-1, 1 and N-2, and between; its first off-diagonal at
 // (0, 1) and (N-2, N-1), and between; its second off-diagonal
@@ -971,8 +978,16 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // g - Tc, before LAYER's "- pred" and FILL's factor.  The usual class forms g as fma(x, ., -T0 tbg): Tc joins T0 tbg once per
 // row and lane; the four rare sites subtract it.  The Gaussian class has no g: nfa_specset_set_continuum refuses that model.
 // Tc = 0 changes no bits (x - 0 is x for every x; T0 tbg > 0, so T0 tbg + 0 is itself).  No LDS, no barrier.
+// ROBUST (the weighted form in the general component form only): Student-t channel noise.  chan_w and wdata
+// hold g and g d, and the channel's term t = pred (g pred - 2 g d), formed in fp64 as in the weighted form, enters as log1p(t):
+// 1 + t = (1 + a (d - p)^2) / (1 + a d^2) > 0, and t = 0 where the model is 0 or the channel masked, so the rows no window
+// touches stay unread.  The logarithm is fp64 in the table mode and fp32 in the fast mode, added to the fp64 sum: rounding t
+// to fp32 and log1pf's own error are each a few 2^-24 |t| / (1 + t), inside the mode's 1e-6 of g (p^2 + 2 |d p|) max(1, 1 /
+// (1 + t)), and the fp64 one cost the fast mode 1.57 against the general weighted form at two components where this costs
+// 1.31.  A spectrum with nu = 0 beside robust ones takes the weighted form's own fma (a
+// branch uniform over the unit).  The epilogue is totsq + k tot, k of SpecDev.rob.  No LDS, no barrier.
 template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false,
-          bool LAYER = false, bool CALIB = false, bool CORR = false, bool RESP = false, bool TMPL = false, bool CONT = false>
+          bool LAYER = false, bool CALIB = false, bool CORR = false, bool RESP = false, bool TMPL = false, bool CONT = false, bool ROBUST = false>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
@@ -1187,6 +1202,9 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     static_assert(!TMPL || (BASELINE && NCOMP == 0 && !DYN && !CALIB && !CORR), "nuisance templates: the baseline form in the general component form");
     static_assert(!CONT || (WEIGHTED && BASELINE && NCOMP == 0 && !DYN && !CALIB && !CORR && !TMPL),
                   "a continuum background: the baseline form in the general component form");
+    static_assert(!ROBUST || (WEIGHTED && !BASELINE && NCOMP == 0 && !DYN && !CORR), "a robust likelihood: the weighted form in the general component form");
+    bool rob_t = false;                                            // ROBUST: the spectrum's nu is not 0, uniform over the unit
+    if constexpr (ROBUST) rob_t = ((k_dbl_p)S.rob)[2 * (p_ix * nspec + s)] != 0.0;
     constexpr int NBL = TMPL ? NFA_TP_NB : BASELINE ? NFA_BL_NB : 1;
     double tc = 0.0;                                               // CONT: Tc of the (pixel, spectrum), uniform over the unit
     if constexpr (CONT) tc = ((k_dbl_p)S.cont)[p_ix * nspec + s];
@@ -1528,6 +1546,11 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                 if (!owner) pred = 0.0;
                 acc = __builtin_fma(pred, __builtin_fma(-2.0, dj, wj * pred), acc);
                 acc = __builtin_fma(2.0 * pred, __builtin_fma(q1j, pn1, q2j * pn2), acc);
+            } else if constexpr (ROBUST) {
+                // lanes beyond N and masked channels: t = 0, log1p(0) = 0
+                const double x = __builtin_fma(-2.0, dj, wj * pred);
+                if (rob_t) acc += MODE == 2 ? (double)log1pf((float)(pred * x)) : log1p(pred * x);
+                else acc = __builtin_fma(pred, x, acc);
             } else
             // lanes beyond N: pred = 0
             if (any) acc = __builtin_fma(pred, __builtin_fma(-2.0, dj, WEIGHTED ? wj * pred : pred), acc);
@@ -1601,6 +1624,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     // sum of squared deviations of the unit; lnl_sum_kernel scales and adds
     if (lane == 0 && part) {
         if (BASELINE) part[unit] = (S.totsq[p_ix * nspec + s] + tot) - bl_q;
+        else if constexpr (ROBUST) part[unit] = __builtin_fma(S.rob[2 * (p_ix * nspec + s) + 1], tot, S.totsq[p_ix * nspec + s]);
         else part[unit] = S.totsq[p_ix * nspec + s] + tot;
     }
 }
@@ -1710,6 +1734,22 @@ lnl_kernel_cont(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
     if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
     lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, LAYER, false, false, false, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs,
                                                                                                          smem, sm, n_shared, blockIdx.x, &grp);
+}
+
+// The kernels of a set with a ROBUST LIKELIHOOD (nfa_specset_set_robust): the weighted form in the general
+// component form with lnl_body's ROBUST flag, 32 instances over the same five flags, beside the table like lnl_kernel_corr.
+// launch_lnl takes them when SpecDev.rob is set, with the weighted form's plan.  One instance serves every nu, a Gaussian
+// spectrum (nu = 0) beside robust ones included.
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
+lnl_kernel_robust(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+                  double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int n_shared = 0;
+    const double *sm = smem;
+    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, FILL, LAYER, false, false, false, false, false, true>(S, nullptr, D, part, spec_out, B, G,
+                                                                                                                g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one
@@ -1994,6 +2034,50 @@ __global__ void nmarg_setup_kernel(SpecDev S, long n_pix, const double *__restri
         out[2 * u] = a;
         out[2 * u + 1] = a == 0.0 ? 0.0 : a + 0.5 * nu;
     }
+}
+
+// A robust likelihood, pixels [pix0, pix0 + n_pix): g = a / (1 + a d^2) and g d of every channel, a = w / (nu
+// sigma_ref^2) of the set's own weights `w` (null, a scalar noise: 1), into `g` and `gd`; totsq = k sum_j log1p(a_j d_j^2), k =
+// (nu + 1) sigma_ref^2, and the record {nu, k}.  A spectrum with nu = 0 keeps the weighted set's: w, w d, the sums of w d^2
+// that launch_rowsq left in totsq, and k = 1.  One wave per (pixel, spectrum); each lane sums its channels j = lane, lane +
+// 64, ... in order and wave_sum adds the lanes: one order whatever the launch.  (k = 1 for nu = 0 is exact: 1 tot = tot.)
+struct RobNu { double nu[MAXSPEC]; };
+__global__ void rob_setup_kernel(SpecDev S, long pix0, long n_pix, const double *__restrict__ w, RobNu nu_of, double *__restrict__ g,
+                                 double *__restrict__ gd, double *__restrict__ totsq, double *__restrict__ rob) {
+    const int lane = threadIdx.x & 63;
+    const long u = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (u >= n_pix * S.n_spec) return;
+    const long p = pix0 + u / S.n_spec;
+    const int s = (int)(u % S.n_spec);
+    const long k0 = p * S.chan_tot + S.off[s];
+    const double nu = nu_of.nu[s], sig = S.noise[p * S.n_spec + s];
+    const double ia = 1.0 / (nu * (sig * sig));                     // (nu = 0: unused)
+    double c = 0.0;
+    for (int j = lane; j < S.size[s]; j += 64) {
+        const double wj = w ? w[k0 + j] : 1.0, d = S.data[k0 + j];
+        if (nu == 0.0) { g[k0 + j] = wj; gd[k0 + j] = wj * d; continue; }
+        const double a = wj * ia, ad2 = a * d * d;
+        const double gj = a / (1.0 + ad2);
+        g[k0 + j] = gj;
+        gd[k0 + j] = gj * d;
+        c += log1p(ad2);
+    }
+    c = wave_sum(c);
+    if (lane == 0) {
+        const double k = nu == 0.0 ? 1.0 : (nu + 1.0) * (sig * sig);
+        rob[2 * (p * S.n_spec + s)] = nu;
+        rob[2 * (p * S.n_spec + s) + 1] = k;
+        if (nu != 0.0) totsq[p * S.n_spec + s] = k * c;
+    }
+}
+
+// null_lnZ of a robust set: the likelihood kernel's own value at p = 0, where tot = 0 and part = totsq, scaled as
+// lnl_sum_kernel scales it.  One lane per (pixel, spectrum).
+__global__ void null_lnz_rob_kernel(SpecDev S, long n_pix, double *__restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix * S.n_spec) return;
+    const double sigma = S.noise[i];
+    out[i] = -S.totsq[i] / (2 * (sigma * sigma));
 }
 
 // null_lnZ of a set with an uncertain noise level: every null_lnz_*_kernel leaves -h, and the term is nmarg_lnl's of h

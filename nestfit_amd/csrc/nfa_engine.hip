@@ -237,6 +237,10 @@ struct nfa_specset {
     // a continuum background (nfa_specset_set_continuum): SpecDev.cont and the caller's values [n_pix][n_spec]; empty without
     double *d_cont = nullptr;
     std::vector<double> h_cont;
+    // a robust likelihood (nfa_specset_set_robust): g and g d (SpecDev.chan_w and .wdata while it lasts; d_w and d_wdata keep
+    // the set's own), SpecDev.rob and the caller's degrees of freedom
+    double *d_rg = nullptr, *d_rgd = nullptr, *d_rob = nullptr;
+    double  h_rob[MAXSPEC] = {};
 };
 
 struct nfa_priors {
@@ -571,6 +575,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     d.cal2 = nullptr;                                                   // no calibration uncertainty (nfa_specset_set_calibration)
     d.tmpl = d.tp = nullptr;                                            // no nuisance templates (nfa_specset_set_templates)
     d.cont = nullptr;                                                   // no continuum background (nfa_specset_set_continuum)
+    d.rob = nullptr;                                                    // no robust likelihood (nfa_specset_set_robust)
     HIP_TRY(hipMalloc(&ss->d_lines, sizeof(LineRow) * n_spec));
     HIP_TRY(hipMemcpy(ss->d_lines, h_lines.data(), sizeof(LineRow) * n_spec, hipMemcpyHostToDevice));
     d.lines = ss->d_lines;
@@ -992,16 +997,20 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_tmpl); (void)hipFree(ss->d_tp);
     (void)hipFree(ss->d_nmarg);
     (void)hipFree(ss->d_cont);
+    (void)hipFree(ss->d_rg); (void)hipFree(ss->d_rgd); (void)hipFree(ss->d_rob);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
 }
+
+static int rob_form(nfa_specset *ss, int64_t pix0, int64_t n, const double *nu);
 
 int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data) {
     if (!ss || !data || pix < 0 || pix >= ss->n_pix) return fail(NFA_ERR_ARG, "bad pixel index");
     int rc = engine_init(); if (rc) return rc;
     HIP_TRY(hipMemcpy(ss->d_data + pix * ss->dev.chan_tot, data, sizeof(double) * ss->dev.chan_tot,
                       hipMemcpyHostToDevice));
+    if (ss->dev.rob) return rob_form(ss, pix, 1, ss->h_rob);                                     // the set's own w d and sums, then g, g d and C
     if (ss->dev.corr_q1) { rc = launch_corr_setup(ss, pix, 1, false); if (rc) return rc; }      // Q stays, Q d again
     else if (ss->dev.chan_w) { rc = launch_chan_weight(ss, pix, 1, false); if (rc) return rc; }      // the mask stays
     rc = launch_rowsq(ss, pix, 1); if (rc) return rc;
@@ -1071,11 +1080,17 @@ static int specset_form_records(nfa_specset *ss) {
     return NFA_OK;
 }
 
+// Under a Student-t likelihood (nfa_specset_set_robust) no linear nuisance has a closed form and a part is no
+// chi^2: such a set takes none of the other likelihoods, and none of theirs takes it.  The same words in either order.
+#define ROB_REFUSES(what) "a set with a robust likelihood takes no " what
+#define ROB_REFUSED(what) "a set with " what " takes no robust likelihood"
+
 int nfa_specset_set_baseline(nfa_specset *ss, int order) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
     if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
     if (order >= 0 && ss->dev.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no baseline");
     if (order >= 0 && ss->dev.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no baseline");
+    if (order >= 0 && ss->dev.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("baseline"));
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     const int was = ss->dev.bl_order;
@@ -1114,6 +1129,7 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
     if (any && d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no calibration uncertainty");
     if (any && d.nmarg) return fail(NFA_ERR_ARG, NMARG_CALIB_REFUSAL);
     if (any && d.cont) return fail(NFA_ERR_ARG, CONT_CALIB_REFUSAL);
+    if (any && d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("calibration uncertainty"));
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any) {                                               // null, or all zeros: the set's former kernels and bits
@@ -1174,6 +1190,7 @@ int nfa_specset_set_noise_uncertainty(nfa_specset *ss, const double *f) {
         any = any || f[s] > 0.0;
     }
     if (any && d.cal2) return fail(NFA_ERR_ARG, NMARG_CALIB_REFUSAL);
+    if (any && d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("noise uncertainty"));
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any) {                                               // null, or all zeros: the set's former arithmetic and bits
@@ -1331,6 +1348,7 @@ int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
         if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no noise correlation");
         if (d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no noise correlation");
         if (d.cont) return fail(NFA_ERR_ARG, CONT_CORR_REFUSAL);
+        if (d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("noise correlation"));
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1370,6 +1388,7 @@ int nfa_specset_set_response(nfa_specset *ss, const double *taps) {
         if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no channel response");
         if (d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no channel response");
         if (d.cont) return fail(NFA_ERR_ARG, CONT_RESP_REFUSAL);
+        if (d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("channel response"));
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1443,6 +1462,7 @@ int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmp
         if (d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no nuisance templates");
         if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no nuisance templates");
         if (d.cont) return fail(NFA_ERR_ARG, CONT_TMPL_REFUSAL);
+        if (d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("nuisance templates"));
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1502,6 +1522,7 @@ int nfa_specset_set_continuum(nfa_specset *ss, const double *tc) {
         if (d.corr_q1) return fail(NFA_ERR_ARG, CONT_CORR_REFUSAL);
         if (d.cal2) return fail(NFA_ERR_ARG, CONT_CALIB_REFUSAL);
         if (d.tmpl) return fail(NFA_ERR_ARG, CONT_TMPL_REFUSAL);
+        if (d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("continuum background"));
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1519,6 +1540,90 @@ int nfa_specset_set_continuum(nfa_specset *ss, const double *tc) {
 int nfa_specset_continuum(const nfa_specset *ss, double *out) {
     if (!ss || !ss->dev.cont) return 0;
     if (out) memcpy(out, ss->h_cont.data(), sizeof(double) * ss->h_cont.size());
+    return 1;
+}
+
+// The set's own state of pixels [pix0, pix0 + n) behind chan_w and wdata: its weights and w d (a scalar noise: none), the
+// sums of w d^2 -- bit for bit what the set was created with
+static int rob_base(nfa_specset *ss, int64_t pix0, int64_t n) {
+    SpecDev &d = ss->dev;
+    d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
+    if (ss->d_w) { int rc = launch_chan_weight(ss, pix0, n, false); if (rc) return rc; }
+    return launch_rowsq(ss, pix0, n);
+}
+
+// ... and over it g, g d, totsq = k C and the records of a robust likelihood with nu[n_spec] (rob_setup_kernel): the spectra
+// with nu = 0 keep the sums rob_base left
+static int rob_form(nfa_specset *ss, int64_t pix0, int64_t n, const double *nu) {
+    SpecDev &d = ss->dev;
+    d.rob = nullptr;
+    int rc = rob_base(ss, pix0, n); if (rc) return rc;
+    RobNu nu_of = {};
+    for (int s = 0; s < d.n_spec; ++s) nu_of.nu[s] = nu[s];
+    d.chan_w = ss->d_rg; d.wdata = ss->d_rgd;
+    hipLaunchKernelGGL(rob_setup_kernel, dim3((unsigned)((n * d.n_spec * 64 + 255) / 256)), dim3(256), 0, 0, d, (long)pix0, (long)n,
+                       (const double *)ss->d_w, nu_of, ss->d_rg, ss->d_rgd, ss->d_totsq, ss->d_rob);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    d.rob = ss->d_rob;
+    return NFA_OK;
+}
+
+// The device's state for the degrees of freedom nu[n_spec], valid and not all zero; null: no robust likelihood, the set's
+// former kernels and bits
+static int rob_apply(nfa_specset *ss, const double *nu) {
+    SpecDev &d = ss->dev;
+    if (!nu) {
+        (void)hipFree(ss->d_rg); (void)hipFree(ss->d_rgd); (void)hipFree(ss->d_rob);
+        ss->d_rg = ss->d_rgd = ss->d_rob = nullptr; d.rob = nullptr;
+        memset(ss->h_rob, 0, sizeof ss->h_rob);
+        return rob_base(ss, 0, ss->n_pix);
+    }
+    const size_t n = (size_t)(ss->n_pix * d.chan_tot);
+    if (!ss->d_rg) HIP_TRY(hipMalloc(&ss->d_rg, sizeof(double) * n));
+    if (!ss->d_rgd) HIP_TRY(hipMalloc(&ss->d_rgd, sizeof(double) * n));
+    if (!ss->d_rob) HIP_TRY(hipMalloc(&ss->d_rob, sizeof(double) * 2 * ss->n_pix * d.n_spec));
+    int rc = rob_form(ss, 0, ss->n_pix, nu); if (rc) return rc;
+    if (nu != ss->h_rob) { memset(ss->h_rob, 0, sizeof ss->h_rob); memcpy(ss->h_rob, nu, sizeof(double) * d.n_spec); }
+    return NFA_OK;
+}
+
+int nfa_specset_set_robust(nfa_specset *ss, const double *nu) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    SpecDev &d = ss->dev;
+    bool any = false;
+    for (int s = 0; nu && s < d.n_spec; ++s) {
+        if (!(nu[s] == 0.0 || (nu[s] >= 1.0 && nu[s] <= 1e6)))   // (NaN fails all)
+            return fail(NFA_ERR_ARG, "a robust likelihood takes finite degrees of freedom per spectrum, 0 (Gaussian) or in [1, 1e6]");
+        any = any || nu[s] > 0.0;
+    }
+    if (any) {
+        if (d.bl_order >= 0) return fail(NFA_ERR_ARG, ROB_REFUSED("a baseline"));
+        if (d.tmpl) return fail(NFA_ERR_ARG, ROB_REFUSED("nuisance templates"));
+        if (d.cal2) return fail(NFA_ERR_ARG, ROB_REFUSED("a calibration uncertainty"));
+        if (d.resp) return fail(NFA_ERR_ARG, ROB_REFUSED("a channel response"));
+        if (d.corr_q1) return fail(NFA_ERR_ARG, ROB_REFUSED("correlated channel noise"));
+        if (d.nmarg) return fail(NFA_ERR_ARG, ROB_REFUSED("a noise uncertainty"));
+        if (d.cont) return fail(NFA_ERR_ARG, ROB_REFUSED("a continuum background"));
+    }
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    if (!any && !d.rob) return NFA_OK;                        // null, or all zeros, and none before: nothing changes
+    const bool had = d.rob != nullptr;
+    double was[MAXSPEC];
+    memcpy(was, ss->h_rob, sizeof was);
+    rc = rob_apply(ss, any ? nu : nullptr);
+    if (rc) {                                                 // the set stays as it was: its former degrees of freedom, or none
+        const std::string why = g_err;
+        (void)rob_apply(ss, had ? was : nullptr);
+        g_err = why;
+    }
+    return rc;
+}
+
+int nfa_specset_robust(const nfa_specset *ss, double *out) {
+    if (!ss || !ss->dev.rob) return 0;
+    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->h_rob[s];
     return 1;
 }
 
@@ -1541,7 +1646,9 @@ int nfa_specset_null_lnz(const nfa_specset *ss, double *out) {
     const int64_t n = ss->n_pix * ss->dev.n_spec;
     double *d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(double) * n));
-    if (ss->dev.tmpl)                                         // the model of baseline and templates alone
+    if (ss->dev.rob)                                          // the likelihood kernel's own value at p = 0
+        hipLaunchKernelGGL(null_lnz_rob_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
+    else if (ss->dev.tmpl)                                    // the model of baseline and templates alone
         hipLaunchKernelGGL(null_lnz_tmpl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
     else if (ss->dev.bl_order >= 0)                           // the baseline-only model (a calibrated set's zeroed record is no baseline)
         hipLaunchKernelGGL(null_lnz_bl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
@@ -2004,6 +2111,21 @@ static LnlKernel lnl_kernel_cont_of(int mode, bool write_spec, const LnlPlan &P)
     return lnl_kernel_cont_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
                               std::make_index_sequence<32>());
 }
+// ... and of a set with a robust likelihood: lnl_kernel_robust over the same five, with the weighted form's plan
+template <int I>
+static LnlKernel lnl_kernel_robust_inst() {
+    return lnl_kernel_robust<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
+}
+template <size_t... I>
+static LnlKernel lnl_kernel_robust_at(int i, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])() = {lnl_kernel_robust_inst<(int)I>...};
+    return inst[i]();
+}
+static LnlKernel lnl_kernel_robust_of(int mode, bool write_spec, const LnlPlan &P) {
+    if (P.form != LNL_WEIGHTED) return nullptr;
+    return lnl_kernel_robust_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
+                                std::make_index_sequence<32>());
+}
 #ifdef NFA_TEST_HOOKS
 #include <atomic>
 // Likelihood launches by (lnl_inst_index, LnlForm) since the last reset (nfa_test_lnl_launches): host side, counted where
@@ -2035,7 +2157,8 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = S.cont ? lnl_kernel_cont_of(mode, d_spec != nullptr, P)
+    const LnlKernel kern = S.rob ? lnl_kernel_robust_of(mode, d_spec != nullptr, P)
+                         : S.cont ? lnl_kernel_cont_of(mode, d_spec != nullptr, P)
                          : S.tmpl ? lnl_kernel_tmpl_of(mode, d_spec != nullptr, P)
                          : S.resp ? lnl_kernel_resp_of(mode, d_spec != nullptr, P)
                          : S.corr_q1 ? lnl_kernel_corr_of(mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
@@ -2254,7 +2377,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
     const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
-                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr);
+                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

@@ -363,12 +363,15 @@ struct FusedPlan { const char *refusal, *ring_error; LnlGeom G; int n_blocks, ct
 // and the reason must be its own)
 // continuum: a set with a continuum background (nfa_specset_set_continuum: the batch kernels only -- such a set is weighted and
 // runs the baseline form, and the reason must be its own)
+// robust: a set with a robust likelihood (nfa_specset_set_robust: the batch kernels only, and refused first of all -- such a
+// set is weighted to its kernels, whose weighted sum would be no likelihood of it)
 inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted, bool banded = false,
                             bool filled = false, bool layered = false, bool calibrated = false, bool correlated = false,
-                            bool response = false, bool templates = false, bool continuum = false) {
+                            bool response = false, bool templates = false, bool continuum = false, bool robust = false) {
     FusedPlan P = {};
     P.G = lnl_geom(s, k, 1);
-    if (response) P.refusal = "the resident kernel has no form for a channel response: use nfa_ring_serve";
+    if (robust) P.refusal = "the resident kernel has no form for a robust likelihood: use nfa_ring_serve";
+    else if (response) P.refusal = "the resident kernel has no form for a channel response: use nfa_ring_serve";
     else if (correlated) P.refusal = "the resident kernel has no form for correlated channel noise: use nfa_ring_serve";
     else if (calibrated) P.refusal = "the resident kernel has no form for a calibration uncertainty: use nfa_ring_serve";
     else if (layered) P.refusal = "the resident kernel has no form for layered transfer: use nfa_ring_serve";

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_response, check_templates, gain_fit, half_chi2, noise_fit, nuisance_fit, signed_peak
+from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_response, check_robust, check_templates, gain_fit, half_chi2, noise_fit, nuisance_fit, robust_outliers, signed_peak
 from .core import _as_inplace_matrix
 
 
@@ -59,6 +59,9 @@ class CubeRunner:
         spectrum's channels (`ripple(n_chan, period)`: a standing wave of known period; shared by all pixels) whose amplitudes
         are profiled out of the likelihood per (pixel, spectrum) together with the baseline; not with a
         calibration, a correlation or a response; null_lnZ is then the model of baseline and templates alone
+    robust : None, or the degrees of freedom of Student-t channel noise (a number, or one per spectrum, each 0 -- Gaussian -- or
+        in [1, 1e6]; shared by all pixels): spikes and unflagged bad channels cost the logarithm of their residual (DESIGN
+        4.18); with none of the other likelihood options; null_lnZ is the same expression at p = 0
     noise_uncertainty : None, or the fractional 1-sigma uncertainty of the spectra's noise levels (a number, or one per
         spectrum, each in [0, 0.5]; shared by all pixels), integrated out of the likelihood per (pixel, spectrum) in closed
         form; with everything but a calibration; null_lnZ is the same function of the parts at p = 0
@@ -70,7 +73,7 @@ class CubeRunner:
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
                  model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False,
-                 calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None, continuum=None):
+                 calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None, continuum=None, robust=None):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
@@ -88,6 +91,8 @@ class CubeRunner:
         response = check_response(response, len(xarrs), sizes, masked, baseline_order, calibration)
         templates = check_templates(templates, len(xarrs), sizes, calibration, correlation, response)
         continuum = check_continuum(continuum, len(xarrs), int(np.shape(data)[0]), model, calibration, correlation, response, templates)
+        robust = check_robust(robust, len(xarrs), baseline_order, calibration, correlation, response, templates, noise_uncertainty,
+                              continuum)
         if species is None and int(model) == 4 and lines is not None:
             from .lte import LteBand, LteBlend, LteLines, lines_species
             lines = list(lines)
@@ -116,6 +121,8 @@ class CubeRunner:
             self._ss.set_noise_uncertainty(noise_uncertainty)
         if continuum is not None:
             self._ss.set_continuum(continuum)
+        if robust is not None:
+            self._ss.set_robust(robust)
         self._data, self._noise = data, noise                # (fit_baseline, fit_gain, fit_noise)
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -283,6 +290,37 @@ class CubeRunner:
                 sigma = 1.0 if self._ss.per_channel else noise[b, k]
                 mean[b, k], std[b, k] = gain_fit(data[b, sl], spec[b, sl], w, sigma, cal[k], self.baseline_order)
         return mean, std
+
+    @property
+    def robust(self):
+        """None, or the float64 array [n_spec] of the degrees of freedom of the spectra's Student-t channel noise."""
+        nu = self._ss.robust
+        return None if nu is None else nu.copy()
+
+    def set_robust(self, nu):
+        """Sets (a number, or one per spectrum) or removes (None, zeros) the robust likelihood; null_lnZ
+        follows."""
+        self._ss.set_robust(nu)
+        self.null_lnZ = self._ss.null_lnZ().sum(axis=1)
+
+    def fit_outliers(self, pix, theta):
+        """Every channel's posterior mean precision factor (nu + 1) / (nu + r_j^2 / sigma_j^2), [B, chan_tot], at physical
+        parameter rows theta[B, ndim] against pixels pix[B]: about 1 for a good channel, towards 0 for one the fit distrusted
+        (1 in a spectrum with nu = 0, NaN at a masked channel).  numpy on `predict_batch`'s spectra (`robust_outliers`).
+        ValueError without a robust likelihood."""
+        nu = self.robust
+        if nu is None:
+            raise ValueError('this runner has no robust likelihood (robust=None)')
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        spec, _ = self.predict_batch(pix, theta)
+        data = np.asarray(self._data, dtype=np.float64)[pix]
+        noise = np.asarray(self._noise, dtype=np.float64)[pix]
+        off = self._ss.offsets
+        out = np.empty_like(spec)
+        for k in range(self.n_spec):
+            sl = slice(off[k], off[k + 1])
+            out[:, sl] = robust_outliers(data[:, sl], spec[:, sl], noise[:, sl] if self._ss.per_channel else noise[:, k:k + 1], nu[k])
+        return out
 
     @property
     def continuum(self):

@@ -340,6 +340,37 @@ def estimate_noise(cube, line_free, correlation=None):
     return rms, float(1.0 / np.sqrt(2.0 * n_eff))
 
 
+def estimate_tails(cube, line_free):
+    """The degrees of freedom nu of Student-t channel noise from the pooled excess kurtosis of the channels without line
+    emission -- what `robust=` of a runner takes -- or None where the noise shows no heavy tails.  cube and
+    line_free as for `estimate_correlation`.  Per pixel the mean of its line-free channels is taken off and they are divided by
+    their rms; kappa = m_4 / m_2^2 - 3 over all of them (n values); pixels with a NaN in a line-free channel are left out.  A
+    Student-t with nu > 4 has kappa = 6 / (nu - 4), so nu = 4 + 6 / kappa, clipped into [1, 1e6] (a sample's kappa is
+    finite even where the distribution's is not: nu then comes out a little above 4).  "Significantly above 0" is kappa > 3
+    sqrt(24 / n), three standard deviations of the sample excess kurtosis of n Gaussian values; below that: None.  numpy on
+    the host."""
+    data = np.asarray(getattr(cube, 'data', cube), dtype=np.float64)
+    n = data.shape[-1]
+    keep = np.zeros(n, dtype=bool)
+    keep[line_free] = True
+    if keep.sum() < 8:
+        raise ValueError('estimate_tails needs 8 line-free channels and more')
+    x = data.reshape(-1, n)[:, keep]
+    x = x[np.all(np.isfinite(x), axis=1)]
+    if x.shape[0] == 0:
+        raise ValueError('estimate_tails: no pixel without a NaN in its line-free channels')
+    x = x - x.mean(axis=1, keepdims=True)
+    rms = np.sqrt(np.mean(x * x, axis=1, keepdims=True))
+    x = (x / np.where(rms > 0.0, rms, 1.0)).ravel()
+    m2 = np.mean(x * x)
+    if not m2 > 0.0:
+        return None
+    kappa = float(np.mean(x ** 4) / (m2 * m2) - 3.0)
+    if not kappa > 3.0 * np.sqrt(24.0 / x.size):
+        return None
+    return float(np.clip(4.0 + 6.0 / kappa, 1.0, 1e6))
+
+
 # celestial keywords a two-dimensional map product inherits from the cube
 _MAP_KEYWORDS = ('SIMPLE', 'BITPIX', 'NAXIS', 'NAXIS1', 'NAXIS2', 'WCSAXES') + tuple(
     f'{stem}{axis}' for stem in ('CRPIX', 'CDELT', 'CUNIT', 'CTYPE', 'CRVAL') for axis in (1, 2)) + ('RADESYS', 'EQUINOX')

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import sampler
-from ._model import check_calibration, check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_response, check_templates
+from ._model import check_calibration, check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_response, check_robust, check_templates
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
@@ -98,6 +98,11 @@ class CubeFitter:
         self.continuum = getattr(stack, 'continuum_maps', lambda: None)()
         if self.continuum is not None and np.any(np.nan_to_num(self.continuum) > 0.0):
             check_continuum(1.0, None, None, self.model_id, self.calibration, self.correlation, self.response, self.templates)
+        # a robust likelihood (runner_kwargs['robust']): and this, with everything it does not go with
+        self.robust = check_robust(self.runner_kwargs.get('robust'), None if cubes is None else len(cubes),
+                                   self.runner_kwargs.get('baseline_order'), self.calibration, self.correlation, self.response,
+                                   self.templates, self.noise_uncertainty,
+                                   None if self.continuum is None else np.nan_to_num(self.continuum))
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
         self.lnZ_thresh, self.ncomp_max, self.nlive_snr_fact = lnZ_thresh, ncomp_max, nlive_snr_fact
         self.nlive_quantum = max(1, int(nlive_quantum))

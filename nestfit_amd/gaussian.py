@@ -7,7 +7,7 @@ radiative-transfer pass.
 import numpy as np
 
 from . import core
-from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_continuum, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
+from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_continuum, check_robust, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
 
 N_PARAMS = 3
 
@@ -34,14 +34,14 @@ class GaussianRunner(EngineRunner):
     N_MODEL = N_PARAMS
 
     def __init__(self, spectrum, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None):
+                 noise_uncertainty=None, continuum=None, robust=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         check_layered(layered, MODEL_GAUSSIAN)                        # ValueError for True: no optical depth, nothing absorbs
         self.spectrum = spectrum
         self._setup([spectrum], utrans, ncomp, rest_freqs=[float(spectrum.rest_freq)], baseline_order=baseline_order,
                     calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum)
+                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -49,6 +49,8 @@ class GaussianRunner(EngineRunner):
         check_layered(kwargs.get('layered', False), MODEL_GAUSSIAN)
         check_calibration(kwargs.get('calibration'), 1)
         check_noise_uncertainty(kwargs.get('noise_uncertainty'), 1, kwargs.get('calibration'))
+        check_robust(kwargs.get('robust'), 1, kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
+                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
         check_continuum(kwargs.get('continuum'), 1, None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
                         kwargs.get('response'), kwargs.get('templates'))
         check_correlation(kwargs.get('correlation'), 1, *spec_data_sizes_masked([spec_data]),

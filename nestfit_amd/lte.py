@@ -47,7 +47,7 @@ function come from a catalogue of the user's.
 """
 import numpy as np
 
-from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_continuum, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
+from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_continuum, check_robust, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
 from .core import HyperfineSpectrum as _HyperfineBase
 from .hyperfine import CKMS, MAX_LINES, LineTable
 
@@ -406,7 +406,7 @@ class LteRunner(EngineRunner):
     N_MODEL = N_PARAMS
 
     def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None):
+                 noise_uncertainty=None, continuum=None, robust=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
@@ -414,7 +414,7 @@ class LteRunner(EngineRunner):
         self.molecule = check_one_molecule([s.lines for s in self.spectra])
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
                     calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum)
+                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -423,6 +423,8 @@ class LteRunner(EngineRunner):
         check_layered(kwargs.get('layered', False))
         check_calibration(kwargs.get('calibration'), len(spec_data))
         check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
+        check_robust(kwargs.get('robust'), len(spec_data), kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
+                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
         check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
                         kwargs.get('response'), kwargs.get('templates'))
         check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
@@ -554,7 +556,7 @@ class _MixRunner(EngineRunner):
     MIX = None
 
     def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None):
+                 noise_uncertainty=None, continuum=None, robust=None):
         assert ncomp > 0
         baseline_order = check_baseline_order(baseline_order)
         layered = check_layered(layered)
@@ -563,7 +565,7 @@ class _MixRunner(EngineRunner):
         self.species = self.MIX.species
         self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
                     calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum)
+                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
@@ -572,6 +574,8 @@ class _MixRunner(EngineRunner):
         check_layered(kwargs.get('layered', False))
         check_calibration(kwargs.get('calibration'), len(spec_data))
         check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
+        check_robust(kwargs.get('robust'), len(spec_data), kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
+                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
         check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
                         kwargs.get('response'), kwargs.get('templates'))
         check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),

@@ -24,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import hdf5
-from ._model import check_calibration, check_correlation, check_noise_uncertainty, check_response, check_templates
+from ._model import check_calibration, check_correlation, check_noise_uncertainty, check_response, check_robust, check_templates
 
 HDF5_SUFFIXES = ('.hdf', '.h5', '.hdf5')
 
@@ -462,6 +462,11 @@ class HdfStore:
                                        None if cubes is None else len(cubes))
         if nunc is not None:
             self.hdf.attrs['noise_uncertainty'] = nunc
+        # a robust likelihood (runner_kwargs['robust']): root attribute `robust_dof`, float64 [n_spec], the degrees
+        # of freedom of the Student-t channel noise.  A store without it was fitted with Gaussian noise.
+        rob = check_robust((getattr(fitter, 'runner_kwargs', None) or {}).get('robust'), None if cubes is None else len(cubes))
+        if rob is not None:
+            self.hdf.attrs['robust_dof'] = rob
         # a continuum background behind the components (DataCube(..., continuum=)): root dataset
         # `model_continuum`, float64 (t, b, l) like the per-spectrum map products, in K, NaN where a map has none.  A store
         # without it was fitted against the cosmic background alone.
@@ -527,6 +532,14 @@ class HdfStore:
         assert self.is_open
         nunc = self.hdf.attrs.get('noise_uncertainty')
         return None if nunc is None else np.asarray(nunc, dtype=np.float64)
+
+    def read_model_robust(self):
+        """The degrees of freedom of the Student-t channel noise of every spectrum the store was fitted with
+        (`runner_kwargs={'robust': ...}`): the root attribute `robust_dof` as a float64 array [n_spec]; None for a store
+        without it."""
+        assert self.is_open
+        rob = self.hdf.attrs.get('robust_dof')
+        return None if rob is None else np.asarray(rob, dtype=np.float64)
 
     def read_model_continuum(self):
         """The continuum maps the store was fitted with (`DataCube(..., continuum=)`): the root dataset `model_continuum` as a
