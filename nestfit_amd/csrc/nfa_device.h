@@ -145,19 +145,19 @@ struct SpecDev {
     // matrix R has a pentadiagonal inverse.  With u = sigma_ref / sigma_c, Q = diag(u) R^-1 diag(u) and chi^2 = (d - p)^T Q (d - p):
     // chan_w then holds Q's diagonal and wdata = Q d (the set's own u^2 stay in its buffer behind them), corr_q1[j] = Q[j][j+1] and
     // corr_q2[j] = Q[j][j+2], 0 beyond the spectrum's end, [n_pix][chan_tot] like `data`; corr_coef [n_spec][NFA_CORR_NC], the
-    // entries of R^-1 (corr_setup_kernel).  Such a set runs lnl_kernel_corr.
+    // entries of R^-1 (corr_setup_kernel).  Such a set runs lnl_kernel_side<..., LNL_SIDE_CORR>.
     const double  *corr_q1, *corr_q2, *corr_coef;
     // Spectra sets with a channel response (nfa_specset_set_response; null without): [n_spec][NFA_RESP_NT], the
     // taps h_-2 .. h_2 of every spectrum (three taps: zero ends; an unfiltered spectrum beside filtered ones: 0, 0, 1, 0, 0).
     // The model that meets the data is p~_j = sum_k h_k p_{j+k}, p = 0 beyond the spectrum's ends.  Such a set always has
     // chan_w, wdata, corr_q1, corr_q2 and corr_coef (the white entries 1, 1, 1, 0, 0, 0 without a correlation) and runs
-    // lnl_kernel_resp.
+    // lnl_kernel_side<..., LNL_SIDE_RESP>.
     const double  *resp;
     // Spectra sets with nuisance templates (nfa_specset_set_templates; null without): tmpl
     // [NFA_TMPL_MAX][chan_tot], slot k of every spectrum scaled to max |t| = 1, zeros where a spectrum leaves the slot
     // unused, shared by all pixels; tp [n_pix][n_spec][NFA_TP_REC], the records of tmpl_setup_kernel (below).  Such a set
     // always has chan_w and wdata (a scalar noise: chan_w == 1), keeps bl and bl_order for nfa_specset_set_baseline's sake
-    // and runs lnl_kernel_tmpl, which reads tp alone.
+    // and runs lnl_kernel_side<..., LNL_SIDE_TMPL>, which reads tp alone.
     const double  *tmpl, *tp;
     // Spectra sets with an uncertain noise level per spectrum (nfa_specset_set_noise_uncertainty; null without):
     // [n_pix][n_spec][2], a = 1 / (4 f^2) of the spectrum's fractional uncertainty f (0: the spectrum's noise is exact) and
@@ -167,14 +167,14 @@ struct SpecDev {
     // Spectra sets with a continuum background behind the components (nfa_specset_set_continuum; null without):
     // [n_pix][n_spec], Tc >= 0 in K of every (pixel, spectrum) -- data of the continuum map that was subtracted, no parameter.
     // Every component's T0 (y - tbg) becomes T0 (y - tbg) - Tc.  Such a set always has chan_w, wdata and bl (a scalar noise:
-    // chan_w == 1; a zeroed record, bl_order -1, without a baseline) and runs lnl_kernel_cont.
+    // chan_w == 1; a zeroed record, bl_order -1, without a baseline) and runs lnl_kernel_side<..., LNL_SIDE_CONT>.
     const double  *cont;
     // Spectra sets with a robust likelihood (nfa_specset_set_robust; null without): [n_pix][n_spec][2], {nu, k}:
     // the degrees of freedom of the spectrum's Student-t channel noise (0: the spectrum stays Gaussian) and k = (nu + 1)
     // sigma_ref^2 (1 for nu = 0).  While it lasts chan_w holds g = a / (1 + a d^2), a = w / (nu sigma_ref^2), and wdata g d
     // (rob_setup_kernel; the set's own weights stay in its buffer behind them; a Gaussian spectrum: w and w d), and totsq
     // k sum log1p(a d^2): part = totsq + k sum log1p(p (g p - 2 g d)) makes -part / (2 sigma_ref^2) the likelihood.  Such a
-    // set runs lnl_kernel_robust.
+    // set runs lnl_kernel_side<..., LNL_SIDE_ROBUST>.
     const double  *rob;
 };
 // entries of R^-1 of a spectrum: its diagonal at channels 0 and N-1, 1 and N-2, and between; its first off-diagonal at
@@ -986,13 +986,17 @@ __device__ __forceinline__ double one_minus_fastexp_table_row(double tau) {
 // (1 + t)), and the fp64 one cost the fast mode 1.57 against the general weighted form at two components where this costs
 // 1.31.  A spectrum with nu = 0 beside robust ones takes the weighted form's own fma (a
 // branch uniform over the unit).  The epilogue is totsq + k tot, k of SpecDev.rob.  No LDS, no barrier.
-template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, bool WEIGHTED = false, bool BASELINE = false, bool FILL = false,
-          bool LAYER = false, bool CALIB = false, bool CORR = false, bool RESP = false, bool TMPL = false, bool CONT = false, bool ROBUST = false>
+// FLAGS: the word of those flags (LNL_K_*, LNL_F_*, nfa_launch_plan.h); 0 is the plain, unweighted set.
+template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP, bool DYN = false, unsigned FLAGS = 0>
 __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict__ pix, const double *__restrict__ D,
                                          double *__restrict__ part, double *__restrict__ spec_out, long B,
                                          const LnlGeom &G, const double *__restrict__ g_tabs, double *smem,
                                          const double *sm, int n_shared, unsigned block_id,
                                          const BatchGroup *grp = nullptr, long unit_dyn = -1) {
+    constexpr bool WEIGHTED = (FLAGS & LNL_K_WEIGHTED) != 0, BASELINE = (FLAGS & LNL_K_BASELINE) != 0, FILL = (FLAGS & LNL_K_FILL) != 0;
+    constexpr bool LAYER = (FLAGS & LNL_K_LAYER) != 0, CALIB = (FLAGS & LNL_K_CALIB) != 0, CORR = (FLAGS & LNL_F_CORR) != 0;
+    constexpr bool RESP = (FLAGS & LNL_F_RESP) != 0, TMPL = (FLAGS & LNL_F_TMPL) != 0, CONT = (FLAGS & LNL_F_CONT) != 0;
+    constexpr bool ROBUST = (FLAGS & LNL_F_ROBUST) != 0;
     typedef typename std::conditional<MODE == 2, float, double>::type tau_t;
     constexpr int NC = NCOMP > 0 ? NCOMP : 1;
     // the fast mode's narrow form: at most 26 lines per transition (32-bit line masks), fp32 optical depth, the
@@ -1669,87 +1673,31 @@ lnl_kernel_kind(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
     int n_shared = 0;
     const double *sm = smem;
     if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP, false, (KIND & LNL_K_WEIGHTED) != 0, (KIND & LNL_K_BASELINE) != 0, (KIND & LNL_K_FILL) != 0,
-             (KIND & LNL_K_LAYER) != 0, (KIND & LNL_K_CALIB) != 0>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+    lnl_body<MODE, WRITE_SPEC, WIDE, NCOMP, false, KIND>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
-// The kernels of a set with CORRELATED channel noise (nfa_specset_set_correlation): the weighted form in the
-// general component form with lnl_body's CORR flag, 32 instances over (MODE, WRITE_SPEC, WIDE, FILL, LAYER) beside the table
-// of kinds (which stays at its 32 kinds).  launch_lnl takes them for such a set with the weighted form's plan: the same waves,
-// LDS and workgroups.  No unrolled component loop, no queue, no w8, no fused form.
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
+// The side family, beside the table of kinds (which stays at its 32 kinds): the kernels of a set that is one of LnlSide
+// (nfa_launch_plan.h), in the general component form, 32 instances per side over (MODE, WRITE_SPEC, WIDE, FILL, LAYER).
+// lnl_side_flags says which of lnl_body's flags a side switches on, lnl_side_form whose plan launch_lnl gives its kernels:
+//   corr    correlated channel noise (nfa_specset_set_correlation): the weighted form with CORR
+//   resp    a channel response (nfa_specset_set_response, 4.14): corr's with RESP; without a correlation, over white coefficients
+//   tmpl    nuisance templates (nfa_specset_set_templates, 4.15): the baseline form with TMPL, its plan over nine sums per part
+//           (plan_lnl's `templates`); one instance for every baseline order and every number of templates
+//   cont    a continuum background (nfa_specset_set_continuum, 4.17): the baseline form with CONT; one instance for every
+//           baseline order (none: a zeroed record) and every Tc, a spectrum with Tc = 0 beside one with a continuum included
+//   robust  a robust likelihood (nfa_specset_set_robust, 4.18): the weighted form with ROBUST; one instance for every nu, a
+//           Gaussian spectrum (nu = 0) beside robust ones included
+// The same waves, LDS and workgroups as that form's kernels.  No unrolled component loop, no queue, no w8, no fused form.
+template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER, int SIDE>      // SIDE: an LnlSide, as the number a profile shows
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_corr(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
+lnl_kernel_side(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
                 double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     int n_shared = 0;
     const double *sm = smem;
     if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, FILL, LAYER, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared,
-                                                                                     blockIdx.x, &grp);
-}
-
-// The kernels of a set with a CHANNEL RESPONSE (nfa_specset_set_response): lnl_kernel_corr's form with lnl_body's
-// RESP flag, 32 more instances over the same five flags, beside the table like those.  launch_lnl takes them when SpecDev.resp
-// is set, with the weighted form's plan.  A response without a correlation runs them over white coefficients.
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_resp(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, FILL, LAYER, false, true, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm,
-                                                                                           n_shared, blockIdx.x, &grp);
-}
-
-// The kernels of a set with NUISANCE TEMPLATES (nfa_specset_set_templates): the baseline form in the general
-// component form with lnl_body's TMPL flag, 32 instances over the same five flags, beside the table like lnl_kernel_corr.
-// launch_lnl takes them when SpecDev.tmpl is set, with the baseline form's plan over nine sums per part (plan_lnl's
-// `templates`).  One instance serves every baseline order and every number of templates.
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_tmpl(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, LAYER, false, false, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs, smem,
-                                                                                                  sm, n_shared, blockIdx.x, &grp);
-}
-
-// The kernels of a set with a CONTINUUM BACKGROUND (nfa_specset_set_continuum): the baseline form in the general
-// component form with lnl_body's CONT flag, 32 instances over the same five flags, beside the table like lnl_kernel_corr.
-// launch_lnl takes them when SpecDev.cont is set, with the baseline form's plan.  One instance serves every baseline order
-// (none: a zeroed record) and every Tc, a spectrum with Tc = 0 beside one with a continuum included.
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_cont(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, true, FILL, LAYER, false, false, false, false, true>(S, nullptr, D, part, spec_out, B, G, g_tabs,
-                                                                                                         smem, sm, n_shared, blockIdx.x, &grp);
-}
-
-// The kernels of a set with a ROBUST LIKELIHOOD (nfa_specset_set_robust): the weighted form in the general
-// component form with lnl_body's ROBUST flag, 32 instances over the same five flags, beside the table like lnl_kernel_corr.
-// launch_lnl takes them when SpecDev.rob is set, with the weighted form's plan.  One instance serves every nu, a Gaussian
-// spectrum (nu = 0) beside robust ones included.
-template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
-lnl_kernel_robust(SpecDev S, BatchGroup grp, const double *__restrict__ D, double *__restrict__ part,
-                  double *__restrict__ spec_out, long B, LnlGeom G, const double *__restrict__ g_tabs) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    int n_shared = 0;
-    const double *sm = smem;
-    if (MODE != 2) sm = stage_exp_tables<MODE == 2 ? 1 : MODE>(smem, g_tabs, &n_shared);
-    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, true, false, FILL, LAYER, false, false, false, false, false, true>(S, nullptr, D, part, spec_out, B, G,
-                                                                                                                g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
+    lnl_body<MODE, WRITE_SPEC, WIDE, 0, false, lnl_side_flags((LnlSide)SIDE) | (FILL ? LNL_K_FILL : 0u) | (LAYER ? LNL_K_LAYER : 0u)>(
+        S, nullptr, D, part, spec_out, B, G, g_tabs, smem, sm, n_shared, blockIdx.x, &grp);
 }
 
 // Table mode, one wave per unit, the units drawn from a queue.  A workgroup of the table mode is sixteen waves behind one
@@ -2329,7 +2277,7 @@ __global__ void __launch_bounds__(256) tmpl_setup_kernel(SpecDev S, long pix0, l
     for (int k = NFA_TP_NB + NFA_TP_NB * (NFA_TP_NB + 1) / 2; k < NFA_TP_REC; ++k) R[k] = 0.0;
 }
 
-// null_lnZ of a set with templates: -(totsq - ||L^-1 m(d)||^2) / (2 sigma_ref^2), lnl_kernel_tmpl's own value at p = 0
+// null_lnZ of a set with templates: -(totsq - ||L^-1 m(d)||^2) / (2 sigma_ref^2), lnl_kernel_side<..., LNL_SIDE_TMPL>'s own value at p = 0
 // (tot = 0 and m(p) = 0 there).  One lane per (pixel, spectrum).
 __global__ void null_lnz_tmpl_kernel(SpecDev S, long n_pix, double *__restrict__ out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -26,6 +26,7 @@
 #include "nh3_data.h"
 #include "n2hp_data.h"
 #include "nfa_device.h"
+#include "nfa_set_rules.h"
 
 // ---------------------------------------------------------------------------
 //  error plumbing
@@ -1080,17 +1081,19 @@ static int specset_form_records(nfa_specset *ss) {
     return NFA_OK;
 }
 
-// Under a Student-t likelihood (nfa_specset_set_robust) no linear nuisance has a closed form and a part is no
-// chi^2: such a set takes none of the other likelihoods, and none of theirs takes it.  The same words in either order.
-#define ROB_REFUSES(what) "a set with a robust likelihood takes no " what
-#define ROB_REFUSED(what) "a set with " what " takes no robust likelihood"
+// What the set has, as set_refusal (nfa_set_rules.h) asks: which of the likelihoods a setter may not put beside its own.
+// ("correlated" is the coefficients of the correlated kernels, which a response over white noise has too.)
+static unsigned specset_has(const nfa_specset *ss) {
+    const SpecDev &d = ss->dev;
+    return (ss->masked ? SET_HAS_MASK : 0u) | (d.bl_order >= 0 ? SET_HAS_BASELINE : 0u) | (d.cal2 ? SET_HAS_CALIB : 0u) |
+           (d.nmarg ? SET_HAS_NMARG : 0u) | (d.corr_q1 ? SET_HAS_CORR : 0u) | (d.resp ? SET_HAS_RESP : 0u) | (d.tmpl ? SET_HAS_TMPL : 0u) |
+           (d.cont ? SET_HAS_CONT : 0u) | (d.rob ? SET_HAS_ROBUST : 0u);
+}
 
 int nfa_specset_set_baseline(nfa_specset *ss, int order) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
     if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
-    if (order >= 0 && ss->dev.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no baseline");
-    if (order >= 0 && ss->dev.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no baseline");
-    if (order >= 0 && ss->dev.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("baseline"));
+    if (const char *why = order >= 0 ? set_refusal(specset_has(ss), SET_TAKES_BASELINE) : nullptr) return fail(NFA_ERR_ARG, why);
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     const int was = ss->dev.bl_order;
@@ -1105,16 +1108,6 @@ int nfa_specset_set_baseline(nfa_specset *ss, int order) {
     return rc;
 }
 
-// a calibrated set's part is chi^2 plus sigma^2 log1p(s^2 A / sigma^2): no chi^2 whose noise scale integrates
-// out in closed form.  The same words from either setter.
-#define NMARG_CALIB_REFUSAL "a set takes a calibration uncertainty or a noise uncertainty, not both: a calibrated set's part is no chi^2"
-// a continuum background (nfa_specset_set_continuum) has one kernel family, the baseline form's: the same words
-// from nfa_specset_set_continuum and from the other setter, whichever comes second
-#define CONT_CALIB_REFUSAL "a set with a calibration uncertainty takes no continuum background"
-#define CONT_CORR_REFUSAL  "a set with correlated channel noise takes no continuum background"
-#define CONT_RESP_REFUSAL  "a set with a channel response takes no continuum background"
-#define CONT_TMPL_REFUSAL  "a set with nuisance templates takes no continuum background"
-
 int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
     SpecDev &d = ss->dev;
@@ -1124,12 +1117,7 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
             return fail(NFA_ERR_ARG, "a calibration uncertainty is a finite fraction in [0, 1] per spectrum");
         any = any || cal[s] > 0.0;
     }
-    if (any && d.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no calibration uncertainty");
-    if (any && d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no calibration uncertainty");
-    if (any && d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no calibration uncertainty");
-    if (any && d.nmarg) return fail(NFA_ERR_ARG, NMARG_CALIB_REFUSAL);
-    if (any && d.cont) return fail(NFA_ERR_ARG, CONT_CALIB_REFUSAL);
-    if (any && d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("calibration uncertainty"));
+    if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_CALIB) : nullptr) return fail(NFA_ERR_ARG, why);
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any) {                                               // null, or all zeros: the set's former kernels and bits
@@ -1189,8 +1177,7 @@ int nfa_specset_set_noise_uncertainty(nfa_specset *ss, const double *f) {
             return fail(NFA_ERR_ARG, "a noise uncertainty is a finite fraction in [0, 0.5] per spectrum");
         any = any || f[s] > 0.0;
     }
-    if (any && d.cal2) return fail(NFA_ERR_ARG, NMARG_CALIB_REFUSAL);
-    if (any && d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("noise uncertainty"));
+    if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_NMARG) : nullptr) return fail(NFA_ERR_ARG, why);
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any) {                                               // null, or all zeros: the set's former arithmetic and bits
@@ -1343,12 +1330,7 @@ int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
     if (any) {
         for (int s = 0; s < d.n_spec; ++s)
             if (d.size[s] < 4) return fail(NFA_ERR_ARG, "a noise correlation needs spectra of 4 channels and more");
-        if (ss->masked) return fail(NFA_ERR_ARG, "a set with a masked channel takes no noise correlation");
-        if (d.bl_order >= 0) return fail(NFA_ERR_ARG, "a set with a baseline takes no noise correlation");
-        if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no noise correlation");
-        if (d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no noise correlation");
-        if (d.cont) return fail(NFA_ERR_ARG, CONT_CORR_REFUSAL);
-        if (d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("noise correlation"));
+        if (const char *why = set_refusal(specset_has(ss), SET_TAKES_CORR)) return fail(NFA_ERR_ARG, why);
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1383,12 +1365,7 @@ int nfa_specset_set_response(nfa_specset *ss, const double *taps) {
     if (any) {
         for (int s = 0; s < d.n_spec; ++s)
             if (d.size[s] < 4) return fail(NFA_ERR_ARG, "a channel response needs spectra of 4 channels and more");
-        if (ss->masked) return fail(NFA_ERR_ARG, "a set with a masked channel takes no channel response");
-        if (d.bl_order >= 0) return fail(NFA_ERR_ARG, "a set with a baseline takes no channel response");
-        if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no channel response");
-        if (d.tmpl) return fail(NFA_ERR_ARG, "a set with nuisance templates takes no channel response");
-        if (d.cont) return fail(NFA_ERR_ARG, CONT_RESP_REFUSAL);
-        if (d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("channel response"));
+        if (const char *why = set_refusal(specset_has(ss), SET_TAKES_RESP)) return fail(NFA_ERR_ARG, why);
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1458,11 +1435,7 @@ int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmp
                 }
                 if (zero) return fail(NFA_ERR_ARG, "nuisance templates: a template is zero over its whole spectrum");
             }
-        if (d.resp) return fail(NFA_ERR_ARG, "a set with a channel response takes no nuisance templates");
-        if (d.corr_q1) return fail(NFA_ERR_ARG, "a set with correlated channel noise takes no nuisance templates");
-        if (d.cal2) return fail(NFA_ERR_ARG, "a set with a calibration uncertainty takes no nuisance templates");
-        if (d.cont) return fail(NFA_ERR_ARG, CONT_TMPL_REFUSAL);
-        if (d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("nuisance templates"));
+        if (const char *why = set_refusal(specset_has(ss), SET_TAKES_TMPL)) return fail(NFA_ERR_ARG, why);
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1518,11 +1491,7 @@ int nfa_specset_set_continuum(nfa_specset *ss, const double *tc) {
     if (any) {
         if (d.model == NFA_MODEL_GAUSSIAN)
             return fail(NFA_ERR_ARG, "the Gaussian model has no optical depth: its components cannot absorb a continuum background");
-        if (d.resp) return fail(NFA_ERR_ARG, CONT_RESP_REFUSAL);
-        if (d.corr_q1) return fail(NFA_ERR_ARG, CONT_CORR_REFUSAL);
-        if (d.cal2) return fail(NFA_ERR_ARG, CONT_CALIB_REFUSAL);
-        if (d.tmpl) return fail(NFA_ERR_ARG, CONT_TMPL_REFUSAL);
-        if (d.rob) return fail(NFA_ERR_ARG, ROB_REFUSES("continuum background"));
+        if (const char *why = set_refusal(specset_has(ss), SET_TAKES_CONT)) return fail(NFA_ERR_ARG, why);
     }
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
@@ -1597,15 +1566,7 @@ int nfa_specset_set_robust(nfa_specset *ss, const double *nu) {
             return fail(NFA_ERR_ARG, "a robust likelihood takes finite degrees of freedom per spectrum, 0 (Gaussian) or in [1, 1e6]");
         any = any || nu[s] > 0.0;
     }
-    if (any) {
-        if (d.bl_order >= 0) return fail(NFA_ERR_ARG, ROB_REFUSED("a baseline"));
-        if (d.tmpl) return fail(NFA_ERR_ARG, ROB_REFUSED("nuisance templates"));
-        if (d.cal2) return fail(NFA_ERR_ARG, ROB_REFUSED("a calibration uncertainty"));
-        if (d.resp) return fail(NFA_ERR_ARG, ROB_REFUSED("a channel response"));
-        if (d.corr_q1) return fail(NFA_ERR_ARG, ROB_REFUSED("correlated channel noise"));
-        if (d.nmarg) return fail(NFA_ERR_ARG, ROB_REFUSED("a noise uncertainty"));
-        if (d.cont) return fail(NFA_ERR_ARG, ROB_REFUSED("a continuum background"));
-    }
+    if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_ROBUST) : nullptr) return fail(NFA_ERR_ARG, why);
     int rc = engine_init(); if (rc) return rc;
     rc = specset_quiesce(ss); if (rc) return rc;
     if (!any && !d.rob) return NFA_OK;                        // null, or all zeros, and none before: nothing changes
@@ -1926,6 +1887,11 @@ static SpecDev runner_specdev(const nfa_runner *r) {
     S.t0_xmin = g_eng.t0_xmin; S.t0_xmax = g_eng.t0_xmax; S.t0_inv_dx = g_eng.t0_inv_dx;
     return S;
 }
+// the plan of the fused kernels for a runner's points (S: runner_specdev(r)): what its set is right now, said once
+static FusedPlan runner_fused_plan(const nfa_runner *r, int mode, const SpecDev &S) {
+    return plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
+                      S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr);
+}
 
 // A kernel that wants more than 64 KB of dynamic LDS has to be told so -- once per kernel and size, not on every
 // launch (the attribute call is a trip into the runtime: 1-2 us of the ~10 the host spends on enqueueing a step).
@@ -2049,82 +2015,22 @@ static LnlKernel lnl_kernel_of(int mode, bool write_spec, int ncomp, const LnlPl
     return lnl_kernel_at(lnl_inst_index({mode, write_spec, P.wide, lnl_plan_ncomp(P, ncomp), lnl_plan_kind(P)}), P.form,
                          std::make_index_sequence<LNL_INSTANCES>());
 }
-// The kernel of a set with correlated channel noise: lnl_kernel_corr over (mode, spectra out, wide, filled, layered), beside
-// the table (its launches are on no entry of it, so count_lnl_launch counts none of them)
-template <int I>     // I: bit 4 layered, bit 3 filled, bit 2 fast mode, bit 1 spectra out, bit 0 wide
-static LnlKernel lnl_kernel_corr_inst() {
-    return lnl_kernel_corr<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
+// The kernel of a set of a side (LnlSide): lnl_kernel_side over (side, lnl_side_index), beside the table (its launches are
+// on no entry of it, so count_lnl_launch counts none of them).  Null unless the plan has the side's form.
+template <int I>     // I: 32 (side - 1) + lnl_side_index
+static LnlKernel lnl_kernel_side_inst() {
+    constexpr LnlSideInst N = lnl_side_at(I % LNL_SIDE_INSTANCES);
+    return lnl_kernel_side<N.mode, N.write_spec, N.wide, N.filled, N.layered, I / LNL_SIDE_INSTANCES + 1>;
 }
 template <size_t... I>
-static LnlKernel lnl_kernel_corr_at(int i, std::index_sequence<I...>) {
-    static constexpr LnlKernel (*inst[])() = {lnl_kernel_corr_inst<(int)I>...};
+static LnlKernel lnl_kernel_side_at(int i, std::index_sequence<I...>) {
+    static constexpr LnlKernel (*inst[])() = {lnl_kernel_side_inst<(int)I>...};
     return inst[i]();
 }
-static LnlKernel lnl_kernel_corr_of(int mode, bool write_spec, const LnlPlan &P) {
-    if (P.form != LNL_WEIGHTED) return nullptr;               // the weighted form's plan: waves, LDS, workgroups
-    return lnl_kernel_corr_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
-                              std::make_index_sequence<32>());
-}
-// ... and of a set with a channel response: lnl_kernel_resp over the same five, chosen the same way
-template <int I>
-static LnlKernel lnl_kernel_resp_inst() {
-    return lnl_kernel_resp<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
-}
-template <size_t... I>
-static LnlKernel lnl_kernel_resp_at(int i, std::index_sequence<I...>) {
-    static constexpr LnlKernel (*inst[])() = {lnl_kernel_resp_inst<(int)I>...};
-    return inst[i]();
-}
-static LnlKernel lnl_kernel_resp_of(int mode, bool write_spec, const LnlPlan &P) {
-    if (P.form != LNL_WEIGHTED) return nullptr;
-    return lnl_kernel_resp_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
-                              std::make_index_sequence<32>());
-}
-// ... and of a set with nuisance templates: lnl_kernel_tmpl over the same five, with the baseline form's plan (plan_lnl's
-// `templates`: nine sums per part)
-template <int I>
-static LnlKernel lnl_kernel_tmpl_inst() {
-    return lnl_kernel_tmpl<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
-}
-template <size_t... I>
-static LnlKernel lnl_kernel_tmpl_at(int i, std::index_sequence<I...>) {
-    static constexpr LnlKernel (*inst[])() = {lnl_kernel_tmpl_inst<(int)I>...};
-    return inst[i]();
-}
-static LnlKernel lnl_kernel_tmpl_of(int mode, bool write_spec, const LnlPlan &P) {
-    if (P.form != LNL_BASELINE) return nullptr;
-    return lnl_kernel_tmpl_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
-                              std::make_index_sequence<32>());
-}
-// ... and of a set with a continuum background: lnl_kernel_cont over the same five, with the baseline form's plan
-template <int I>
-static LnlKernel lnl_kernel_cont_inst() {
-    return lnl_kernel_cont<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
-}
-template <size_t... I>
-static LnlKernel lnl_kernel_cont_at(int i, std::index_sequence<I...>) {
-    static constexpr LnlKernel (*inst[])() = {lnl_kernel_cont_inst<(int)I>...};
-    return inst[i]();
-}
-static LnlKernel lnl_kernel_cont_of(int mode, bool write_spec, const LnlPlan &P) {
-    if (P.form != LNL_BASELINE) return nullptr;
-    return lnl_kernel_cont_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
-                              std::make_index_sequence<32>());
-}
-// ... and of a set with a robust likelihood: lnl_kernel_robust over the same five, with the weighted form's plan
-template <int I>
-static LnlKernel lnl_kernel_robust_inst() {
-    return lnl_kernel_robust<(I & 4) ? 2 : 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0, (I & 16) != 0>;
-}
-template <size_t... I>
-static LnlKernel lnl_kernel_robust_at(int i, std::index_sequence<I...>) {
-    static constexpr LnlKernel (*inst[])() = {lnl_kernel_robust_inst<(int)I>...};
-    return inst[i]();
-}
-static LnlKernel lnl_kernel_robust_of(int mode, bool write_spec, const LnlPlan &P) {
-    if (P.form != LNL_WEIGHTED) return nullptr;
-    return lnl_kernel_robust_at((P.layered ? 16 : 0) | (P.filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (P.wide ? 1 : 0),
-                                std::make_index_sequence<32>());
+static LnlKernel lnl_kernel_side_of(LnlSide side, int mode, bool write_spec, const LnlPlan &P) {
+    if (P.form != lnl_side_form(side)) return nullptr;
+    return lnl_kernel_side_at(LNL_SIDE_INSTANCES * (side - 1) + lnl_side_index(mode, write_spec, P.wide, P.filled, P.layered),
+                              std::make_index_sequence<LNL_SIDES * LNL_SIDE_INSTANCES>());
 }
 #ifdef NFA_TEST_HOOKS
 #include <atomic>
@@ -2157,11 +2063,8 @@ static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, in
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlKernel kern = S.rob ? lnl_kernel_robust_of(mode, d_spec != nullptr, P)
-                         : S.cont ? lnl_kernel_cont_of(mode, d_spec != nullptr, P)
-                         : S.tmpl ? lnl_kernel_tmpl_of(mode, d_spec != nullptr, P)
-                         : S.resp ? lnl_kernel_resp_of(mode, d_spec != nullptr, P)
-                         : S.corr_q1 ? lnl_kernel_corr_of(mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
+    const LnlSide side = lnl_side_of(S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr);
+    const LnlKernel kern = side != LNL_SIDE_NONE ? lnl_kernel_side_of(side, mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
 #ifdef NFA_TEST_HOOKS
     count_lnl_launch(kern);
@@ -2376,8 +2279,7 @@ static int few_points_kernel(nfa_runner *r, const int32_t *pix, double *U, doubl
     if (!g_eng.point || r->profiling || B > NFA_POINT_MAXB) return 0;
     const int mode = runner_mode(r);
     const SpecDev S = runner_specdev(r);
-    const FusedPlan P = plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
-                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr);
+    const FusedPlan P = runner_fused_plan(r, mode, S);
     if (P.refusal || P.lds_point > LDS_PER_CU) return 0;
     if (reserve_lane(r, 0, B) != NFA_OK) return -1;
     if (!r->h_point) {

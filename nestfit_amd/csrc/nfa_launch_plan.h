@@ -185,7 +185,9 @@ struct LnlPlan { LnlForm form; bool wide, filled, layered, calibrated; LnlGeom G
 
 // The kind of a spectra set: which of lnl_body's WEIGHTED, BASELINE, FILL, LAYER, CALIB flags its kernel switches on
 // (lnl_kernel_kind<..., KIND>, nfa_device.h).  Kind 0 is the plain set: lnl_kernel, lnl_kernel_w8, lnl_kernel_queue.
-enum : unsigned { LNL_K_WEIGHTED = 1, LNL_K_BASELINE = 2, LNL_K_FILL = 4, LNL_K_LAYER = 8, LNL_K_CALIB = 16 };
+// Behind the five kind bits, in the same word, the flags of lnl_body that no kind has: the side family's (LnlSide below).
+enum : unsigned { LNL_K_WEIGHTED = 1, LNL_K_BASELINE = 2, LNL_K_FILL = 4, LNL_K_LAYER = 8, LNL_K_CALIB = 16,
+                  LNL_F_CORR = 32, LNL_F_RESP = 64, LNL_F_TMPL = 128, LNL_F_CONT = 256, LNL_F_ROBUST = 512 };
 constexpr unsigned LNL_KINDS = 32;      // kinds 0 .. 31: every set of the five bits
 constexpr unsigned lnl_plan_kind(const LnlPlan &P) {
     return (P.form == LNL_WEIGHTED || P.form == LNL_BASELINE ? LNL_K_WEIGHTED : 0u) | (P.form == LNL_BASELINE ? LNL_K_BASELINE : 0u) |
@@ -228,9 +230,41 @@ constexpr bool lnl_inst_round_trip() {
     return true;
 }
 static_assert(lnl_inst_round_trip(), "lnl_inst_at must invert lnl_inst_index over the whole table");
+
+// The side family, lnl_kernel_side<MODE, WRITE_SPEC, WIDE, FILL, LAYER, SIDE> (nfa_device.h): the kernels of a set with
+// correlated channel noise, a channel response, nuisance templates, a continuum background or a robust likelihood.  They stand
+// beside the table of kinds, in the general component form only (NCOMP 0), 32 instances per side; a side says which flags
+// of lnl_body its kernels switch on and, through them, under which plan form they run.
+enum LnlSide { LNL_SIDE_NONE, LNL_SIDE_CORR, LNL_SIDE_RESP, LNL_SIDE_TMPL, LNL_SIDE_CONT, LNL_SIDE_ROBUST };
+constexpr int LNL_SIDES = 5, LNL_SIDE_INSTANCES = 32;
+constexpr unsigned lnl_side_flags(LnlSide side) {
+    return side == LNL_SIDE_CORR ? LNL_K_WEIGHTED | LNL_F_CORR : side == LNL_SIDE_RESP ? LNL_K_WEIGHTED | LNL_F_CORR | LNL_F_RESP :
+           side == LNL_SIDE_TMPL ? LNL_K_WEIGHTED | LNL_K_BASELINE | LNL_F_TMPL :
+           side == LNL_SIDE_CONT ? LNL_K_WEIGHTED | LNL_K_BASELINE | LNL_F_CONT : side == LNL_SIDE_ROBUST ? LNL_K_WEIGHTED | LNL_F_ROBUST : 0u;
+}
+// the plan form a side's kernels run under: the weighted form's waves, LDS and workgroups, or the baseline form's
+constexpr LnlForm lnl_side_form(LnlSide side) { return lnl_kind_form(lnl_side_flags(side)); }
+// the side of a set: a robust likelihood first, then a continuum, templates, a response (which is correlated too), a correlation
+constexpr LnlSide lnl_side_of(bool corr, bool resp, bool tmpl, bool cont, bool rob) {
+    return rob ? LNL_SIDE_ROBUST : cont ? LNL_SIDE_CONT : tmpl ? LNL_SIDE_TMPL : resp ? LNL_SIDE_RESP : corr ? LNL_SIDE_CORR : LNL_SIDE_NONE;
+}
+// An instance of a side and its index: bit 0 wide, 1 spectra out, 2 fast mode, 3 filled, 4 layered
+struct LnlSideInst { int mode; bool write_spec, wide, filled, layered; };
+constexpr int lnl_side_index(int mode, bool write_spec, bool wide, bool filled, bool layered) {
+    return (layered ? 16 : 0) | (filled ? 8 : 0) | (mode == 0 ? 0 : 4) | (write_spec ? 2 : 0) | (wide ? 1 : 0);
+}
+constexpr LnlSideInst lnl_side_at(int i) { return {(i & 4) ? 2 : 0, (i & 2) != 0, (i & 1) != 0, (i & 8) != 0, (i & 16) != 0}; }
+constexpr bool lnl_side_round_trip() {
+    for (int i = 0; i < LNL_SIDE_INSTANCES; ++i) {
+        const LnlSideInst a = lnl_side_at(i);
+        if (lnl_side_index(a.mode, a.write_spec, a.wide, a.filled, a.layered) != i || (a.mode != 0 && a.mode != 2)) return false;
+    }
+    return true;
+}
+static_assert(lnl_side_round_trip(), "lnl_side_at must invert lnl_side_index over a side's 32 instances");
 // Plans the likelihood launch of L.B items (the table of forms in DESIGN 4.2 is tested against this chain).
 // templates: the set has nuisance templates (nfa_specset_set_templates): the baseline form's plan over nine
-// sums per part, for lnl_kernel_tmpl (beside the table: the plan names no instance of it).
+// sums per part, for lnl_kernel_side's templates side (beside the table: the plan names no instance of it).
 inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L, bool templates = false) {
     LnlPlan P = {};
     const int64_t units = L.B * s.n_spec;

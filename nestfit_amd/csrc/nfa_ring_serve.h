@@ -193,8 +193,7 @@ int nfa_ring_serve_device(nfa_ring *ring, nfa_runner *run, int lifetime_ms, int 
     RUNNER_LOCK(run);
     const int mode = runner_mode(run);
     const SpecDev S = runner_specdev(run);
-    const FusedPlan P = plan_fused(run->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, run->ss->filled, run->ss->layered,
-                                     S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr);
+    const FusedPlan P = runner_fused_plan(run, mode, S);
     if (P.refusal) return fail(NFA_ERR_ARG, P.refusal);
     if (lifetime_ms <= 0) lifetime_ms = 20;
     if (lifetime_ms > 1000) lifetime_ms = 1000;

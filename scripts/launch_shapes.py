@@ -7,7 +7,7 @@ plan_setup, plan_fused) and prints a checksum of every result array.  It is dete
 process, no timing, a synchronisation after every launch -- so that two builds of the engine can be compared: run it
 under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/launch_shapes.py` with each, reduce the
 two traces with the second form to (kernel, grid, workgroup, LDS) in dispatch order, and diff the two lists and the two
-outputs (profiles/launch_plan/README.md, profiles/set_kinds/README.md).  The resident ring kernel needs a client process: tests/test_ring.py."""
+outputs (profiles/launch_plan/README.md, profiles/set_kinds/README.md, profiles/side_family/README.md).  The resident ring kernel needs a client process: tests/test_ring.py."""
 import csv
 import ctypes as C
 import hashlib
@@ -213,6 +213,15 @@ def main():
                                                  ('ammonia calibrated, baseline 3', ammonia, dict(calibration=0.1, baseline_order=3)),
                                                  ('filled mix layered calibrated', filled, dict(layered=True, calibration=0.1)))):
             host_calls(f'{mode} {what}', make(**kw), (1, 16, 300, 4096), 56 + seed, spectra_rows=300)
+        # the side family (lnl_kernel_side), one small set per side: ammonia of 2 x 300 channels, the same layered, and the
+        # filled mix -- a correlation, a response with its correlation, templates beside a baseline, a continuum, a robust likelihood
+        short = lambda **kw: na.AmmoniaRunner.from_data(ammonia_spectra(300, 3), na.get_irdc_priors(size=500), ncomp=2, **kw)
+        ripples = [na.ripple(300, 137.3)] * 2
+        for seed, (side, kw) in enumerate((('correlation', dict(correlation=na.HANNING)), ('response', na.smoothed(na.HANNING_RESPONSE)),
+                                           ('templates', dict(templates=ripples, baseline_order=1)), ('continuum', dict(continuum=30.0)),
+                                           ('robust', dict(robust=4)))):
+            for what, make, more in (('ammonia', short, {}), ('ammonia layered', short, dict(layered=True)), ('filled mix', filled, {})):
+                host_calls(f'{mode} {side} {what}', make(**kw, **more), (1, 16, 300), 90 + seed, spectra_rows=300)
         # weighted sets and baselines: the split parts' LDS differs with a baseline
         for what, kw in (('channel noise', dict(chan_noise=True)), ('baseline 1', dict(baseline_order=1)),
                          ('channel noise, baseline 3', dict(chan_noise=True, baseline_order=3))):

@@ -2,8 +2,8 @@
 
 lnL evaluations/s at the metric shape -- 4096-row batches, two spectra of 1024 channels, a noise per channel -- of spectra sets
 on the same data: the weighted set, the set with a baseline of order 1 (the baseline kind), the same set layered (the baseline
-kind in the general component form, which is the form lnl_kernel_cont has), and the sets with a continuum background of 30 K
-per (pixel, spectrum) behind them (`continuum=`, lnl_kernel_cont: one more add per visited row and lane), with the baseline
+kind in the general component form, which is the form lnl_kernel_side (cont) has), and the sets with a continuum background of 30 K
+per (pixel, spectrum) behind them (`continuum=`, lnl_kernel_side (cont): one more add per visited row and lane), with the baseline
 and without one (a zeroed record), summed and layered.  At four components every set runs the general component form and
 `time_vs_baseline` of the set 'continuum' is the feature's own cost; at two the baseline set is the UNROLLED form (NCOMP = 2,
 packed windows) and that ratio is the form's cost -- `time_vs_general`, against the layered baseline set, leaves it out.

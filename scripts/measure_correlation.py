@@ -2,7 +2,7 @@
 
 lnL evaluations/s at the metric shape -- 4096-row batches, two spectra of 1024 channels -- of one weighted spectra set (a
 noise per channel, constant over each spectrum) against the same data with correlated channel noise (`correlation=HANNING`,
-nfa_specset_set_correlation: lnl_kernel_corr, the weighted form in the general component form with rows of 62 channels and
+nfa_specset_set_correlation: lnl_kernel_side (corr), the weighted form in the general component form with rows of 62 channels and
 two more loads and a neighbour product per row), in the table mode (the unit queue off, which weighted sets skip anyway) and
 the fast mode.  --ncomp 4: both sets take the general component form, so the kernels differ by the correlation alone (34
 rows of 62 channels against 32 of 64, the halo lanes' model values, two DPP shifts and a fused multiply-add chain per row).

@@ -2,8 +2,8 @@
 
 lnL evaluations/s at the metric shape -- 4096-row batches, two spectra of 1024 channels, a noise per channel -- of three
 spectra sets on the same data: the weighted set, the set with correlated channel noise (`correlation=HANNING`,
-lnl_kernel_corr: rows of 62 channels) and the set with a channel response as well (`**na.smoothed(na.HANNING_RESPONSE)`,
-lnl_kernel_resp: rows of 58 channels, four more wave shifts and five multiply-adds per visited row), and the response alone
+lnl_kernel_side (corr): rows of 62 channels) and the set with a channel response as well (`**na.smoothed(na.HANNING_RESPONSE)`,
+lnl_kernel_side (resp): rows of 58 channels, four more wave shifts and five multiply-adds per visited row), and the response alone
 (over white coefficients).  Table and fast mode, the sets timed in turn, R times each, the median of each reported: the
 set-up, the timing loop and the record of scripts/measure_correlation.py, whose `time_vs_weighted` is kept and
 `time_vs_correlated` added.  --ncomp 4: every set takes the general component form; --ncomp 2: the weighted side is the

@@ -2,7 +2,7 @@
 
 lnL evaluations/s at the metric shape -- 4096-row batches, two spectra of 1024 channels, a noise per channel -- of spectra sets
 on the same data: the weighted set, the same set layered (the weighted kind in the general component form, which is the form
-lnl_kernel_robust has), and the sets with a robust likelihood (`robust=4`, lnl_kernel_robust: an fp64 log1p per visited row
+lnl_kernel_side (robust) has), and the sets with a robust likelihood (`robust=4`, lnl_kernel_side (robust): an fp64 log1p per visited row
 and lane where the weighted form has a fused multiply-add), summed and layered.  At four components every set runs the
 general component form and `time_vs_weighted` of the set 'robust' is the feature's own cost; at two the weighted set is the
 UNROLLED form (NCOMP = 2, packed windows) and that ratio includes the form's cost -- `time_vs_general`, against the layered

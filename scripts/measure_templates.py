@@ -2,9 +2,9 @@
 
 lnL evaluations/s at the metric shape -- 4096-row batches, two spectra of 1024 channels, a noise per channel -- of spectra sets
 on the same data: the weighted set, the set with a baseline of order 1 (the baseline kind: four moments), the same set layered
-(the baseline kind in the general component form, which is the form lnl_kernel_tmpl has: at two components the difference to the
+(the baseline kind in the general component form, which is the form lnl_kernel_side (tmpl) has: at two components the difference to the
 baseline set is what the unrolled component loop is worth, not what templates cost), and the set with the baseline and nuisance
-templates (`templates=`, lnl_kernel_tmpl: eight moments, four more loads and multiply-adds per visited row) -- a ripple's sine
+templates (`templates=`, lnl_kernel_side (tmpl): eight moments, four more loads and multiply-adds per visited row) -- a ripple's sine
 and cosine per spectrum, and four templates per spectrum, which cost the same: all four slots are always formed.  Table and fast
 mode, the sets timed in turn, R times each, the median of each reported: the set-up, the timing loop and the record of
 scripts/measure_correlation.py, whose `time_vs_weighted` is kept; `time_vs_baseline` and `time_vs_general` (against the layered

@@ -1,5 +1,5 @@
 """A continuum background behind the components on the device (nfa_specset_set_continuum, `continuum=`): every
-component's g = T0 (y - tbg) becomes g - Tc in lnl_kernel_cont, the baseline form with one more flag.
+component's g = T0 (y - tbg) becomes g - Tc in lnl_kernel_side (cont), the baseline form with one more flag.
 
 The reference is tests/cont_restatement.py on the draws of tests/cont_cases.py (tests/test_continuum_cpu.py holds both to
 the sibling restatements and to what is said of the draws below), at the sizes of the sibling tests: 300 channels -- four

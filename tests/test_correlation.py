@@ -1,5 +1,5 @@
 """Channel noise correlated along the spectral axis on the device (nfa_specset_set_correlation, `correlation=`):
-chi^2 = (d - p)^T Q (d - p) with Q = diag(u) R^-1 diag(u) pentadiagonal, in lnl_kernel_corr, whose rows advance by 62 channels
+chi^2 = (d - p)^T Q (d - p) with Q = diag(u) R^-1 diag(u) pentadiagonal, in lnl_kernel_side (corr), whose rows advance by 62 channels
 with a halo of two lanes.
 
 The reference is tests/corr_restatement.py (R as a Toeplitz matrix from the autocorrelation recursion, chi^2 from a dense

@@ -99,6 +99,15 @@ void plan_inst(const LpShape *s, const LpKnobs *k, const LpLaunch *L, int filled
     const LnlPlan P = plan_lnl(*s, *k, l);
     out[0] = P.error != nullptr; out[1] = P.form; out[2] = P.wide; out[3] = (int)lnl_plan_kind(P); out[4] = lnl_plan_ncomp(P, s->ncomp);
 }
+// the side family (lnl_kernel_side): a side's flag word and plan form, an instance's index and its inverse, the side of a set
+unsigned side_flags(int side) { return lnl_side_flags((LnlSide)side); }
+int side_form(int side) { return lnl_side_form((LnlSide)side); }
+int side_index(int mode, int ws, int wide, int filled, int layered) { return lnl_side_index(mode, ws != 0, wide != 0, filled != 0, layered != 0); }
+void side_at(int i, int *out) {
+    const LnlSideInst a = lnl_side_at(i);
+    out[0] = a.mode; out[1] = a.write_spec; out[2] = a.wide; out[3] = a.filled; out[4] = a.layered;
+}
+int side_of(int corr, int resp, int tmpl, int cont, int rob) { return lnl_side_of(corr != 0, resp != 0, tmpl != 0, cont != 0, rob != 0); }
 int sizes(int i) {
     const int s[] = {sizeof(LpShape), sizeof(LpLaunch), sizeof(LpKnobs), sizeof(LnlGeom), sizeof(LnlPlan), sizeof(SetupPlan), sizeof(FusedPlan),
                      SM_TABLE_DOUBLES, SM_TABLE_TAIL, (int)LDS_PER_CU, LNL_PARTS, NFA_BL_NB, SETUP_TI, QREC, POINT_WAVES, NFA_POINT_MAXDIM, NFA_GROUP_MAX};
@@ -552,3 +561,37 @@ def test_lanes_and_coalescing_at_their_edges(lib):
     assert [full(n, 4096, knobs(coalesce=2)) for n in (1, 2)] == [False, True]
     assert [full(n, 8192) for n in (2, 3, 4)] == [False, False, True]
     assert [full(n, 16384) for n in (1, 2)] == [False, True]
+
+
+# ---- the side family ------------------------------------------------------------------------------------------------
+F_CORR, F_RESP, F_TMPL, F_CONT, F_ROBUST = 32, 64, 128, 256, 512
+SIDE_NONE, SIDE_CORR, SIDE_RESP, SIDE_TMPL, SIDE_CONT, SIDE_ROBUST = range(6)
+# a side's kernels: the flags of lnl_body they switch on, and the form whose plan they are launched with
+SIDES = {SIDE_CORR: (K_WEIGHTED | F_CORR, WEIGHTED), SIDE_RESP: (K_WEIGHTED | F_CORR | F_RESP, WEIGHTED),
+         SIDE_TMPL: (K_WEIGHTED | K_BASELINE | F_TMPL, BASELINE), SIDE_CONT: (K_WEIGHTED | K_BASELINE | F_CONT, BASELINE),
+         SIDE_ROBUST: (K_WEIGHTED | F_ROBUST, WEIGHTED)}
+
+
+def test_the_side_family_is_the_five_words_their_forms_one_layout_and_one_precedence(lib):
+    """lnl_kernel_side's host side against a table written here: the flag word of each side (none: the plain set's 0), the
+    plan form it runs under (the weighted form for a correlation, a response and a robust likelihood, the baseline form for
+    templates and a continuum), the index of an instance -- bit 0 wide, 1 spectra out, 2 fast mode, 3 filled, 4 layered, so
+    exactly the values 0..31, each once, and lnl_side_at its inverse -- and the side of a set: a robust likelihood before a
+    continuum before templates before a response before a correlation."""
+    lib.side_flags.restype = C.c_uint
+    assert lib.side_flags(SIDE_NONE) == 0 and lib.side_form(SIDE_NONE) == PLAIN
+    for side, (flags, form) in SIDES.items():
+        assert (lib.side_flags(side), lib.side_form(side)) == (flags, form), side
+    assert len({flags for flags, _ in SIDES.values()}) == 5
+    seen, out = {}, (C.c_int * 5)()
+    for layered, filled, mode, ws, wide in itertools.product((0, 1), (0, 1), (0, 2), (0, 1), (0, 1)):
+        i = lib.side_index(mode, ws, wide, filled, layered)
+        assert i == 16 * layered + 8 * filled + (4 if mode == 2 else 0) + 2 * ws + wide
+        lib.side_at(i, out)
+        assert list(out) == [mode, ws, wide, filled, layered]
+        seen[i] = (mode, ws, wide, filled, layered)
+    assert sorted(seen) == list(range(32))
+    for corr, resp, tmpl, cont, rob in itertools.product((0, 1), repeat=5):
+        want = (SIDE_ROBUST if rob else SIDE_CONT if cont else SIDE_TMPL if tmpl else SIDE_RESP if resp else SIDE_CORR if corr
+                else SIDE_NONE)
+        assert lib.side_of(corr, resp, tmpl, cont, rob) == want, (corr, resp, tmpl, cont, rob)

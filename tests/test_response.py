@@ -1,5 +1,5 @@
 """A channel response on the device (nfa_specset_set_response, `response=`): the model that meets the data is
-p~_j = sum_k h_k p_{j+k}, formed in lnl_kernel_resp, whose rows advance by 58 channels: a lane evaluates the model two channels
+p~_j = sum_k h_k p_{j+k}, formed in lnl_kernel_side (resp), whose rows advance by 58 channels: a lane evaluates the model two channels
 before the one whose p~ it holds, four wave shifts and five multiply-adds make p~, and two lanes of p~ are the halo of the
 correlated form.
 

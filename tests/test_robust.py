@@ -1,5 +1,5 @@
 """A robust likelihood on the device (nfa_specset_set_robust, `robust=`): Student-t channel noise with nu degrees
-of freedom per spectrum, lnL_s = -(nu + 1) / 2 sum_j log1p(a_j (d_j - p_j)^2), in lnl_kernel_robust -- the weighted form over
+of freedom per spectrum, lnL_s = -(nu + 1) / 2 sum_j log1p(a_j (d_j - p_j)^2), in lnl_kernel_side (robust) -- the weighted form over
 g = a / (1 + a d^2) and g d with log1p(t) where the weighted form adds t.
 
 The reference is tests/robust_restatement.py (the direct sum in longdouble; no g, no difference form) on model spectra of the

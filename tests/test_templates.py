@@ -1,5 +1,5 @@
 """Nuisance templates profiled out with the baseline on the device (nfa_specset_set_templates, `templates=`):
-chi2_min over span{P_0..P_K, t_1..t_T} in lnl_kernel_tmpl, eight moments where the baseline form has four.
+chi2_min over span{P_0..P_K, t_1..t_T} in lnl_kernel_side (tmpl), eight moments where the baseline form has four.
 
 The reference is tests/tmpl_restatement.py (weighted least squares by QR in longdouble, no moments) on model spectra of the
 oracle and the other restatements, never the device's.
