@@ -6,67 +6,22 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from ._options import (APPLY_ORDER, MODEL_GAUSSIAN, OPTION_NAMES, TMPL_MAX, Options, check_baseline_order, check_calibration,  # noqa: F401
+                       check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_options, check_response,
+                       check_robust, check_templates, is_set, normalise, refusal, yule_walker)
 from .core import Runner, _as_inplace_matrix, _as_inplace_vector
 
-MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_GAUSSIAN, MODEL_HYPERFINE, MODEL_LTE = 0, 1, 2, 3, 4
+MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, MODEL_LTE = 0, 1, 3, 4                 # (MODEL_GAUSSIAN = 2: _options)
 # parameters per component
 N_MODEL = {MODEL_AMMONIA: 6, MODEL_DIAZENYLIUM: 4, MODEL_GAUSSIAN: 3, MODEL_HYPERFINE: 4, MODEL_LTE: 4}
-BASELINE_MAX = 3          # NFA_BASELINE_MAX
-
-
-def check_baseline_order(order):
-    """`baseline_order` of a runner: None (or -1) for no baseline, else an integer 0..BASELINE_MAX; ValueError otherwise."""
-    if order is None:
-        return None
-    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)):
-        raise ValueError(f'baseline_order must be None or an integer in -1..{BASELINE_MAX}, not {order!r}')
-    order = int(order)
-    if not -1 <= order <= BASELINE_MAX:
-        raise ValueError(f'baseline_order must be None or an integer in -1..{BASELINE_MAX}, not {order}')
-    return None if order == -1 else order
-
-
-def check_calibration(cal, n_spec=None):
-    """`calibration` of a runner: the fractional 1-sigma uncertainty of every spectrum's intensity scale.  None
-    for none; a number applies to all `n_spec` spectra; else one value per spectrum.  Every value is a finite number in
-    [0, 1]; all zeros is None.  Returns None or a float64 array (of n_spec values when n_spec is given); ValueError
-    otherwise.  Needs no device."""
-    if cal is None:
-        return None
-    what = 'calibration must be None, a number in [0, 1] or one such number per spectrum'
-    is_num = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-    if is_num(cal):
-        vals = [cal] * (1 if n_spec is None else int(n_spec))
-    elif isinstance(cal, np.ndarray) and cal.ndim == 1 and cal.dtype.kind in 'iuf':
-        vals = list(cal)
-    elif isinstance(cal, (list, tuple)) and all(is_num(v) for v in cal):
-        vals = list(cal)
-    else:
-        raise ValueError(f'{what}, not {cal!r}')
-    if not is_num(cal) and n_spec is not None and len(vals) != int(n_spec):
-        raise ValueError(f'{what}: {len(vals)} values for {int(n_spec)} spectra')
-    out = np.array(vals, dtype=np.float64)
-    if out.size == 0 or not np.all(np.isfinite(out)) or np.any(out < 0.0) or np.any(out > 1.0):
-        raise ValueError(f'{what}, not {cal!r}')
-    return out if np.any(out > 0.0) else None
-
 
 HANNING = (2.0 / 3.0, 1.0 / 6.0)      # (rho_1, rho_2) of white noise smoothed with the Hanning kernel (1/4, 1/2, 1/4)
-CORR_V_MIN = 0.01                     # smallest innovations variance a noise correlation may have (DESIGN 4.13)
 
 
 def ar1(rho):
     """The pair (rho, rho^2) of an AR(1) process: `correlation=ar1(0.5)`."""
     rho = float(rho)
     return (rho, rho * rho)
-
-
-def yule_walker(rho1, rho2):
-    """(phi_1, phi_2, v) of the unit-variance AR(2) process whose first two autocorrelations are (rho1, rho2): the
-    coefficients and the innovations variance."""
-    den = 1.0 - rho1 * rho1
-    phi1, phi2 = rho1 * (1.0 - rho2) / den, (rho2 - rho1 * rho1) / den
-    return phi1, phi2, 1.0 - phi1 * rho1 - phi2 * rho2
 
 
 def corr_bands(rho1, rho2, n):
@@ -86,105 +41,7 @@ def corr_lndet(rho1, rho2, n):
     return (n - 2) * np.log(yule_walker(rho1, rho2)[2]) + np.log(1.0 - rho1 * rho1)
 
 
-def check_correlation(corr, n_spec=None, sizes=None, masked=False, baseline_order=None, calibration=None):
-    """`correlation` of a runner: the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis
-    (DESIGN 4.13).  None for none; a pair applies to all `n_spec` spectra; an array [n_spec, 2] gives one pair per spectrum
-    (a one-dimensional value is always ONE pair).  Every pair is finite with |rho_1| < 1, 2 rho_1^2 - 1 < rho_2 < 1 and an
-    innovations variance v >= 0.01, or (0, 0) for white noise; all zeros is None.  A correlation goes with neither a masked
-    channel (`masked`), a baseline (`baseline_order`) nor a calibration uncertainty (`calibration`), and needs spectra of 4
-    channels and more (`sizes`).  Returns None or a float64 array [n_spec, 2] ([1, 2] without n_spec); ValueError otherwise.
-    Needs no device."""
-    if corr is None:
-        return None
-    what = 'correlation must be None, a pair (rho_1, rho_2) or an array [n_spec, 2] of such pairs'
-    try:
-        out = np.array(corr, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f'{what}, not {corr!r}') from None
-    if isinstance(corr, np.ndarray) and corr.dtype.kind not in 'iuf':
-        raise ValueError(f'{what}, not {corr!r}')
-    if out.ndim == 1 and out.shape == (2,):
-        out = np.tile(out, (1 if n_spec is None else int(n_spec), 1))
-    elif out.ndim != 2 or out.shape[1] != 2 or out.shape[0] == 0:
-        raise ValueError(f'{what}, not {corr!r}')
-    elif n_spec is not None and out.shape[0] != int(n_spec):
-        raise ValueError(f'{what}: {out.shape[0]} pairs for {int(n_spec)} spectra')
-    if not np.all(np.isfinite(out)):
-        raise ValueError(f'{what}: every value finite, not {corr!r}')
-    for r1, r2 in out:
-        if r1 == 0.0 and r2 == 0.0:
-            continue
-        if not abs(r1) < 1.0:
-            raise ValueError(f'correlation: |rho_1| < 1, not {r1!r}')
-        if not 2.0 * r1 * r1 - 1.0 < r2 < 1.0:
-            raise ValueError(f'correlation: 2 rho_1^2 - 1 < rho_2 < 1 (a positive definite correlation matrix), not ({r1!r}, {r2!r})')
-        if not yule_walker(r1, r2)[2] >= CORR_V_MIN:
-            raise ValueError(f'correlation: the innovations variance of ({r1!r}, {r2!r}) is below {CORR_V_MIN}: the noise is '
-                             'nearly determined by its neighbours')
-    if not np.any(out != 0.0):
-        return None
-    if sizes is not None and np.any(np.asarray(sizes) < 4):
-        raise ValueError('a noise correlation needs spectra of 4 channels and more')
-    if masked:
-        raise ValueError('a noise correlation does not go with masked channels (channel noise inf)')
-    if baseline_order is not None and baseline_order != -1:
-        raise ValueError('a noise correlation does not go with a baseline (baseline_order)')
-    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
-        raise ValueError('a noise correlation does not go with a calibration uncertainty (calibration)')
-    return out
-
-
 HANNING_RESPONSE = (0.25, 0.5, 0.25)  # the Hanning kernel as a channel response: `response=HANNING_RESPONSE` (DESIGN 4.14)
-RESP_SUM_TOL = 1e-9                   # how far the taps of a channel response may miss the sum 1
-
-
-def check_response(resp, n_spec=None, sizes=None, masked=False, baseline_order=None, calibration=None):
-    """`response` of a runner: the channel response of the spectrometer, an odd number of taps, 3 or 5, (h_-T .. h_0 .. h_T)
-    in units of channels; the model that meets the data is sum_k h_k p_{j+k}.  None for none; one response
-    applies to all `n_spec` spectra; an array [n_spec, 3 | 5] gives one per spectrum (a one-dimensional value is always ONE
-    response).  Every tap is finite, the taps sum to 1 within 1e-9 and h_0 > 0; (0, 1, 0) is an unfiltered spectrum, and
-    the identity everywhere is None.  A response goes with neither a masked channel (`masked`), a baseline
-    (`baseline_order`) nor a calibration uncertainty (`calibration`), and needs spectra of 4 channels and more (`sizes`).
-    Returns None or a float64 array [n_spec, 5] ([1, 5] without n_spec), three taps padded with zero ends; ValueError
-    otherwise.  Needs no device."""
-    if resp is None:
-        return None
-    what = 'response must be None, 3 or 5 taps (h_-T .. h_T) or an array [n_spec, 3 | 5] of such taps'
-    if isinstance(resp, (list, tuple)) and len(resp) > 0 and all(isinstance(r, (list, tuple, np.ndarray)) and np.ndim(r) == 1 and
-                                                                 len(r) in (3, 5) for r in resp):
-        resp = [[0.0, *r, 0.0] if len(r) == 3 else list(r) for r in resp]      # responses of three and of five taps side by side
-    try:
-        out = np.array(resp, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f'{what}, not {resp!r}') from None
-    if isinstance(resp, np.ndarray) and resp.dtype.kind not in 'iuf':
-        raise ValueError(f'{what}, not {resp!r}')
-    if out.ndim == 1 and out.shape[0] in (3, 5):
-        out = np.tile(out, (1 if n_spec is None else int(n_spec), 1))
-    elif out.ndim != 2 or out.shape[1] not in (3, 5) or out.shape[0] == 0:
-        raise ValueError(f'{what}, not {resp!r}')
-    elif n_spec is not None and out.shape[0] != int(n_spec):
-        raise ValueError(f'{what}: {out.shape[0]} responses for {int(n_spec)} spectra')
-    if not np.all(np.isfinite(out)):
-        raise ValueError(f'{what}: every tap finite, not {resp!r}')
-    if out.shape[1] == 3:
-        out = np.pad(out, ((0, 0), (1, 1)))
-    for h in out:
-        if not abs(float(np.sum(h)) - 1.0) <= RESP_SUM_TOL:
-            raise ValueError(f'channel response: the taps sum to 1 (it conserves the integrated intensity), not {float(np.sum(h))!r}')
-        if not h[2] > 0.0:
-            raise ValueError(f'channel response: the central tap is > 0, not {float(h[2])!r}')
-    if np.all(out == np.array([0.0, 0.0, 1.0, 0.0, 0.0])):
-        return None
-    if sizes is not None and np.any(np.asarray(sizes) < 4):
-        raise ValueError('a channel response needs spectra of 4 channels and more')
-    if masked:
-        raise ValueError('a channel response does not go with masked channels (channel noise inf)')
-    if baseline_order is not None and baseline_order != -1:
-        raise ValueError('a channel response does not go with a baseline (baseline_order)')
-    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
-        raise ValueError('a channel response does not go with a calibration uncertainty (calibration)')
-    return np.ascontiguousarray(out)
 
 
 def correlation_of_response(taps):
@@ -204,9 +61,6 @@ def smoothed(taps):
     return {'response': taps, 'correlation': correlation_of_response(taps)}
 
 
-TMPL_MAX = 4              # NFA_TMPL_MAX
-
-
 def ripple(n_chan, period, phase=None):
     """Templates of a standing wave of `period` channels (any real number > 0) on a spectrum of `n_chan` channels, for
     `templates=`: the rows sin(2 pi j / period) and cos(2 pi j / period), float64 [2, n_chan], whose two amplitudes stand for
@@ -221,58 +75,6 @@ def ripple(n_chan, period, phase=None):
     if not np.isfinite(float(phase)):
         raise ValueError(f'ripple: a finite phase (radians), not {phase!r}')
     return np.sin(arg + float(phase))[None, :]
-
-
-def check_templates(tmpl, n_spec=None, sizes=None, calibration=None, correlation=None, response=None):
-    """`templates` of a runner: fixed shapes on the channel grid, known up to an amplitude, that are profiled out of the
-    likelihood with the baseline.  None for none; else a list with one entry per spectrum, each None or an
-    array [T, N_s] of 1 <= T <= 4 templates over the spectrum's N_s channels (one row may be given as a 1-D array).  Every
-    value is finite and no template is zero over its whole spectrum; all entries None is None.  Nuisance templates go with
-    neither a calibration uncertainty, a noise correlation nor a channel response.  Returns None or a list of n_spec entries,
-    None or float64 [T, N_s]; ValueError otherwise.  Needs no device."""
-    if tmpl is None:
-        return None
-    what = 'templates must be None or a list with one entry per spectrum, each None or an array [T, n_chan] of 1..4 templates'
-    if isinstance(tmpl, np.ndarray) and tmpl.ndim in (1, 2) and tmpl.dtype.kind in 'iuf' and n_spec in (None, 1):
-        tmpl = [tmpl]                                         # one spectrum: its array alone
-    if not isinstance(tmpl, (list, tuple)) or len(tmpl) == 0:
-        raise ValueError(f'{what}, not {tmpl!r}')
-    if n_spec is not None and len(tmpl) != int(n_spec):
-        raise ValueError(f'{what}: {len(tmpl)} entries for {int(n_spec)} spectra')
-    out = []
-    for k, t in enumerate(tmpl):
-        if t is None:
-            out.append(None)
-            continue
-        try:
-            a = np.array(t, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f'{what}; spectrum {k}: {t!r}') from None
-        if a.ndim == 1:
-            a = a[None, :]
-        if a.ndim != 2 or a.shape[1] == 0:
-            raise ValueError(f'{what}; spectrum {k} has shape {a.shape}')
-        if a.shape[0] == 0:
-            out.append(None)
-            continue
-        if a.shape[0] > TMPL_MAX:
-            raise ValueError(f'nuisance templates: at most {TMPL_MAX} per spectrum, not {a.shape[0]} (spectrum {k})')
-        if sizes is not None and a.shape[1] != int(sizes[k]):
-            raise ValueError(f'nuisance templates: spectrum {k} has {int(sizes[k])} channels, its templates {a.shape[1]}')
-        if not np.all(np.isfinite(a)):
-            raise ValueError(f'nuisance templates: every value finite (spectrum {k})')
-        if np.any(np.all(a == 0.0, axis=1)):
-            raise ValueError(f'nuisance templates: a template is zero over its whole spectrum (spectrum {k})')
-        out.append(np.ascontiguousarray(a))
-    if all(a is None for a in out):
-        return None
-    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
-        raise ValueError('nuisance templates do not go with a calibration uncertainty (calibration)')
-    if check_correlation(correlation) is not None:            # (all zeros: none)
-        raise ValueError('nuisance templates do not go with a noise correlation (correlation)')
-    if check_response(response) is not None:                  # (the identity: none)
-        raise ValueError('nuisance templates do not go with a channel response (response)')
-    return out
 
 
 def nuisance_fit(resid, weight, order, templates):
@@ -306,135 +108,6 @@ def spec_data_sizes_masked(spec_data):
     sizes = [int(np.size(row[0])) for row in spec_data]
     masked = any(np.ndim(row[2]) > 0 and not np.all(np.isfinite(np.asarray(row[2], dtype=np.float64))) for row in spec_data)
     return sizes, masked
-
-
-NOISE_UNCERTAINTY_MAX = 0.5
-_NUNC_CALIB = 'a noise uncertainty does not go with a calibration uncertainty (calibration): a calibrated spectrum\'s part is no chi^2'
-
-
-def check_noise_uncertainty(f, n_spec=None, calibration=None):
-    """`noise_uncertainty` of a runner: the fractional 1-sigma uncertainty of every spectrum's noise level.
-    None for none; a number applies to all `n_spec` spectra; else one value per spectrum.  Every value is a finite number
-    in [0, 0.5] (above that the first-order relation a = 1 / (4 f^2) means nothing); all zeros is None.  Not with a
-    calibration uncertainty (`calibration`).  Returns None or a float64 array (of n_spec values when n_spec is given);
-    ValueError otherwise.  Needs no device."""
-    if f is None:
-        return None
-    what = 'noise uncertainty (noise_uncertainty) must be None, a number in [0, 0.5] or one such number per spectrum'
-    is_num = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-    if is_num(f):
-        vals = [f] * (1 if n_spec is None else int(n_spec))
-    elif isinstance(f, np.ndarray) and f.ndim == 1 and f.dtype.kind in 'iuf':
-        vals = list(f)
-    elif isinstance(f, (list, tuple)) and all(is_num(v) for v in f):
-        vals = list(f)
-    else:
-        raise ValueError(f'{what}, not {f!r}')
-    if not is_num(f) and n_spec is not None and len(vals) != int(n_spec):
-        raise ValueError(f'{what}: {len(vals)} values for {int(n_spec)} spectra')
-    out = np.array(vals, dtype=np.float64)
-    if out.size == 0 or not np.all(np.isfinite(out)) or np.any(out < 0.0) or np.any(out > NOISE_UNCERTAINTY_MAX):
-        raise ValueError(f'{what}, not {f!r}')
-    if not np.any(out > 0.0):
-        return None
-    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
-        raise ValueError(_NUNC_CALIB)
-    return out
-
-
-def check_continuum(tc, n_spec=None, n_pix=None, model=None, calibration=None, correlation=None, response=None, templates=None):
-    """`continuum` of a runner: the brightness temperature Tc >= 0 (K, on the data's scale) of a continuum source behind all
-    components, per spectrum (DESIGN 4.17) -- data of the continuum map that was subtracted, not a parameter.  None for none;
-    a number applies to all spectra (and pixels); one value per spectrum, [n_spec]; with `n_pix` given (a cube) also
-    [n_pix, n_spec].  Every value is finite and >= 0; all zeros is None.  A continuum goes with neither the Gaussian model
-    (`model`: no optical depth), a calibration uncertainty, a noise correlation, a channel response nor nuisance templates.
-    Returns None or a float64 array [n_spec] ([n_pix, n_spec] with n_pix; [1] for a number without n_spec); ValueError
-    otherwise.  Needs no device."""
-    if tc is None:
-        return None
-    what = ('continuum must be None, a brightness temperature >= 0 in K, one per spectrum'
-            + (' or an array [n_pix, n_spec]' if n_pix is not None else ''))
-    if isinstance(tc, (bool, np.bool_)) or (isinstance(tc, np.ndarray) and tc.dtype.kind not in 'iuf'):
-        raise ValueError(f'{what}, not {tc!r}')
-    try:
-        out = np.array(tc, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f'{what}, not {tc!r}') from None
-    if out.ndim == 0:
-        out = np.full(1 if n_spec is None else int(n_spec), float(out))
-    elif out.ndim == 1 and out.size > 0:
-        if n_spec is not None and out.shape[0] != int(n_spec):
-            raise ValueError(f'{what}: {out.shape[0]} values for {int(n_spec)} spectra')
-    elif out.ndim == 2 and n_pix is not None and out.size > 0:
-        if out.shape[0] != int(n_pix) or (n_spec is not None and out.shape[1] != int(n_spec)):
-            raise ValueError(f'{what}: shape {out.shape} for {int(n_pix)} pixels of {n_spec} spectra')
-    else:
-        raise ValueError(f'{what}, not an array of shape {out.shape}')
-    if not np.all(np.isfinite(out)) or np.any(out < 0.0):
-        raise ValueError(f'{what}: every value finite and >= 0, not {tc!r}')
-    if not np.any(out > 0.0):
-        return None
-    if n_pix is not None and out.ndim == 1:
-        out = np.tile(out, (int(n_pix), 1))
-    if model is not None and int(model) == MODEL_GAUSSIAN:
-        raise ValueError('the Gaussian model has no optical depth: its components cannot absorb a continuum background (continuum)')
-    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
-        raise ValueError('a continuum background does not go with a calibration uncertainty (calibration)')
-    if check_correlation(correlation) is not None:            # (all zeros: none)
-        raise ValueError('a continuum background does not go with a noise correlation (correlation)')
-    if check_response(response) is not None:                  # (the identity: none)
-        raise ValueError('a continuum background does not go with a channel response (response)')
-    if templates is not None and any(t is not None for t in templates):
-        raise ValueError('a continuum background does not go with nuisance templates (templates)')
-    return np.ascontiguousarray(out)
-
-
-ROBUST_MIN, ROBUST_MAX = 1.0, 1e6
-_ROB_NOT_WITH = 'a robust likelihood (robust) does not go with {}: under Student-t noise no linear nuisance has a closed form and a part is no chi^2'
-
-
-def check_robust(nu, n_spec=None, baseline_order=None, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None):
-    """`robust` of a runner: the degrees of freedom nu of the Student-t channel noise of every spectrum.  None
-    for none; a number applies to all `n_spec` spectra; else one value per spectrum.  Every value is finite and either 0
-    (that spectrum stays Gaussian) or in [1, 1e6] (beyond, the value is the Gaussian one within 1e-6: leave it out); all
-    zeros is None.  A robust likelihood goes with none of a baseline, a calibration uncertainty, a noise correlation, a
-    channel response, nuisance templates, a noise uncertainty and a continuum background.  Returns None or a float64 array
-    (of n_spec values when n_spec is given); ValueError otherwise.  Needs no device."""
-    if nu is None:
-        return None
-    what = 'robust must be None, degrees of freedom in [1, 1e6] (0: Gaussian) or one such number per spectrum'
-    is_num = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-    if is_num(nu):
-        vals = [nu] * (1 if n_spec is None else int(n_spec))
-    elif isinstance(nu, np.ndarray) and nu.ndim == 1 and nu.dtype.kind in 'iuf':
-        vals = list(nu)
-    elif isinstance(nu, (list, tuple)) and all(is_num(v) for v in nu):
-        vals = list(nu)
-    else:
-        raise ValueError(f'{what}, not {nu!r}')
-    if not is_num(nu) and n_spec is not None and len(vals) != int(n_spec):
-        raise ValueError(f'{what}: {len(vals)} values for {int(n_spec)} spectra')
-    out = np.array(vals, dtype=np.float64)
-    if out.size == 0 or not np.all(np.isfinite(out)) or np.any((out != 0.0) & ((out < ROBUST_MIN) | (out > ROBUST_MAX))):
-        raise ValueError(f'{what}, not {nu!r}')
-    if not np.any(out > 0.0):
-        return None
-    if check_baseline_order(baseline_order) is not None:
-        raise ValueError(_ROB_NOT_WITH.format('a baseline (baseline_order)'))
-    if calibration is not None and np.any(np.asarray(calibration, dtype=np.float64) > 0.0):
-        raise ValueError(_ROB_NOT_WITH.format('a calibration uncertainty (calibration)'))
-    if check_correlation(correlation) is not None:            # (all zeros: none)
-        raise ValueError(_ROB_NOT_WITH.format('a noise correlation (correlation)'))
-    if check_response(response) is not None:                  # (the identity: none)
-        raise ValueError(_ROB_NOT_WITH.format('a channel response (response)'))
-    if templates is not None and any(t is not None for t in templates):
-        raise ValueError(_ROB_NOT_WITH.format('nuisance templates (templates)'))
-    if check_noise_uncertainty(noise_uncertainty) is not None:
-        raise ValueError(_ROB_NOT_WITH.format('a noise uncertainty (noise_uncertainty)'))
-    if continuum is not None and np.any(np.asarray(continuum, dtype=np.float64) > 0.0):
-        raise ValueError(_ROB_NOT_WITH.format('a continuum background (continuum)'))
-    return out
 
 
 def _robust_a(noise, n, nu):
@@ -609,16 +282,6 @@ def channel_weights(noise, size):
     return 1.0 / np.asarray(noise, dtype=np.float64) ** 2
 
 
-def check_layered(layered, model=None):
-    """`layered` as a bool; ValueError for anything but True / False, and for the Gaussian model, which has no optical
-    depth.  Needs no device."""
-    if not isinstance(layered, (bool, np.bool_)):
-        raise ValueError('`layered` is True or False: whether a component absorbs the components behind it')
-    if layered and model is not None and int(model) == MODEL_GAUSSIAN:
-        raise ValueError('the Gaussian model has no optical depth: its components cannot absorb one another (`layered`)')
-    return bool(layered)
-
-
 class _SpecSet:
     """Owner of a device-resident set of spectra (one pixel or a cube)."""
 
@@ -725,68 +388,66 @@ class _SpecSet:
         _ffi.check(rc)
         self.handle = h
         self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
-        self.baseline_order = None
-        self.layered = False
-        self.calibration = None
-        self.correlation = None
-        self.response = None
-        self.templates = None
-        self.noise_uncertainty = None
-        self.continuum = None
-        self.robust = None
+        self.options = Options()                             # what the set has: ss.robust, ss.templates, ... read it
         self.masked = bool(self.per_channel and not np.all(np.isfinite(noise)))
+
+    def __getattr__(self, name):
+        """`ss.robust`, `ss.templates`, ...: the set's normalised options by their names, read from the one record."""
+        if name in OPTION_NAMES:
+            return getattr(self.options, name)
+        raise AttributeError(name)
+
+    def _set(self, name, value, args=None, **about):
+        """The body of every setter: the option's value check (`_options.normalise`; `about`: the model and the pixels, where
+        a setter lets it ask), the rules table against what the set has where the value switches the option on
+        (`_options.refusal`), the engine's nfa_specset_set_* with `args(value)` (by default the array, or NULL for none),
+        then the record."""
+        value = normalise(name, value, self.n_spec, self.sizes, **about)
+        if is_set(value):
+            why = refusal(name, self.options.has(self.masked))
+            if why is not None:
+                raise ValueError(why)
+        call = getattr(_ffi.load(), 'nfa_specset_set_' + name.replace('_order', ''))
+        _ffi.check(call(self.handle, *(args(value) if args else (None if value is None else _ffi.dptr(value),))))
+        setattr(self.options, name, value)
 
     def set_robust(self, nu):
         """The degrees of freedom of the spectra's Student-t channel noise (`check_robust`'s argument), or none (None,
         zeros): nfa_specset_set_robust.  null_lnZ() follows."""
-        nu = check_robust(nu, self.n_spec, self.baseline_order, self.calibration, self.correlation, self.response, self.templates,
-                          self.noise_uncertainty, self.continuum)
-        _ffi.check(_ffi.load().nfa_specset_set_robust(self.handle, None if nu is None else _ffi.dptr(nu)))
-        self.robust = nu
+        self._set('robust', nu)
 
     def get_robust(self):
         """The degrees of freedom as the engine holds them (nfa_specset_robust): None, or float64 [n_spec]."""
         out = np.zeros(self.n_spec)
         return out if _ffi.load().nfa_specset_robust(self.handle, _ffi.dptr(out)) else None
 
-    def _no_robust(self, what):
-        if self.robust is not None:
-            raise ValueError(_ROB_NOT_WITH.format(what))
-
     def set_continuum(self, tc):
         """The continuum brightness temperature behind the components, per (pixel, spectrum) (`check_continuum`'s argument:
         a number, [n_spec] or [n_pix, n_spec]), or none (None, zeros): nfa_specset_set_continuum.  null_lnZ() does not
         change: the null model has no absorber."""
-        tc = check_continuum(tc, self.n_spec, self.n_pix, self.model, self.calibration, self.correlation, self.response, self.templates)
-        if tc is not None:
-            self._no_robust('a continuum background (continuum)')
-        _ffi.check(_ffi.load().nfa_specset_set_continuum(self.handle, None if tc is None else _ffi.dptr(tc)))
-        self.continuum = tc
+        self._set('continuum', tc, model=self.model, n_pix=self.n_pix)
 
     def get_continuum(self):
         """The continuum as the engine holds it (nfa_specset_continuum): None, or float64 [n_pix, n_spec]."""
         out = np.zeros((self.n_pix, self.n_spec))
         return out if _ffi.load().nfa_specset_continuum(self.handle, _ffi.dptr(out)) else None
 
+    def _packed_templates(self, tmpl):
+        """The two arguments of nfa_specset_set_templates: the templates as [TMPL_MAX, chan_tot] and every spectrum's count."""
+        if tmpl is None:
+            return None, None
+        vals = np.zeros((TMPL_MAX, self.chan_tot))
+        counts = np.zeros(self.n_spec, dtype=np.int32)
+        for k, a in enumerate(tmpl):
+            if a is not None:
+                counts[k] = a.shape[0]
+                vals[:a.shape[0], self.offsets[k]:self.offsets[k + 1]] = a
+        return _ffi.dptr(vals), counts.ctypes.data_as(_ffi._ip)
+
     def set_templates(self, tmpl):
         """Nuisance templates per spectrum, profiled out of the likelihood with the baseline (`check_templates`'s argument),
         or none (None): nfa_specset_set_templates.  null_lnZ() then is the model of baseline and templates alone."""
-        tmpl = check_templates(tmpl, self.n_spec, self.sizes, self.calibration, self.correlation, self.response)
-        if tmpl is not None and self.continuum is not None:
-            raise ValueError('nuisance templates do not go with a continuum background (continuum)')
-        if tmpl is not None:
-            self._no_robust('nuisance templates (templates)')
-        if tmpl is None:
-            _ffi.check(_ffi.load().nfa_specset_set_templates(self.handle, None, None))
-        else:
-            vals = np.zeros((TMPL_MAX, self.chan_tot))
-            counts = np.zeros(self.n_spec, dtype=np.int32)
-            for k, a in enumerate(tmpl):
-                if a is not None:
-                    counts[k] = a.shape[0]
-                    vals[:a.shape[0], self.offsets[k]:self.offsets[k + 1]] = a
-            _ffi.check(_ffi.load().nfa_specset_set_templates(self.handle, _ffi.dptr(vals), counts.ctypes.data_as(_ffi._ip)))
-        self.templates = tmpl
+        self._set('templates', tmpl, self._packed_templates)
 
     def get_templates(self):
         """The templates as the engine holds them (nfa_specset_templates): None, or a list of n_spec entries, None or
@@ -800,78 +461,33 @@ class _SpecSet:
     def set_response(self, resp):
         """The channel response of the spectra (`check_response`'s argument), or none (None, the identity):
         nfa_specset_set_response.  null_lnZ() does not change."""
-        resp = check_response(resp, self.n_spec, self.sizes, self.masked, self.baseline_order, self.calibration)
-        if resp is not None and self.templates is not None:
-            raise ValueError('a channel response does not go with nuisance templates (templates)')
-        if resp is not None and self.continuum is not None:
-            raise ValueError('a channel response does not go with a continuum background (continuum)')
-        if resp is not None:
-            self._no_robust('a channel response (response)')
-        _ffi.check(_ffi.load().nfa_specset_set_response(self.handle, None if resp is None else _ffi.dptr(resp)))
-        self.response = resp
+        self._set('response', resp)
 
     def set_correlation(self, corr):
         """The autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis (`check_correlation`'s argument),
         or none (None, zeros): nfa_specset_set_correlation.  null_lnZ() follows."""
-        corr = check_correlation(corr, self.n_spec, self.sizes, self.masked, self.baseline_order, self.calibration)
-        corr = None if corr is None else np.ascontiguousarray(corr)
-        if corr is not None and self.templates is not None:
-            raise ValueError('a noise correlation does not go with nuisance templates (templates)')
-        if corr is not None and self.continuum is not None:
-            raise ValueError('a noise correlation does not go with a continuum background (continuum)')
-        if corr is not None:
-            self._no_robust('a noise correlation (correlation)')
-        _ffi.check(_ffi.load().nfa_specset_set_correlation(self.handle, None if corr is None else _ffi.dptr(corr)))
-        self.correlation = corr
+        self._set('correlation', corr)
 
     def set_noise_uncertainty(self, f):
         """The fractional uncertainty of every spectrum's noise level, integrated out of the likelihood
         (`check_noise_uncertainty`'s argument), or none (None, zeros): nfa_specset_set_noise_uncertainty.  null_lnZ()
         follows."""
-        f = check_noise_uncertainty(f, self.n_spec, self.calibration)
-        if f is not None:
-            self._no_robust('a noise uncertainty (noise_uncertainty)')
-        _ffi.check(_ffi.load().nfa_specset_set_noise_uncertainty(self.handle, None if f is None else _ffi.dptr(f)))
-        self.noise_uncertainty = f
+        self._set('noise_uncertainty', f)
 
     def set_calibration(self, cal):
         """A calibration uncertainty per spectrum, integrated out of the likelihood (`check_calibration`'s argument), or
         none (None, zeros): nfa_specset_set_calibration.  null_lnZ() does not change."""
-        cal = check_calibration(cal, self.n_spec)
-        if cal is not None and self.noise_uncertainty is not None:
-            raise ValueError(_NUNC_CALIB)
-        if cal is not None and self.response is not None:
-            raise ValueError('a calibration uncertainty does not go with a channel response (response)')
-        if cal is not None and self.correlation is not None:
-            raise ValueError('a calibration uncertainty does not go with a noise correlation (correlation)')
-        if cal is not None and self.templates is not None:
-            raise ValueError('a calibration uncertainty does not go with nuisance templates (templates)')
-        if cal is not None and self.continuum is not None:
-            raise ValueError('a calibration uncertainty does not go with a continuum background (continuum)')
-        if cal is not None:
-            self._no_robust('a calibration uncertainty (calibration)')
-        _ffi.check(_ffi.load().nfa_specset_set_calibration(self.handle, None if cal is None else _ffi.dptr(cal)))
-        self.calibration = cal
+        self._set('calibration', cal)
 
     def set_layered(self, on):
         """Layered transfer (True) or the summed model (False): nfa_specset_set_layered.  Layered, component 0 is the
         farthest from the observer and each component absorbs those behind it."""
-        on = check_layered(on)
-        _ffi.check(_ffi.load().nfa_specset_set_layered(self.handle, int(on)))
-        self.layered = on
+        self._set('layered', on, lambda v: (int(v),))
 
     def set_baseline(self, order):
         """A polynomial baseline of degree <= `order` per (pixel, spectrum) profiled out of the likelihood, or none
         (None / -1): nfa_specset_set_baseline.  null_lnZ() then is the baseline-only model's."""
-        order = check_baseline_order(order)
-        if order is not None and self.response is not None:
-            raise ValueError('a baseline does not go with a channel response (response)')
-        if order is not None and self.correlation is not None:
-            raise ValueError('a baseline does not go with a noise correlation (correlation)')
-        if order is not None:
-            self._no_robust('a baseline (baseline_order)')
-        _ffi.check(_ffi.load().nfa_specset_set_baseline(self.handle, -1 if order is None else order))
-        self.baseline_order = order
+        self._set('baseline_order', order, lambda v: (-1 if v is None else v,))
 
     def null_lnZ(self):
         out = np.empty((self.n_pix, self.n_spec))
@@ -978,63 +594,34 @@ class EngineSpectrumMixin:
         return np.array(self._pred)
 
 
+# the options an EngineRunner hands to its set through its own setter, which keeps null_lnZ (read right after set_baseline) and
+# the spectra's prefactors in step; `layered` and `calibration` go to the set itself
+RUNNER_SETS = ('baseline_order', 'correlation', 'response', 'templates', 'noise_uncertainty', 'continuum', 'robust')
+
+
+def apply_options(options, ss, runner=None):
+    """Hands the options of the record `options` that are on to the new spectra set `ss`, in APPLY_ORDER: through the set's
+    setters, or, with an EngineRunner `runner`, the RUNNER_SETS among them through the runner's."""
+    for name in APPLY_ORDER:
+        value = getattr(options, name)
+        if is_set(value):
+            owner = runner if runner is not None and name in RUNNER_SETS else ss
+            getattr(owner, 'set_' + name.replace('_order', ''))(value)
+
+
 class EngineRunner(Runner):
     """Runner attributes and methods common to the three models (reference:
     ammonia.pyx:369-447, diazenylium.pyx:161-231, gaussian.pyx:57-112)."""
     MODEL = MODEL_AMMONIA
     N_MODEL = 6
 
-    def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, baseline_order=None, layered=False,
-               calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None, continuum=None, robust=None):
-        """robust: None, or the degrees of freedom nu of Student-t channel noise -- a number for all spectra or one per
-        spectrum, each 0 (that spectrum stays Gaussian) or in [1, 1e6] -- so that an interference spike or an unflagged bad
-        channel costs the logarithm of its residual, not its square (nfa_specset_set_robust); 4 is a common
-        choice, `cubeio.estimate_tails` measures one.  With a scalar noise, a noise per channel, masked channels, `layered`
-        and filled sets; with none of the other likelihood options.  null_lnZ is the same expression at p = 0.
-        continuum: None, or the brightness temperature Tc >= 0 (K) of a continuum source behind all components -- a number
-        for all spectra or one per spectrum -- taken from the continuum map that was subtracted from the data: data, not a
-        parameter (nfa_specset_set_continuum).  The line then goes negative wherever J(tex) < J(Tcmb) + Tc.  All
-        zeros is None.  Not with the Gaussian model, a calibration, a correlation, a response or templates.  null_lnZ is
-        unchanged.  `predict` of such a runner goes through the runner's own spectra set, as for `layered`.
-        noise_uncertainty: None, or the fractional 1-sigma uncertainty of the spectra's noise levels -- a number for all of
-        them or one per spectrum, each in [0, 0.5] -- integrated out of the likelihood in closed form per spectrum
-        (nfa_specset_set_noise_uncertainty); all zeros is None.  Goes with everything but a calibration.
-        null_lnZ is then the same function of the parts at p = 0.
-        templates: None, or a list with one entry per spectrum, each None or an array [T, N_s] of 1..4 fixed shapes on the
-        spectrum's channels whose amplitudes are profiled out of the likelihood in closed form together with the baseline
-        (nfa_specset_set_templates): `ripple(n_chan, period)` for a standing wave of known period.  Not with a
-        calibration, a correlation or a response.  null_lnZ is then the model of baseline and templates alone.
-        response: None, or the channel response of the spectrometer -- 3 or 5 taps for all spectra (`HANNING_RESPONSE`) or
-        an array [n_spec, 3 | 5] -- with which the model is convolved before it meets the data (nfa_specset_set_response,
-        DESIGN 4.14); the identity is None.  Not with masked channels, a baseline or a calibration.  null_lnZ is unchanged.
-        correlation: None, or the first two autocorrelations (rho_1, rho_2) of the channel noise along the spectral axis -- a
-        pair for all spectra (`HANNING`, `ar1(rho)`) or an array [n_spec, 2] -- for cubes that were smoothed, regridded or
-        oversampled (nfa_specset_set_correlation); all zeros is None.  Not with masked channels, a baseline or a
-        calibration.  null_lnZ is then d^T Q d's, and the spectra's `prefactor` gains -ln det R / 2.
-        calibration: None, or the fractional 1-sigma uncertainty of the spectra's intensity scales -- a number for all of
-        them or one per spectrum, each in [0, 1] -- integrated out of the likelihood in closed form per spectrum
-        (nfa_specset_set_calibration); all zeros is None.  null_lnZ is unchanged.
-        layered: layered radiative transfer (nfa_specset_set_layered) -- the components are layers along the
-        line of sight, component 0 the farthest, and each absorbs those behind it; False: the components are summed.
-        `predict` of a layered runner goes through the runner's own spectra set (`_predict_layered`).
-        baseline_order: None, or 0..3 for a polynomial baseline of that degree per spectrum, profiled out of the
-        likelihood in closed form (nfa_specset_set_baseline).  null_lnZ is then the baseline-only model's, from
-        the runner's own spectra set (the spectra keep the reference's spectrum-alone value), and lnZ - null_lnZ is a Bayes
-        factor of baseline-marginalised models."""
+    def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, options=None):
+        """options: the mapping of the keywords that the runner's constructor took as `**options` -- the likelihood options
+        of its spectra set (see `_options` for each) and nothing else: any other key is the constructor's TypeError."""
         assert ncomp > 0
-        baseline_order = check_baseline_order(baseline_order)
-        layered = check_layered(layered, self.MODEL)
-        calibration = check_calibration(calibration, len(spectra))
-        noise_uncertainty = check_noise_uncertainty(noise_uncertainty, len(spectra), calibration)
-        check_correlation(correlation, len(spectra), [s.size for s in spectra],
-                          any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
-        check_response(response, len(spectra), [s.size for s in spectra],
-                       any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), baseline_order, calibration)
-        templates = check_templates(templates, len(spectra), [s.size for s in spectra], calibration,
-                                    check_correlation(correlation, len(spectra)), check_response(response, len(spectra)))
-        continuum = check_continuum(continuum, len(spectra), None, self.MODEL, calibration, correlation, response, templates)
-        robust = check_robust(robust, len(spectra), baseline_order, calibration, correlation, response, templates, noise_uncertainty,
-                              continuum)
+        options = check_options(options or {}, len(spectra), [s.size for s in spectra],
+                                any(np.ndim(s.noise) and not np.all(np.isfinite(s.noise)) for s in spectra), self.MODEL,
+                                caller=type(self).__init__.__qualname__)
         self.n_model = self.N_MODEL
         self.utrans = utrans
         self.ncomp = int(ncomp)
@@ -1057,27 +644,8 @@ class EngineRunner(Runner):
                             lines=[s.lines for s in spectra] if self.MODEL in (MODEL_HYPERFINE, MODEL_LTE) else None,
                             species=getattr(self, 'SPECIES', None), fill=getattr(self, 'FILL', False))
         self._run = _RunnerHandle(self._ss, utrans, self.ncomp, cold, lte)
-        self.layered = layered
-        if layered:
-            self._ss.set_layered(True)
-        self.baseline_order = baseline_order
-        if baseline_order is not None:
-            self._ss.set_baseline(baseline_order)
-            self.null_lnZ = float(self._ss.null_lnZ().sum())
-        if calibration is not None:
-            self._ss.set_calibration(calibration)
-        if correlation is not None:
-            self.set_correlation(correlation)
-        if response is not None:
-            self.set_response(response)
-        if templates is not None:
-            self.set_templates(templates)
-        if noise_uncertainty is not None:
-            self.set_noise_uncertainty(noise_uncertainty)
-        if continuum is not None:
-            self.set_continuum(continuum)
-        if robust is not None:
-            self.set_robust(robust)
+        self.layered, self.baseline_order = options.layered, options.baseline_order
+        apply_options(options, self._ss, self)
 
     @property
     def robust(self):

@@ -5,7 +5,7 @@ behaviour; all arithmetic runs in the HIP engine through the C ABI.
 import numpy as np
 
 from ._model import (MODEL_AMMONIA, EngineRunner, EngineSpectrumMixin, _pix_ptr, _RunnerHandle,  # noqa: F401
-                     _SpecSet, check_baseline_order, check_calibration, check_continuum, check_robust, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names)
+                     _SpecSet, check_options, spec_data_sizes_masked, par_names)
 from .core import HyperfineSpectrum
 
 N_LEVELS = 9
@@ -51,38 +51,20 @@ class AmmoniaRunner(EngineRunner):
     ncomp : int, number of velocity components
     cold : bool, Swift et al. (2005) Tkin -> Trot
     lte : bool, Tex = Trot
+    **options : the likelihood options of the spectra (`baseline_order`, `layered`, `calibration`, ...): see `_options`
     """
     MODEL = MODEL_AMMONIA
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None, robust=None):
-        assert ncomp > 0
-        baseline_order = check_baseline_order(baseline_order)
-        layered = check_layered(layered)
+    def __init__(self, spectra, utrans, ncomp=1, cold=False, lte=False, **options):
         self.spectra = list(spectra)
         self.cold = bool(cold)
         self.lte = bool(lte)
-        self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
+        self._setup(self.spectra, utrans, ncomp, self.cold, self.lte, options=options)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
-        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
-        check_layered(kwargs.get('layered', False))
-        check_calibration(kwargs.get('calibration'), len(spec_data))
-        check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
-        check_robust(kwargs.get('robust'), len(spec_data), kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
-                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
-        check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
-                        kwargs.get('response'), kwargs.get('templates'))
-        check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                          baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                       baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
-                        kwargs.get('correlation'), kwargs.get('response'))
+        check_options(kwargs, len(spec_data), *spec_data_sizes_masked(spec_data), model=cls.MODEL)     # before any device call
         spectra = np.array([AmmoniaSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._model import _RunnerHandle, _SpecSet, baseline_fit, check_baseline_order, check_calibration, check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_response, check_robust, check_templates, gain_fit, half_chi2, noise_fit, nuisance_fit, robust_outliers, signed_peak
+from ._model import _RunnerHandle, _SpecSet, apply_options, baseline_fit, check_options, gain_fit, half_chi2, noise_fit, nuisance_fit, robust_outliers, signed_peak
 from .core import _as_inplace_matrix
 
 
@@ -72,27 +72,18 @@ class CubeRunner:
     """
 
     def __init__(self, xarrs, trans_ids, data, noise, utrans, ncomp=1, cold=False, lte=False,
-                 model=0, rest_freqs=None, baseline_order=None, lines=None, species=None, fill=False, layered=False,
-                 calibration=None, correlation=None, response=None, templates=None, noise_uncertainty=None, continuum=None, robust=None):
+                 model=0, rest_freqs=None, *, lines=None, species=None, fill=False, **options):
         """model: 0 ammonia (default), 1 diazenylium, 2 gaussian (then `rest_freqs` = [Hz]), 3 hyperfine (then `lines` =
         one `LineTable` per spectrum; `trans_ids` is not used), 4 LTE (then `lines` = one `LteLines`, or one `LteBand` of several
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
         spectrum of the ordered `Molecule`s `species` -- without `species`, lines of several molecules take them in the order of
         their first appearance).  An LTE mix has 3 + len(species) parameters per component; fill: and a beam filling factor
-        as one more, the last (`LteMix(species, fill=True)`; one species included)."""
+        as one more, the last (`LteMix(species, fill=True)`; one species included).  options: the likelihood options above."""
         assert ncomp > 0
-        baseline_order = check_baseline_order(baseline_order)
-        layered = check_layered(layered, model)                      # before any device call
-        calibration = check_calibration(calibration, len(xarrs))
-        noise_uncertainty = check_noise_uncertainty(noise_uncertainty, len(xarrs), calibration)
         sizes = [np.size(x) for x in xarrs]
         masked = np.shape(noise)[-1] == sum(sizes) and not np.all(np.isfinite(noise))
-        correlation = check_correlation(correlation, len(xarrs), sizes, masked, baseline_order, calibration)
-        response = check_response(response, len(xarrs), sizes, masked, baseline_order, calibration)
-        templates = check_templates(templates, len(xarrs), sizes, calibration, correlation, response)
-        continuum = check_continuum(continuum, len(xarrs), int(np.shape(data)[0]), model, calibration, correlation, response, templates)
-        robust = check_robust(robust, len(xarrs), baseline_order, calibration, correlation, response, templates, noise_uncertainty,
-                              continuum)
+        options = check_options(options, len(xarrs), sizes, masked, model, int(np.shape(data)[0]),      # before any device call
+                                caller='CubeRunner.__init__')
         if species is None and int(model) == 4 and lines is not None:
             from .lte import LteBand, LteBlend, LteLines, lines_species
             lines = list(lines)
@@ -103,26 +94,8 @@ class CubeRunner:
         self._ss = _SpecSet(xarrs, trans_ids, data, noise, model=model, rest_freqs=rest_freqs, lines=lines, species=species,
                             fill=fill)
         self._run = _RunnerHandle(self._ss, utrans, ncomp, cold, lte)
-        self.layered = layered
-        if layered:
-            self._ss.set_layered(True)
-        self.baseline_order = baseline_order
-        if baseline_order is not None:
-            self._ss.set_baseline(baseline_order)
-        if calibration is not None:
-            self._ss.set_calibration(calibration)
-        if correlation is not None:
-            self._ss.set_correlation(correlation)
-        if response is not None:
-            self._ss.set_response(response)
-        if templates is not None:
-            self._ss.set_templates(templates)
-        if noise_uncertainty is not None:
-            self._ss.set_noise_uncertainty(noise_uncertainty)
-        if continuum is not None:
-            self._ss.set_continuum(continuum)
-        if robust is not None:
-            self._ss.set_robust(robust)
+        self.layered, self.baseline_order = options.layered, options.baseline_order
+        apply_options(options, self._ss)
         self._data, self._noise = data, noise                # (fit_baseline, fit_gain, fit_noise)
         self.utrans = utrans
         self.ncomp = int(ncomp)

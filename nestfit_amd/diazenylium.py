@@ -5,7 +5,7 @@ nestfit/models/hyperfine.pyx:52-118).  Parameters per component: voff, tex, ltau
 """
 import numpy as np
 
-from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_continuum, check_robust, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
+from ._model import MODEL_DIAZENYLIUM, EngineRunner, EngineSpectrumMixin, check_options, spec_data_sizes_masked, par_names
 from .core import HyperfineSpectrum
 
 N_LEVELS = 3
@@ -42,36 +42,18 @@ def nnhp_predict(s, params):
 
 
 class DiazenyliumRunner(EngineRunner):
-    """Prior transform + model + log-likelihood (reference: diazenylium.pyx:161-231)."""
+    """Prior transform + model + log-likelihood (reference: diazenylium.pyx:161-231).  **options: the likelihood options of
+    the spectra (`baseline_order`, `layered`, `calibration`, ...): see `_options`."""
     MODEL = MODEL_DIAZENYLIUM
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None, robust=None):
-        assert ncomp > 0
-        baseline_order = check_baseline_order(baseline_order)
-        layered = check_layered(layered)
+    def __init__(self, spectra, utrans, ncomp=1, **options):
         self.spectra = list(spectra)
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
+        self._setup(self.spectra, utrans, ncomp, options=options)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
-        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
-        check_layered(kwargs.get('layered', False))
-        check_calibration(kwargs.get('calibration'), len(spec_data))
-        check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
-        check_robust(kwargs.get('robust'), len(spec_data), kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
-                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
-        check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
-                        kwargs.get('response'), kwargs.get('templates'))
-        check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                          baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                       baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
-                        kwargs.get('correlation'), kwargs.get('response'))
+        check_options(kwargs, len(spec_data), *spec_data_sizes_masked(spec_data), model=cls.MODEL)     # before any device call
         spectra = np.array([DiazenyliumSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

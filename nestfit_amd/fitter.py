@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import sampler
-from ._model import check_calibration, check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_response, check_robust, check_templates
+from ._options import check_options
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
@@ -75,34 +75,17 @@ class CubeFitter:
         self.fill = bool(getattr(model, 'fill', False))  # ... and whether its components have a filling factor
         self.stack, self.utrans, self.runner_cls = stack, utrans, runner_cls
         self.runner_kwargs = dict(runner_kwargs or {})
-        # layered transfer (runner_kwargs['layered']): checked here, before any pixel is fitted
-        self.layered = check_layered(self.runner_kwargs.get('layered', False), self.model_id)
-        # a calibration uncertainty per spectrum (runner_kwargs['calibration']): checked here as well
-        cubes = getattr(stack, 'cubes', None)
-        self.calibration = check_calibration(self.runner_kwargs.get('calibration'), None if cubes is None else len(cubes))
-        # correlated channel noise (runner_kwargs['correlation']): and this
-        self.correlation = check_correlation(self.runner_kwargs.get('correlation'), None if cubes is None else len(cubes),
-                                             baseline_order=self.runner_kwargs.get('baseline_order'), calibration=self.calibration)
-        # a channel response (runner_kwargs['response']): and this
-        self.response = check_response(self.runner_kwargs.get('response'), None if cubes is None else len(cubes),
-                                       baseline_order=self.runner_kwargs.get('baseline_order'), calibration=self.calibration)
-        # nuisance templates (runner_kwargs['templates']): and these
-        self.templates = check_templates(self.runner_kwargs.get('templates'), None if cubes is None else len(cubes),
-                                         calibration=self.calibration, correlation=self.correlation, response=self.response)
-        # an uncertain noise level per spectrum (runner_kwargs['noise_uncertainty']): and this
-        self.noise_uncertainty = check_noise_uncertainty(self.runner_kwargs.get('noise_uncertainty'),
-                                                         None if cubes is None else len(cubes), self.calibration)
-        # a continuum background (DataCube(..., continuum=)): the cubes' maps, and what they do not go with
+        # the likelihood options among runner_kwargs (`_options`): checked here, before any pixel is fitted.  The continuum
+        # background comes from the cubes' maps (DataCube(..., continuum=)) and is checked as one that is on.
         if self.runner_kwargs.get('continuum') is not None:
             raise ValueError("the continuum of a cube fit comes from its cubes (DataCube(..., continuum=)), not from runner_kwargs")
         self.continuum = getattr(stack, 'continuum_maps', lambda: None)()
-        if self.continuum is not None and np.any(np.nan_to_num(self.continuum) > 0.0):
-            check_continuum(1.0, None, None, self.model_id, self.calibration, self.correlation, self.response, self.templates)
-        # a robust likelihood (runner_kwargs['robust']): and this, with everything it does not go with
-        self.robust = check_robust(self.runner_kwargs.get('robust'), None if cubes is None else len(cubes),
-                                   self.runner_kwargs.get('baseline_order'), self.calibration, self.correlation, self.response,
-                                   self.templates, self.noise_uncertainty,
-                                   None if self.continuum is None else np.nan_to_num(self.continuum))
+        has_continuum = self.continuum is not None and np.any(np.nan_to_num(self.continuum) > 0.0)
+        cubes = getattr(stack, 'cubes', None)
+        options = check_options({**self.runner_kwargs, 'continuum': 1.0 if has_continuum else None},
+                                None if cubes is None else len(cubes), model=self.model_id)
+        for name in ('layered', 'calibration', 'correlation', 'response', 'templates', 'noise_uncertainty', 'robust'):
+            setattr(self, name, getattr(options, name))
         self.mn_kwargs = {**MN_CUBE_DEFAULTS, **(mn_kwargs or {})}
         self.lnZ_thresh, self.ncomp_max, self.nlive_snr_fact = lnZ_thresh, ncomp_max, nlive_snr_fact
         self.nlive_quantum = max(1, int(nlive_quantum))

@@ -7,7 +7,7 @@ radiative-transfer pass.
 import numpy as np
 
 from . import core
-from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_continuum, check_robust, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
+from ._model import MODEL_GAUSSIAN, EngineRunner, EngineSpectrumMixin, check_options, spec_data_sizes_masked, par_names
 
 N_PARAMS = 3
 
@@ -29,36 +29,18 @@ def gauss_predict(s, params):
 
 class GaussianRunner(EngineRunner):
     """Prior transform + model + log-likelihood for one spectrum (reference:
-    gaussian.pyx:57-112)."""
+    gaussian.pyx:57-112).  **options: the likelihood options of the spectrum (`baseline_order`, `calibration`, ...): see
+    `_options`; no `layered=True` and no `continuum`: the model has no optical depth, nothing absorbs."""
     MODEL = MODEL_GAUSSIAN
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectrum, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None, robust=None):
-        assert ncomp > 0
-        baseline_order = check_baseline_order(baseline_order)
-        check_layered(layered, MODEL_GAUSSIAN)                        # ValueError for True: no optical depth, nothing absorbs
+    def __init__(self, spectrum, utrans, ncomp=1, **options):
         self.spectrum = spectrum
-        self._setup([spectrum], utrans, ncomp, rest_freqs=[float(spectrum.rest_freq)], baseline_order=baseline_order,
-                    calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
+        self._setup([spectrum], utrans, ncomp, rest_freqs=[float(spectrum.rest_freq)], options=options)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
-        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
-        check_layered(kwargs.get('layered', False), MODEL_GAUSSIAN)
-        check_calibration(kwargs.get('calibration'), 1)
-        check_noise_uncertainty(kwargs.get('noise_uncertainty'), 1, kwargs.get('calibration'))
-        check_robust(kwargs.get('robust'), 1, kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
-                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
-        check_continuum(kwargs.get('continuum'), 1, None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
-                        kwargs.get('response'), kwargs.get('templates'))
-        check_correlation(kwargs.get('correlation'), 1, *spec_data_sizes_masked([spec_data]),
-                          baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_response(kwargs.get('response'), 1, *spec_data_sizes_masked([spec_data]),
-                       baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_templates(kwargs.get('templates'), 1, spec_data_sizes_masked([spec_data])[0], kwargs.get('calibration'),
-                        kwargs.get('correlation'), kwargs.get('response'))
+        check_options(kwargs, 1, *spec_data_sizes_masked([spec_data]), model=cls.MODEL)                # before any device call
         return cls(Spectrum(*spec_data), utrans, **kwargs)
 
     def get_spectrum(self):

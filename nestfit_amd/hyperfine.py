@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _ffi
 from ._model import (MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, EngineRunner, EngineSpectrumMixin,
-                     check_baseline_order, check_calibration, check_continuum, check_robust, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names)
+                     check_options, spec_data_sizes_masked, par_names)
 from .core import HyperfineSpectrum as _HyperfineBase
 
 N_PARAMS = 4
@@ -129,37 +129,19 @@ def hf_predict(s, params):
 
 
 class HyperfineRunner(EngineRunner):
-    """Prior transform + model + log-likelihood of spectra with a `LineTable` each."""
+    """Prior transform + model + log-likelihood of spectra with a `LineTable` each.  **options: the likelihood options of the
+    spectra (`baseline_order`, `layered`, `calibration`, ...): see `_options`."""
     MODEL = MODEL_HYPERFINE
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None, robust=None):
-        assert ncomp > 0
-        baseline_order = check_baseline_order(baseline_order)
-        layered = check_layered(layered)
+    def __init__(self, spectra, utrans, ncomp=1, **options):
         self.spectra = list(spectra)
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
+        self._setup(self.spectra, utrans, ncomp, options=options)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         """spec_data: rows [xarr, data, noise, LineTable]."""
-        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
-        check_layered(kwargs.get('layered', False))
-        check_calibration(kwargs.get('calibration'), len(spec_data))
-        check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
-        check_robust(kwargs.get('robust'), len(spec_data), kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
-                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
-        check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
-                        kwargs.get('response'), kwargs.get('templates'))
-        check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                          baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                       baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
-                        kwargs.get('correlation'), kwargs.get('response'))
+        check_options(kwargs, len(spec_data), *spec_data_sizes_masked(spec_data), model=cls.MODEL)     # before any device call
         spectra = np.array([HyperfineSpectrum(*args) for args in spec_data])
         return cls(spectra, utrans, **kwargs)
 

@@ -47,7 +47,8 @@ function come from a catalogue of the user's.
 """
 import numpy as np
 
-from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_baseline_order, check_calibration, check_continuum, check_robust, check_correlation, check_noise_uncertainty, check_layered, check_response, check_templates, spec_data_sizes_masked, par_names
+from ._model import MODEL_LTE, EngineRunner, EngineSpectrumMixin, check_options, spec_data_sizes_masked, par_names
+from ._options import refuse_unknown
 from .core import HyperfineSpectrum as _HyperfineBase
 from .hyperfine import CKMS, MAX_LINES, LineTable
 
@@ -401,38 +402,21 @@ def lte_predict(s, params):
 
 
 class LteRunner(EngineRunner):
-    """Prior transform + model + log-likelihood of spectra with an `LteLines` or an `LteBand` each, all of one `Molecule`."""
+    """Prior transform + model + log-likelihood of spectra with an `LteLines` or an `LteBand` each, all of one `Molecule`.
+    **options: the likelihood options of the spectra (`baseline_order`, `layered`, `calibration`, ...): see `_options`."""
     MODEL = MODEL_LTE
     N_MODEL = N_PARAMS
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None, robust=None):
-        assert ncomp > 0
-        baseline_order = check_baseline_order(baseline_order)
-        layered = check_layered(layered)
+    def __init__(self, spectra, utrans, ncomp=1, **options):
+        refuse_unknown(options, 'LteRunner.__init__')        # (a keyword it does not take: before it looks at the lines)
         self.spectra = list(spectra)
         self.molecule = check_one_molecule([s.lines for s in self.spectra])
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
+        self._setup(self.spectra, utrans, ncomp, options=options)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         """spec_data: rows [xarr, data, noise, LteLines or LteBand]."""
-        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
-        check_layered(kwargs.get('layered', False))
-        check_calibration(kwargs.get('calibration'), len(spec_data))
-        check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
-        check_robust(kwargs.get('robust'), len(spec_data), kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
-                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
-        check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
-                        kwargs.get('response'), kwargs.get('templates'))
-        check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                          baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                       baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
-                        kwargs.get('correlation'), kwargs.get('response'))
+        check_options(kwargs, len(spec_data), *spec_data_sizes_masked(spec_data), model=cls.MODEL)     # before any device call
         spec_data = list(spec_data)
         check_one_molecule([row[3] for row in spec_data])
         spectra = np.array([LteSpectrum(*args) for args in spec_data])
@@ -551,39 +535,22 @@ class _MixSpectrum(EngineSpectrumMixin, _HyperfineBase):
 
 
 class _MixRunner(EngineRunner):
-    """Prior transform + model + log-likelihood of the spectra of an `LteMix` (its `Runner`)."""
+    """Prior transform + model + log-likelihood of the spectra of an `LteMix` (its `Runner`).  **options: the likelihood
+    options of the spectra (`baseline_order`, `layered`, `calibration`, ...): see `_options`."""
     MODEL = MODEL_LTE
     MIX = None
 
-    def __init__(self, spectra, utrans, ncomp=1, baseline_order=None, layered=False, calibration=None, correlation=None, response=None, templates=None,
-                 noise_uncertainty=None, continuum=None, robust=None):
-        assert ncomp > 0
-        baseline_order = check_baseline_order(baseline_order)
-        layered = check_layered(layered)
+    def __init__(self, spectra, utrans, ncomp=1, **options):
+        refuse_unknown(options, '_MixRunner.__init__')
         self.spectra = list(spectra)
         check_mix_lines(self.MIX.species, [s.lines for s in self.spectra])
         self.species = self.MIX.species
-        self._setup(self.spectra, utrans, ncomp, baseline_order=baseline_order, layered=layered,
-                    calibration=calibration, correlation=correlation, response=response, templates=templates,
-                    noise_uncertainty=noise_uncertainty, continuum=continuum, robust=robust)
+        self._setup(self.spectra, utrans, ncomp, options=options)
 
     @classmethod
     def from_data(cls, spec_data, utrans, **kwargs):
         """spec_data: rows [xarr, data, noise, LteLines | LteBand | LteBlend]."""
-        check_baseline_order(kwargs.get('baseline_order'))            # before any device call
-        check_layered(kwargs.get('layered', False))
-        check_calibration(kwargs.get('calibration'), len(spec_data))
-        check_noise_uncertainty(kwargs.get('noise_uncertainty'), len(spec_data), kwargs.get('calibration'))
-        check_robust(kwargs.get('robust'), len(spec_data), kwargs.get('baseline_order'), kwargs.get('calibration'), kwargs.get('correlation'),
-                     kwargs.get('response'), kwargs.get('templates'), kwargs.get('noise_uncertainty'), kwargs.get('continuum'))
-        check_continuum(kwargs.get('continuum'), len(spec_data), None, cls.MODEL, kwargs.get('calibration'), kwargs.get('correlation'),
-                        kwargs.get('response'), kwargs.get('templates'))
-        check_correlation(kwargs.get('correlation'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                          baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_response(kwargs.get('response'), len(spec_data), *spec_data_sizes_masked(spec_data),
-                       baseline_order=kwargs.get('baseline_order'), calibration=kwargs.get('calibration'))
-        check_templates(kwargs.get('templates'), len(spec_data), spec_data_sizes_masked(spec_data)[0], kwargs.get('calibration'),
-                        kwargs.get('correlation'), kwargs.get('response'))
+        check_options(kwargs, len(spec_data), *spec_data_sizes_masked(spec_data), model=cls.MODEL)     # before any device call
         spec_data = list(spec_data)
         check_mix_lines(cls.MIX.species, [row[3] for row in spec_data])
         spectra = np.array([cls.MIX.Spectrum(*args) for args in spec_data])

@@ -24,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import hdf5
-from ._model import check_calibration, check_correlation, check_noise_uncertainty, check_response, check_robust, check_templates
+from ._options import normalise
 
 HDF5_SUFFIXES = ('.hdf', '.h5', '.hdf5')
 
@@ -423,50 +423,36 @@ class HdfStore:
         self.hdf.attrs.update({name: get(fitter) for name, get in FITTER_ATTRS})
         # the built-in sampler's named setting (sampler.PRECISION: margins of its bound's free rejections), where the results are
         self.hdf.attrs['sampler_precision'] = str(getattr(fitter, 'mn_kwargs', {}).get('precision') or 'default')
+        kwargs = getattr(fitter, 'runner_kwargs', None) or {}
         # the polynomial baseline profiled out of the likelihood (runner_kwargs['baseline_order']), -1 for none;
         # a store without the attribute was fitted without one
-        order = (getattr(fitter, 'runner_kwargs', None) or {}).get('baseline_order')
+        order = kwargs.get('baseline_order')
         self.hdf.attrs['baseline_order'] = -1 if order is None else int(order)
         # layered radiative transfer (runner_kwargs['layered']): root attribute `layered`.  A store without it
         # was fitted with summed components.
-        if (getattr(fitter, 'runner_kwargs', None) or {}).get('layered', False):
+        if kwargs.get('layered', False):
             self.hdf.attrs['layered'] = True
-        # a calibration uncertainty per spectrum integrated out of the likelihood (runner_kwargs['calibration']):
-        # root attribute `calibration`, float64 [n_spec].  A store without it was fitted without one.
+        # the options that are arrays per spectrum, normalised (`_options.normalise`), each under a root attribute; a store
+        # without one was fitted without that option:
+        #   calibration        `calibration`, float64 [n_spec]
+        #   correlation        `noise_correlation`, float64 [n_spec, 2], the pairs (rho_1, rho_2)
+        #   response           `channel_response`, float64 [n_spec, 5], the taps h_-2 .. h_2
+        #   templates          root group `nuisance_templates`, one float64 dataset spec<k> [T, n_chan] per
+        #                                    spectrum that has any
+        #   noise_uncertainty  `noise_uncertainty`, float64 [n_spec]
+        #   robust             `robust_dof`, float64 [n_spec], the degrees of freedom of the Student-t noise
         cubes = getattr(getattr(fitter, 'stack', None), 'cubes', None)
-        cal = check_calibration((getattr(fitter, 'runner_kwargs', None) or {}).get('calibration'), None if cubes is None else len(cubes))
-        if cal is not None:
-            self.hdf.attrs['calibration'] = cal
-        # channel noise correlated along the spectral axis (runner_kwargs['correlation']): root attribute
-        # `noise_correlation`, float64 [n_spec, 2], the pairs (rho_1, rho_2).  A store without it was fitted with white noise.
-        corr = check_correlation((getattr(fitter, 'runner_kwargs', None) or {}).get('correlation'), None if cubes is None else len(cubes))
-        if corr is not None:
-            self.hdf.attrs['noise_correlation'] = corr
-        # a channel response (runner_kwargs['response']): root attribute `channel_response`, float64 [n_spec, 5],
-        # the taps h_-2 .. h_2.  A store without it was fitted with the model at the channel centres.
-        resp = check_response((getattr(fitter, 'runner_kwargs', None) or {}).get('response'), None if cubes is None else len(cubes))
-        if resp is not None:
-            self.hdf.attrs['channel_response'] = resp
-        # nuisance templates (runner_kwargs['templates']): root group `nuisance_templates`, one float64 dataset
-        # spec<k> [T, n_chan] per spectrum that has any.  A store without the group was fitted without templates.
-        tmpl = check_templates((getattr(fitter, 'runner_kwargs', None) or {}).get('templates'), None if cubes is None else len(cubes))
-        if tmpl is not None:
-            group = self.hdf.create_group('nuisance_templates')
-            group.attrs['n_spec'] = len(tmpl)
-            for k, a in enumerate(tmpl):
-                if a is not None:
-                    group.create_dataset(f'spec{k}', data=a)
-        # an uncertain noise level per spectrum integrated out of the likelihood (runner_kwargs['noise_uncertainty'], DESIGN
-        # 4.16): root attribute `noise_uncertainty`, float64 [n_spec].  A store without it was fitted with the noise as given.
-        nunc = check_noise_uncertainty((getattr(fitter, 'runner_kwargs', None) or {}).get('noise_uncertainty'),
-                                       None if cubes is None else len(cubes))
-        if nunc is not None:
-            self.hdf.attrs['noise_uncertainty'] = nunc
-        # a robust likelihood (runner_kwargs['robust']): root attribute `robust_dof`, float64 [n_spec], the degrees
-        # of freedom of the Student-t channel noise.  A store without it was fitted with Gaussian noise.
-        rob = check_robust((getattr(fitter, 'runner_kwargs', None) or {}).get('robust'), None if cubes is None else len(cubes))
-        if rob is not None:
-            self.hdf.attrs['robust_dof'] = rob
+        for name, attr in (('calibration', 'calibration'), ('correlation', 'noise_correlation'), ('response', 'channel_response'),
+                           ('templates', None), ('noise_uncertainty', 'noise_uncertainty'), ('robust', 'robust_dof')):
+            value = normalise(name, kwargs.get(name), None if cubes is None else len(cubes))
+            if value is not None and attr is not None:
+                self.hdf.attrs[attr] = value
+            elif value is not None:
+                group = self.hdf.create_group('nuisance_templates')
+                group.attrs['n_spec'] = len(value)
+                for k, a in enumerate(value):
+                    if a is not None:
+                        group.create_dataset(f'spec{k}', data=a)
         # a continuum background behind the components (DataCube(..., continuum=)): root dataset
         # `model_continuum`, float64 (t, b, l) like the per-spectrum map products, in K, NaN where a map has none.  A store
         # without it was fitted against the cosmic background alone.
