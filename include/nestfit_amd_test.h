@@ -49,6 +49,11 @@ int nfa_test_queue_trace_read(unsigned long long *out);
  * reset != 0: the counts are cleared as they are read. */
 int nfa_test_lnl_launches(int64_t *out, int reset);
 
+/* An option key of this library's nfa_set_option alone, like "ablate" (the product library refuses both):
+ * "fail_alloc", k > 0 -- the k-th allocation from now of a buffer that a likelihood option of a spectra set needs (the
+ * nfa_specset_set_* calls of this library) fails, once: the call returns NFA_ERR_DEVICE with its out-of-memory message, on
+ * the host -- the device is asked for nothing.  k = 0 disarms.  No entry point of its own. */
+
 #ifdef __cplusplus
 }
 #endif

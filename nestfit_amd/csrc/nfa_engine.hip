@@ -27,6 +27,7 @@
 #include "n2hp_data.h"
 #include "nfa_device.h"
 #include "nfa_set_rules.h"
+#include "nfa_set_state.h"
 
 // ---------------------------------------------------------------------------
 //  error plumbing
@@ -200,6 +201,14 @@ static int engine_init_once() {
     return NFA_OK;
 }
 
+// A set's likelihood options: the per-spectrum part (nfa_set_state.h) and the two large arrays, empty where the option is off
+struct SetRecord {
+    SetOptions o;
+    std::vector<double> tmpl;                       // the caller's templates [NFA_TMPL_MAX][chan_tot], unused slots zero
+    std::vector<double> cont;                       // the caller's continuum [n_pix][n_spec]
+};
+static_assert(SET_RESP_NT == NFA_RESP_NT, "nfa_set_state.h keeps the taps of a response");
+
 struct nfa_specset {
     SpecDev dev{};
     int64_t n_pix = 0;
@@ -215,34 +224,57 @@ struct nfa_specset {
     int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
     bool    filled = false;                         // an LTE set with a beam filling factor per component: the last parameter
     bool    layered = false;                        // layered transfer: a component absorbs those behind it (nfa_specset_set_layered)
-    bool    bl_w1 = false;                          // a baseline or a calibration on a scalar noise: d_w (== 1) and d_wdata were made for it
-    double *d_cal2 = nullptr;                       // a calibration uncertainty: SpecDev.cal2 (nfa_specset_set_calibration)
-    double  h_cal[MAXSPEC] = {};                    // ... the caller's fractional 1-sigma values
-    bool    masked = false;                         // a noise per channel with a masked channel (w = 0) somewhere
-    // correlated channel noise (nfa_specset_set_correlation): Q's diagonal (SpecDev.chan_w while it lasts; d_w keeps u^2) and
-    // off-diagonals, the entries of R^-1 per spectrum, the caller's (rho_1, rho_2)
-    double *d_q0 = nullptr, *d_q1 = nullptr, *d_q2 = nullptr, *d_corr = nullptr;
-    double  h_rho[MAXSPEC][2] = {};
-    bool    corr_w1 = false;                        // ... on a scalar noise: d_w (== 1) and d_wdata were made for it
-    bool    has_corr = false;                       // ... some pair is not (0, 0): Q's arrays also serve a response alone, over white entries
-    // a channel response (nfa_specset_set_response): SpecDev.resp and the caller's taps
-    double *d_resp = nullptr;
-    double  h_resp[MAXSPEC][NFA_RESP_NT] = {};
-    // nuisance templates (nfa_specset_set_templates): SpecDev.tmpl (scaled) and .tp, the caller's values and counts
-    double *d_tmpl = nullptr, *d_tp = nullptr;
-    std::vector<double> h_tmpl;                     // [NFA_TMPL_MAX][chan_tot], unused slots zero; empty without templates
-    int     h_ntmpl[MAXSPEC] = {};
-    // an uncertain noise level (nfa_specset_set_noise_uncertainty): SpecDev.nmarg and the caller's fractional 1-sigma values
-    double *d_nmarg = nullptr;
-    double  h_nunc[MAXSPEC] = {};
-    // a continuum background (nfa_specset_set_continuum): SpecDev.cont and the caller's values [n_pix][n_spec]; empty without
-    double *d_cont = nullptr;
-    std::vector<double> h_cont;
-    // a robust likelihood (nfa_specset_set_robust): g and g d (SpecDev.chan_w and .wdata while it lasts; d_w and d_wdata keep
-    // the set's own), SpecDev.rob and the caller's degrees of freedom
+    bool    chan_noise = false;                     // a noise per channel: d_w and d_wdata are the set's from its creation
+    bool    masked = false;                         // ... with a masked channel (w = 0) somewhere
+    // The likelihood options as the caller gave them (the nfa_specset_set_* calls): "is option X on" is a question to this
+    // record.  The buffers below are what set_layout (nfa_set_state.h) makes of it, kept so by specset_realise alone.
+    SetRecord opt;
+    double *d_cal2 = nullptr;                       // a calibration uncertainty: SpecDev.cal2
+    // correlated channel noise or a channel response: Q's diagonal (SpecDev.chan_w while it lasts; d_w keeps u^2) and
+    // off-diagonals, the entries of R^-1 per spectrum (white without a correlation); SpecDev.resp
+    double *d_q0 = nullptr, *d_q1 = nullptr, *d_q2 = nullptr, *d_corr = nullptr, *d_resp = nullptr;
+    double *d_tmpl = nullptr, *d_tp = nullptr;      // nuisance templates: SpecDev.tmpl (scaled) and .tp
+    double *d_nmarg = nullptr;                      // an uncertain noise level: SpecDev.nmarg
+    double *d_cont = nullptr;                       // a continuum background: SpecDev.cont
+    // a robust likelihood: g and g d (SpecDev.chan_w and .wdata while it lasts; d_w and d_wdata keep the set's own), SpecDev.rob
     double *d_rg = nullptr, *d_rgd = nullptr, *d_rob = nullptr;
-    double  h_rob[MAXSPEC] = {};
 };
+// The option-dependent buffers of a set: specset_realise allocates and frees through this list, nfa_specset_destroy frees
+// through it.  (Doubles all of them; the message is what a failed allocation says.)
+static const char OOM_WEIGHTS[] = "out of device memory for the channel weights";
+struct SetBuf { unsigned bit; double *nfa_specset::*p; const char *oom; };
+static const SetBuf SET_BUFS[SB_N] = {
+    {SB_W, &nfa_specset::d_w, OOM_WEIGHTS}, {SB_WDATA, &nfa_specset::d_wdata, OOM_WEIGHTS},
+    {SB_BL, &nfa_specset::d_bl, "out of device memory for the baseline records"},
+    {SB_TP, &nfa_specset::d_tp, "out of device memory for the templates' records"},
+    {SB_CAL2, &nfa_specset::d_cal2, "out of device memory for the calibration uncertainties"},
+    {SB_NMARG, &nfa_specset::d_nmarg, "out of device memory for the noise uncertainties' records"},
+    {SB_Q0, &nfa_specset::d_q0, "out of device memory for the correlated weights"},
+    {SB_Q1, &nfa_specset::d_q1, "out of device memory for the correlated weights"},
+    {SB_Q2, &nfa_specset::d_q2, "out of device memory for the correlated weights"},
+    {SB_CORR, &nfa_specset::d_corr, "out of device memory for the correlation's coefficients"},
+    {SB_RESP, &nfa_specset::d_resp, "out of device memory for the channel response"},
+    {SB_TMPL, &nfa_specset::d_tmpl, "out of device memory for the templates"},
+    {SB_CONT, &nfa_specset::d_cont, "out of device memory for the continuum"},
+    {SB_RG, &nfa_specset::d_rg, "out of device memory for the robust weights"},
+    {SB_RGD, &nfa_specset::d_rgd, "out of device memory for the robust weights"},
+    {SB_ROB, &nfa_specset::d_rob, "out of device memory for the robust records"},
+};
+static size_t set_buf_doubles(const nfa_specset *ss, unsigned bit) {
+    const SpecDev &d = ss->dev;
+    const size_t spec = (size_t)(ss->n_pix * d.n_spec);
+    switch (bit) {
+    case SB_BL: return NFA_BL_REC * spec;
+    case SB_TP: return NFA_TP_REC * spec;
+    case SB_CAL2: return (size_t)d.n_spec;
+    case SB_NMARG: case SB_ROB: return 2 * spec;
+    case SB_CORR: return NFA_CORR_NC * MAXSPEC;
+    case SB_RESP: return NFA_RESP_NT * MAXSPEC;
+    case SB_TMPL: return NFA_TMPL_MAX * (size_t)d.chan_tot;
+    case SB_CONT: return spec;
+    default: return (size_t)(ss->n_pix * d.chan_tot);      // per channel, like the data
+    }
+}
 
 struct nfa_priors {
     PriorProg prog{};
@@ -313,6 +345,11 @@ static LpLaunch plan_launch(const nfa_runner *r, int64_t B, int mode, bool write
     return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl_order >= 0 || r->ss->dev.cont != nullptr,
                     r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr, r->ss->filled, r->ss->layered, r->ss->dev.cal2 != nullptr};
 }
+#ifdef NFA_TEST_HOOKS
+// nfa_testhooks.h: the test library's option "fail_alloc" arms set_alloc's k-th call from now to fail, once
+static void test_fail_alloc(int k);
+static bool test_alloc_fails();
+#endif
 
 extern "C" {
 
@@ -397,6 +434,9 @@ int nfa_set_option(const char *key, int value) {
     if (key && !strcmp(key, "wpb") && value >= 1 && value <= 16) { g_eng.wpb = value; return NFA_OK; }
 #ifdef NFA_ABLATE
     if (key && !strcmp(key, "ablate") && value >= 0 && value <= 127) { g_eng.ablate = value; return NFA_OK; }
+#endif
+#ifdef NFA_TEST_HOOKS
+    if (key && !strcmp(key, "fail_alloc") && value >= 0) { test_fail_alloc(value); return NFA_OK; }
 #endif
     if (key && !strcmp(key, "streams") && value >= 0 && value <= NFA_MAX_LANES) { g_eng.streams = value; return NFA_OK; }
     return fail(NFA_ERR_ARG, "unknown option, or value out of range");
@@ -572,11 +612,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
     HIP_TRY(hipGetLastError());
     d.xarr = ss->d_xarr; d.t0 = ss->d_t0; d.tbg = ss->d_tbg; d.data = ss->d_data; d.noise = ss->d_noise;
     d.t0tbg = ss->d_t0tbg; d.rowsq = ss->d_rowsq; d.totsq = ss->d_totsq;
-    d.bl = nullptr; d.bl_order = -1;                                    // no baseline (nfa_specset_set_baseline)
-    d.cal2 = nullptr;                                                   // no calibration uncertainty (nfa_specset_set_calibration)
-    d.tmpl = d.tp = nullptr;                                            // no nuisance templates (nfa_specset_set_templates)
-    d.cont = nullptr;                                                   // no continuum background (nfa_specset_set_continuum)
-    d.rob = nullptr;                                                    // no robust likelihood (nfa_specset_set_robust)
+    d.bl_order = ss->opt.o.bl_order;                                    // no option yet (the nfa_specset_set_* calls): their pointers stay null
     HIP_TRY(hipMalloc(&ss->d_lines, sizeof(LineRow) * n_spec));
     HIP_TRY(hipMemcpy(ss->d_lines, h_lines.data(), sizeof(LineRow) * n_spec, hipMemcpyHostToDevice));
     d.lines = ss->d_lines;
@@ -600,6 +636,7 @@ static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *s
         HIP_TRY(hipMalloc(&ss->d_wdata, sizeof(double) * tot * n_pix));
         HIP_TRY(hipMemcpy(ss->d_w, chan_noise, sizeof(double) * tot * n_pix, hipMemcpyHostToDevice));
         d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
+        ss->chan_noise = true;
         int rc = launch_chan_weight(ss, 0, n_pix, true); if (rc) return rc;
     }
     return launch_rowsq(ss, 0, n_pix);
@@ -990,38 +1027,15 @@ int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double 
 int nfa_specset_destroy(nfa_specset *ss) {
     if (!ss) return NFA_OK;
     (void)hipFree(ss->d_xarr); (void)hipFree(ss->d_t0); (void)hipFree(ss->d_tbg); (void)hipFree(ss->d_data); (void)hipFree(ss->d_noise);
-    (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq);
-    (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata); (void)hipFree(ss->d_bl); (void)hipFree(ss->d_lines);
-    (void)hipFree(ss->d_cal2);
-    (void)hipFree(ss->d_q0); (void)hipFree(ss->d_q1); (void)hipFree(ss->d_q2); (void)hipFree(ss->d_corr);
-    (void)hipFree(ss->d_resp);
-    (void)hipFree(ss->d_tmpl); (void)hipFree(ss->d_tp);
-    (void)hipFree(ss->d_nmarg);
-    (void)hipFree(ss->d_cont);
-    (void)hipFree(ss->d_rg); (void)hipFree(ss->d_rgd); (void)hipFree(ss->d_rob);
+    (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq); (void)hipFree(ss->d_lines);
+    for (const SetBuf &b : SET_BUFS) (void)hipFree(ss->*b.p);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
     delete ss;
     return NFA_OK;
 }
 
-static int rob_form(nfa_specset *ss, int64_t pix0, int64_t n, const double *nu);
-
-int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data) {
-    if (!ss || !data || pix < 0 || pix >= ss->n_pix) return fail(NFA_ERR_ARG, "bad pixel index");
-    int rc = engine_init(); if (rc) return rc;
-    HIP_TRY(hipMemcpy(ss->d_data + pix * ss->dev.chan_tot, data, sizeof(double) * ss->dev.chan_tot,
-                      hipMemcpyHostToDevice));
-    if (ss->dev.rob) return rob_form(ss, pix, 1, ss->h_rob);                                     // the set's own w d and sums, then g, g d and C
-    if (ss->dev.corr_q1) { rc = launch_corr_setup(ss, pix, 1, false); if (rc) return rc; }      // Q stays, Q d again
-    else if (ss->dev.chan_w) { rc = launch_chan_weight(ss, pix, 1, false); if (rc) return rc; }      // the mask stays
-    rc = launch_rowsq(ss, pix, 1); if (rc) return rc;
-    if (ss->dev.bl) { rc = launch_bl_setup(ss, pix, 1, false); if (rc) return rc; }              // the basis stays
-    return ss->dev.tp ? launch_tmpl_setup(ss, pix, 1, false) : NFA_OK;                           // ... and the templates' too
-}
-
-// What nfa_specset_set_baseline and nfa_specset_set_calibration do before they change a set: held batches were accepted for
-// the old likelihood, launches in flight read the buffers changed there, and a runner's captured single-point graph holds
-// the old SpecDev
+// What the nfa_specset_set_* calls do before they change a set: held batches were accepted for the old likelihood, launches
+// in flight read the buffers changed there, and a runner's captured single-point graph holds the old SpecDev
 static int specset_quiesce(nfa_specset *ss) {
     int rc = flush_all_runners(); if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
@@ -1031,186 +1045,8 @@ static int specset_quiesce(nfa_specset *ss) {
     return NFA_OK;
 }
 
-// The weighted arrays and the baseline records as the set's baseline order and calibration ask for them, whichever of the
-// two setters changed last: both run the baseline form (a scalar noise with w == 1; a calibrated set without
-// a baseline with a zeroed record: bl_setup_kernel leaves L^-1 = 0 for order -1 and m(d) as it is), neither needs them.
-// Nuisance templates (SpecDev.tmpl set by nfa_specset_set_templates) run the same weighted form and keep records of their own
-// (SpecDev.tp) beside the baseline's, formed here for the same reason.
-// A continuum background (SpecDev.cont set by nfa_specset_set_continuum) runs the baseline form like a calibration.
-static int specset_form_records(nfa_specset *ss) {
-    SpecDev &d = ss->dev;
-    const bool want_bl = d.bl_order >= 0 || d.cal2 || d.cont, want_tp = d.tmpl != nullptr;
-    if (!want_tp) {
-        (void)hipFree(ss->d_tp);
-        ss->d_tp = nullptr; d.tp = nullptr;
-    }
-    if (!want_bl) {
-        (void)hipFree(ss->d_bl);
-        ss->d_bl = nullptr; d.bl = nullptr;
-    }
-    if (!want_bl && !want_tp) {
-        if (ss->bl_w1) {                  // back to the scalar set, whose totsq the w == 1 form left as they were
-            (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata);
-            ss->d_w = ss->d_wdata = nullptr; d.chan_w = d.wdata = nullptr;
-            ss->bl_w1 = false;
-        }
-        return NFA_OK;
-    }
-    const size_t n = (size_t)(ss->n_pix * d.chan_tot);
-    if (!d.chan_w) {                      // a scalar noise runs as the weighted form with w == 1: its bits
-        double *w = nullptr, *wdata = nullptr;                // both, or neither
-        HIP_TRY(hipMalloc(&w, sizeof(double) * n));
-        if (hipMalloc(&wdata, sizeof(double) * n) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(w); return fail(NFA_ERR_DEVICE, "out of device memory for the channel weights"); }
-        ss->d_w = w; ss->d_wdata = wdata;
-        ss->bl_w1 = true;
-        std::vector<double> one(n, 1.0);
-        HIP_TRY(hipMemcpy(ss->d_w, one.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-        d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
-        int rc = launch_chan_weight(ss, 0, ss->n_pix, false); if (rc) return rc;
-    }
-    if (want_bl) {
-        if (!ss->d_bl) HIP_TRY(hipMalloc(&ss->d_bl, sizeof(double) * NFA_BL_REC * ss->n_pix * d.n_spec));
-        d.bl = ss->d_bl;
-        int rc = launch_bl_setup(ss, 0, ss->n_pix, true); if (rc) return rc;
-    }
-    if (want_tp) {
-        if (!ss->d_tp) HIP_TRY(hipMalloc(&ss->d_tp, sizeof(double) * NFA_TP_REC * ss->n_pix * d.n_spec));
-        d.tp = ss->d_tp;
-        int rc = launch_tmpl_setup(ss, 0, ss->n_pix, true); if (rc) return rc;
-    }
-    return NFA_OK;
-}
-
-// What the set has, as set_refusal (nfa_set_rules.h) asks: which of the likelihoods a setter may not put beside its own.
-// ("correlated" is the coefficients of the correlated kernels, which a response over white noise has too.)
-static unsigned specset_has(const nfa_specset *ss) {
-    const SpecDev &d = ss->dev;
-    return (ss->masked ? SET_HAS_MASK : 0u) | (d.bl_order >= 0 ? SET_HAS_BASELINE : 0u) | (d.cal2 ? SET_HAS_CALIB : 0u) |
-           (d.nmarg ? SET_HAS_NMARG : 0u) | (d.corr_q1 ? SET_HAS_CORR : 0u) | (d.resp ? SET_HAS_RESP : 0u) | (d.tmpl ? SET_HAS_TMPL : 0u) |
-           (d.cont ? SET_HAS_CONT : 0u) | (d.rob ? SET_HAS_ROBUST : 0u);
-}
-
-int nfa_specset_set_baseline(nfa_specset *ss, int order) {
-    if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
-    if (const char *why = order >= 0 ? set_refusal(specset_has(ss), SET_TAKES_BASELINE) : nullptr) return fail(NFA_ERR_ARG, why);
-    int rc = engine_init(); if (rc) return rc;
-    rc = specset_quiesce(ss); if (rc) return rc;
-    const int was = ss->dev.bl_order;
-    ss->dev.bl_order = order;
-    rc = specset_form_records(ss);
-    if (rc) {                                                 // the set stays as it was: the old order, its records formed again
-        const std::string why = g_err;
-        ss->dev.bl_order = was;
-        (void)specset_form_records(ss);
-        g_err = why;
-    }
-    return rc;
-}
-
-int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
-    if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    SpecDev &d = ss->dev;
-    bool any = false;
-    for (int s = 0; cal && s < d.n_spec; ++s) {
-        if (!(cal[s] >= 0.0 && cal[s] <= 1.0))                // (NaN fails both)
-            return fail(NFA_ERR_ARG, "a calibration uncertainty is a finite fraction in [0, 1] per spectrum");
-        any = any || cal[s] > 0.0;
-    }
-    if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_CALIB) : nullptr) return fail(NFA_ERR_ARG, why);
-    int rc = engine_init(); if (rc) return rc;
-    rc = specset_quiesce(ss); if (rc) return rc;
-    if (!any) {                                               // null, or all zeros: the set's former kernels and bits
-        if (!d.cal2) return NFA_OK;
-        (void)hipFree(ss->d_cal2);
-        ss->d_cal2 = nullptr; d.cal2 = nullptr;
-        for (int s = 0; s < MAXSPEC; ++s) ss->h_cal[s] = 0.0;
-        return d.bl_order >= 0 ? NFA_OK : specset_form_records(ss);      // (a baseline's records stay as they are)
-    }
-    double s2[MAXSPEC];
-    for (int s = 0; s < d.n_spec; ++s) s2[s] = cal[s] * cal[s];
-    if (!ss->d_cal2) HIP_TRY(hipMalloc(&ss->d_cal2, sizeof(double) * d.n_spec));
-    HIP_TRY(hipMemcpy(ss->d_cal2, s2, sizeof(double) * d.n_spec, hipMemcpyHostToDevice));
-    for (int s = 0; s < d.n_spec; ++s) ss->h_cal[s] = cal[s];
-    const bool formed = d.cal2 != nullptr || d.bl_order >= 0;           // the records are there already
-    d.cal2 = ss->d_cal2;
-    if (formed) return NFA_OK;
-    rc = specset_form_records(ss);
-    if (rc) {                                                 // the set stays as it was: without a calibration, and without
-        const std::string why = g_err;                        // whatever was made for it
-        (void)hipFree(ss->d_cal2);
-        ss->d_cal2 = nullptr; d.cal2 = nullptr;
-        for (int s = 0; s < MAXSPEC; ++s) ss->h_cal[s] = 0.0;
-        (void)specset_form_records(ss);
-        g_err = why;
-    }
-    return rc;
-}
-
-int nfa_specset_calibration(const nfa_specset *ss, double *out) {
-    if (!ss || !ss->dev.cal2) return 0;
-    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->h_cal[s];
-    return 1;
-}
-
-// The records {a, a + nu / 2} of every (pixel, spectrum) for the fractional uncertainties f[n_spec], some of them > 0
-static int nmarg_form(nfa_specset *ss, const double *f) {
-    SpecDev &d = ss->dev;
-    NmargA a_of = {};
-    for (int s = 0; s < d.n_spec; ++s) a_of.a[s] = f[s] > 0.0 ? 1.0 / (4.0 * f[s] * f[s]) : 0.0;
-    const int64_t n = ss->n_pix * d.n_spec;
-    if (!ss->d_nmarg) HIP_TRY(hipMalloc(&ss->d_nmarg, sizeof(double) * 2 * n));
-    // the set's own weights u^2: d_w (ones where a baseline, templates or a correlation made it for a scalar noise); none: nu = N
-    hipLaunchKernelGGL(nmarg_setup_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0, d, (long)ss->n_pix,
-                       (const double *)ss->d_w, a_of, ss->d_nmarg);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    return NFA_OK;
-}
-
-int nfa_specset_set_noise_uncertainty(nfa_specset *ss, const double *f) {
-    if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    SpecDev &d = ss->dev;
-    bool any = false;
-    for (int s = 0; f && s < d.n_spec; ++s) {
-        if (!(f[s] >= 0.0 && f[s] <= 0.5))                    // (NaN fails both)
-            return fail(NFA_ERR_ARG, "a noise uncertainty is a finite fraction in [0, 0.5] per spectrum");
-        any = any || f[s] > 0.0;
-    }
-    if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_NMARG) : nullptr) return fail(NFA_ERR_ARG, why);
-    int rc = engine_init(); if (rc) return rc;
-    rc = specset_quiesce(ss); if (rc) return rc;
-    if (!any) {                                               // null, or all zeros: the set's former arithmetic and bits
-        (void)hipFree(ss->d_nmarg);
-        ss->d_nmarg = nullptr; d.nmarg = nullptr;
-        for (int s = 0; s < MAXSPEC; ++s) ss->h_nunc[s] = 0.0;
-        return NFA_OK;
-    }
-    const bool had = d.nmarg != nullptr;
-    double was[MAXSPEC];
-    memcpy(was, ss->h_nunc, sizeof was);
-    d.nmarg = nullptr;                                        // (the set-up kernel's copy of the set reads none of it)
-    rc = nmarg_form(ss, f);
-    if (rc) {                                                 // the set stays as it was: its former values, or none
-        const std::string why = g_err;
-        if (!had || nmarg_form(ss, was) != NFA_OK) { (void)hipFree(ss->d_nmarg); ss->d_nmarg = nullptr; memset(ss->h_nunc, 0, sizeof ss->h_nunc); }
-        d.nmarg = ss->d_nmarg;
-        g_err = why;
-        return rc;
-    }
-    d.nmarg = ss->d_nmarg;
-    for (int s = 0; s < d.n_spec; ++s) ss->h_nunc[s] = f[s];
-    return NFA_OK;
-}
-
-int nfa_specset_noise_uncertainty(const nfa_specset *ss, double *out) {
-    if (!ss || !ss->dev.nmarg) return 0;
-    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->h_nunc[s];
-    return 1;
-}
-
 // The entries of R^-1 (NFA_CORR_NC of them) of the unit-variance AR(2) process with autocorrelations (r1, r2) by Yule-Walker;
-// null if the pair is outside the domain, `why` then says how
+// false if the pair is outside the domain, `why` then says how
 static bool corr_coef(double r1, double r2, double *c, const char **why) {
     if (!std::isfinite(r1) || !std::isfinite(r2)) { *why = "a noise correlation is a pair of finite numbers (rho_1, rho_2) per spectrum"; return false; }
     if (!(std::fabs(r1) < 1.0)) { *why = "a noise correlation needs |rho_1| < 1"; return false; }
@@ -1224,100 +1060,217 @@ static bool corr_coef(double r1, double r2, double *c, const char **why) {
     return true;
 }
 
-// The set without a correlation again: its own weights behind chan_w, wdata = w d and the sums of w d^2 (a scalar noise:
-// no weights at all), bit for bit what the set was created with
-static int corr_remove(nfa_specset *ss) {
-    SpecDev &d = ss->dev;
-    (void)hipFree(ss->d_q0); (void)hipFree(ss->d_q1); (void)hipFree(ss->d_q2); (void)hipFree(ss->d_corr);
-    ss->d_q0 = ss->d_q1 = ss->d_q2 = ss->d_corr = nullptr;
-    d.corr_q1 = d.corr_q2 = d.corr_coef = nullptr;
-    for (int s = 0; s < MAXSPEC; ++s) ss->h_rho[s][0] = ss->h_rho[s][1] = 0.0;
-    if (ss->corr_w1) {
-        (void)hipFree(ss->d_w); (void)hipFree(ss->d_wdata);
-        ss->d_w = ss->d_wdata = nullptr; d.chan_w = d.wdata = nullptr;
-        ss->corr_w1 = false;
-    } else if (ss->d_w) {
-        d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
-        int rc = launch_chan_weight(ss, 0, ss->n_pix, false); if (rc) return rc;
-    } else {                              // a scalar noise whose weights were never made (the first allocation failed): nothing to form
-        d.chan_w = d.wdata = nullptr;
-    }
-    return launch_rowsq(ss, 0, ss->n_pix);
+// The one allocation of an option's buffer
+static int set_alloc(double **p, size_t doubles, const char *oom) {
+#ifdef NFA_TEST_HOOKS
+    if (test_alloc_fails()) return fail(NFA_ERR_DEVICE, oom);
+#endif
+    if (hipMalloc(p, sizeof(double) * doubles) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return fail(NFA_ERR_DEVICE, oom); }
+    return NFA_OK;
 }
 
-// Q's bands, Q d and the sums d^T Q d for the pairs rho[n_spec][2] (their entries of R^-1 in coef)
-static int corr_apply(nfa_specset *ss, const double *rho, const double (*coef)[NFA_CORR_NC]) {
+// SpecDev's pointers as layout L of options o names them.  base: chan_w and wdata of a robust set at what lies beneath g, the
+// set's own weights (a scalar noise: none) -- the state launch_rowsq forms its sums from before rob_setup_kernel turns them into k C.
+static void specset_point(nfa_specset *ss, const SetOptions &o, const SetLayout &L, bool base) {
     SpecDev &d = ss->dev;
-    const size_t n = (size_t)(ss->n_pix * d.chan_tot);
-    if (!ss->d_w) {                       // a scalar noise: u == 1
-        double *w = nullptr, *wdata = nullptr;                // both, or neither
-        HIP_TRY(hipMalloc(&w, sizeof(double) * n));
-        if (hipMalloc(&wdata, sizeof(double) * n) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(w); return fail(NFA_ERR_DEVICE, "out of device memory for the channel weights"); }
-        ss->d_w = w; ss->d_wdata = wdata;
-        ss->corr_w1 = true;
-        std::vector<double> one(n, 1.0);
-        HIP_TRY(hipMemcpy(ss->d_w, one.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    }
-    if (!ss->d_q0) HIP_TRY(hipMalloc(&ss->d_q0, sizeof(double) * n));
-    if (!ss->d_q1) HIP_TRY(hipMalloc(&ss->d_q1, sizeof(double) * n));
-    if (!ss->d_q2) HIP_TRY(hipMalloc(&ss->d_q2, sizeof(double) * n));
-    if (!ss->d_corr) HIP_TRY(hipMalloc(&ss->d_corr, sizeof(double) * NFA_CORR_NC * MAXSPEC));
-    HIP_TRY(hipMemcpy(ss->d_corr, coef, sizeof(double) * NFA_CORR_NC * d.n_spec, hipMemcpyHostToDevice));
-    d.chan_w = ss->d_q0; d.wdata = ss->d_wdata;
-    d.corr_q1 = ss->d_q1; d.corr_q2 = ss->d_q2; d.corr_coef = ss->d_corr;
-    for (int s = 0; s < d.n_spec; ++s) { ss->h_rho[s][0] = rho[2 * s]; ss->h_rho[s][1] = rho[2 * s + 1]; }
-    int rc = launch_corr_setup(ss, 0, ss->n_pix, true); if (rc) return rc;
-    return launch_rowsq(ss, 0, ss->n_pix);
+    const bool own = L.chan_w == CHAN_W_OWN || (L.chan_w == CHAN_W_ROBUST && (base && L.has(SB_W)));
+    const bool rob = L.chan_w == CHAN_W_ROBUST && !base;
+    d.chan_w = L.chan_w == CHAN_W_Q ? ss->d_q0 : own ? ss->d_w : rob ? ss->d_rg : nullptr;
+    d.wdata = L.chan_w == CHAN_W_Q || own ? ss->d_wdata : rob ? ss->d_rgd : nullptr;
+    d.bl = L.has(SB_BL) ? ss->d_bl : nullptr;
+    d.bl_order = o.bl_order;
+    d.tmpl = L.has(SB_TMPL) ? ss->d_tmpl : nullptr;
+    d.tp = L.has(SB_TP) ? ss->d_tp : nullptr;
+    d.cal2 = L.has(SB_CAL2) ? ss->d_cal2 : nullptr;
+    d.nmarg = L.has(SB_NMARG) ? ss->d_nmarg : nullptr;
+    d.corr_q1 = L.has(SB_Q1) ? ss->d_q1 : nullptr;
+    d.corr_q2 = L.has(SB_Q2) ? ss->d_q2 : nullptr;
+    d.corr_coef = L.has(SB_CORR) ? ss->d_corr : nullptr;
+    d.resp = L.has(SB_RESP) ? ss->d_resp : nullptr;
+    d.cont = L.has(SB_CONT) ? ss->d_cont : nullptr;
+    d.rob = rob ? ss->d_rob : nullptr;
 }
 
-static void corr_coef_white(double *c) { c[0] = c[1] = c[2] = 1.0; c[3] = c[4] = c[5] = 0.0; }
-
-// The device's state for the pairs rho[n_spec][2] (null: no correlation) and the taps resp[n_spec][NFA_RESP_NT] (null: no
-// response), both valid: neither -- the set's own weights and its former kernels; either -- Q's arrays, over the white entries
-// of R^-1 where there is no correlation, and the taps where there is a response
-static int qstate_apply(nfa_specset *ss, const double *rho, const double *resp) {
+// The device state of record `next`, whatever the set holds now, for pixels [pix0, pix0 + n): `work` is the copies and
+// forming stages to run (set_stages_*, nfa_set_state.h).  Three phases.  1. Allocate every buffer the layout needs that is not
+// there; a failure frees what this call allocated and returns with nothing the kernels read touched.  2. Copy the small
+// arrays up, point SpecDev at the layout's buffers and run the stages in their order; *touched says this phase began.
+// 3. Free what the layout does not need.  A call turns one option on or off, so its peak memory is max(before, after).
+static int specset_realise(nfa_specset *ss, const SetRecord &next, int64_t pix0, int64_t n, unsigned work, bool *touched = nullptr) {
     SpecDev &d = ss->dev;
-    if (!resp) {
-        (void)hipFree(ss->d_resp);
-        ss->d_resp = nullptr; d.resp = nullptr;
-        memset(ss->h_resp, 0, sizeof ss->h_resp);
+    const SetOptions &o = next.o;
+    const SetLayout L = set_layout(o, ss->chan_noise);
+    double *made[SB_N] = {};
+    for (int i = 0; i < SB_N; ++i) {
+        const SetBuf &b = SET_BUFS[i];
+        if (!L.has(b.bit) || ss->*b.p) continue;
+        const int rc = set_alloc(&made[i], set_buf_doubles(ss, b.bit), b.oom);
+        if (rc) { for (double *m : made) (void)hipFree(m); return rc; }
     }
-    ss->has_corr = rho != nullptr;
-    if (!rho && !resp) return d.corr_q1 ? corr_remove(ss) : NFA_OK;
-    double coef[MAXSPEC][NFA_CORR_NC], pairs[MAXSPEC][2] = {};
-    for (int s = 0; s < d.n_spec; ++s) {
-        const char *why = nullptr;
-        if (rho) { pairs[s][0] = rho[2 * s]; pairs[s][1] = rho[2 * s + 1]; }
-        if (pairs[s][0] == 0.0 && pairs[s][1] == 0.0) corr_coef_white(coef[s]);      // white noise in this spectrum: R = 1
-        else if (!corr_coef(pairs[s][0], pairs[s][1], coef[s], &why)) return fail(NFA_ERR_ARG, why);
+    for (int i = 0; i < SB_N; ++i) if (made[i]) ss->*SET_BUFS[i].p = made[i];
+
+    if (touched) *touched = true;
+    const size_t chan = (size_t)d.chan_tot, all = (size_t)(ss->n_pix * d.chan_tot);
+    if (work & UP_CAL2) {
+        double s2[MAXSPEC];
+        for (int s = 0; s < d.n_spec; ++s) s2[s] = o.cal[s] * o.cal[s];
+        HIP_TRY(hipMemcpy(ss->d_cal2, s2, sizeof(double) * d.n_spec, hipMemcpyHostToDevice));
     }
-    if (resp) {
-        if (!ss->d_resp) HIP_TRY(hipMalloc(&ss->d_resp, sizeof(double) * NFA_RESP_NT * MAXSPEC));
-        HIP_TRY(hipMemcpy(ss->d_resp, resp, sizeof(double) * NFA_RESP_NT * d.n_spec, hipMemcpyHostToDevice));
-        if (resp != &ss->h_resp[0][0]) memcpy(ss->h_resp, resp, sizeof(double) * NFA_RESP_NT * d.n_spec);
-        d.resp = ss->d_resp;
+    if (work & UP_CORR) {             // white noise in a spectrum (and everywhere under a response alone): R = 1
+        double coef[MAXSPEC][NFA_CORR_NC];
+        for (int s = 0; s < d.n_spec; ++s) {
+            const char *why = nullptr;
+            if ((o.rho[s][0] == 0.0 && o.rho[s][1] == 0.0) || !corr_coef(o.rho[s][0], o.rho[s][1], coef[s], &why)) {
+                coef[s][0] = coef[s][1] = coef[s][2] = 1.0; coef[s][3] = coef[s][4] = coef[s][5] = 0.0;
+            }
+        }
+        HIP_TRY(hipMemcpy(ss->d_corr, coef, sizeof(double) * NFA_CORR_NC * d.n_spec, hipMemcpyHostToDevice));
     }
-    return corr_apply(ss, &pairs[0][0], coef);
+    if (work & UP_RESP) HIP_TRY(hipMemcpy(ss->d_resp, o.resp, sizeof(double) * NFA_RESP_NT * d.n_spec, hipMemcpyHostToDevice));
+    if (work & UP_TMPL) {             // each template goes up scaled to max |t| = 1 over its spectrum
+        std::vector<double> scaled(NFA_TMPL_MAX * chan, 0.0);
+        for (int s = 0; s < d.n_spec; ++s)
+            for (int k = 0; k < o.ntmpl[s]; ++k) {
+                const double *t = next.tmpl.data() + k * chan + d.off[s];
+                double top = 0.0;
+                for (int j = 0; j < d.size[s]; ++j) top = std::max(top, std::fabs(t[j]));
+                for (int j = 0; j < d.size[s]; ++j) scaled[k * chan + d.off[s] + j] = t[j] / top;
+            }
+        HIP_TRY(hipMemcpy(ss->d_tmpl, scaled.data(), sizeof(double) * scaled.size(), hipMemcpyHostToDevice));
+    }
+    if (work & UP_CONT) HIP_TRY(hipMemcpy(ss->d_cont, next.cont.data(), sizeof(double) * next.cont.size(), hipMemcpyHostToDevice));
+    specset_point(ss, o, L, true);
+    int rc = NFA_OK;
+    if (work & ST_ONES) {             // a scalar noise runs as the weighted form with w == 1: its bits
+        std::vector<double> one(all, 1.0);
+        HIP_TRY(hipMemcpy(ss->d_w, one.data(), sizeof(double) * all, hipMemcpyHostToDevice));
+    }
+    if (work & ST_CHAN_WEIGHT) { rc = launch_chan_weight(ss, pix0, n, false); if (rc) return rc; }      // the mask stays
+    if (work & ST_CORR) { rc = launch_corr_setup(ss, pix0, n, (work & ST_FORM_Q) != 0); if (rc) return rc; }
+    if (work & ST_ROWSQ) { rc = launch_rowsq(ss, pix0, n); if (rc) return rc; }
+    if (work & ST_ROB) {              // g, g d, totsq = k C and the records; the spectra with nu = 0 keep the sums beneath
+        // (the kernel reads the set's data, noise, sizes and offsets and its own arguments, neither S.chan_w nor S.wdata:
+        // that `d` still points at the base here is nothing to it)
+        RobNu nu_of = {};
+        for (int s = 0; s < d.n_spec; ++s) nu_of.nu[s] = o.rob[s];
+        hipLaunchKernelGGL(rob_setup_kernel, dim3((unsigned)((n * d.n_spec * 64 + 255) / 256)), dim3(256), 0, 0, d, (long)pix0, (long)n,
+                           (const double *)ss->d_w, nu_of, ss->d_rg, ss->d_rgd, ss->d_totsq, ss->d_rob);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    specset_point(ss, o, L, false);
+    if (work & ST_BL) { rc = launch_bl_setup(ss, pix0, n, (work & ST_BL_BASIS) != 0); if (rc) return rc; }
+    if (work & ST_TP) { rc = launch_tmpl_setup(ss, pix0, n, (work & ST_TP_BASIS) != 0); if (rc) return rc; }
+    if (work & ST_NMARG) {            // {a, a + nu / 2} of every (pixel, spectrum), nu the channels whose own weight is > 0
+        NmargA a_of = {};
+        for (int s = 0; s < d.n_spec; ++s) a_of.a[s] = o.nunc[s] > 0.0 ? 1.0 / (4.0 * o.nunc[s] * o.nunc[s]) : 0.0;
+        const int64_t spec = ss->n_pix * d.n_spec;
+        hipLaunchKernelGGL(nmarg_setup_kernel, dim3((unsigned)((spec * 64 + 255) / 256)), dim3(256), 0, 0, d, (long)ss->n_pix,
+                           (const double *)ss->d_w, a_of, ss->d_nmarg);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+    }
+
+    for (const SetBuf &b : SET_BUFS)
+        if (!L.has(b.bit) && ss->*b.p) { (void)hipFree(ss->*b.p); ss->*b.p = nullptr; }
+    return NFA_OK;
 }
 
-// qstate_apply, and after a failure the former state again (the failure's reason stays)
-static int qstate_change(nfa_specset *ss, const double *rho, const double *resp) {
-    const bool had_corr = ss->has_corr, had_resp = ss->dev.resp != nullptr;
-    double was_rho[MAXSPEC][2], was_resp[MAXSPEC][NFA_RESP_NT];
-    memcpy(was_rho, ss->h_rho, sizeof was_rho);
-    memcpy(was_resp, ss->h_resp, sizeof was_resp);
-    const int rc = qstate_apply(ss, rho, resp);
-    if (rc) {
+// The shared body of the setters, after a setter's value checks and the table's refusal: the set becomes `next`, or stays as
+// it was -- a failed allocation touches nothing, and after a failed copy or launch the old record is realised once more with
+// every stage (the first error's text stays).
+static int specset_change(nfa_specset *ss, SetRecord &next) {
+    int rc = engine_init(); if (rc) return rc;
+    rc = specset_quiesce(ss); if (rc) return rc;
+    const auto differ = [](const std::vector<double> &a, const std::vector<double> &b) {      // bit for bit, like set_options_equal
+        return a.size() != b.size() || (!a.empty() && memcmp(a.data(), b.data(), sizeof(double) * a.size()) != 0);
+    };
+    const bool tmpl_changed = differ(next.tmpl, ss->opt.tmpl), cont_changed = differ(next.cont, ss->opt.cont);
+    if (set_options_equal(next.o, ss->opt.o) && !tmpl_changed && !cont_changed) return NFA_OK;
+    const SetLayout la = set_layout(ss->opt.o, ss->chan_noise), lb = set_layout(next.o, ss->chan_noise);
+    bool touched = false;
+    rc = specset_realise(ss, next, 0, ss->n_pix, set_stages_change(ss->opt.o, la, next.o, lb, tmpl_changed, cont_changed), &touched);
+    if (rc == NFA_OK) { ss->opt = std::move(next); return NFA_OK; }
+    if (touched) {
         const std::string why = g_err;
-        (void)qstate_apply(ss, had_corr ? &was_rho[0][0] : nullptr, had_resp ? &was_resp[0][0] : nullptr);
+        (void)specset_realise(ss, ss->opt, 0, ss->n_pix, set_stages_all(la));
         g_err = why;
     }
     return rc;
 }
 
+int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data) {
+    if (!ss || !data || pix < 0 || pix >= ss->n_pix) return fail(NFA_ERR_ARG, "bad pixel index");
+    int rc = engine_init(); if (rc) return rc;
+    HIP_TRY(hipMemcpy(ss->d_data + pix * ss->dev.chan_tot, data, sizeof(double) * ss->dev.chan_tot,
+                      hipMemcpyHostToDevice));
+    return specset_realise(ss, ss->opt, pix, 1, set_stages_data(set_layout(ss->opt.o, ss->chan_noise)));
+}
+
+// What the set has, as set_refusal (nfa_set_rules.h) asks: which of the likelihoods a setter may not put beside its own
+static unsigned specset_has(const nfa_specset *ss) { return set_has(ss->opt.o, ss->masked); }
+
+// A setter: null check, its value check (`any`: the request switches the option on), the table's refusal, a copy of the
+// record with its one field edited, specset_change.
+int nfa_specset_set_baseline(nfa_specset *ss, int order) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    if (order < -1 || order > NFA_BASELINE_MAX) return fail(NFA_ERR_ARG, "baseline order must be in -1..3 (-1: none)");
+    if (const char *why = order >= 0 ? set_refusal(specset_has(ss), SET_TAKES_BASELINE) : nullptr) return fail(NFA_ERR_ARG, why);
+    SetRecord next = ss->opt;
+    next.o.bl_order = order;
+    return specset_change(ss, next);
+}
+
+// the per-spectrum values of a request into their field of the record: vals[n_spec][width] if `any`, zeros otherwise
+static void set_field(double *field, size_t bytes, bool *has, bool any, const double *vals, int n) {
+    memset(field, 0, bytes);
+    if (any) memcpy(field, vals, sizeof(double) * n);
+    *has = any;
+}
+
+int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    bool any = false;
+    for (int s = 0; cal && s < ss->dev.n_spec; ++s) {
+        if (!(cal[s] >= 0.0 && cal[s] <= 1.0))                // (NaN fails both)
+            return fail(NFA_ERR_ARG, "a calibration uncertainty is a finite fraction in [0, 1] per spectrum");
+        any = any || cal[s] > 0.0;
+    }
+    if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_CALIB) : nullptr) return fail(NFA_ERR_ARG, why);
+    SetRecord next = ss->opt;                                 // (null, or all zeros: the set's former kernels and bits)
+    set_field(next.o.cal, sizeof next.o.cal, &next.o.cal_on, any, cal, ss->dev.n_spec);
+    return specset_change(ss, next);
+}
+
+int nfa_specset_calibration(const nfa_specset *ss, double *out) {
+    if (!ss || !ss->opt.o.cal_on) return 0;
+    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->opt.o.cal[s];
+    return 1;
+}
+
+int nfa_specset_set_noise_uncertainty(nfa_specset *ss, const double *f) {
+    if (!ss) return fail(NFA_ERR_ARG, "null argument");
+    bool any = false;
+    for (int s = 0; f && s < ss->dev.n_spec; ++s) {
+        if (!(f[s] >= 0.0 && f[s] <= 0.5))                    // (NaN fails both)
+            return fail(NFA_ERR_ARG, "a noise uncertainty is a finite fraction in [0, 0.5] per spectrum");
+        any = any || f[s] > 0.0;
+    }
+    if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_NMARG) : nullptr) return fail(NFA_ERR_ARG, why);
+    SetRecord next = ss->opt;                                 // (null, or all zeros: the set's former arithmetic and bits)
+    set_field(next.o.nunc, sizeof next.o.nunc, &next.o.nunc_on, any, f, ss->dev.n_spec);
+    return specset_change(ss, next);
+}
+
+int nfa_specset_noise_uncertainty(const nfa_specset *ss, double *out) {
+    if (!ss || !ss->opt.o.nunc_on) return 0;
+    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->opt.o.nunc[s];
+    return 1;
+}
+
 int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    SpecDev &d = ss->dev;
+    const SpecDev &d = ss->dev;
     double coef[NFA_CORR_NC];
     bool any = false;
     for (int s = 0; rho && s < d.n_spec; ++s) {
@@ -1332,24 +1285,20 @@ int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
             if (d.size[s] < 4) return fail(NFA_ERR_ARG, "a noise correlation needs spectra of 4 channels and more");
         if (const char *why = set_refusal(specset_has(ss), SET_TAKES_CORR)) return fail(NFA_ERR_ARG, why);
     }
-    int rc = engine_init(); if (rc) return rc;
-    rc = specset_quiesce(ss); if (rc) return rc;
-    if (!any && !ss->has_corr) return NFA_OK;                 // null, or all zeros, and none before: nothing changes
-    // (null, or all zeros: the set's former kernels and bits, or a response's over white noise)
-    double resp[MAXSPEC][NFA_RESP_NT];
-    memcpy(resp, ss->h_resp, sizeof resp);
-    return qstate_change(ss, any ? rho : nullptr, d.resp ? &resp[0][0] : nullptr);
+    SetRecord next = ss->opt;         // (null, or all zeros: the set's former kernels and bits, or a response's over white noise)
+    set_field(&next.o.rho[0][0], sizeof next.o.rho, &next.o.corr_on, any, rho, 2 * d.n_spec);
+    return specset_change(ss, next);
 }
 
 int nfa_specset_correlation(const nfa_specset *ss, double *out) {
-    if (!ss || !ss->has_corr) return 0;
-    for (int s = 0; out && s < ss->dev.n_spec; ++s) { out[2 * s] = ss->h_rho[s][0]; out[2 * s + 1] = ss->h_rho[s][1]; }
+    if (!ss || !ss->opt.o.corr_on) return 0;
+    if (out) memcpy(out, ss->opt.o.rho, sizeof(double) * 2 * ss->dev.n_spec);
     return 1;
 }
 
 int nfa_specset_set_response(nfa_specset *ss, const double *taps) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    SpecDev &d = ss->dev;
+    const SpecDev &d = ss->dev;
     bool any = false;
     for (int s = 0; taps && s < d.n_spec; ++s) {
         const double *h = taps + s * NFA_RESP_NT;
@@ -1367,54 +1316,20 @@ int nfa_specset_set_response(nfa_specset *ss, const double *taps) {
             if (d.size[s] < 4) return fail(NFA_ERR_ARG, "a channel response needs spectra of 4 channels and more");
         if (const char *why = set_refusal(specset_has(ss), SET_TAKES_RESP)) return fail(NFA_ERR_ARG, why);
     }
-    int rc = engine_init(); if (rc) return rc;
-    rc = specset_quiesce(ss); if (rc) return rc;
-    if (!any && !d.resp) return NFA_OK;                       // null, or the identity everywhere, and none before: nothing changes
-    // (null, or the identity everywhere: the correlated set's kernels and bits, or the set's former ones)
-    double rho[MAXSPEC][2];
-    memcpy(rho, ss->h_rho, sizeof rho);
-    return qstate_change(ss, ss->has_corr ? &rho[0][0] : nullptr, any ? taps : nullptr);
+    SetRecord next = ss->opt;         // (null, or the identity everywhere: the correlated set's kernels and bits, or the set's former ones)
+    set_field(&next.o.resp[0][0], sizeof next.o.resp, &next.o.resp_on, any, taps, NFA_RESP_NT * d.n_spec);
+    return specset_change(ss, next);
 }
 
 int nfa_specset_response(const nfa_specset *ss, double *out) {
-    if (!ss || !ss->dev.resp) return 0;
-    for (int s = 0; out && s < ss->dev.n_spec; ++s)
-        for (int k = 0; k < NFA_RESP_NT; ++k) out[s * NFA_RESP_NT + k] = ss->h_resp[s][k];
+    if (!ss || !ss->opt.o.resp_on) return 0;
+    if (out) memcpy(out, ss->opt.o.resp, sizeof(double) * NFA_RESP_NT * ss->dev.n_spec);
     return 1;
-}
-
-// The device's state for the caller's templates vals[NFA_TMPL_MAX][chan_tot] (unused slots zero) and counts[n_spec], both
-// valid; null: no templates.  Each template goes up scaled to max |t| = 1 over its spectrum.
-static int tmpl_apply(nfa_specset *ss, const double *vals, const int *counts) {
-    SpecDev &d = ss->dev;
-    if (!vals) {
-        (void)hipFree(ss->d_tmpl);
-        ss->d_tmpl = nullptr; d.tmpl = nullptr;
-        ss->h_tmpl.clear();
-        memset(ss->h_ntmpl, 0, sizeof ss->h_ntmpl);
-        return specset_form_records(ss);
-    }
-    const size_t n = (size_t)d.chan_tot;
-    std::vector<double> scaled(NFA_TMPL_MAX * n, 0.0), keep(vals, vals + NFA_TMPL_MAX * n);
-    for (int s = 0; s < d.n_spec; ++s)
-        for (int k = 0; k < counts[s]; ++k) {
-            const double *t = vals + k * n + d.off[s];
-            double top = 0.0;
-            for (int j = 0; j < d.size[s]; ++j) top = std::max(top, std::fabs(t[j]));
-            for (int j = 0; j < d.size[s]; ++j) scaled[k * n + d.off[s] + j] = t[j] / top;
-        }
-    if (!ss->d_tmpl) HIP_TRY(hipMalloc(&ss->d_tmpl, sizeof(double) * NFA_TMPL_MAX * n));
-    HIP_TRY(hipMemcpy(ss->d_tmpl, scaled.data(), sizeof(double) * NFA_TMPL_MAX * n, hipMemcpyHostToDevice));
-    d.tmpl = ss->d_tmpl;
-    ss->h_tmpl.swap(keep);
-    memset(ss->h_ntmpl, 0, sizeof ss->h_ntmpl);
-    for (int s = 0; s < d.n_spec; ++s) ss->h_ntmpl[s] = counts[s];
-    return specset_form_records(ss);
 }
 
 int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmpl) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    SpecDev &d = ss->dev;
+    const SpecDev &d = ss->dev;
     const size_t n = (size_t)d.chan_tot;
     bool any = false;
     for (int s = 0; t && n_tmpl && s < d.n_spec; ++s) {
@@ -1437,51 +1352,23 @@ int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmp
             }
         if (const char *why = set_refusal(specset_has(ss), SET_TAKES_TMPL)) return fail(NFA_ERR_ARG, why);
     }
-    int rc = engine_init(); if (rc) return rc;
-    rc = specset_quiesce(ss); if (rc) return rc;
-    if (!any && !d.tmpl) return NFA_OK;                       // null, or no template anywhere, and none before: nothing changes
-    const std::vector<double> was = ss->h_tmpl;
-    int was_n[MAXSPEC];
-    memcpy(was_n, ss->h_ntmpl, sizeof was_n);
-    rc = tmpl_apply(ss, any ? vals.data() : nullptr, n_tmpl);
-    if (rc) {                                                 // the set stays as it was: its former templates, or none
-        const std::string why = g_err;
-        (void)tmpl_apply(ss, was.empty() ? nullptr : was.data(), was_n);
-        g_err = why;
-    }
-    return rc;
+    SetRecord next = ss->opt;
+    next.o.tmpl_on = any;
+    for (int s = 0; s < MAXSPEC; ++s) next.o.ntmpl[s] = any && s < d.n_spec ? n_tmpl[s] : 0;
+    next.tmpl.swap(vals);
+    return specset_change(ss, next);
 }
 
 int nfa_specset_templates(const nfa_specset *ss, double *out_t, int *out_n) {
-    if (!ss || !ss->dev.tmpl) return 0;
-    if (out_t) memcpy(out_t, ss->h_tmpl.data(), sizeof(double) * ss->h_tmpl.size());
-    for (int s = 0; out_n && s < ss->dev.n_spec; ++s) out_n[s] = ss->h_ntmpl[s];
+    if (!ss || !ss->opt.o.tmpl_on) return 0;
+    if (out_t) memcpy(out_t, ss->opt.tmpl.data(), sizeof(double) * ss->opt.tmpl.size());
+    for (int s = 0; out_n && s < ss->dev.n_spec; ++s) out_n[s] = ss->opt.o.ntmpl[s];
     return 1;
-}
-
-// The device's state for the caller's continuum vals[n_pix][n_spec], valid and not all zero; null: no continuum.  The
-// weighted arrays and the baseline record follow (specset_form_records): such a set runs the baseline form.
-static int cont_apply(nfa_specset *ss, const double *vals) {
-    SpecDev &d = ss->dev;
-    if (!vals) {
-        (void)hipFree(ss->d_cont);
-        ss->d_cont = nullptr; d.cont = nullptr;
-        ss->h_cont.clear();
-        return specset_form_records(ss);
-    }
-    const size_t n = (size_t)(ss->n_pix * d.n_spec);
-    std::vector<double> keep(vals, vals + n);
-    if (!ss->d_cont) HIP_TRY(hipMalloc(&ss->d_cont, sizeof(double) * n));
-    HIP_TRY(hipMemcpy(ss->d_cont, keep.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    d.cont = ss->d_cont;
-    ss->h_cont.swap(keep);
-    return specset_form_records(ss);
 }
 
 int nfa_specset_set_continuum(nfa_specset *ss, const double *tc) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    SpecDev &d = ss->dev;
-    const int64_t n = ss->n_pix * d.n_spec;
+    const int64_t n = ss->n_pix * ss->dev.n_spec;
     bool any = false;
     for (int64_t i = 0; tc && i < n; ++i) {
         if (!(tc[i] >= 0.0 && tc[i] < INFINITY))              // (NaN fails both)
@@ -1489,102 +1376,39 @@ int nfa_specset_set_continuum(nfa_specset *ss, const double *tc) {
         any = any || tc[i] > 0.0;
     }
     if (any) {
-        if (d.model == NFA_MODEL_GAUSSIAN)
+        if (ss->dev.model == NFA_MODEL_GAUSSIAN)
             return fail(NFA_ERR_ARG, "the Gaussian model has no optical depth: its components cannot absorb a continuum background");
         if (const char *why = set_refusal(specset_has(ss), SET_TAKES_CONT)) return fail(NFA_ERR_ARG, why);
     }
-    int rc = engine_init(); if (rc) return rc;
-    rc = specset_quiesce(ss); if (rc) return rc;
-    if (!any && !d.cont) return NFA_OK;                       // null, or all zeros, and none before: nothing changes
-    const std::vector<double> was = ss->h_cont;
-    rc = cont_apply(ss, any ? tc : nullptr);
-    if (rc) {                                                 // the set stays as it was: its former continuum, or none
-        const std::string why = g_err;
-        (void)cont_apply(ss, was.empty() ? nullptr : was.data());
-        g_err = why;
-    }
-    return rc;
+    SetRecord next = ss->opt;
+    next.o.cont_on = any;
+    if (any) next.cont.assign(tc, tc + n); else next.cont.clear();
+    return specset_change(ss, next);
 }
 
 int nfa_specset_continuum(const nfa_specset *ss, double *out) {
-    if (!ss || !ss->dev.cont) return 0;
-    if (out) memcpy(out, ss->h_cont.data(), sizeof(double) * ss->h_cont.size());
+    if (!ss || !ss->opt.o.cont_on) return 0;
+    if (out) memcpy(out, ss->opt.cont.data(), sizeof(double) * ss->opt.cont.size());
     return 1;
-}
-
-// The set's own state of pixels [pix0, pix0 + n) behind chan_w and wdata: its weights and w d (a scalar noise: none), the
-// sums of w d^2 -- bit for bit what the set was created with
-static int rob_base(nfa_specset *ss, int64_t pix0, int64_t n) {
-    SpecDev &d = ss->dev;
-    d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
-    if (ss->d_w) { int rc = launch_chan_weight(ss, pix0, n, false); if (rc) return rc; }
-    return launch_rowsq(ss, pix0, n);
-}
-
-// ... and over it g, g d, totsq = k C and the records of a robust likelihood with nu[n_spec] (rob_setup_kernel): the spectra
-// with nu = 0 keep the sums rob_base left
-static int rob_form(nfa_specset *ss, int64_t pix0, int64_t n, const double *nu) {
-    SpecDev &d = ss->dev;
-    d.rob = nullptr;
-    int rc = rob_base(ss, pix0, n); if (rc) return rc;
-    RobNu nu_of = {};
-    for (int s = 0; s < d.n_spec; ++s) nu_of.nu[s] = nu[s];
-    d.chan_w = ss->d_rg; d.wdata = ss->d_rgd;
-    hipLaunchKernelGGL(rob_setup_kernel, dim3((unsigned)((n * d.n_spec * 64 + 255) / 256)), dim3(256), 0, 0, d, (long)pix0, (long)n,
-                       (const double *)ss->d_w, nu_of, ss->d_rg, ss->d_rgd, ss->d_totsq, ss->d_rob);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    d.rob = ss->d_rob;
-    return NFA_OK;
-}
-
-// The device's state for the degrees of freedom nu[n_spec], valid and not all zero; null: no robust likelihood, the set's
-// former kernels and bits
-static int rob_apply(nfa_specset *ss, const double *nu) {
-    SpecDev &d = ss->dev;
-    if (!nu) {
-        (void)hipFree(ss->d_rg); (void)hipFree(ss->d_rgd); (void)hipFree(ss->d_rob);
-        ss->d_rg = ss->d_rgd = ss->d_rob = nullptr; d.rob = nullptr;
-        memset(ss->h_rob, 0, sizeof ss->h_rob);
-        return rob_base(ss, 0, ss->n_pix);
-    }
-    const size_t n = (size_t)(ss->n_pix * d.chan_tot);
-    if (!ss->d_rg) HIP_TRY(hipMalloc(&ss->d_rg, sizeof(double) * n));
-    if (!ss->d_rgd) HIP_TRY(hipMalloc(&ss->d_rgd, sizeof(double) * n));
-    if (!ss->d_rob) HIP_TRY(hipMalloc(&ss->d_rob, sizeof(double) * 2 * ss->n_pix * d.n_spec));
-    int rc = rob_form(ss, 0, ss->n_pix, nu); if (rc) return rc;
-    if (nu != ss->h_rob) { memset(ss->h_rob, 0, sizeof ss->h_rob); memcpy(ss->h_rob, nu, sizeof(double) * d.n_spec); }
-    return NFA_OK;
 }
 
 int nfa_specset_set_robust(nfa_specset *ss, const double *nu) {
     if (!ss) return fail(NFA_ERR_ARG, "null argument");
-    SpecDev &d = ss->dev;
     bool any = false;
-    for (int s = 0; nu && s < d.n_spec; ++s) {
+    for (int s = 0; nu && s < ss->dev.n_spec; ++s) {
         if (!(nu[s] == 0.0 || (nu[s] >= 1.0 && nu[s] <= 1e6)))   // (NaN fails all)
             return fail(NFA_ERR_ARG, "a robust likelihood takes finite degrees of freedom per spectrum, 0 (Gaussian) or in [1, 1e6]");
         any = any || nu[s] > 0.0;
     }
     if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_ROBUST) : nullptr) return fail(NFA_ERR_ARG, why);
-    int rc = engine_init(); if (rc) return rc;
-    rc = specset_quiesce(ss); if (rc) return rc;
-    if (!any && !d.rob) return NFA_OK;                        // null, or all zeros, and none before: nothing changes
-    const bool had = d.rob != nullptr;
-    double was[MAXSPEC];
-    memcpy(was, ss->h_rob, sizeof was);
-    rc = rob_apply(ss, any ? nu : nullptr);
-    if (rc) {                                                 // the set stays as it was: its former degrees of freedom, or none
-        const std::string why = g_err;
-        (void)rob_apply(ss, had ? was : nullptr);
-        g_err = why;
-    }
-    return rc;
+    SetRecord next = ss->opt;                                 // (null, or all zeros: the set's former kernels and bits)
+    set_field(next.o.rob, sizeof next.o.rob, &next.o.rob_on, any, nu, ss->dev.n_spec);
+    return specset_change(ss, next);
 }
 
 int nfa_specset_robust(const nfa_specset *ss, double *out) {
-    if (!ss || !ss->dev.rob) return 0;
-    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->h_rob[s];
+    if (!ss || !ss->opt.o.rob_on) return 0;
+    for (int s = 0; out && s < ss->dev.n_spec; ++s) out[s] = ss->opt.o.rob[s];
     return 1;
 }
 
@@ -1607,17 +1431,18 @@ int nfa_specset_null_lnz(const nfa_specset *ss, double *out) {
     const int64_t n = ss->n_pix * ss->dev.n_spec;
     double *d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(double) * n));
-    if (ss->dev.rob)                                          // the likelihood kernel's own value at p = 0
+    const SetOptions &o = ss->opt.o;
+    if (o.rob_on)                                            // the likelihood kernel's own value at p = 0
         hipLaunchKernelGGL(null_lnz_rob_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
-    else if (ss->dev.tmpl)                                    // the model of baseline and templates alone
+    else if (o.tmpl_on)                                      // the model of baseline and templates alone
         hipLaunchKernelGGL(null_lnz_tmpl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
-    else if (ss->dev.bl_order >= 0)                           // the baseline-only model (a calibrated set's zeroed record is no baseline)
+    else if (o.bl_order >= 0)                                 // the baseline-only model (a calibrated set's zeroed record is no baseline)
         hipLaunchKernelGGL(null_lnz_bl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
     else
-        hipLaunchKernelGGL(ss->dev.chan_w ? null_lnz_w_kernel : null_lnz_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0,
-                           ss->dev, (long)ss->n_pix, d_out);
+        hipLaunchKernelGGL(set_layout(o, ss->chan_noise).chan_w != CHAN_W_NONE ? null_lnz_w_kernel : null_lnz_kernel,
+                           dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, 0, ss->dev, (long)ss->n_pix, d_out);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && ss->dev.nmarg) {                   // an uncertain noise level: lnl_of_item's term of the same h
+    if (e == hipSuccess && o.nunc_on) {                      // an uncertain noise level: lnl_of_item's term of the same h
         hipLaunchKernelGGL(null_lnz_nmarg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ss->dev.nmarg, (long)n, d_out);
         e = hipGetLastError();
     }

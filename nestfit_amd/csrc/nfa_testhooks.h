@@ -213,6 +213,14 @@ int nfa_test_lnl_launches(int64_t *out, int reset) {
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
+//  a failing allocation of an option's buffer (set_alloc, nfa_engine.hip): nfa_set_option("fail_alloc", k) of this library
+//  fails the k-th from now, once; 0 disarms.  Host code only: the device is asked for nothing and sees no fault.
+// ---------------------------------------------------------------------------
+static int g_fail_alloc_in = 0;
+static void test_fail_alloc(int k) { g_fail_alloc_in = k; }
+static bool test_alloc_fails() { return g_fail_alloc_in > 0 && --g_fail_alloc_in == 0; }
+
+// ---------------------------------------------------------------------------
 //  timeline of the queue form of the table-mode likelihood kernel (lnl_kernel_queue): with a buffer attached every
 //  wave of a launch records {start, end, item * nspec + spectrum, position in the order} of up to 8 units, in ticks of
 //  10 ns (s_memrealtime); the buffer holds the last launch
