@@ -51,8 +51,9 @@ int nfa_test_lnl_launches(int64_t *out, int reset);
 
 /* An option key of this library's nfa_set_option alone, like "ablate" (the product library refuses both):
  * "fail_alloc", k > 0 -- the k-th allocation from now of a buffer that a likelihood option of a spectra set needs (the
- * nfa_specset_set_* calls of this library) fails, once: the call returns NFA_ERR_DEVICE with its out-of-memory message, on
- * the host -- the device is asked for nothing.  k = 0 disarms.  No entry point of its own. */
+ * nfa_specset_set_* calls of this library) or that a noise per channel needs when a set is created (its weights and weighted
+ * data: two allocations of every creator given chan_noise) fails, once: the call returns NFA_ERR_DEVICE with its
+ * out-of-memory message, on the host -- the device is asked for nothing.  k = 0 disarms.  No entry point of its own. */
 
 #ifdef __cplusplus
 }

@@ -41,70 +41,11 @@
 #include <stdint.h>
 #include "nfa_line_window.h"   // the quotients behind a line's channel window: the reference's sequence and the short form
 #include "nfa_launch_plan.h"   // the layout constants (MAXSPEC, SM_*, LNL_PARTS, NFA_BL_NB, NFA_GROUP_MAX) and LnlGeom
+#include "nfa_set_decl.h"      // the records a set keeps in device memory (LineRow, LteRec, BandRec, MixRec) and the NFA_T_* indices
 
 #define MAXCOMP   10          // ResolvedPlacementPrior's own limit (core.pyx:399)
-// Transition indices of every model in one index space: 0..8 NH3 (1,1)..(9,9), 9..11 N2H+ 1-0, 2-1, 3-2, 12 the
-// Gaussian model's single "line" (offset 0, weight 1, rest frequency from the spectrum), 13 a spectrum of the
-// hyperfine model or of the LTE model, whose lines the caller supplies (nfa_specset_create_lines, _create_lte).
-// SpecDev.trans holds index + 1.
-// The index selects what belongs to a transition beyond its lines (c_nu and c_ea: ammonia only; the Gaussian
-// model's line centre, nf_line); the lines themselves are per spectrum, in device memory (SpecDev.lines).
-#define NFA_T_N2HP   NFA_N_LEVELS
-#define NFA_T_GAUSS  (NFA_N_LEVELS + NFA_N2HP_LEVELS)
-#define NFA_T_LINES  (NFA_T_GAUSS + 1)
-#define NFA_T_ALL    (NFA_T_LINES + 1)
 __constant__ double c_nu[NFA_T_ALL];
 __constant__ double c_ea[NFA_N_LEVELS];
-
-// The lines of one spectrum as the kernels read them (nfa_engine.hip: line_row_fill; the shipped tables for ammonia,
-// N2H+ and the Gaussian model, the caller's for the hyperfine model): hf_freq = (1 - voff / CKMS) * nu of every line
-// (hyperfine.pyx:71), its weight, the number of lines, and the position of every line when the lines are ordered by
-// their velocity offset (stable): in that order the lines whose windows touch a row of channels form ONE run of
-// neighbours (fast mode's line table, lnl_body).
-struct LineRow {
-    double        hfreq[NFA_MAX_HF_N];
-    double        tauw[NFA_MAX_HF_N];
-    int           nhf;
-    unsigned char rank[NFA_MAX_HF_N];
-};
-
-// What the LTE model (NFA_MODEL_LTE, nfa_specset_create_lte) needs beyond the lines, one record per spectra set in
-// device memory: the upper level and the Einstein coefficient of every spectrum's transition, and the species'
-// partition function as ln Q over ln T with the slope of every segment (slope[k]: entries k, k + 1).  Only the set-up
-// stage's derive_lte_lane reads it (nfa_setup.h).
-#define NFA_LTE_MAXQ 64
-struct LteRec {
-    double e_up[MAXSPEC], g_up[MAXSPEC], a_ul[MAXSPEC];      // K, statistical weight, 1/s
-    int    n_q, pad;
-    double ln_t[NFA_LTE_MAXQ], ln_q[NFA_LTE_MAXQ], slope[NFA_LTE_MAXQ];
-};
-
-// LTE bands (nfa_specset_create_lte_bands): a spectrum that covers several transitions g of the species, each
-// with lines of its own.  One record per banded spectra set in device memory (null for every other set): the number of
-// transitions of every spectrum and the transition of every line, and per (spectrum, transition), formed on the host in
-// doubles against the spectrum's reference transition 0 (the one of the lowest lower-level energy, whose numbers
-// SpecDev.rest and LteRec hold):  t0 = h nu_g / k,  de = (E_g - t0_g) - (E_0 - t0_0) >= 0,
-// k = (g_g A_g / nu_g^3) / (g_0 A_0 / nu_0^3).  lte_band_kernel (nfa_setup.h) reads the numbers, lnl_body grp.
-#define NFA_BAND_MAXT 8
-struct BandRec {
-    int           n_trans[MAXSPEC];
-    unsigned char grp[MAXSPEC][NFA_MAX_HF_N];
-    double        t0[MAXSPEC][NFA_BAND_MAXT], de[MAXSPEC][NFA_BAND_MAXT], k[MAXSPEC][NFA_BAND_MAXT];
-};
-
-// LTE mixes (nfa_specset_create_lte_mix): a set whose transitions belong to K = 2..4 species that share voff,
-// tex and sigm, each with a column density (parameter 3 + k of a component for species k >= 1; species 0's stays
-// parameter 2) and a partition table of its own.  One record per such set in device memory (null for every other set)
-// beside a BandRec, which a mix set always owns: the species of every (spectrum, transition) in the band's order, and the
-// partition tables of species 1..K-1 as LteRec holds species 0's (entry k - 1: species k).  Only lte_mix_kernel
-// (nfa_setup.h) reads it.
-#define NFA_LTE_MAXSP 4
-struct MixRec {
-    int           n_species, pad;
-    unsigned char species[MAXSPEC][NFA_BAND_MAXT];
-    int           n_q[NFA_LTE_MAXSP - 1], pad2;
-    double        ln_t[NFA_LTE_MAXSP - 1][NFA_LTE_MAXQ], ln_q[NFA_LTE_MAXSP - 1][NFA_LTE_MAXQ], slope[NFA_LTE_MAXSP - 1][NFA_LTE_MAXQ];
-};
 
 struct SpecDev {
     int     n_spec, ncomp, cold, lte;

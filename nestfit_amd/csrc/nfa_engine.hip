@@ -26,6 +26,7 @@
 #include "nh3_data.h"
 #include "n2hp_data.h"
 #include "nfa_device.h"
+#include "nfa_set_decl.h"
 #include "nfa_set_rules.h"
 #include "nfa_set_state.h"
 
@@ -105,51 +106,6 @@ static std::vector<nfa_runner *> g_runners;         // live runners: nfa_device_
 // library is loaded, and only if the user has not set it.
 __attribute__((constructor)) static void nfa_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
 
-// The line row of one spectrum as the kernels read it (LineRow, nfa_device.h), from a table of n lines: hf_freq of every
-// line with one rounding per operation (hyperfine.pyx:71) and the rank of every line when the lines are ordered by
-// velocity offset (stable).  The slots behind the last line hold hf_freq of a zero offset, weight 0 and their own index.
-static void line_row_fill(LineRow &row, int n, double nu, const double *voff, const double *tauw) {
-    row.nhf = n;
-    for (int i = 0; i < NFA_MAX_HF_N; ++i) {
-        volatile double q = (i < n ? voff[i] : 0.0) / NFA_CKMS;       // hyperfine.pyx:71, one rounding per operation
-        volatile double f = 1.0 - q;
-        row.hfreq[i] = f * nu;
-        row.tauw[i] = i < n ? tauw[i] : 0.0;
-        row.rank[i] = (unsigned char)i;
-    }
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return voff[a] > voff[b]; });
-    for (int k = 0; k < n; ++k) row.rank[order[k]] = (unsigned char)k;
-}
-// The line row of a banded LTE spectrum (nfa_specset_create_lte_bands): every line against the rest frequency of its own
-// transition, nu[i], with the same two operations; the rank is the stable rank of ascending hf_freq -- for one
-// transition the permutation line_row_fill's descending offsets give.
-static void line_row_fill_band(LineRow &row, int n, const double *nu, const double *voff, const double *tauw) {
-    row.nhf = n;
-    for (int i = 0; i < NFA_MAX_HF_N; ++i) {
-        volatile double q = (i < n ? voff[i] : 0.0) / NFA_CKMS;
-        volatile double f = 1.0 - q;
-        row.hfreq[i] = f * nu[i < n ? i : 0];
-        row.tauw[i] = i < n ? tauw[i] : 0.0;
-        row.rank[i] = (unsigned char)i;
-    }
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return row.hfreq[a] < row.hfreq[b]; });
-    for (int k = 0; k < n; ++k) row.rank[order[k]] = (unsigned char)k;
-}
-// The shipped table of global transition index tg (NFA_T_*): the line count, the rest frequency, offsets and weights
-static int builtin_table(int tg, double *nu, const double **voff, const double **tauw) {
-    static const double gauss_voff[NFA_MAX_HF_N] = {0.0}, gauss_w[NFA_MAX_HF_N] = {1.0};
-    if (tg < NFA_T_N2HP) { *nu = nfa_nu[tg]; *voff = nfa_voff[tg]; *tauw = nfa_tau_wts[tg]; return nfa_nhf[tg]; }
-    if (tg < NFA_T_GAUSS) {
-        const int t = tg - NFA_T_N2HP;
-        *nu = nfa_n2hp_nu[t]; *voff = nfa_n2hp_voff[t]; *tauw = nfa_n2hp_tau_wts[t]; return nfa_n2hp_nhf[t];
-    }
-    *nu = 0.0; *voff = gauss_voff; *tauw = gauss_w; return 1;
-}
-
 static int engine_init_once();
 // HIP's current device is per host thread (default 0): every public entry point that allocates or
 // launches binds the calling thread to the engine's device first (broker threads, sampler threads
@@ -175,7 +131,7 @@ static int engine_init_once() {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, g_eng.device));
     g_eng.n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    {   // what belongs to a transition beyond its lines (nfa_device.h); the lines are per spectra set (specset_fill)
+    {   // what belongs to a transition beyond its lines (nfa_device.h); the lines are per spectra set (set_plan, nfa_set_decl.h)
         static double h_nu[NFA_T_ALL];
         for (int t = 0; t < NFA_N_LEVELS; ++t) h_nu[t] = nfa_nu[t];
         for (int t = 0; t < NFA_N2HP_LEVELS; ++t) h_nu[NFA_T_N2HP + t] = nfa_n2hp_nu[t];
@@ -455,13 +411,6 @@ int nfa_set_iemtex_table(const double *t0_x, const double *t0_y, int64_t n) {
 }
 
 // ---- spectra ---------------------------------------------------------------
-int nfa_specset_create(nfa_specset **out, int n_spec, const int64_t *sizes,
-                       const int32_t *trans_ids, const double *const *xarr,
-                       int64_t n_pix, const double *data, const double *noise) {
-    return nfa_specset_create_model(out, NFA_MODEL_AMMONIA, n_spec, sizes, trans_ids, nullptr, xarr, n_pix,
-                                    data, noise);
-}
-
 // sums of data^2 per row of 64 channels (chi^2 of the rows without a line window) of pixels
 // [pix0, pix0 + n)
 static int launch_rowsq(nfa_specset *ss, int64_t pix0, int64_t n) {
@@ -514,287 +463,34 @@ static int launch_tmpl_setup(nfa_specset *ss, int64_t pix0, int64_t n, bool form
     return NFA_OK;
 }
 
-// The caller's line tables of the hyperfine model (nfa_specset_create_lines): n_lines[n_spec], and the spectra's offsets
-// and weights concatenated; `lte`: the LTE model's record as well (nfa_specset_create_lte), null for the hyperfine model;
-// `band`, `line_nu`: a banded LTE set's record and the rest frequency of every line's own transition
-// (nfa_specset_create_lte_bands), null otherwise; `mix`: the record of a set of several species, which has 3 + n_species
-// parameters per component (nfa_specset_create_lte_mix), null otherwise; `filled`: with a beam filling factor as one more,
-// the last (nfa_specset_create_lte_filled)
-struct LineTables { const int32_t *n_lines; const double *voff, *tau_wts; const LteRec *lte; const BandRec *band; const double *line_nu;
-                    const MixRec *mix = nullptr; bool filled = false; };
-
-static int specset_fill(nfa_specset *ss, int model, int n_spec, const int64_t *sizes, const int32_t *trans_ids,
-                        const double *rest_freqs, const double *const *xarr, int64_t n_pix, const double *data,
-                        const double *noise, const double *chan_noise, const LineTables *lines) {
-    SpecDev &d = ss->dev;
-    d.n_spec = n_spec;
-    d.model = model;
-    const bool tabled = model == NFA_MODEL_HYPERFINE || model == NFA_MODEL_LTE;      // the caller's line tables
-    d.npar = model == NFA_MODEL_DIAZENYLIUM || tabled ? NFA_N2HP_PARAMS
-           : model == NFA_MODEL_GAUSSIAN ? NFA_GAUSS_PARAMS : NFA_N_PARAMS;
-    if (model == NFA_MODEL_LTE && lines->mix) d.npar = 3 + lines->mix->n_species + (lines->filled ? 1 : 0);
-    ss->filled = model == NFA_MODEL_LTE && lines->mix && lines->filled;
-    std::vector<LineRow> h_lines((size_t)n_spec, LineRow{});          // the line rows of the spectra
-    int64_t tot = 0, rows = 0, line0 = 0;
-    for (int s = 0; s < n_spec; ++s) {
-        if (sizes[s] < 2 || sizes[s] > (1 << 24)) return fail(NFA_ERR_ARG, "spectrum size out of range");
-        int tglob;                                                      // index into the device tables
-        if (model == NFA_MODEL_AMMONIA) {
-            if (trans_ids[s] < 1 || trans_ids[s] > NFA_N_LEVELS)        // ammonia.pyx:268
-                return fail(NFA_ERR_ARG, "trans_id must be in 1..9");
-            tglob = trans_ids[s] - 1;
-            d.rest[s] = nfa_nu[tglob];
-            ss->nhf_max = std::max(ss->nhf_max, nfa_nhf[tglob]);
-        } else if (model == NFA_MODEL_DIAZENYLIUM) {
-            if (trans_ids[s] < 1 || trans_ids[s] > NFA_N2HP_LEVELS)     // diazenylium.pyx:128
-                return fail(NFA_ERR_ARG, "trans_id must be in 1..3");
-            tglob = NFA_T_N2HP + trans_ids[s] - 1;
-            d.rest[s] = nfa_n2hp_nu[trans_ids[s] - 1];
-            ss->nhf_max = std::max(ss->nhf_max, nfa_n2hp_nhf[trans_ids[s] - 1]);
-        } else if (model == NFA_MODEL_GAUSSIAN) {
-            tglob = NFA_T_GAUSS;
-            d.rest[s] = rest_freqs ? rest_freqs[s] : 0.0;               // core.pyx:510
-            ss->nhf_max = std::max(ss->nhf_max, 1);
-        } else {
-            tglob = NFA_T_LINES;
-            d.rest[s] = rest_freqs[s];
-            ss->nhf_max = std::max(ss->nhf_max, (int)lines->n_lines[s]);
-        }
-        {
-            double nu; const double *voff, *tauw;
-            int n;
-            if (tabled) {
-                n = lines->n_lines[s]; nu = rest_freqs[s]; voff = lines->voff + line0; tauw = lines->tau_wts + line0;
-                line0 += n;
-            } else {
-                n = builtin_table(tglob, &nu, &voff, &tauw);
-            }
-            ss->h_nhf[s] = n;
-            if (tabled && lines->band) line_row_fill_band(h_lines[s], n, lines->line_nu + (line0 - n), voff, tauw);
-            else line_row_fill(h_lines[s], n, nu, voff, tauw);
-        }
-        const double nu_chan = xarr[s][1] - xarr[s][0];
-        if (!(nu_chan > 0)) return fail(NFA_ERR_ARG, "frequency axis must be ascending");   // core.pyx:503-504
-        d.size[s] = (int)sizes[s];
-        d.trans[s] = tglob + 1;
-        d.off[s] = (int)tot;
-        d.row_off[s] = (int)rows;
-        d.nu_min[s] = xarr[s][0];
-        d.nu_chan[s] = nu_chan;
-        {   // the reciprocal nf_line divides with (0: a width that is not an ordinary number, or whose mantissa is all ones)
-            uint64_t bits; memcpy(&bits, &nu_chan, sizeof bits);
-            const bool ordinary = std::isnormal(nu_chan) && nu_chan > 1e-100 && nu_chan < 1e100;
-            d.r_chan[s] = ordinary && (bits & 0xfffffffffffffull) != 0xfffffffffffffull ? 1.0 / nu_chan : 0.0;
-        }
-        tot += sizes[s];
-        rows += (sizes[s] + 63) / 64;
-    }
-    for (int64_t i = 0; i < n_pix * n_spec; ++i)
-        if (!(noise[i] > 0)) return fail(NFA_ERR_ARG, "noise must be > 0");                 // core.pyx:502
-    d.chan_tot = tot;
-    d.rows_tot = rows;
-    ss->n_pix = n_pix;
-    std::vector<double> xcat(tot);
-    for (int s = 0; s < n_spec; ++s) memcpy(xcat.data() + d.off[s], xarr[s], sizeof(double) * sizes[s]);
-    HIP_TRY(hipMalloc(&ss->d_xarr, sizeof(double) * tot));
-    HIP_TRY(hipMalloc(&ss->d_t0, sizeof(double) * tot));
-    HIP_TRY(hipMalloc(&ss->d_tbg, sizeof(double) * tot));
-    HIP_TRY(hipMalloc(&ss->d_t0tbg, sizeof(double) * tot));
-    HIP_TRY(hipMalloc(&ss->d_data, sizeof(double) * tot * n_pix));
-    HIP_TRY(hipMalloc(&ss->d_noise, sizeof(double) * n_spec * n_pix));
-    HIP_TRY(hipMalloc(&ss->d_rowsq, sizeof(double) * rows * n_pix));
-    HIP_TRY(hipMalloc(&ss->d_totsq, sizeof(double) * n_spec * n_pix));
-    HIP_TRY(hipMemcpy(ss->d_xarr, xcat.data(), sizeof(double) * tot, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ss->d_data, data, sizeof(double) * tot * n_pix, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ss->d_noise, noise, sizeof(double) * n_spec * n_pix, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0,
-                       ss->d_xarr, ss->d_t0, ss->d_tbg, ss->d_t0tbg, (long)tot);
-    HIP_TRY(hipGetLastError());
-    d.xarr = ss->d_xarr; d.t0 = ss->d_t0; d.tbg = ss->d_tbg; d.data = ss->d_data; d.noise = ss->d_noise;
-    d.t0tbg = ss->d_t0tbg; d.rowsq = ss->d_rowsq; d.totsq = ss->d_totsq;
-    d.bl_order = ss->opt.o.bl_order;                                    // no option yet (the nfa_specset_set_* calls): their pointers stay null
-    HIP_TRY(hipMalloc(&ss->d_lines, sizeof(LineRow) * n_spec));
-    HIP_TRY(hipMemcpy(ss->d_lines, h_lines.data(), sizeof(LineRow) * n_spec, hipMemcpyHostToDevice));
-    d.lines = ss->d_lines;
-    if (model == NFA_MODEL_LTE) {
-        HIP_TRY(hipMalloc(&ss->d_lte, sizeof(LteRec)));
-        HIP_TRY(hipMemcpy(ss->d_lte, lines->lte, sizeof(LteRec), hipMemcpyHostToDevice));
-        d.lte_rec = ss->d_lte;
-    }
-    if (model == NFA_MODEL_LTE && lines->band) {
-        HIP_TRY(hipMalloc(&ss->d_band, sizeof(BandRec)));
-        HIP_TRY(hipMemcpy(ss->d_band, lines->band, sizeof(BandRec), hipMemcpyHostToDevice));
-        d.band = ss->d_band;
-    }
-    if (model == NFA_MODEL_LTE && lines->mix) {
-        HIP_TRY(hipMalloc(&ss->d_mix, sizeof(MixRec)));
-        HIP_TRY(hipMemcpy(ss->d_mix, lines->mix, sizeof(MixRec), hipMemcpyHostToDevice));
-        d.mix = ss->d_mix;
-    }
-    if (chan_noise) {
-        HIP_TRY(hipMalloc(&ss->d_w, sizeof(double) * tot * n_pix));
-        HIP_TRY(hipMalloc(&ss->d_wdata, sizeof(double) * tot * n_pix));
-        HIP_TRY(hipMemcpy(ss->d_w, chan_noise, sizeof(double) * tot * n_pix, hipMemcpyHostToDevice));
-        d.chan_w = ss->d_w; d.wdata = ss->d_wdata;
-        ss->chan_noise = true;
-        int rc = launch_chan_weight(ss, 0, n_pix, true); if (rc) return rc;
-    }
-    return launch_rowsq(ss, 0, n_pix);
-}
-
-static int specset_create(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
-                          const int32_t *trans_ids, const double *rest_freqs,
-                          const double *const *xarr, int64_t n_pix, const double *data,
-                          const double *noise, const double *chan_noise, const LineTables *lines = nullptr) {
-    if (model == NFA_MODEL_HYPERFINE && !lines)
-        return fail(NFA_ERR_ARG, "the hyperfine model takes its line tables through nfa_specset_create_lines");
-    if (model == NFA_MODEL_LTE && !(lines && lines->lte))
-        return fail(NFA_ERR_ARG, "unknown model to this creator: the LTE model takes its line tables and partition function "
-                                 "through nfa_specset_create_lte");
-    if (model < NFA_MODEL_AMMONIA || model > NFA_MODEL_LTE) return fail(NFA_ERR_ARG, "unknown model");
-    if (model != NFA_MODEL_GAUSSIAN && !lines && !trans_ids) return fail(NFA_ERR_ARG, "null argument");
-    if (model == NFA_MODEL_GAUSSIAN && n_spec != 1)                     // gaussian.pyx:57-89
-        return fail(NFA_ERR_ARG, "the Gaussian model takes one spectrum");
-    if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
-    if (n_pix < 1) return fail(NFA_ERR_ARG, "n_pix must be >= 1");
-    int rc = engine_init(); if (rc) return rc;
-    nfa_specset *ss = new nfa_specset();
-    rc = specset_fill(ss, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, noise, chan_noise, lines);
-    if (rc) { nfa_specset_destroy(ss); return rc; }          // frees whatever was allocated
-    *out = ss;
-    return NFA_OK;
-}
+// The creators of include/nestfit_amd.h: each fills its prefix of the declaration (SetDecl, nfa_set_decl.h) with what it was
+// given, and specset_build, behind specset_realise below, makes the set of it.
+static int specset_build(nfa_specset **out, const SetDecl &decl);
 
 int nfa_specset_create_model(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
                              const int32_t *trans_ids, const double *rest_freqs,
                              const double *const *xarr, int64_t n_pix, const double *data,
                              const double *noise) {
-    if (!out || !sizes || !xarr || !data || !noise) return fail(NFA_ERR_ARG, "null argument");
-    return specset_create(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, noise, nullptr);
+    return specset_build(out, SetDecl{DECL_MODEL, out, model, n_spec, sizes, xarr, n_pix, data, noise, nullptr, rest_freqs, trans_ids});
 }
-
-// sigma_ref of every (pixel, spectrum) -- the smallest finite sigma_c -- after the checks of the declaration
-static int specset_create_channel_noise(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
-                                        const int32_t *trans_ids, const double *rest_freqs,
-                                        const double *const *xarr, int64_t n_pix, const double *data,
-                                        const double *chan_noise, const LineTables *lines) {
-    if (!out || !sizes || !xarr || !data || !chan_noise) return fail(NFA_ERR_ARG, "null argument");
-    if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
-    if (n_pix < 1) return fail(NFA_ERR_ARG, "n_pix must be >= 1");
-    int64_t tot = 0;
-    for (int s = 0; s < n_spec; ++s) {
-        if (sizes[s] < 2 || sizes[s] > (1 << 24)) return fail(NFA_ERR_ARG, "spectrum size out of range");
-        tot += sizes[s];
-    }
-    std::vector<double> ref((size_t)(n_pix * n_spec));
-    bool masked = false;
-    for (int64_t p = 0; p < n_pix; ++p) {
-        int64_t c = p * tot;
-        for (int s = 0; s < n_spec; ++s) {
-            double lo = INFINITY;
-            for (int64_t j = 0; j < sizes[s]; ++j, ++c) {
-                const double sg = chan_noise[c];
-                if (!(sg > 0)) return fail(NFA_ERR_ARG, "channel noise must be > 0 (NaN is not allowed; inf masks the channel)");
-                if (sg == INFINITY) { masked = true; continue; }
-                if (std::isnan(data[c])) return fail(NFA_ERR_ARG, "NaN data in a channel that is not masked (channel noise inf masks it)");
-                lo = std::min(lo, sg);
-            }
-            if (lo == INFINITY) return fail(NFA_ERR_ARG, "every channel of a spectrum is masked (channel noise inf)");
-            ref[(size_t)(p * n_spec + s)] = lo;
-        }
-    }
-    const int rc = specset_create(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, ref.data(), chan_noise, lines);
-    if (rc == NFA_OK) (*out)->masked = masked;
-    return rc;
+int nfa_specset_create(nfa_specset **out, int n_spec, const int64_t *sizes,
+                       const int32_t *trans_ids, const double *const *xarr,
+                       int64_t n_pix, const double *data, const double *noise) {
+    return specset_build(out, SetDecl{DECL_MODEL, out, NFA_MODEL_AMMONIA, n_spec, sizes, xarr, n_pix, data, noise, nullptr, nullptr, trans_ids});
 }
 int nfa_specset_create_channel_noise(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
                                      const int32_t *trans_ids, const double *rest_freqs,
                                      const double *const *xarr, int64_t n_pix, const double *data,
                                      const double *chan_noise) {
-    return specset_create_channel_noise(out, model, n_spec, sizes, trans_ids, rest_freqs, xarr, n_pix, data, chan_noise, nullptr);
-}
-
-// the checks of nfa_specset_create_lines on one table of n lines (`at`: where, for the message)
-static int check_one_table(int n, double nu, const double *voff, const double *tau_wts, const std::string &at) {
-    if (n < 1 || n > NFA_MAX_HF_N) return fail(NFA_ERR_ARG, "a line table must have 1..50 lines" + at);
-    if (!(std::isfinite(nu) && nu > 0)) return fail(NFA_ERR_ARG, "a rest frequency must be finite and positive" + at);
-    bool any = false;
-    for (int i = 0; i < n; ++i) {
-        const double v = voff[i], w = tau_wts[i];
-        if (!(std::isfinite(v) && std::fabs(v) < NFA_CKMS))
-            return fail(NFA_ERR_ARG, "a velocity offset must be finite and below the speed of light" + at);
-        if (!(std::isfinite(w) && w >= 0)) return fail(NFA_ERR_ARG, "a line weight must be finite and not negative" + at);
-        any = any || w > 0;
-    }
-    if (!any) return fail(NFA_ERR_ARG, "the weights of a line table are all zero" + at);
-    return NFA_OK;
-}
-
-// the checks of nfa_specset_create_lines on its own arguments
-static int check_line_tables(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
-                             const double *rest_freqs, const double *voff, const double *tau_wts,
-                             const double *const *xarr, const double *data, const double *noise, const double *chan_noise) {
-    if (!out || !sizes || !n_lines || !rest_freqs || !voff || !tau_wts || !xarr || !data)
-        return fail(NFA_ERR_ARG, "null argument");
-    if ((noise != nullptr) == (chan_noise != nullptr))
-        return fail(NFA_ERR_ARG, "exactly one of noise and chan_noise must be given");
-    if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
-    int64_t l0 = 0;
-    for (int s = 0; s < n_spec; ++s) {
-        const int n = n_lines[s];
-        int rc = check_one_table(n, rest_freqs[s], voff + l0, tau_wts + l0, " (spectrum " + std::to_string(s) + ")");
-        if (rc) return rc;
-        l0 += n;
-    }
-    return NFA_OK;
-}
-
-// the checks of nfa_specset_create_lte on one transition beyond its line table's
-static int check_one_transition(double e_up, double g_up, double a_ul, int n, const double *tau_wts, const std::string &at) {
-    if (!(std::isfinite(e_up) && e_up >= 0))
-        return fail(NFA_ERR_ARG, "an upper-level energy must be finite and not negative (K)" + at);
-    if (!(std::isfinite(g_up) && g_up > 0))
-        return fail(NFA_ERR_ARG, "an upper-level weight must be finite and positive" + at);
-    if (!(std::isfinite(a_ul) && a_ul > 0))
-        return fail(NFA_ERR_ARG, "an Einstein coefficient must be finite and positive (1/s)" + at);
-    double sum = 0.0;
-    for (int i = 0; i < n; ++i) sum += tau_wts[i];
-    if (!(std::fabs(sum - 1.0) <= 1e-6))
-        return fail(NFA_ERR_ARG, "the weights of a transition must sum to 1 within 1e-6" + at);
-    return NFA_OK;
-}
-
-// ... and on the partition function, which it leaves in the record as ln Q over ln T with the segments' slopes
-static int lte_partition_fill(LteRec &rec, int n_q, const double *q_temp, const double *q_val) {
-    if (n_q < 2 || n_q > NFA_LTE_MAXQ) return fail(NFA_ERR_ARG, "a partition table must have 2..64 entries");
-    for (int k = 0; k < n_q; ++k) {
-        if (!(std::isfinite(q_temp[k]) && q_temp[k] > 0 && (k == 0 || q_temp[k] > q_temp[k - 1])))
-            return fail(NFA_ERR_ARG, "the temperatures of a partition table must be finite, positive and strictly ascending");
-        if (!(std::isfinite(q_val[k]) && q_val[k] > 0))
-            return fail(NFA_ERR_ARG, "a partition function value must be finite and positive");
-        rec.ln_t[k] = log(q_temp[k]);
-        rec.ln_q[k] = log(q_val[k]);
-    }
-    for (int k = 0; k + 1 < n_q; ++k) {
-        if (!(rec.ln_t[k + 1] > rec.ln_t[k]))
-            return fail(NFA_ERR_ARG, "the temperatures of a partition table must be finite, positive and strictly ascending");
-        rec.slope[k] = (rec.ln_q[k + 1] - rec.ln_q[k]) / (rec.ln_t[k + 1] - rec.ln_t[k]);
-    }
-    rec.n_q = n_q;
-    return NFA_OK;
+    return specset_build(out, SetDecl{DECL_CHANNEL_NOISE, out, model, n_spec, sizes, xarr, n_pix, data, nullptr, chan_noise, rest_freqs, trans_ids});
 }
 
 int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
                              const double *rest_freqs, const double *voff, const double *tau_wts,
                              const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                              const double *chan_noise) {
-    int rc = check_line_tables(out, n_spec, sizes, n_lines, rest_freqs, voff, tau_wts, xarr, data, noise, chan_noise);
-    if (rc) return rc;
-    const LineTables lt = {n_lines, voff, tau_wts, nullptr, nullptr, nullptr};
-    if (chan_noise)
-        return specset_create_channel_noise(out, NFA_MODEL_HYPERFINE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data,
-                                            chan_noise, &lt);
-    return specset_create(out, NFA_MODEL_HYPERFINE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data, noise, nullptr, &lt);
+    return specset_build(out, SetDecl{DECL_LINES, out, NFA_MODEL_HYPERFINE, n_spec, sizes, xarr, n_pix, data, noise, chan_noise, rest_freqs, nullptr,
+                                      n_lines, voff, tau_wts});
 }
 
 int nfa_specset_create_lte(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
@@ -803,95 +499,9 @@ int nfa_specset_create_lte(nfa_specset **out, int n_spec, const int64_t *sizes, 
                            int n_q, const double *q_temp, const double *q_val,
                            const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                            const double *chan_noise) {
-    int rc = check_line_tables(out, n_spec, sizes, n_lines, rest_freqs, voff, tau_wts, xarr, data, noise, chan_noise);
-    if (rc) return rc;
-    if (!e_up || !g_up || !a_ul || !q_temp || !q_val) return fail(NFA_ERR_ARG, "null argument");
-    LteRec rec = {};
-    int64_t l0 = 0;
-    for (int s = 0; s < n_spec; ++s) {
-        rc = check_one_transition(e_up[s], g_up[s], a_ul[s], n_lines[s], tau_wts + l0, " (spectrum " + std::to_string(s) + ")");
-        if (rc) return rc;
-        l0 += n_lines[s];
-        rec.e_up[s] = e_up[s]; rec.g_up[s] = g_up[s]; rec.a_ul[s] = a_ul[s];
-    }
-    rc = lte_partition_fill(rec, n_q, q_temp, q_val); if (rc) return rc;
-    const LineTables lt = {n_lines, voff, tau_wts, &rec, nullptr, nullptr};
-    if (chan_noise)
-        return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data,
-                                            chan_noise, &lt);
-    return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, rest_freqs, xarr, n_pix, data, noise, nullptr, &lt);
-}
-
-// What the bands creator and the mix creator share: the checks per transition, and the spectra's transitions in the engine's
-// order with their lines one after the other -- the band record, the reference transitions' numbers for the set-up stage
-// (rec, s_rest) and the flattened line arrays.  `species` (null: one species): the species of every transition, which goes
-// into the mix record in the band's order; the same transition twice is then refused within a species.
-struct BandLayout {
-    LteRec rec = {};
-    BandRec band = {};
-    MixRec mix = {};
-    std::vector<int32_t> s_lines;
-    std::vector<double> s_rest, l_voff, l_wts, l_nu;
-};
-static int band_layout(BandLayout &L, int n_spec, const int32_t *n_trans, const int32_t *n_lines, const double *trans_freqs,
-                       const double *voff, const double *tau_wts, const double *e_up, const double *g_up, const double *a_ul,
-                       const int32_t *species) {
-    // the spectra's transitions in the engine's order -- ascending lower-level energy, then rest frequency, then the caller's
-    // order -- and their lines one after the other: what the caller's order of a spectrum's transitions cannot change
-    L.s_lines.assign((size_t)n_spec, 0);
-    L.s_rest.assign((size_t)n_spec, 0.0);
-    int64_t tr0 = 0, l0 = 0;
-    for (int s = 0; s < n_spec; ++s) {
-        const int nt = n_trans[s];
-        std::vector<int64_t> first((size_t)nt);                     // the first line of every transition
-        std::vector<double> e_low((size_t)nt);
-        int total = 0;
-        for (int j = 0; j < nt; ++j) {
-            const int64_t t = tr0 + j;
-            const std::string at = " (spectrum " + std::to_string(s) + ", transition " + std::to_string(j) + ")";
-            first[j] = l0;
-            if (n_lines[t] >= 1 && n_lines[t] <= NFA_MAX_HF_N && total + n_lines[t] > NFA_MAX_HF_N)
-                return fail(NFA_ERR_ARG, "the transitions of a spectrum must have at most 50 lines together (spectrum " + std::to_string(s) + ")");
-            int rc = check_one_table(n_lines[t], trans_freqs[t], voff + l0, tau_wts + l0, at); if (rc) return rc;
-            rc = check_one_transition(e_up[t], g_up[t], a_ul[t], n_lines[t], tau_wts + l0, at); if (rc) return rc;
-            for (int i = 0; i < j; ++i)
-                if ((!species || species[tr0 + i] == species[t]) && trans_freqs[tr0 + i] == trans_freqs[t] && e_up[tr0 + i] == e_up[t] &&
-                    g_up[tr0 + i] == g_up[t] && a_ul[tr0 + i] == a_ul[t])
-                    return fail(NFA_ERR_ARG, (species ? "a spectrum lists the same transition of a species twice" : "a spectrum lists the same transition twice") + at);
-            e_low[j] = e_up[t] - NFA_H * trans_freqs[t] / NFA_KB;
-            total += n_lines[t];
-            l0 += n_lines[t];
-        }
-        std::vector<int> order((size_t)nt);
-        for (int j = 0; j < nt; ++j) order[j] = j;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-            return e_low[a] != e_low[b] ? e_low[a] < e_low[b] : trans_freqs[tr0 + a] < trans_freqs[tr0 + b];
-        });
-        const int64_t r = tr0 + order[0];                           // the reference transition
-        const double ref_t0 = NFA_H * trans_freqs[r] / NFA_KB;
-        const double ref_k = g_up[r] * a_ul[r] / (trans_freqs[r] * trans_freqs[r] * trans_freqs[r]);
-        L.s_rest[s] = trans_freqs[r];
-        L.rec.e_up[s] = e_up[r]; L.rec.g_up[s] = g_up[r]; L.rec.a_ul[s] = a_ul[r];
-        L.band.n_trans[s] = nt;
-        int line = 0;
-        for (int g = 0; g < nt; ++g) {
-            const int64_t t = tr0 + order[g];
-            const double nu = trans_freqs[t], tg = NFA_H * nu / NFA_KB;
-            L.band.t0[s][g] = tg;
-            L.band.de[s][g] = (e_up[t] - tg) - (e_up[r] - ref_t0);
-            L.band.k[s][g] = (g_up[t] * a_ul[t] / (nu * nu * nu)) / ref_k;
-            if (species) L.mix.species[s][g] = (unsigned char)species[t];
-            for (int i = 0; i < n_lines[t]; ++i, ++line) {
-                L.band.grp[s][line] = (unsigned char)g;
-                L.l_voff.push_back(voff[first[order[g]] + i]);
-                L.l_wts.push_back(tau_wts[first[order[g]] + i]);
-                L.l_nu.push_back(nu);
-            }
-        }
-        L.s_lines[s] = line;
-        tr0 += nt;
-    }
-    return NFA_OK;
+    const int32_t nq = n_q;
+    return specset_build(out, SetDecl{DECL_LTE, out, NFA_MODEL_LTE, n_spec, sizes, xarr, n_pix, data, noise, chan_noise, rest_freqs, nullptr,
+                                      n_lines, voff, tau_wts, e_up, g_up, a_ul, &nq, q_temp, q_val});
 }
 
 int nfa_specset_create_lte_bands(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
@@ -900,95 +510,9 @@ int nfa_specset_create_lte_bands(nfa_specset **out, int n_spec, const int64_t *s
                                  int n_q, const double *q_temp, const double *q_val,
                                  const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                                  const double *chan_noise) {
-    if (!out || !sizes || !n_trans || !n_lines || !trans_freqs || !voff || !tau_wts || !xarr || !data)
-        return fail(NFA_ERR_ARG, "null argument");
-    if ((noise != nullptr) == (chan_noise != nullptr))
-        return fail(NFA_ERR_ARG, "exactly one of noise and chan_noise must be given");
-    if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
-    bool banded = false;
-    for (int s = 0; s < n_spec; ++s) {
-        if (n_trans[s] < 1 || n_trans[s] > NFA_BAND_MAXT)
-            return fail(NFA_ERR_ARG, "a spectrum must have 1..8 transitions (spectrum " + std::to_string(s) + ")");
-        banded = banded || n_trans[s] > 1;
-    }
-    // a transition per spectrum: nfa_specset_create_lte's set, bit for bit, on its routes
-    if (!banded)
-        return nfa_specset_create_lte(out, n_spec, sizes, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, n_q, q_temp, q_val,
-                                      xarr, n_pix, data, noise, chan_noise);
-    if (!e_up || !g_up || !a_ul || !q_temp || !q_val) return fail(NFA_ERR_ARG, "null argument");
-    BandLayout L;
-    int rc = band_layout(L, n_spec, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, nullptr); if (rc) return rc;
-    rc = lte_partition_fill(L.rec, n_q, q_temp, q_val); if (rc) return rc;
-    const LineTables lt = {L.s_lines.data(), L.l_voff.data(), L.l_wts.data(), &L.rec, &L.band, L.l_nu.data()};
-    if (chan_noise)
-        return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data,
-                                            chan_noise, &lt);
-    return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data, noise, nullptr, &lt);
-}
-
-// nfa_specset_create_lte_mix, and with `filled` nfa_specset_create_lte_filled: the same checks and records, one more
-// parameter per component.  A filled set owns its band and mix records whatever it holds -- one species, a transition per
-// spectrum -- so that launch_band runs for it.
-static int create_lte_mix(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
-                          const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
-                          const double *e_up, const double *g_up, const double *a_ul,
-                          int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
-                          const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
-                          const double *chan_noise, bool filled) {
-    if (!out || !sizes || !n_trans || !n_lines || !trans_freqs || !voff || !tau_wts || !xarr || !data || !species || !n_q)
-        return fail(NFA_ERR_ARG, "null argument");
-    if (n_species < 1 || n_species > NFA_LTE_MAXSP) return fail(NFA_ERR_ARG, "n_species must be in 1..4");
-    if ((noise != nullptr) == (chan_noise != nullptr))
-        return fail(NFA_ERR_ARG, "exactly one of noise and chan_noise must be given");
-    if (n_spec < 1 || n_spec > MAXSPEC) return fail(NFA_ERR_ARG, "n_spec must be in 1..16");
-    int64_t n_all = 0;
-    for (int s = 0; s < n_spec; ++s) {
-        if (n_trans[s] < 1 || n_trans[s] > NFA_BAND_MAXT)
-            return fail(NFA_ERR_ARG, "a spectrum must have 1..8 transitions (spectrum " + std::to_string(s) + ")");
-        n_all += n_trans[s];
-    }
-    bool seen[NFA_LTE_MAXSP] = {};
-    for (int64_t t = 0; t < n_all; ++t) {
-        if (species[t] < 0 || species[t] >= n_species)
-            return fail(NFA_ERR_ARG, "a species index must be in 0..n_species - 1 (transition " + std::to_string(t) + ")");
-        seen[species[t]] = true;
-    }
-    for (int k = 0; k < n_species; ++k)
-        if (!seen[k])
-            return fail(NFA_ERR_ARG, "a species without a transition in any spectrum: its column density would be unconstrained (species "
-                                     + std::to_string(k) + ")");
-    // one species: the bands creator's set, bit for bit, on its routes
-    if (n_species == 1 && !filled)
-        return nfa_specset_create_lte_bands(out, n_spec, sizes, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul,
-                                            n_q[0], q_temp, q_val, xarr, n_pix, data, noise, chan_noise);
-    if (!e_up || !g_up || !a_ul || !q_temp || !q_val) return fail(NFA_ERR_ARG, "null argument");
-    BandLayout L;
-    LteRec &rec = L.rec;
-    MixRec &mix = L.mix;
-    mix.n_species = n_species;
-    int rc = band_layout(L, n_spec, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, species); if (rc) return rc;
-    // the partition tables: species 0's where the set-up stage reads it, the others' in the mix record
-    int64_t q0 = 0;
-    for (int k = 0; k < n_species; ++k) {
-        LteRec one = {};
-        const int nq = n_q[k];
-        rc = lte_partition_fill(k == 0 ? rec : one, nq, q_temp + q0, q_val + q0);
-        if (rc) { const std::string why = g_err; return fail(rc, why + " (species " + std::to_string(k) + ")"); }
-        if (k > 0) {
-            mix.n_q[k - 1] = nq;
-            std::copy(one.ln_t, one.ln_t + NFA_LTE_MAXQ, mix.ln_t[k - 1]);
-            std::copy(one.ln_q, one.ln_q + NFA_LTE_MAXQ, mix.ln_q[k - 1]);
-            std::copy(one.slope, one.slope + NFA_LTE_MAXQ, mix.slope[k - 1]);
-        }
-        q0 += nq;
-    }
-    LineTables lt = {L.s_lines.data(), L.l_voff.data(), L.l_wts.data(), &rec, &L.band, L.l_nu.data()};
-    lt.mix = &mix;
-    lt.filled = filled;
-    if (chan_noise)
-        return specset_create_channel_noise(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data,
-                                            chan_noise, &lt);
-    return specset_create(out, NFA_MODEL_LTE, n_spec, sizes, nullptr, L.s_rest.data(), xarr, n_pix, data, noise, nullptr, &lt);
+    const int32_t nq = n_q;
+    return specset_build(out, SetDecl{DECL_BANDS, out, NFA_MODEL_LTE, n_spec, sizes, xarr, n_pix, data, noise, chan_noise, trans_freqs, nullptr,
+                                      n_lines, voff, tau_wts, e_up, g_up, a_ul, &nq, q_temp, q_val, n_trans});
 }
 
 int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
@@ -997,18 +521,20 @@ int nfa_specset_create_lte_mix(nfa_specset **out, int n_spec, const int64_t *siz
                                int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
                                const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                                const double *chan_noise) {
-    return create_lte_mix(out, n_spec, sizes, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, n_species, species, n_q,
-                          q_temp, q_val, xarr, n_pix, data, noise, chan_noise, false);
+    return specset_build(out, SetDecl{DECL_MIX, out, NFA_MODEL_LTE, n_spec, sizes, xarr, n_pix, data, noise, chan_noise, trans_freqs, nullptr,
+                                      n_lines, voff, tau_wts, e_up, g_up, a_ul, n_q, q_temp, q_val, n_trans, n_species, species});
 }
 
+// nfa_specset_create_lte_mix with one more parameter per component.  A filled set owns its band and mix records whatever it
+// holds -- one species, a transition per spectrum -- so that launch_band runs for it (SetKind, nfa_set_decl.h).
 int nfa_specset_create_lte_filled(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_trans,
                                   const int32_t *n_lines, const double *trans_freqs, const double *voff, const double *tau_wts,
                                   const double *e_up, const double *g_up, const double *a_ul,
                                   int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
                                   const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                                   const double *chan_noise) {
-    return create_lte_mix(out, n_spec, sizes, n_trans, n_lines, trans_freqs, voff, tau_wts, e_up, g_up, a_ul, n_species, species, n_q,
-                          q_temp, q_val, xarr, n_pix, data, noise, chan_noise, true);
+    return specset_build(out, SetDecl{DECL_FILLED, out, NFA_MODEL_LTE, n_spec, sizes, xarr, n_pix, data, noise, chan_noise, trans_freqs, nullptr,
+                                      n_lines, voff, tau_wts, e_up, g_up, a_ul, n_q, q_temp, q_val, n_trans, n_species, species});
 }
 
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n) {
@@ -1096,7 +622,9 @@ static void specset_point(nfa_specset *ss, const SetOptions &o, const SetLayout 
 // there; a failure frees what this call allocated and returns with nothing the kernels read touched.  2. Copy the small
 // arrays up, point SpecDev at the layout's buffers and run the stages in their order; *touched says this phase began.
 // 3. Free what the layout does not need.  A call turns one option on or off, so its peak memory is max(before, after).
-static int specset_realise(nfa_specset *ss, const SetRecord &next, int64_t pix0, int64_t n, unsigned work, bool *touched = nullptr) {
+// `sigmas`: the caller's noise per channel [n_pix][chan_tot] for ST_FORM_W, the stage of a set's creation.
+static int specset_realise(nfa_specset *ss, const SetRecord &next, int64_t pix0, int64_t n, unsigned work, bool *touched = nullptr,
+                           const double *sigmas = nullptr) {
     SpecDev &d = ss->dev;
     const SetOptions &o = next.o;
     const SetLayout L = set_layout(o, ss->chan_noise);
@@ -1145,7 +673,8 @@ static int specset_realise(nfa_specset *ss, const SetRecord &next, int64_t pix0,
         std::vector<double> one(all, 1.0);
         HIP_TRY(hipMemcpy(ss->d_w, one.data(), sizeof(double) * all, hipMemcpyHostToDevice));
     }
-    if (work & ST_CHAN_WEIGHT) { rc = launch_chan_weight(ss, pix0, n, false); if (rc) return rc; }      // the mask stays
+    if (work & ST_FORM_W) HIP_TRY(hipMemcpy(ss->d_w, sigmas, sizeof(double) * all, hipMemcpyHostToDevice));       // creation alone
+    if (work & ST_CHAN_WEIGHT) { rc = launch_chan_weight(ss, pix0, n, (work & ST_FORM_W) != 0); if (rc) return rc; }      // (otherwise the mask stays)
     if (work & ST_CORR) { rc = launch_corr_setup(ss, pix0, n, (work & ST_FORM_Q) != 0); if (rc) return rc; }
     if (work & ST_ROWSQ) { rc = launch_rowsq(ss, pix0, n); if (rc) return rc; }
     if (work & ST_ROB) {              // g, g d, totsq = k C and the records; the spectra with nu = 0 keep the sums beneath
@@ -1173,6 +702,57 @@ static int specset_realise(nfa_specset *ss, const SetRecord &next, int64_t pix0,
 
     for (const SetBuf &b : SET_BUFS)
         if (!L.has(b.bit) && ss->*b.p) { (void)hipFree(ss->*b.p); ss->*b.p = nullptr; }
+    return NFA_OK;
+}
+
+static int upload(void *dst, const void *src, size_t bytes) {          // dst: where the device pointer goes
+    HIP_TRY(hipMalloc((void **)dst, bytes));
+    HIP_TRY(hipMemcpy(*(void **)dst, src, bytes, hipMemcpyHostToDevice));
+    return NFA_OK;
+}
+// A set from its declaration.  The header's part first (nfa_set_decl.h: every check and every host-side record, no device
+// call), then the device: the base arrays go up, and the rest is specset_realise of the empty options record with every stage
+// -- for a noise per channel the weights' buffers, w from the sigmas and w d, for every set the sums.
+static int specset_upload(nfa_specset *ss, const SetDecl &decl, const SetPlan &p) {
+    SpecDev &d = ss->dev;
+    d.n_spec = p.n_spec; d.model = p.model; d.npar = p.npar; d.chan_tot = p.chan_tot; d.rows_tot = p.rows_tot;
+    memcpy(d.rest, p.rest, sizeof d.rest); memcpy(d.size, p.size, sizeof d.size); memcpy(d.trans, p.trans, sizeof d.trans);
+    memcpy(d.off, p.off, sizeof d.off); memcpy(d.row_off, p.row_off, sizeof d.row_off); memcpy(d.nu_min, p.nu_min, sizeof d.nu_min);
+    memcpy(d.nu_chan, p.nu_chan, sizeof d.nu_chan); memcpy(d.r_chan, p.r_chan, sizeof d.r_chan);
+    ss->n_pix = p.n_pix; ss->nhf_max = p.nhf_max; memcpy(ss->h_nhf, p.h_nhf, sizeof ss->h_nhf);
+    ss->filled = p.filled; ss->chan_noise = p.chan_noise; ss->masked = p.masked;
+    const int64_t tot = p.chan_tot, spec = p.n_pix * p.n_spec;
+    std::vector<double> xcat(tot);
+    for (int s = 0; s < p.n_spec; ++s) memcpy(xcat.data() + p.off[s], decl.xarr[s], sizeof(double) * p.size[s]);
+    // (the allocations in the order they always had: where the buffers lie relative to each other is part of the likelihood's speed)
+    for (double **b : {&ss->d_xarr, &ss->d_t0, &ss->d_tbg, &ss->d_t0tbg}) HIP_TRY(hipMalloc(b, sizeof(double) * tot));
+    HIP_TRY(hipMalloc(&ss->d_data, sizeof(double) * tot * p.n_pix));
+    HIP_TRY(hipMalloc(&ss->d_noise, sizeof(double) * spec));
+    HIP_TRY(hipMalloc(&ss->d_rowsq, sizeof(double) * p.rows_tot * p.n_pix));
+    HIP_TRY(hipMalloc(&ss->d_totsq, sizeof(double) * spec));
+    HIP_TRY(hipMemcpy(ss->d_xarr, xcat.data(), sizeof(double) * tot, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ss->d_data, decl.data, sizeof(double) * tot * p.n_pix, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ss->d_noise, p.chan_noise ? p.sigma_ref.data() : decl.noise, sizeof(double) * spec, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0,
+                       ss->d_xarr, ss->d_t0, ss->d_tbg, ss->d_t0tbg, (long)tot);
+    HIP_TRY(hipGetLastError());
+    d.xarr = ss->d_xarr; d.t0 = ss->d_t0; d.tbg = ss->d_tbg; d.data = ss->d_data; d.noise = ss->d_noise;
+    d.t0tbg = ss->d_t0tbg; d.rowsq = ss->d_rowsq; d.totsq = ss->d_totsq;
+    int rc = upload(&ss->d_lines, p.lines, sizeof(LineRow) * p.n_spec); if (rc) return rc;
+    d.lines = ss->d_lines;
+    if (p.kind >= SET_LTE) { rc = upload(&ss->d_lte, &p.lte, sizeof p.lte); if (rc) return rc; d.lte_rec = ss->d_lte; }
+    if (p.kind >= SET_BANDS) { rc = upload(&ss->d_band, &p.band, sizeof p.band); if (rc) return rc; d.band = ss->d_band; }
+    if (p.kind == SET_MIX) { rc = upload(&ss->d_mix, &p.mix, sizeof p.mix); if (rc) return rc; d.mix = ss->d_mix; }
+    return specset_realise(ss, ss->opt, 0, p.n_pix, set_stages_create(set_layout(ss->opt.o, p.chan_noise)), nullptr, decl.chan_noise);
+}
+static int specset_build(nfa_specset **out, const SetDecl &decl) {
+    SetPlan p; std::string why;
+    int rc = set_plan(decl, p, why); if (rc) return fail(rc, why);
+    rc = engine_init(); if (rc) return rc;
+    nfa_specset *ss = new nfa_specset();
+    rc = specset_upload(ss, decl, p);
+    if (rc) { nfa_specset_destroy(ss); return rc; }          // frees whatever was allocated
+    *out = ss;
     return NFA_OK;
 }
 

@@ -104,6 +104,7 @@ enum : unsigned {
     ST_TP = 1u << 16,             // launch_tmpl_setup: m(d)                      reads: d_wdata, the templates
     ST_TP_BASIS = 1u << 17,       // ... with form_basis                          reads: d_w, the templates, the baseline order
     ST_NMARG = 1u << 18,          // nmarg_setup_kernel                           reads: d_w, the noise uncertainties
+    ST_FORM_W = 1u << 19,         // beside ST_CHAN_WEIGHT, with form_w: w too, from the caller's sigmas, which go into d_w first
     ST_DATA = ST_CHAN_WEIGHT | ST_CORR | ST_ROWSQ | ST_ROB | ST_BL | ST_TP     // the stages that read the data (or what they make of them)
 };
 // (Through the buffers a stage reads the options that decide their presence or content: the set's own weights of a scalar noise
@@ -127,6 +128,8 @@ inline unsigned set_stages_all(const SetLayout &L) {
     if (L.has(SB_NMARG)) st |= ST_NMARG;
     return st;
 }
+// a set's creation (specset_build): the empty record's stages, and a noise per channel becomes the weights
+inline unsigned set_stages_create(const SetLayout &L) { return set_stages_all(L) | (L.has(SB_W) ? ST_FORM_W : 0u); }
 // new data in a pixel (nfa_specset_set_data): Q, the mask, the baseline basis and the templates' stay
 inline unsigned set_stages_data(const SetLayout &L) { return set_stages_all(L) & ST_DATA; }
 // from options a (layout la) to options b (layout lb), which differ in one option; tmpl_changed, cont_changed: the values of
