@@ -554,6 +554,29 @@ int nfa_host_free(void *p);
 int nfa_runner_predict_batch(nfa_runner *r, const int32_t *pix, const double *theta,
                              int64_t B, double *spectra_out, double *lnL_out);
 
+/* Weighted posterior moments of model spectra; host pointers, synchronous.  Segment g is the rows seg_off[g] ..
+ * seg_off[g + 1] - 1 of theta (physical parameters, as for nfa_runner_predict_batch), all of pixel seg_pix[g], with
+ * weights w_i >= 0.  p_i is the model spectrum nfa_runner_predict_batch returns for row i (the runner's numerical mode;
+ * the filtered, layered, filled and continuum forms where the set has them).  The moments are taken about the segment's
+ * row of largest weight i* (the first on ties), d_i = p_i - p_i*: with S0 = sum w_i, S1 = sum w_i d_i, S2 = sum w_i d_i^2
+ *     mean = p_i* + S1 / S0,    std = sqrt(max(S2 / S0 - (S1 / S0)^2, 0))
+ * per channel -- raw second moments cancel where the posterior is tight.  The row statistics are the peak (the
+ * NaN-ignoring maximum; for a set with a continuum the signed value of largest magnitude) and the total (the NaN-ignoring
+ * sum) of every (row, spectrum); their weighted mean and std over a segment are the same moments.  A segment without
+ * rows or with S0 = 0 gives NaN, a segment of one row std = 0.  The rows are predicted chunk_rows at a time and reduced
+ * on the device; no sum depends on scheduling: the same arguments give the same bits.
+ * NFA_ERR_ARG: a negative or non-finite weight, a decreasing seg_off, a chunk_rows that is no multiple of 64, all four
+ * outputs null, a pixel out of range.  n_seg = 0 is a no-op. */
+int nfa_runner_predict_moments(nfa_runner *r, int64_t n_seg, const int32_t *seg_pix /* NULL: pixel 0 */,
+        const int64_t *seg_off /* [n_seg+1], seg_off[0] = 0, non-decreasing */,
+        const double *theta /* [seg_off[n_seg]][ndim] */, const double *weight /* or NULL */,
+        int64_t chunk_rows /* 0: 4096; else a multiple of 64 */,
+        double *spec_mean /* [n_seg][chan_tot] or NULL */, double *spec_std /* or NULL */,
+        double *stat_mean /* [n_seg][n_spec][2]: peak, total; or NULL */, double *stat_std /* or NULL */);
+/* peak and total of every spectrum of B rows: peak_and_integrated without the spectra crossing the bus */
+int nfa_runner_row_statistics(nfa_runner *r, const int32_t *pix, const double *theta, int64_t B,
+        double *peak /* [B][n_spec] */, double *total /* [B][n_spec] */);
+
 /* Same as nfa_runner_loglike_batch with every buffer already resident in device
  * memory (from nfa_malloc); enqueued, returns without synchronising.  d_pix may be
  * NULL.  Consecutive calls of one shape may be launched together (option "coalesce");

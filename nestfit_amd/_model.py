@@ -912,6 +912,25 @@ class EngineRunner(Runner):
             _ffi.dptr(spec) if want_spectra else None, _ffi.dptr(lnl)))
         return spec, lnl
 
+    def row_statistics(self, theta):
+        """(peak, total), [B, n_spec] each, of the model spectra of parameter rows theta[B, ndim], formed on the device
+        (`CubeRunner.row_statistics`)."""
+        from .cube import _row_statistics
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.ndim:
+            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        return _row_statistics(self._run.handle, None, theta, self.n_spec)
+
+    def predict_moments(self, theta, weights=None):
+        """Weighted moments of the model spectra over the parameter rows theta[B, ndim] with weights[B] >= 0 (None: all
+        ones), one segment: a `PosteriorMoments` record of one row per field (`CubeRunner.predict_moments`)."""
+        from .cube import _predict_moments
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.ndim:
+            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        offsets = np.array([0, theta.shape[0]], dtype=np.int64)
+        return _predict_moments(self._run.handle, None, offsets, theta, weights, None, True, self._ss.chan_tot, self.n_spec)
+
 
 def par_names(short, ncomp=None):
     if ncomp is not None:

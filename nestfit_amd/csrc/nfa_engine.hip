@@ -26,6 +26,7 @@
 #include "nh3_data.h"
 #include "n2hp_data.h"
 #include "nfa_device.h"
+#include "nfa_moments.h"
 #include "nfa_set_decl.h"
 #include "nfa_set_rules.h"
 #include "nfa_set_state.h"
@@ -240,6 +241,20 @@ struct nfa_priors {
     std::vector<double *> d_arrays;
 };
 
+// Scratch of the posterior moments (nfa_moments.h), owned by a runner and grown on demand.  Per segment: the reference
+// rows' spectra and row statistics, the accumulator planes of both matrices, S0.  Per chunk: the rows' statistics and
+// weights and the chunk's pieces; two pinned staging slots (a chunk's pixel per row, then its pieces) that the host fills
+// for chunk c + 1 while the device works on chunk c -- a slot's event stands behind the copies out of it.
+struct MomScratch {
+    double *d_ref = nullptr, *d_acc = nullptr, *d_sref = nullptr, *d_sacc = nullptr, *d_s0 = nullptr;
+    int64_t cap_seg = 0;
+    double *d_stat = nullptr, *d_w = nullptr;
+    MomPiece *d_pieces = nullptr;
+    int64_t cap_rows = 0;
+    char *h_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
 #define NFA_MAX_LANES 8
 struct nfa_runner {
     nfa_specset *ss = nullptr;
@@ -285,6 +300,7 @@ struct nfa_runner {
     hipEvent_t *ev_cur = nullptr;        // profiling: [set-up start, stop, likelihood start, stop] of the call under way
     BatchGroup  cur_group = {};          // the batches of the launches being enqueued (run_group)
     BatchGroup  pending = {};            // device-pointer batches accepted but not yet launched (coalescing)
+    MomScratch  mom;                     // nfa_runner_predict_moments, nfa_runner_row_statistics: reference rows, accumulators, staging
     bool        pending_prior = true;    // ... loglike batches (unit cube, prior transform) or predict batches (physical parameters)
     // One in-flight call per runner is the contract (include/nestfit_amd.h); the process-wide calls
     // (nfa_device_synchronize, nfa_set_exp_mode) walk every live runner from whatever thread makes them, so the state a
@@ -1246,6 +1262,12 @@ int nfa_runner_destroy(nfa_runner *r) {
     if (r->g1) (void)hipGraphExecDestroy(r->g1);
     if (r->h_pin) (void)hipHostFree(r->h_pin);
     if (r->h_point) (void)hipHostFree(r->h_point);
+    {
+        MomScratch &m = r->mom;
+        (void)hipFree(m.d_ref); (void)hipFree(m.d_acc); (void)hipFree(m.d_sref); (void)hipFree(m.d_sacc); (void)hipFree(m.d_s0);
+        (void)hipFree(m.d_stat); (void)hipFree(m.d_w); (void)hipFree(m.d_pieces);
+        for (int k = 0; k < 2; ++k) { if (m.h_stage[k]) (void)hipHostFree(m.h_stage[k]); if (m.ev[k]) (void)hipEventDestroy(m.ev[k]); }
+    }
     if (r->d_point_done) (void)hipFree(r->d_point_done);
     for (hipEvent_t x : r->ev) (void)hipEventDestroy(x);
     for (int k = 0; k < r->n_lanes; ++k) (void)hipStreamDestroy(r->lanes[k]);
@@ -1905,6 +1927,208 @@ int nfa_runner_predict_batch_dev(nfa_runner *r, const int32_t *d_pix, const doub
     // longest wave, 37.8 us against 26 per batch in a launch of eight)
     return enqueue_dev(r, d_pix, const_cast<double *>(d_theta), d_lnL, d_spectra, B, false);
 }
+
+}  // extern "C"
+
+// ---- posterior moments of model spectra (nfa_moments.h, nfa_moments_plan.h) -------------------------------------
+static int mom_reserve_rows(nfa_runner *r, int64_t rows) {
+    MomScratch &m = r->mom;
+    if (rows <= m.cap_rows) return NFA_OK;
+    (void)hipFree(m.d_stat); (void)hipFree(m.d_w); (void)hipFree(m.d_pieces);
+    for (int k = 0; k < 2; ++k) { if (m.h_stage[k]) (void)hipHostFree(m.h_stage[k]); m.h_stage[k] = nullptr; }
+    m.d_stat = nullptr; m.d_w = nullptr; m.d_pieces = nullptr; m.cap_rows = 0;
+    HIP_TRY(hipMalloc(&m.d_stat, sizeof(double) * mom_stat_doubles(rows, r->ss->dev.n_spec)));
+    HIP_TRY(hipMalloc(&m.d_w, sizeof(double) * rows));
+    HIP_TRY(hipMalloc(&m.d_pieces, sizeof(MomPiece) * rows));
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(hipHostMalloc((void **)&m.h_stage[k], (sizeof(int32_t) + sizeof(MomPiece)) * rows, hipHostMallocDefault));
+        if (!m.ev[k]) HIP_TRY(hipEventCreateWithFlags(&m.ev[k], hipEventDisableTiming));
+    }
+    m.cap_rows = rows;
+    return NFA_OK;
+}
+static int mom_reserve_segs(nfa_runner *r, int64_t n_seg) {
+    MomScratch &m = r->mom;
+    if (n_seg <= m.cap_seg) return NFA_OK;
+    (void)hipFree(m.d_ref); (void)hipFree(m.d_acc); (void)hipFree(m.d_sref); (void)hipFree(m.d_sacc); (void)hipFree(m.d_s0);
+    m.d_ref = m.d_acc = m.d_sref = m.d_sacc = m.d_s0 = nullptr; m.cap_seg = 0;
+    const int64_t chan_tot = r->ss->dev.chan_tot, nstat = 2 * r->ss->dev.n_spec;
+    HIP_TRY(hipMalloc(&m.d_ref, sizeof(double) * mom_ref_doubles(n_seg, chan_tot)));
+    HIP_TRY(hipMalloc(&m.d_acc, sizeof(double) * mom_acc_doubles(n_seg, chan_tot)));
+    HIP_TRY(hipMalloc(&m.d_sref, sizeof(double) * mom_ref_doubles(n_seg, nstat)));
+    HIP_TRY(hipMalloc(&m.d_sacc, sizeof(double) * mom_acc_doubles(n_seg, nstat)));
+    HIP_TRY(hipMalloc(&m.d_s0, sizeof(double) * n_seg));
+    m.cap_seg = n_seg;
+    return NFA_OK;
+}
+static MomSpecs mom_specs(const nfa_runner *r) {
+    MomSpecs S = {};
+    S.n_spec = r->ss->dev.n_spec;
+    for (int s = 0; s < S.n_spec; ++s) { S.size[s] = r->ss->dev.size[s]; S.off[s] = r->ss->dev.off[s]; }
+    return S;
+}
+// peak and total of `rows` rows of spec[rows][chan_tot] on the runner's stream (step: see row_stats_kernel)
+static int launch_row_stats(nfa_runner *r, const double *d_spec, int64_t rows, double *d_peak, double *d_total, int step) {
+    hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)mom_stat_blocks(rows, r->ss->dev.n_spec)), dim3(MOM_STAT_WAVES * 64), 0, r->lanes[0],
+                       d_spec, (long)rows, (long)r->ss->dev.chan_tot, mom_specs(r), r->ss->dev.cont != nullptr ? 1 : 0, d_peak, d_total, step);
+    HIP_TRY(hipGetLastError());
+    return NFA_OK;
+}
+static int launch_accumulate(nfa_runner *r, const double *d_x, int64_t ld, int64_t ncol, const double *d_w, int64_t n_pieces,
+                             int64_t max_rows, const double *d_ref, double *d_acc, int64_t n_seg) {
+    const MomGeom G = mom_geom(n_pieces, ncol, max_rows, g_eng.n_cu);
+    hipLaunchKernelGGL(moments_accumulate_kernel, dim3(G.grid_x, G.grid_y), dim3(G.threads), G.lds, r->lanes[0],
+                       d_x, (long)ld, (long)ncol, d_w, (const MomPiece *)r->mom.d_pieces, d_ref, d_acc, (long)n_seg, G.R);
+    HIP_TRY(hipGetLastError());
+    return NFA_OK;
+}
+
+extern "C" {
+
+int nfa_runner_predict_moments(nfa_runner *r, int64_t n_seg, const int32_t *seg_pix, const int64_t *seg_off, const double *theta,
+                               const double *weight, int64_t chunk_rows, double *spec_mean, double *spec_std,
+                               double *stat_mean, double *stat_std) {
+    if (!r) return fail(NFA_ERR_ARG, "null runner");
+    if (n_seg < 0 || n_seg > INT32_MAX) return fail(NFA_ERR_ARG, "the number of segments is out of range");
+    if (!spec_mean && !spec_std && !stat_mean && !stat_std) return fail(NFA_ERR_ARG, "predict_moments: all four outputs are null");
+    if (const char *why = mom_check_chunk_rows(chunk_rows)) return fail(NFA_ERR_ARG, why);
+    if (n_seg == 0) return NFA_OK;
+    if (!seg_off) return fail(NFA_ERR_ARG, "null argument");
+    if (seg_off[0] != 0) return fail(NFA_ERR_ARG, "segment offsets start at 0");
+    for (int64_t g = 0; g < n_seg; ++g)
+        if (seg_off[g + 1] < seg_off[g]) return fail(NFA_ERR_ARG, "segment offsets must not decrease");
+    const int64_t rows = seg_off[n_seg];
+    if (rows > 0 && !theta) return fail(NFA_ERR_ARG, "null argument");
+    int rc = check_pix(r, seg_pix, n_seg); if (rc) return rc;
+    if (weight)
+        for (int64_t i = 0; i < rows; ++i)
+            if (!(weight[i] >= 0.0) || !std::isfinite(weight[i])) return fail(NFA_ERR_ARG, "a weight is finite and >= 0");
+    const int64_t chan_tot = r->ss->dev.chan_tot, nstat = 2 * r->ss->dev.n_spec, chunk = mom_chunk_rows(chunk_rows);
+    const bool want_spec = spec_mean || spec_std, want_stat = stat_mean || stat_std;
+    if (rows == 0) {                                         // nothing to predict: every segment is empty
+        for (double *out : {spec_mean, spec_std}) if (out) std::fill(out, out + n_seg * chan_tot, (double)NAN);
+        for (double *out : {stat_mean, stat_std}) if (out) std::fill(out, out + n_seg * nstat, (double)NAN);
+        return NFA_OK;
+    }
+    // S0 and the reference row of every segment: the row of largest weight, the first on ties (an empty segment borrows
+    // a row: its S0 = 0 makes every output NaN whatever that row's spectrum is)
+    const int ndim = r->ndim;
+    std::vector<double> s0((size_t)n_seg), ref_theta((size_t)n_seg * ndim);
+    for (int64_t g = 0; g < n_seg; ++g) {
+        int64_t best = std::min(seg_off[g], rows - 1);
+        double sum = 0.0;
+        for (int64_t i = seg_off[g]; i < seg_off[g + 1]; ++i) {
+            const double w = weight ? weight[i] : 1.0;
+            sum += w;
+            if (w > (weight ? weight[best] : 1.0)) best = i;
+        }
+        s0[(size_t)g] = sum;
+        std::copy(theta + best * ndim, theta + (best + 1) * ndim, ref_theta.begin() + (size_t)g * ndim);
+    }
+    RUNNER_LOCK(r);
+    rc = sync_all_lanes(r); if (rc) return rc;
+    rc = runner_reserve(r, chunk, true); if (rc) return rc;
+    rc = mom_reserve_rows(r, chunk); if (rc) return rc;
+    rc = mom_reserve_segs(r, n_seg); if (rc) return rc;
+    MomScratch &m = r->mom;
+    hipStream_t st = r->lanes[0];
+    HIP_TRY(hipMemcpyAsync(m.d_s0, s0.data(), sizeof(double) * n_seg, hipMemcpyHostToDevice, st));
+    if (want_spec) HIP_TRY(hipMemsetAsync(m.d_acc, 0, sizeof(double) * mom_acc_doubles(n_seg, chan_tot), st));
+    if (want_stat) HIP_TRY(hipMemsetAsync(m.d_sacc, 0, sizeof(double) * mom_acc_doubles(n_seg, nstat), st));
+    // the reference rows: ordinary predict launches of n_seg rows into ref[n_seg][chan_tot], their statistics taken there
+    for (int64_t b0 = 0; b0 < n_seg; b0 += r->cap_B) {
+        const int64_t nb = std::min<int64_t>(r->cap_B, n_seg - b0);
+        HIP_TRY(hipMemcpyAsync(r->d_U, ref_theta.data() + b0 * ndim, sizeof(double) * nb * ndim, hipMemcpyHostToDevice, st));
+        if (seg_pix) HIP_TRY(hipMemcpyAsync(r->d_pix, seg_pix + b0, sizeof(int) * nb, hipMemcpyHostToDevice, st));
+        rc = run_batch(r, seg_pix ? r->d_pix : nullptr, r->d_U, r->d_lnL, m.d_ref + b0 * chan_tot, nb, false, 0);
+        if (rc) return rc;
+    }
+    if (want_stat) { rc = launch_row_stats(r, m.d_ref, n_seg, m.d_sref, m.d_sref + 1, 2); if (rc) return rc; }
+    // chunk by chunk: predict into the spectra scratch, reduce there
+    const int64_t n_chunks = mom_n_chunks(rows, chunk);
+    int64_t cursor = 0;
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const int64_t a = c * chunk, nb = std::min(chunk, rows - a);
+        const int slot = (int)(c & 1);
+        if (c >= 2) HIP_TRY(hipEventSynchronize(m.ev[slot]));          // the copies out of this slot two chunks ago
+        int32_t *h_pix = (int32_t *)m.h_stage[slot];
+        MomPiece *h_pieces = (MomPiece *)(m.h_stage[slot] + sizeof(int32_t) * m.cap_rows);
+        const int64_t n_pieces = mom_cut(seg_off, n_seg, chunk, c, &cursor, h_pieces);
+        int64_t max_rows = 0;
+        for (int64_t k = 0; k < n_pieces; ++k) {
+            max_rows = std::max<int64_t>(max_rows, h_pieces[k].n);
+            if (seg_pix) std::fill(h_pix + h_pieces[k].row0, h_pix + h_pieces[k].row0 + h_pieces[k].n, seg_pix[h_pieces[k].seg]);
+        }
+        HIP_TRY(hipMemcpyAsync(r->d_U, theta + a * ndim, sizeof(double) * nb * ndim, hipMemcpyHostToDevice, st));
+        if (weight) HIP_TRY(hipMemcpyAsync(m.d_w, weight + a, sizeof(double) * nb, hipMemcpyHostToDevice, st));
+        if (seg_pix) HIP_TRY(hipMemcpyAsync(r->d_pix, h_pix, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.d_pieces, h_pieces, sizeof(MomPiece) * n_pieces, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(m.ev[slot], st));
+        rc = run_batch(r, seg_pix ? r->d_pix : nullptr, r->d_U, r->d_lnL, r->d_spec, nb, false, 0);
+        if (rc) return rc;
+        const double *d_w = weight ? m.d_w : nullptr;
+        if (want_spec) {
+            rc = launch_accumulate(r, r->d_spec, chan_tot, chan_tot, d_w, n_pieces, max_rows, m.d_ref, m.d_acc, n_seg);
+            if (rc) return rc;
+        }
+        if (want_stat) {
+            rc = launch_row_stats(r, r->d_spec, nb, m.d_stat, m.d_stat + 1, 2); if (rc) return rc;
+            rc = launch_accumulate(r, m.d_stat, nstat, nstat, d_w, n_pieces, max_rows, m.d_sref, m.d_sacc, n_seg);
+            if (rc) return rc;
+        }
+    }
+    if (want_spec) {
+        const int64_t n = n_seg * chan_tot;
+        hipLaunchKernelGGL(moments_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m.d_acc, (const double *)m.d_ref,
+                           (const double *)m.d_s0, (long)n_seg, (long)chan_tot);
+        HIP_TRY(hipGetLastError());
+        if (spec_mean) HIP_TRY(hipMemcpyAsync(spec_mean, m.d_acc, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        if (spec_std) HIP_TRY(hipMemcpyAsync(spec_std, m.d_acc + n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    }
+    if (want_stat) {
+        const int64_t n = n_seg * nstat;
+        hipLaunchKernelGGL(moments_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m.d_sacc, (const double *)m.d_sref,
+                           (const double *)m.d_s0, (long)n_seg, (long)nstat);
+        HIP_TRY(hipGetLastError());
+        if (stat_mean) HIP_TRY(hipMemcpyAsync(stat_mean, m.d_sacc, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        if (stat_std) HIP_TRY(hipMemcpyAsync(stat_std, m.d_sacc + n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    r->lane_busy &= ~1u;
+    return NFA_OK;
+}
+
+int nfa_runner_row_statistics(nfa_runner *r, const int32_t *pix, const double *theta, int64_t B, double *peak, double *total) {
+    if (!r || !theta || !peak || !total) return fail(NFA_ERR_ARG, "null argument");
+    if (B <= 0) return NFA_OK;
+    int rc = check_pix(r, pix, B); if (rc) return rc;
+    RUNNER_LOCK(r);
+    rc = sync_all_lanes(r); if (rc) return rc;
+    const int64_t chunk = std::min<int64_t>(MOM_CHUNK_ROWS, (B + 63) / 64 * 64);
+    rc = runner_reserve(r, chunk, true); if (rc) return rc;
+    rc = mom_reserve_rows(r, chunk); if (rc) return rc;
+    MomScratch &m = r->mom;
+    hipStream_t st = r->lanes[0];
+    const int n_spec = r->ss->dev.n_spec, ndim = r->ndim;
+    double *d_peak = m.d_stat, *d_total = m.d_stat + m.cap_rows * n_spec;
+    for (int64_t a = 0; a < B; a += chunk) {
+        const int64_t nb = std::min(chunk, B - a);
+        HIP_TRY(hipMemcpyAsync(r->d_U, theta + a * ndim, sizeof(double) * nb * ndim, hipMemcpyHostToDevice, st));
+        if (pix) HIP_TRY(hipMemcpyAsync(r->d_pix, pix + a, sizeof(int) * nb, hipMemcpyHostToDevice, st));
+        rc = run_batch(r, pix ? r->d_pix : nullptr, r->d_U, r->d_lnL, r->d_spec, nb, false, 0);
+        if (rc) return rc;
+        rc = launch_row_stats(r, r->d_spec, nb, d_peak, d_total, 1); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(peak + a * n_spec, d_peak, sizeof(double) * nb * n_spec, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(total + a * n_spec, d_total, sizeof(double) * nb * n_spec, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    r->lane_busy &= ~1u;
+    return NFA_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 void nfa_loglike_callback(double *Cube, int *ndim, int *npars, double *lnew, void *ctx) {
     (void)npars;

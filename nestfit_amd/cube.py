@@ -354,3 +354,65 @@ class CubeRunner:
         peak = np.stack([top(spec[:, off[k]:off[k + 1]], axis=1) for k in range(self.n_spec)], axis=1)
         tot = np.stack([np.nansum(spec[:, off[k]:off[k + 1]], axis=1) for k in range(self.n_spec)], axis=1)
         return peak, tot
+
+    def row_statistics(self, pix, theta):
+        """(peak, total), [B, n_spec] each, of the model spectra of parameter rows theta[B, ndim] against pixels pix[B]:
+        the numbers of `peak_and_integrated`, formed on the device (csrc/nfa_moments.h: row_stats_kernel) -- the spectra do
+        not cross the bus.  peak is the same to the bit; total is the sum of the same channels in another order."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.ndim:
+            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        if pix.shape != (theta.shape[0],):
+            raise ValueError('one pixel index per row is required')
+        return _row_statistics(self._run.handle, pix, theta, self.n_spec)
+
+    def predict_moments(self, pix, offsets, theta, weights=None, chunk_rows=None, want_spectra=True):
+        """Weighted moments of the model spectra over segments of parameter rows: segment g is the rows
+        offsets[g] .. offsets[g + 1] - 1 of theta[rows, ndim] (physical parameters, as for `predict_batch`), all of pixel
+        pix[g], with weights[rows] >= 0 (None: all ones) -- a pixel's weighted posterior sample, say.  Returns a
+        `PosteriorMoments` record: mean, std [n_seg, n_chan_tot] (None without `want_spectra`) and peak_mean, peak_std,
+        total_mean, total_std [n_seg, n_spec], the moments of `row_statistics`' two numbers.  NaN for a segment without rows
+        or whose weights sum to 0.  The rows are predicted `chunk_rows` at a time (None: 4096; a multiple of 64) and
+        reduced on the device; `nestfit_amd.moments` is the same arithmetic in numpy on given spectra."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.ndim:
+            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or offsets.size < 1:
+            raise ValueError('offsets must hold n_seg + 1 row numbers')
+        if offsets[-1] != theta.shape[0]:
+            raise ValueError('the last offset must be the number of rows of theta')
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        if pix.shape != (offsets.size - 1,):
+            raise ValueError('one pixel index per segment is required')
+        return _predict_moments(self._run.handle, pix, offsets, theta, weights, chunk_rows, want_spectra,
+                                self.n_chan_tot, self.n_spec)
+
+
+def _row_statistics(handle, pix, theta, n_spec):
+    """nfa_runner_row_statistics on checked arrays (pix: int32[B] or None)."""
+    B = theta.shape[0]
+    peak, total = np.empty((B, n_spec)), np.empty((B, n_spec))
+    _ffi.check(_ffi.load().nfa_runner_row_statistics(handle, None if pix is None else pix.ctypes.data_as(_ffi._ip),
+                                                     _ffi.dptr(theta), B, _ffi.dptr(peak), _ffi.dptr(total)))
+    return peak, total
+
+
+def _predict_moments(handle, pix, offsets, theta, weights, chunk_rows, want_spectra, n_chan_tot, n_spec):
+    """nfa_runner_predict_moments on checked arrays (pix: int32[n_seg] or None) -> `PosteriorMoments`."""
+    from .moments import PosteriorMoments
+    n_seg = offsets.size - 1
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.shape != (theta.shape[0],):
+            raise ValueError('one weight per row is required')
+    mean = np.empty((n_seg, n_chan_tot)) if want_spectra else None
+    std = np.empty((n_seg, n_chan_tot)) if want_spectra else None
+    smean, sstd = np.empty((n_seg, n_spec, 2)), np.empty((n_seg, n_spec, 2))
+    opt = lambda a: None if a is None else _ffi.dptr(a)
+    _ffi.check(_ffi.load().nfa_runner_predict_moments(
+        handle, n_seg, None if pix is None else pix.ctypes.data_as(_ffi._ip), offsets.ctypes.data_as(_ffi._lp),
+        _ffi.dptr(theta), opt(weights), 0 if chunk_rows is None else int(chunk_rows), opt(mean), opt(std),
+        _ffi.dptr(smean), _ffi.dptr(sstd)))
+    return PosteriorMoments(mean, std, smean[:, :, 0].copy(), sstd[:, :, 0].copy(), smean[:, :, 1].copy(), sstd[:, :, 1].copy())

@@ -366,12 +366,10 @@ def _spec_name(k, dc):
     return f'spec{k}' if getattr(dc, 'lines', None) is not None else f'trans{dc.trans_id}'
 
 
-def _device_predictor(store, stack, ncomp=1, layered=False):
-    """predict(lon[B], lat[B], theta[B, p], want_spectra) -> (spectra[B, chan_tot] or None, peak[B, t],
-    integrated[B, t]) on the GPU: every pixel's data stay where the fit left them conceptually -- a predict
-    needs only the axes, so the spectra set is built over the requested pixels alone.  ncomp, layered: a predictor of
-    whole models of that many layers (theta[B, p * ncomp], parameter-major) for `model_spec_total`; the default is the
-    reference's one-component predictor, for which layered and summed are the same thing."""
+def _device_runner(store, stack, ncomp=1, layered=False):
+    """(runner, pix_of, chan_tot): the `CubeRunner` behind `_device_predictor` and `_device_moments`, and pix_of(lon, lat) ->
+    the set's pixel of map pixels -- every pixel's data stay where the fit left them conceptually: a predict needs only
+    the axes, so one all-zero pixel serves every row, unless the store has continuum maps."""
     from .cube import CubeRunner
     model_id = _MODEL_ID[store.hdf.attrs['model_name']]
     xarrs = [dc.xarr for dc in stack.cubes]
@@ -400,12 +398,24 @@ def _device_predictor(store, stack, ncomp=1, layered=False):
                         model=model_id, layered=layered, **extra)
     runner.set_exp_mode('table')                         # map products in the reference's own arithmetic: a one-off, not a rate
 
+    def pix_of(lon, lat):
+        if cont is None:
+            return np.zeros(np.size(lon), dtype=np.int32)
+        return (np.asarray(lon, dtype=np.int64) * n_lat + np.asarray(lat, dtype=np.int64)).astype(np.int32)
+    return runner, pix_of, chan_tot
+
+
+def _device_predictor(store, stack, ncomp=1, layered=False):
+    """predict(lon[B], lat[B], theta[B, p], want_spectra) -> (spectra[B, chan_tot] or None, peak[B, t],
+    integrated[B, t]) on the GPU: every pixel's data stay where the fit left them conceptually -- a predict
+    needs only the axes, so the spectra set is built over the requested pixels alone.  ncomp, layered: a predictor of
+    whole models of that many layers (theta[B, p * ncomp], parameter-major) for `model_spec_total`; the default is the
+    reference's one-component predictor, for which layered and summed are the same thing."""
+    runner, pix_of, chan_tot = _device_runner(store, stack, ncomp, layered)
     scratch = {}
 
     def predict(lon, lat, theta, want_spectra):
-        pix = np.zeros(theta.shape[0], dtype=np.int32)
-        if cont is not None:
-            pix = (np.asarray(lon, dtype=np.int64) * n_lat + np.asarray(lat, dtype=np.int64)).astype(np.int32)
+        pix = pix_of(lon, lat)
         if want_spectra:
             # (one buffer the device addresses itself serves every batch: the callers use a batch's spectra before
             # they ask for the next)
@@ -511,6 +521,125 @@ def generate_total_profiles(store, stack, predict_backend=None):
         store.create_dataset(_spec_name(k, dc), cube, group=f'{store.dpath}/model_spec_total')
 
 
+def _posterior_rows(store, thin):
+    """Per pixel with conv_nbest = n > 0: (l, b, n, theta[rows, p * n], weight[rows]) of the posterior sample of run n,
+    without the rows whose weight is 0 or below thin * max(weight)."""
+    choice = _product(store, 'conv_nbest')
+    out = []
+    for group in store.iter_pix_groups():
+        l, b = int(group.attrs['i_lon']), int(group.attrs['i_lat'])
+        n = int(choice[b, l])
+        if n <= 0:
+            continue
+        post = np.asarray(group[f'{n}']['posteriors'][...], dtype=np.float64)
+        w = post[:, -1]
+        keep = (w > 0) & (w >= float(thin) * w.max()) if w.size else np.zeros(0, dtype=bool)
+        if keep.any():
+            out.append((l, b, n, np.ascontiguousarray(post[keep, :-2]), np.ascontiguousarray(w[keep])))
+    return out
+
+
+POSTERIOR_ROWS = 65536           # rows per `predict_moments` call (whole segments; one segment may be longer)
+
+
+def _segment_batches(sizes):
+    """Slices of consecutive segments of at most POSTERIOR_ROWS rows together (one segment at least)."""
+    a, rows = 0, 0
+    for k, n in enumerate(sizes):
+        if k > a and rows + n > POSTERIOR_ROWS:
+            yield slice(a, k)
+            a, rows = k, 0
+        rows += n
+    if len(sizes) > a:
+        yield slice(a, len(sizes))
+
+
+def _moments_through(store, stack, ncomp, layered, predict_backend):
+    """moments(lon[G], lat[G], offsets[G + 1], theta[rows, p * ncomp], weights[rows], want_spectra) -> `PosteriorMoments` of G
+    segments: on the device (`CubeRunner.predict_moments`: the spectra are reduced where they are computed), or, with a
+    `predict_backend`, by the numpy twin on the spectra or the row statistics the backend returns."""
+    from . import moments as mo
+    if predict_backend is None:
+        runner, pix_of, _ = _device_runner(store, stack, ncomp, layered)
+        return lambda lon, lat, off, theta, w, want_spectra: runner.predict_moments(pix_of(lon, lat), off, theta, w,
+                                                                                    want_spectra=want_spectra)
+
+    def through_backend(lon, lat, off, theta, w, want_spectra):
+        rep = np.diff(off)
+        lon_r, lat_r = np.repeat(lon, rep), np.repeat(lat, rep)
+        if want_spectra:
+            spec, _, _ = predict_backend(lon_r, lat_r, theta, True)
+            edges = np.concatenate([[0], np.cumsum([dc.nchan for dc in stack.cubes])])
+            cont = store.read_model_continuum()
+            signed = cont is not None and bool(np.any(np.nan_to_num(cont) > 0.0))
+            return mo.posterior_moments_of(np.asarray(spec, dtype=np.float64), w, off, edges, signed=signed)
+        _, peak, tot = predict_backend(lon_r, lat_r, theta, False)
+        pm, ps = mo.moments_of(peak, w, off)
+        tm, ts = mo.moments_of(tot, w, off)
+        return mo.PosteriorMoments(None, None, pm, ps, tm, ts)
+    return through_backend
+
+
+def generate_posterior_profiles(store, stack, thin=0.0, predict_backend=None):
+    """Posterior-mean model cubes with their 1-sigma band, and error bars on the deblended intensities: for
+    every pixel with conv_nbest = n > 0, weighted moments over the posterior sample of run n (rows of weight below
+    thin * max(weight) left out; the default keeps every row of positive weight).
+
+    The whole model, through a predictor of n components (layered where the store is): 'model_spec_mean/<name>',
+    'model_spec_std/<name>' (S, b, l), float32, NaN where the pixel has no component.  Every component alone, through the
+    one-component predictor over (sample, component) rows: 'peak_intensity_mean', 'peak_intensity_std',
+    'integrated_intensity_mean', 'integrated_intensity_std' (t, m, b, l), K and K km/s like `deblend_hf_intensity`'s.
+
+    One model evaluation per posterior sample: the spectra are reduced on the device as they are computed and only the
+    moments come back.  `predict_backend`: callable(lon, lat, theta, want_spectra) standing in for the device (tests
+    without a GPU); the moments are then formed by `nestfit_amd.moments` from what it returns."""
+    print(':: Generating posterior model profiles and intensity errors')
+    n_lon, n_lat = _map_shape(store)
+    n_max, n_par = int(store.hdf.attrs['n_max_components']), int(store.hdf.attrs['n_params'])
+    n_spec = stack.n_cubes
+    layered = check_model_layered(store)
+    pixels = _posterior_rows(store, thin)
+    cubes = {kind: [np.full((dc.nchan, n_lat, n_lon), np.nan, dtype=np.float32) for dc in stack.cubes] for kind in ('mean', 'std')}
+    edges = np.concatenate([[0], np.cumsum([dc.nchan for dc in stack.cubes])])
+    stats = {name: _nans((n_spec, n_max, n_lat, n_lon)) for name in ('peak_intensity_mean', 'peak_intensity_std',
+                                                                     'integrated_intensity_mean', 'integrated_intensity_std')}
+    # the whole model of every pixel: one segment per pixel, the pixels of one component count together
+    for n in sorted({px[2] for px in pixels}):
+        group = [px for px in pixels if px[2] == n]
+        moments = _moments_through(store, stack, n, layered, predict_backend)
+        sizes = [px[3].shape[0] for px in group]
+        for s in _segment_batches(sizes):
+            part = group[s]
+            lon, lat = np.array([px[0] for px in part]), np.array([px[1] for px in part])
+            off = np.concatenate([[0], np.cumsum(sizes[s])]).astype(np.int64)
+            res = moments(lon, lat, off, np.concatenate([px[3] for px in part]), np.concatenate([px[4] for px in part]), True)
+            for k in range(n_spec):
+                cubes['mean'][k][:, lat, lon] = res.mean[:, edges[k]:edges[k + 1]].T
+                cubes['std'][k][:, lat, lon] = res.std[:, edges[k]:edges[k + 1]].T
+    # every component alone: one segment per (pixel, component); parameter q of component c is column q * n + c
+    if pixels:
+        moments = _moments_through(store, stack, 1, False, predict_backend)
+        segs = [(l, b, c, np.ascontiguousarray(theta[:, c::n]), w) for l, b, n, theta, w in pixels for c in range(n)]
+        sizes = [sg[3].shape[0] for sg in segs]
+        for s in _segment_batches(sizes):
+            part = segs[s]
+            lon, lat, comp = (np.array([sg[i] for sg in part]) for i in range(3))
+            off = np.concatenate([[0], np.cumsum(sizes[s])]).astype(np.int64)
+            res = moments(lon, lat, off, np.concatenate([sg[3] for sg in part]), np.concatenate([sg[4] for sg in part]), False)
+            stats['peak_intensity_mean'][:, comp, lat, lon] = res.peak_mean.T
+            stats['peak_intensity_std'][:, comp, lat, lon] = res.peak_std.T
+            stats['integrated_intensity_mean'][:, comp, lat, lon] = res.total_mean.T
+            stats['integrated_intensity_std'][:, comp, lat, lon] = res.total_std.T
+    dv = np.array([dc.dv for dc in stack.cubes]).reshape(-1, 1, 1, 1)          # K -> K km/s
+    stats['integrated_intensity_mean'] *= dv
+    stats['integrated_intensity_std'] *= np.abs(dv)
+    for kind in ('mean', 'std'):
+        for k, (cube, dc) in enumerate(zip(cubes[kind], stack.cubes)):
+            store.create_dataset(_spec_name(k, dc), cube, group=f'{store.dpath}/model_spec_{kind}')
+    for name, arr in stats.items():
+        store.create_dataset(name, arr, group=store.dpath)
+
+
 def create_fits_from_store(store, prefix='source'):
     """The deblended cubes as FITS files, one per transition, the components added up, on the velocity grid of
     the PDF bins: `<prefix>_hf_deblended_trans<t>.fits` (main.py:1196-1237; peak / integrated intensity and the
@@ -529,8 +658,9 @@ def create_fits_from_store(store, prefix='source'):
 
 
 def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, post_kernel=None,
-                    evid_weight=True, predict_backend=None):
-    """All steps in the reference's order (main.py:1240-1276)."""
+                    evid_weight=True, predict_backend=None, posterior_profiles=False):
+    """All steps in the reference's order (main.py:1240-1276).  posterior_profiles: then `generate_posterior_profiles`, the
+    posterior-mean model cubes and the error bars of the intensities (one model evaluation per posterior sample)."""
     if store.hdf.attrs.get('model_name') in ('hyperfine', 'lte', 'lte_mix'):     # before any product is written
         check_model_lines(store, stack)
         check_model_fill(store, runner)
@@ -544,3 +674,5 @@ def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, 
     quantize_conv_marginals(store)
     deblend_hf_intensity(store, stack, runner, predict_backend=predict_backend)
     generate_predicted_profiles(store, stack, runner, predict_backend=predict_backend)
+    if posterior_profiles:
+        generate_posterior_profiles(store, stack, predict_backend=predict_backend)
