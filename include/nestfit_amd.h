@@ -577,6 +577,31 @@ int nfa_runner_predict_moments(nfa_runner *r, int64_t n_seg, const int32_t *seg_
 int nfa_runner_row_statistics(nfa_runner *r, const int32_t *pix, const double *theta, int64_t B,
         double *peak /* [B][n_spec] */, double *total /* [B][n_spec] */);
 
+/* The normal equations of a least-squares fit at B points (pixel, theta); host pointers, synchronous.
+ * p(theta) is the model spectrum nfa_runner_predict_batch returns for the point (the runner's numerical mode; the layered,
+ * filled and continuum forms where the set has them).  The probes of parameter k are theta+ = theta + step_k e_k and theta- =
+ * theta - step_k e_k, each clipped into [lower_k, upper_k] where those are given, and
+ *     J_k = (p(theta+) - p(theta-)) / (theta+_k - theta-_k)
+ * with the difference of the two doubles as they are; a parameter with theta+_k == theta-_k is fixed and has J_k = 0.  The
+ * weight of channel j is W_j = 1 / sigma^2 for a scalar noise and chan_w_j / sigma_ref^2 for a noise per channel; a channel of
+ * weight 0 (masked) is left out whatever the model or the data hold there, and a model value that is not finite at a channel
+ * of positive weight makes the point's outputs NaN.  With r_j = d_j - p_j(theta):
+ *     chi2 = sum_j W_j r_j^2,   grad_k = sum_j W_j J_kj r_j (= -1/2 d chi2 / d theta_k),   curv_kl = sum_j W_j J_kj J_lj
+ * (full and symmetric, both triangles written): the entries of one augmented Gram matrix [J r]^T W [J r].  With grad and curv
+ * both null the call predicts one row per point and returns chi2 alone, the same bits as the full call's; step may then be
+ * null.  Otherwise a point takes R = 1 + 2 ndim rows, a chunk holds floor(chunk_rows / R) points, and the spectra are reduced
+ * on the device as each chunk is predicted; no sum depends on scheduling: the same arguments give the same bits.
+ * NFA_ERR_ARG: a null theta or chi2, grad or curv without step, a step that is not finite and > 0, lower_k > upper_k, a
+ * chunk_rows that is no multiple of 64 or smaller than R, ndim > NFA_LSQ_MAX_DIM, a pixel out of range.  NFA_ERR_STATE, with a
+ * sentence: a set whose likelihood is not -chi^2 / 2 of white noise -- a baseline, templates, a calibration uncertainty, a noise
+ * correlation, a channel response, a noise uncertainty, a robust likelihood.  B = 0 is a no-op. */
+#define NFA_LSQ_MAX_DIM  24
+int nfa_runner_normal_equations(nfa_runner *r, const int32_t *pix /* [B] or NULL: pixel 0 */,
+        const double *theta /* [B][ndim], physical parameters as for nfa_runner_predict_batch */, int64_t B,
+        const double *step /* [ndim], > 0 */, const double *lower /* [ndim] or NULL */, const double *upper /* [ndim] or NULL */,
+        int64_t chunk_rows /* 0: 4096; else a multiple of 64 and >= 1 + 2 ndim */,
+        double *chi2 /* [B] */, double *grad /* [B][ndim] or NULL */, double *curv /* [B][ndim][ndim] or NULL */);
+
 /* Same as nfa_runner_loglike_batch with every buffer already resident in device
  * memory (from nfa_malloc); enqueued, returns without synchronising.  d_pix may be
  * NULL.  Consecutive calls of one shape may be launched together (option "coalesce");

@@ -100,6 +100,7 @@ SIGNATURES = {
     'nfa_runner_predict_batch': (C.c_int, [C.c_void_p, _ip, _dp, C.c_int64, _dp, _dp]),
     'nfa_runner_predict_moments': (C.c_int, [C.c_void_p, C.c_int64, _ip, _lp, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
     'nfa_runner_row_statistics': (C.c_int, [C.c_void_p, _ip, _dp, C.c_int64, _dp, _dp]),
+    'nfa_runner_normal_equations': (C.c_int, [C.c_void_p, _ip, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp]),
     'nfa_runner_predict_batch_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'nfa_runner_loglike_batch_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int64]),

@@ -931,6 +931,23 @@ class EngineRunner(Runner):
         offsets = np.array([0, theta.shape[0]], dtype=np.int64)
         return _predict_moments(self._run.handle, None, offsets, theta, weights, None, True, self._ss.chan_tot, self.n_spec)
 
+    def normal_equations(self, theta, step, lower=None, upper=None, chunk_rows=None, want_curvature=True):
+        """The normal equations of a least-squares fit at the parameter rows theta[B, ndim]: a `NormalEquations` record
+        of chi2, grad = J^T W r and curv = J^T W J (`CubeRunner.normal_equations`)."""
+        from .cube import _normal_equations
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.ndim:
+            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        return _normal_equations(self._run.handle, None, theta, step, lower, upper, chunk_rows, want_curvature)
+
+    def chi_squared(self, theta):
+        """chi2[B] of the parameter rows theta[B, ndim] (`CubeRunner.chi_squared`)."""
+        from .cube import _normal_equations
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.ndim:
+            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        return _normal_equations(self._run.handle, None, theta, None, None, None, None, False, want_grad=False).chi2
+
 
 def par_names(short, ncomp=None):
     if ncomp is not None:

@@ -26,6 +26,7 @@
 #include "nh3_data.h"
 #include "n2hp_data.h"
 #include "nfa_device.h"
+#include "nfa_lsq.h"
 #include "nfa_moments.h"
 #include "nfa_set_decl.h"
 #include "nfa_set_rules.h"
@@ -255,6 +256,14 @@ struct MomScratch {
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
+// Scratch of the normal equations (nfa_lsq.h), owned by a runner and grown on demand: one slab of doubles in the order of
+// lsq_scratch (nfa_lsq_plan.h) and the points' pixels.
+struct LsqScratch {
+    double *d_buf = nullptr;
+    int    *d_pix = nullptr;
+    int64_t cap_B = 0;
+};
+
 #define NFA_MAX_LANES 8
 struct nfa_runner {
     nfa_specset *ss = nullptr;
@@ -301,6 +310,7 @@ struct nfa_runner {
     BatchGroup  cur_group = {};          // the batches of the launches being enqueued (run_group)
     BatchGroup  pending = {};            // device-pointer batches accepted but not yet launched (coalescing)
     MomScratch  mom;                     // nfa_runner_predict_moments, nfa_runner_row_statistics: reference rows, accumulators, staging
+    LsqScratch  lsq;                     // nfa_runner_normal_equations: the points, their probe steps and the outputs
     bool        pending_prior = true;    // ... loglike batches (unit cube, prior transform) or predict batches (physical parameters)
     // One in-flight call per runner is the contract (include/nestfit_amd.h); the process-wide calls
     // (nfa_device_synchronize, nfa_set_exp_mode) walk every live runner from whatever thread makes them, so the state a
@@ -1268,6 +1278,7 @@ int nfa_runner_destroy(nfa_runner *r) {
         (void)hipFree(m.d_stat); (void)hipFree(m.d_w); (void)hipFree(m.d_pieces);
         for (int k = 0; k < 2; ++k) { if (m.h_stage[k]) (void)hipHostFree(m.h_stage[k]); if (m.ev[k]) (void)hipEventDestroy(m.ev[k]); }
     }
+    (void)hipFree(r->lsq.d_buf); (void)hipFree(r->lsq.d_pix);
     if (r->d_point_done) (void)hipFree(r->d_point_done);
     for (hipEvent_t x : r->ev) (void)hipEventDestroy(x);
     for (int k = 0; k < r->n_lanes; ++k) (void)hipStreamDestroy(r->lanes[k]);
@@ -2121,6 +2132,83 @@ int nfa_runner_row_statistics(nfa_runner *r, const int32_t *pix, const double *t
         HIP_TRY(hipMemcpyAsync(peak + a * n_spec, d_peak, sizeof(double) * nb * n_spec, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(total + a * n_spec, d_total, sizeof(double) * nb * n_spec, hipMemcpyDeviceToHost, st));
     }
+    HIP_TRY(hipStreamSynchronize(st));
+    r->lane_busy &= ~1u;
+    return NFA_OK;
+}
+
+}  // extern "C"
+
+// ---- normal equations of a least-squares fit (nfa_lsq.h, nfa_lsq_plan.h) ------------------------------------------
+static int lsq_reserve(nfa_runner *r, int64_t B) {
+    LsqScratch &q = r->lsq;
+    if (B <= q.cap_B) return NFA_OK;
+    (void)hipFree(q.d_buf); (void)hipFree(q.d_pix);
+    q.d_buf = nullptr; q.d_pix = nullptr; q.cap_B = 0;
+    HIP_TRY(hipMalloc(&q.d_buf, sizeof(double) * lsq_scratch(B, r->ndim).total));
+    HIP_TRY(hipMalloc(&q.d_pix, sizeof(int) * B));
+    q.cap_B = B;
+    return NFA_OK;
+}
+
+extern "C" {
+
+int nfa_runner_normal_equations(nfa_runner *r, const int32_t *pix, const double *theta, int64_t B, const double *step,
+                                const double *lower, const double *upper, int64_t chunk_rows, double *chi2, double *grad, double *curv) {
+    if (!r) return fail(NFA_ERR_ARG, "null runner");
+    if (B < 0 || B > INT32_MAX) return fail(NFA_ERR_ARG, "the number of points is out of range");
+    const int ndim = r->ndim;
+    if (const char *why = lsq_check_ndim(ndim)) return fail(NFA_ERR_ARG, why);
+    const int nj = grad || curv ? ndim : 0;                  // probed parameters: none for chi^2 alone
+    if (const char *why = lsq_check_chunk_rows(chunk_rows, nj)) return fail(NFA_ERR_ARG, why);
+    if (nj && !step) return fail(NFA_ERR_ARG, "normal_equations: grad or curv without step");
+    if (nj) {
+        for (int k = 0; k < ndim; ++k) {
+            if (!(step[k] > 0.0) || !std::isfinite(step[k])) return fail(NFA_ERR_ARG, "a step is finite and > 0");
+            if (lower && upper && lower[k] > upper[k]) return fail(NFA_ERR_ARG, "a lower bound lies above its upper bound");
+            if ((lower && lower[k] != lower[k]) || (upper && upper[k] != upper[k])) return fail(NFA_ERR_ARG, "a bound is NaN");
+        }
+    }
+    if (const char *why = lsq_refusal(specset_has(r->ss))) return fail(NFA_ERR_STATE, why);
+    if (B == 0) return NFA_OK;
+    if (!theta || !chi2) return fail(NFA_ERR_ARG, "null argument");
+    int rc = check_pix(r, pix, B); if (rc) return rc;
+    const int R = lsq_rows_per_point(nj);
+    const int64_t chunk = lsq_chunk_rows(chunk_rows), per = lsq_points_per_chunk(chunk_rows, nj);
+    RUNNER_LOCK(r);
+    rc = sync_all_lanes(r); if (rc) return rc;
+    rc = runner_reserve(r, chunk, true); if (rc) return rc;
+    rc = lsq_reserve(r, B); if (rc) return rc;
+    const LsqScratchPlan P = lsq_scratch(r->lsq.cap_B, ndim);
+    double *buf = r->lsq.d_buf;
+    hipStream_t st = r->lanes[0];
+    HIP_TRY(hipMemcpyAsync(buf + P.theta, theta, sizeof(double) * B * ndim, hipMemcpyHostToDevice, st));
+    if (pix) HIP_TRY(hipMemcpyAsync(r->lsq.d_pix, pix, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    if (nj) {
+        HIP_TRY(hipMemcpyAsync(buf + P.step, step, sizeof(double) * ndim, hipMemcpyHostToDevice, st));
+        if (lower) HIP_TRY(hipMemcpyAsync(buf + P.lower, lower, sizeof(double) * ndim, hipMemcpyHostToDevice, st));
+        if (upper) HIP_TRY(hipMemcpyAsync(buf + P.upper, upper, sizeof(double) * ndim, hipMemcpyHostToDevice, st));
+    }
+    const int *d_ppix = pix ? r->lsq.d_pix : nullptr;
+    const SpecDev S = runner_specdev(r);
+    for (int64_t a = 0; a < B; a += per) {                   // chunk by chunk: probe rows, predict, reduce
+        const int64_t np = std::min(per, B - a);
+        hipLaunchKernelGGL(lsq_probe_kernel, dim3(lsq_probe_blocks(np, nj)), dim3(256), 0, st, (const double *)(buf + P.theta + a * ndim),
+                           d_ppix ? d_ppix + a : nullptr, (long)np, ndim, nj, (const double *)(buf + P.step),
+                           lower ? (const double *)(buf + P.lower) : nullptr, upper ? (const double *)(buf + P.upper) : nullptr,
+                           r->d_U, r->d_pix, buf + P.inv_d + a * ndim);
+        HIP_TRY(hipGetLastError());
+        rc = run_batch(r, pix ? r->d_pix : nullptr, r->d_U, r->d_lnL, r->d_spec, np * R, false, 0);
+        if (rc) return rc;
+        const LsqGeom G = lsq_geom(nj, np);
+        hipLaunchKernelGGL(G.ept == 2 ? lsq_gram_kernel<2> : lsq_gram_kernel<4>, dim3(G.grid), dim3(G.threads), G.lds, st,
+                           (const double *)r->d_spec, S, d_ppix, (const double *)(buf + P.inv_d), (long)a, nj, buf + P.chi2, buf + P.grad,
+                           buf + P.curv);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(chi2, buf + P.chi2, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    if (grad) HIP_TRY(hipMemcpyAsync(grad, buf + P.grad, sizeof(double) * B * ndim, hipMemcpyDeviceToHost, st));
+    if (curv) HIP_TRY(hipMemcpyAsync(curv, buf + P.curv, sizeof(double) * B * ndim * ndim, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     r->lane_busy &= ~1u;
     return NFA_OK;

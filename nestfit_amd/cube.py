@@ -389,6 +389,32 @@ class CubeRunner:
         return _predict_moments(self._run.handle, pix, offsets, theta, weights, chunk_rows, want_spectra,
                                 self.n_chan_tot, self.n_spec)
 
+    def normal_equations(self, pix, theta, step, lower=None, upper=None, chunk_rows=None, want_curvature=True):
+        """The normal equations of a least-squares fit at the points (pix[B], theta[B, ndim]): a
+        `NormalEquations` record of chi2[B] = sum W r^2, grad[B, ndim] = J^T W r (minus half the gradient of chi^2) and
+        curv[B, ndim, ndim] = J^T W J (None without `want_curvature`), with r = data - model, W the channels' inverse
+        variances and J the central difference of `predict_batch`'s spectra over theta_k +- step[k], the probes clipped
+        into [lower[k], upper[k]] where those are given (a parameter whose probes coincide is fixed: a zero row and column).
+        The probe rows are predicted `chunk_rows` at a time (None: 4096; a multiple of 64 and at least 1 + 2 ndim) and
+        reduced on the device; `nestfit_amd.lsq.normal_equations_from_spectra` is the same arithmetic in numpy."""
+        pix, theta = self._lsq_points(pix, theta)
+        return _normal_equations(self._run.handle, pix, theta, step, lower, upper, chunk_rows, want_curvature)
+
+    def chi_squared(self, pix, theta):
+        """chi2[B] = sum W (data - model)^2 of the points (pix[B], theta[B, ndim]): `normal_equations`' chi2, the same
+        bits, from one predicted row per point."""
+        pix, theta = self._lsq_points(pix, theta)
+        return _normal_equations(self._run.handle, pix, theta, None, None, None, None, False, want_grad=False).chi2
+
+    def _lsq_points(self, pix, theta):
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.ndim:
+            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        if pix.shape != (theta.shape[0],):
+            raise ValueError('one pixel index per row is required')
+        return pix, theta
+
 
 def _row_statistics(handle, pix, theta, n_spec):
     """nfa_runner_row_statistics on checked arrays (pix: int32[B] or None)."""
@@ -397,6 +423,29 @@ def _row_statistics(handle, pix, theta, n_spec):
     _ffi.check(_ffi.load().nfa_runner_row_statistics(handle, None if pix is None else pix.ctypes.data_as(_ffi._ip),
                                                      _ffi.dptr(theta), B, _ffi.dptr(peak), _ffi.dptr(total)))
     return peak, total
+
+
+def _normal_equations(handle, pix, theta, step, lower, upper, chunk_rows, want_curvature, want_grad=True):
+    """nfa_runner_normal_equations on checked points (pix: int32[B] or None; theta: float64[B, ndim]) -> `NormalEquations`."""
+    from .lsq import NormalEquations
+    B, ndim = theta.shape
+
+    def vector(a, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (ndim,):
+            raise ValueError(f'{name} must hold one value per parameter')
+        return a
+    step, lower, upper = vector(step, 'step'), vector(lower, 'lower'), vector(upper, 'upper')
+    chi2 = np.empty(B)
+    grad = np.empty((B, ndim)) if want_grad else None
+    curv = np.empty((B, ndim, ndim)) if want_curvature else None
+    opt = lambda a: None if a is None else _ffi.dptr(a)
+    _ffi.check(_ffi.load().nfa_runner_normal_equations(
+        handle, None if pix is None else pix.ctypes.data_as(_ffi._ip), _ffi.dptr(theta), B, opt(step), opt(lower), opt(upper),
+        0 if chunk_rows is None else int(chunk_rows), _ffi.dptr(chi2), opt(grad), opt(curv)))
+    return NormalEquations(chi2, grad, curv)
 
 
 def _predict_moments(handle, pix, offsets, theta, weights, chunk_rows, want_spectra, n_chan_tot, n_spec):
