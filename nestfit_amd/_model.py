@@ -2,14 +2,15 @@
 device-resident spectra, the runner handle and the reference's Spectrum / Runner
 behaviour (nestfit/core/core.pyx:486-561) on top of the C ABI."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
-from . import _ffi
+from . import _calls, _diagnostics, _ffi
 from ._options import (APPLY_ORDER, MODEL_GAUSSIAN, OPTION_NAMES, TMPL_MAX, Options, check_baseline_order, check_calibration,  # noqa: F401
                        check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_options, check_response,
                        check_robust, check_templates, is_set, normalise, refusal, yule_walker)
-from .core import Runner, _as_inplace_matrix, _as_inplace_vector
+from .core import Runner, _as_inplace_vector
 
 MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, MODEL_LTE = 0, 1, 3, 4                 # (MODEL_GAUSSIAN = 2: _options)
 # parameters per component
@@ -594,9 +595,107 @@ class EngineSpectrumMixin:
         return np.array(self._pred)
 
 
-# the options an EngineRunner hands to its set through its own setter, which keeps null_lnZ (read right after set_baseline) and
-# the spectra's prefactors in step; `layered` and `calibration` go to the set itself
-RUNNER_SETS = ('baseline_order', 'correlation', 'response', 'templates', 'noise_uncertainty', 'continuum', 'robust')
+# ---- the runner surface: what a one-pixel runner (`EngineRunner`) and a `CubeRunner` show of their set's options ------------
+# Per option: `value`, the words of the read-only property; `sets`, the words of `set_<name>`; `null_lnZ`, what the setter does
+# with the runner's null_lnZ -- 'read' it from the set, 'refresh' it (a one-pixel runner: `_refresh_null_lnZ`; a CubeRunner
+# reads) or None: leave it; `prefactor`: a one-pixel runner hands every spectrum's value on to the `Spectrum`'s own setter,
+# which keeps its `prefactor`.  A one-pixel runner's spectra each own a private one-spectrum set, which follows none of this:
+# what that means stands with each setter.
+RunnerOption = namedtuple('RunnerOption', 'value sets null_lnZ prefactor')
+_OWN_LNL = ("a spectrum's own `loglikelihood` is the plain one; the runner's `loglikelihood`, `loglikelihood_batch` and "
+            "`predict_batch` ")
+SURFACE = {
+    'robust': RunnerOption(
+        "None, or the float64 array [n_spec] of the degrees of freedom of the spectra's Student-t channel noise.",
+        "Sets (a number, or one per spectrum) or removes (None, zeros) the robust likelihood of the runner's spectra (DESIGN "
+        "4.18); null_lnZ follows, and a one-pixel runner's spectra's `prefactor`.  Those spectra's private one-spectrum sets "
+        "stay Gaussian: " + _OWN_LNL + "are the robust ones.", 'refresh', True),
+    'continuum': RunnerOption(
+        "None, or the float64 array of the continuum brightness temperatures behind the spectra (K): [n_spec] of a one-pixel "
+        "runner, [n_pix, n_spec] of a CubeRunner.",
+        "Sets (a number or one value per spectrum; a CubeRunner: or [n_pix, n_spec]; in K) or removes (None, zeros) the continuum "
+        "background of the runner's spectra.  null_lnZ is read again and does not change: the null model has no absorber.  A "
+        "one-pixel runner's spectra's private one-spectrum sets have no continuum: `predict` fills them from the runner's own "
+        "set (`_predict_layered`).", 'refresh', False),
+    'noise_uncertainty': RunnerOption(
+        "None, or the float64 array of the fractional uncertainties of the spectra's noise levels.",
+        "Sets (a number, or one per spectrum) or removes (None, zeros) the uncertainty of the noise levels of the runner's "
+        "spectra; null_lnZ follows, and a one-pixel runner's spectra's `prefactor`.  Those spectra's private one-spectrum sets "
+        "keep the noise exact: " + _OWN_LNL + "are the marginal ones.", 'refresh', True),
+    'templates': RunnerOption(
+        "None, or the list of the spectra's nuisance templates: per spectrum None or a float64 array [T, N_s].",
+        "Sets (a list with an array [T, N_s] or None per spectrum) or removes (None) the nuisance templates of the runner's "
+        "spectra; null_lnZ follows.  A one-pixel runner's spectra's private one-spectrum sets have none: " + _OWN_LNL
+        + "profile the templates out.", 'refresh', False),
+    'response': RunnerOption(
+        "None, or the float64 array [n_spec, 5] of the spectra's channel responses (h_-2 .. h_2).",
+        "Sets (3 or 5 taps, or such a row per spectrum) or removes (None, the identity) the channel response of the runner's "
+        "spectra; null_lnZ is untouched.  A one-pixel runner's spectra's private one-spectrum sets stay unfiltered: "
+        "`predict(params)` leaves the unsmoothed model in the spectra; the runner's `loglikelihood`, `loglikelihood_batch` and "
+        "`predict_batch` are the filtered ones.", None, False),
+    'correlation': RunnerOption(
+        "None, or the float64 array [n_spec, 2] of the spectra's noise autocorrelations (rho_1, rho_2).",
+        "Sets (a pair, or one per spectrum) or removes (None, zeros) the noise correlation of the runner's spectra; null_lnZ "
+        "follows, and a one-pixel runner's spectra's `prefactor`.  Those spectra's private one-spectrum sets stay white: a "
+        "spectrum's own `loglikelihood` and `null_lnZ` (and what `predict` leaves there) are white-noise values and must not be "
+        "combined with its correlated `prefactor`; the runner's `loglikelihood`, `loglikelihood_batch` and `predict_batch` are "
+        "the correlated ones.", 'read', True),
+    'calibration': RunnerOption(
+        "None, or the float64 array of the spectra's fractional calibration uncertainties.",
+        "Sets (a number, or one per spectrum) or removes (None, zeros) the calibration uncertainty of the runner's spectra; "
+        "null_lnZ is untouched.", None, False),
+}
+# the options a runner hands to its set through its own setters, which keep null_lnZ (read right after set_baseline) and the
+# spectra's prefactors in step; `layered` goes to the set itself
+RUNNER_SETS = ('baseline_order', *SURFACE)
+
+
+def _option_property(name):
+    def get(self):
+        value = getattr(self._ss, name)
+        if value is None:
+            return None
+        if name == 'templates':
+            return [None if a is None else a.copy() for a in value]
+        return (value[0] if name == 'continuum' and self.ONE_PIXEL else value).copy()
+    return property(get, doc=SURFACE[name].value)
+
+
+def _option_setter(name):
+    def set_option(self, value):
+        if name == 'continuum' and self.ONE_PIXEL:           # (one value per spectrum at the most, in and out)
+            value = check_continuum(value, self.n_spec, None, self.MODEL)
+        getattr(self._ss, 'set_' + name)(value)
+        self._after_set(name)
+    set_option.__name__, set_option.__qualname__, set_option.__doc__ = 'set_' + name, 'RunnerSurface.set_' + name, SURFACE[name].sets
+    return set_option
+
+
+class RunnerSurface:
+    """The part of a runner that is its spectra set's (`self._ss`) and its handle's (`self._run`): for every option of
+    SURFACE the read-only property of its name, a copy of the set's normalised value, and `set_<name>`, the set's setter and
+    then the class's `_after_set(name)`; `set_baseline`, whose value is the mirrored attribute `baseline_order`."""
+    ONE_PIXEL = False                                        # a cube's continuum is [n_pix, n_spec], one pixel's [n_spec]
+
+    def set_baseline(self, order):
+        """Sets (0..3) or removes (None) the baseline of the runner's spectra; null_lnZ follows."""
+        self._ss.set_baseline(order)
+        self.baseline_order = self._ss.baseline_order
+        self._read_null_lnZ()
+
+    def _after_set(self, name):
+        if SURFACE[name].null_lnZ is not None:
+            self._read_null_lnZ()
+
+    def set_exp_mode(self, mode):
+        """Numerical mode of this runner alone (None: the process default again): runners of different
+        modes can then be used side by side, also from different threads."""
+        self._run.set_exp_mode(mode)
+
+
+for _name in SURFACE:
+    setattr(RunnerSurface, _name, _option_property(_name))
+    setattr(RunnerSurface, 'set_' + _name, _option_setter(_name))
 
 
 def apply_options(options, ss, runner=None):
@@ -609,11 +708,20 @@ def apply_options(options, ss, runner=None):
             getattr(owner, 'set_' + name.replace('_order', ''))(value)
 
 
-class EngineRunner(Runner):
+def _noise_row(spectra):
+    """The noise of one pixel's spectra as a set takes it: [1, n_spec], or, with a noise per channel in any spectrum, for all of
+    them: [1, chan_tot]."""
+    if any(np.ndim(s.noise) for s in spectra):
+        return np.concatenate([np.broadcast_to(s.noise, (s.size,)) for s in spectra]).reshape(1, -1)
+    return np.array([[s.noise for s in spectra]])
+
+
+class EngineRunner(RunnerSurface, Runner):
     """Runner attributes and methods common to the three models (reference:
     ammonia.pyx:369-447, diazenylium.pyx:161-231, gaussian.pyx:57-112)."""
     MODEL = MODEL_AMMONIA
     N_MODEL = 6
+    ONE_PIXEL = True
 
     def _setup(self, spectra, utrans, ncomp, cold=False, lte=False, rest_freqs=None, options=None):
         """options: the mapping of the keywords that the runner's constructor took as `**options` -- the likelihood options
@@ -635,11 +743,7 @@ class EngineRunner(Runner):
             self.n_chan_tot += spec.n_chan
         self.run_lnZ = np.nan
         data = np.concatenate([s.data for s in spectra]).reshape(1, -1)
-        if any(np.ndim(s.noise) for s in spectra):        # a noise per channel in any spectrum: for all of them
-            noise = np.concatenate([np.broadcast_to(s.noise, (s.size,)) for s in spectra]).reshape(1, -1)
-        else:
-            noise = np.array([[s.noise for s in spectra]])
-        self._ss = _SpecSet([s.xarr for s in spectra], [s.trans_id for s in spectra], data, noise,
+        self._ss = _SpecSet([s.xarr for s in spectra], [s.trans_id for s in spectra], data, _noise_row(spectra),
                             model=self.MODEL, rest_freqs=rest_freqs,
                             lines=[s.lines for s in spectra] if self.MODEL in (MODEL_HYPERFINE, MODEL_LTE) else None,
                             species=getattr(self, 'SPECIES', None), fill=getattr(self, 'FILL', False))
@@ -647,69 +751,20 @@ class EngineRunner(Runner):
         self.layered, self.baseline_order = options.layered, options.baseline_order
         apply_options(options, self._ss, self)
 
-    @property
-    def robust(self):
-        """None, or the float64 array [n_spec] of the degrees of freedom of the spectra's Student-t channel noise."""
-        nu = self._ss.robust
-        return None if nu is None else nu.copy()
+    def _read_null_lnZ(self):
+        self.null_lnZ = float(self._ss.null_lnZ().sum())
 
-    def set_robust(self, nu):
-        """Sets (a number, or one per spectrum) or removes (None, zeros) the robust likelihood of this runner's spectra;
-        null_lnZ follows, and the spectra's `prefactor`.  The spectra's private one-spectrum sets stay Gaussian: a
-        spectrum's own `loglikelihood` is the plain one; the runner's `loglikelihood`, `loglikelihood_batch` and
-        `predict_batch` are the robust ones."""
-        self._ss.set_robust(nu)
-        nu = self._ss.robust
-        self._refresh_null_lnZ()
-        for k, s in enumerate(self._model_spectra()):
-            s.set_robust(None if nu is None else nu[k])
-
-    def fit_outliers(self, params):
-        """Per spectrum, every channel's posterior mean precision factor (nu + 1) / (nu + r_j^2 / sigma_j^2) at physical
-        `params`: a list of n_spec arrays, about 1 for a good channel and towards 0 for one the fit distrusted (1 everywhere
-        in a spectrum with nu = 0, NaN at a masked channel).  numpy on the host (`robust_outliers`) over `predict_batch`'s
-        spectra.  ValueError without a robust likelihood."""
-        nu = self.robust
-        if nu is None:
-            raise ValueError('this runner has no robust likelihood (robust=None)')
-        spec = self.predict_batch(np.asarray(params, dtype=np.float64).reshape(1, -1))[0][0]
-        off = self._ss.offsets
-        return [robust_outliers(s.data, spec[off[k]:off[k + 1]], s.noise, nu[k]) for k, s in enumerate(self._model_spectra())]
-
-    @property
-    def continuum(self):
-        """None, or the float64 array [n_spec] of the continuum brightness temperatures behind the spectra (K)."""
-        tc = self._ss.continuum
-        return None if tc is None else tc[0].copy()
-
-    def set_continuum(self, tc):
-        """Sets (a number, or one per spectrum, in K) or removes (None, zeros) the continuum background of this runner's
-        spectra.  null_lnZ is read again and does not change: the null model has no absorber.  The spectra's private
-        one-spectrum sets have no continuum: `predict` fills them from the runner's own set (`_predict_layered`)."""
-        self._ss.set_continuum(check_continuum(tc, self.n_spec, None, self.MODEL))
-        self._refresh_null_lnZ()
-
-    def _predict_through_set(self):
-        """Whether `predict` takes the model from the runner's own spectra set: the spectra's one-spectrum sets are summed and
-        stand before the cosmic background alone."""
-        return self.layered or self._ss.continuum is not None
-
-    @property
-    def noise_uncertainty(self):
-        """None, or the float64 array of the fractional uncertainties of the spectra's noise levels."""
-        f = self._ss.noise_uncertainty
-        return None if f is None else f.copy()
-
-    def set_noise_uncertainty(self, f):
-        """Sets (a number, or one per spectrum) or removes (None, zeros) the uncertainty of the noise levels of this
-        runner's spectra; null_lnZ follows, and the spectra's `prefactor`.  The spectra's private one-spectrum sets keep
-        the noise exact: a spectrum's own `loglikelihood` is the plain one; the runner's `loglikelihood`,
-        `loglikelihood_batch` and `predict_batch` are the marginal ones."""
-        self._ss.set_noise_uncertainty(f)
-        f = self._ss.noise_uncertainty
-        self._refresh_null_lnZ()
-        for k, s in enumerate(self._model_spectra()):
-            s.set_noise_uncertainty(None if f is None else f[k])
+    def _after_set(self, name):
+        """What a setter of SURFACE leaves behind: null_lnZ by the option's rule, and the spectra's prefactors."""
+        rule = SURFACE[name]
+        if rule.null_lnZ == 'read':
+            self._read_null_lnZ()
+        elif rule.null_lnZ == 'refresh':
+            self._refresh_null_lnZ()
+        if rule.prefactor:
+            value = getattr(self._ss, name)
+            for k, s in enumerate(self._model_spectra()):
+                getattr(s, 'set_' + name)(None if value is None else value[k])
 
     def _refresh_null_lnZ(self):
         """null_lnZ after a setter that can remove what it depended on: the runner's own set's wherever that set's likelihood is
@@ -718,87 +773,14 @@ class EngineRunner(Runner):
         ss = self._ss
         if (self.baseline_order is not None or ss.templates is not None or ss.correlation is not None
                 or ss.noise_uncertainty is not None or ss.robust is not None):
-            self.null_lnZ = float(ss.null_lnZ().sum())
+            self._read_null_lnZ()
         else:
             self.null_lnZ = float(sum(s.null_lnZ for s in self._model_spectra()))
 
-    def fit_noise(self, params):
-        """Posterior mean and standard deviation of every spectrum's noise scale t (true noise = t * stated noise) at
-        physical `params`: two arrays of n_spec values, 1 and 0 for a spectrum whose uncertainty is 0.  numpy on the host
-        (`half_chi2`, `noise_fit`, after `predict`, which this calls) with the spectra's chi^2 as the runner's set forms
-        them, whatever it profiles out, filters or correlates.  ValueError without a noise uncertainty."""
-        f = self.noise_uncertainty
-        if f is None:
-            raise ValueError('this runner has no noise uncertainty (noise_uncertainty=None)')
-        self.predict(params)
-        tmpl, corr, resp = self._ss.templates, self._ss.correlation, self._ss.response
-        mean, std = np.ones(self.n_spec), np.zeros(self.n_spec)
-        for k, s in enumerate(self._model_spectra()):
-            h, nu = half_chi2(s.data, s.get_spec(), s.noise, self.baseline_order, None if tmpl is None else tmpl[k],
-                              None if corr is None else corr[k], None if resp is None else resp[k])
-            mean[k], std[k] = noise_fit(h, nu, f[k])
-        return mean, std
-
-    @property
-    def templates(self):
-        """None, or the list of the spectra's nuisance templates: per spectrum None or a float64 array [T, N_s]."""
-        tmpl = self._ss.templates
-        return None if tmpl is None else [None if a is None else a.copy() for a in tmpl]
-
-    def set_templates(self, tmpl):
-        """Sets (a list with an array [T, N_s] or None per spectrum) or removes (None) the nuisance templates of this
-        runner's spectra; null_lnZ follows.  The spectra's private one-spectrum sets have none: a spectrum's own
-        `loglikelihood` is the plain one; the runner's `loglikelihood`, `loglikelihood_batch` and `predict_batch` profile
-        the templates out."""
-        self._ss.set_templates(tmpl)
-        self._refresh_null_lnZ()
-
-    @property
-    def response(self):
-        """None, or the float64 array [n_spec, 5] of the spectra's channel responses (h_-2 .. h_2)."""
-        resp = self._ss.response
-        return None if resp is None else resp.copy()
-
-    def set_response(self, resp):
-        """Sets (3 or 5 taps, or such a row per spectrum) or removes (None, the identity) the channel response of this
-        runner's spectra; null_lnZ is untouched.  The spectra's private one-spectrum sets stay unfiltered: `predict(params)`
-        leaves the unsmoothed model in the spectra; the runner's `loglikelihood`, `loglikelihood_batch` and `predict_batch`
-        are the filtered ones."""
-        self._ss.set_response(resp)
-
-    @property
-    def correlation(self):
-        """None, or the float64 array [n_spec, 2] of the spectra's noise autocorrelations (rho_1, rho_2)."""
-        corr = self._ss.correlation
-        return None if corr is None else corr.copy()
-
-    def set_correlation(self, corr):
-        """Sets (a pair, or one per spectrum) or removes (None, zeros) the noise correlation of this runner's spectra;
-        null_lnZ follows, and the spectra's `prefactor`.  The spectra's private one-spectrum sets stay white: a spectrum's own
-        `loglikelihood` and `null_lnZ` (and what `predict` leaves there) are white-noise values and must not be combined with
-        its correlated `prefactor`; the runner's `loglikelihood`, `loglikelihood_batch` and `predict_batch` are the
-        correlated ones."""
-        self._ss.set_correlation(corr)
-        self.null_lnZ = float(self._ss.null_lnZ().sum())
-        corr = self._ss.correlation
-        for k, s in enumerate(self._model_spectra()):
-            s.set_correlation(None if corr is None else corr[k])
-
-    @property
-    def calibration(self):
-        """None, or the float64 array of the spectra's fractional calibration uncertainties."""
-        cal = self._ss.calibration
-        return None if cal is None else cal.copy()
-
-    def set_calibration(self, cal):
-        """Sets (a number, or one per spectrum) or removes (None, zeros) the calibration uncertainty of this runner's spectra."""
-        self._ss.set_calibration(cal)
-
-    def set_baseline(self, order):
-        """Sets (0..3) or removes (None) the baseline of this runner's spectra; null_lnZ follows."""
-        self._ss.set_baseline(order)
-        self.baseline_order = self._ss.baseline_order
-        self.null_lnZ = float(self._ss.null_lnZ().sum())
+    def _predict_through_set(self):
+        """Whether `predict` takes the model from the runner's own spectra set: the spectra's one-spectrum sets are summed and
+        stand before the cosmic background alone."""
+        return self.layered or self._ss.continuum is not None
 
     def _predict_layered(self, params):
         """`predict` of a layered runner, and of one with a continuum background: the spectra's own one-spectrum sets are summed
@@ -816,77 +798,70 @@ class EngineRunner(Runner):
     def _model_spectra(self):
         return list(self.spectra)
 
+    def _diagnose(self, which, params, batch=False, **how):
+        """`_diagnostics.fit_<which>` on the one row of this pixel: the spectra's data and noise and the model they hold after
+        `predict(params)`, which this calls (batch: `predict_batch`'s row, and the spectra stay as they are)."""
+        _diagnostics.require(which, self._ss.options)
+        spectra = self._model_spectra()
+        if batch:
+            spec = self.predict_batch(np.asarray(params, dtype=np.float64).reshape(1, -1))[0]
+        else:
+            self.predict(params)
+            spec = np.concatenate([s.get_spec() for s in spectra])[None]
+        return getattr(_diagnostics, 'fit_' + which)(np.concatenate([s.data for s in spectra])[None], _noise_row(spectra), spec,
+                                                     self._ss.offsets, self._ss.options, **how)
+
     def fit_baseline(self, params):
         """Best-fit baseline of every spectrum for physical `params` (after `predict`, which this calls): one array of
         n_chan_tot values, the spectra concatenated.  numpy on the host (`baseline_fit`): for residual plots, not the hot
         path.  A runner with nuisance templates returns the whole nuisance curve, polynomial and templates
         (`nuisance_fit`).  ValueError without a baseline and without templates."""
-        tmpl = self._ss.templates
-        if self.baseline_order is None and tmpl is None:
-            raise ValueError('this runner has no baseline (baseline_order=None)')
-        self.predict(params)
-        out = []
-        for k, s in enumerate(self._model_spectra()):
-            w = channel_weights(s.noise, s.size)
-            resid = np.where(w > 0, s.data - s.get_spec(), 0.0)
-            if tmpl is None:
-                out.append(baseline_fit(resid, w, self.baseline_order))
-            else:
-                out.append(nuisance_fit(resid, w, self.baseline_order, tmpl[k])[0])
-        return np.concatenate(out)
+        return self._diagnose('baseline', params)[0]
 
     def fit_templates(self, params):
         """Best-fit amplitudes of every spectrum's templates, in the caller's scaling, for physical `params` (after `predict`,
         which this calls): a list of n_spec arrays [T] (empty for a spectrum without templates).  numpy on the host
         (`nuisance_fit`).  ValueError without templates."""
-        tmpl = self._ss.templates
-        if tmpl is None:
-            raise ValueError('this runner has no nuisance templates (templates=None)')
-        self.predict(params)
-        out = []
-        for k, s in enumerate(self._model_spectra()):
-            w = channel_weights(s.noise, s.size)
-            resid = np.where(w > 0, s.data - s.get_spec(), 0.0)
-            out.append(nuisance_fit(resid, w, self.baseline_order, tmpl[k])[1])
-        return out
+        return [a[0] for a in self._diagnose('templates', params)]
 
     def fit_gain(self, params):
         """Posterior mean and standard deviation of every spectrum's gain at physical `params` (after `predict`, which
         this calls): two arrays of n_spec values, 1 and 0 for a spectrum whose uncertainty is 0.  numpy on the host
         (`gain_fit`, with `fit_baseline`'s projection where there is a baseline).  ValueError without a calibration."""
-        cal = self.calibration
-        if cal is None:
-            raise ValueError('this runner has no calibration uncertainty (calibration=None)')
-        self.predict(params)
-        mean, std = np.ones(self.n_spec), np.zeros(self.n_spec)
-        for k, s in enumerate(self._model_spectra()):
-            w = channel_weights(s.noise, s.size)
-            sigma = 1.0 if np.ndim(s.noise) else float(s.noise)            # (channel_weights: 1 / sigma_c^2, or ones)
-            mean[k], std[k] = gain_fit(s.data, s.get_spec(), w, sigma, cal[k], self.baseline_order)
-        return mean, std
+        mean, std = self._diagnose('gain', params)
+        return mean[0], std[0]
 
-    def set_exp_mode(self, mode):
-        """Numerical mode of this runner alone (None: the process default again): runners of different
-        modes can then be used side by side, also from different threads."""
-        self._run.set_exp_mode(mode)
+    def fit_noise(self, params):
+        """Posterior mean and standard deviation of every spectrum's noise scale t (true noise = t * stated noise) at
+        physical `params`: two arrays of n_spec values, 1 and 0 for a spectrum whose uncertainty is 0.  numpy on the host
+        (`half_chi2`, `noise_fit`, after `predict`, which this calls) with the spectra's chi^2 as the runner's set forms
+        them, whatever it profiles out, filters or correlates: where `predict` goes through the runner's set, the spectra
+        hold the filtered model already.  ValueError without a noise uncertainty."""
+        mean, std = self._diagnose('noise', params, filtered=self._predict_through_set())
+        return mean[0], std[0]
+
+    def fit_outliers(self, params):
+        """Per spectrum, every channel's posterior mean precision factor (nu + 1) / (nu + r_j^2 / sigma_j^2) at physical
+        `params`: a list of n_spec arrays, about 1 for a good channel and towards 0 for one the fit distrusted (1 everywhere
+        in a spectrum with nu = 0, NaN at a masked channel).  numpy on the host (`robust_outliers`) over `predict_batch`'s
+        spectra.  ValueError without a robust likelihood."""
+        out = self._diagnose('outliers', params, batch=True)
+        off = self._ss.offsets
+        return [out[0, off[k]:off[k + 1]] for k in range(self.n_spec)]
 
     def loglikelihood(self, utheta):
         """lnL of one unit-cube point; `utheta` is overwritten with the physical
         parameters exactly like the reference (core.pyx:558-561)."""
         utheta = _as_inplace_vector(utheta)
         if utheta.shape[0] != self.ndim:
-            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {utheta.shape[0]}')
+            raise _calls.shape_error(self, utheta.shape[0])
         return float(self.loglikelihood_batch(utheta.reshape(1, -1))[0])
 
     def loglikelihood_batch(self, U, out=None):
         """lnL[B] for unit-cube rows U[B, ndim] (overwritten with parameters).  `out`: where lnL goes; with `U`
         and `out` from `nestfit_amd.pinned_empty` the kernels work on the caller's arrays directly (no copies)."""
-        U = _as_inplace_matrix(U)
-        if U.shape[1] != self.ndim:
-            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {U.shape[1]}')
-        lnL = np.empty(U.shape[0]) if out is None else out
-        if lnL.shape != (U.shape[0],) or lnL.dtype != np.float64 or not lnL.flags.c_contiguous:
-            raise ValueError('out must be a contiguous float64 array of one value per row')
+        U = _calls.unit_rows(self, U)
+        lnL = _calls.out_array(out, (U.shape[0],), 'of one value per row')
         _ffi.check(_ffi.load().nfa_runner_loglike_batch(self._run.handle, None, _ffi.dptr(U),
                                                         _ffi.dptr(lnL), U.shape[0]))
         return lnL
@@ -894,16 +869,12 @@ class EngineRunner(Runner):
     def _check_params(self, params):
         params = np.ascontiguousarray(params, dtype=np.float64)
         if params.shape[0] != self.ndim:
-            ncomp = self.ncomp
-            shape = params.shape[0]
-            raise ValueError(f'Invalid shape for ncomp={ncomp}: {shape}')
+            raise _calls.shape_error(self, params.shape[0])
         return params
 
     def predict_batch(self, theta, want_spectra=True):
         """spectra[B, n_chan_tot] and lnL[B] for parameter rows theta[B, ndim]."""
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.ndim != 2 or theta.shape[1] != self.ndim:
-            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        theta = _calls.parameter_rows(self, theta)
         B = theta.shape[0]
         spec = np.empty((B, self._ss.chan_tot)) if want_spectra else None
         lnl = np.empty(B)
@@ -915,38 +886,25 @@ class EngineRunner(Runner):
     def row_statistics(self, theta):
         """(peak, total), [B, n_spec] each, of the model spectra of parameter rows theta[B, ndim], formed on the device
         (`CubeRunner.row_statistics`)."""
-        from .cube import _row_statistics
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.ndim != 2 or theta.shape[1] != self.ndim:
-            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
-        return _row_statistics(self._run.handle, None, theta, self.n_spec)
+        return _calls._row_statistics(self._run.handle, None, _calls.parameter_rows(self, theta), self.n_spec)
 
     def predict_moments(self, theta, weights=None):
         """Weighted moments of the model spectra over the parameter rows theta[B, ndim] with weights[B] >= 0 (None: all
         ones), one segment: a `PosteriorMoments` record of one row per field (`CubeRunner.predict_moments`)."""
-        from .cube import _predict_moments
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.ndim != 2 or theta.shape[1] != self.ndim:
-            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
+        theta = _calls.parameter_rows(self, theta)
         offsets = np.array([0, theta.shape[0]], dtype=np.int64)
-        return _predict_moments(self._run.handle, None, offsets, theta, weights, None, True, self._ss.chan_tot, self.n_spec)
+        return _calls._predict_moments(self._run.handle, None, offsets, theta, weights, None, True, self._ss.chan_tot, self.n_spec)
 
     def normal_equations(self, theta, step, lower=None, upper=None, chunk_rows=None, want_curvature=True):
         """The normal equations of a least-squares fit at the parameter rows theta[B, ndim]: a `NormalEquations` record
         of chi2, grad = J^T W r and curv = J^T W J (`CubeRunner.normal_equations`)."""
-        from .cube import _normal_equations
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.ndim != 2 or theta.shape[1] != self.ndim:
-            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
-        return _normal_equations(self._run.handle, None, theta, step, lower, upper, chunk_rows, want_curvature)
+        return _calls._normal_equations(self._run.handle, None, _calls.parameter_rows(self, theta), step, lower, upper, chunk_rows,
+                                        want_curvature)
 
     def chi_squared(self, theta):
         """chi2[B] of the parameter rows theta[B, ndim] (`CubeRunner.chi_squared`)."""
-        from .cube import _normal_equations
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.ndim != 2 or theta.shape[1] != self.ndim:
-            raise ValueError(f'Invalid shape for ncomp={self.ncomp}: {theta.shape}')
-        return _normal_equations(self._run.handle, None, theta, None, None, None, None, False, want_grad=False).chi2
+        return _calls._normal_equations(self._run.handle, None, _calls.parameter_rows(self, theta), None, None, None, None, False,
+                                        want_grad=False).chi2
 
 
 def par_names(short, ncomp=None):

@@ -503,6 +503,99 @@ def test_fit_noise_finds_an_understated_noise(engine, mode, mode_guard):
         probe.fit_noise(truth)
 
 
+def _smoothed_noise(rng, shape):
+    """Unit-variance white noise smoothed with the Hanning kernel along the last axis."""
+    white = rng.normal(size=(*shape[:-1], shape[-1] + 2))
+    return (0.25 * white[..., :-2] + 0.5 * white[..., 1:-1] + 0.25 * white[..., 2:]) / np.sqrt(0.375)
+
+
+def _noise_scale_of(data, filtered_model, noise, rho, f):
+    """`noise_fit` of the chi^2 of a model that is filtered already: ONE filter, the set's own."""
+    from nestfit_amd._model import half_chi2, noise_fit
+    return noise_fit(*half_chi2(data, filtered_model, noise, None, None, rho, None), f)
+
+
+@pytest.mark.parametrize('mode', MODES)
+def test_fit_noise_of_a_cube_filters_the_model_once(engine, mode, mode_guard):
+    """A Gaussian cube of one spectrum of 64 channels and 2 pixels, lines of sigma = 1.5 channels, `smoothed(HANNING_RESPONSE)`
+    and f = 0.3; the data are the filtered model plus Hanning-smoothed noise stated at 1 / 1.3 of its level.  `fit_noise` is
+    `noise_fit` of the chi^2 of `predict_batch`'s spectra, which ARE the filtered model, to rel 1e-12: the same numpy on the
+    same bits (filtering them again moved the mean by 2e-2).  A GaussianRunner of each pixel, whose spectrum holds the
+    unfiltered model and whose chi^2 filters it on the host, agrees to rel 1e-9: the rounding of a five-tap sum."""
+    import nestfit_amd as na
+    from nestfit_amd.cube import CubeRunner
+    engine.set_exp_mode(mode)
+    n, stated, f = 64, 0.1, 0.3
+    velo, x = _gauss_axis(n)
+    theta = np.array([[velo[30] + 0.1 * DV, 1.5 * DV, 1.5], [velo[41] - 0.2 * DV, 1.5 * DV, 0.8]])
+    pix = np.arange(2, dtype=np.int32)
+    kw = dict(ncomp=1, model=2, rest_freqs=[GAUSS_NU], **na.smoothed(na.HANNING_RESPONSE))
+    probe = CubeRunner([x], [-1], np.zeros((1, n)), np.full((1, 1), stated), None, **kw)
+    model, _ = probe.predict_batch(np.zeros(2, dtype=np.int32), theta)
+    data = model + 1.3 * stated * _smoothed_noise(np.random.default_rng(23), model.shape)
+    cube = CubeRunner([x], [-1], data, np.full((2, 1), stated), None, noise_uncertainty=f, **kw)
+    mean, std = cube.fit_noise(pix, theta)
+    assert mean.shape == std.shape == (2, 1)
+    spec = cube.predict_batch(pix, theta)[0]
+    assert np.array_equal(spec, model)
+    for b in range(2):
+        want = _noise_scale_of(data[b], spec[b], stated, cube.correlation[0], f)
+        print(f'cube fit_noise {mode} pixel {b}: {mean[b, 0]!r} +- {std[b, 0]!r}, want {want!r}')
+        assert (mean[b, 0], std[b, 0]) == pytest.approx(want, rel=1e-12)
+        run = engine.GaussianRunner.from_data([x, data[b], stated, GAUSS_NU], None, ncomp=1, noise_uncertainty=f,
+                                              **na.smoothed(na.HANNING_RESPONSE))
+        one = run.fit_noise(theta[b])
+        print(f'     GaussianRunner: {one[0][0]!r} +- {one[1][0]!r}')
+        assert (one[0][0], one[1][0]) == pytest.approx((mean[b, 0], std[b, 0]), rel=1e-9)
+
+
+@pytest.mark.parametrize('mode', MODES)
+def test_fit_noise_of_a_layered_runner_filters_the_model_once(engine, mode, mode_guard):
+    """A layered HyperfineRunner of two spectra of 64 channels, one component, the same response and f: `predict` goes through
+    the runner's set, so the spectra hold the FILTERED model, and `fit_noise` is `noise_fit` of their chi^2 without another
+    filter, to rel 1e-12."""
+    import nestfit_amd as na
+    import hf_restatement as hfr
+    engine.set_exp_mode(mode)
+    n, stated, f = 64, 0.05, 0.3
+    tables = [engine.LineTable(72.4e9, [0.0], [1.0], name='one'), engine.LineTable(86.1e9, [-3.0, 2.0], [0.4, 0.6], name='two')]
+    axes = [t.nu * (1.0 - np.linspace(10.0, -10.0, n) / hfr.CKMS) for t in tables]
+    theta = np.array([0.3, 9.0, 0.2, 0.7])
+    kw = dict(ncomp=1, layered=True, noise_uncertainty=f, **na.smoothed(na.HANNING_RESPONSE))
+    probe = engine.HyperfineRunner.from_data([[x, np.zeros(n), stated, t] for x, t in zip(axes, tables)], None, **kw)
+    model = probe.predict_batch(theta[None])[0][0]
+    data = model + 1.3 * stated * _smoothed_noise(np.random.default_rng(29), (2, n)).reshape(-1)
+    run = engine.HyperfineRunner.from_data([[x, data[k * n:(k + 1) * n], stated, t] for k, (x, t) in enumerate(zip(axes, tables))],
+                                           None, **kw)
+    mean, std = run.fit_noise(theta)
+    assert mean.shape == std.shape == (2,)
+    spec = run.predict_batch(theta[None])[0][0]
+    assert np.array_equal(spec, model) and np.array_equal(np.concatenate([s.get_spec() for s in run.spectra]), spec)
+    for k in range(2):
+        want = _noise_scale_of(data[k * n:(k + 1) * n], spec[k * n:(k + 1) * n], stated, run.correlation[k], f)
+        print(f'layered fit_noise {mode} spectrum {k}: {mean[k]!r} +- {std[k]!r}, want {want!r}')
+        assert (mean[k], std[k]) == pytest.approx(want, rel=1e-12)
+
+
+def test_a_cube_takes_and_drops_a_calibration(engine):
+    """`CubeRunner.set_calibration`, the setter the one option surface gives the cube: on, the lnL is another; off, the one
+    before, bit for bit; null_lnZ does not move."""
+    from nestfit_amd.cube import CubeRunner
+    n = 64
+    velo, x = _gauss_axis(n)
+    theta = np.array([[velo[30], 1.5 * DV, 1.5], [velo[41], 1.5 * DV, 0.8]])
+    pix = np.arange(2, dtype=np.int32)
+    data = np.random.default_rng(31).normal(0, 0.1, (2, n))
+    cube = CubeRunner([x], [-1], data, np.full((2, 1), 0.1), None, ncomp=1, model=2, rest_freqs=[GAUSS_NU])
+    before, null = cube.predict_batch(pix, theta, want_spectra=False)[1], cube.null_lnZ.copy()
+    cube.set_calibration(0.1)
+    assert np.array_equal(cube.calibration, [0.1]) and np.array_equal(cube.null_lnZ, null)
+    assert not np.any(cube.predict_batch(pix, theta, want_spectra=False)[1] == before)
+    cube.set_calibration(None)
+    assert cube.calibration is None and np.array_equal(cube.null_lnZ, null)
+    assert np.array_equal(cube.predict_batch(pix, theta, want_spectra=False)[1], before)
+
+
 # ---------------------------------------------------------------------------- 8. the device sampler
 def test_the_device_sampler_follows_the_twin(engine):
     """One Gaussian component, 64 channels, nlive 50, noise_uncertainty = 0.2: `fit_pixels(device=True)` against the numpy
