@@ -154,6 +154,10 @@ int nfa_specset_create(nfa_specset **out, int n_spec, const int64_t *sizes,
 #define NFA_MODEL_GAUSSIAN     2
 #define NFA_MODEL_HYPERFINE    3   /* nfa_specset_create_lines below; this function returns NFA_ERR_ARG for it */
 #define NFA_MODEL_LTE          4   /* nfa_specset_create_lte below; this function returns NFA_ERR_ARG for it */
+#define NFA_MODEL_GRID         5   /* nfa_specset_create_grid below; this function returns NFA_ERR_ARG for it */
+#define NFA_GRID_PARAMS        5   /* voff, tkin, lnden, lncol, sigm */
+#define NFA_GRID_MAXN          64      /* nodes of an axis of an excitation grid */
+#define NFA_GRID_MAXCELLS      65536   /* ... and of the three axes together: nt * nn * nc */
 int nfa_specset_create_model(nfa_specset **out, int model, int n_spec, const int64_t *sizes,
                              const int32_t *trans_ids, const double *rest_freqs,
                              const double *const *xarr, int64_t n_pix, const double *data,
@@ -273,6 +277,43 @@ int nfa_specset_create_lte_filled(nfa_specset **out, int n_spec, const int64_t *
                                   int n_species, const int32_t *species, const int32_t *n_q, const double *q_temp, const double *q_val,
                                   const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
                                   const double *chan_noise);
+/* model 5 = non-LTE excitation from a grid of the caller's: every transition of a species has an excitation temperature
+ * and an optical depth of its own, read from radiative-transfer tables (RADEX, LVG) over kinetic temperature, H2 density
+ * and column density per line width.  No molecular data ship: the caller brings the tables, as with line tables and
+ * partition functions.  NFA_GRID_PARAMS = 5 parameters per component, parameter-major:
+ *     voff (km/s), tkin (K), lnden = log10 n(H2)/cm^-3, lncol = log10 N/cm^-2, sigm (km/s)
+ * Spectrum s covers ONE transition with any hyperfine structure inside it: n_lines, rest_freqs, voff and tau_wts as for
+ * nfa_specset_create_lte (the weights of a transition sum to 1).  The three axes are shared by all spectra: tkin[nt],
+ * lnden[nn] and lncd[nc], each strictly ascending and finite with 1..64 nodes (one node: the axis has no effect),
+ * nt nn nc <= 65536; lncd is log10 of the column density per unit line width, N / (cm^-2 (km/s)^-1), the width as FWHM.
+ * tex[n_spec][nt][nn][nc] (K) and ltau[n_spec][nt][nn][nc] hold for each spectrum the excitation temperature and log10
+ * of the line's peak optical depth summed over its hyperfine lines.  For component c and spectrum s:
+ *     x = (tkin_c, lnden_c, lncol_c - log10(sqrt(8 ln 2) sigm_c))
+ *     per axis a with nodes a_0 < ... < a_{n-1}:
+ *         k = #{ i in 1..n-2 : x >= a_i }                     (n = 1: k = 0)
+ *         f = clamp((x - a_k) / (a_{k+1} - a_k), 0, 1)        (n = 1: f = 0) -- outside the grid the edge value holds
+ *     v(x) = trilinear over the eight corners, each step v0 + f (v1 - v0), lncd innermost, then lnden, then tkin
+ *     tex_{c,s} = tex_s(x)      tau_main_{c,s} = 10^ltau_s(x)
+ * and the spectrum follows as for model 3: c_hf_predict with (voff_c, tex_{c,s}, tau_main_{c,s}, sigm_c) on spectrum s,
+ * line i with tau_main_{c,s} tau_wts[i].  A tkin, lnden or lncol that is not finite, or a sigm that is not an ordinary
+ * positive number, gives a NaN tau_main (model 4's rule).  CLAMPING is deliberate: a prior that leaves the grid sees a
+ * flat likelihood in that direction; nothing is extrapolated.
+ * A set of this model takes a noise per channel, masked channels, a baseline (nfa_specset_set_baseline), layered
+ * transfer and a noise uncertainty; the setters of templates, a continuum, a correlation, a response, a calibration and a
+ * robust likelihood refuse it ("a set of the excitation-grid model takes no ...") and leave it as it was.  Served by the
+ * batch entry points (host and device pointers, predict), single points and a broker's handful (through the batch
+ * kernels), the broker, the callback and nfa_ring_serve; nfa_ring_serve_device refuses it ("the resident kernel has no
+ * form for an excitation per spectrum: use nfa_ring_serve").
+ * Returns NFA_ERR_ARG, with a message, for everything nfa_specset_create_lines refuses, a transition whose weights do
+ * not sum to 1 within 1e-6, a node count outside 1..64, nt nn nc above 65536, an axis that is not finite and strictly
+ * ascending, a tex that is not finite and positive (a population inversion: cut the grid) and an ltau that is not
+ * finite. */
+int nfa_specset_create_grid(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
+                            const double *rest_freqs, const double *voff, const double *tau_wts,
+                            int nt, const double *tkin, int nn, const double *lnden, int nc, const double *lncd,
+                            const double *tex, const double *ltau,
+                            const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                            const double *chan_noise);
 /* A shipped line table, as a template for nfa_specset_create_lines: model 0 (trans_id 1..9) or 1 (trans_id 1..3);
  * voff and tau_wts take 50 doubles each (zero behind the *n lines), *nu the rest frequency in Hz.  Needs no device. */
 int nfa_builtin_lines(int model, int trans_id, double *nu, double *voff, double *tau_wts, int *n);

@@ -55,6 +55,8 @@ SIGNATURES = {
                                                    C.POINTER(_dp), C.c_int64, _dp, _dp]),
     'nfa_specset_create_lines': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _lp, _ip, _dp, _dp, _dp,
                                            C.POINTER(_dp), C.c_int64, _dp, _dp, _dp]),
+    'nfa_specset_create_grid': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _lp, _ip, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp,
+                                          C.c_int, _dp, _dp, _dp, C.POINTER(_dp), C.c_int64, _dp, _dp, _dp]),
     'nfa_specset_create_lte': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _lp, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
                                          C.c_int, _dp, _dp, C.POINTER(_dp), C.c_int64, _dp, _dp, _dp]),
     'nfa_specset_create_lte_bands': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _lp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp,

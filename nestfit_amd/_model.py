@@ -9,12 +9,13 @@ import numpy as np
 from . import _calls, _diagnostics, _ffi
 from ._options import (APPLY_ORDER, MODEL_GAUSSIAN, OPTION_NAMES, TMPL_MAX, Options, check_baseline_order, check_calibration,  # noqa: F401
                        check_continuum, check_correlation, check_layered, check_noise_uncertainty, check_options, check_response,
-                       check_robust, check_templates, is_set, normalise, refusal, yule_walker)
+                       check_robust, check_templates, is_set, model_refusal, normalise, refusal, yule_walker)
 from .core import Runner, _as_inplace_vector
 
-MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, MODEL_LTE = 0, 1, 3, 4                 # (MODEL_GAUSSIAN = 2: _options)
+MODEL_AMMONIA, MODEL_DIAZENYLIUM, MODEL_HYPERFINE, MODEL_LTE, MODEL_GRID = 0, 1, 3, 4, 5   # (MODEL_GAUSSIAN = 2: _options)
 # parameters per component
-N_MODEL = {MODEL_AMMONIA: 6, MODEL_DIAZENYLIUM: 4, MODEL_GAUSSIAN: 3, MODEL_HYPERFINE: 4, MODEL_LTE: 4}
+N_MODEL = {MODEL_AMMONIA: 6, MODEL_DIAZENYLIUM: 4, MODEL_GAUSSIAN: 3, MODEL_HYPERFINE: 4, MODEL_LTE: 4, MODEL_GRID: 5}
+TABLED_MODELS = (MODEL_HYPERFINE, MODEL_LTE, MODEL_GRID)   # the models whose spectra bring their line tables (`lines`)
 
 HANNING = (2.0 / 3.0, 1.0 / 6.0)      # (rho_1, rho_2) of white noise smoothed with the Hanning kernel (1/4, 1/2, 1/4)
 
@@ -296,11 +297,21 @@ class _SpecSet:
         per component.  fill: such a set with a beam filling factor per component as one more parameter, the last
         (nfa_specset_create_lte_filled)."""
         self.model = int(model)
-        if (self.model in (MODEL_HYPERFINE, MODEL_LTE)) != (lines is not None):
-            raise ValueError('the hyperfine model (3) and the LTE model (4), and no other, take `lines`: one LineTable '
-                             '(LteLines) per spectrum')
+        if (self.model in TABLED_MODELS) != (lines is not None):
+            raise ValueError('the hyperfine model (3), the LTE model (4) and the excitation-grid model (5), and no other, take '
+                             '`lines`: one LineTable (LteLines, GridLines) per spectrum')
         molecule = None
-        if lines is not None:
+        self.grid = None
+        if self.model == MODEL_GRID:
+            from .excitation import check_one_grid
+            if species is not None or fill:
+                raise ValueError('`species` and `fill` belong to the LTE model (4)')
+            lines = list(lines)
+            if len(lines) != len(xarrs):
+                raise ValueError('`lines` must hold one GridLines per spectrum')
+            self.grid = check_one_grid(lines)
+            trans_ids = [-1] * len(lines)
+        elif lines is not None:
             from .hyperfine import LineTable
             from .lte import LteBand, LteBlend, check_mix_lines, check_one_molecule, transitions_of
             lines = list(lines)
@@ -348,7 +359,21 @@ class _SpecSet:
         self.rest_freqs = (None if rest_freqs is None
                            else np.ascontiguousarray(rest_freqs, dtype=np.float64))
         sizes_p = self.sizes.ctypes.data_as(_ffi._lp)
-        if lines is not None:                       # the caller's tables: exactly one of the two noise arguments
+        if self.grid is not None:                   # the excitation-grid model: the lines creator's arguments and the grid
+            g = self.grid
+            self.rest_freqs = np.array([t.nu for t in lines], dtype=np.float64)
+            n_lines = np.array([t.n for t in lines], dtype=np.int32)
+            voff = np.ascontiguousarray(np.concatenate([t.voff for t in lines]), dtype=np.float64)
+            tau_wts = np.ascontiguousarray(np.concatenate([t.tau_wts for t in lines]), dtype=np.float64)
+            tex = np.ascontiguousarray(np.stack([t.tex for t in lines]), dtype=np.float64)
+            ltau = np.ascontiguousarray(np.stack([t.ltau for t in lines]), dtype=np.float64)
+            axes = [np.ascontiguousarray(a) for a in (g.tkin, g.lnden, g.lncd)]
+            rc = lib.nfa_specset_create_grid(
+                C.byref(h), self.n_spec, sizes_p, n_lines.ctypes.data_as(_ffi._ip), _ffi.dptr(self.rest_freqs), _ffi.dptr(voff),
+                _ffi.dptr(tau_wts), axes[0].size, _ffi.dptr(axes[0]), axes[1].size, _ffi.dptr(axes[1]), axes[2].size,
+                _ffi.dptr(axes[2]), _ffi.dptr(tex), _ffi.dptr(ltau), xp, self.n_pix, _ffi.dptr(data),
+                None if self.per_channel else _ffi.dptr(noise), _ffi.dptr(noise) if self.per_channel else None)
+        elif lines is not None:                     # the caller's tables: exactly one of the two noise arguments
             self.rest_freqs = np.array([t.nu for t in lines], dtype=np.float64)
             banded = species is not None or any(isinstance(t, LteBand) for t in lines)
             n_trans = np.array([len(transitions_of(t)) for t in lines], dtype=np.int32)
@@ -405,7 +430,7 @@ class _SpecSet:
         then the record."""
         value = normalise(name, value, self.n_spec, self.sizes, **about)
         if is_set(value):
-            why = refusal(name, self.options.has(self.masked))
+            why = model_refusal(name, self.model) or refusal(name, self.options.has(self.masked))
             if why is not None:
                 raise ValueError(why)
         call = getattr(_ffi.load(), 'nfa_specset_set_' + name.replace('_order', ''))
@@ -745,7 +770,7 @@ class EngineRunner(RunnerSurface, Runner):
         data = np.concatenate([s.data for s in spectra]).reshape(1, -1)
         self._ss = _SpecSet([s.xarr for s in spectra], [s.trans_id for s in spectra], data, _noise_row(spectra),
                             model=self.MODEL, rest_freqs=rest_freqs,
-                            lines=[s.lines for s in spectra] if self.MODEL in (MODEL_HYPERFINE, MODEL_LTE) else None,
+                            lines=[s.lines for s in spectra] if self.MODEL in TABLED_MODELS else None,
                             species=getattr(self, 'SPECIES', None), fill=getattr(self, 'FILL', False))
         self._run = _RunnerHandle(self._ss, utrans, self.ncomp, cold, lte)
         self.layered, self.baseline_order = options.layered, options.baseline_order

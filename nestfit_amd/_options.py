@@ -334,6 +334,20 @@ RULES = (
 )
 
 
+MODEL_GRID = 5
+# A set of the excitation-grid model (nestfit_amd.excitation) runs a kernel side of its own, and a side is
+# exclusive: the options of the other sides, and a calibration, are refused by the model, in the engine's words.
+_GRID_TAKES_NO = {'calibration': 'calibration uncertainty', 'correlation': 'noise correlation', 'response': 'channel response',
+                  'templates': 'nuisance templates', 'continuum': 'continuum background', 'robust': 'robust likelihood'}
+
+
+def model_refusal(takes, model):
+    """Why a set of `model` does not take option `takes` whatever else it has, or None: the excitation-grid model's six."""
+    if model is not None and int(model) == MODEL_GRID and takes in _GRID_TAKES_NO:
+        return 'a set of the excitation-grid model takes no ' + _GRID_TAKES_NO[takes]
+    return None
+
+
 def refusal(takes, has):
     """Why a set that has the features `has` (names of OPTION_NAMES and 'masked') does not take option `takes`, or None."""
     return next((why for t, h, why in RULES if t == takes and h in has), None)
@@ -477,7 +491,7 @@ def check_options(options, n_spec, sizes=None, masked=False, model=None, n_pix=N
         if name in options:
             value = normalise(name, options[name], n_spec, sizes, model, n_pix)
             if is_set(value):
-                why = refusal(name, out.has(masked))
+                why = model_refusal(name, model) or refusal(name, out.has(masked))
                 if why is not None:
                     raise ValueError(why)
             setattr(out, name, value)

@@ -117,6 +117,12 @@ struct SpecDev {
     // k sum log1p(a d^2): part = totsq + k sum log1p(p (g p - 2 g d)) makes -part / (2 sigma_ref^2) the likelihood.  Such a
     // set runs lnl_kernel_side<..., LNL_SIDE_ROBUST>.
     const double  *rob;
+    // Spectra sets of the excitation-grid model (nfa_specset_create_grid; null for models 0..4): the axes and
+    // the tables of tex and log10 tau per spectrum.  grid_derive_kernel (nfa_setup.h) reads it between the two stages and
+    // writes the item records of such a set, which are the larger ones (drec_size's texs): an excitation temperature per
+    // (component, spectrum).  Such a set always has chan_w, wdata and bl (a scalar noise: chan_w == 1; a zeroed record,
+    // bl_order -1, without a baseline) and runs lnl_kernel_side<..., LNL_SIDE_TEXS>.
+    const GridRec *grid;
 };
 // entries of R^-1 of a spectrum: its diagonal at channels 0 and N-1, 1 and N-2, and between; its first off-diagonal at
 // (0, 1) and (N-2, N-1), and between; its second off-diagonal
@@ -238,7 +244,18 @@ __device__ __forceinline__ double bl_quad_cal(const double *R, const double *mp,
 // factor 10^lnff there, in the record of every spectrum, between the two stages, and lnl_body<..., FILL> multiplies the
 // component's Tb by it
 #define DK_FILL 15
+// texs: the record of a set of the excitation-grid model (grid_derive_kernel, nfa_setup.h; lnl_body<..., LNL_F_TEXS>), whose
+// leading block is four doubles per (component, spectrum) in place of per component:
+//   [(c*nspec + s)*4 + 0] tex of (component, spectrum)  [+ 1] sigm/CKMS  [+ 2] voff/CKMS  [+ 3] 1/tex
+// followed by the same DREC_CS block per (component, spectrum).
+static_assert(LP_DREC_CS == DREC_CS, "lnl_drec_doubles (nfa_launch_plan.h) counts this record");
+__host__ __device__ constexpr int drec_lead(int ncomp, int nspec, bool texs = false) { return 4 * ncomp * (texs ? nspec : 1); }
 __host__ __device__ inline int drec_size(int ncomp, int nspec) { return 4 * ncomp + ncomp * nspec * DREC_CS; }
+__host__ __device__ constexpr int drec_size(int ncomp, int nspec, bool texs) {
+    return drec_lead(ncomp, nspec, texs) + ncomp * nspec * DREC_CS;
+}
+static_assert(drec_size(3, 2, true) == lnl_drec_doubles(3, 2, true) && drec_size(3, 2, false) == lnl_drec_doubles(3, 2),
+              "the engine sizes a lane's records through lnl_drec_doubles");
 
 // Up to NFA_GROUP_MAX batches of `each` rows that a caller enqueues one after the other travel as ONE launch (the
 // engine coalesces them, nfa_engine.hip): item b of the launch is row b - c * each of batch c = b / each, and every
@@ -938,6 +955,23 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     constexpr bool LAYER = (FLAGS & LNL_K_LAYER) != 0, CALIB = (FLAGS & LNL_K_CALIB) != 0, CORR = (FLAGS & LNL_F_CORR) != 0;
     constexpr bool RESP = (FLAGS & LNL_F_RESP) != 0, TMPL = (FLAGS & LNL_F_TMPL) != 0, CONT = (FLAGS & LNL_F_CONT) != 0;
     constexpr bool ROBUST = (FLAGS & LNL_F_ROBUST) != 0;
+    // TEXS (the baseline form in the general component form only): an excitation temperature per (component, spectrum), the
+    // excitation-grid model's.  The item's record is the larger one (drec_size's texs): tex, sigm/CKMS, voff/CKMS
+    // and 1/tex in four doubles per (component, spectrum), where grid_derive_kernel left them.  The three sites that read tex
+    // or 1/tex of a component -- the hoist, the fast mode's general class, the exact modes' x = T0 / tex -- read them there,
+    // the line constants their width and velocity, and the DREC_CS blocks lie behind the wider leading block: LEAD4(c) and
+    // DLEAD.  Nothing else differs from the baseline form: no LDS, no barrier, the same summation rule.
+    // Both are macros over this function's locals, undefined behind it: constant-folded expressions, so that the instances
+    // without the flag keep their instructions (profiles/grid/README.md).  They read
+    //   DLEAD     TEXS, ncomp, nspec           where the DREC_CS blocks begin (drec_lead)
+    //   LEAD4(c)  TEXS, nspec, s               the four leading doubles of component c: the component's own, or (TEXS)
+    //                                          those of (component, the unit's spectrum s)
+    // and may be used only below the definitions of those locals (`s`: the unit's spectrum, behind the early return).
+    constexpr bool TEXS = (FLAGS & LNL_F_TEXS) != 0;
+#define DLEAD (TEXS ? 4 * ncomp * nspec : 4 * ncomp)
+#define LEAD4(c) (TEXS ? ((c) * nspec + s) * 4 : (c) * 4)
+    static_assert(!TEXS || (NCOMP == 0 && !DYN && WEIGHTED && BASELINE && !CALIB && !CORR && !RESP && !TMPL && !CONT && !ROBUST),
+                  "an excitation per spectrum: the baseline form in the general component form, beside no other side");
     typedef typename std::conditional<MODE == 2, float, double>::type tau_t;
     constexpr int NC = NCOMP > 0 ? NCOMP : 1;
     // the fast mode's narrow form: at most 26 lines per transition (32-bit line masks), fp32 optical depth, the
@@ -960,7 +994,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
     const int lane = lane_, waves = blockDim.x >> 6;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ncomp = NCOMP > 0 ? NCOMP : S.ncomp, nspec = S.n_spec;
-    const int drec = drec_size(ncomp, nspec);
+    // (not DLEAD + ncomp nspec DREC_CS: written so, lnl_kernel_queue<*, 0> and ring_serve_kernel<2, 0> change their registers)
+    const int drec = TEXS ? drec_size(ncomp, nspec, true) : drec_size(ncomp, nspec);
 
     // One unit per wave, or `split` = 2 or 4 waves per unit (small launches: more, shorter waves than wave
     // slots, so that the hardware places them as slots free up; the waves of a unit share its line table).
@@ -1022,7 +1057,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
         double r_nucen = 0.0, r_idenom = 0.0, r_htau = 0.0;
         int r_lo = 0, r_len = 0, slot = p;
         if (i < nhf) {
-            const LineConst lc = nf_line<MODE == 0>(t, lrow->hfreq, i, D[b * drec + c * 4 + 2], D[b * drec + c * 4 + 1], nu0, S.nu_min[s],
+            const LineConst lc = nf_line<MODE == 0>(t, lrow->hfreq, i, D[b * drec + LEAD4(c) + 2], D[b * drec + LEAD4(c) + 1], nu0, S.nu_min[s],
                                          S.nu_chan[s], N, S.r_chan[s]);
             int lo = lc.lo;
             const int hi = lc.hi;
@@ -1040,7 +1075,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
             r_nucen = lc.nucen;
             r_idenom = lc.idenom;
             r_htau = S.band ? S.band_tau[((b * ncomp + c) * nspec + s) * NFA_BAND_MAXT + S.band->grp[s][i]] * lrow->tauw[i]
-                            : D[b * drec + 4 * ncomp + (c * nspec + s) * DREC_CS + DK_TMAIN] * lrow->tauw[i];
+                            : D[b * drec + DLEAD + (c * nspec + s) * DREC_CS + DK_TMAIN] * lrow->tauw[i];
             r_lo = lo;
             r_len = hi > lo ? hi - lo : 0;
             slot = c * G.nhf_max + lrow->rank[i];                 // velocity order: the lines of a row are neighbours
@@ -1099,14 +1134,14 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
             if (!PACK2) window_of(c, lane, wlo[c], whi[c]);
             lbase_c[c] = (unsigned)(uintptr_t)(lds_char_p)(w_line + c * G.nhf_max);
             asm volatile("" : "+v"(lbase_c[c]));
-            const int dko = 4 * ncomp + (c * nspec + s) * DREC_CS;
+            const int dko = DLEAD + (c * nspec + s) * DREC_CS;
             ck_kind[c] = Dk[dko + DK_KIND]; ck_a0x[c] = Dk[dko + DK_A0X]; ck_b0x[c] = Dk[dko + DK_B0X];
             if (MODE != 2) {
                 ck_cls[c] = __builtin_amdgcn_readfirstlane(tb_class(ck_kind[c]));
                 asm volatile("" : "+s"(ck_cls[c]));
             }
             if (HOISTX) {
-                cx_tex[c] = Dk[c * 4]; cx_rtex[c] = Dk[c * 4 + 3];
+                cx_tex[c] = Dk[LEAD4(c)]; cx_rtex[c] = Dk[LEAD4(c) + 3];
                 cx_xkind[c] = Dk[dko + DK_XKIND]; cx_xs[c] = Dk[dko + DK_XS]; cx_xlo[c] = Dk[dko + DK_XLO]; cx_ylo[c] = Dk[dko + DK_YLO];
             }
         }
@@ -1346,7 +1381,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                 if (MODE != 2) asm volatile("" : "+s"(cls_hot));
                 // FILL: the component's beam filling factor (the same in the record of every spectrum)
                 double ff = 1.0;
-                if constexpr (FILL) ff = Dk[4 * ncomp + (c * nspec + s) * DREC_CS + DK_FILL];
+                if constexpr (FILL) ff = Dk[DLEAD + (c * nspec + s) * DREC_CS + DK_FILL];
                 // Table mode: every class hands its two factors to ONE multiply-add behind the chain, pred <- fx fy + pred.  The
                 // usual class: fx = T0 (y - tbg), fy = 1 - FastExp(tau).  The rare classes, whose reference order is a rounded
                 // product added to pred: fx = that product, fy = 1.0 -- fx * 1.0 + pred rounds once, like the addition: the same
@@ -1381,7 +1416,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     pred += (double)tau;                              // tau == 0 adds nothing
                     return false;
                 }
-                const int dko = 4 * ncomp + (c * nspec + s) * DREC_CS;
+                const int dko = DLEAD + (c * nspec + s) * DREC_CS;
                 if (MODE == 2) {
                     double g;                                         // T0 (y(T0) - tbg)
                     if (cls == 2) {
@@ -1398,7 +1433,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                         unsigned jr = jo;
                         asm volatile("" : "+v"(jr));
                         const double T0 = *(const double *)((const char *)t0s + jr), tbg = *(const double *)((const char *)tbgs + jr);
-                        const double y = nf_iemtex(T0 / Dk[c * 4], g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
+                        const double y = nf_iemtex(T0 / Dk[LEAD4(c)], g_t0x, g_t0y, S.t0_xmin, S.t0_xmax, S.t0_inv_dx);
                         g = T0 * (y - tbg);
                     }
                     if constexpr (CONT) g -= tc;                      // the source behind all layers: g - Tc, then - pred, then f
@@ -1415,7 +1450,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     // a tex whose mantissa is all ones, has probability 2^-52): the same bits as the division
                     // (400 M random pairs on the host: 0 differences).  A tex that is not an ordinary positive number
                     // takes the division.
-                    const double tex = (HOISTX && NCOMP > 0) ? cx_tex[c] : Dk[c * 4], rtex = (HOISTX && NCOMP > 0) ? cx_rtex[c] : Dk[c * 4 + 3];
+                    const double tex = (HOISTX && NCOMP > 0) ? cx_tex[c] : Dk[LEAD4(c)], rtex = (HOISTX && NCOMP > 0) ? cx_rtex[c] : Dk[LEAD4(c) + 3];
                     double x;
                     if (tex > 1e-100 && tex < 1e100) {
                         const double q = T0 * rtex;
@@ -1462,7 +1497,7 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
                     window_of(c, lane, lo, hi);
                     const unsigned long long mask = __builtin_amdgcn_ballot_w64((lo < r0 + 64) & (hi > r0) & (hi > lo));
                     if (mask == 0ull) continue;
-                    const int dko = 4 * ncomp + (c * nspec + s) * DREC_CS;
+                    const int dko = DLEAD + (c * nspec + s) * DREC_CS;
                     component(c, mask, Dk[dko + DK_KIND], tb_class(Dk[dko + DK_KIND]), Dk[dko + DK_A0X], Dk[dko + DK_B0X]);
                 }
             }
@@ -1573,6 +1608,8 @@ __device__ __forceinline__ void lnl_body(const SpecDev &S, const int *__restrict
         else part[unit] = S.totsq[p_ix * nspec + s] + tot;
     }
 }
+#undef LEAD4
+#undef DLEAD
 
 // WIDE (fast mode only): the spectra set holds a transition with more than 26 lines (N2H+)
 template <int MODE, bool WRITE_SPEC, bool WIDE, int NCOMP>
@@ -1628,6 +1665,9 @@ lnl_kernel_kind(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
 //           baseline order (none: a zeroed record) and every Tc, a spectrum with Tc = 0 beside one with a continuum included
 //   robust  a robust likelihood (nfa_specset_set_robust, 4.18): the weighted form with ROBUST; one instance for every nu, a
 //           Gaussian spectrum (nu = 0) beside robust ones included
+//   texs    an excitation temperature per (component, spectrum), the excitation-grid model's (nfa_specset_create_grid, 4.23): the
+//           baseline form with TEXS over the larger item records; one instance for every baseline order (none: a zeroed
+//           record).  The FILL instances exist and are never launched: no creator makes a filled set of that model
 // The same waves, LDS and workgroups as that form's kernels.  No unrolled component loop, no queue, no w8, no fused form.
 template <int MODE, bool WRITE_SPEC, bool WIDE, bool FILL, bool LAYER, int SIDE>      // SIDE: an LnlSide, as the number a profile shows
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80)))
@@ -1659,7 +1699,7 @@ lnl_kernel_side(SpecDev S, BatchGroup grp, const double *__restrict__ D, double 
 #define NFA_QUEUE_WORDS  (2 * NFA_QUEUE_STRIDE)
 struct QueueArgs { SpecDev S; BatchGroup grp; const double *D; double *part; double *spec_out; long B; LnlGeom G; const double *g_tabs; };
 // (the argument segment places every argument at the next multiple of its alignment: 8 for all of these, so the struct's
-// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1040, 1312, 1320, 1328, 1336, 1344, 1384)
+// layout is the segment's -- .offset of the kernel's .args in the code object: 0, 1048, 1320, 1328, 1336, 1344, 1352, 1392)
 static_assert(sizeof(SpecDev) % 8 == 0 && sizeof(BatchGroup) % 8 == 0 && sizeof(LnlGeom) % 8 == 0 && alignof(SpecDev) == 8 &&
               alignof(BatchGroup) == 8 && alignof(LnlGeom) == 8, "QueueArgs must mirror the kernel argument segment");
 template <bool WRITE_SPEC, int NCOMP>

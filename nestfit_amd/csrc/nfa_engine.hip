@@ -179,6 +179,8 @@ struct nfa_specset {
     LteRec  *d_lte = nullptr;                       // the LTE model's record: SpecDev.lte_rec (null for the other models)
     BandRec *d_band = nullptr;                      // LTE bands: SpecDev.band (null for a set without a banded spectrum)
     MixRec  *d_mix = nullptr;                       // LTE mixes: SpecDev.mix (null for a set of one species)
+    GridRec *d_grid = nullptr;                      // the excitation-grid model's record: SpecDev.grid (null for the other models) ...
+    double  *d_grid_tex = nullptr, *d_grid_ltau = nullptr;     // ... and its tables [n_spec][nt][nn][nc], which the record points at
     int     h_nhf[MAXSPEC] = {};                    // lines of every spectrum
     bool    filled = false;                         // an LTE set with a beam filling factor per component: the last parameter
     bool    layered = false;                        // layered transfer: a component absorbs those behind it (nfa_specset_set_layered)
@@ -324,7 +326,7 @@ static int runner_mode(const nfa_runner *r) { return r->exp_mode >= 0 ? r->exp_m
 // the inputs of the launch plans: the options as they stand now, and a launch of B items of the runner's set as it is now
 static LpKnobs plan_knobs() { return {g_eng.n_cu, g_eng.setup_ti, g_eng.setup_threads, g_eng.setup_sub, g_eng.lnl_queue, g_eng.lnl_queue_wg, g_eng.coalesce, g_eng.ablate}; }
 static LpLaunch plan_launch(const nfa_runner *r, int64_t B, int mode, bool write_spec, bool has_prior, int slot) {
-    return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl_order >= 0 || r->ss->dev.cont != nullptr,
+    return LpLaunch{B, mode, r->cur_group.n, r->cur_group.each, write_spec, has_prior, r->ss->dev.bl_order >= 0 || r->ss->dev.cont != nullptr || r->ss->dev.grid != nullptr,
                     r->ss->dev.chan_w != nullptr, r->d_queue[slot] != nullptr, r->ss->filled, r->ss->layered, r->ss->dev.cal2 != nullptr};
 }
 #ifdef NFA_TEST_HOOKS
@@ -519,6 +521,20 @@ int nfa_specset_create_lines(nfa_specset **out, int n_spec, const int64_t *sizes
                                       n_lines, voff, tau_wts});
 }
 
+// nfa_specset_create_lines with an excitation grid: the declaration is the lines creator's, the grid rides beside it
+int nfa_specset_create_grid(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
+                            const double *rest_freqs, const double *voff, const double *tau_wts,
+                            int nt, const double *tkin, int nn, const double *lnden, int nc, const double *lncd,
+                            const double *tex, const double *ltau,
+                            const double *const *xarr, int64_t n_pix, const double *data, const double *noise,
+                            const double *chan_noise) {
+    SetDecl d{DECL_LINES, out, NFA_MODEL_GRID, n_spec, sizes, xarr, n_pix, data, noise, chan_noise, rest_freqs, nullptr, n_lines, voff, tau_wts};
+    d.grid = true;
+    d.g_nt = nt; d.g_nn = nn; d.g_nc = nc;
+    d.g_tkin = tkin; d.g_lnden = lnden; d.g_lncd = lncd; d.g_tex = tex; d.g_ltau = ltau;
+    return specset_build(out, d);
+}
+
 int nfa_specset_create_lte(nfa_specset **out, int n_spec, const int64_t *sizes, const int32_t *n_lines,
                            const double *rest_freqs, const double *voff, const double *tau_wts,
                            const double *e_up, const double *g_up, const double *a_ul,
@@ -582,6 +598,7 @@ int nfa_specset_destroy(nfa_specset *ss) {
     (void)hipFree(ss->d_t0tbg); (void)hipFree(ss->d_rowsq); (void)hipFree(ss->d_totsq); (void)hipFree(ss->d_lines);
     for (const SetBuf &b : SET_BUFS) (void)hipFree(ss->*b.p);
     (void)hipFree(ss->d_lte); (void)hipFree(ss->d_band); (void)hipFree(ss->d_mix);
+    (void)hipFree(ss->d_grid); (void)hipFree(ss->d_grid_tex); (void)hipFree(ss->d_grid_ltau);
     delete ss;
     return NFA_OK;
 }
@@ -769,6 +786,16 @@ static int specset_upload(nfa_specset *ss, const SetDecl &decl, const SetPlan &p
     if (p.kind >= SET_LTE) { rc = upload(&ss->d_lte, &p.lte, sizeof p.lte); if (rc) return rc; d.lte_rec = ss->d_lte; }
     if (p.kind >= SET_BANDS) { rc = upload(&ss->d_band, &p.band, sizeof p.band); if (rc) return rc; d.band = ss->d_band; }
     if (p.kind == SET_MIX) { rc = upload(&ss->d_mix, &p.mix, sizeof p.mix); if (rc) return rc; d.mix = ss->d_mix; }
+    if (p.grid) {                 // the tables, then the record that points at them; the set's kernels are the baseline form's
+        const size_t bytes = sizeof(double) * (size_t)p.grid_rec.nt * p.grid_rec.nn * p.grid_rec.nc * p.n_spec;
+        rc = upload(&ss->d_grid_tex, decl.g_tex, bytes); if (rc) return rc;
+        rc = upload(&ss->d_grid_ltau, decl.g_ltau, bytes); if (rc) return rc;
+        GridRec rec = p.grid_rec;
+        rec.tex = ss->d_grid_tex; rec.ltau = ss->d_grid_ltau;
+        rc = upload(&ss->d_grid, &rec, sizeof rec); if (rc) return rc;
+        d.grid = ss->d_grid;
+        ss->opt.o.grid_on = true;
+    }
     return specset_realise(ss, ss->opt, 0, p.n_pix, set_stages_create(set_layout(ss->opt.o, p.chan_noise)), nullptr, decl.chan_noise);
 }
 static int specset_build(nfa_specset **out, const SetDecl &decl) {
@@ -815,6 +842,14 @@ int nfa_specset_set_data(nfa_specset *ss, int64_t pix, const double *data) {
 
 // What the set has, as set_refusal (nfa_set_rules.h) asks: which of the likelihoods a setter may not put beside its own
 static unsigned specset_has(const nfa_specset *ss) { return set_has(ss->opt.o, ss->masked); }
+// A set of the excitation-grid model runs a side of its own (LNL_SIDE_TEXS) and a side is exclusive: the setters of the other
+// sides' options, and of a calibration, refuse it by its model, as nfa_specset_set_layered refuses the Gaussian model
+// (`what`: "nuisance templates", ...).  nfa_set_rules.h stays the table of option pairs.
+static bool grid_refuses(const nfa_specset *ss, const char *what) {
+    if (ss->dev.model != NFA_MODEL_GRID) return false;
+    fail(NFA_ERR_ARG, std::string("a set of the excitation-grid model takes no ") + what);
+    return true;
+}
 
 // A setter: null check, its value check (`any`: the request switches the option on), the table's refusal, a copy of the
 // record with its one field edited, specset_change.
@@ -842,6 +877,7 @@ int nfa_specset_set_calibration(nfa_specset *ss, const double *cal) {
             return fail(NFA_ERR_ARG, "a calibration uncertainty is a finite fraction in [0, 1] per spectrum");
         any = any || cal[s] > 0.0;
     }
+    if (any && grid_refuses(ss, "calibration uncertainty")) return NFA_ERR_ARG;
     if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_CALIB) : nullptr) return fail(NFA_ERR_ARG, why);
     SetRecord next = ss->opt;                                 // (null, or all zeros: the set's former kernels and bits)
     set_field(next.o.cal, sizeof next.o.cal, &next.o.cal_on, any, cal, ss->dev.n_spec);
@@ -889,6 +925,7 @@ int nfa_specset_set_correlation(nfa_specset *ss, const double *rho) {
     if (any) {
         for (int s = 0; s < d.n_spec; ++s)
             if (d.size[s] < 4) return fail(NFA_ERR_ARG, "a noise correlation needs spectra of 4 channels and more");
+        if (grid_refuses(ss, "noise correlation")) return NFA_ERR_ARG;
         if (const char *why = set_refusal(specset_has(ss), SET_TAKES_CORR)) return fail(NFA_ERR_ARG, why);
     }
     SetRecord next = ss->opt;         // (null, or all zeros: the set's former kernels and bits, or a response's over white noise)
@@ -920,6 +957,7 @@ int nfa_specset_set_response(nfa_specset *ss, const double *taps) {
     if (any) {
         for (int s = 0; s < d.n_spec; ++s)
             if (d.size[s] < 4) return fail(NFA_ERR_ARG, "a channel response needs spectra of 4 channels and more");
+        if (grid_refuses(ss, "channel response")) return NFA_ERR_ARG;
         if (const char *why = set_refusal(specset_has(ss), SET_TAKES_RESP)) return fail(NFA_ERR_ARG, why);
     }
     SetRecord next = ss->opt;         // (null, or the identity everywhere: the correlated set's kernels and bits, or the set's former ones)
@@ -956,6 +994,7 @@ int nfa_specset_set_templates(nfa_specset *ss, const double *t, const int *n_tmp
                 }
                 if (zero) return fail(NFA_ERR_ARG, "nuisance templates: a template is zero over its whole spectrum");
             }
+        if (grid_refuses(ss, "nuisance templates")) return NFA_ERR_ARG;
         if (const char *why = set_refusal(specset_has(ss), SET_TAKES_TMPL)) return fail(NFA_ERR_ARG, why);
     }
     SetRecord next = ss->opt;
@@ -984,6 +1023,7 @@ int nfa_specset_set_continuum(nfa_specset *ss, const double *tc) {
     if (any) {
         if (ss->dev.model == NFA_MODEL_GAUSSIAN)
             return fail(NFA_ERR_ARG, "the Gaussian model has no optical depth: its components cannot absorb a continuum background");
+        if (grid_refuses(ss, "continuum background")) return NFA_ERR_ARG;
         if (const char *why = set_refusal(specset_has(ss), SET_TAKES_CONT)) return fail(NFA_ERR_ARG, why);
     }
     SetRecord next = ss->opt;
@@ -1006,6 +1046,7 @@ int nfa_specset_set_robust(nfa_specset *ss, const double *nu) {
             return fail(NFA_ERR_ARG, "a robust likelihood takes finite degrees of freedom per spectrum, 0 (Gaussian) or in [1, 1e6]");
         any = any || nu[s] > 0.0;
     }
+    if (any && grid_refuses(ss, "robust likelihood")) return NFA_ERR_ARG;
     if (const char *why = any ? set_refusal(specset_has(ss), SET_TAKES_ROBUST) : nullptr) return fail(NFA_ERR_ARG, why);
     SetRecord next = ss->opt;                                 // (null, or all zeros: the set's former kernels and bits)
     set_field(next.o.rob, sizeof next.o.rob, &next.o.rob_on, any, nu, ss->dev.n_spec);
@@ -1240,7 +1281,7 @@ int nfa_runner_create(nfa_runner **out, nfa_specset *ss, nfa_priors *priors, int
     if (!out || !ss) return fail(NFA_ERR_ARG, "null argument");
     if (ncomp < 1 || ncomp > MAXCOMP) return fail(NFA_ERR_ARG, "ncomp must be in 1..10");   // ammonia.pyx:401
     if (priors && priors->prog.n_param != ss->dev.npar)
-        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+, hyperfine and LTE, 3 Gaussian, 3 + the species of an LTE mix, one more with a filling factor)");
+        return fail(NFA_ERR_ARG, "prior program must cover the model's parameters (6 NH3, 4 N2H+, hyperfine and LTE, 3 Gaussian, 3 + the species of an LTE mix, one more with a filling factor, 5 excitation grid)");
     int rc = engine_init(); if (rc) return rc;
     nfa_runner *r = new nfa_runner();
     r->ss = ss; r->pr = priors; r->ncomp = ncomp; r->cold = cold ? 1 : 0; r->lte = lte ? 1 : 0;
@@ -1328,7 +1369,8 @@ static SpecDev runner_specdev(const nfa_runner *r) {
 // the plan of the fused kernels for a runner's points (S: runner_specdev(r)): what its set is right now, said once
 static FusedPlan runner_fused_plan(const nfa_runner *r, int mode, const SpecDev &S) {
     return plan_fused(r->shape, plan_knobs(), mode, S.bl_order >= 0, S.chan_w != nullptr, S.band != nullptr, r->ss->filled, r->ss->layered,
-                      S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr);
+                      S.cal2 != nullptr, S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr,
+                      S.grid != nullptr);
 }
 
 // A kernel that wants more than 64 KB of dynamic LDS has to be told so -- once per kernel and size, not on every
@@ -1360,7 +1402,9 @@ static int reserve_lane(nfa_runner *r, int slot, int64_t B) {
     (void)hipFree(r->d_D[slot]); (void)hipFree(r->d_part[slot]); (void)hipFree(r->d_band[slot]);
     r->d_D[slot] = nullptr; r->d_part[slot] = nullptr; r->d_band[slot] = nullptr; r->cap_D[slot] = 0;
     const int64_t cap = std::max<int64_t>(B, 4096);
-    HIP_TRY(hipMalloc(&r->d_D[slot], sizeof(double) * cap * drec_size(r->ncomp, n_spec)));
+    // (the record as the plan header counts it, which tests/test_grid_cpu.py holds to the kernels' layout: an excitation-grid
+    // set's is the larger one)
+    HIP_TRY(hipMalloc(&r->d_D[slot], sizeof(double) * cap * lnl_drec_doubles(r->ncomp, n_spec, r->ss->dev.grid != nullptr)));
     if (r->ss->dev.band) HIP_TRY(hipMalloc(&r->d_band[slot], sizeof(double) * cap * r->ncomp * n_spec * NFA_BAND_MAXT));
     HIP_TRY(hipMalloc(&r->d_part[slot], sizeof(double) * cap * n_spec));
     if (!r->d_queue[slot]) {
@@ -1419,6 +1463,19 @@ static int launch_band(nfa_runner *r, int slot, int64_t B) {
     }
     hipLaunchKernelGGL(lte_band_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, r->lanes[slot],
                        (const BandRec *)r->ss->d_band, (const double *)r->d_D[slot], r->d_band[slot], (long)B, r->ncomp, n_spec);
+    HIP_TRY(hipGetLastError());
+    return NFA_OK;
+}
+
+// The excitation-grid model: the records of every (item, component, spectrum) of the B items whose theta the set-up stage
+// has just left in the batches of r->cur_group on this lane (grid_derive_kernel, nfa_setup.h), one launch between the two
+// stages; the fast mode's records where the set-up stage would have written those
+static int launch_grid(nfa_runner *r, int slot, int64_t B, int mode) {
+    const SpecDev S = runner_specdev(r);
+    const int64_t recs = B * r->ncomp * S.n_spec;
+    const auto kern = mode == 2 ? grid_derive_kernel<true> : grid_derive_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, r->lanes[slot], S, r->d_D[slot], r->cur_group,
+                       (long)B, (const double *)g_eng.d_tabs);
     HIP_TRY(hipGetLastError());
     return NFA_OK;
 }
@@ -1495,13 +1552,13 @@ static void count_lnl_launch(LnlKernel kern) {
 static int launch_lnl(nfa_runner *r, int slot, bool want_lnl, double *d_spec, int64_t B, int mode) {
     SpecDev S = runner_specdev(r);
     S.band_tau = r->d_band[slot];                             // (null unless the set is banded)
-    LnlPlan P = plan_lnl(r->shape, plan_knobs(), plan_launch(r, B, mode, d_spec != nullptr, false, slot), S.tmpl != nullptr);
+    LnlPlan P = plan_lnl(r->shape, plan_knobs(), plan_launch(r, B, mode, d_spec != nullptr, false, slot), S.tmpl != nullptr, S.grid != nullptr);
     if (P.error) return fail(NFA_ERR_ARG, P.error);
     if (P.form == LNL_QUEUE) P.G.queue = r->d_queue[slot];
 #ifdef NFA_TEST_HOOKS
     P.G.trace = g_eng.d_trace;
 #endif
-    const LnlSide side = lnl_side_of(S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr);
+    const LnlSide side = lnl_side_of(S.corr_q1 != nullptr, S.resp != nullptr, S.tmpl != nullptr, S.cont != nullptr, S.rob != nullptr, S.grid != nullptr);
     const LnlKernel kern = side != LNL_SIDE_NONE ? lnl_kernel_side_of(side, mode, d_spec != nullptr, P) : lnl_kernel_of(mode, d_spec != nullptr, r->ncomp, P);
     if (!kern) return fail(NFA_ERR_STATE, "no likelihood kernel of the planned form");
 #ifdef NFA_TEST_HOOKS
@@ -1561,6 +1618,7 @@ static int run_group(nfa_runner *r, const BatchGroup &grp, double *d_spec, bool 
     int rc = launch_setup(r, B, has_prior, slot, mode);
     if (rc) return rc;
     if (r->ss->dev.band) { rc = launch_band(r, slot, B); if (rc) return rc; }
+    if (r->ss->dev.grid) { rc = launch_grid(r, slot, B, mode); if (rc) return rc; }
     rc = launch_lnl(r, slot, grp.lnL[0] != nullptr, d_spec, B, mode);
     if (rc) return rc;
     r->n_calls++;

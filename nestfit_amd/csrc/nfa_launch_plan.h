@@ -178,6 +178,12 @@ inline size_t lnl_units_lds(const LpShape &s, bool table, int split, int waves, 
     return sizeof(double) * ((size_t)(table ? SM_TABLE_DOUBLES : 0) + ((size_t)lnl_wave_doubles(s) + part_doubles) * (waves / split));
 }
 
+// doubles of an item's derived record (nfa_device.h: drec_size): a leading block of four per component -- texs, a set of the
+// excitation-grid model: per (component, spectrum) -- and DREC_CS = 16 per (component, spectrum)
+constexpr int LP_DREC_CS = 16;
+constexpr int lnl_drec_doubles(int ncomp, int nspec, bool texs = false) {
+    return 4 * ncomp * (texs ? nspec : 1) + ncomp * nspec * LP_DREC_CS;
+}
 enum LnlForm { LNL_PLAIN, LNL_W8, LNL_QUEUE, LNL_WEIGHTED, LNL_BASELINE };
 // waves per workgroup, its dynamic LDS in bytes, workgroups; error: null, or why there is no plan.  filled, layered,
 // calibrated: the launch's (in the padding behind `wide`).  Which kernel instance a plan names: lnl_instance_exists below.
@@ -187,7 +193,7 @@ struct LnlPlan { LnlForm form; bool wide, filled, layered, calibrated; LnlGeom G
 // (lnl_kernel_kind<..., KIND>, nfa_device.h).  Kind 0 is the plain set: lnl_kernel, lnl_kernel_w8, lnl_kernel_queue.
 // Behind the five kind bits, in the same word, the flags of lnl_body that no kind has: the side family's (LnlSide below).
 enum : unsigned { LNL_K_WEIGHTED = 1, LNL_K_BASELINE = 2, LNL_K_FILL = 4, LNL_K_LAYER = 8, LNL_K_CALIB = 16,
-                  LNL_F_CORR = 32, LNL_F_RESP = 64, LNL_F_TMPL = 128, LNL_F_CONT = 256, LNL_F_ROBUST = 512 };
+                  LNL_F_CORR = 32, LNL_F_RESP = 64, LNL_F_TMPL = 128, LNL_F_CONT = 256, LNL_F_ROBUST = 512, LNL_F_TEXS = 1024 };
 constexpr unsigned LNL_KINDS = 32;      // kinds 0 .. 31: every set of the five bits
 constexpr unsigned lnl_plan_kind(const LnlPlan &P) {
     return (P.form == LNL_WEIGHTED || P.form == LNL_BASELINE ? LNL_K_WEIGHTED : 0u) | (P.form == LNL_BASELINE ? LNL_K_BASELINE : 0u) |
@@ -232,21 +238,24 @@ constexpr bool lnl_inst_round_trip() {
 static_assert(lnl_inst_round_trip(), "lnl_inst_at must invert lnl_inst_index over the whole table");
 
 // The side family, lnl_kernel_side<MODE, WRITE_SPEC, WIDE, FILL, LAYER, SIDE> (nfa_device.h): the kernels of a set with
-// correlated channel noise, a channel response, nuisance templates, a continuum background or a robust likelihood.  They stand
+// correlated channel noise, a channel response, nuisance templates, a continuum background or a robust likelihood, and of a
+// set of the excitation-grid model (an excitation temperature per (component, spectrum): LNL_F_TEXS).  They stand
 // beside the table of kinds, in the general component form only (NCOMP 0), 32 instances per side; a side says which flags
 // of lnl_body its kernels switch on and, through them, under which plan form they run.
-enum LnlSide { LNL_SIDE_NONE, LNL_SIDE_CORR, LNL_SIDE_RESP, LNL_SIDE_TMPL, LNL_SIDE_CONT, LNL_SIDE_ROBUST };
-constexpr int LNL_SIDES = 5, LNL_SIDE_INSTANCES = 32;
+enum LnlSide { LNL_SIDE_NONE, LNL_SIDE_CORR, LNL_SIDE_RESP, LNL_SIDE_TMPL, LNL_SIDE_CONT, LNL_SIDE_ROBUST, LNL_SIDE_TEXS };
+constexpr int LNL_SIDES = 6, LNL_SIDE_INSTANCES = 32;
 constexpr unsigned lnl_side_flags(LnlSide side) {
     return side == LNL_SIDE_CORR ? LNL_K_WEIGHTED | LNL_F_CORR : side == LNL_SIDE_RESP ? LNL_K_WEIGHTED | LNL_F_CORR | LNL_F_RESP :
            side == LNL_SIDE_TMPL ? LNL_K_WEIGHTED | LNL_K_BASELINE | LNL_F_TMPL :
-           side == LNL_SIDE_CONT ? LNL_K_WEIGHTED | LNL_K_BASELINE | LNL_F_CONT : side == LNL_SIDE_ROBUST ? LNL_K_WEIGHTED | LNL_F_ROBUST : 0u;
+           side == LNL_SIDE_CONT ? LNL_K_WEIGHTED | LNL_K_BASELINE | LNL_F_CONT : side == LNL_SIDE_ROBUST ? LNL_K_WEIGHTED | LNL_F_ROBUST :
+           side == LNL_SIDE_TEXS ? LNL_K_WEIGHTED | LNL_K_BASELINE | LNL_F_TEXS : 0u;
 }
 // the plan form a side's kernels run under: the weighted form's waves, LDS and workgroups, or the baseline form's
 constexpr LnlForm lnl_side_form(LnlSide side) { return lnl_kind_form(lnl_side_flags(side)); }
-// the side of a set: a robust likelihood first, then a continuum, templates, a response (which is correlated too), a correlation
-constexpr LnlSide lnl_side_of(bool corr, bool resp, bool tmpl, bool cont, bool rob) {
-    return rob ? LNL_SIDE_ROBUST : cont ? LNL_SIDE_CONT : tmpl ? LNL_SIDE_TMPL : resp ? LNL_SIDE_RESP : corr ? LNL_SIDE_CORR : LNL_SIDE_NONE;
+// the side of a set: an excitation per spectrum first (the model's own side: such a set takes none of the others), then a
+// robust likelihood, a continuum, templates, a response (which is correlated too), a correlation
+constexpr LnlSide lnl_side_of(bool corr, bool resp, bool tmpl, bool cont, bool rob, bool texs = false) {
+    return texs ? LNL_SIDE_TEXS : rob ? LNL_SIDE_ROBUST : cont ? LNL_SIDE_CONT : tmpl ? LNL_SIDE_TMPL : resp ? LNL_SIDE_RESP : corr ? LNL_SIDE_CORR : LNL_SIDE_NONE;
 }
 // An instance of a side and its index: bit 0 wide, 1 spectra out, 2 fast mode, 3 filled, 4 layered
 struct LnlSideInst { int mode; bool write_spec, wide, filled, layered; };
@@ -265,7 +274,10 @@ static_assert(lnl_side_round_trip(), "lnl_side_at must invert lnl_side_index ove
 // Plans the likelihood launch of L.B items (the table of forms in DESIGN 4.2 is tested against this chain).
 // templates: the set has nuisance templates (nfa_specset_set_templates): the baseline form's plan over nine
 // sums per part, for lnl_kernel_side's templates side (beside the table: the plan names no instance of it).
-inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L, bool templates = false) {
+// texs: the set is of the excitation-grid model: the baseline form whatever the set's options, for
+// lnl_kernel_side's excitation side, whose item records are the larger ones (lnl_drec_doubles) -- in global memory, so the
+// plan's LDS is the baseline form's, slot for slot.
+inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L, bool templates = false, bool texs = false) {
     LnlPlan P = {};
     const int64_t units = L.B * s.n_spec;
     if (units * 8 >= (1LL << 28)) { P.error = "batch too large for one launch"; return P; }
@@ -304,7 +316,7 @@ inline LnlPlan plan_lnl(const LpShape &s, const LpKnobs &k, const LpLaunch &L, b
     const bool fills_twice = units >= 2 * ((int64_t)k.n_cu * wg_per_cu) * waves;
     // The form: the first line that applies.
     P.form = LNL_PLAIN;
-    if (L.calibrated || templates) P.form = LNL_BASELINE;      // a calibration uncertainty, templates: the baseline form (whatever the order)
+    if (L.calibrated || templates || texs) P.form = LNL_BASELINE;      // a calibration uncertainty, templates, an excitation per spectrum: the baseline form (whatever the order)
     else if (L.baseline) P.form = LNL_BASELINE;      // every mode, wide, spectra out; such a set is weighted too
     else if (L.weighted) P.form = LNL_WEIGHTED;      // every mode, wide, spectra out: no queue or w8 form of its own (the
                                                      // units give the same bits whatever the form, so none is instantiated)
@@ -401,10 +413,14 @@ struct FusedPlan { const char *refusal, *ring_error; LnlGeom G; int n_blocks, ct
 // set is weighted to its kernels, whose weighted sum would be no likelihood of it)
 inline FusedPlan plan_fused(const LpShape &s, const LpKnobs &k, int mode, bool baseline, bool weighted, bool banded = false,
                             bool filled = false, bool layered = false, bool calibrated = false, bool correlated = false,
-                            bool response = false, bool templates = false, bool continuum = false, bool robust = false) {
+                            bool response = false, bool templates = false, bool continuum = false, bool robust = false,
+                            bool texs = false) {
     FusedPlan P = {};
     P.G = lnl_geom(s, k, 1);
-    if (robust) P.refusal = "the resident kernel has no form for a robust likelihood: use nfa_ring_serve";
+    // texs: a set of the excitation-grid model (nfa_specset_create_grid: the batch kernels only, and refused first of all --
+    // the fused kernels read one excitation temperature per component from a record that has none)
+    if (texs) P.refusal = "the resident kernel has no form for an excitation per spectrum: use nfa_ring_serve";
+    else if (robust) P.refusal = "the resident kernel has no form for a robust likelihood: use nfa_ring_serve";
     else if (response) P.refusal = "the resident kernel has no form for a channel response: use nfa_ring_serve";
     else if (correlated) P.refusal = "the resident kernel has no form for correlated channel noise: use nfa_ring_serve";
     else if (calibrated) P.refusal = "the resident kernel has no form for a calibration uncertainty: use nfa_ring_serve";

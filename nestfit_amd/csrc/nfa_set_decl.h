@@ -16,6 +16,7 @@
 #include "../../include/nestfit_amd.h"   // NFA_MODEL_*, NFA_ERR_ARG
 #include "n2hp_data.h"                   // the shipped tables (and nh3_data.h: NFA_MAX_HF_N, the constants)
 #include "nfa_launch_plan.h"             // MAXSPEC
+#include "nfa_grid_decl.h"               // the excitation-grid model's record and checks (GridRec, grid_fill)
 
 // Transition indices of every model in one index space: 0..8 NH3 (1,1)..(9,9), 9..11 N2H+ 1-0, 2-1, 3-2, 12 the
 // Gaussian model's single "line" (offset 0, weight 1, rest frequency from the spectrum), 13 a spectrum of the
@@ -106,6 +107,11 @@ struct SetDecl {
     const int32_t *n_trans = nullptr;               // from DECL_BANDS on: transitions per spectrum
     int n_species = 1;                              // from DECL_MIX on
     const int32_t *species = nullptr;               // ... per transition
+    // nfa_specset_create_grid: a DECL_LINES declaration with an excitation grid (`grid` says so: the pointers may be null)
+    bool grid = false;
+    int g_nt = 0, g_nn = 0, g_nc = 0;               // nodes of the three axes
+    const double *g_tkin = nullptr, *g_lnden = nullptr, *g_lncd = nullptr;
+    const double *g_tex = nullptr, *g_ltau = nullptr;     // [n_spec][nt * nn * nc]
 };
 
 // What kind of set a declaration makes.  Each kind owns the records of the one before: SET_LTE an LteRec, SET_BANDS a BandRec
@@ -128,6 +134,8 @@ struct SetPlan {
     LteRec  lte;                                    // kind >= SET_LTE
     BandRec band;                                   // kind >= SET_BANDS
     MixRec  mix;                                    // kind == SET_MIX
+    bool    grid = false;                           // the excitation-grid model: a SET_LINES set with ...
+    GridRec grid_rec;                               // ... its axes (the tables' pointers are the engine's to fill)
     std::vector<double> sigma_ref;                  // chan_noise: the smallest finite sigma_c of every (pixel, spectrum)
 };
 
@@ -293,6 +301,7 @@ inline int band_layout(std::string &why, const SetDecl &d, const int32_t *specie
 inline int set_plan(const SetDecl &d, SetPlan &p, std::string &why) {
     p = SetPlan{};
     memset(p.lines, 0, sizeof p.lines); memset(&p.lte, 0, sizeof p.lte); memset(&p.band, 0, sizeof p.band); memset(&p.mix, 0, sizeof p.mix);
+    memset(&p.grid_rec, 0, sizeof p.grid_rec);
     const SetCreator who = d.who;
     const bool chan = who == DECL_CHANNEL_NOISE || (who >= DECL_LINES && d.chan_noise);
     const auto n_spec_range = [&] { return d.n_spec < 1 || d.n_spec > MAXSPEC ? decl_refuse(why, "n_spec must be in 1..16") : NFA_OK; };
@@ -303,7 +312,7 @@ inline int set_plan(const SetDecl &d, SetPlan &p, std::string &why) {
     // 1. the arguments every route of the creator reads
     if (!d.out || !d.sizes || !d.xarr || !d.data || (who == DECL_MODEL && !d.noise) || (who == DECL_CHANNEL_NOISE && !d.chan_noise) ||
         (who >= DECL_LINES && (!d.n_lines || !d.rest_freqs || !d.voff || !d.tau_wts)) || (who >= DECL_BANDS && !d.n_trans) ||
-        (who >= DECL_MIX && (!d.species || !d.n_q)))
+        (who >= DECL_MIX && (!d.species || !d.n_q)) || (d.grid && (!d.g_tkin || !d.g_lnden || !d.g_lncd || !d.g_tex || !d.g_ltau)))
         return decl_refuse(why, "null argument");
     if (who >= DECL_MIX && (d.n_species < 1 || d.n_species > NFA_LTE_MAXSP)) return decl_refuse(why, "n_species must be in 1..4");
     if (who >= DECL_LINES && (d.noise != nullptr) == (d.chan_noise != nullptr))
@@ -346,6 +355,12 @@ inline int set_plan(const SetDecl &d, SetPlan &p, std::string &why) {
             if (rc) return rc;
             l0 += d.n_lines[s];
         }
+    }
+    if (d.grid && who == DECL_LINES) {                          // the grid creator: every transition's weights, then the grid
+        rc = grid_check_weights(why, d.n_spec, d.n_lines, d.tau_wts); if (rc) return rc;
+        rc = grid_fill(why, p.grid_rec, GridDecl{d.g_nt, d.g_nn, d.g_nc, d.g_tkin, d.g_lnden, d.g_lncd, d.g_tex, d.g_ltau}, d.n_spec);
+        if (rc) return rc;
+        p.grid = true;
     }
     if (p.kind >= SET_LTE && (!d.e_up || !d.g_up || !d.a_ul || !d.q_temp || !d.q_val)) return decl_refuse(why, "null argument");
     if (p.kind == SET_LTE) {
@@ -396,12 +411,13 @@ inline int set_plan(const SetDecl &d, SetPlan &p, std::string &why) {
         p.chan_noise = true;
     }
     // 5. the model of the two creators that take one
-    p.model = who >= DECL_LTE ? NFA_MODEL_LTE : who == DECL_LINES ? NFA_MODEL_HYPERFINE : d.model;
+    p.model = who >= DECL_LTE ? NFA_MODEL_LTE : who == DECL_LINES ? (p.grid ? NFA_MODEL_GRID : NFA_MODEL_HYPERFINE) : d.model;
     if (who < DECL_LINES) {
         if (d.model == NFA_MODEL_HYPERFINE) return decl_refuse(why, "the hyperfine model takes its line tables through nfa_specset_create_lines");
         if (d.model == NFA_MODEL_LTE)
             return decl_refuse(why, "unknown model to this creator: the LTE model takes its line tables and partition function "
                                     "through nfa_specset_create_lte");
+        if (d.model == NFA_MODEL_GRID) return decl_refuse(why, grid_model_refusal());
         if (d.model < NFA_MODEL_AMMONIA || d.model > NFA_MODEL_LTE) return decl_refuse(why, "unknown model");
         if (d.model != NFA_MODEL_GAUSSIAN && !d.trans_ids) return decl_refuse(why, "null argument");
         if (d.model == NFA_MODEL_GAUSSIAN && d.n_spec != 1) return decl_refuse(why, "the Gaussian model takes one spectrum");     // gaussian.pyx:57-89
@@ -416,6 +432,7 @@ inline int set_plan(const SetDecl &d, SetPlan &p, std::string &why) {
     p.npar = model == NFA_MODEL_DIAZENYLIUM || tabled ? NFA_N2HP_PARAMS
            : model == NFA_MODEL_GAUSSIAN ? NFA_GAUSS_PARAMS : NFA_N_PARAMS;
     if (p.kind == SET_MIX) p.npar = 3 + d.n_species + (p.filled ? 1 : 0);
+    if (p.grid) p.npar = NFA_GRID_PARAMS;
     int64_t tot = 0, rows = 0, line0 = 0;
     for (int s = 0; s < d.n_spec; ++s) {
         rc = size_range(s); if (rc) return rc;

@@ -23,12 +23,14 @@ struct SetOptions {
     double resp[MAXSPEC][SET_RESP_NT] = {};     // nfa_specset_set_response: the taps
     int    ntmpl[MAXSPEC] = {};                 // nfa_specset_set_templates: templates per spectrum
     double rob[MAXSPEC] = {};                   // nfa_specset_set_robust: degrees of freedom
+    bool   grid_on = false;                     // no request: a set of the excitation-grid model, from its creation on (its
+                                                // kernels are the baseline form's: set_layout)
 };
 // bit for bit: -0.0 is another request than 0.0 (a getter hands it back)
 #define SET_SAME(f) (memcmp(a.f, b.f, sizeof a.f) == 0)
 inline bool set_options_equal(const SetOptions &a, const SetOptions &b) {
     return a.bl_order == b.bl_order && a.cal_on == b.cal_on && a.nunc_on == b.nunc_on && a.corr_on == b.corr_on &&
-           a.resp_on == b.resp_on && a.tmpl_on == b.tmpl_on && a.cont_on == b.cont_on && a.rob_on == b.rob_on &&
+           a.resp_on == b.resp_on && a.tmpl_on == b.tmpl_on && a.cont_on == b.cont_on && a.rob_on == b.rob_on && a.grid_on == b.grid_on &&
            SET_SAME(cal) && SET_SAME(nunc) && SET_SAME(rho) && SET_SAME(resp) && SET_SAME(ntmpl) && SET_SAME(rob);
 }
 // the word set_refusal (nfa_set_rules.h) asks about.  ("correlated" is the coefficients of the correlated kernels, which a
@@ -59,6 +61,7 @@ enum SetChanW { CHAN_W_NONE,      // nothing: a scalar noise and no option that 
 //   baseline order >= 0   ones*, bl                         own
 //   calibration           ones*, bl (zeroed without a baseline), cal2      own
 //   continuum             ones*, bl (likewise), cont        own
+//   (excitation-grid set) ones*, bl (likewise)              own
 //   templates             ones*, tmpl, tp                   own
 //   noise uncertainty     nmarg                             (as it was)
 //   correlation           ones*, q0 q1 q2 corr              Q
@@ -74,7 +77,8 @@ struct SetLayout {
 inline SetLayout set_layout(const SetOptions &o, bool has_channel_noise) {
     SetLayout L;
     const bool q = o.corr_on || o.resp_on;
-    const bool bl = o.bl_order >= 0 || o.cal_on || o.cont_on;             // a calibration or a continuum alone: the zeroed record
+    // a calibration or a continuum alone, a set of the excitation-grid model: the zeroed record
+    const bool bl = o.bl_order >= 0 || o.cal_on || o.cont_on || o.grid_on;
     L.ones = !has_channel_noise && (bl || o.tmpl_on || q);
     if (has_channel_noise || L.ones) L.bufs |= SB_W | SB_WDATA;
     if (bl) L.bufs |= SB_BL;
@@ -129,7 +133,8 @@ inline unsigned set_stages_all(const SetLayout &L) {
     return st;
 }
 // a set's creation (specset_build): the empty record's stages, and a noise per channel becomes the weights
-inline unsigned set_stages_create(const SetLayout &L) { return set_stages_all(L) | (L.has(SB_W) ? ST_FORM_W : 0u); }
+// (a set of the excitation-grid model over a scalar noise is created with the ones: no sigmas to form weights from)
+inline unsigned set_stages_create(const SetLayout &L) { return set_stages_all(L) | (L.has(SB_W) && !L.ones ? ST_FORM_W : 0u); }
 // new data in a pixel (nfa_specset_set_data): Q, the mask, the baseline basis and the templates' stay
 inline unsigned set_stages_data(const SetLayout &L) { return set_stages_all(L) & ST_DATA; }
 // from options a (layout la) to options b (layout lb), which differ in one option; tmpl_changed, cont_changed: the values of

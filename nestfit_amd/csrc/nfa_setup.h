@@ -581,7 +581,10 @@ __device__ __forceinline__ void setup_body(const PriorProg *__restrict__ ppp, co
     }
     if (kb >= 0) wave_lds_sync(); else __syncthreads();
     // ---- phase 3: lanes = (item, component, spectrum)
-    for (int q = t; q < n_pair * nspec && !(ablate & 64); q += step) {
+    // (a set of the excitation-grid model has its records, which are larger ones, from grid_derive_kernel behind this launch:
+    // the stage leaves theta in U and skips the records, here and below)
+    const bool records = S.model != NFA_MODEL_GRID;
+    for (int q = t; q < n_pair * nspec && !(ablate & 64) && records; q += step) {
         const int pair = pair0 + q / nspec, s = q % nspec;
         const int it = pair / ncomp, c = pair - it * ncomp;
         double *Db = D + (b0 + it) * drec;
@@ -591,7 +594,7 @@ __device__ __forceinline__ void setup_body(const PriorProg *__restrict__ ppp, co
     if (kb >= 0) {
         // ---- the velocities are there: into the records (hyperfine.pyx:73), and theta back to U
         __syncthreads();
-        for (int q = tid; q < n_it * ncomp && !(ablate & 64); q += nthr) {
+        for (int q = tid; q < n_it * ncomp && !(ablate & 64) && records; q += nthr) {
             const int it = q / ncomp, c = q - it * ncomp;
             D[(b0 + it) * drec + c * 4 + 2] = th_all[c * 64 + it] / NFA_CKMS;
         }
@@ -835,4 +838,75 @@ lte_fill_kernel(double *__restrict__ D, BatchGroup grp, long B, int ncomp, int n
     const int cg = group_of(grp, b);
     const double *th = grp.U[cg] + (b - (long)cg * grp.each) * (npar * ncomp);
     D[b * drec_size(ncomp, nspec) + 4 * ncomp + (c * nspec + s) * DREC_CS + DK_FILL] = exp10(th[(npar - 1) * ncomp + c]);
+}
+
+// ---------------------------------------------------------------------------
+//  grid_derive_kernel: the excitation-grid model (nfa_specset_create_grid, GridRec).  The set-up stage has
+//  left theta in U and written no record for such a set (setup_body's `records`); this kernel, behind it on the lane, writes
+//  the whole record of every (item, component, spectrum), the larger one (drec_size's texs), from the batch's theta, read as
+//  lte_fill_kernel reads it.  Parameters of a component, parameter-major: voff, tkin, lnden, lncol, sigm.
+//      x = (tkin, lnden, lncol - log10(sqrt(8 ln 2) sigm))             the third: log10 of N per unit FWHM
+//      per axis: k = #{ i in 1..n-2 : x >= a_i }  (derive_lte_lane's scan: compares against uniform loads),
+//                f = clamp((x - a_k) / (a_{k+1} - a_k), 0, 1);  one node: k = 0, f = 0
+//      tex = tex_s(x), tau_main = 10^ltau_s(x): trilinear over the eight corners, every step v0 + f (v1 - v0), lncd
+//      innermost, then lnden, then tkin -- sixteen gathers from tables that lie in L2, seven steps per table, one exp10
+//  Outside the grid the edge value holds (f clamped, an infinite coordinate included): nothing is extrapolated.  A NaN
+//  coordinate leaves f, and so tex, NaN (neither compare of the clamp holds) unless its axis has one node (f = 0); a tkin,
+//  lnden or lncol that is not finite, or a sigm that is not an ordinary positive number, gives a NaN tau_main (the LTE
+//  model's rule).  No model has a reference whose log10 round trip would be
+//  to mirror: 10^ltau by exp10 in every mode.  1 / tex is the division's correctly rounded reciprocal, which the exact
+//  modes' division-free x = T0 / tex relies on (lnl_body).  FAST: write_y_model's.  One lane per (item, component, spectrum).
+#define NFA_GRID_FWHM 2.3548200450309493      // sqrt(8 ln 2)
+__device__ __forceinline__ int grid_cell(const double *__restrict__ a, int n, double x, double &f) {
+    int k = 0;
+    for (int i = 1; i < n - 1; ++i) k += x >= a[i] ? 1 : 0;
+    f = 0.0;
+    if (n > 1) {
+        const double t = (x - a[k]) / (a[k + 1] - a[k]);
+        f = t < 0.0 ? 0.0 : t > 1.0 ? 1.0 : t;                    // (NaN stays NaN)
+    }
+    return k;
+}
+template <bool FAST>
+__global__ void __launch_bounds__(256)
+grid_derive_kernel(SpecDev S, double *__restrict__ D, BatchGroup grp, long B, const double *__restrict__ g_tabs) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int ncomp = S.ncomp, nspec = S.n_spec;
+    if (i >= B * ncomp * nspec) return;
+    const int s = (int)(i % nspec);
+    const long bc = i / nspec;
+    const int c = (int)(bc % ncomp);
+    const long b = bc / ncomp;
+    const int cg = group_of(grp, b);
+    const double *th = grp.U[cg] + (b - (long)cg * grp.each) * (NFA_GRID_PARAMS * ncomp);
+    const double voff = th[c], tkin = th[ncomp + c], lnden = th[2 * ncomp + c], lncol = th[3 * ncomp + c], sigm = th[4 * ncomp + c];
+    const GridRec &G = *S.grid;
+    const int nt = G.nt, nn = G.nn, nc = G.nc;
+    double ft, fn, fc;
+    const int kt = grid_cell(G.tkin, nt, tkin, ft);
+    const int kn = grid_cell(G.lnden, nn, lnden, fn);
+    const int kc = grid_cell(G.lncd, nc, lncol - log10(NFA_GRID_FWHM * sigm), fc);
+    const int kt1 = nt > 1 ? kt + 1 : kt, kn1 = nn > 1 ? kn + 1 : kn, kc1 = nc > 1 ? kc + 1 : kc;     // one node: the node itself
+    const size_t cell0 = (size_t)s * nt * nn * nc;
+    const size_t r00 = cell0 + ((size_t)kt * nn + kn) * nc, r01 = cell0 + ((size_t)kt * nn + kn1) * nc;
+    const size_t r10 = cell0 + ((size_t)kt1 * nn + kn) * nc, r11 = cell0 + ((size_t)kt1 * nn + kn1) * nc;
+    auto trilinear = [&](const double *__restrict__ T) {
+        const double a00 = T[r00 + kc], b00 = T[r00 + kc1], a01 = T[r01 + kc], b01 = T[r01 + kc1];
+        const double a10 = T[r10 + kc], b10 = T[r10 + kc1], a11 = T[r11 + kc], b11 = T[r11 + kc1];
+        const double v00 = a00 + fc * (b00 - a00), v01 = a01 + fc * (b01 - a01);
+        const double v10 = a10 + fc * (b10 - a10), v11 = a11 + fc * (b11 - a11);
+        const double v0 = v00 + fn * (v01 - v00), v1 = v10 + fn * (v11 - v10);
+        return v0 + ft * (v1 - v0);
+    };
+    const double tex = trilinear(G.tex), ltau = trilinear(G.ltau);
+    const bool ordinary = fabs(tkin) < INFINITY && fabs(lnden) < INFINITY && fabs(lncol) < INFINITY && sigm > 0.0 && sigm < INFINITY;
+    double *Db = D + b * drec_size(ncomp, nspec, true);
+    double *d = Db + (c * nspec + s) * 4;
+    d[0] = tex;
+    d[1] = sigm / NFA_CKMS;                                       // hyperfine.pyx:72
+    d[2] = voff / NFA_CKMS;                                       // hyperfine.pyx:73
+    d[3] = 1.0 / tex;
+    double *dk = Db + drec_lead(ncomp, nspec, true) + (c * nspec + s) * DREC_CS;
+    dk[DK_TMAIN] = ordinary ? exp10(ltau) : NAN;
+    write_y_model<FAST>(dk, S, s, tex, g_tabs);
 }

@@ -76,7 +76,9 @@ class CubeRunner(RunnerSurface):
         transitions, per spectrum, all of one `Molecule`; or, an LTE mix, `lines` = an `LteLines`, `LteBand` or `LteBlend` per
         spectrum of the ordered `Molecule`s `species` -- without `species`, lines of several molecules take them in the order of
         their first appearance).  An LTE mix has 3 + len(species) parameters per component; fill: and a beam filling factor
-        as one more, the last (`LteMix(species, fill=True)`; one species included).  options: the likelihood options above."""
+        as one more, the last (`LteMix(species, fill=True)`; one species included).  5 excitation grid (then `lines` = one
+        `GridLines` per spectrum, all on one `ExcitationGrid`; five parameters per component).  options: the likelihood options
+        above."""
         assert ncomp > 0
         sizes = [np.size(x) for x in xarrs]
         masked = np.shape(noise)[-1] == sum(sizes) and not np.all(np.isfinite(noise))

@@ -585,7 +585,7 @@ class CubeStack:
                                     for dc in self.cubes], axis=1)
         else:
             noise = np.stack([dc.noise_map.values_at(lon, lat) for dc in self.cubes], axis=1)
-        if model in (3, 4):                                          # the hyperfine and LTE models: the cubes' line tables
+        if model in (3, 4, 5):                                       # the hyperfine, LTE and excitation-grid models: the cubes' line tables
             runner_kwargs = dict(runner_kwargs, lines=[getattr(dc, 'lines', None) for dc in self.cubes])
         maps = self.continuum_maps()
         if maps is not None:                                         # the cubes' continuum maps: [n_pix, n_spec]

@@ -17,7 +17,7 @@ from ._options import check_options
 from .cube import get_multiproc_indices
 from .store import HdfStore, StoreFile
 
-_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4, 'lte_mix': 4}
+_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4, 'lte_mix': 4, 'grid': 5}
 
 
 class _RunInfo:

@@ -16,7 +16,7 @@ runner gives them).
 """
 import numpy as np
 
-_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4, 'lte_mix': 4}
+_MODEL_ID = {'ammonia': 0, 'diazenylium': 1, 'gaussian': 2, 'hyperfine': 3, 'lte': 4, 'lte_mix': 4, 'grid': 5}
 N_PDF_BINS = 200                 # edges when `aggregate_run_pdfs` makes its own bins (main.py:905-917)
 PDF_FLOOR = 1e-32                # zero-probability bins before the logarithm (main.py:980)
 PREDICT_ROWS = 4096              # (pixel, component) rows per device batch
@@ -379,7 +379,7 @@ def _device_runner(store, stack, ncomp=1, layered=False):
     extra = {}
     if model_id == 2:                                    # the Gaussian model has no transition table to take them from
         extra['rest_freqs'] = [float(dc.full_header.get('RESTFRQ', dc.full_header.get('RESTFREQ'))) for dc in stack.cubes]
-    if model_id in (3, 4):                               # the caller's line tables: the stack's, which must be the store's
+    if model_id in (3, 4, 5):                            # the caller's line tables (model 5: with their grid tables): the stack's, which must be the store's
         extra['lines'] = check_model_lines(store, stack)
         if store.read_model_species():                   # an LTE mix: the species in the order of the fit
             extra['species'] = store.read_model_species()
@@ -661,7 +661,7 @@ def postprocess_run(store, stack, runner=None, par_bins=None, evid_kernel=None, 
                     evid_weight=True, predict_backend=None, posterior_profiles=False):
     """All steps in the reference's order (main.py:1240-1276).  posterior_profiles: then `generate_posterior_profiles`, the
     posterior-mean model cubes and the error bars of the intensities (one model evaluation per posterior sample)."""
-    if store.hdf.attrs.get('model_name') in ('hyperfine', 'lte', 'lte_mix'):     # before any product is written
+    if store.hdf.attrs.get('model_name') in ('hyperfine', 'lte', 'lte_mix', 'grid'):     # before any product is written
         check_model_lines(store, stack)
         check_model_fill(store, runner)
     check_model_layered(store, runner)

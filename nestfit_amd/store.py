@@ -278,6 +278,7 @@ FILE_SUFFIXES = {'hdf5': '.hdf', 'npz': '.npz'}       # '.hdf' is the reference'
 PRODUCTS_GROUP = '/products'
 MODEL_LINES_GROUP = '/model_lines'
 MODEL_PARTITION_GROUP = '/model_partition'
+MODEL_GRID_GROUP = '/model_grid'
 
 # root attribute of the table file  <-  attribute of the CubeFitter          (store_spec.rst:60-63)
 FITTER_ATTRS = (
@@ -555,12 +556,24 @@ class HdfStore:
         tables = [getattr(dc, 'lines', None) for dc in stack.cubes]
         if all(t is None for t in tables):
             return
-        for old in (MODEL_LINES_GROUP, MODEL_PARTITION_GROUP):
+        for old in (MODEL_LINES_GROUP, MODEL_PARTITION_GROUP, MODEL_GRID_GROUP):
             if old in self.hdf:
                 del self.hdf[old]
         if any(t is None for t in tables):
             raise ValueError('either every cube of a stack has a LineTable or none has')
         molecule = None
+        if any(hasattr(t, 'grid') for t in tables):
+            # the excitation-grid model: the lines as the hyperfine model's below, and /model_grid -- the axes all cubes share
+            # (datasets `tkin`, `lnden`, `lncd`, attribute `name`) and every cube's tables, datasets `tex<k>` and `ltau<k>`
+            from .excitation import check_one_grid
+            grid = check_one_grid(tables)
+            group = self.hdf.require_group(MODEL_GRID_GROUP)
+            group.attrs.update(name='' if grid.name is None else grid.name)
+            for key in ('tkin', 'lnden', 'lncd'):
+                group.create_dataset(key, data=np.array(getattr(grid, key)))
+            for k, t in enumerate(tables):
+                group.create_dataset(f'tex{k}', data=np.array(t.tex))
+                group.create_dataset(f'ltau{k}', data=np.array(t.ltau))
         if species is not None and (len(species) > 1 or fill or any(type(t).__name__ == 'LteBlend' for t in tables)):
             from .lte import check_mix_lines, transitions_of
             species = tuple(species)
@@ -653,6 +666,17 @@ class HdfStore:
             if molecule is not None:
                 return molecule.transition(g.attrs['nu'], g.attrs['e_up'], g.attrs['g_up'], g.attrs['a_ul'], voff, tau_wts, name=name)
             return LineTable(g.attrs['nu'], voff, tau_wts, name=name)
+        if MODEL_GRID_GROUP in self.hdf:                             # the excitation-grid model: `GridLines` of the stored grid
+            from .excitation import ExcitationGrid
+            gg = self.hdf[MODEL_GRID_GROUP]
+            grid = ExcitationGrid(*(np.asarray(gg[key][...]) for key in ('tkin', 'lnden', 'lncd')), name=gg.attrs.get('name') or None)
+            out = []
+            for k in range(len(list(top))):
+                g = top[f'spec{k}']
+                out.append(grid.transition(g.attrs['nu'], np.asarray(gg[f'tex{k}'][...]), np.asarray(gg[f'ltau{k}'][...]),
+                                           voff=np.asarray(g['voff'][...]), tau_wts=np.asarray(g['tau_wts'][...]),
+                                           name=g.attrs.get('name') or None))
+            return out
         out = []
         for k in range(len(list(top))):
             g = top[f'spec{k}']
