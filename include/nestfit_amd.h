@@ -845,6 +845,60 @@ int nfa_sampler_dead(nfa_sampler *s, int64_t p, int64_t n, double *theta, double
 int nfa_sampler_dead_packed(nfa_sampler *s, const int64_t *offsets, double *theta, double *lnL, double *lnw);
 int nfa_sampler_live(nfa_sampler *s, double *theta, double *lnL);
 
+/* ---- ensemble MCMC on the device: posteriors at a fixed component count -------------
+ * The affine-invariant stretch move (Goodman & Weare 2010) of n_pix pixels in lock-step, in the unit cube, where the prior
+ * is flat by construction: the target is L(theta(u)) on (0, 1)^D under every prior kind, model and likelihood option.
+ *
+ * Setting.  pix[n_pix] = cube pixel of each (NULL: all pixel 0, a one-pixel runner).  Each pixel has W = n_walkers walkers, W
+ * even, W / 2 >= D + 1, W <= NFA_ENS_MAX_WALKERS, in the D sampled unit-cube slots (free_mask[ndim] as in nfa_sampler_create;
+ * the other slots stay at u = 0.5).  A walker holds u[D], theta[ndim] (what the likelihood batch leaves in its row) and lnL;
+ * nfa_ensemble_run turns a lnL that is not finite into log_zero.
+ * One step is two half-steps, h = 0 then h = 1; in half-step h the walkers k of [h W/2, (h+1) W/2) move against the other half
+ * as it stands.  For walker k in step s (from 1 in every nfa_ensemble_run call) of the pixel with cube index p, with
+ * stream = ns_stream(seed, p, NFA_ENS_TAG + 2 s + h) and r_i = ns_uniform_of(stream, 3 k + i), the nested sampler's generator:
+ *     partner   j = the other half's first walker + min(floor(r_0 W/2), W/2 - 1)
+ *     stretch   z = ((a - 1) r_1 + 1)^2 / a                       (1 < a <= 16)
+ *     proposal  y_d = u_j,d + z (u_k,d - u_j,d) for every sampled d  (f64, plain products and sums in that association)
+ *     outside   any y_d not in (0, 1): rejected whatever its likelihood; its batch row carries the walker's own u, so every
+ *               half-step evaluates the same n_pix W/2 rows and nothing between the launches of a run waits for the host
+ *     accept    iff inside, lnL_y finite and log(r_2) < (D - 1) log(z) + (lnL_y - lnL_k), in that order: the walker takes y,
+ *               the row's theta and its lnL.
+ * Every lnL is bitwise what nfa_runner_loglike_batch returns for that (pixel, u).  Because the cube pixel is in the stream, a
+ * pixel's run does not depend on the pixels it travels with.  Counters per pixel, of the last run: accepted, outside,
+ * evaluated (W/2 per half-step, outside rows included: what was launched).
+ * The state after step s is kept iff s > n_burn and (s - n_burn) % thin == 0; n_keep = (n_steps - n_burn) / thin; layout
+ * chain_theta[n_pix][n_keep][W][ndim], chain_lnL[n_pix][n_keep][W], on the device until fetched.  After every step
+ * trace[n_pix][n_steps][D + 1] holds the mean over the walkers of every sampled u and of lnL (lane l of a wave adds walkers
+ * l, l + 64, ... in order, then a butterfly over the lanes: the same arguments give the same bits).
+ *
+ * nfa_ensemble_create evaluates the start rows u0 once (NFA_ERR_ARG: a u0 outside (0, 1) at a sampled slot, W odd, W / 2 <
+ * D + 1, a pixel out of range).  nfa_ensemble_run may be called again and continues from the state; it numbers its steps from
+ * 1, so a continuation needs another seed (20 steps are not two runs of 10 with one seed), and it replaces chain, trace and
+ * counters.  NFA_ERR_ARG: a outside (1, 16], thin < 1, n_burn >= n_steps, n_keep < 1.  nfa_ensemble_state returns u as
+ * [n_pix][W][ndim], 0.5 in the slots that are not sampled: a u0.  nfa_ensemble_summary reduces the chain on the device, per
+ * parameter of theta over the N = n_keep W kept samples of a pixel: summary[n_pix][ndim][2] = mean and standard deviation
+ * (divisor N) as moments of the differences from the pixel's best row, best[n_pix][ndim + 1] = theta and lnL of the row of
+ * largest lnL (the first in (keep, walker) order on ties), quant[n_pix][ndim][n_levels] = s[i] + (s[i+1] - s[i]) g of the
+ * sorted samples with h = (N - 1) q, i = floor(h), g = h - i (NFA_ERR_ARG: more than NFA_ENS_MAX_Q levels, a level outside
+ * [0, 1], N > NFA_ENS_MAX_SORT with n_levels > 0; NFA_ERR_STATE before the first run).  nfa_ensemble_bytes: the device
+ * bytes of an ensemble and its run (a caller cuts a cube into groups of pixels with it).  All buffers belong to the
+ * nfa_ensemble and go with it; it uses its runner, which must outlive it, one call at a time. */
+#define NFA_ENS_MAX_WALKERS 512
+#define NFA_ENS_MAX_Q       8
+#define NFA_ENS_MAX_SORT    8192
+typedef struct nfa_ensemble nfa_ensemble;
+int nfa_ensemble_create(nfa_ensemble **out, nfa_runner *r, const int32_t *pix, int64_t n_pix, int n_walkers,
+                        const int32_t *free_mask /* [ndim] or NULL */, const double *u0 /* [n_pix][n_walkers][ndim], in (0,1) */);
+int nfa_ensemble_destroy(nfa_ensemble *e);
+int nfa_ensemble_run(nfa_ensemble *e, int64_t n_steps, int64_t n_burn, int64_t thin, double a, int64_t seed, double log_zero);
+int nfa_ensemble_counts(nfa_ensemble *e, int64_t *accepted, int64_t *outside, int64_t *evaluated);   /* [n_pix] each */
+int nfa_ensemble_state(nfa_ensemble *e, double *u, double *theta, double *lnL);                        /* the walkers as they stand */
+int nfa_ensemble_trace(nfa_ensemble *e, double *trace);
+int nfa_ensemble_chain(nfa_ensemble *e, double *theta, double *lnL);                                   /* either may be NULL */
+int nfa_ensemble_chain_dev(nfa_ensemble *e, const double **d_theta, const double **d_lnL, int64_t *n_keep);
+int nfa_ensemble_summary(nfa_ensemble *e, const double *levels, int n_levels, double *summary, double *best, double *quant);
+int64_t nfa_ensemble_bytes(int64_t n_pix, int n_walkers, int ndim, int n_sampled, int64_t n_steps, int64_t n_keep);
+
 /* ---- the exchange step of a sharded cube fit ---------------------
  * The reference stripes pixels over processes, (lon_ix[i::nproc], lat_ix[i::nproc])
  * (nestfit/main.py:565-571), and exchanges nothing while sampling; its processes meet through chunk

@@ -11,7 +11,7 @@ from .ammonia import AmmoniaRunner, AmmoniaSpectrum, amm_predict
 from .diazenylium import DiazenyliumRunner, DiazenyliumSpectrum, nnhp_predict
 from .gaussian import GaussianRunner, gauss_predict
 from ._model import HANNING, HANNING_RESPONSE, ar1, check_robust, correlation_of_response, ripple, robust_lnl, smoothed
-from . import ammonia, diazenylium, excitation, gaussian, hyperfine, lsq, lte
+from . import ammonia, diazenylium, ensemble, excitation, gaussian, hyperfine, lsq, lte
 from .excitation import ExcitationGrid, GridLines, GridRunner, GridSpectrum, grid_predict
 from .hyperfine import HyperfineRunner, LineTable
 from .lte import LteBand, LteBlend, LteLines, LteMix, LteRunner, LteSpectrum, Molecule, lte_predict
@@ -37,7 +37,7 @@ __all__ = [
     'CenSepPrior', 'ResolvedCenSepPrior', 'ResolvedPlacementPrior', 'PriorTransformer',
     'AmmoniaSpectrum', 'AmmoniaRunner', 'amm_predict', 'get_irdc_priors', 'get_synth_priors',
     'DiazenyliumSpectrum', 'DiazenyliumRunner', 'nnhp_predict', 'GaussianRunner', 'gauss_predict',
-    'MODELS', 'hyperfine', 'LineTable', 'HyperfineRunner', 'model_module', 'lsq',
+    'MODELS', 'hyperfine', 'LineTable', 'HyperfineRunner', 'model_module', 'lsq', 'ensemble',
     'lte', 'Molecule', 'LteLines', 'LteBand', 'LteSpectrum', 'LteRunner', 'lte_predict', 'LteBlend', 'LteMix',
     'excitation', 'ExcitationGrid', 'GridLines', 'GridSpectrum', 'GridRunner', 'grid_predict',
 ]

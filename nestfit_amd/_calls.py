@@ -43,6 +43,13 @@ def out_array(out, shape, what):
     return out
 
 
+def _sample_posterior(runner, pix, **kw):
+    """`ensemble.sample_pixels` of a runner's pixels (pix: None for the pixel of a one-pixel runner): the ensemble sampler's
+    arguments are checked once, by the engine."""
+    from .ensemble import sample_pixels
+    return sample_pixels(runner, pix, **kw)
+
+
 def _row_statistics(handle, pix, theta, n_spec):
     """nfa_runner_row_statistics on checked arrays (pix: int32[B] or None)."""
     B = theta.shape[0]

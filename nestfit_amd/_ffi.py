@@ -153,7 +153,17 @@ SIGNATURES = {
     'nfa_sampler_dead': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp]),
     'nfa_sampler_dead_packed': (C.c_int, [C.c_void_p, _lp, _dp, _dp, _dp]),
     'nfa_sampler_live': (C.c_int, [C.c_void_p, _dp, _dp]),
-    'nfa_comm_unique_id': (C.c_int, [C.POINTER(C.c_ubyte)]),
+    'nfa_ensemble_create': (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, _ip, C.c_int64, C.c_int, _ip, _dp]),
+    'nfa_ensemble_destroy': (C.c_int, [C.c_void_p]),
+    'nfa_ensemble_run': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_double]),
+    'nfa_ensemble_counts': (C.c_int, [C.c_void_p, _lp, _lp, _lp]),
+    'nfa_ensemble_state': (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    'nfa_ensemble_trace': (C.c_int, [C.c_void_p, _dp]),
+    'nfa_ensemble_chain': (C.c_int, [C.c_void_p, _dp, _dp]),
+    'nfa_ensemble_chain_dev': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _lp]),
+    'nfa_ensemble_summary': (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, _dp]),
+    'nfa_ensemble_bytes': (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    'nfa_comm_unique_id':(C.c_int, [C.POINTER(C.c_ubyte)]),
     'nfa_comm_create': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.c_int, C.c_int]),
     'nfa_comm_destroy': (C.c_int, [C.c_void_p]),
     'nfa_comm_rank': (C.c_int, [C.c_void_p]),

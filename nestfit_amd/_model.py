@@ -931,6 +931,11 @@ class EngineRunner(RunnerSurface, Runner):
         return _calls._normal_equations(self._run.handle, None, _calls.parameter_rows(self, theta), None, None, None, None, False,
                                         want_grad=False).chi2
 
+    def sample_posterior(self, **kw):
+        """The posterior of the runner's pixel at its component count by ensemble MCMC on the device: an `EnsembleResult` of
+        one row (`nestfit_amd.ensemble.sample_pixels`' keywords)."""
+        return _calls._sample_posterior(self, None, **kw)
+
 
 def par_names(short, ncomp=None):
     if ncomp is not None:

@@ -2327,6 +2327,7 @@ int nfa_event_elapsed_ms(void *start, void *stop, float *ms) {
 #include "nfa_ring.h"
 #include "nfa_ring_serve.h"
 #include "nfa_sampler.h"
+#include "nfa_ensemble.h"
 #include "nfa_comm.h"
 #ifdef NFA_TEST_HOOKS
 #include "nfa_testhooks.h"      // libnestfit_amd_test.so only

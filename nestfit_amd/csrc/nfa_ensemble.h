@@ -1,0 +1,469 @@
+// nfa_ensemble.h -- the kernels behind nfa_ensemble_* (gfx950, wave64): an affine-invariant ensemble sampler (the stretch
+// move of Goodman & Weare 2010) of many pixels in lock-step, in the sampled slots of the unit cube, around the engine's
+// likelihood batch.  The contract is the head of nfa_ensemble_plan.h.  f64 throughout, plain products and sums (the build
+// has -ffp-contract=off), the nested sampler's counter-based random numbers; no atomics and no order that depends on
+// scheduling: the same arguments give the same bits.  One half-step is ens_propose_kernel, the likelihood launches over
+// its P W/2 rows, ens_accept_kernel; a step ends with ens_trace_kernel and, where it is kept, ens_keep_kernel.
+// (Included after nfa_sampler.h: ns_stream, ns_uniform_of.)
+#pragma once
+
+#include "nfa_ensemble_plan.h"
+
+struct EnsDev {
+    int     P, W, D, DT;                // pixels, walkers per pixel, SAMPLED dimensions, length of a theta row
+    const int *fmap;                    // [D] slot of every sampled dimension; the others stay at u = 0.5
+    const int *pix;                     // [P] cube pixel of every pixel of the run: in the random stream and in the rows
+    double *u, *theta, *lnL;            // the walkers: [P][W][D], [P][W][DT], [P][W]
+    double *rows, *row_lnL, *y;         // a half-step's batch: [P W/2][DT] (u in, theta out), [P W/2], and the proposals [P W/2][D]
+    int    *row_pix, *inside;           // [P W/2] each
+    long   *counts;                     // [P][3]: accepted, outside, evaluated
+};
+
+__device__ __forceinline__ double ens_stretch(double a, double r1) {
+    const double t = (a - 1.0) * r1 + 1.0;
+    return t * t / a;
+}
+__device__ __forceinline__ uint64_t ens_stream(const EnsDev &E, uint64_t seed, int p, long step, int h) {
+    return ns_stream(seed, (uint64_t)E.pix[p], NFA_ENS_TAG + 2ull * (uint64_t)step + (uint64_t)h);
+}
+
+// Workgroup = pixel, thread m < W/2 = walker k = h W/2 + m of the moving half.  Writes the proposal y, whether it is
+// inside, and the batch row: y through fmap where it is inside, the walker's own u where it is not (every half-step has
+// the same P W/2 rows: no compaction, no count read back), 0.5 in the slots that are not sampled.
+__global__ __launch_bounds__(256)
+void ens_propose_kernel(EnsDev E, long step, int h, double a, uint64_t seed) {
+    const int p = (int)blockIdx.x, m = (int)threadIdx.x, half = E.W >> 1;
+    if (m >= half) return;
+    const int k = h * half + m, other = (1 - h) * half;
+    const uint64_t strm = ens_stream(E, seed, p, step, h);
+    const double r0 = ns_uniform_of(strm, 3ull * (uint64_t)k), r1 = ns_uniform_of(strm, 3ull * (uint64_t)k + 1ull);
+    const int j = other + min((int)(r0 * (double)half), half - 1);
+    const double z = ens_stretch(a, r1);
+    const long row = (long)p * half + m;
+    const double *uk = E.u + ((long)p * E.W + k) * E.D, *uj = E.u + ((long)p * E.W + j) * E.D;
+    double *y = E.y + row * E.D, *t = E.rows + row * E.DT;
+    int in = 1;
+    for (int d = 0; d < E.D; ++d) {
+        const double v = uj[d] + z * (uk[d] - uj[d]);
+        y[d] = v;
+        if (!(v > 0.0 && v < 1.0)) in = 0;
+    }
+    for (int c = 0; c < E.DT; ++c) t[c] = 0.5;
+    for (int d = 0; d < E.D; ++d) t[E.fmap[d]] = in ? y[d] : uk[d];
+    E.row_pix[row] = E.pix[p];
+    E.inside[row] = in;
+}
+
+// Same geometry, after the likelihood of the rows.  An accepted walker takes y, the row's theta and its lnL.  The pixel's
+// counters: every wave counts its lanes with a ballot, the waves' counts meet in LDS and thread 0 adds them in wave order
+// (one workgroup per pixel: one writer).
+__global__ __launch_bounds__(256)
+void ens_accept_kernel(EnsDev E, long step, int h, double a, uint64_t seed) {
+    __shared__ int s_acc[4], s_out[4];
+    const int p = (int)blockIdx.x, m = (int)threadIdx.x, half = E.W >> 1;
+    int acc = 0, out = 0;
+    if (m < half) {
+        const int k = h * half + m;
+        const long row = (long)p * half + m, w = (long)p * E.W + k;
+        const uint64_t strm = ens_stream(E, seed, p, step, h);
+        const double r1 = ns_uniform_of(strm, 3ull * (uint64_t)k + 1ull), r2 = ns_uniform_of(strm, 3ull * (uint64_t)k + 2ull);
+        const double z = ens_stretch(a, r1), Ly = E.row_lnL[row], Lk = E.lnL[w];
+        out = E.inside[row] ? 0 : 1;
+        if (!out && isfinite(Ly)) {
+            const double rhs = (double)(E.D - 1) * log(z) + (Ly - Lk);
+            acc = log(r2) < rhs ? 1 : 0;
+        }
+        if (acc) {
+            const double *y = E.y + row * E.D, *t = E.rows + row * E.DT;
+            double *uk = E.u + w * E.D, *tk = E.theta + w * E.DT;
+            for (int d = 0; d < E.D; ++d) uk[d] = y[d];
+            for (int c = 0; c < E.DT; ++c) tk[c] = t[c];
+            E.lnL[w] = Ly;
+        }
+    }
+    const int wave = (int)threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
+    const int wa = __popcll(__ballot(acc)), wo = __popcll(__ballot(out));
+    if ((threadIdx.x & 63) == 0) { s_acc[wave] = wa; s_out[wave] = wo; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long ta = 0, to = 0;
+        for (int v = 0; v < nw; ++v) { ta += s_acc[v]; to += s_out[v]; }
+        long *c = E.counts + (long)p * 3;
+        c[0] += ta; c[1] += to; c[2] += half;
+    }
+}
+
+// One wave per pixel: trace[p][step - 1][0 .. D] = the mean over the walkers of every sampled u and of lnL.  Lane l adds
+// walkers l, l + 64, ... in that order, then a butterfly over the lanes (32, 16, .. 1): a fixed shape, the same bits.
+__global__ __launch_bounds__(64)
+void ens_trace_kernel(EnsDev E, long step, long n_steps, double *__restrict__ trace) {
+    const int p = (int)blockIdx.x, lane = (int)threadIdx.x;
+    double *out = trace + ((long)p * n_steps + (step - 1)) * (E.D + 1);
+    for (int q = 0; q <= E.D; ++q) {
+        double v = 0.0;
+        for (int w = lane; w < E.W; w += 64) v += q < E.D ? E.u[((long)p * E.W + w) * E.D + q] : E.lnL[(long)p * E.W + w];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) out[q] = v / (double)E.W;
+    }
+}
+
+// The state into slot `slot` of the chain: chain_theta[P][n_keep][W][DT], chain_lnL[P][n_keep][W]; a thread per double.
+__global__ __launch_bounds__(256)
+void ens_keep_kernel(EnsDev E, long slot, long n_keep, double *__restrict__ chain_theta, double *__restrict__ chain_lnL) {
+    const long nt = (long)E.W * E.DT, per = nt + E.W, i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)E.P * per) return;
+    const long p = i / per, e = i - p * per;
+    if (e < nt) chain_theta[(p * n_keep + slot) * nt + e] = E.theta[p * nt + e];
+    else chain_lnL[(p * n_keep + slot) * E.W + (e - nt)] = E.lnL[p * E.W + (e - nt)];
+}
+
+// ---- the summary of a chain --------------------------------------------------------------------------------------
+// Sums over the workgroup in a fixed shape: a butterfly inside every wave, the waves' results through red[] in wave order.
+__device__ __forceinline__ double ens_block_sum(double v, double *red) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    const int nw = (int)blockDim.x >> 6;
+    __syncthreads();                                           // the readers of the sum before are done
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int w = 0; w < nw; ++w) t += red[w];
+    return t;
+}
+// (value, index) a before b: the larger value, the smaller index on ties
+__device__ __forceinline__ bool ens_before(double va, long ia, double vb, long ib) { return va > vb || (va == vb && ia < ib); }
+
+// Workgroup = pixel; N = n_keep W kept samples in (keep, walker) order.  best[p][0 .. DT] = theta and lnL of the row of
+// largest lnL, the first on ties.  Per parameter c, with d_i = x_i - best_c: summary[p][c] = (best_c + S1 / N,
+// sqrt(max(S2 / N - (S1 / N)^2, 0))) -- moments of differences, for the reason DESIGN 4.21 gives; one sample: std 0.  With
+// nq > 0 levels (N <= NFA_ENS_MAX_SORT) the parameter's samples are sorted in LDS, padded with +inf to npow2 (bitonic: a
+// thread per compare-exchange), and quant[p][c][l] = s[i] + (s[i + 1] - s[i]) g with h = (N - 1) q_l, i = floor(h), g = h - i.
+// Dynamic LDS: red[ENS_RED_DOUBLES], then s[npow2].
+__global__ __launch_bounds__(1024)
+void ens_summary_kernel(const double *__restrict__ chain_theta, const double *__restrict__ chain_lnL, long N, int DT,
+                        const double *__restrict__ levels, int nq, long npow2,
+                        double *__restrict__ summary, double *__restrict__ best, double *__restrict__ quant) {
+    extern __shared__ __attribute__((aligned(16))) double ens_sm[];
+    double *red = ens_sm, *redv = ens_sm + 16, *s = ens_sm + ENS_RED_DOUBLES;
+    long *redi = (long *)(ens_sm + 32);
+    const long p = blockIdx.x;
+    const int t = (int)threadIdx.x, T = (int)blockDim.x, lane = t & 63, wave = t >> 6, nw = T >> 6;
+    const double *X = chain_theta + p * N * DT, *L = chain_lnL + p * N;
+    // the best row
+    double bv = -INFINITY; long bi = N;
+    for (long i = t; i < N; i += T) { const double v = L[i]; if (ens_before(v, i, bv, bi)) { bv = v; bi = i; } }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(bv, off); const long oi = __shfl_xor(bi, off);
+        if (ens_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { redv[wave] = bv; redi[wave] = bi; }
+    __syncthreads();
+    bv = redv[0]; bi = redi[0];
+    for (int w = 1; w < nw; ++w) if (ens_before(redv[w], redi[w], bv, bi)) { bv = redv[w]; bi = redi[w]; }
+    if (bi >= N) bi = 0;                                       // (every lnL NaN)
+    if (t <= DT) best[p * (DT + 1) + t] = t < DT ? X[bi * DT + t] : L[bi];
+    const double inv_n = 1.0 / (double)N;
+    for (int c = 0; c < DT; ++c) {
+        const double ref = X[bi * DT + c];
+        double s1 = 0.0, s2 = 0.0;
+        for (long i = t; i < N; i += T) { const double d = X[i * DT + c] - ref; s1 += d; s2 += d * d; }
+        s1 = ens_block_sum(s1, red);
+        s2 = ens_block_sum(s2, red);
+        if (t == 0) {
+            const double m = s1 * inv_n, var = s2 * inv_n - m * m;
+            summary[(p * DT + c) * 2] = ref + m;
+            summary[(p * DT + c) * 2 + 1] = var > 0.0 ? sqrt(var) : 0.0;
+        }
+        if (nq <= 0) continue;
+        __syncthreads();                                       // the quantiles of the parameter before are read
+        for (long i = t; i < npow2; i += T) s[i] = i < N ? X[i * DT + c] : (double)INFINITY;
+        __syncthreads();
+        for (long k = 2; k <= npow2; k <<= 1) {
+            for (long j = k >> 1; j > 0; j >>= 1) {
+                for (long i = t; i < npow2; i += T) {
+                    const long o = i ^ j;
+                    if (o > i) {
+                        const double x = s[i], y = s[o];
+                        if ((i & k) == 0 ? x > y : x < y) { s[i] = y; s[o] = x; }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (t < nq) {
+            const double hq = (double)(N - 1) * levels[t];
+            const long i = (long)hq, i1 = i + 1 < N ? i + 1 : N - 1;
+            const double g = hq - (double)i;
+            quant[(p * DT + c) * nq + t] = s[i] + (s[i1] - s[i]) * g;
+        }
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+// Everything an ensemble holds on the device belongs to it: `bufs` lives as long as the ensemble, `run_bufs` (chain and
+// trace) as long as the last run.  The likelihood batch works on the ensemble's own rows, as the nested sampler's does on
+// its candidates: run_batch on lane 0, nothing of the runner's staging.
+struct nfa_ensemble {
+    nfa_runner *r = nullptr;
+    EnsDev d = {};
+    std::vector<int> fm;                 // sampled slots
+    bool has_pix = false;
+    int *d_start_pix = nullptr;          // [P][W] cube pixel of every start row
+    std::vector<void *> bufs, run_bufs;
+    double *chain_theta = nullptr, *chain_lnL = nullptr, *trace = nullptr;
+    double *d_summary = nullptr, *d_best = nullptr, *d_quant = nullptr, *d_levels = nullptr;
+    int64_t n_keep = 0, n_steps = 0;
+};
+
+template <typename T>
+static int ens_alloc(std::vector<void *> &owner, T **out, size_t count) {
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, sizeof(T) * std::max<size_t>(count, 1)));
+    owner.push_back(p);
+    *out = (T *)p;
+    return NFA_OK;
+}
+static void ens_free(std::vector<void *> &owner) {
+    for (void *p : owner) (void)hipFree(p);
+    owner.clear();
+}
+// the likelihood of `rows` rows on lane 0, in pieces of ENS_PIECE_ROWS at most
+static int ens_evaluate(nfa_runner *r, const int *d_pix, double *d_rows, double *d_lnL, int64_t rows) {
+    for (int64_t a = 0; a < rows; a += ENS_PIECE_ROWS) {
+        const int64_t n = std::min<int64_t>(ENS_PIECE_ROWS, rows - a);
+        int rc = run_batch(r, d_pix + a, d_rows + a * r->ndim, d_lnL + a, nullptr, n, true, 0);
+        if (rc) return rc;
+    }
+    return NFA_OK;
+}
+// after a failure on lane 0: whatever was enqueued is waited for, so that the runner is usable and buffers may go
+static int ens_abandon(nfa_runner *r, int rc) {
+    const std::string why = g_err;
+    (void)hipStreamSynchronize(r->lanes[0]);
+    (void)hipGetLastError();
+    r->lane_busy &= ~1u;
+    g_err = why;
+    return rc;
+}
+
+static int ens_create_on_device(nfa_ensemble *e, const int32_t *pix, const std::vector<double> &u, const std::vector<double> &rows) {
+    nfa_runner *r = e->r;
+    EnsDev &d = e->d;
+    const size_t P = (size_t)d.P, W = (size_t)d.W, D = (size_t)d.D, DT = (size_t)d.DT, half = W / 2;
+    int rc;
+    int *fmap = nullptr, *dpix = nullptr;
+    if ((rc = ens_alloc(e->bufs, &fmap, D)) || (rc = ens_alloc(e->bufs, &dpix, P)) ||
+        (rc = ens_alloc(e->bufs, &d.u, P * W * D)) || (rc = ens_alloc(e->bufs, &d.theta, P * W * DT)) ||
+        (rc = ens_alloc(e->bufs, &d.lnL, P * W)) || (rc = ens_alloc(e->bufs, &e->d_start_pix, P * W)) ||
+        (rc = ens_alloc(e->bufs, &d.rows, P * half * DT)) || (rc = ens_alloc(e->bufs, &d.row_lnL, P * half)) ||
+        (rc = ens_alloc(e->bufs, &d.y, P * half * D)) || (rc = ens_alloc(e->bufs, &d.row_pix, P * half)) ||
+        (rc = ens_alloc(e->bufs, &d.inside, P * half)) || (rc = ens_alloc(e->bufs, &d.counts, P * 3)) ||
+        (rc = ens_alloc(e->bufs, &e->d_summary, P * DT * 2)) || (rc = ens_alloc(e->bufs, &e->d_best, P * (DT + 1))) ||
+        (rc = ens_alloc(e->bufs, &e->d_quant, P * DT * NFA_ENS_MAX_Q)) || (rc = ens_alloc(e->bufs, &e->d_levels, (size_t)NFA_ENS_MAX_Q)))
+        return rc;
+    d.fmap = fmap; d.pix = dpix;
+    std::vector<int> h_pix(P, 0), h_start(P * W, 0);
+    for (size_t p = 0; p < P; ++p) {
+        h_pix[p] = pix ? pix[p] : 0;
+        for (size_t w = 0; w < W; ++w) h_start[p * W + w] = h_pix[p];
+    }
+    HIP_TRY(hipMemcpy(fmap, e->fm.data(), sizeof(int) * D, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dpix, h_pix.data(), sizeof(int) * P, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_start_pix, h_start.data(), sizeof(int) * P * W, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.u, u.data(), sizeof(double) * P * W * D, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.theta, rows.data(), sizeof(double) * P * W * DT, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d.counts, 0, sizeof(long) * P * 3));
+    // the start rows, once: theta and lnL of every walker, straight into the state
+    rc = ens_evaluate(r, e->d_start_pix, d.theta, d.lnL, (int64_t)(P * W));
+    if (rc) return ens_abandon(r, rc);
+    hipError_t err = hipStreamSynchronize(r->lanes[0]);
+    r->lane_busy &= ~1u;
+    if (err != hipSuccess) return fail(NFA_ERR_DEVICE, std::string("ensemble start rows: ") + hipGetErrorString(err));
+    return NFA_OK;
+}
+
+extern "C" {
+
+int nfa_ensemble_destroy(nfa_ensemble *e) {
+    if (!e) return NFA_OK;
+    ens_free(e->run_bufs);
+    ens_free(e->bufs);
+    delete e;
+    return NFA_OK;
+}
+
+int64_t nfa_ensemble_bytes(int64_t n_pix, int n_walkers, int ndim, int n_sampled, int64_t n_steps, int64_t n_keep) {
+    if (n_pix < 0 || n_walkers < 0 || ndim < 0 || n_sampled < 0 || n_steps < 0 || n_keep < 0) return -1;
+    return ens_bytes(n_pix, n_walkers, ndim, n_sampled, n_steps, n_keep).total;
+}
+
+int nfa_ensemble_create(nfa_ensemble **out, nfa_runner *r, const int32_t *pix, int64_t n_pix, int n_walkers,
+                        const int32_t *free_mask, const double *u0) {
+    if (!out || !r || !u0) return fail(NFA_ERR_ARG, "null argument");
+    if (!r->pr) return fail(NFA_ERR_STATE, "runner has no priors (predict-only)");
+    if (n_pix < 1 || n_pix > (1 << 24)) return fail(NFA_ERR_ARG, "n_pix out of range");
+    if (r->ndim > NS_MAXD) return fail(NFA_ERR_ARG, "too many dimensions");
+    int rc = check_pix(r, pix, n_pix); if (rc) return rc;
+    std::vector<int> fm;
+    for (int j = 0; j < r->ndim; ++j) if (!free_mask || free_mask[j]) fm.push_back(j);
+    if (fm.empty()) return fail(NFA_ERR_ARG, "no free dimension to sample");
+    const int D = (int)fm.size(), DT = r->ndim, W = n_walkers;
+    if (const char *why = ens_check_walkers(W, D)) return fail(NFA_ERR_ARG, why);
+    // the start: u of the sampled slots, and the full rows with 0.5 elsewhere
+    const size_t n = (size_t)n_pix * (size_t)W;
+    std::vector<double> u(n * D), rows(n * DT, 0.5);
+    for (size_t i = 0; i < n; ++i)
+        for (int d = 0; d < D; ++d) {
+            const double v = u0[i * DT + fm[d]];
+            if (!(v > 0.0 && v < 1.0)) return fail(NFA_ERR_ARG, "ensemble: u0 must lie inside (0, 1) at every sampled slot");
+            u[i * D + d] = v; rows[i * DT + fm[d]] = v;
+        }
+    rc = engine_init(); if (rc) return rc;
+    nfa_ensemble *e = new nfa_ensemble();
+    e->r = r; e->fm = fm; e->has_pix = pix != nullptr;
+    e->d.P = (int)n_pix; e->d.W = W; e->d.D = D; e->d.DT = DT;
+    {
+        RUNNER_LOCK(r);
+        rc = sync_all_lanes(r);
+        if (!rc) rc = ens_create_on_device(e, pix, u, rows);
+    }
+    if (rc) { const std::string why = g_err; nfa_ensemble_destroy(e); g_err = why; return rc; }
+    *out = e;
+    return NFA_OK;
+}
+
+int nfa_ensemble_run(nfa_ensemble *e, int64_t n_steps, int64_t n_burn, int64_t thin, double a, int64_t seed, double log_zero) {
+    if (!e) return fail(NFA_ERR_ARG, "null ensemble");
+    if (const char *why = ens_check_run(n_steps, n_burn, thin, a)) return fail(NFA_ERR_ARG, why);
+    nfa_runner *r = e->r;
+    EnsDev &d = e->d;
+    const int64_t P = d.P, W = d.W, half = W / 2, n_keep = ens_n_keep(n_steps, n_burn, thin);
+    RUNNER_LOCK(r);
+    int rc = sync_all_lanes(r); if (rc) return rc;
+    // chain and trace of the run before go, this run's come
+    ens_free(e->run_bufs);
+    e->chain_theta = e->chain_lnL = e->trace = nullptr; e->n_keep = e->n_steps = 0;
+    if ((rc = ens_alloc(e->run_bufs, &e->chain_theta, (size_t)(P * n_keep * W * d.DT))) ||
+        (rc = ens_alloc(e->run_bufs, &e->chain_lnL, (size_t)(P * n_keep * W))) ||
+        (rc = ens_alloc(e->run_bufs, &e->trace, (size_t)(P * n_steps * (d.D + 1))))) {
+        const std::string why = g_err; ens_free(e->run_bufs); e->chain_theta = e->chain_lnL = e->trace = nullptr; g_err = why;
+        return rc;
+    }
+    hipStream_t st = r->lanes[0];
+    const EnsGeom Gw = ens_walk_geom(P, (int)W), Gt = ens_trace_geom(P), Gk = ens_keep_geom(P, (int)W, d.DT);
+    auto steps = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(d.counts, 0, sizeof(long) * P * 3, st));
+        hipLaunchKernelGGL(ns_sanitize_kernel, dim3((unsigned)((P * W + 255) / 256)), dim3(256), 0, st, d.lnL, (long)(P * W), log_zero);
+        HIP_TRY(hipGetLastError());
+        for (int64_t s = 1; s <= n_steps; ++s) {
+            for (int h = 0; h < 2; ++h) {
+                hipLaunchKernelGGL(ens_propose_kernel, dim3(Gw.grid), dim3(Gw.threads), 0, st, d, (long)s, h, a, (uint64_t)seed);
+                HIP_TRY(hipGetLastError());
+                int rcb = ens_evaluate(r, d.row_pix, d.rows, d.row_lnL, P * half);
+                if (rcb) return rcb;
+                hipLaunchKernelGGL(ens_accept_kernel, dim3(Gw.grid), dim3(Gw.threads), 0, st, d, (long)s, h, a, (uint64_t)seed);
+                HIP_TRY(hipGetLastError());
+            }
+            hipLaunchKernelGGL(ens_trace_kernel, dim3(Gt.grid), dim3(Gt.threads), 0, st, d, (long)s, (long)n_steps, e->trace);
+            HIP_TRY(hipGetLastError());
+            if (ens_keeps(s, n_burn, thin)) {
+                hipLaunchKernelGGL(ens_keep_kernel, dim3(Gk.grid), dim3(Gk.threads), 0, st, d, (long)ens_keep_slot(s, n_burn, thin),
+                                   (long)n_keep, e->chain_theta, e->chain_lnL);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        return NFA_OK;
+    };
+    rc = steps();
+    if (rc) return ens_abandon(r, rc);
+    r->lane_busy &= ~1u;
+    e->n_keep = n_keep; e->n_steps = n_steps;
+    return NFA_OK;
+}
+
+int nfa_ensemble_counts(nfa_ensemble *e, int64_t *accepted, int64_t *outside, int64_t *evaluated) {
+    if (!e || !accepted || !outside || !evaluated) return fail(NFA_ERR_ARG, "null argument");
+    RUNNER_LOCK(e->r);
+    std::vector<long> h((size_t)e->d.P * 3);
+    HIP_TRY(hipMemcpy(h.data(), e->d.counts, sizeof(long) * h.size(), hipMemcpyDeviceToHost));
+    for (int p = 0; p < e->d.P; ++p) { accepted[p] = h[3 * p]; outside[p] = h[3 * p + 1]; evaluated[p] = h[3 * p + 2]; }
+    return NFA_OK;
+}
+
+int nfa_ensemble_state(nfa_ensemble *e, double *u, double *theta, double *lnL) {
+    if (!e) return fail(NFA_ERR_ARG, "null ensemble");
+    RUNNER_LOCK(e->r);
+    const EnsDev &d = e->d;
+    const size_t n = (size_t)d.P * d.W;
+    if (u) {
+        std::vector<double> h(n * d.D);
+        HIP_TRY(hipMemcpy(h.data(), d.u, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            for (int c = 0; c < d.DT; ++c) u[i * d.DT + c] = 0.5;
+            for (int k = 0; k < d.D; ++k) u[i * d.DT + e->fm[k]] = h[i * d.D + k];
+        }
+    }
+    if (theta) HIP_TRY(hipMemcpy(theta, d.theta, sizeof(double) * n * d.DT, hipMemcpyDeviceToHost));
+    if (lnL) HIP_TRY(hipMemcpy(lnL, d.lnL, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return NFA_OK;
+}
+
+int nfa_ensemble_trace(nfa_ensemble *e, double *trace) {
+    if (!e || !trace) return fail(NFA_ERR_ARG, "null argument");
+    if (!e->trace) return fail(NFA_ERR_STATE, "ensemble: no run yet");
+    RUNNER_LOCK(e->r);
+    HIP_TRY(hipMemcpy(trace, e->trace, sizeof(double) * (size_t)e->d.P * e->n_steps * (e->d.D + 1), hipMemcpyDeviceToHost));
+    return NFA_OK;
+}
+
+int nfa_ensemble_chain(nfa_ensemble *e, double *theta, double *lnL) {
+    if (!e) return fail(NFA_ERR_ARG, "null ensemble");
+    if (!e->chain_theta) return fail(NFA_ERR_STATE, "ensemble: no run yet");
+    RUNNER_LOCK(e->r);
+    const size_t n = (size_t)e->d.P * e->n_keep * e->d.W;
+    if (theta) HIP_TRY(hipMemcpy(theta, e->chain_theta, sizeof(double) * n * e->d.DT, hipMemcpyDeviceToHost));
+    if (lnL) HIP_TRY(hipMemcpy(lnL, e->chain_lnL, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return NFA_OK;
+}
+
+int nfa_ensemble_chain_dev(nfa_ensemble *e, const double **d_theta, const double **d_lnL, int64_t *n_keep) {
+    if (!e) return fail(NFA_ERR_ARG, "null ensemble");
+    if (!e->chain_theta) return fail(NFA_ERR_STATE, "ensemble: no run yet");
+    if (d_theta) *d_theta = e->chain_theta;
+    if (d_lnL) *d_lnL = e->chain_lnL;
+    if (n_keep) *n_keep = e->n_keep;
+    return NFA_OK;
+}
+
+int nfa_ensemble_summary(nfa_ensemble *e, const double *levels, int n_levels, double *summary, double *best, double *quant) {
+    if (!e) return fail(NFA_ERR_ARG, "null ensemble");
+    if (!e->chain_theta) return fail(NFA_ERR_STATE, "ensemble: no run yet");
+    const EnsDev &d = e->d;
+    const int64_t N = e->n_keep * d.W;
+    if (const char *why = ens_check_levels(levels, n_levels, N)) return fail(NFA_ERR_ARG, why);
+    if (n_levels > 0 && !quant) return fail(NFA_ERR_ARG, "ensemble: quantile levels without a place for the quantiles");
+    nfa_runner *r = e->r;
+    RUNNER_LOCK(r);
+    int rc = sync_all_lanes(r); if (rc) return rc;
+    hipStream_t st = r->lanes[0];
+    const EnsGeom G = ens_summary_geom(d.P, N, n_levels);
+    rc = ensure_dynamic_lds((const void *)ens_summary_kernel, G.lds); if (rc) return rc;
+    auto work = [&]() -> int {
+        if (n_levels > 0) HIP_TRY(hipMemcpyAsync(e->d_levels, levels, sizeof(double) * n_levels, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(ens_summary_kernel, dim3(G.grid), dim3(G.threads), G.lds, st, (const double *)e->chain_theta,
+                           (const double *)e->chain_lnL, (long)N, d.DT, (const double *)e->d_levels, n_levels,
+                           (long)ens_sort_len(N, n_levels), e->d_summary, e->d_best, e->d_quant);
+        HIP_TRY(hipGetLastError());
+        const size_t P = (size_t)d.P, DT = (size_t)d.DT;
+        if (summary) HIP_TRY(hipMemcpyAsync(summary, e->d_summary, sizeof(double) * P * DT * 2, hipMemcpyDeviceToHost, st));
+        if (best) HIP_TRY(hipMemcpyAsync(best, e->d_best, sizeof(double) * P * (DT + 1), hipMemcpyDeviceToHost, st));
+        if (n_levels > 0) HIP_TRY(hipMemcpyAsync(quant, e->d_quant, sizeof(double) * P * DT * n_levels, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return NFA_OK;
+    };
+    rc = work();
+    if (rc) return ens_abandon(r, rc);
+    return NFA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,98 @@
+// nfa_ensemble_plan.h -- the ensemble sampler (nfa_ensemble_*, nfa_ensemble.h), planned on the host: its limits and the
+// tag of its random streams, the checks of its arguments, which steps are kept, the bytes a run holds on the device, the
+// launch geometries and the LDS of the summary.
+//
+// Standard C++17 without a HIP include, like nfa_lsq_plan.h and nfa_moments_plan.h: a host compiler builds this header
+// alone, and tests/test_ensemble_cpu.py checks it without a GPU.  Arithmetic only.  Errors travel as `const char *`, in
+// the words the engine fails with.
+//
+// The contract (include/nestfit_amd.h and DESIGN 4.24 say the same).  A run holds P pixels with W walkers each, W even,
+// W / 2 >= D + 1, in the D sampled slots of the unit cube.  One step is two half-steps h = 0, 1; in half-step h the
+// walkers k of [h W/2, (h+1) W/2) move against the other half as it stands.  With p the pixel's cube index, s the step
+// (from 1 in every run) and r_i = ns_uniform_of(ns_stream(seed, p, NFA_ENS_TAG + 2 s + h), 3 k + i):
+//     partner  j = other half's base + min(floor(r_0 W/2), W/2 - 1)
+//     stretch  z = ((a - 1) r_1 + 1)^2 / a
+//     proposal y_d = u_j,d + z (u_k,d - u_j,d)                     (inside: every y_d in (0, 1))
+//     accept   inside, lnL_y finite, and log(r_2) < (D - 1) log(z) + (lnL_y - lnL_k)
+// The state after step s is kept iff s > n_burn and (s - n_burn) % thin == 0.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#define NFA_ENS_MAX_WALKERS 512          // include/nestfit_amd.h says the same for these three
+#define NFA_ENS_MAX_Q       8            // quantile levels of a summary
+#define NFA_ENS_MAX_SORT    8192         // kept samples per pixel a summary sorts: 64 KB of LDS
+// The streams of a run: ns_stream(seed, pixel, NFA_ENS_TAG + 2 step + half).  The nested sampler's third stream argument
+// is a count of proposals (below 2^61), NS_FRAME_SEED (2^31) or NS_TAG_LIVE + live point (2^62 ..); a run of 2^59 steps
+// stays inside [2^61, 2^62).
+#define NFA_ENS_TAG         (1ull << 61)
+#define ENS_A_MAX           16.0         // the stretch scale: 1 < a <= 16
+#define ENS_PIECE_ROWS      (1 << 20)    // rows of one likelihood launch at most; a larger half-step is cut into pieces
+#define ENS_STEPS_MAX       (1ll << 40)
+#define ENS_RED_DOUBLES     64           // head of the summary's LDS: the partial results of up to 16 waves, three arrays
+
+// ---- argument checks: null, or why the argument is refused
+inline const char *ens_check_walkers(int n_walkers, int n_sampled) {
+    if (n_walkers < 2 || n_walkers > NFA_ENS_MAX_WALKERS) return "ensemble: n_walkers must be in 2 .. NFA_ENS_MAX_WALKERS = 512";
+    if (n_walkers % 2 != 0) return "ensemble: n_walkers must be even: each half moves against the other";
+    if (n_walkers / 2 < n_sampled + 1) return "ensemble: half the walkers must number the sampled dimensions + 1 at least";
+    return nullptr;
+}
+inline int64_t ens_n_keep(int64_t n_steps, int64_t n_burn, int64_t thin) { return thin < 1 ? 0 : (n_steps - n_burn) / thin; }
+inline bool ens_keeps(int64_t step, int64_t n_burn, int64_t thin) { return step > n_burn && (step - n_burn) % thin == 0; }
+inline int64_t ens_keep_slot(int64_t step, int64_t n_burn, int64_t thin) { return (step - n_burn) / thin - 1; }
+inline const char *ens_check_run(int64_t n_steps, int64_t n_burn, int64_t thin, double a) {
+    if (!(a > 1.0 && a <= ENS_A_MAX)) return "ensemble: the stretch scale a must lie in (1, 16]";
+    if (thin < 1) return "ensemble: thin must be 1 at least";
+    if (n_steps < 1 || n_steps > ENS_STEPS_MAX) return "ensemble: n_steps is out of range";
+    if (n_burn < 0 || n_burn >= n_steps) return "ensemble: n_burn must lie in 0 .. n_steps - 1";
+    if (ens_n_keep(n_steps, n_burn, thin) < 1) return "ensemble: no step is kept: (n_steps - n_burn) / thin is 0";
+    return nullptr;
+}
+// the quantile levels of a summary over n_samples = n_keep W kept samples per pixel
+inline const char *ens_check_levels(const double *levels, int n_levels, int64_t n_samples) {
+    if (n_levels < 0 || n_levels > NFA_ENS_MAX_Q) return "ensemble: a summary takes NFA_ENS_MAX_Q = 8 quantile levels at most";
+    if (n_levels > 0 && !levels) return "ensemble: quantile levels are counted but not given";
+    for (int i = 0; i < n_levels; ++i)
+        if (!(levels[i] >= 0.0 && levels[i] <= 1.0)) return "ensemble: a quantile level lies outside [0, 1]";
+    if (n_levels > 0 && n_samples > NFA_ENS_MAX_SORT) return "ensemble: quantiles take NFA_ENS_MAX_SORT = 8192 kept samples per pixel at most";
+    return nullptr;
+}
+
+// ---- device bytes of an ensemble of P pixels: what create allocates (state: the walkers, a half-step's proposal rows,
+// the counters and the summary's outputs), and what a run of n_steps steps with n_keep kept adds (chain, trace)
+struct EnsBytes { int64_t state, chain, trace, total; };
+inline EnsBytes ens_bytes(int64_t P, int W, int ndim, int D, int64_t n_steps, int64_t n_keep) {
+    const int64_t d = 8, i = 4, walkers = P * W, rows = P * (W / 2);
+    EnsBytes B;
+    B.state = walkers * (D + ndim + 1) * d + walkers * i           // u, theta, lnL; the pixel of every start row
+            + rows * (ndim + D + 1) * d + rows * 2 * i             // a half-step: rows, y, lnL; pixel and inside flag
+            + P * 3 * d + P * i + (int64_t)D * i                   // counters, pix, fmap
+            + P * ((int64_t)ndim * 2 + (ndim + 1) + (int64_t)ndim * NFA_ENS_MAX_Q) * d + NFA_ENS_MAX_Q * d;    // summary, best, quant, levels
+    B.chain = P * n_keep * W * (ndim + 1) * d;
+    B.trace = P * n_steps * (D + 1) * d;
+    B.total = B.state + B.chain + B.trace;
+    return B;
+}
+
+// ---- launch geometries
+struct EnsGeom { unsigned grid, threads; size_t lds; };
+// propose and accept: a workgroup per pixel, a thread per walker of the moving half (whole waves: 64 .. 256 threads)
+inline EnsGeom ens_walk_geom(int64_t P, int W) { return EnsGeom{(unsigned)P, (unsigned)((W / 2 + 63) / 64 * 64), 0}; }
+// trace: one wave per pixel
+inline EnsGeom ens_trace_geom(int64_t P) { return EnsGeom{(unsigned)P, 64u, 0}; }
+// keep: a thread per double of the state's theta and lnL
+inline EnsGeom ens_keep_geom(int64_t P, int W, int ndim) { return EnsGeom{(unsigned)((P * W * (ndim + 1) + 255) / 256), 256u, 0}; }
+// summary: a workgroup per pixel.  With quantiles the n_samples of a parameter are sorted in LDS, padded to a power of two
+// (bitonic); the head of the LDS holds the waves' partial results.
+inline int64_t ens_pow2(int64_t n) { int64_t m = 1; while (m < n) m <<= 1; return m; }
+inline int64_t ens_sort_len(int64_t n_samples, int n_levels) { return n_levels > 0 ? (ens_pow2(n_samples) < 2 ? 2 : ens_pow2(n_samples)) : 0; }
+inline size_t ens_summary_lds(int64_t n_samples, int n_levels) {
+    return sizeof(double) * (size_t)(ENS_RED_DOUBLES + ens_sort_len(n_samples, n_levels));
+}
+inline EnsGeom ens_summary_geom(int64_t P, int64_t n_samples, int n_levels) {
+    int64_t t = ens_pow2(n_samples) / 2;                   // a thread per compare-exchange of a sorting stage, up to 1024
+    t = t < 64 ? 64 : t > 1024 ? 1024 : t;
+    return EnsGeom{(unsigned)P, (unsigned)t, ens_summary_lds(n_samples, n_levels)};
+}

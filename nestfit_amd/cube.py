@@ -234,3 +234,8 @@ class CubeRunner(RunnerSurface):
         return _calls._normal_equations(self._run.handle, _calls.pixel_indices(pix, theta.shape[0]), theta, None, None, None, None,
                                         False, want_grad=False).chi2
 
+    def sample_posterior(self, pix, **kw):
+        """The posteriors of the pixels pix[P] at the runner's component count by ensemble MCMC on the device: an
+        `EnsembleResult` of one row per pixel (`nestfit_amd.ensemble.sample_pixels`' keywords)."""
+        return _calls._sample_posterior(self, np.ascontiguousarray(pix, dtype=np.int32), **kw)
+

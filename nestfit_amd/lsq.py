@@ -171,6 +171,26 @@ def prior_box(utrans, ncomp, n=4096, seed=0):
     return U.min(axis=0), U.max(axis=0)
 
 
+def best_draws(runner, pix, n_draws, n_best, rng, unit=False):
+    """Per pixel of `pix`, the `n_best` prior draws of highest lnL among `n_draws`, ties by draw index: [len(pix), n_best,
+    ndim], the physical parameters, or (`unit`) the unit-cube rows they came from.  The draws are scored with
+    `loglikelihood_batch` in blocks of pixels; `pix` None: the pixel of a one-pixel runner."""
+    one = pix is None
+    pix = np.zeros(1, dtype=np.int32) if one else np.ascontiguousarray(pix, dtype=np.int32)
+    n_pix, ndim = pix.size, runner.ndim
+    out = np.empty((n_pix, n_best, ndim))
+    block = max(1, (1 << 22) // (n_draws * ndim))            # pixels scored per call: 32 MB of draws
+    for a in range(0, n_pix, block):
+        b = min(n_pix, a + block)
+        U = rng.uniform(size=((b - a) * n_draws, ndim))
+        kept = U.copy() if unit else U
+        lnl = runner.loglikelihood_batch(U) if one else runner.loglikelihood_batch(np.repeat(pix[a:b], n_draws), U)      # U becomes theta
+        lnl = np.where(np.isfinite(lnl), lnl, -np.inf).reshape(b - a, n_draws)
+        best = np.argsort(-lnl, axis=1, kind='stable')[:, :n_best]
+        out[a:b] = kept.reshape(b - a, n_draws, ndim)[np.arange(b - a)[:, None], best]
+    return out
+
+
 def _free(theta, grad, curv, lower, upper):
     """The parameters a step may move: a positive curvature, and not at a bound with the gradient pointing outward."""
     diag = np.diagonal(curv, axis1=1, axis2=2)
@@ -284,16 +304,7 @@ def fit_cube(stack, utrans, runner_cls, ncomp=1, n_draws=2048, n_starts=4, runne
     n_pix, ndim = runner.n_pix, runner.ndim
     n_starts = min(int(n_starts), int(n_draws))
     lower, upper = prior_box(utrans, ncomp, seed=seed)
-    rng = np.random.default_rng(seed)
-    starts = np.empty((n_pix, n_starts, ndim))
-    block = max(1, (1 << 22) // (n_draws * ndim))            # pixels scored per call: 32 MB of draws
-    for a in range(0, n_pix, block):
-        b = min(n_pix, a + block)
-        U = rng.uniform(size=((b - a) * n_draws, ndim))
-        lnl = runner.loglikelihood_batch(np.repeat(np.arange(a, b, dtype=np.int32), n_draws), U)      # U becomes theta
-        lnl = np.where(np.isfinite(lnl), lnl, -np.inf).reshape(b - a, n_draws)
-        best = np.argsort(-lnl, axis=1, kind='stable')[:, :n_starts]
-        starts[a:b] = U.reshape(b - a, n_draws, ndim)[np.arange(b - a)[:, None], best]
+    starts = best_draws(runner, np.arange(n_pix, dtype=np.int32), n_draws, n_starts, np.random.default_rng(seed))
     lower, upper = np.minimum(lower, starts.min(axis=(0, 1))), np.maximum(upper, starts.max(axis=(0, 1)))
     pix = np.repeat(np.arange(n_pix), n_starts)
     res = fit_pixels(DeviceBackend(runner), pix, starts.reshape(n_pix * n_starts, ndim), lower, upper, **fit_kw)

@@ -1,0 +1,135 @@
+"""What the ensemble sampler costs on the device.
+
+1. Wall time per step: P = 1024 pixels, W = 64 walkers, two spectra of 1024 channels, two ammonia components (ten sampled
+   dimensions), both numerical modes; a host clock around `nfa_ensemble_run` (synchronous), the median of REPEATS runs of
+   200 steps after warm-up.  The split by kernel comes from a kernel trace of this script in a run of its own (`--trace`:
+   one run of 50 steps per mode and nothing else).
+2. The summary on the device against the host route: `nfa_ensemble_summary` against fetching the chain and `ensemble.summarize`
+   (the same reductions in numpy), same shape, 8192 kept samples per pixel.
+3. `--cube`: evaluations per pixel on the 32 x 32 cube of config 5 (synth.c5_stack), two components, until n_eff >= 1000 in
+   every sampled dimension: runs of doubling length, the share of pixels that got there and of pixels whose tau is not yet
+   trustworthy (n_steps - n_burn < 50 tau), reported, not dropped.
+
+    python scripts/measure_ensemble.py [--out profiles/ensemble.txt] [--pixels 1024] [--trace | --cube]
+"""
+import argparse
+import ctypes as C
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+REPEATS = 20
+
+
+def cube(args, lines):
+    import nestfit_amd as na
+    from nestfit_amd import ensemble
+    from nestfit_amd.synth import c5_stack
+    stack, _, _, _, _, ut = c5_stack(side=args.side, n=args.chan)
+    na.set_exp_mode('table')
+    mask = ut.free_mask(2)
+    for n_steps in args.steps:
+        t0 = time.perf_counter()
+        maps = ensemble.sample_cube(stack, ut, na.AmmoniaRunner, 2, n_walkers=64, n_steps=n_steps, free_mask=mask, levels=())
+        dt = time.perf_counter() - t0
+        n_eff = np.nanmin(np.where(np.isfinite(maps.n_eff), maps.n_eff, 0.0), axis=0).ravel()
+        tau = np.nanmax(np.where(np.isfinite(maps.tau), maps.tau, np.inf), axis=0).ravel()
+        young = (n_steps - n_steps // 2) < 50 * tau
+        evals = maps.n_evals.ravel() + 2048                     # the start draws included
+        lines += [f'sample_cube, table mode: {args.side} x {args.side} pixels, 2 x {args.chan} channels, ncomp 2, W = 64, {n_steps} steps, half burned',
+                  f'  whole call {dt:8.2f} s; evaluations per pixel {int(np.median(evals))} (nested run, DESIGN 6: 1.10 M)',
+                  f'  pixels with n_eff >= 1000 in every sampled dimension: {float(np.mean(n_eff >= 1000)):.3f}; median of the smallest n_eff {float(np.median(n_eff)):.0f}',
+                  f'  pixels whose tau is not yet trustworthy (n_steps - n_burn < 50 tau): {float(np.mean(young)):.3f}; median of the largest tau {float(np.median(tau)):.1f} steps',
+                  f'  acceptance {float(np.nanmedian(maps.acceptance)):.3f}, outside {float(np.nanmedian(maps.outside)):.3f}', '']
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=str(ROOT / 'profiles' / 'ensemble.txt'))
+    ap.add_argument('--pixels', type=int, default=1024)
+    ap.add_argument('--chan', type=int, default=1024)
+    ap.add_argument('--side', type=int, default=32)
+    ap.add_argument('--steps', type=int, nargs='+', default=[1000, 4000])
+    ap.add_argument('--repeats', type=int, default=REPEATS)
+    ap.add_argument('--trace', action='store_true', help='one run of 50 steps per mode and nothing else (for a kernel trace)')
+    ap.add_argument('--cube', action='store_true', help='evaluations per pixel on the cube of config 5')
+    args = ap.parse_args()
+
+    import nestfit_amd as na
+    from nestfit_amd import _ffi, ensemble
+    from nestfit_amd.cube import CubeRunner
+    from nestfit_amd.synth import TRUTH_2COMP, freq_axis
+    lib = _ffi.engine()
+    assert na.device_count() > 0, 'no GPU visible'
+    name = C.create_string_buffer(256)
+    _ffi.check(lib.nfa_device_name(name, 256))
+    lines = [f'ensemble sampler, {name.value.decode()}', '']
+    if args.cube:
+        cube(args, lines)
+        text = '\n'.join(lines)
+        print(text)
+        Path(args.out).write_text(text + '\n')
+        return 0
+
+    P, W, n = args.pixels, 64, args.chan
+    rng = np.random.default_rng(1)
+    axes = [freq_axis(1, n), freq_axis(2, n)]
+    ut = na.get_irdc_priors(size=500, vsys=0.0)
+    na.set_exp_mode('table')
+    probe = CubeRunner(axes, (1, 2), np.zeros((1, 2 * n)), np.full((1, 2), 0.2), ut, ncomp=2)
+    model, _ = probe.predict_batch(np.zeros(P, np.int32), np.repeat(TRUTH_2COMP[None], P, axis=0))
+    runner = CubeRunner(axes, (1, 2), model + rng.normal(0, 0.2, model.shape), np.full((P, 2), 0.2), ut, ncomp=2)
+    pix = np.arange(P, dtype=np.int32)
+    mask = ut.free_mask(2)
+    u0 = ensemble.starts(runner, pix, W, n_init=256, seed=1)
+    for mode in ('table', 'fast'):
+        runner.set_exp_mode(mode)
+        ens = ensemble.DeviceEnsemble(runner, pix, W, u0, mask)
+        if args.trace:
+            ens.run(50, 0, 1, 2.0, 1)
+            ens.close()
+            continue
+        ens.run(20, 0, 1, 2.0, 1)                                  # warm-up: the kernels load, the lanes' workspaces come
+        times = []
+        for k in range(args.repeats):
+            t0 = time.perf_counter()
+            ens.run(200, 100, 1, 2.0, 2 + k)
+            times.append(time.perf_counter() - t0)
+        per_step = statistics.median(times) / 200
+        lines += [f'mode {mode}: P = {P}, W = {W}, 2 x {n} channels, ncomp 2 (D = {ens.D} of {ens.ndim}); {P * W // 2} rows per half-step',
+                  f'  run of 200 steps, median of {args.repeats}   {statistics.median(times) * 1e3:10.2f} ms  ({min(times) * 1e3:.2f} .. {max(times) * 1e3:.2f})',
+                  f'  per step                          {per_step * 1e6:10.1f} us  = {P * W / per_step / 1e6:.1f} M evaluations/s']
+        # the summary: 128 kept steps x 64 walkers = 8192 samples per pixel
+        ens.run(256, 128, 1, 2.0, 99)
+        levels = (0.16, 0.5, 0.84)
+        ens.summary(levels)
+        t_dev, t_host = [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            dev = ens.summary(levels)
+            t_dev.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            theta, lnL = ens.chain()
+            host = ensemble.summarize(theta, lnL, levels)
+            t_host.append(time.perf_counter() - t0)
+        assert np.array_equal(dev[2], host[2]) and np.array_equal(dev[4], host[4])
+        lines += [f'  summary of {P} x 8192 samples x {ens.ndim} parameters, three quantiles:',
+                  f'    nfa_ensemble_summary            {statistics.median(t_dev) * 1e3:10.2f} ms',
+                  f'    chain to the host + numpy       {statistics.median(t_host) * 1e3:10.2f} ms  (the chain is {theta.nbytes / 1e6:.0f} MB)', '']
+        ens.close()
+    if args.trace:
+        return 0
+    text = '\n'.join(lines)
+    print(text)
+    Path(args.out).write_text(text + '\n')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
