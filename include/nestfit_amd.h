@@ -899,6 +899,27 @@ int nfa_ensemble_chain_dev(nfa_ensemble *e, const double **d_theta, const double
 int nfa_ensemble_summary(nfa_ensemble *e, const double *levels, int n_levels, double *summary, double *best, double *quant);
 int64_t nfa_ensemble_bytes(int64_t n_pix, int n_walkers, int ndim, int n_sampled, int64_t n_steps, int64_t n_keep);
 
+/* The products of the last run's chain, reduced where it lies; N = n_keep W samples per pixel in (keep,
+ * walker) order.  Each takes the runner's lock, waits for its lanes and works on lane 0 like nfa_ensemble_summary; NFA_ERR_STATE
+ * before the first run; a failure leaves runner and ensemble usable; the same arguments give the same bits.
+ * nfa_ensemble_histogram bins column c of every pixel on edges[c][0 .. n_bins], strictly increasing and finite, 1 <= n_bins <=
+ * NFA_ENS_MAX_BINS (else NFA_ERR_ARG): bin b counts edges[b] <= x < edges[b + 1], the last bin x == edges[n_bins] too; a NaN,
+ * an x < edges[0] and an x > edges[n_bins] are counted in outside[p][c] and in no bin -- np.histogram(x, bins=edges[c])[0].
+ * nfa_ensemble_covariance: about the pixel's best row b (nfa_ensemble_summary's), d_i,a = x_i,a - x_b,a, S_a = sum d_i,a,
+ * S_ab = sum d_i,a d_i,b: cov_ab = S_ab / N - (S_a / N)(S_b / N), the diagonal not below 0, computed for a <= b and mirrored; a
+ * slot that is not sampled has an exact zero row and column.
+ * nfa_ensemble_moments is nfa_runner_predict_moments with n_seg = n_pix, seg_pix the ensemble's pixels, seg_off[g] = g N, theta
+ * the chain and no weights, bit for bit (one function behind both), the chain read where it lies and left as it is.
+ * nfa_ensemble_moments_bytes: the runner scratch that call holds per pixel, beside nfa_ensemble_bytes; histogram and
+ * covariance hold a fixed scratch for the length of the call, whatever n_pix. */
+#define NFA_ENS_MAX_BINS 1024
+int nfa_ensemble_histogram(nfa_ensemble *e, const double *edges /* [ndim][n_bins + 1] */, int n_bins,
+                           int64_t *counts /* [n_pix][ndim][n_bins] */, int64_t *outside /* [n_pix][ndim] or NULL */);
+int nfa_ensemble_covariance(nfa_ensemble *e, double *cov /* [n_pix][ndim][ndim] */);
+int nfa_ensemble_moments(nfa_ensemble *e, int64_t chunk_rows /* as nfa_runner_predict_moments */,
+                         double *spec_mean, double *spec_std, double *stat_mean, double *stat_std);
+int64_t nfa_ensemble_moments_bytes(int64_t n_pix, int64_t chan_tot, int n_spec);
+
 /* ---- the exchange step of a sharded cube fit ---------------------
  * The reference stripes pixels over processes, (lon_ix[i::nproc], lat_ix[i::nproc])
  * (nestfit/main.py:565-571), and exchanges nothing while sampling; its processes meet through chunk

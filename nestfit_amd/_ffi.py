@@ -163,6 +163,10 @@ SIGNATURES = {
     'nfa_ensemble_chain_dev': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _lp]),
     'nfa_ensemble_summary': (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, _dp]),
     'nfa_ensemble_bytes': (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    'nfa_ensemble_histogram': (C.c_int, [C.c_void_p, _dp, C.c_int, _lp, _lp]),
+    'nfa_ensemble_covariance': (C.c_int, [C.c_void_p, _dp]),
+    'nfa_ensemble_moments': (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
+    'nfa_ensemble_moments_bytes': (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
     'nfa_comm_unique_id':(C.c_int, [C.POINTER(C.c_ubyte)]),
     'nfa_comm_create': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.c_int, C.c_int]),
     'nfa_comm_destroy': (C.c_int, [C.c_void_p]),

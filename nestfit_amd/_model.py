@@ -933,7 +933,8 @@ class EngineRunner(RunnerSurface, Runner):
 
     def sample_posterior(self, **kw):
         """The posterior of the runner's pixel at its component count by ensemble MCMC on the device: an `EnsembleResult` of
-        one row (`nestfit_amd.ensemble.sample_pixels`' keywords)."""
+        one row (`nestfit_amd.ensemble.sample_pixels`' keywords; `par_bins`, `covariance`, `moments`: the marginal
+        histograms, parameter covariances and model moments of the chain)."""
         return _calls._sample_posterior(self, None, **kw)
 
 

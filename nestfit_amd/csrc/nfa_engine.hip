@@ -2052,62 +2052,34 @@ static int launch_accumulate(nfa_runner *r, const double *d_x, int64_t ld, int64
     return NFA_OK;
 }
 
-extern "C" {
-
-int nfa_runner_predict_moments(nfa_runner *r, int64_t n_seg, const int32_t *seg_pix, const int64_t *seg_off, const double *theta,
-                               const double *weight, int64_t chunk_rows, double *spec_mean, double *spec_std,
-                               double *stat_mean, double *stat_std) {
-    if (!r) return fail(NFA_ERR_ARG, "null runner");
-    if (n_seg < 0 || n_seg > INT32_MAX) return fail(NFA_ERR_ARG, "the number of segments is out of range");
-    if (!spec_mean && !spec_std && !stat_mean && !stat_std) return fail(NFA_ERR_ARG, "predict_moments: all four outputs are null");
-    if (const char *why = mom_check_chunk_rows(chunk_rows)) return fail(NFA_ERR_ARG, why);
-    if (n_seg == 0) return NFA_OK;
-    if (!seg_off) return fail(NFA_ERR_ARG, "null argument");
-    if (seg_off[0] != 0) return fail(NFA_ERR_ARG, "segment offsets start at 0");
-    for (int64_t g = 0; g < n_seg; ++g)
-        if (seg_off[g + 1] < seg_off[g]) return fail(NFA_ERR_ARG, "segment offsets must not decrease");
-    const int64_t rows = seg_off[n_seg];
-    if (rows > 0 && !theta) return fail(NFA_ERR_ARG, "null argument");
-    int rc = check_pix(r, seg_pix, n_seg); if (rc) return rc;
-    if (weight)
-        for (int64_t i = 0; i < rows; ++i)
-            if (!(weight[i] >= 0.0) || !std::isfinite(weight[i])) return fail(NFA_ERR_ARG, "a weight is finite and >= 0");
-    const int64_t chan_tot = r->ss->dev.chan_tot, nstat = 2 * r->ss->dev.n_spec, chunk = mom_chunk_rows(chunk_rows);
-    const bool want_spec = spec_mean || spec_std, want_stat = stat_mean || stat_std;
-    if (rows == 0) {                                         // nothing to predict: every segment is empty
-        for (double *out : {spec_mean, spec_std}) if (out) std::fill(out, out + n_seg * chan_tot, (double)NAN);
-        for (double *out : {stat_mean, stat_std}) if (out) std::fill(out, out + n_seg * nstat, (double)NAN);
-        return NFA_OK;
-    }
-    // S0 and the reference row of every segment: the row of largest weight, the first on ties (an empty segment borrows
-    // a row: its S0 = 0 makes every output NaN whatever that row's spectrum is)
+// The moments of nfa_runner_predict_moments once its arguments are checked, S0 of every segment is summed and the lanes
+// are idle (the caller holds the runner's lock): scratch, reference rows, the chunk loop, the finish and the copies out.
+// The rows are the host's (T.host, with the segments' reference rows in T.ref: copied into the staging chunk by chunk) or
+// lie on the device with equal weights and segments of seg_off[1] rows each (T.dev: the batch reads a chunk's rows where
+// they are -- run_batch without a prior writes none of its rows -- and the reference rows are gathered on the device).
+struct MomRows { const double *host, *dev, *ref; };
+static int mom_reduce(nfa_runner *r, int64_t n_seg, const int32_t *seg_pix, const int64_t *seg_off, MomRows T, const double *weight,
+                      const double *s0, int64_t chunk, double *spec_mean, double *spec_std, double *stat_mean, double *stat_std) {
     const int ndim = r->ndim;
-    std::vector<double> s0((size_t)n_seg), ref_theta((size_t)n_seg * ndim);
-    for (int64_t g = 0; g < n_seg; ++g) {
-        int64_t best = std::min(seg_off[g], rows - 1);
-        double sum = 0.0;
-        for (int64_t i = seg_off[g]; i < seg_off[g + 1]; ++i) {
-            const double w = weight ? weight[i] : 1.0;
-            sum += w;
-            if (w > (weight ? weight[best] : 1.0)) best = i;
-        }
-        s0[(size_t)g] = sum;
-        std::copy(theta + best * ndim, theta + (best + 1) * ndim, ref_theta.begin() + (size_t)g * ndim);
-    }
-    RUNNER_LOCK(r);
-    rc = sync_all_lanes(r); if (rc) return rc;
-    rc = runner_reserve(r, chunk, true); if (rc) return rc;
+    const int64_t chan_tot = r->ss->dev.chan_tot, nstat = 2 * r->ss->dev.n_spec, rows = seg_off[n_seg];
+    const bool want_spec = spec_mean || spec_std, want_stat = stat_mean || stat_std;
+    int rc = runner_reserve(r, chunk, true); if (rc) return rc;
     rc = mom_reserve_rows(r, chunk); if (rc) return rc;
     rc = mom_reserve_segs(r, n_seg); if (rc) return rc;
     MomScratch &m = r->mom;
     hipStream_t st = r->lanes[0];
-    HIP_TRY(hipMemcpyAsync(m.d_s0, s0.data(), sizeof(double) * n_seg, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m.d_s0, s0, sizeof(double) * n_seg, hipMemcpyHostToDevice, st));
     if (want_spec) HIP_TRY(hipMemsetAsync(m.d_acc, 0, sizeof(double) * mom_acc_doubles(n_seg, chan_tot), st));
     if (want_stat) HIP_TRY(hipMemsetAsync(m.d_sacc, 0, sizeof(double) * mom_acc_doubles(n_seg, nstat), st));
     // the reference rows: ordinary predict launches of n_seg rows into ref[n_seg][chan_tot], their statistics taken there
     for (int64_t b0 = 0; b0 < n_seg; b0 += r->cap_B) {
         const int64_t nb = std::min<int64_t>(r->cap_B, n_seg - b0);
-        HIP_TRY(hipMemcpyAsync(r->d_U, ref_theta.data() + b0 * ndim, sizeof(double) * nb * ndim, hipMemcpyHostToDevice, st));
+        if (T.dev) {
+            hipLaunchKernelGGL(moments_first_rows_kernel, dim3((unsigned)((nb * ndim + 255) / 256)), dim3(256), 0, st, T.dev, (long)seg_off[1],
+                               (long)b0, (long)nb, ndim, r->d_U);
+            HIP_TRY(hipGetLastError());
+        } else
+            HIP_TRY(hipMemcpyAsync(r->d_U, T.ref + b0 * ndim, sizeof(double) * nb * ndim, hipMemcpyHostToDevice, st));
         if (seg_pix) HIP_TRY(hipMemcpyAsync(r->d_pix, seg_pix + b0, sizeof(int) * nb, hipMemcpyHostToDevice, st));
         rc = run_batch(r, seg_pix ? r->d_pix : nullptr, r->d_U, r->d_lnL, m.d_ref + b0 * chan_tot, nb, false, 0);
         if (rc) return rc;
@@ -2128,12 +2100,13 @@ int nfa_runner_predict_moments(nfa_runner *r, int64_t n_seg, const int32_t *seg_
             max_rows = std::max<int64_t>(max_rows, h_pieces[k].n);
             if (seg_pix) std::fill(h_pix + h_pieces[k].row0, h_pix + h_pieces[k].row0 + h_pieces[k].n, seg_pix[h_pieces[k].seg]);
         }
-        HIP_TRY(hipMemcpyAsync(r->d_U, theta + a * ndim, sizeof(double) * nb * ndim, hipMemcpyHostToDevice, st));
+        if (T.host) HIP_TRY(hipMemcpyAsync(r->d_U, T.host + a * ndim, sizeof(double) * nb * ndim, hipMemcpyHostToDevice, st));
         if (weight) HIP_TRY(hipMemcpyAsync(m.d_w, weight + a, sizeof(double) * nb, hipMemcpyHostToDevice, st));
         if (seg_pix) HIP_TRY(hipMemcpyAsync(r->d_pix, h_pix, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(m.d_pieces, h_pieces, sizeof(MomPiece) * n_pieces, hipMemcpyHostToDevice, st));
         HIP_TRY(hipEventRecord(m.ev[slot], st));
-        rc = run_batch(r, seg_pix ? r->d_pix : nullptr, r->d_U, r->d_lnL, r->d_spec, nb, false, 0);
+        double *d_rows = T.host ? r->d_U : const_cast<double *>(T.dev) + a * ndim;
+        rc = run_batch(r, seg_pix ? r->d_pix : nullptr, d_rows, r->d_lnL, r->d_spec, nb, false, 0);
         if (rc) return rc;
         const double *d_w = weight ? m.d_w : nullptr;
         if (want_spec) {
@@ -2165,6 +2138,53 @@ int nfa_runner_predict_moments(nfa_runner *r, int64_t n_seg, const int32_t *seg_
     HIP_TRY(hipStreamSynchronize(st));
     r->lane_busy &= ~1u;
     return NFA_OK;
+}
+
+extern "C" {
+
+int nfa_runner_predict_moments(nfa_runner *r, int64_t n_seg, const int32_t *seg_pix, const int64_t *seg_off, const double *theta,
+                               const double *weight, int64_t chunk_rows, double *spec_mean, double *spec_std,
+                               double *stat_mean, double *stat_std) {
+    if (!r) return fail(NFA_ERR_ARG, "null runner");
+    if (n_seg < 0 || n_seg > INT32_MAX) return fail(NFA_ERR_ARG, "the number of segments is out of range");
+    if (!spec_mean && !spec_std && !stat_mean && !stat_std) return fail(NFA_ERR_ARG, "predict_moments: all four outputs are null");
+    if (const char *why = mom_check_chunk_rows(chunk_rows)) return fail(NFA_ERR_ARG, why);
+    if (n_seg == 0) return NFA_OK;
+    if (!seg_off) return fail(NFA_ERR_ARG, "null argument");
+    if (seg_off[0] != 0) return fail(NFA_ERR_ARG, "segment offsets start at 0");
+    for (int64_t g = 0; g < n_seg; ++g)
+        if (seg_off[g + 1] < seg_off[g]) return fail(NFA_ERR_ARG, "segment offsets must not decrease");
+    const int64_t rows = seg_off[n_seg];
+    if (rows > 0 && !theta) return fail(NFA_ERR_ARG, "null argument");
+    int rc = check_pix(r, seg_pix, n_seg); if (rc) return rc;
+    if (weight)
+        for (int64_t i = 0; i < rows; ++i)
+            if (!(weight[i] >= 0.0) || !std::isfinite(weight[i])) return fail(NFA_ERR_ARG, "a weight is finite and >= 0");
+    const int64_t chan_tot = r->ss->dev.chan_tot, nstat = 2 * r->ss->dev.n_spec, chunk = mom_chunk_rows(chunk_rows);
+    if (rows == 0) {                                         // nothing to predict: every segment is empty
+        for (double *out : {spec_mean, spec_std}) if (out) std::fill(out, out + n_seg * chan_tot, (double)NAN);
+        for (double *out : {stat_mean, stat_std}) if (out) std::fill(out, out + n_seg * nstat, (double)NAN);
+        return NFA_OK;
+    }
+    // S0 and the reference row of every segment: the row of largest weight, the first on ties (an empty segment borrows
+    // a row: its S0 = 0 makes every output NaN whatever that row's spectrum is)
+    const int ndim = r->ndim;
+    std::vector<double> s0((size_t)n_seg), ref_theta((size_t)n_seg * ndim);
+    for (int64_t g = 0; g < n_seg; ++g) {
+        int64_t best = std::min(seg_off[g], rows - 1);
+        double sum = 0.0;
+        for (int64_t i = seg_off[g]; i < seg_off[g + 1]; ++i) {
+            const double w = weight ? weight[i] : 1.0;
+            sum += w;
+            if (w > (weight ? weight[best] : 1.0)) best = i;
+        }
+        s0[(size_t)g] = sum;
+        std::copy(theta + best * ndim, theta + (best + 1) * ndim, ref_theta.begin() + (size_t)g * ndim);
+    }
+    RUNNER_LOCK(r);
+    rc = sync_all_lanes(r); if (rc) return rc;
+    return mom_reduce(r, n_seg, seg_pix, seg_off, MomRows{theta, nullptr, ref_theta.data()}, weight, s0.data(), chunk,
+                      spec_mean, spec_std, stat_mean, stat_std);
 }
 
 int nfa_runner_row_statistics(nfa_runner *r, const int32_t *pix, const double *theta, int64_t B, double *peak, double *total) {

@@ -3,7 +3,9 @@
 // likelihood batch.  The contract is the head of nfa_ensemble_plan.h.  f64 throughout, plain products and sums (the build
 // has -ffp-contract=off), the nested sampler's counter-based random numbers; no atomics and no order that depends on
 // scheduling: the same arguments give the same bits.  One half-step is ens_propose_kernel, the likelihood launches over
-// its P W/2 rows, ens_accept_kernel; a step ends with ens_trace_kernel and, where it is kept, ens_keep_kernel.
+// its P W/2 rows, ens_accept_kernel; a step ends with ens_trace_kernel and, where it is kept, ens_keep_kernel.  The chain
+// is reduced where it lies: ens_summary_kernel, ens_hist_kernel (whose integer counts alone meet in LDS adds: the same in
+// any order), ens_cov_kernel, and the moments of its model spectra through the engine's mom_reduce.
 // (Included after nfa_sampler.h: ns_stream, ns_uniform_of.)
 #pragma once
 
@@ -132,6 +134,23 @@ __device__ __forceinline__ double ens_block_sum(double v, double *red) {
 // (value, index) a before b: the larger value, the smaller index on ties
 __device__ __forceinline__ bool ens_before(double va, long ia, double vb, long ib) { return va > vb || (va == vb && ia < ib); }
 
+// The row of largest lnL among L[0 .. N), the first on ties (row 0 where every lnL is NaN), known to every thread of the
+// workgroup: a strided scan, a butterfly inside every wave, the waves' candidates through redv[], redi[] in wave order.
+__device__ __forceinline__ long ens_best_row(const double *__restrict__ L, long N, double *redv, long *redi) {
+    const int t = (int)threadIdx.x, T = (int)blockDim.x, lane = t & 63, wave = t >> 6, nw = T >> 6;
+    double bv = -INFINITY; long bi = N;
+    for (long i = t; i < N; i += T) { const double v = L[i]; if (ens_before(v, i, bv, bi)) { bv = v; bi = i; } }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(bv, off); const long oi = __shfl_xor(bi, off);
+        if (ens_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { redv[wave] = bv; redi[wave] = bi; }
+    __syncthreads();
+    bv = redv[0]; bi = redi[0];
+    for (int w = 1; w < nw; ++w) if (ens_before(redv[w], redi[w], bv, bi)) { bv = redv[w]; bi = redi[w]; }
+    return bi >= N ? 0 : bi;
+}
+
 // Workgroup = pixel; N = n_keep W kept samples in (keep, walker) order.  best[p][0 .. DT] = theta and lnL of the row of
 // largest lnL, the first on ties.  Per parameter c, with d_i = x_i - best_c: summary[p][c] = (best_c + S1 / N,
 // sqrt(max(S2 / N - (S1 / N)^2, 0))) -- moments of differences, for the reason DESIGN 4.21 gives; one sample: std 0.  With
@@ -146,20 +165,9 @@ void ens_summary_kernel(const double *__restrict__ chain_theta, const double *__
     double *red = ens_sm, *redv = ens_sm + 16, *s = ens_sm + ENS_RED_DOUBLES;
     long *redi = (long *)(ens_sm + 32);
     const long p = blockIdx.x;
-    const int t = (int)threadIdx.x, T = (int)blockDim.x, lane = t & 63, wave = t >> 6, nw = T >> 6;
+    const int t = (int)threadIdx.x, T = (int)blockDim.x;
     const double *X = chain_theta + p * N * DT, *L = chain_lnL + p * N;
-    // the best row
-    double bv = -INFINITY; long bi = N;
-    for (long i = t; i < N; i += T) { const double v = L[i]; if (ens_before(v, i, bv, bi)) { bv = v; bi = i; } }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(bv, off); const long oi = __shfl_xor(bi, off);
-        if (ens_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { redv[wave] = bv; redi[wave] = bi; }
-    __syncthreads();
-    bv = redv[0]; bi = redi[0];
-    for (int w = 1; w < nw; ++w) if (ens_before(redv[w], redi[w], bv, bi)) { bv = redv[w]; bi = redi[w]; }
-    if (bi >= N) bi = 0;                                       // (every lnL NaN)
+    const long bi = ens_best_row(L, N, redv, redi);
     if (t <= DT) best[p * (DT + 1) + t] = t < DT ? X[bi * DT + t] : L[bi];
     const double inv_n = 1.0 / (double)N;
     for (int c = 0; c < DT; ++c) {
@@ -198,6 +206,86 @@ void ens_summary_kernel(const double *__restrict__ chain_theta, const double *__
     }
 }
 
+// ---- the products of a chain -------------------------------------------------------------------------------------
+// Workgroup = (pixel p, parameter c) = blockIdx.x / DT, blockIdx.x % DT of a slab of pixels whose chain starts at chain_theta.
+// The parameter's nb + 1 edges and nb + 1 32-bit counters (the last: outside) sit in LDS.  A thread takes the samples t,
+// t + T, ... of the pixel's N (stride DT doubles, as the summary reads them); a sample inside [e_0, e_nb] finds the last
+// edge not above it among e_0 .. e_nb-1 by a binary search without a branch on the data -- so x == e_nb lands in the last
+// bin, as np.histogram puts it -- and counts there with an integer LDS add: integer counts are the same in any order.  The
+// workgroup is the one writer of its nb counts, widened to 64 bits; no global atomics.  (The host has checked N < 2^32.)
+__global__ __launch_bounds__(256)
+void ens_hist_kernel(const double *__restrict__ chain_theta, long N, int DT, const double *__restrict__ edges, int nb,
+                     long *__restrict__ counts, long *__restrict__ outside) {
+    extern __shared__ __attribute__((aligned(16))) double ens_hist_sm[];
+    double *ed = ens_hist_sm;
+    unsigned *cnt = (unsigned *)(ens_hist_sm + nb + 1);
+    const long p = blockIdx.x / (unsigned)DT;
+    const int c = (int)(blockIdx.x - (unsigned)p * (unsigned)DT), t = (int)threadIdx.x, T = (int)blockDim.x;
+    for (int b = t; b <= nb; b += T) { ed[b] = edges[(long)c * (nb + 1) + b]; cnt[b] = 0u; }
+    __syncthreads();
+    const double *X = chain_theta + p * N * DT + c;
+    const double lo = ed[0], hi = ed[nb];
+    unsigned out = 0u;
+    for (long i = t; i < N; i += T) {
+        const double x = X[i * DT];
+        if (!(x >= lo && x <= hi)) { out += 1u; continue; }   // (a NaN too)
+        int b = 0, n = nb;                                     // the last edge <= x lies in [b, b + n)
+        while (n > 1) {
+            const int half = n >> 1;
+            b = ed[b + half] <= x ? b + half : b;
+            n -= half;
+        }
+        atomicAdd(&cnt[b], 1u);
+    }
+    if (out) atomicAdd(&cnt[nb], out);
+    __syncthreads();
+    const long o = p * DT + c;
+    for (int b = t; b < nb; b += T) counts[o * nb + b] = (long)cnt[b];
+    if (t == 0) outside[o] = (long)cnt[nb];
+}
+
+// Workgroup = pixel of a slab whose chain starts at chain_theta, chain_lnL; cov[p][DT][DT].  About the best row (ens_best_row,
+// the summary's): first every parameter's S_a and S_aa -> its mean of differences m_a = S_a / N into LDS and the diagonal
+// max(S_aa / N - m_a^2, 0); then every pair a < b: cov_ab = S_ab / N - m_a m_b, written at [a][b] and [b][a].  Every sum is
+// a strided scan and ens_block_sum: a fixed shape, no atomics.  A parameter that is constant has d = 0 throughout: an exact
+// zero row and column.
+__global__ __launch_bounds__(256)
+void ens_cov_kernel(const double *__restrict__ chain_theta, const double *__restrict__ chain_lnL, long N, int DT, double *__restrict__ cov) {
+    __shared__ double red[4], redv[4], m[NS_MAXD];
+    __shared__ long redi[4];
+    const long p = blockIdx.x;
+    const int t = (int)threadIdx.x, T = (int)blockDim.x;
+    const double *X = chain_theta + p * N * DT, *L = chain_lnL + p * N;
+    double *C = cov + p * DT * DT;
+    const double *R = X + ens_best_row(L, N, redv, redi) * DT;
+    const double n = (double)N;
+    for (int a = 0; a < DT; ++a) {
+        const double ra = R[a];
+        double s1 = 0.0, s2 = 0.0;
+        for (long i = t; i < N; i += T) { const double d = X[i * DT + a] - ra; s1 += d; s2 += d * d; }
+        s1 = ens_block_sum(s1, red);
+        s2 = ens_block_sum(s2, red);
+        if (t == 0) {
+            const double ma = s1 / n, var = s2 / n - ma * ma;
+            m[a] = ma;
+            C[a * DT + a] = var > 0.0 ? var : 0.0;
+        }
+    }
+    __syncthreads();
+    for (int a = 0; a < DT; ++a)
+        for (int b = a + 1; b < DT; ++b) {
+            const double ra = R[a], rb = R[b];
+            double s = 0.0;
+            for (long i = t; i < N; i += T) s += (X[i * DT + a] - ra) * (X[i * DT + b] - rb);
+            s = ens_block_sum(s, red);
+            if (t == 0) {
+                const double v = s / n - m[a] * m[b];
+                C[a * DT + b] = v;
+                C[b * DT + a] = v;
+            }
+        }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------
 // Everything an ensemble holds on the device belongs to it: `bufs` lives as long as the ensemble, `run_bufs` (chain and
 // trace) as long as the last run.  The likelihood batch works on the ensemble's own rows, as the nested sampler's does on
@@ -206,6 +294,7 @@ struct nfa_ensemble {
     nfa_runner *r = nullptr;
     EnsDev d = {};
     std::vector<int> fm;                 // sampled slots
+    std::vector<int32_t> h_pix;          // [P] the cube pixels, as d.pix holds them
     bool has_pix = false;
     int *d_start_pix = nullptr;          // [P][W] cube pixel of every start row
     std::vector<void *> bufs, run_bufs;
@@ -261,7 +350,9 @@ static int ens_create_on_device(nfa_ensemble *e, const int32_t *pix, const std::
         (rc = ens_alloc(e->bufs, &e->d_quant, P * DT * NFA_ENS_MAX_Q)) || (rc = ens_alloc(e->bufs, &e->d_levels, (size_t)NFA_ENS_MAX_Q)))
         return rc;
     d.fmap = fmap; d.pix = dpix;
-    std::vector<int> h_pix(P, 0), h_start(P * W, 0);
+    std::vector<int32_t> &h_pix = e->h_pix;
+    std::vector<int> h_start(P * W, 0);
+    h_pix.assign(P, 0);
     for (size_t p = 0; p < P; ++p) {
         h_pix[p] = pix ? pix[p] : 0;
         for (size_t w = 0; w < W; ++w) h_start[p * W + w] = h_pix[p];
@@ -464,6 +555,100 @@ int nfa_ensemble_summary(nfa_ensemble *e, const double *levels, int n_levels, do
     rc = work();
     if (rc) return ens_abandon(r, rc);
     return NFA_OK;
+}
+
+int nfa_ensemble_histogram(nfa_ensemble *e, const double *edges, int n_bins, int64_t *counts, int64_t *outside) {
+    if (!e || !counts) return fail(NFA_ERR_ARG, "null argument");
+    if (!e->chain_theta) return fail(NFA_ERR_STATE, "ensemble: no run yet");
+    const EnsDev &d = e->d;
+    const int64_t N = e->n_keep * d.W, P = d.P, DT = d.DT;
+    if (const char *why = ens_check_edges(edges, d.DT, n_bins, N)) return fail(NFA_ERR_ARG, why);
+    nfa_runner *r = e->r;
+    RUNNER_LOCK(r);
+    int rc = sync_all_lanes(r); if (rc) return ens_abandon(r, rc);
+    hipStream_t st = r->lanes[0];
+    const int64_t slab = std::min(P, ens_slab_pixels(ens_hist_pixel_bytes(d.DT, n_bins)));
+    std::vector<void *> took;
+    double *d_edges = nullptr;
+    long *d_counts = nullptr, *d_out = nullptr;
+    std::vector<int64_t> h_out(outside ? 0 : (size_t)(slab * DT));        // (the copy out needs a place either way)
+    auto work = [&]() -> int {
+        int rcw;
+        if ((rcw = ens_alloc(took, &d_edges, (size_t)(DT * (n_bins + 1)))) || (rcw = ens_alloc(took, &d_counts, (size_t)(slab * DT * n_bins))) ||
+            (rcw = ens_alloc(took, &d_out, (size_t)(slab * DT))))
+            return rcw;
+        HIP_TRY(hipMemcpyAsync(d_edges, edges, sizeof(double) * DT * (n_bins + 1), hipMemcpyHostToDevice, st));
+        for (int64_t p0 = 0; p0 < P; p0 += slab) {
+            const int64_t np = std::min(slab, P - p0);
+            const EnsGeom G = ens_hist_geom(np, d.DT, N, n_bins);
+            hipLaunchKernelGGL(ens_hist_kernel, dim3(G.grid), dim3(G.threads), G.lds, st, (const double *)e->chain_theta + p0 * N * DT, (long)N,
+                               d.DT, (const double *)d_edges, n_bins, d_counts, d_out);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(counts + p0 * DT * n_bins, d_counts, sizeof(long) * np * DT * n_bins, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(outside ? outside + p0 * DT : h_out.data(), d_out, sizeof(long) * np * DT, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));                 // the slab's scratch is free for the next one
+        }
+        return NFA_OK;
+    };
+    rc = work();
+    if (rc) rc = ens_abandon(r, rc);
+    ens_free(took);
+    return rc;
+}
+
+int nfa_ensemble_covariance(nfa_ensemble *e, double *cov) {
+    if (!e || !cov) return fail(NFA_ERR_ARG, "null argument");
+    if (!e->chain_theta) return fail(NFA_ERR_STATE, "ensemble: no run yet");
+    const EnsDev &d = e->d;
+    const int64_t N = e->n_keep * d.W, P = d.P, DT = d.DT;
+    nfa_runner *r = e->r;
+    RUNNER_LOCK(r);
+    int rc = sync_all_lanes(r); if (rc) return ens_abandon(r, rc);
+    hipStream_t st = r->lanes[0];
+    const int64_t slab = std::min(P, ens_slab_pixels(ens_cov_pixel_bytes(d.DT)));
+    std::vector<void *> took;
+    double *d_cov = nullptr;
+    auto work = [&]() -> int {
+        int rcw = ens_alloc(took, &d_cov, (size_t)(slab * DT * DT)); if (rcw) return rcw;
+        for (int64_t p0 = 0; p0 < P; p0 += slab) {
+            const int64_t np = std::min(slab, P - p0);
+            const EnsGeom G = ens_cov_geom(np, N);
+            hipLaunchKernelGGL(ens_cov_kernel, dim3(G.grid), dim3(G.threads), 0, st, (const double *)e->chain_theta + p0 * N * DT,
+                               (const double *)e->chain_lnL + p0 * N, (long)N, d.DT, d_cov);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(cov + p0 * DT * DT, d_cov, sizeof(double) * np * DT * DT, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return NFA_OK;
+    };
+    rc = work();
+    if (rc) rc = ens_abandon(r, rc);
+    ens_free(took);
+    return rc;
+}
+
+int nfa_ensemble_moments(nfa_ensemble *e, int64_t chunk_rows, double *spec_mean, double *spec_std, double *stat_mean, double *stat_std) {
+    if (!e) return fail(NFA_ERR_ARG, "null ensemble");
+    if (!e->chain_theta) return fail(NFA_ERR_STATE, "ensemble: no run yet");
+    if (!spec_mean && !spec_std && !stat_mean && !stat_std) return fail(NFA_ERR_ARG, "predict_moments: all four outputs are null");
+    if (const char *why = mom_check_chunk_rows(chunk_rows)) return fail(NFA_ERR_ARG, why);
+    const int64_t N = e->n_keep * e->d.W, P = e->d.P;
+    // nfa_runner_predict_moments' arguments: a segment of N rows per pixel, equal weights, so S0 = N
+    std::vector<int64_t> seg_off((size_t)P + 1);
+    for (int64_t g = 0; g <= P; ++g) seg_off[(size_t)g] = g * N;
+    const std::vector<double> s0((size_t)P, (double)N);
+    nfa_runner *r = e->r;
+    RUNNER_LOCK(r);
+    int rc = sync_all_lanes(r);
+    if (!rc) rc = mom_reduce(r, P, e->has_pix ? e->h_pix.data() : nullptr, seg_off.data(), MomRows{nullptr, e->chain_theta, nullptr}, nullptr,
+                             s0.data(), mom_chunk_rows(chunk_rows), spec_mean, spec_std, stat_mean, stat_std);
+    if (rc) return ens_abandon(r, rc);
+    return NFA_OK;
+}
+
+int64_t nfa_ensemble_moments_bytes(int64_t n_pix, int64_t chan_tot, int n_spec) {
+    if (n_pix < 0 || chan_tot < 0 || n_spec < 0) return -1;
+    return ens_moments_bytes(n_pix, chan_tot, n_spec);
 }
 
 }  // extern "C"

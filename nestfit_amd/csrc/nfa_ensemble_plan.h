@@ -1,6 +1,6 @@
 // nfa_ensemble_plan.h -- the ensemble sampler (nfa_ensemble_*, nfa_ensemble.h), planned on the host: its limits and the
 // tag of its random streams, the checks of its arguments, which steps are kept, the bytes a run holds on the device, the
-// launch geometries and the LDS of the summary.
+// launch geometries and the LDS of the summary, and the same for the products of a chain (histogram, covariance, moments).
 //
 // Standard C++17 without a HIP include, like nfa_lsq_plan.h and nfa_moments_plan.h: a host compiler builds this header
 // alone, and tests/test_ensemble_cpu.py checks it without a GPU.  Arithmetic only.  Errors travel as `const char *`, in
@@ -15,6 +15,14 @@
 //     proposal y_d = u_j,d + z (u_k,d - u_j,d)                     (inside: every y_d in (0, 1))
 //     accept   inside, lnL_y finite, and log(r_2) < (D - 1) log(z) + (lnL_y - lnL_k)
 // The state after step s is kept iff s > n_burn and (s - n_burn) % thin == 0.
+//
+// The products of the last run's chain; a pixel has N = n_keep W samples in (keep, walker) order.
+//     histogram   column c on edges[c][0 .. n_bins], strictly increasing and finite: bin b counts edges[b] <= x < edges[b + 1],
+//                 the last bin x == edges[n_bins] too; a NaN and an x beyond the edges count as outside and in no bin
+//                 (np.histogram of an edge array)
+//     covariance  about the best row b of the summary: d_i,a = x_i,a - x_b,a, S_a = sum d_i,a, S_ab = sum d_i,a d_i,b,
+//                 cov_ab = S_ab / N - (S_a / N)(S_b / N) for a <= b, mirrored; the diagonal not below 0
+//     moments     nfa_runner_predict_moments over the chain where it lies: a segment per pixel, equal weights
 #pragma once
 
 #include <cstddef>
@@ -23,6 +31,7 @@
 #define NFA_ENS_MAX_WALKERS 512          // include/nestfit_amd.h says the same for these three
 #define NFA_ENS_MAX_Q       8            // quantile levels of a summary
 #define NFA_ENS_MAX_SORT    8192         // kept samples per pixel a summary sorts: 64 KB of LDS
+#define NFA_ENS_MAX_BINS    1024         // bins of a histogram: its edges and counts are 8 KB + 4 KB of LDS
 // The streams of a run: ns_stream(seed, pixel, NFA_ENS_TAG + 2 step + half).  The nested sampler's third stream argument
 // is a count of proposals (below 2^61), NS_FRAME_SEED (2^31) or NS_TAG_LIVE + live point (2^62 ..); a run of 2^59 steps
 // stays inside [2^61, 2^62).
@@ -31,6 +40,8 @@
 #define ENS_PIECE_ROWS      (1 << 20)    // rows of one likelihood launch at most; a larger half-step is cut into pieces
 #define ENS_STEPS_MAX       (1ll << 40)
 #define ENS_RED_DOUBLES     64           // head of the summary's LDS: the partial results of up to 16 waves, three arrays
+#define ENS_SLAB_BYTES      (8 << 20)    // device scratch of a histogram or covariance call: the pixels go through it in slabs
+#define ENS_SAMPLES_MAX     (1ll << 32)  // kept samples per pixel a histogram counts: its LDS counters are 32 bits wide
 
 // ---- argument checks: null, or why the argument is refused
 inline const char *ens_check_walkers(int n_walkers, int n_sampled) {
@@ -59,6 +70,20 @@ inline const char *ens_check_levels(const double *levels, int n_levels, int64_t 
     if (n_levels > 0 && n_samples > NFA_ENS_MAX_SORT) return "ensemble: quantiles take NFA_ENS_MAX_SORT = 8192 kept samples per pixel at most";
     return nullptr;
 }
+// the edges[ndim][n_bins + 1] of a histogram over n_samples kept samples per pixel
+inline const char *ens_check_edges(const double *edges, int ndim, int n_bins, int64_t n_samples = 0) {
+    if (n_bins < 1 || n_bins > NFA_ENS_MAX_BINS) return "ensemble: a histogram takes 1 .. NFA_ENS_MAX_BINS = 1024 bins";
+    if (!edges) return "ensemble: bins are counted but their edges are not given";
+    for (int c = 0; c < ndim; ++c) {
+        const double *e = edges + (size_t)c * (size_t)(n_bins + 1);
+        for (int b = 0; b <= n_bins; ++b) {
+            if (!(e[b] - e[b] == 0.0)) return "ensemble: a bin edge is not finite";
+            if (b > 0 && !(e[b] > e[b - 1])) return "ensemble: the bin edges of a parameter must increase strictly";
+        }
+    }
+    if (n_samples >= ENS_SAMPLES_MAX) return "ensemble: a histogram counts fewer than 2^32 kept samples per pixel";
+    return nullptr;
+}
 
 // ---- device bytes of an ensemble of P pixels: what create allocates (state: the walkers, a half-step's proposal rows,
 // the counters and the summary's outputs), and what a run of n_steps steps with n_keep kept adds (chain, trace)
@@ -75,6 +100,14 @@ inline EnsBytes ens_bytes(int64_t P, int W, int ndim, int D, int64_t n_steps, in
     B.total = B.state + B.chain + B.trace;
     return B;
 }
+// A histogram and a covariance hold ENS_SLAB_BYTES of device scratch whatever the number of pixels (a lone pixel whose
+// outputs are larger: that pixel's), for the length of the call: pixels [p0, p0 + ens_slab_pixels) go through it at a time.
+// So ens_bytes has nothing to add for them.  The moments use the runner's scratch of nfa_runner_predict_moments, which
+// does grow with the pixels: reference rows and two accumulator planes of chan_tot + 2 n_spec columns, and S0.
+inline int64_t ens_slab_pixels(int64_t bytes_per_pixel) { return bytes_per_pixel >= ENS_SLAB_BYTES ? 1 : ENS_SLAB_BYTES / bytes_per_pixel; }
+inline int64_t ens_hist_pixel_bytes(int ndim, int n_bins) { return (int64_t)ndim * (n_bins + 1) * 8; }     // counts and outside
+inline int64_t ens_cov_pixel_bytes(int ndim) { return (int64_t)ndim * ndim * 8; }
+inline int64_t ens_moments_bytes(int64_t P, int64_t chan_tot, int n_spec) { return P * (3 * (chan_tot + 2 * (int64_t)n_spec) + 1) * 8; }
 
 // ---- launch geometries
 struct EnsGeom { unsigned grid, threads; size_t lds; };
@@ -96,3 +129,15 @@ inline EnsGeom ens_summary_geom(int64_t P, int64_t n_samples, int n_levels) {
     t = t < 64 ? 64 : t > 1024 ? 1024 : t;
     return EnsGeom{(unsigned)P, (unsigned)t, ens_summary_lds(n_samples, n_levels)};
 }
+// histogram: a workgroup per (pixel, parameter), pixel-major; a thread per strided sample, whole waves up to four.  LDS:
+// the parameter's n_bins + 1 edges, then n_bins + 1 32-bit counters (the last one counts outside).
+inline unsigned ens_scan_threads(int64_t n_samples) {
+    const int64_t t = (n_samples + 63) / 64 * 64;
+    return (unsigned)(t < 64 ? 64 : t > 256 ? 256 : t);
+}
+inline size_t ens_hist_lds(int n_bins) { return (sizeof(double) + sizeof(uint32_t)) * (size_t)(n_bins + 1); }
+inline EnsGeom ens_hist_geom(int64_t P, int ndim, int64_t n_samples, int n_bins) {
+    return EnsGeom{(unsigned)(P * ndim), ens_scan_threads(n_samples), ens_hist_lds(n_bins)};
+}
+// covariance: a workgroup per pixel, the same threads; its LDS is static
+inline EnsGeom ens_cov_geom(int64_t P, int64_t n_samples) { return EnsGeom{(unsigned)P, ens_scan_threads(n_samples), 0}; }

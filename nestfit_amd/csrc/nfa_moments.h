@@ -108,3 +108,14 @@ void moments_finish_kernel(double *__restrict__ acc, const double *__restrict__ 
     acc[k] = ref[k] + m1;
     acc[n_seg * ncol + k] = var < 0.0 ? 0.0 : sqrt(var);
 }
+
+// Row g of out[n][ndim] = the first row of segment first + g of theta[.][ndim] on the device, whose segments are seg_rows
+// rows each: the reference rows where the rows of a call lie in HBM with equal weights (a segment's row of largest weight
+// is then its first).  A thread per double.
+__global__ __launch_bounds__(256)
+void moments_first_rows_kernel(const double *__restrict__ theta, long seg_rows, long first, long n, int ndim, double *__restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * ndim) return;
+    const long g = i / ndim, k = i - g * ndim;
+    out[i] = theta[(first + g) * seg_rows * ndim + k];
+}

@@ -236,6 +236,7 @@ class CubeRunner(RunnerSurface):
 
     def sample_posterior(self, pix, **kw):
         """The posteriors of the pixels pix[P] at the runner's component count by ensemble MCMC on the device: an
-        `EnsembleResult` of one row per pixel (`nestfit_amd.ensemble.sample_pixels`' keywords)."""
+        `EnsembleResult` of one row per pixel (`nestfit_amd.ensemble.sample_pixels`' keywords; `par_bins`,
+        `covariance`, `moments`: the marginal histograms, parameter covariances and model moments of the chain)."""
         return _calls._sample_posterior(self, np.ascontiguousarray(pix, dtype=np.int32), **kw)
 

@@ -6,7 +6,10 @@ bars under every prior kind, model and likelihood option, without an evidence.
 record (`EnsState`, fields named like `EnsDev`'s) and one function per stage of the device -- `_create` (nfa_ensemble_create),
 `_propose` (ens_propose_kernel), `_accept` (the likelihood batch and ens_accept_kernel), `_trace` (ens_trace_kernel), `_keep`
 (ens_keep_kernel) -- with the same arithmetic and the same random numbers (`nested._uniform`), so the same arguments give
-the same run.  `summarize` is the twin of ens_summary_kernel.  `sample_pixels` and `sample_cube` drive the device."""
+the same run.  `summarize` is the twin of ens_summary_kernel, `pdf_counts` of ens_hist_kernel (equal to the bit) and
+`covariance_of` of ens_cov_kernel (the same formula summed in another order).  `sample_pixels` and `sample_cube` drive the
+device; the products of a chain -- marginal histograms, parameter covariances, moments of the model spectra --
+are reduced there, so the chain need not leave it."""
 import ctypes as C
 import math
 import types
@@ -19,6 +22,7 @@ from .nested import LOG_ZERO, _U64, _uniform
 # csrc/nfa_ensemble_plan.h (tests/test_ensemble_cpu.py compares them with the header's)
 ENS_TAG = 1 << 61
 MAX_WALKERS, MAX_Q, MAX_SORT, A_MAX = 512, 8, 8192, 16.0
+MAX_BINS = 1024
 
 
 class EnsState(types.SimpleNamespace):
@@ -216,6 +220,49 @@ def summarize(chain_theta, chain_lnL, levels=()):
     return best + m, np.sqrt(np.maximum(var, 0.0)), best, L[np.arange(P), row], quant
 
 
+def pdf_counts(chain_theta, edges):
+    """ens_hist_kernel in numpy, on chain_theta[P, n_keep, W, ndim] and edges[ndim, n_bins + 1]: (counts int64[P, ndim, n_bins],
+    outside int64[P, ndim]) -- `np.histogram(x, bins=edges[c])[0]` of every (pixel, column), and the samples it left out (a NaN,
+    an x beyond the edges)."""
+    P, n_keep, W, ndim = chain_theta.shape
+    edges = np.asarray(edges, dtype=np.float64)
+    if edges.ndim != 2 or edges.shape[0] != ndim or edges.shape[1] < 2:
+        raise ValueError('edges must be [ndim, n_bins + 1]')
+    X = chain_theta.reshape(P, n_keep * W, ndim)
+    counts = np.empty((P, ndim, edges.shape[1] - 1), dtype=np.int64)
+    for p in range(P):
+        for c in range(ndim):
+            counts[p, c] = np.histogram(X[p, :, c], bins=edges[c])[0]
+    return counts, n_keep * W - counts.sum(axis=2)
+
+
+def covariance_of(chain_theta, chain_lnL, dtype=np.float64):
+    """ens_cov_kernel's formula in numpy, computed in `dtype`: cov[P, ndim, ndim] of chain_theta[P, n_keep, W, ndim] about every
+    pixel's best row (the first of largest chain_lnL[P, n_keep, W]): with d the differences from that row, S_ab / N - (S_a / N)
+    (S_b / N), the diagonal not below 0 -- a population covariance of differences, for the reason DESIGN 4.21 gives."""
+    P, n_keep, W, ndim = chain_theta.shape
+    N = n_keep * W
+    X, L = chain_theta.reshape(P, N, ndim).astype(dtype), chain_lnL.reshape(P, N)
+    row = np.argmax(np.where(np.isnan(L), -np.inf, L), axis=1)
+    d = X - X[np.arange(P), row][:, None, :]
+    m = d.sum(axis=1) / dtype(N)
+    cov = np.einsum('pia,pib->pab', d, d) / dtype(N) - m[:, :, None] * m[:, None, :]
+    k = np.arange(ndim)
+    cov[:, k, k] = np.maximum(cov[:, k, k], 0)
+    return cov
+
+
+def bin_edges(utrans, ncomp, n_bins):
+    """edges[ndim, n_bins + 1] for `histogram`: per column of a theta row (the chain's layout, `lsq.prior_box`'s)
+    `np.linspace(lower, upper, n_bins + 1)` over the box of the priors.  A column whose box is a point (a constant parameter)
+    gets the box of width 1 around it: edges have to increase."""
+    from .lsq import prior_box
+    lower, upper = prior_box(utrans, ncomp)
+    point = ~(upper > lower)
+    lower, upper = np.where(point, lower - 0.5, lower), np.where(point, upper + 0.5, upper)
+    return np.ascontiguousarray(np.linspace(lower, upper, int(n_bins) + 1, axis=1))
+
+
 def autocorr_time(x, c=5.0):
     """Integrated autocorrelation time of the series x[n] (in its steps) by Sokal's windowed estimator: tau(M) = 1 + 2
     sum_{t=1..M} rho_t at the smallest M with M >= c tau(M); NaN for a constant series."""
@@ -260,8 +307,9 @@ class _Handle:
 
 
 class DeviceEnsemble:
-    """The C calls of an ensemble on arrays: `run`, `counts`, `state`, `trace`, `chain`, `summary`.  pix: int32[P] cube pixels,
-    or None for the pixel of a one-pixel runner (then P = 1); u0[P, W, ndim]."""
+    """The C calls of an ensemble on arrays: `run`, `counts`, `state`, `trace`, `chain`, `summary`, and the products of the
+    chain `histogram`, `covariance`, `moments`.  pix: int32[P] cube pixels, or None for the pixel of a one-pixel runner (then
+    P = 1); u0[P, W, ndim]."""
 
     def __init__(self, runner, pix, n_walkers, u0, free_mask=None):
         self.ndim, self.W = int(runner.ndim), int(n_walkers)
@@ -274,6 +322,7 @@ class DeviceEnsemble:
         u0 = np.ascontiguousarray(u0, dtype=np.float64)
         if u0.shape != (self.P, self.W, self.ndim):
             raise ValueError('the start must be [n_pix, n_walkers, ndim]')
+        self.n_spec, self.n_chan_tot = int(runner.n_spec), int(runner._ss.chan_tot)
         self._h = _Handle(runner, self.pix, n_walkers, fm, u0)
         self.n_steps = self.n_keep = 0
 
@@ -315,12 +364,43 @@ class DeviceEnsemble:
                                                     _ffi.dptr(best), _ffi.dptr(quant) if nq else None))
         return summ[:, :, 0].copy(), summ[:, :, 1].copy(), best[:, :self.ndim].copy(), best[:, self.ndim].copy(), quant
 
+    def histogram(self, edges):
+        """(counts int64[P, ndim, n_bins], outside int64[P, ndim]) of the chain on edges[ndim, n_bins + 1], as `pdf_counts`
+        returns them, counted on the device."""
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if edges.ndim != 2 or edges.shape[0] != self.ndim:
+            raise ValueError('edges must be [ndim, n_bins + 1]')
+        n_bins = edges.shape[1] - 1
+        counts, outside = np.empty((self.P, self.ndim, max(n_bins, 0)), dtype=np.int64), np.empty((self.P, self.ndim), dtype=np.int64)
+        _ffi.check(_ffi.load().nfa_ensemble_histogram(self._h.handle, _ffi.dptr(edges), n_bins, counts.ctypes.data_as(_ffi._lp),
+                                                      outside.ctypes.data_as(_ffi._lp)))
+        return counts, outside
+
+    def covariance(self):
+        """cov[P, ndim, ndim] of the chain about every pixel's best row, as `covariance_of` defines it, summed on the device."""
+        cov = np.empty((self.P, self.ndim, self.ndim))
+        _ffi.check(_ffi.load().nfa_ensemble_covariance(self._h.handle, _ffi.dptr(cov)))
+        return cov
+
+    def moments(self, chunk_rows=None, want_spectra=True):
+        """The `PosteriorMoments` of the runner's `predict_moments` over every pixel's kept samples with equal weights, one
+        segment per pixel, bit for bit -- from the chain where it lies."""
+        from .moments import PosteriorMoments
+        mean = np.empty((self.P, self.n_chan_tot)) if want_spectra else None
+        std = np.empty((self.P, self.n_chan_tot)) if want_spectra else None
+        smean, sstd = np.empty((self.P, self.n_spec, 2)), np.empty((self.P, self.n_spec, 2))
+        opt = lambda a: None if a is None else _ffi.dptr(a)
+        _ffi.check(_ffi.load().nfa_ensemble_moments(self._h.handle, 0 if chunk_rows is None else int(chunk_rows), opt(mean), opt(std),
+                                                    _ffi.dptr(smean), _ffi.dptr(sstd)))
+        return PosteriorMoments(mean, std, smean[:, :, 0].copy(), sstd[:, :, 0].copy(), smean[:, :, 1].copy(), sstd[:, :, 1].copy())
+
 
 class EnsembleResult(types.SimpleNamespace):
     """`sample_pixels`' outputs, one row per pixel: mean, std, best [P, ndim], best_lnL [P], quantiles [P, ndim, len(levels)],
     levels; acceptance (accepted / proposed), outside (the share of proposals outside the unit cube), n_evals [P]; tau, n_eff
     [P, D] per sampled dimension; trace [P, n_steps, D + 1]; with `keep_chain` theta [P, n_keep, W, ndim] and lnL [P, n_keep,
-    W]."""
+    W].  The products asked for, None otherwise: pdf_counts int64[P, ndim, n_bins], pdf_outside int64[P, ndim], pdf_bins [ndim,
+    n_bins] (the bins' centres), cov [P, ndim, ndim], model (a `PosteriorMoments` of one row per pixel)."""
 
     def chain(self):
         """(theta, lnL) of the kept samples: the fetched copy, or fetched now from the device."""
@@ -332,14 +412,17 @@ class EnsembleResult(types.SimpleNamespace):
 
     def moments(self, runner, chunk_rows=None, want_spectra=True):
         """`predict_moments` over every pixel's kept samples with equal weights: a `PosteriorMoments` record, one segment per
-        pixel.  The chain goes through the host (the moments call takes host rows)."""
+        pixel.  While the ensemble is open the chain is reduced where it lies (`DeviceEnsemble.moments`); with only a fetched
+        chain left its rows go through the host.  The same bits either way."""
+        from . import _calls
+        if self._ensemble is not None:
+            return self._ensemble.moments(chunk_rows, want_spectra)
         theta, _ = self.chain()
         P, n_keep, W, ndim = theta.shape
         rows = theta.reshape(P * n_keep * W, ndim)
-        if self.pix is None:
-            return runner.predict_moments(rows)
         offsets = np.arange(P + 1, dtype=np.int64) * (n_keep * W)
-        return runner.predict_moments(self.pix, offsets, rows, chunk_rows=chunk_rows, want_spectra=want_spectra)
+        return _calls._predict_moments(runner._run.handle, self.pix, offsets, _calls.parameter_rows(runner, rows), None, chunk_rows,
+                                       want_spectra, int(runner._ss.chan_tot), int(runner.n_spec))
 
     def close(self):
         """Frees the ensemble on the device (the chain with it)."""
@@ -360,13 +443,21 @@ def default_thin(n_steps, n_walkers):
 
 
 def sample_pixels(runner, pix, n_walkers=64, n_steps=2000, n_burn=None, thin=None, a=2.0, seed=1, start=None, free_mask=None,
-                  levels=(0.16, 0.5, 0.84), keep_chain=False, log_zero=LOG_ZERO, n_init=2048):
+                  levels=(0.16, 0.5, 0.84), keep_chain=False, log_zero=LOG_ZERO, n_init=2048, par_bins=None, covariance=False,
+                  moments=False, utrans=None):
     """The posterior of the cube pixels `pix` of a `CubeRunner` (None: the pixel of a one-pixel runner) by `n_steps` steps of
     `n_walkers` walkers each on the device: an `EnsembleResult`.  n_burn None: half the steps; thin None: so that the kept
     samples of a pixel number 8192 at most, what the quantiles sort.  start: u0[P, n_walkers, ndim] in (0, 1), None:
     `starts(runner, pix, n_walkers, n_init, seed)`.  free_mask: the sampled unit-cube slots (None: all; `utrans.free_mask(ncomp)`
-    leaves out the slots of constant and duplicated parameters).  The argument checks are the engine's (`EngineError`)."""
+    leaves out the slots of constant and duplicated parameters).  par_bins: edges[ndim, n_bins + 1] of the marginal histograms
+    (an int with `utrans=`: `bin_edges(utrans, runner.ncomp, par_bins)`); covariance, moments: the parameter covariances and
+    the moments of the model spectra.  The three are reduced on the device before the result is handed back, so they outlive
+    `close()`.  The argument checks are the engine's (`EngineError`)."""
     n_steps = int(n_steps)
+    if par_bins is not None and np.ndim(par_bins) == 0:
+        if utrans is None:
+            raise ValueError('a number of bins needs utrans= for the edges')
+        par_bins = bin_edges(utrans, runner.ncomp, int(par_bins))
     n_burn = n_steps // 2 if n_burn is None else int(n_burn)
     thin = default_thin(n_steps, int(n_walkers)) if thin is None else int(thin)
     pix = None if pix is None else np.ascontiguousarray(pix, dtype=np.int32)
@@ -378,6 +469,13 @@ def sample_pixels(runner, pix, n_walkers=64, n_steps=2000, n_burn=None, thin=Non
         trace = ens.trace()
         mean, std, best, best_lnL, quant = ens.summary(levels)
         theta, lnL = ens.chain() if keep_chain else (None, None)
+        pdf, pdf_out, pdf_bins = None, None, None
+        if par_bins is not None:
+            edges = np.ascontiguousarray(par_bins, dtype=np.float64)
+            pdf, pdf_out = ens.histogram(edges)
+            pdf_bins = 0.5 * (edges[:, :-1] + edges[:, 1:])
+        cov = ens.covariance() if covariance else None
+        model = ens.moments() if moments else None
     except Exception:
         ens.close()
         raise
@@ -387,7 +485,8 @@ def sample_pixels(runner, pix, n_walkers=64, n_steps=2000, n_burn=None, thin=Non
         n_eff = int(n_walkers) * (n_steps - n_burn) / tau
     return EnsembleResult(mean=mean, std=std, best=best, best_lnL=best_lnL, quantiles=quant, levels=tuple(levels),
                           acceptance=accepted / proposed, outside=outside / proposed, n_evals=evaluated, tau=tau, n_eff=n_eff,
-                          trace=trace, theta=theta, lnL=lnL, pix=pix, n_steps=n_steps, n_burn=n_burn, thin=thin, _ensemble=ens)
+                          trace=trace, theta=theta, lnL=lnL, pix=pix, n_steps=n_steps, n_burn=n_burn, thin=thin, pdf_counts=pdf,
+                          pdf_outside=pdf_out, pdf_bins=pdf_bins, cov=cov, model=model, _ensemble=ens)
 
 
 MAP_FIELDS = ('mean', 'std', 'best', 'best_lnL', 'quantiles', 'acceptance', 'outside', 'n_evals', 'tau', 'n_eff')
@@ -399,12 +498,16 @@ def pixel_groups(n_pix, bytes_per_pixel, memory_budget):
     return [(a, min(n_pix, a + per)) for a in range(0, n_pix, per)]
 
 
-def sample_cube(stack, utrans, runner_cls, ncomp, runner_kwargs=None, memory_budget=2 << 30, **kw):
+def sample_cube(stack, utrans, runner_cls, ncomp, runner_kwargs=None, memory_budget=2 << 30, par_bins=None, covariance=False,
+                moments=False, **kw):
     """`sample_pixels` over every good pixel of a `CubeStack` with `ncomp` components: a namespace of maps (lat, lon) of
     every field of the result -- mean, std, best [ndim, lat, lon], best_lnL, acceptance, outside, n_evals [lat, lon],
     quantiles [ndim, n_levels, lat, lon], tau, n_eff [D, lat, lon] -- NaN where a pixel is not good (n_evals: -1).  The runner
-    is built as `CubeFitter` builds it; the pixels go in groups whose device bytes (nfa_ensemble_bytes: state, chain and
-    trace) fit `memory_budget`.  A pixel's run does not depend on its group: the cube pixel is in the random stream, and
+    With par_bins (edges[ndim, n_bins + 1], or an int: `bin_edges(utrans, ncomp, par_bins)`) pdf_counts [ndim, n_bins, lat, lon]
+    and pdf_outside [ndim, lat, lon] (int64, -1 where a pixel is not good) and pdf_bins [ndim, n_bins]; with covariance cov [ndim,
+    ndim, lat, lon]; with moments spec_mean, spec_std [chan_tot, lat, lon] and peak_mean, peak_std, total_mean, total_std
+    [n_spec, lat, lon].  The runner is built as `CubeFitter` builds it; the pixels go in groups whose device bytes
+    (nfa_ensemble_bytes: state, chain and trace; with moments nfa_ensemble_moments_bytes too) fit `memory_budget`.  A pixel's run does not depend on its group: the cube pixel is in the random stream, and
     the starts are drawn for all pixels before the cut.  kw: `sample_pixels`' keywords."""
     from .fitter import CubeFitter
     fitter = CubeFitter(stack, utrans, runner_cls, runner_kwargs=runner_kwargs)
@@ -421,10 +524,15 @@ def sample_cube(stack, utrans, runner_cls, ncomp, runner_kwargs=None, memory_bud
     if start is None:
         start = starts(runner, all_pix, W, kw.get('n_init', 2048), kw.get('seed', 1))
     per_pixel = _ffi.load().nfa_ensemble_bytes(1, W, ndim, D, n_steps, max(0, n_keep_of(n_steps, n_burn, thin)))
+    if moments:
+        per_pixel += _ffi.load().nfa_ensemble_moments_bytes(1, runner.n_chan_tot, runner.n_spec)
+    if par_bins is not None and np.ndim(par_bins) == 0:
+        par_bins = bin_edges(utrans, ncomp, int(par_bins))
     groups = pixel_groups(n_pix, per_pixel, memory_budget)
     parts = []
     for first, end in groups:
-        res = sample_pixels(runner, all_pix[first:end], start=start[first:end], **kw)
+        res = sample_pixels(runner, all_pix[first:end], start=start[first:end], par_bins=par_bins, covariance=covariance,
+                            moments=moments, **kw)
         res.close()
         parts.append(res)
     n_lon, n_lat = stack.spatial_shape
@@ -435,6 +543,21 @@ def sample_cube(stack, utrans, runner_cls, ncomp, runner_kwargs=None, memory_bud
             full = np.full((n_lat, n_lon), -1, dtype=np.int64)
         else:
             full = np.full(val.shape[1:] + (n_lat, n_lon), np.nan)
+        full[..., lat, lon] = np.moveaxis(val, 0, -1)
+        setattr(maps, name, full)
+    products = {}
+    if par_bins is not None:
+        products.update(pdf_counts=[part.pdf_counts for part in parts], pdf_outside=[part.pdf_outside for part in parts])
+        maps.pdf_bins = parts[0].pdf_bins if parts else None
+    if covariance:
+        products['cov'] = [part.cov for part in parts]
+    if moments:
+        for name, field in (('spec_mean', 'mean'), ('spec_std', 'std'), ('peak_mean',) * 2, ('peak_std',) * 2, ('total_mean',) * 2,
+                            ('total_std',) * 2):
+            products[name] = [getattr(part.model, field) for part in parts]
+    for name, vals in products.items():
+        val = np.concatenate(vals, axis=0)
+        full = np.full(val.shape[1:] + (n_lat, n_lon), -1 if val.dtype == np.int64 else np.nan, dtype=val.dtype)
         full[..., lat, lon] = np.moveaxis(val, 0, -1)
         setattr(maps, name, full)
     return maps

@@ -9,8 +9,12 @@
 3. `--cube`: evaluations per pixel on the 32 x 32 cube of config 5 (synth.c5_stack), two components, until n_eff >= 1000 in
    every sampled dimension: runs of doubling length, the share of pixels that got there and of pixels whose tau is not yet
    trustworthy (n_steps - n_burn < 50 tau), reported, not dropped.
+4. `--products`: the products of a chain by the device route against the host route of the same tree, P = 256,
+   W = 64, n_keep = 128, two spectra of 1024 channels, two components, both modes, the median of REPEATS: `moments` against
+   fetching the chain and `predict_moments`; `histogram` (64 bins over the priors' box) and `covariance` against fetching
+   the chain and the numpy twins.  Default --out: profiles/ensemble_products.txt.
 
-    python scripts/measure_ensemble.py [--out profiles/ensemble.txt] [--pixels 1024] [--trace | --cube]
+    python scripts/measure_ensemble.py [--out profiles/ensemble.txt] [--pixels 1024] [--trace | --cube | --products]
 """
 import argparse
 import ctypes as C
@@ -49,9 +53,63 @@ def cube(args, lines):
                   f'  acceptance {float(np.nanmedian(maps.acceptance)):.3f}, outside {float(np.nanmedian(maps.outside)):.3f}', '']
 
 
+def products(args, lines):
+    import nestfit_amd as na
+    from nestfit_amd import ensemble
+    from nestfit_amd.cube import CubeRunner
+    from nestfit_amd.synth import TRUTH_2COMP, freq_axis
+    P, W, n, n_keep, n_bins = 256, 64, args.chan, 128, 64
+    rng = np.random.default_rng(1)
+    axes = [freq_axis(1, n), freq_axis(2, n)]
+    ut = na.get_irdc_priors(size=500, vsys=0.0)
+    na.set_exp_mode('table')
+    probe = CubeRunner(axes, (1, 2), np.zeros((1, 2 * n)), np.full((1, 2), 0.2), ut, ncomp=2)
+    model, _ = probe.predict_batch(np.zeros(P, np.int32), np.repeat(TRUTH_2COMP[None], P, axis=0))
+    runner = CubeRunner(axes, (1, 2), model + rng.normal(0, 0.2, model.shape), np.full((P, 2), 0.2), ut, ncomp=2)
+    pix = np.arange(P, dtype=np.int32)
+    edges = ensemble.bin_edges(ut, 2, n_bins)
+    offsets = np.arange(P + 1, dtype=np.int64) * (n_keep * W)
+    u0 = ensemble.starts(runner, pix, W, n_init=256, seed=1)
+
+    def median_ms(call):
+        call()
+        times = []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            out = call()
+            times.append(time.perf_counter() - t0)
+        return statistics.median(times) * 1e3, out
+
+    for mode in ('table', 'fast'):
+        runner.set_exp_mode(mode)
+        ens = ensemble.DeviceEnsemble(runner, pix, W, u0, ut.free_mask(2))
+        ens.run(2 * n_keep, n_keep, 1, 2.0, 1)
+
+        def host_moments():
+            theta, _ = ens.chain()
+            return runner.predict_moments(pix, offsets, theta.reshape(-1, ens.ndim))
+
+        def host_histogram():
+            return ensemble.pdf_counts(ens.chain()[0], edges)
+
+        def host_covariance():
+            return ensemble.covariance_of(*ens.chain())
+        lines.append(f'mode {mode}: P = {P}, W = {W}, n_keep = {n_keep} ({n_keep * W} samples per pixel), 2 x {n} channels, ncomp 2, '
+                     f'chain {P * n_keep * W * (ens.ndim + 1) * 8 / 1e6:.0f} MB; median of {args.repeats}')
+        for what, dev_call, host_call in (('moments', ens.moments, host_moments), (f'histogram, {n_bins} bins', lambda: ens.histogram(edges), host_histogram),
+                                          ('covariance', ens.covariance, host_covariance)):
+            t_dev, dev = median_ms(dev_call)
+            t_host, host = median_ms(host_call)
+            if what != 'covariance':
+                assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(dev, host)), what
+            lines.append(f'  {what:22s} device {t_dev:10.2f} ms   chain to the host + host route {t_host:10.2f} ms')
+        lines.append('')
+        ens.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=str(ROOT / 'profiles' / 'ensemble.txt'))
+    ap.add_argument('--out', default='')
     ap.add_argument('--pixels', type=int, default=1024)
     ap.add_argument('--chan', type=int, default=1024)
     ap.add_argument('--side', type=int, default=32)
@@ -59,7 +117,9 @@ def main():
     ap.add_argument('--repeats', type=int, default=REPEATS)
     ap.add_argument('--trace', action='store_true', help='one run of 50 steps per mode and nothing else (for a kernel trace)')
     ap.add_argument('--cube', action='store_true', help='evaluations per pixel on the cube of config 5')
+    ap.add_argument('--products', action='store_true', help='histogram, covariance and moments: device route against host route')
     args = ap.parse_args()
+    args.out = args.out or str(ROOT / 'profiles' / ('ensemble_products.txt' if args.products else 'ensemble.txt'))
 
     import nestfit_amd as na
     from nestfit_amd import _ffi, ensemble
@@ -70,8 +130,8 @@ def main():
     name = C.create_string_buffer(256)
     _ffi.check(lib.nfa_device_name(name, 256))
     lines = [f'ensemble sampler, {name.value.decode()}', '']
-    if args.cube:
-        cube(args, lines)
+    if args.cube or args.products:
+        (cube if args.cube else products)(args, lines)
         text = '\n'.join(lines)
         print(text)
         Path(args.out).write_text(text + '\n')
