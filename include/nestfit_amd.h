@@ -920,6 +920,47 @@ int nfa_ensemble_moments(nfa_ensemble *e, int64_t chunk_rows /* as nfa_runner_pr
                          double *spec_mean, double *spec_std, double *stat_mean, double *stat_std);
 int64_t nfa_ensemble_moments_bytes(int64_t n_pix, int64_t chan_tot, int n_spec);
 
+/* ---- tempered ensembles: evidences and multimodal posteriors --------------------------
+ * A tempered ensemble is an nfa_ensemble with n_temps = T rungs per pixel, 2 <= T <= NFA_ENS_MAX_TEMPS, at the inverse
+ * temperatures betas[T]: betas[0] == 1, strictly decreasing, finite, betas[T - 1] >= 0 (else NFA_ERR_ARG); every (pixel, rung)
+ * has W walkers under the rules above; u0 is [n_pix][T][W][ndim].  Rung t moves by the move above against L^beta_t:
+ *     stream   ns_stream(seed, p, NFA_ENS_TAG + t 2^48 + 2 s + h)
+ *     accept   iff inside, lnL_y finite and log(r_2) < (D - 1) log(z) + beta_t (lnL_y - lnL_k), the product formed last in plain
+ *              f64; beta_0 = 1 multiplies exactly, so rung 0 of a run that never swaps has the bits of the untempered run with
+ *              the same arguments.  Outside proposals and a lnL_y that is not finite are rejected at every beta, 0 included.
+ * After the two half-steps of step s, if swap_every > 0 and s % swap_every == 0, with n the number of swap sweeps before in
+ * this run, the pairs (t, t + 1) with t % 2 == n % 2 exchange: walker k of rung t and walker k of rung t + 1 swap u, theta and
+ * lnL iff log(r) < (beta_t - beta_t+1)(lnL_t+1,k - lnL_t,k), r = ns_uniform_of(ns_stream(seed, p, NFA_ENS_TAG + 2^60 + t 2^48 +
+ * s), k).  With n_steps <= 2^40 and t < 32 every tag lies in [2^61, 2^62) and the move tags below the swap tags.  Swaps come
+ * before the trace and the keep of the step.
+ * Kept: the theta chain of rung 0 only, in the layout above, so nfa_ensemble_summary, _histogram, _covariance, _moments, _chain,
+ * _chain_dev, _counts, _state and _trace of a tempered ensemble describe the cold chain with the shapes of an untempered one;
+ * lnL of every rung, [n_pix][T][n_keep][W]; the trace of every rung, [n_pix][T][n_steps][D + 1]; counters of the last run per
+ * (pixel, rung) and per (pixel, pair (t, t + 1)): swaps accepted, swaps proposed (W per sweep the pair is active in).
+ * nfa_ensemble_rung_state returns u as [n_pix][T][W][ndim]: a u0.
+ * nfa_ensemble_evidence reduces the kept lnL on the device per (pixel, rung t, set j): set 0 is all n_keep kept steps, sets
+ * 1 .. n_blocks are contiguous blocks of floor(n_keep / n_blocks) kept steps, 1 <= n_blocks <= NFA_ENS_MAX_BLOCKS, n_blocks <=
+ * n_keep (else NFA_ERR_ARG).  With x_i the n values of the set: out[n_pix][T][n_blocks + 1][3] =
+ *     mean = x_first + S1 / n,  var = max(S2 / n - (S1 / n)^2, 0)        (S1, S2: sums of x_i - x_first and of its square)
+ *     r    = delta M + log(sum exp(delta (x_i - M)) / n),  delta = beta_t-1 - beta_t,  M = max x_i;  r = 0 for t = 0
+ * the sums in a fixed shape (strided per thread, a butterfly per wave, the waves in order): the same arguments give the same
+ * bits.  With betas[T - 1] == 0 the sum over t of r is ln Z, by the stepping-stone identity Z_beta_t-1 / Z_beta_t =
+ * E_beta_t[L^delta] and Z(0) = 1 in the unit cube.  NFA_ERR_STATE before a run; NFA_ERR_ARG on an untempered ensemble, as for
+ * every nfa_ensemble_rung_* call.  A failure leaves runner and ensemble usable. */
+#define NFA_ENS_MAX_TEMPS  32
+#define NFA_ENS_MAX_BLOCKS 16
+int nfa_ensemble_create_tempered(nfa_ensemble **out, nfa_runner *r, const int32_t *pix, int64_t n_pix, int n_walkers,
+                                 const double *betas /* [n_temps] */, int n_temps, int64_t swap_every /* 0: never */,
+                                 const int32_t *free_mask, const double *u0 /* [n_pix][n_temps][n_walkers][ndim] */);
+int nfa_ensemble_rung_counts(nfa_ensemble *e, int64_t *accepted, int64_t *outside, int64_t *evaluated /* [n_pix][T] each */,
+                             int64_t *swaps_accepted, int64_t *swaps_proposed /* [n_pix][T - 1] each */);
+int nfa_ensemble_rung_state(nfa_ensemble *e, double *u, double *theta, double *lnL);                   /* any may be NULL */
+int nfa_ensemble_rung_trace(nfa_ensemble *e, double *trace);
+int nfa_ensemble_rung_lnl(nfa_ensemble *e, double *lnL);
+int nfa_ensemble_evidence(nfa_ensemble *e, int n_blocks, double *out /* [n_pix][T][n_blocks + 1][3] */);
+int64_t nfa_ensemble_tempered_bytes(int64_t n_pix, int n_walkers, int n_temps, int ndim, int n_sampled, int64_t n_steps,
+                                    int64_t n_keep);
+
 /* ---- the exchange step of a sharded cube fit ---------------------
  * The reference stripes pixels over processes, (lon_ix[i::nproc], lat_ix[i::nproc])
  * (nestfit/main.py:565-571), and exchanges nothing while sampling; its processes meet through chunk

@@ -45,7 +45,7 @@ def out_array(out, shape, what):
 
 def _sample_posterior(runner, pix, **kw):
     """`ensemble.sample_pixels` of a runner's pixels (pix: None for the pixel of a one-pixel runner): the ensemble sampler's
-    arguments are checked once, by the engine."""
+    arguments are checked once, by the engine -- the ladder `betas=` of a tempered ensemble among them."""
     from .ensemble import sample_pixels
     return sample_pixels(runner, pix, **kw)
 

@@ -167,6 +167,14 @@ SIGNATURES = {
     'nfa_ensemble_covariance': (C.c_int, [C.c_void_p, _dp]),
     'nfa_ensemble_moments': (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
     'nfa_ensemble_moments_bytes': (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
+    'nfa_ensemble_create_tempered': (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, _ip, C.c_int64, C.c_int, _dp, C.c_int, C.c_int64,
+                                               _ip, _dp]),
+    'nfa_ensemble_rung_counts': (C.c_int, [C.c_void_p, _lp, _lp, _lp, _lp, _lp]),
+    'nfa_ensemble_rung_state': (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    'nfa_ensemble_rung_trace': (C.c_int, [C.c_void_p, _dp]),
+    'nfa_ensemble_rung_lnl': (C.c_int, [C.c_void_p, _dp]),
+    'nfa_ensemble_evidence': (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    'nfa_ensemble_tempered_bytes': (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
     'nfa_comm_unique_id':(C.c_int, [C.POINTER(C.c_ubyte)]),
     'nfa_comm_create': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.c_int, C.c_int]),
     'nfa_comm_destroy': (C.c_int, [C.c_void_p]),

@@ -23,10 +23,34 @@
 //     covariance  about the best row b of the summary: d_i,a = x_i,a - x_b,a, S_a = sum d_i,a, S_ab = sum d_i,a d_i,b,
 //                 cov_ab = S_ab / N - (S_a / N)(S_b / N) for a <= b, mirrored; the diagonal not below 0
 //     moments     nfa_runner_predict_moments over the chain where it lies: a segment per pixel, equal weights
+//
+// A tempered ensemble holds T = n_temps rungs per pixel, 2 <= T <= NFA_ENS_MAX_TEMPS, at inverse temperatures
+// 1 = beta_0 > beta_1 > .. > beta_T-1 >= 0, W walkers each.  A (pixel, rung) unit moves like a pixel above with two changes:
+//     stream   ns_stream(seed, p, NFA_ENS_TAG + t 2^48 + 2 s + h)
+//     accept   log(r_2) < (D - 1) log(z) + beta_t (lnL_y - lnL_k), the product formed last; beta_0 = 1 multiplies exactly, so
+//              rung 0 of a run that never swaps has the bits of the untempered run (which is T = 1, beta = 1)
+// Outside proposals and a lnL_y that is not finite are rejected at every beta, 0 included.  After the two half-steps of step
+// s, if swap_every > 0 and s % swap_every == 0, with n the number of swap sweeps before in this run: the pairs (t, t + 1) with
+// t % 2 == n % 2 exchange walker k for walker k (u, theta, lnL) iff
+//     log(r) < (beta_t - beta_t+1) (lnL_t+1,k - lnL_t,k),   r = ns_uniform_of(ns_stream(seed, p, NFA_ENS_SWAP_TAG + t 2^48 + s), k)
+// before the trace and the keep of the step.  Kept: the theta chain of rung 0 in the layout above (summary, histogram,
+// covariance, moments, chain, counts, state and trace describe the cold chain), lnL of every rung [P][T][n_keep][W], the trace
+// of every rung [P][T][n_steps][D + 1]; counters per (pixel, rung) and per (pixel, pair): swaps accepted, proposed.
+// The evidence reduction, per (pixel, rung t, set j) over the kept lnL x_i: set 0 is all n_keep kept steps, sets 1 .. B are
+// contiguous blocks of floor(n_keep / B) kept steps, 1 <= B <= NFA_ENS_MAX_BLOCKS, B <= n_keep.  With d_i = x_i - x_first:
+//     mean = x_first + S1 / n,  var = max(S2 / n - (S1 / n)^2, 0),
+//     r    = delta M + log(sum exp(delta (x_i - M)) / n),  delta = beta_t-1 - beta_t, M = max x_i     (t = 0: r = 0)
+// out[P][T][B + 1][3]; with beta_T-1 = 0 the sum over t of r is ln Z (stepping stones: Z_beta_t-1 / Z_beta_t = E_beta_t[L^delta]).
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+
+#ifdef __HIP__
+#define ENS_HD __host__ __device__          // what the kernels of nfa_ensemble.h call too
+#else
+#define ENS_HD
+#endif
 
 #define NFA_ENS_MAX_WALKERS 512          // include/nestfit_amd.h says the same for these three
 #define NFA_ENS_MAX_Q       8            // quantile levels of a summary
@@ -42,6 +66,16 @@
 #define ENS_RED_DOUBLES     64           // head of the summary's LDS: the partial results of up to 16 waves, three arrays
 #define ENS_SLAB_BYTES      (8 << 20)    // device scratch of a histogram or covariance call: the pixels go through it in slabs
 #define ENS_SAMPLES_MAX     (1ll << 32)  // kept samples per pixel a histogram counts: its LDS counters are 32 bits wide
+// A tempered ensemble.  Rung t moves on the tags NFA_ENS_TAG + t 2^48 + 2 s + h and swaps with rung t + 1 on NFA_ENS_SWAP_TAG
+// + t 2^48 + s.  With s <= ENS_STEPS_MAX = 2^40 and t < 32 = 2^5: 2 s + h <= 2^41 + 1 < 2^48, so the rungs' tags do not meet,
+// and t 2^48 + 2 s + h < 2^53 + 2^42; the largest move tag lies below 2^61 + 2^54 < 2^61 + 2^60, the smallest swap tag, and
+// the largest swap tag below 2^61 + 2^60 + 2^54 < 2^62: all inside [2^61, 2^62), moves and swaps apart.
+#define NFA_ENS_MAX_TEMPS   32           // include/nestfit_amd.h says the same for these two
+#define NFA_ENS_MAX_BLOCKS  16           // blocks of an evidence's batch means
+#define ENS_RUNG_SHIFT      48
+#define NFA_ENS_SWAP_TAG    (NFA_ENS_TAG + (1ull << 60))
+#define ENS_SWAP_THREADS_MAX 512         // = NFA_ENS_MAX_WALKERS: a thread per walker
+#define ENS_EVID_THREADS    256
 
 // ---- argument checks: null, or why the argument is refused
 inline const char *ens_check_walkers(int n_walkers, int n_sampled) {
@@ -84,6 +118,36 @@ inline const char *ens_check_edges(const double *edges, int ndim, int n_bins, in
     if (n_samples >= ENS_SAMPLES_MAX) return "ensemble: a histogram counts fewer than 2^32 kept samples per pixel";
     return nullptr;
 }
+// the ladder betas[n_temps] of a tempered ensemble
+inline const char *ens_check_betas(const double *betas, int n_temps) {
+    if (n_temps < 2 || n_temps > NFA_ENS_MAX_TEMPS) return "ensemble: a tempered ensemble takes 2 .. NFA_ENS_MAX_TEMPS = 32 rungs";
+    if (!betas) return "ensemble: rungs are counted but their betas are not given";
+    for (int t = 0; t < n_temps; ++t)
+        if (!(betas[t] - betas[t] == 0.0)) return "ensemble: a beta is not finite";
+    if (betas[0] != 1.0) return "ensemble: betas[0] must be 1: rung 0 is the cold chain";
+    for (int t = 1; t < n_temps; ++t)
+        if (!(betas[t] < betas[t - 1])) return "ensemble: the betas must decrease strictly";
+    if (betas[n_temps - 1] < 0.0) return "ensemble: the last beta must not be negative";
+    return nullptr;
+}
+inline const char *ens_check_swap_every(int64_t swap_every) {
+    return swap_every < 0 ? "ensemble: swap_every must be 0 (never) or a number of steps" : nullptr;
+}
+// the blocks of an evidence over n_keep kept steps
+inline const char *ens_check_blocks(int n_blocks, int64_t n_keep) {
+    if (n_blocks < 1 || n_blocks > NFA_ENS_MAX_BLOCKS) return "ensemble: an evidence takes 1 .. NFA_ENS_MAX_BLOCKS = 16 blocks";
+    if (n_blocks > n_keep) return "ensemble: an evidence takes no more blocks than kept steps";
+    return nullptr;
+}
+// ---- swaps: whether step s ends with a sweep; sweep n (from 0 in every run) exchanges the pairs (t, t + 1) with t % 2 == n % 2
+inline bool ens_swaps(int64_t step, int64_t swap_every) { return swap_every > 0 && step % swap_every == 0; }
+inline int ens_swap_parity(int64_t sweep) { return (int)(sweep & 1); }
+inline int ens_swap_pairs(int n_temps, int parity) { return (n_temps - parity) / 2; }      // t = parity, parity + 2, .. <= T - 2
+ENS_HD inline uint64_t ens_move_tag(int rung, int64_t step, int h) { return NFA_ENS_TAG + ((uint64_t)rung << ENS_RUNG_SHIFT) + 2ull * (uint64_t)step + (uint64_t)h; }
+ENS_HD inline uint64_t ens_swap_tag(int rung, int64_t step) { return NFA_ENS_SWAP_TAG + ((uint64_t)rung << ENS_RUNG_SHIFT) + (uint64_t)step; }
+// ---- evidence: the kept steps [first, first + count) of set j of n_blocks blocks (set 0: all of them)
+ENS_HD inline int64_t ens_set_steps(int64_t n_keep, int n_blocks, int j) { return j == 0 ? n_keep : n_keep / n_blocks; }
+ENS_HD inline int64_t ens_set_first(int64_t n_keep, int n_blocks, int j) { return j == 0 ? 0 : (int64_t)(j - 1) * (n_keep / n_blocks); }
 
 // ---- device bytes of an ensemble of P pixels: what create allocates (state: the walkers, a half-step's proposal rows,
 // the counters and the summary's outputs), and what a run of n_steps steps with n_keep kept adds (chain, trace)
@@ -97,6 +161,23 @@ inline EnsBytes ens_bytes(int64_t P, int W, int ndim, int D, int64_t n_steps, in
             + P * ((int64_t)ndim * 2 + (ndim + 1) + (int64_t)ndim * NFA_ENS_MAX_Q) * d + NFA_ENS_MAX_Q * d;    // summary, best, quant, levels
     B.chain = P * n_keep * W * (ndim + 1) * d;
     B.trace = P * n_steps * (D + 1) * d;
+    B.total = B.state + B.chain + B.trace;
+    return B;
+}
+// A tempered ensemble of P pixels and T rungs: the walkers, the half-step rows and the (pixel, rung) counters of P T units;
+// the summary's outputs of P pixels; the ladder, the swap counters of P (T - 1) pairs and the evidence's output at its
+// largest; the cold chain (theta and lnL of rung 0, the layout of an untempered chain) and lnL of every rung; the trace of
+// every rung.
+inline EnsBytes ens_tempered_bytes(int64_t P, int W, int T, int ndim, int D, int64_t n_steps, int64_t n_keep) {
+    const int64_t d = 8, i = 4, units = P * T, walkers = units * W, rows = units * (W / 2);
+    EnsBytes B;
+    B.state = walkers * (D + ndim + 1) * d + walkers * i
+            + rows * (ndim + D + 1) * d + rows * 2 * i
+            + units * 3 * d + units * i + (int64_t)D * i
+            + P * ((int64_t)ndim * 2 + (ndim + 1) + (int64_t)ndim * NFA_ENS_MAX_Q) * d + NFA_ENS_MAX_Q * d
+            + T * d + P * (T - 1) * 2 * d + units * (NFA_ENS_MAX_BLOCKS + 1) * 3 * d;      // betas, swap counters, evidence
+    B.chain = P * n_keep * W * (ndim + 1) * d + units * n_keep * W * d;
+    B.trace = units * n_steps * (D + 1) * d;
     B.total = B.state + B.chain + B.trace;
     return B;
 }
@@ -141,3 +222,11 @@ inline EnsGeom ens_hist_geom(int64_t P, int ndim, int64_t n_samples, int n_bins)
 }
 // covariance: a workgroup per pixel, the same threads; its LDS is static
 inline EnsGeom ens_cov_geom(int64_t P, int64_t n_samples) { return EnsGeom{(unsigned)P, ens_scan_threads(n_samples), 0}; }
+// A tempered ensemble's propose, accept, trace and keep take its P T units where the functions above take P pixels.
+// swap: a workgroup per (pixel, active pair of the sweep), a thread per walker (whole waves: 64 .. 512 threads); grid 0 where
+// the sweep has no pair (T = 2, an odd sweep): nothing is launched
+inline EnsGeom ens_swap_geom(int64_t P, int W, int n_temps, int parity) {
+    return EnsGeom{(unsigned)(P * ens_swap_pairs(n_temps, parity)), (unsigned)((W + 63) / 64 * 64), 0};
+}
+// evidence: a workgroup per (pixel, rung); its LDS is static
+inline EnsGeom ens_evidence_geom(int64_t P, int n_temps) { return EnsGeom{(unsigned)(P * n_temps), (unsigned)ENS_EVID_THREADS, 0}; }

@@ -13,8 +13,14 @@
    W = 64, n_keep = 128, two spectra of 1024 channels, two components, both modes, the median of REPEATS: `moments` against
    fetching the chain and `predict_moments`; `histogram` (64 bins over the priors' box) and `covariance` against fetching
    the chain and the numpy twins.  Default --out: profiles/ensemble_products.txt.
+5. `--tempered`: tempered ensembles, P = 64, W = 64, T = 16 (`ladder(16)`), two spectra of 1024 channels, two
+   components, both modes: the wall time per step against the untempered step of P T = 1024 pixels of the same runner -- the
+   same number of rows a half-step -- as in 1; `nfa_ensemble_evidence` against fetching the rung lnL and `ensemble.evidence_of`,
+   as in 4.  With `--trace` one tempered run of 50 steps per mode and nothing else (for the swap kernel's share in a kernel
+   trace); with `--cube` the config-5 cube, two components: lnZ_err per pixel after runs of `--steps` steps, next to the
+   evaluations per pixel they took, all rungs counted.  Default --out: profiles/ensemble_tempered.txt.
 
-    python scripts/measure_ensemble.py [--out profiles/ensemble.txt] [--pixels 1024] [--trace | --cube | --products]
+    python scripts/measure_ensemble.py [--out profiles/ensemble.txt] [--pixels 1024] [--trace | --cube | --products | --tempered]
 """
 import argparse
 import ctypes as C
@@ -107,6 +113,87 @@ def products(args, lines):
         ens.close()
 
 
+def tempered_cube(args, lines):
+    import nestfit_amd as na
+    from nestfit_amd import ensemble
+    from nestfit_amd.synth import c5_stack
+    stack, _, _, _, _, ut = c5_stack(side=args.side, n=args.chan)
+    na.set_exp_mode('table')
+    betas, W = ensemble.ladder(16), 64
+    for n_steps in args.steps:
+        t0 = time.perf_counter()
+        maps = ensemble.sample_cube(stack, ut, na.AmmoniaRunner, 2, n_walkers=W, n_steps=n_steps, free_mask=ut.free_mask(2), levels=(),
+                                    betas=betas)
+        dt = time.perf_counter() - t0
+        err = maps.lnZ_err[np.isfinite(maps.lnZ_err)]
+        evals = betas.size * (n_steps * W + W) + 2048          # every rung's steps and start rows, and the start draws
+        lines += [f'sample_cube, table mode, ladder(16): {args.side} x {args.side} pixels, 2 x {args.chan} channels, ncomp 2, W = {W}, {n_steps} steps, half burned',
+                  f'  whole call {dt:8.2f} s; evaluations per pixel {evals} (nested run, DESIGN 6: 1.10 M, lnZ_err 0.25)',
+                  f'  lnZ_err (8 blocks): median {float(np.median(err)):.3f}, largest {float(err.max()):.3f}; pixels below 0.25: {float(np.mean(err < 0.25)):.3f}',
+                  f'  smallest swap rate {float(np.nanmin(maps.swap_rate)):.3f}, median {float(np.nanmedian(maps.swap_rate)):.3f}; cold acceptance {float(np.nanmedian(maps.acceptance)):.3f}', '']
+
+
+def tempered(args, lines):
+    import nestfit_amd as na
+    from nestfit_amd import ensemble
+    from nestfit_amd.cube import CubeRunner
+    from nestfit_amd.synth import TRUTH_2COMP, freq_axis
+    P, W, T, n = 64, 64, 16, args.chan
+    betas = ensemble.ladder(T)
+    rng = np.random.default_rng(1)
+    axes = [freq_axis(1, n), freq_axis(2, n)]
+    ut = na.get_irdc_priors(size=500, vsys=0.0)
+    na.set_exp_mode('table')
+    probe = CubeRunner(axes, (1, 2), np.zeros((1, 2 * n)), np.full((1, 2), 0.2), ut, ncomp=2)
+    model, _ = probe.predict_batch(np.zeros(P * T, np.int32), np.repeat(TRUTH_2COMP[None], P * T, axis=0))
+    runner = CubeRunner(axes, (1, 2), model + rng.normal(0, 0.2, model.shape), np.full((P * T, 2), 0.2), ut, ncomp=2)
+    pix = np.arange(P * T, dtype=np.int32)
+    mask = ut.free_mask(2)
+    u0 = ensemble.starts(runner, pix, W, n_init=256, seed=1)
+
+    def per_step(ens):
+        ens.run(20, 0, 1, 2.0, 1)                                  # warm-up
+        times = []
+        for k in range(args.repeats):
+            t0 = time.perf_counter()
+            ens.run(200, 100, 1, 2.0, 2 + k)
+            times.append(time.perf_counter() - t0)
+        return statistics.median(times) / 200, min(times) / 200, max(times) / 200
+
+    for mode in ('table', 'fast'):
+        runner.set_exp_mode(mode)
+        hot = ensemble.DeviceEnsemble(runner, pix[:P], W, u0[:P], mask, betas=betas, swap_every=1)
+        if args.trace:
+            hot.run(50, 0, 1, 2.0, 1)
+            hot.close()
+            continue
+        t_hot = per_step(hot)
+        cold = ensemble.DeviceEnsemble(runner, pix, W, u0, mask)
+        t_cold = per_step(cold)
+        cold.close()
+        lines += [f'mode {mode}: P = {P}, W = {W}, T = {T}, 2 x {n} channels, ncomp 2 (D = {hot.D} of {hot.ndim}); {P * T * W // 2} rows per half-step; '
+                  f'runs of 200 steps, median of {args.repeats}',
+                  f'  tempered, a swap sweep every step      {t_hot[0] * 1e6:10.1f} us per step  ({t_hot[1] * 1e6:.1f} .. {t_hot[2] * 1e6:.1f})',
+                  f'  untempered, {P * T} pixels              {t_cold[0] * 1e6:10.1f} us per step  ({t_cold[1] * 1e6:.1f} .. {t_cold[2] * 1e6:.1f})']
+        hot.run(256, 128, 1, 2.0, 99)                              # 128 kept steps x 64 walkers = 8192 values per (pixel, rung)
+        hot.evidence(8)
+        t_dev, t_host = [], []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            dev = hot.evidence(8)
+            t_dev.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            host = ensemble.evidence_of(hot.rung_lnL(), betas, 8)
+            t_host.append(time.perf_counter() - t0)
+        assert np.allclose(dev.lnZ, host.lnZ, rtol=0, atol=1e-9)
+        lines += [f'  evidence of {P} x {T} x 8192 kept lnL, 8 blocks:',
+                  f'    nfa_ensemble_evidence               {statistics.median(t_dev) * 1e3:10.2f} ms',
+                  f'    rung lnL to the host + evidence_of  {statistics.median(t_host) * 1e3:10.2f} ms  (the rung lnL is {P * T * 8192 * 8 / 1e6:.0f} MB)',
+                  f'  lnZ_err of the {P} pixels: median {float(np.median(dev.lnZ_err)):.3f}; smallest swap rate '
+                  f'{float((hot.rung_counts()[3] / hot.rung_counts()[4]).min()):.3f}', '']
+        hot.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
@@ -118,8 +205,10 @@ def main():
     ap.add_argument('--trace', action='store_true', help='one run of 50 steps per mode and nothing else (for a kernel trace)')
     ap.add_argument('--cube', action='store_true', help='evaluations per pixel on the cube of config 5')
     ap.add_argument('--products', action='store_true', help='histogram, covariance and moments: device route against host route')
+    ap.add_argument('--tempered', action='store_true', help='tempered ensembles: step time, evidence call; with --cube the evidences of config 5')
     args = ap.parse_args()
-    args.out = args.out or str(ROOT / 'profiles' / ('ensemble_products.txt' if args.products else 'ensemble.txt'))
+    args.out = args.out or str(ROOT / 'profiles' / ('ensemble_tempered.txt' if args.tempered else 'ensemble_products.txt' if args.products
+                                                    else 'ensemble.txt'))
 
     import nestfit_amd as na
     from nestfit_amd import _ffi, ensemble
@@ -130,8 +219,15 @@ def main():
     name = C.create_string_buffer(256)
     _ffi.check(lib.nfa_device_name(name, 256))
     lines = [f'ensemble sampler, {name.value.decode()}', '']
-    if args.cube or args.products:
-        (cube if args.cube else products)(args, lines)
+    if args.cube or args.products or args.tempered:
+        if args.tempered:
+            tempered(args, lines)
+            if args.trace:
+                return 0
+            if args.cube:
+                tempered_cube(args, lines)
+        else:
+            (cube if args.cube else products)(args, lines)
         text = '\n'.join(lines)
         print(text)
         Path(args.out).write_text(text + '\n')
